@@ -9,15 +9,18 @@ by the ONE gather of per-rank tile-major accumulator blocks to rank 0 and the
 root's un-tile.  A batch is 32 samples — the reference's default `sync_rate` (src/trace.rs:75), the number of
 samples its GPU loop renders between two read-backs; default 8 steps x 32 spp = the full 256 spp of the config.
 
-  python bench.py --gpus 1 --steps 8 --warmup 3
+  python bench.py --gpus 1 --steps 8 --warmup 3 [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line.  `value` = (extension + shadow rays traced by all
 ranks in the K timed steps) / max-over-ranks wall time, scene and state already
 resident in HBM.  Extra objects: `roofline` (dominant kernel, HIP-event timed in
-the same run) and `cpu_baseline` (the CPU oracle — a port of the reference's
-trace_cpu, test infrastructure — timed on this host's cores on a bounded sample).
+the same run).  A plain run does only set-up, warm-up, the timed steps and the line;
+`--full` adds `cpu_baseline` (the CPU oracle — a port of the reference's trace_cpu,
+test infrastructure — timed on this host's cores on a bounded sample), `parity_check`,
+`readback` and, at N = 1, the other single-GPU workloads under `workloads`.
+`--dump-outputs DIR` writes the accumulators the last timed step left (dump_outputs).
 """
 import argparse
 import importlib
@@ -268,6 +271,24 @@ def parity_windows(world, cfg, seeds, image, image_spp, want_spp, W, H, budget_s
 
 def parity_ok(parity):
     return parity is None or (parity["bitwise"] and parity["rel_l2"] <= 1e-4)
+
+
+DUMP_BYTES_MAX = 60 << 20       # a dump stays under 64 MB, headers and row indices included
+
+
+def dump_outputs(path, image):
+    """--dump-outputs: what a caller of the timed path receives after its last step — the accumulators (rpt_read_accum / rpt_read_gathered:
+    H x W x 4 float32, RGB sums and the sample count) — as DIR/accum.npy.  Seeds and scene are fixed, so the same arguments give the same inputs
+    on every run.  An image over DUMP_BYTES_MAX is written as a fixed, seeded sample of its rows, their indices in DIR/accum_rows.npy (float64)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    image = np.ascontiguousarray(image, np.float32)
+    if image.nbytes > DUMP_BYTES_MAX:
+        n_rows = DUMP_BYTES_MAX // image[0].nbytes
+        rows = np.sort(np.random.default_rng(0).choice(image.shape[0], n_rows, replace=False))
+        np.save(os.path.join(path, "accum_rows.npy"), rows.astype(np.float64))
+        image = image[rows]
+    np.save(os.path.join(path, "accum.npy"), image)
 
 
 def workload_label(scene, W, H, steps, spp_per_step, total_spp, cfg):
@@ -559,9 +580,12 @@ def run_multi_driver(args):
     share = r0.local_pixels() / float(W * H)
     roofline, whole = stage_roofline(hip, args.workload, k0, k1, args.steps, elapsed, cus, clock_mhz, pipeline_bytes * share, share * args.spp_per_step / 32.0)
     parity = None
-    if not args.no_parity_check:
+    if not args.no_parity_check or args.dump_outputs:
         image, image_spp = m.read_accum()
-        parity = parity_windows(world, cfg, seeds, image, image_spp, args.spp_per_step * (args.warmup + args.steps), W, H)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, image)
+        if not args.no_parity_check:
+            parity = parity_windows(world, cfg, seeds, image, image_spp, args.spp_per_step * (args.warmup + args.steps), W, H)
     order, last_order = shadow_order_label(r0), last_bounce_label(r0)
     out = {}
     if args.rehearsal:
@@ -635,7 +659,15 @@ def main():
     ap.add_argument("--extra-steps", type=int, default=4)
     ap.add_argument("--extra-warmup", type=int, default=1)
     ap.add_argument("--no-readback", action="store_true", help="skip the extra render -> read_accum loop (reference loop shape, src/trace.rs:182-204)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the CPU baseline, the parity check against the CPU oracle, the "
+                         "read-back loops and (N = 1) the extra workloads; the --no-* options above still leave a part of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the accumulators of the last one to DIR/accum.npy (float32; see dump_outputs)")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run does only what its headline needs: set-up, warm-up, the timed steps, --dump-outputs and the line
+        args.no_cpu_baseline = args.no_parity_check = args.no_readback = args.no_extra_workloads = True
 
     if args.spp_per_step is None:
         args.spp_per_step = min(256, 32 * max(1, args.gpus))
@@ -812,11 +844,13 @@ def main():
     def delta(key):
         return s1[key] - s0[key]
 
-    # (untimed) the image the timed loop produced — every batch since the reset above, warm-up included — for the parity check
+    # (untimed) the image the timed loop produced — every batch since the reset above, warm-up included — for the parity check and --dump-outputs
     bench_image, bench_image_spp = None, 0
-    if rank == 0 and not args.no_parity_check and (gatherer is None):
+    if rank == 0 and (not args.no_parity_check or args.dump_outputs) and (gatherer is None):
         bench_image, bench_image_spp = r.read_gathered() if use_lib_gather else r.read_accum()
         bench_image = bench_image.copy()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, bench_image if gatherer is None else image.cpu().numpy())
 
     # The reference's own loop shape (src/trace.rs:182-204): render sync_rate samples, read the accumulators back to
     # the host, repeat.  Timed separately — it is not `value` (inputs and outputs of `value` stay in HBM) — so that the
@@ -916,7 +950,7 @@ def main():
     # count; a mismatch fails the bench.
     order, last_order = shadow_order_label(r), last_bounce_label(r)
     parity = None
-    if bench_image is not None:
+    if bench_image is not None and not args.no_parity_check:
         parity = parity_windows(world, cfg, seeds, bench_image, bench_image_spp, args.spp_per_step * (args.warmup + args.steps), W, H)
 
     # --- the other single-GPU BASELINE workloads (C2 with MIS, C3, C4 as one GPU sees it, the C5 stand-in): after the headline, never

@@ -14,6 +14,9 @@ def test_plain_multi_gpu_command_starts_its_own_ranks_and_relays_their_exit_code
     env["RANK"] = "0"
     env["HIP_VISIBLE_DEVICES"] = ""                      # (were a GPU present: this test is about the launcher only)
     env["CUDA_VISIBLE_DEVICES"] = ""
+    # torch.distributed.run stops every rank as soon as it sees one fail (it looks every 0.1 s by default): a rank still importing torch
+    # would be killed before it reports.  Its first look comes after PET_MONITOR_INTERVAL seconds, by when both ranks have failed on their own.
+    env["PET_MONITOR_INTERVAL"] = "20"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
     assert "starting -m torch.distributed.run --nnodes=1 --nproc-per-node=2" in p.stderr, p.stderr[-2000:]

@@ -126,7 +126,7 @@ def test_bench_dress_rehearsal_of_the_scaling_run(tmp_path, ranks, launcher):
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
-    bench_args = [os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--rehearsal"]
+    bench_args = [os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--rehearsal", "--full"]
     if launcher == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}", "--master-addr", "127.0.0.1",
                "--master-port", str(port)] + bench_args
@@ -176,7 +176,7 @@ def test_a_failing_rank_run_falls_back_to_the_one_process_driver(tmp_path):
     env = _env()
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--rehearsal", "--rehearsal-fail-ranks"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--rehearsal", "--rehearsal-fail-ranks", "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     assert p.returncode == 0, p.stderr[-3000:]
     assert "failing on purpose" in p.stderr and "second attempt with ONE process driving all 2 GPUs" in p.stderr
@@ -194,7 +194,7 @@ def test_bench_line_carries_the_other_single_gpu_workloads(tmp_path):
     extra workloads and short loops here; the driver's run takes all four.)"""
     env = dict(os.environ)
     env.pop("RPT_RCCL_LIBRARY", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-readback",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-readback",
            "--extra-workloads", "darkcornell_mis,veachmis", "--extra-steps", "1", "--extra-warmup", "0"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     assert p.returncode == 0, p.stderr[-3000:]
@@ -224,3 +224,28 @@ def test_bench_line_carries_the_other_single_gpu_workloads(tmp_path):
                 assert r["traffic_kernels"] in (["k_shadow", "k_shadow_resolve"], ["k_shadow"])
         pc = w["parity_check"]
         assert pc["bitwise"] is True and pc["windows"] >= 2 and pc["image_spp"] == pc["spp"] == 32
+
+
+def test_plain_bench_line_and_its_dumped_outputs(tmp_path, rpt, world, oracle):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full runs set-up, warm-up, the K timed steps and the line — no CPU baseline, parity
+    check, read-back loops or extra workloads — and --dump-outputs writes the accumulators the last timed step left: every pixel carries the
+    samples of all W + K batches since the reset, and a window of them equals the CPU oracle's bit for bit."""
+    env = dict(os.environ)
+    env.pop("RPT_RCCL_LIBRARY", None)
+    dump = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(dump)]
+    p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["metric"] == "Mrays/s" and out["value"] > 0 and out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    assert out["cpu_baseline"] is None and out["parity_check"] is None and out["readback"] is None and "workloads" not in out
+    assert sorted(os.listdir(dump)) == ["accum.npy"]
+    acc = np.load(dump / "accum.npy")
+    spp = 32 * (1 + 3)
+    assert acc.dtype == np.float32 and acc.shape == (1024, 1024, 4) and (acc[..., 3] == spp).all()
+    x0, y0, n = 496, 560, 24
+    cfg = rpt.default_config(1024, 1024)
+    ref, _, _ = oracle.trace_cpu(cfg, oracle.scene(world("DarkCornell")), rpt.blue_noise_seeds(1024, 1024), spp, rect=(x0, y0, x0 + n, y0 + n))
+    assert np.array_equal(acc[y0:y0 + n, x0:x0 + n].view(np.uint32), ref[y0:y0 + n, x0:x0 + n].view(np.uint32))
