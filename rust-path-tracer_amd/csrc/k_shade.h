@@ -557,9 +557,7 @@ __device__ __forceinline__ void shade_slot(const DevScene &sc, const DevState &s
  * four workgroup barriers for side queues nothing is pushed to), 40 % of the lanes live in what was issued — the fixed
  * cost per wave, not the shading, was the stage.  Packed, a workgroup does the bookkeeping once per 2 048 slots with
  * eight independent loads in flight per thread, and only full waves shade.  (Generations are completed by k_complete.) */
-#ifndef RPT_SHADE_ROUNDS
-#define RPT_SHADE_ROUNDS 8
-#endif
+constexpr int RPT_SHADE_ROUNDS = 8;
 __device__ __forceinline__ uint32_t block_rank(bool pred, uint32_t *scratch, uint32_t &total) {
     const uint32_t lane = __lane_id(), wave = threadIdx.x / RPT_WAVE;
     constexpr uint32_t NW = RPT_BLOCK / RPT_WAVE;
@@ -621,16 +619,12 @@ __device__ __forceinline__ void count_elided(uint32_t *lds_counter, bool elided)
     if (m != 0ull && __lane_id() == (uint32_t)__ffsll((long long)m) - 1u) atomicAdd(lds_counter, (uint32_t)__popcll(m));
 }
 
-template <int NEE, bool TEXTURED, bool COMPACT>
 /* Occupancy asked of the compiler where it costs no spill (left alone it stops at 68 and 104 VGPRs): the plain nee = 0
  * variant runs at 8 waves per SIMD in 64 VGPRs (DarkCornell shade 31.7 -> 31.0 ms per 8 batches), its packed form at 5 in 96
  * (PBRTest 69.3 -> 67.4 per 4).  The NEE variants spill when pushed (72 VGPRs: 20-44 bytes of scratch; packed: VeachMIS shade 44.0 -> 48.6) and are left alone. */
-#ifndef RPT_SHADE_WAVES_PLAIN
-#define RPT_SHADE_WAVES_PLAIN 8
-#endif
-#ifndef RPT_SHADE_WAVES_PACKED
-#define RPT_SHADE_WAVES_PACKED 5
-#endif
+constexpr int RPT_SHADE_WAVES_PLAIN = 8;
+constexpr int RPT_SHADE_WAVES_PACKED = 5;
+template <int NEE, bool TEXTURED, bool COMPACT>
 __attribute__((amdgpu_waves_per_eu((NEE == RPT_NEE_NONE && !TEXTURED) ? (COMPACT ? RPT_SHADE_WAVES_PACKED : RPT_SHADE_WAVES_PLAIN) : 1, 8)))
 __global__ __launch_bounds__(RPT_BLOCK) void k_shade(DevScene sc, DevState st, DevQueues q, DevConfig cfg, uint32_t iteration,
                                                      DevStats *stats, uint32_t n_samples /* of this render call */) {

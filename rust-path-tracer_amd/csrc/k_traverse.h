@@ -121,12 +121,10 @@ __device__ __forceinline__ bool slab_test(float4 lo, float4 hi, F3 ro, F3 rd, F3
 /* How the generic loop reads the scene: the uploaded node array as is (children adjacent, one visit = 64
  * contiguous bytes = half a cache line through L1/L2) and the (a, e1, e2) triangle records.  A finished lane
  * carries count = 0x80000000 so that "at an inner node" / "at a leaf" are single compares on the register (a
- * ballot of a compare is the compare itself; a ballot of a loop-carried bool costs two more VALU instructions). */
-template <bool COOP>
-struct SceneViewGlobalT {
-    static constexpr bool kCoopLeaves = COOP;               /* leaves may hold dozens of triangles: see walk_run.  The streamed walks are
-                                                               built both ways and the host picks by the scene's largest leaf: the cooperative
-                                                               leaf code costs registers the walk of a thin-leaf scene (every shipped one) needs */
+ * ballot of a compare is the compare itself; a ballot of a loop-carried bool costs two more VALU instructions).
+ * Only the one-ray-per-lane walks (a foreign builder's node pool, the test hook) read the scene this way. */
+struct SceneViewGlobal {
+    static constexpr bool kCoopLeaves = true;               /* leaves may hold dozens of triangles: see walk_run */
     static constexpr bool kUniformScalar = false;
     const float4 *nodes;
     const float *tri_isect;
@@ -157,7 +155,6 @@ struct SceneViewGlobalT {
         return f3(p[0], p[1], p[2]);
     }
 };
-typedef SceneViewGlobalT<true> SceneViewGlobal;
 
 /* The streamed global-memory walks read a PAIR array instead (round 4).  Counters first (profiles/r04_*_pmc_ta.txt): these walks keep the CU's
  * texture-address unit busy 83-92 % of the time (TA_TA_BUSY / TCP_GATE_EN1: VeachMIS shadow 92 %, PBRTest nearest 91 %; the LDS walk 12 %) — that
@@ -171,12 +168,11 @@ typedef SceneViewGlobalT<true> SceneViewGlobal;
  * `links[]` instead of two.  Pair p = the children (2p + 1, 2p + 2) of the reference's node pool (its builder allocates children in pairs after the
  * root); a scene whose pool is not pair-shaped, or with a leaf of 255+ triangles or 2^24+ triangles, keeps the one-shot generic walks.  The node
  * is one register: an inner node is its left child's index (< 2^24). */
-#ifndef RPT_GSTREAM_UNIFORM_SCALAR
-#define RPT_GSTREAM_UNIFORM_SCALAR 1
-#endif
 template <bool COOP>
 struct SceneViewPairsT {
-    static constexpr bool kCoopLeaves = COOP;
+    static constexpr bool kCoopLeaves = COOP;                  /* leaves may hold dozens of triangles: see walk_run.  The streamed walks are
+                                                                  built both ways and the host picks by the scene's largest leaf: the cooperative
+                                                                  leaf code costs registers the walk of a thin-leaf scene (every shipped one) needs */
     const float4 *pairs;          /* 64 bytes per pair: 3 x float4 of boxes, 8 bytes unused, (link L, link R) in the LAST 8 bytes — at offset 48, 16-byte aligned,
                                      the compiler widens the 8-byte load to a 16-byte one; in an array of their own the links cost large scenes a second line */
     const uint32_t *links;        /* per NODE: what a popped stack entry (a node index) resolves to */
@@ -204,8 +200,8 @@ struct SceneViewPairsT {
      * 2048^2 and VeachMIS 1080p (tools/uniform_visit_share.py, profiles/r04_uniform_visit_share.txt).  The wait is inside the asm statement: the
      * compiler's s_waitcnt insertion does not see a load it did not emit.  Destinations are early-clobber ("=&s"): an SMEM destination that overlapped
      * its own base pair would be re-read clobbered if the load were ever replayed (XNACK) — LLVM does the same for its own scalar loads on xnack-any
-     * targets; tests/test_scalar_path_isa.py checks the emitted registers. */
-    static constexpr bool kUniformScalar = RPT_GSTREAM_UNIFORM_SCALAR != 0;
+     * targets. */
+    static constexpr bool kUniformScalar = true;
     __device__ __forceinline__ void children_uniform(uint32_t c, float4 &lmin, float4 &lmax, float4 &rmin, float4 &rmax) const {
         typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
         const float4 *p = pairs + 4u * (c >> 1);
@@ -244,18 +240,6 @@ struct SceneViewPairsT {
         return f3(p[0], p[1], p[2]);
     }
 };
-#ifndef RPT_GSTREAM_PAIRS
-#define RPT_GSTREAM_PAIRS 1
-#endif
-#if RPT_GSTREAM_PAIRS
-#define RPT_GSTREAM_VIEW(COOP, sc) SceneViewPairsT<COOP>{(sc).gpairs, (sc).glinks, (sc).tri_isect}
-#define RPT_GSTREAM_VIEW_SHADOW(COOP, sc) SceneViewPairsT<COOP>{(sc).gpairs_shadow, (sc).glinks_shadow, (sc).tri_isect}
-template <bool COOP> struct GstreamView { typedef SceneViewPairsT<COOP> type; };
-#else
-#define RPT_GSTREAM_VIEW(COOP, sc) SceneViewGlobalT<COOP>{(sc).nodes, (sc).tri_isect}
-#define RPT_GSTREAM_VIEW_SHADOW(COOP, sc) SceneViewGlobalT<COOP>{(sc).nodes, (sc).tri_isect}
-template <bool COOP> struct GstreamView { typedef SceneViewGlobalT<COOP> type; };
-#endif
 
 /* The LDS-resident image of a small scene, built once at upload (rpt_hip.hip, build_lds_image) and copied into
  * LDS by every workgroup.  Measured on MI355X (tools/microbench/valu_rates.hip, SQ counters in profiles/): the
@@ -335,25 +319,17 @@ __device__ __forceinline__ bool moller_trumbore_regs(F3 edge1, F3 edge2, F3 corn
 
 /* One ray per lane through the BVH.  Per lane the sequence of box tests, triangle tests and the value of the
  * running best t at each of them is exactly the reference's (intersection.rs:177-234); what is scheduled is
- * WHEN a lane takes its next step.  Each trip of the loop, lanes standing on an inner node take one box step;
- * lanes standing on a leaf WAIT until at least RPT_LEAF_K lanes of the wave are waiting (or nobody is left at
- * an inner node), then the wave issues the triangle body once for all of them.
+ * WHEN a lane takes its next step.  Each trip of the loop the wave issues ONE body, the one with more lanes ready
+ * for it: the box step for the lanes standing on an inner node, or the triangle body for the lanes standing on a leaf
+ * (a tie goes to the box step).
  * Why: after the first bounce the rays of a wave are incoherent.  A replay of the reference traversal on real
  * DarkCornell bounce rays (tools/traversal_sim.py) gives, in issue slots per ray: classic while-while 148
  * (lanes at a leaf wait for the slowest lane of every round), one-step-per-trip "if-if" 113 (the leaf body,
- * 14 % of the steps, is issued on almost every trip), deferred leaves with K = 12..16: 106; ideal 38.  Measured on MI355X the gain is smaller (LDS/latency share the
- * bill with VALU issue): traverse 23.7 -> 22.4..22.8 ms for K = 8..16, 25.9 ms for K = 64 (= while-while); K = 8 is
- * also the best for VeachMIS.
+ * 14 % of the steps, is issued on almost every trip), deferred leaves (wait for K lanes at a leaf) with K = 12..16: 106; ideal 38.
+ * Measured on MI355X the gain is smaller (LDS/latency share the bill with VALU issue): traverse 23.7 -> 22.4..22.8 ms for
+ * K = 8..16, 25.9 ms for K = 64 (= while-while).  The one-body rule then beat the K = 8 threshold on the global-memory walks
+ * (K = 8 / one body / a leaf counting 60 % of an inner step: VeachMIS 5175 / 5506 / 5453 Mrays/s, PBRTest 4915 / 5027 / 5011).
  * `stack` points at this lane's column of the wave's LDS stack: entry e lives at stack[e * RPT_WAVE]. */
-#ifndef RPT_LEAF_K
-#define RPT_LEAF_K 8
-#endif
-#ifndef RPT_LEAF_GREEDY_PCT_GLOBAL
-#define RPT_LEAF_GREEDY_PCT_GLOBAL 100   /* global-memory walks: 0 = the RPT_LEAF_K threshold rule; > 0 = one body per trip (see lds_walk_run).
-                                            Measured (K = 8 rule / 100 / 60): VeachMIS 5175 / 5506 / 5453 Mrays/s, PBRTest 4915 / 5027 / 5011 */
-#endif
-#ifndef RPT_COOP_LEAF_MIN
-#endif
 __device__ __forceinline__ float rpt_readlane(float v, int lane) { return __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(v), lane)); }
 __device__ __forceinline__ uint32_t rpt_readlane_u(uint32_t v, int lane) { return (uint32_t)__builtin_amdgcn_readlane((int)v, lane); }
 
@@ -401,11 +377,9 @@ __device__ __forceinline__ void walk_run(const View &view, Walk<View> &w, F3 ro,
         const bool at_leaf = View::is_leaf(cur);
         const unsigned long long inner_m = rpt_ballot(at_inner), leaf_m = rpt_ballot(at_leaf);
         if ((inner_m | leaf_m) == 0ull) break;
-#if RPT_LEAF_GREEDY_PCT_GLOBAL
-        if (at_inner && !((uint32_t)__popcll(leaf_m) * 100u > (uint32_t)__popcll(inner_m) * (uint32_t)RPT_LEAF_GREEDY_PCT_GLOBAL)) {
-#else
-        if (at_inner) {
-#endif
+        /* one body per trip (see above); the rule is written out ahead of each body: evaluated once ahead of both, the same
+         * comparison compiles to a different schedule */
+        if (at_inner && (uint32_t)__popcll(leaf_m) <= (uint32_t)__popcll(inner_m)) {
             /* inner node (:207-229): test both children against the current best t */
             float4 lmin, lmax, rmin, rmax;
             float tl, tr;
@@ -444,12 +418,8 @@ __device__ __forceinline__ void walk_run(const View &view, Walk<View> &w, F3 ro,
                 cur = walk_pop<ANY_HIT>(view, stack_get(stack, sp));
             }
         }
-#if RPT_LEAF_GREEDY_PCT_GLOBAL
-        const bool do_leaf = (uint32_t)__popcll(leaf_m) * 100u > (uint32_t)__popcll(inner_m) * (uint32_t)RPT_LEAF_GREEDY_PCT_GLOBAL;
-#else
-        const bool do_leaf = (uint32_t)__popcll(leaf_m) >= (uint32_t)RPT_LEAF_K || inner_m == 0ull;
-#endif
-        if (do_leaf) {                                                                       /* (wave-uniform) */
+        const bool do_leaf = (uint32_t)__popcll(leaf_m) > (uint32_t)__popcll(inner_m);    /* (wave-uniform) */
+        if (do_leaf) {
             bool accepted = false, coop_done = false;
             const uint32_t count = View::leaf_count(cur), first = View::leaf_first(cur);
             if constexpr (View::kCoopLeaves) {
@@ -621,16 +591,11 @@ __device__ __forceinline__ bool slab_pair_lds(float n_x, float n_y, float n_z, f
     return tmax >= tmin && tmax > 0.0f && tmin < prev_min_t;
 }
 
-/* leaf batching threshold of the LDS loop: its inner step is ~25 % cheaper than the generic one, so waiting for
- * more leaf lanes pays (one ray per lane: traverse 28.4 ms at K = 8, 26.8-27.3 ms for K = 16..32, 29.0 ms at 48;
- * streamed: 26.0 / 23.7 / 23.5 / 22.6 / 23.3 ms for K = 8 / 12 / 16 / 24 / 32) */
-#ifndef RPT_LEAF_K_LDS
-#define RPT_LEAF_K_LDS 24
-#endif
-#ifndef RPT_LEAF_GREEDY_PCT
-#define RPT_LEAF_GREEDY_PCT 100    /* 0: the threshold rule above; > 0: one body per trip, see lds_walk_run (measured, streamed DarkCornell:
-                                      traverse 82.6 / 80.0 / 81.4 / 82.8 ms per 8 batches for 0 / 100 / 130 / 170) */
-#endif
+/* The LDS loop schedules its bodies like walk_run: one per trip, the one with more lanes ready.  Its inner step is ~25 % cheaper
+ * than the generic one, so the deferred-leaf threshold it had before was higher (one ray per lane: traverse 28.4 ms at K = 8,
+ * 26.8-27.3 ms for K = 16..32, 29.0 ms at 48; streamed: 26.0 / 23.7 / 23.5 / 22.6 / 23.3 ms for K = 8 / 12 / 16 / 24 / 32); the
+ * one-body rule beat K = 24 and the rules that count a leaf step as more than an inner one (streamed DarkCornell: traverse
+ * 82.6 / 80.0 / 81.4 / 82.8 ms per 8 batches for K = 24 / one body / leaf at 130 % / 170 %). */
 /* A walk over the LDS image that can be stopped after a number of loop trips and resumed (k_traverse_nearest_stream):
  * everything a ray needs besides (ro, rd, 1/rd) is in here and in its stack column. */
 struct LdsWalk {
@@ -677,17 +642,13 @@ __device__ __forceinline__ void lds_walk_run(const SceneViewLds &view, LdsWalk &
         const bool at_leaf = cur >= LDS_DESC_LEAF;
         const unsigned long long inner_m = rpt_ballot(at_inner), leaf_m = rpt_ballot(at_leaf);
         if ((inner_m | leaf_m) == 0ull) break;
-#if RPT_LEAF_GREEDY_PCT
-        /* ONE body per trip, the one with more lanes ready for it (a leaf step counts RPT_LEAF_GREEDY_PCT % of an inner one):
-         * lanes on a leaf no longer sit out a fixed quota of inner steps, and no body is issued for a handful of lanes */
+        /* ONE body per trip, the one with more lanes ready for it: lanes on a leaf no longer sit out a fixed quota of inner
+         * steps, and no body is issued for a handful of lanes */
         /* (the compiler evaluates this wave-uniform comparison on the vector unit, v_mov + v_cmp_gt_u64 per trip; forced into
          * scalar registers with s_cmp / s_cselect the kernel got SLOWER, 75.8 -> 77.0 ms: the scalar chain bcnt -> mul -> cmp ->
          * cselect -> nor -> saveexec is latency the vector form hides) */
-        const bool do_leaf = (uint32_t)__popcll(leaf_m) * 100u > (uint32_t)__popcll(inner_m) * (uint32_t)RPT_LEAF_GREEDY_PCT;
+        const bool do_leaf = (uint32_t)__popcll(leaf_m) > (uint32_t)__popcll(inner_m);
         if (at_inner && !do_leaf) {
-#else
-        if (at_inner) {
-#endif
             const float4 X = px[cur], Y = py[cur], Z = pz[cur];     /* (L.near, R.near, L.far, R.far) per axis */
             const uint32_t d = descs[cur];
             float tl, tr;
@@ -710,11 +671,7 @@ __device__ __forceinline__ void lds_walk_run(const SceneViewLds &view, LdsWalk &
                 cur = stack[sp * RPT_WAVE];
             }
         }
-#if RPT_LEAF_GREEDY_PCT
         if (at_leaf && do_leaf) {
-#else
-        if (at_leaf && ((uint32_t)__popcll(leaf_m) >= (uint32_t)RPT_LEAF_K_LDS || inner_m == 0ull)) {
-#endif
             bool accepted = false;
             const uint32_t count = (cur >> 9) & 63u, first = cur & 511u;
             for (uint32_t i = 0; i < count; ++i) {
@@ -802,17 +759,14 @@ __device__ __forceinline__ void iteration_bookkeeping(const DevQueues &q, uint32
     q.count[Q_REGEN0 + prev * Q_LINE] = 0u;
 }
 
-/* Extension rays.  Thread i owns slot i; it traces the slot's ray if one is
+/* Extension rays of a scene the streamed walks cannot take (a node pool that is not pair-shaped), one ray per lane from
+ * global memory.  Thread i owns slot i; it traces the slot's ray if one is
  * pending (HIT_PENDING) and writes the hit record into hit[slot].  A wave that
  * found work raises this iteration's alive flag (plain store, every writer
  * stores the same value), which the shade stage reports to the host. */
-template <int STACK, bool LDS_SCENE, int THREADS, bool SMALL = false>
+template <int STACK, int THREADS>
 __global__ __launch_bounds__(THREADS) void k_traverse_nearest(DevScene sc, DevState st, DevQueues q, uint32_t iteration) {
-    /* LDS-resident scenes walk 16-bit descriptors: 16-bit stack entries (32 KB per 1024-thread workgroup, which with a
-     * <= 32 KB scene image is the 64 KB a workgroup may hold: 2 workgroups = 32 waves per CU) */
-    typedef typename StackElem<LDS_SCENE || SMALL>::type StackT;
-    __shared__ StackT lds_stack[THREADS / RPT_WAVE][STACK][RPT_WAVE];
-    float4 *lds_scene = rpt_lds_dyn;
+    __shared__ uint32_t lds_stack[THREADS / RPT_WAVE][STACK][RPT_WAVE];
     if (q.count[Q_DRAINED] != 0u) return;                      /* surplus launch (grid-uniform) */
     const uint32_t slot = blockIdx.x * THREADS + threadIdx.x;
     if (slot == 0u) {
@@ -820,8 +774,7 @@ __global__ __launch_bounds__(THREADS) void k_traverse_nearest(DevScene sc, DevSt
     }
     bool pending = false;
     if (slot < st.n_slots) pending = __float_as_uint(st.hit[slot].y) == HIT_PENDING;
-    if (LDS_SCENE && !__syncthreads_or(pending)) return;      /* block-uniform: nothing to trace here */
-    const auto view = stage_scene<LDS_SCENE, THREADS>(sc, lds_scene);
+    const SceneViewGlobal view{sc.nodes, sc.tri_isect};
     unsigned long long active = rpt_ballot(pending);
     if (active == 0ull) return;
     if (__lane_id() == (uint32_t)__ffsll((long long)active) - 1u) {
@@ -833,33 +786,26 @@ __global__ __launch_bounds__(THREADS) void k_traverse_nearest(DevScene sc, DevSt
     float4 ra = st.ray_a[slot];
     float2 rb = st.ray_b[slot];
     F3 ro = f3(ra.x, ra.y, ra.z), rd = f3(ra.w, rb.x, rb.y);
-    StackT *stack = &lds_stack[threadIdx.x / RPT_WAVE][0][threadIdx.x % RPT_WAVE];
+    uint32_t *stack = &lds_stack[threadIdx.x / RPT_WAVE][0][threadIdx.x % RPT_WAVE];
     HitRecord h = traverse_one<STACK, false>(view, sc.fastdiv_ok, ro, rd, 0.0f, stack);
     st.hit[slot] = make_float2(h.t, __uint_as_float(h.tri));
 }
 
-/* Extension rays of an LDS-resident scene, STREAMED: a workgroup owns up to RPT_STREAM_RAYS x THREADS consecutive slots
- * and deals them to the idle lanes of its waves on demand.
+/* Extension rays of an LDS-resident scene, STREAMED: a workgroup takes spans of consecutive slots (between 1 and 8 per
+ * lane, rpt_traverse.hip lds_stream_span) and deals them to the idle lanes of its waves on demand.
  * The traversal is VALU-issue bound and after the first bounce the rays of a wave need very different numbers of
  * trips (DarkCornell bounce 2: median 25, p90 34, max 68 node visits), so a one-ray-per-lane wave spends most of its
  * trips with a minority of lanes alive (lane utilisation 40 %).  Here, every RPT_STREAM_TRIPS trips the wave looks at
  * its idle lanes; when at least RPT_STREAM_REFILL are idle they write their hit records and take the next slots from the
- * workgroup's pool (an LDS counter over the workgroup's RPT_STREAM_RAYS x THREADS consecutive slots).  The walk itself (lds_walk_run) is the same code with a trip budget: no per-lane bookkeeping inside
+ * workgroup's pool (below).  The walk itself (lds_walk_run) is the same code with a trip budget: no per-lane bookkeeping inside
  * the hot loop.  Per ray nothing changes — same tests in the same order — so hit records are the reference's bit for
  * bit, and slots stay identity mapped (a slot's ray is traced by SOME lane of the wave that owns its range). */
-#ifndef RPT_STREAM_RAYS
-#define RPT_STREAM_RAYS 8          /* most slots per lane of a workgroup (the host lowers it for small launches) */
-#endif
 /* a wave looks for new rays every RPT_STREAM_TRIPS loop trips, once RPT_STREAM_REFILL of its lanes are idle.  Re-measured with 64
  * pixels per wave (round 3, three boxes, DarkCornell Mrays/s relative to 8 / 12): trips 4 / 12 / 16 / 24 / 32: -2.3 / +0.4 / +0.8 /
  * +1.1 / -0.2 %; refill 8 / 16 / 24 at 8 trips: -1 / +-0 / +-0; 16 / 16: +1.1 ... +1.7 % (and +1.1 % with nee = MIS, +1.0 % on 1/8 of
  * the image); 20 / 16 and 24 / 16 the same within noise, 16 / 20 less. */
-#ifndef RPT_STREAM_TRIPS
-#define RPT_STREAM_TRIPS 16
-#endif
-#ifndef RPT_STREAM_REFILL
-#define RPT_STREAM_REFILL 16
-#endif
+constexpr int RPT_STREAM_TRIPS = 16;
+constexpr int RPT_STREAM_REFILL = 16;
 /* The workgroup's pool is one 64-bit LDS word (next slot | end slot << 32): a wave takes slots with ONE 64-bit ds_add that
  * returns a consistent (next, end) pair.  When the span is used up the wave that notices fetches the next span of SPAN
  * slots from the launch-wide counter (one global atomic per SPAN slots) — PERSISTENT workgroups: the grid holds as many
@@ -1045,31 +991,28 @@ __global__ __launch_bounds__(THREADS) void k_traverse_nearest_stream(DevScene sc
     }
 }
 
-/* Shadow rays (kernels/src/light_pick.rs:141-148): any-hit over the positions of the
+/* Shadow rays (kernels/src/light_pick.rs:141-148) of a scene the streamed walks cannot take, one ray per lane from global
+ * memory: any-hit over the positions of the
  * shadow queue (k_common.h: sharded, dense up to the shards' tails); if unoccluded the pre-weighted NEE contribution is added to the
  * path's radiance (lib.rs:164).  A path that ended at this bounce (bit 31 of
  * the tag) is finished here: accumulated and, if samples remain, regenerated
  * in place (its slot becomes HIT_PENDING again). */
-template <int STACK, bool LDS_SCENE, int THREADS, bool SMALL = false>
+template <int STACK, int THREADS>
 __global__ __launch_bounds__(THREADS) void k_traverse_shadow(DevScene sc, DevState st, DevQueues q, DevConfig cfg, DevStats *stats) {
-    /* LDS-resident scenes walk 16-bit descriptors: 16-bit stack entries (32 KB per 1024-thread workgroup, which with a
-     * <= 32 KB scene image is the 64 KB a workgroup may hold: 2 workgroups = 32 waves per CU) */
-    typedef typename StackElem<LDS_SCENE || SMALL>::type StackT;
-    __shared__ StackT lds_stack[THREADS / RPT_WAVE][STACK][RPT_WAVE];
-    float4 *lds_scene = rpt_lds_dyn;
-    if (q.count[Q_DRAINED] != 0u) return;                      /* surplus launch (grid-uniform) */
+    __shared__ uint32_t lds_stack[THREADS / RPT_WAVE][STACK][RPT_WAVE];
+    if (q.count[Q_DRAINED] != 0u) return;                     /* surplus launch (grid-uniform) */
     uint32_t i = blockIdx.x * THREADS + threadIdx.x;
     uint32_t positions, n;
     q_extent(q.shadow_cnt, positions, n);
     if (i == 0u && n) atomicAdd(&stats->shadow_rays, (unsigned long long)n);
     if (blockIdx.x * THREADS >= positions) return;             /* block-uniform */
-    const auto view = stage_scene<LDS_SCENE, THREADS>(sc, lds_scene);
+    const SceneViewGlobal view{sc.nodes, sc.tri_isect};
     if (i >= positions || !q_filled(q.shadow_cnt, i)) return;
     float4 o = q.sh_o[i], d = q.sh_d[i];
     uint32_t tag = __float_as_uint(d.w);
     uint32_t slot = tag & 0x7fffffffu;
     bool finish = (tag >> 31) != 0u;
-    StackT *stack = &lds_stack[threadIdx.x / RPT_WAVE][0][threadIdx.x % RPT_WAVE];
+    uint32_t *stack = &lds_stack[threadIdx.x / RPT_WAVE][0][threadIdx.x % RPT_WAVE];
     HitRecord h = traverse_one<STACK, true>(view, sc.fastdiv_ok, f3(o.x, o.y, o.z), f3(d.x, d.y, d.z), o.w, stack);
     bool visible = h.tri == HIT_MISS;
     if (visible || finish) {
@@ -1178,45 +1121,31 @@ __global__ __launch_bounds__(THREADS) void k_traverse_shadow_stream(DevScene sc,
  *   - walks with a trip budget and, when RPT_GSTREAM_REFILL lanes are idle, lets them write their results and take
  *     the next rays of the list.
  * Per ray nothing changes (same tests, same order); slots stay identity mapped. */
-#ifndef RPT_GSTREAM_RAYS
-#define RPT_GSTREAM_RAYS 8         /* most slots per lane of a wave (the host lowers it for small launches) */
-#endif
+constexpr int RPT_GSTREAM_RAYS = 8;        /* most slots per lane of a wave (the host lowers it for small launches) */
 /* The nearest-hit walk streams better over a longer list — its pending list costs LDS (2 bytes per slot), and LDS is what caps
  * the waves of these kernels, so only where the stack is small: 16 slots per lane with a 16-bit stack of <= 24 entries (3 KB
  * + 2 KB per wave: still 8 waves per SIMD).  Measured, PBRTest traverse per 4 batches: 8 / 12 / 16 / 24 slots per lane
  * 92.9 / 89.0 / 86.9 / 95.1 ms; with a 32-entry stack 16 slots cost (the stand-in 439 -> 468 ms), and the any-hit walk
  * prefers 8 everywhere (VeachMIS shadow 56.6 / 58.0 / 57.6 / 60.8). */
-#ifndef RPT_GSTREAM_RAYS_NEAREST_SMALL
-#define RPT_GSTREAM_RAYS_NEAREST_SMALL 16
-#endif
+constexpr int RPT_GSTREAM_RAYS_NEAREST_SMALL = 16;
 __host__ __device__ constexpr int gstream_rays_nearest(int stack, int width) {
     return (stack <= 24 && width <= 21) ? RPT_GSTREAM_RAYS_NEAREST_SMALL : RPT_GSTREAM_RAYS;
 }
-#ifndef RPT_GSTREAM_TRIPS
-#define RPT_GSTREAM_TRIPS 8
-#endif
+constexpr int RPT_GSTREAM_TRIPS = 8;
 /* (measured and dropped, round 3: dealing a span's rays grouped by the octant of their direction — the slots of a wave belong to
  * one or two pixels, so after a bounce their rays leave almost one point — 2 M-node stand-in + 2.4 %, PBRTest - 1.3 %, VeachMIS - 0.8 %,
  * the fat-leaf stand-in +- 0) */
-#ifndef RPT_GSTREAM_REFILL_FIRST
-#define RPT_GSTREAM_REFILL_FIRST 64      /* nearest-hit walk, iteration 0 of a batch: see k_traverse_nearest_gstream */
-#endif
-#ifndef RPT_GSTREAM_REFILL
-#define RPT_GSTREAM_REFILL 24      /* (round 3, 64 pixels per wave: 8 / 16 / 24 idle lanes: PBRTest 7 390 / 7 390 / 7 445, VeachMIS 6 560 / 6 615 / 6 655 Mrays/s;
-                                      trips 4 / 8 / 12 / 16: 7 355 / 7 390 / 7 320 / 7 250 and 6 620 / 6 615 / 6 530 / 6 480) */
-#endif
+constexpr int RPT_GSTREAM_REFILL_FIRST = 64;     /* nearest-hit walk, iteration 0 of a batch: see k_traverse_nearest_gstream */
+constexpr int RPT_GSTREAM_REFILL = 24;     /* (round 3, 64 pixels per wave: 8 / 16 / 24 idle lanes: PBRTest 7 390 / 7 390 / 7 445, VeachMIS 6 560 / 6 615 / 6 655 Mrays/s;
+                                              trips 4 / 8 / 12 / 16: 7 355 / 7 390 / 7 320 / 7 250 and 6 620 / 6 615 / 6 530 / 6 480) */
 /* The global-memory walks wait on memory two thirds of their cycles (profiles/r02_*_pmc_sq.txt) and live on occupancy.  Left
  * alone the compiler settles at 68 / 77 VGPRs (7 / 6 waves per SIMD); asked for 8 it needs 57 / 58 and spills nothing:
  * PBRTest traverse 97.3 -> 92.8 ms per 4 batches, VeachMIS traverse + shadow 91.8 -> 87.9, the 1 M-triangle stand-in's
  * shadow stage 391 -> 366.  (Wider stack entries cap the occupancy through LDS instead: hence the 24-bit form, WaveStack.) */
-#ifndef RPT_GSTREAM_WAVES
-#define RPT_GSTREAM_WAVES 8
-#endif
-#ifndef RPT_GSTREAM_WAVES_COOP
-#define RPT_GSTREAM_WAVES_COOP 8   /* the fat-leaf build holds a leaf's triangle records in registers: 63 / 64 VGPRs, no spill.  Requesting the NEXT
-                                      leaf's records one leaf ahead (9 more registers) was measured and lost at every occupancy: the 1 M-triangle
-                                      stand-in 2 343 Mrays/s without, 2 008 / 2 164 / 2 099 with it at 8 (spilling) / 7 / 6 waves per SIMD */
-#endif
+constexpr int RPT_GSTREAM_WAVES = 8;
+constexpr int RPT_GSTREAM_WAVES_COOP = 8;  /* the fat-leaf build holds a leaf's triangle records in registers: 63 / 64 VGPRs, no spill.  Requesting the NEXT
+                                              leaf's records one leaf ahead (9 more registers) was measured and lost at every occupancy: the 1 M-triangle
+                                              stand-in 2 343 Mrays/s without, 2 008 / 2 164 / 2 099 with it at 8 (spilling) / 7 / 6 waves per SIMD */
 __host__ __device__ constexpr int gstream_waves(int stack, int width, bool coop) {
     return (width <= 21 || (width == 24 && stack <= 24)) ? (coop ? (width >= 21 ? 7 : RPT_GSTREAM_WAVES_COOP) : RPT_GSTREAM_WAVES) : 1;   /* (where LDS allows it at all;
                                                              fat leaves + 21-bit entries: 8 waves would spill 18 registers, + 24-bit entries: 3) */
@@ -1259,8 +1188,8 @@ __attribute__((amdgpu_waves_per_eu(gstream_waves(STACK, WIDTH, COOP), 8)))
         raise_flag(&q.count[Q_ALIVE0 + (iteration & 1u) * Q_LINE]);
         atomicAdd(&q.ray_shards[(blockIdx.x % RPT_STAT_SHARDS) * RPT_STAT_STRIDE], (unsigned long long)count);
     }
-    typedef typename GstreamView<COOP>::type View;
-    const View view = RPT_GSTREAM_VIEW(COOP, sc);
+    typedef SceneViewPairsT<COOP> View;
+    const View view{sc.gpairs, sc.glinks, sc.tri_isect};
     auto stack = lds_stack.column(lane);
     F3 ro = f3(0, 0, 0), rd = f3(1, 1, 1), ird = f3(1, 1, 1);
     Walk<View> w;
@@ -1271,7 +1200,7 @@ __attribute__((amdgpu_waves_per_eu(gstream_waves(STACK, WIDTH, COOP), 8)))
     /* The first iteration of a batch walks CAMERA rays: the 64 slots a wave deals together are one 8 x 8 pixel block at one sample index, their
      * rays stand on the same node step after step (k_traverse.h children_uniform: the scalar-cache path) and end within a few steps of each other.
      * A refill would put rays at the root beside rays deep in the tree and end that: there the wave takes its next 64 slots only when all are done. */
-    const uint32_t refill_at = (View::kUniformScalar && iteration == 0u) ? (uint32_t)RPT_GSTREAM_REFILL_FIRST : (uint32_t)RPT_GSTREAM_REFILL;
+    const uint32_t refill_at = iteration == 0u ? (uint32_t)RPT_GSTREAM_REFILL_FIRST : (uint32_t)RPT_GSTREAM_REFILL;
     for (;;) {
         const unsigned long long idle_m = rpt_ballot(walk_dead(w));
         const uint32_t n_idle = (uint32_t)__popcll(idle_m);
@@ -1357,8 +1286,8 @@ __attribute__((amdgpu_waves_per_eu(gstream_waves(STACK, WIDTH, COOP), 8)))
     if (begin >= n) return;
     const uint32_t end = begin + SPAN < n ? begin + SPAN : n;
     {
-        typedef typename GstreamView<COOP>::type View;
-        const View view = FIXED ? RPT_GSTREAM_VIEW_SHADOW(COOP, sc) : RPT_GSTREAM_VIEW(COOP, sc);
+        typedef SceneViewPairsT<COOP> View;
+        const View view = FIXED ? View{sc.gpairs_shadow, sc.glinks_shadow, sc.tri_isect} : View{sc.gpairs, sc.glinks, sc.tri_isect};
         auto stack = lds_stack.column(lane);
         F3 ro = f3(0, 0, 0), rd = f3(1, 1, 1), ird = f3(1, 1, 1);
         float max_t = 0.0f;

@@ -157,11 +157,6 @@ struct rpt_ctx {
     uint32_t untile_n = 0;
 };
 
-/* workgroup size of the LDS-resident-scene traversal kernels: 2 x (32 KB of 16-bit stacks + up to 32 KB of scene = the 64 KB a
- * workgroup may hold) per CU = 32 waves */
-#ifndef RPT_LDS_THREADS
-#define RPT_LDS_THREADS 1024
-#endif
 /* rpt_traverse.hip: the traversal stages (which walk kernel for the context's scene, on which grid) */
 void rpt_launch_nearest(rpt_ctx *c, uint32_t iteration, bool last_without_nee /* the last extension rays of a batch of known length, no NEE */,
                         bool camera_rays /* iteration 0 of a render call: every ray leaves cfg.cam_position */);

@@ -309,7 +309,7 @@ static void launch_complete(rpt_ctx *c, uint32_t iteration, uint32_t final_pass)
                                                                                                                      c->dev_stats.p);
 }
 
-template <int STACK, int NEE, bool TEXTURED>
+template <int NEE, bool TEXTURED>
 void launch_iteration(rpt_ctx *c, uint32_t iteration, uint32_t blocks, std::vector<hipEvent_t> *ev, size_t &ev_at, bool complete_each, bool sky_now) {
     hipStream_t s = c->stream;
     const bool only_traverse = c->timing_level == 2;
@@ -338,21 +338,21 @@ void launch_iteration(rpt_ctx *c, uint32_t iteration, uint32_t blocks, std::vect
     mark();
 }
 
-template <int STACK>
-void launch_iteration_stack(rpt_ctx *c, uint32_t iteration, uint32_t blocks, std::vector<hipEvent_t> *ev, size_t &ev_at, bool complete_each, bool sky_now) {
+/* one iteration with the shade stage built for the context's NEE mode and scene (the walks pick their stack width themselves: rpt_traverse.hip) */
+static void dispatch_iteration(rpt_ctx *c, uint32_t iteration, uint32_t blocks, std::vector<hipEvent_t> *ev, size_t &ev_at, bool complete_each, bool sky_now) {
     const bool tex = c->scene.textured != 0u;
     switch (c->cfg.nee_mode) {
         case RPT_NEE_MIS:
-            if (tex) launch_iteration<STACK, RPT_NEE_MIS, true>(c, iteration, blocks, ev, ev_at, complete_each, sky_now);
-            else launch_iteration<STACK, RPT_NEE_MIS, false>(c, iteration, blocks, ev, ev_at, complete_each, sky_now);
+            if (tex) launch_iteration<RPT_NEE_MIS, true>(c, iteration, blocks, ev, ev_at, complete_each, sky_now);
+            else launch_iteration<RPT_NEE_MIS, false>(c, iteration, blocks, ev, ev_at, complete_each, sky_now);
             break;
         case RPT_NEE_DIRECT:
-            if (tex) launch_iteration<STACK, RPT_NEE_DIRECT, true>(c, iteration, blocks, ev, ev_at, complete_each, sky_now);
-            else launch_iteration<STACK, RPT_NEE_DIRECT, false>(c, iteration, blocks, ev, ev_at, complete_each, sky_now);
+            if (tex) launch_iteration<RPT_NEE_DIRECT, true>(c, iteration, blocks, ev, ev_at, complete_each, sky_now);
+            else launch_iteration<RPT_NEE_DIRECT, false>(c, iteration, blocks, ev, ev_at, complete_each, sky_now);
             break;
         default:
-            if (tex) launch_iteration<STACK, RPT_NEE_NONE, true>(c, iteration, blocks, ev, ev_at, complete_each, sky_now);
-            else launch_iteration<STACK, RPT_NEE_NONE, false>(c, iteration, blocks, ev, ev_at, complete_each, sky_now);
+            if (tex) launch_iteration<RPT_NEE_NONE, true>(c, iteration, blocks, ev, ev_at, complete_each, sky_now);
+            else launch_iteration<RPT_NEE_NONE, false>(c, iteration, blocks, ev, ev_at, complete_each, sky_now);
             break;
     }
 }
@@ -1361,11 +1361,7 @@ static int render_impl(rpt_ctx *c, uint32_t n_samples, bool allow_async) {
         }
         const bool complete_each = known_iterations == 0 && c->group_shift != 0;
         const bool sky_now = it + 1 == known_iterations - short_batch;      /* (sky_at_end: the one sky launch of the batch) */
-        switch (c->stack_cap) {
-            case 16: launch_iteration_stack<16>(c, (uint32_t)it, blocks, ev, ev_at, complete_each, sky_now); break;
-            case 24: launch_iteration_stack<24>(c, (uint32_t)it, blocks, ev, ev_at, complete_each, sky_now); break;
-            default: launch_iteration_stack<32>(c, (uint32_t)it, blocks, ev, ev_at, complete_each, sky_now); break;
-        }
+        dispatch_iteration(c, (uint32_t)it, blocks, ev, ev_at, complete_each, sky_now);
         full_iterations += 1u;
         it += 1;
         if (it == known_iterations - short_batch) {             /* (no report needed: nothing can be left) */

@@ -97,7 +97,7 @@ RPT_HD float sqrtr(float x) { return __builtin_sqrtf(x); }          /* IEEE corr
  * residual would underflow); callers state why theirs cannot be one.  (With a range test and an IEEE fallback instead of the
  * precondition the sky stage got SLOWER, 52.3 -> 55.3 ms: the branch splits the scheduling region of a latency-bound march.) */
 RPT_HD float div_const_nontiny(float a, float c, float rc) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(RPT_NO_DIV_CONST)
+#if defined(__HIP_DEVICE_COMPILE__)
     const float q0 = a * rc;
     const float r = __builtin_fmaf(-q0, c, a);
     return __builtin_amdgcn_div_fixupf(__builtin_fmaf(r, rc, q0), c, a);
@@ -274,16 +274,9 @@ RPT_HD float expr(float x) {
  * like everything here (IEEE mul / add / fma, explicit fma only), within 1 ulp of the exact value (tests/test_math.py:
  * max 1 ulp from the correctly rounded expr, equal on ~90 % of arguments) — NOT correctly rounded, and it need not be:
  * the sky's radiance ends a path, no later decision of that path (lobe, light pick, roulette, hit / miss) depends on
- * it, so a last-bit difference stays a 1e-7 relative difference of a pixel's value instead of a flipped path.
- * RPT_SKY_EXACT_EXP = 1 routes it back through the correctly rounded expr. */
-#ifndef RPT_SKY_EXACT_EXP
-#define RPT_SKY_EXACT_EXP 0
-#endif
+ * it, so a last-bit difference stays a 1e-7 relative difference of a pixel's value instead of a flipped path. */
 RPT_HD float exp2i_f(int k) { return u2f((uint32_t)(k + 127) << 23); }       /* 2^k, k in [-126, 127] */
 RPT_HD float exp_sky(float x) {
-#if RPT_SKY_EXACT_EXP
-    return expr(x);
-#else
     const float c[RPT_EXPF_C_N] = RPT_EXPF_C_INIT;
     /* Specials without their own branches (84 calls per sky miss: three compares, three selects and their constants were a third of this function): the
      * argument is clamped to [-104, 89] — at 89 the two scaling multiplies below overflow to +inf (1.32 * 2^128), at -104 they round 0.97 * 2^-150 to +0,
@@ -305,7 +298,6 @@ RPT_UNROLL
      * same value for every float, tools/exp_sky_check.cpp compares the two forms), ten instructions of this function's twenty-four, 84 calls per sky miss. */
     const float e = __builtin_ldexpf(p, (int)kf);
     return x_in != x_in ? x_in : e;
-#endif
 }
 
 /* natural log of a positive finite double-representable float value */

@@ -1,20 +1,22 @@
 /*
  * rpt_traverse.hip — the traversal stages of librpt_hip.so: which kernel of k_traverse.h walks the extension rays / the shadow rays of a context's scene,
- * and on which grid.  Its own translation unit since round 6 (the 57 walk kernels are half of the library's compile time; the three units build in parallel).
+ * and on which grid.  Its own translation unit since round 6 (the walk kernels are half of the library's compile time; the three units build in parallel).
  * Entry points (rpt_ctx.h): rpt_launch_nearest, rpt_launch_shadow, rpt_launch_trace_debug, rpt_last_walk_attributes.
  */
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "rpt_ctx.h"
 #include "k_traverse.h"
 
 namespace {
 
-#ifndef RPT_GLOBAL_THREADS
-#define RPT_GLOBAL_THREADS 64      /* one wave: no scene staging to share, and a finished wave frees its stack at once (PBRTest traverse -5 %) */
-#endif
-constexpr int GLOBAL_THREADS = RPT_GLOBAL_THREADS;   /* workgroup size of the global-memory traversal variants */
-constexpr int LDS_THREADS = RPT_LDS_THREADS;     /* (rpt_ctx.h) */
+constexpr int GLOBAL_THREADS = 64;   /* workgroup size of the one-ray-per-lane global-memory walks.  One wave: no scene staging to share, and a
+                                        finished wave frees its stack at once (PBRTest traverse -5 %) */
+/* workgroup size of the LDS-resident-scene traversal kernels: 2 x (32 KB of 16-bit stacks + up to 32 KB of scene = the 64 KB a
+ * workgroup may hold) per CU = 32 waves */
+constexpr int LDS_THREADS = 1024;
 
 
 template <int STACK>
@@ -25,6 +27,17 @@ static int gstream_stack_width(const rpt_ctx *c) {
     const int bits = c->knobs.stack_bits;
     const int w = (c->scene.n_nodes < 65536u && bits <= 16) ? 16 : (c->scene.n_nodes < (1u << 21) && bits <= 21) ? 21 : (c->scene.n_nodes < (1u << 24) && bits <= 24) ? 24 : 32;
     return STACK == 24 && w > 24 ? 24 : w;
+}
+/* launch(std::integral_constant<int, WIDTH>) for the entry width gstream_stack_width<STACK> returned: only the (STACK, WIDTH) pairs it can return
+ * are instantiated */
+template <int STACK, typename F>
+static void with_stack_width(int width, F &&launch) {
+    if constexpr (STACK == 16) launch(std::integral_constant<int, 16>{});
+    else if (width == 16) launch(std::integral_constant<int, 16>{});
+    else if (width == 21) launch(std::integral_constant<int, 21>{});
+    else if constexpr (STACK == 24) launch(std::integral_constant<int, 24>{});
+    else if (width == 24) launch(std::integral_constant<int, 24>{});
+    else launch(std::integral_constant<int, 32>{});
 }
 /* slots per wave of the streamed global-memory walks: as many as keep >= gstream_min_waves waves in the launch, at most `most` per lane */
 static uint32_t gstream_span(const rpt_ctx *c, uint32_t most) {
@@ -50,11 +63,9 @@ template <int STACK, bool COOP>
 static void launch_nearest_gstream(rpt_ctx *c, uint32_t iteration) {
     const int width = gstream_stack_width<STACK>(c);
     const uint32_t span = gstream_span(c, (uint32_t)gstream_rays_nearest(STACK, width)), blocks = (c->n_slots + span - 1) / span;
-#define RPT_LAUNCH_NEAREST(W) k_traverse_nearest_gstream<STACK, W, COOP><<<blocks, RPT_WAVE, 0, c->stream>>>(c->scene, c->state, c->queues, iteration, span)
-    if constexpr (STACK == 16) RPT_LAUNCH_NEAREST(16);
-    else if constexpr (STACK == 24) { if (width == 16) RPT_LAUNCH_NEAREST(16); else if (width == 21) RPT_LAUNCH_NEAREST(21); else RPT_LAUNCH_NEAREST(24); }
-    else { if (width == 16) RPT_LAUNCH_NEAREST(16); else if (width == 21) RPT_LAUNCH_NEAREST(21); else if (width == 24) RPT_LAUNCH_NEAREST(24); else RPT_LAUNCH_NEAREST(32); }
-#undef RPT_LAUNCH_NEAREST
+    with_stack_width<STACK>(width, [&](auto W) {
+        k_traverse_nearest_gstream<STACK, decltype(W)::value, COOP><<<blocks, RPT_WAVE, 0, c->stream>>>(c->scene, c->state, c->queues, iteration, span);
+    });
 }
 
 /* The nearest-hit traversal stage for the context's scene and state: which kernel, which grid.  Used by every iteration of a
@@ -81,7 +92,7 @@ void launch_nearest(rpt_ctx *c, uint32_t iteration, bool last_without_nee = fals
         else launch_nearest_gstream<STACK, false>(c, iteration);
     } else {
         const uint32_t nb = (c->n_slots + GLOBAL_THREADS - 1) / GLOBAL_THREADS;
-        k_traverse_nearest<32, false, GLOBAL_THREADS><<<nb, GLOBAL_THREADS, 0, s>>>(c->scene, c->state, c->queues, iteration);
+        k_traverse_nearest<32, GLOBAL_THREADS><<<nb, GLOBAL_THREADS, 0, s>>>(c->scene, c->state, c->queues, iteration);
     }
 }
 
@@ -90,15 +101,11 @@ template <int STACK, bool COOP>
 static void launch_shadow_gstream(rpt_ctx *c, uint32_t q_positions) {
     const int width = gstream_stack_width<STACK>(c);
     const uint32_t span = gstream_span(c, (uint32_t)RPT_GSTREAM_RAYS), blocks = (q_positions + span - 1) / span;
-#define RPT_LAUNCH_SHADOW(W)                                                                                                                                \
-    do {                                                                                                                                                    \
-        if (c->scene.gpairs_shadow) k_traverse_shadow_gstream<STACK, W, COOP, true><<<blocks, RPT_WAVE, 0, c->stream>>>(c->scene, c->state, c->queues, c->cfg, c->dev_stats.p, span); \
-        else k_traverse_shadow_gstream<STACK, W, COOP, false><<<blocks, RPT_WAVE, 0, c->stream>>>(c->scene, c->state, c->queues, c->cfg, c->dev_stats.p, span);     \
-    } while (0)
-    if constexpr (STACK == 16) RPT_LAUNCH_SHADOW(16);
-    else if constexpr (STACK == 24) { if (width == 16) RPT_LAUNCH_SHADOW(16); else if (width == 21) RPT_LAUNCH_SHADOW(21); else RPT_LAUNCH_SHADOW(24); }
-    else { if (width == 16) RPT_LAUNCH_SHADOW(16); else if (width == 21) RPT_LAUNCH_SHADOW(21); else if (width == 24) RPT_LAUNCH_SHADOW(24); else RPT_LAUNCH_SHADOW(32); }
-#undef RPT_LAUNCH_SHADOW
+    with_stack_width<STACK>(width, [&](auto W) {
+        constexpr int WIDTH = decltype(W)::value;
+        if (c->scene.gpairs_shadow) k_traverse_shadow_gstream<STACK, WIDTH, COOP, true><<<blocks, RPT_WAVE, 0, c->stream>>>(c->scene, c->state, c->queues, c->cfg, c->dev_stats.p, span);
+        else k_traverse_shadow_gstream<STACK, WIDTH, COOP, false><<<blocks, RPT_WAVE, 0, c->stream>>>(c->scene, c->state, c->queues, c->cfg, c->dev_stats.p, span);
+    });
 }
 
 
@@ -107,20 +114,18 @@ void launch_shadow(rpt_ctx *c) {
     hipStream_t s = c->stream;
     const size_t lds_bytes = (size_t)c->scene.lds_vecs * sizeof(float4);
     const uint32_t q_positions = c->n_slots + RPT_Q_SLACK, blocks_q = (q_positions + RPT_BLOCK - 1) / RPT_BLOCK;
-    {
-        if (STACK == 16 && c->scene.lds_scene) {
-            uint32_t grid;
-            const uint32_t span = lds_stream_span(c, grid);
-            if (c->scene.lds_image_shadow) k_traverse_shadow_stream<16, LDS_THREADS, true><<<grid, LDS_THREADS, lds_bytes, s>>>(c->scene, c->state, c->queues, c->dev_stats.p, span);
-            else k_traverse_shadow_stream<16, LDS_THREADS, false><<<grid, LDS_THREADS, lds_bytes, s>>>(c->scene, c->state, c->queues, c->dev_stats.p, span);
-            k_shadow_resolve<<<blocks_q, RPT_BLOCK, 0, s>>>(c->state, c->queues, c->cfg);
-        } else if (c->scene.gpairs) {
-            if (c->fat_leaves) launch_shadow_gstream<STACK, true>(c, q_positions);
-            else launch_shadow_gstream<STACK, false>(c, q_positions);
-        } else {
-            const uint32_t nb = (q_positions + GLOBAL_THREADS - 1) / GLOBAL_THREADS;
-            k_traverse_shadow<32, false, GLOBAL_THREADS><<<nb, GLOBAL_THREADS, 0, s>>>(c->scene, c->state, c->queues, c->cfg, c->dev_stats.p);
-        }
+    if (STACK == 16 && c->scene.lds_scene) {
+        uint32_t grid;
+        const uint32_t span = lds_stream_span(c, grid);
+        if (c->scene.lds_image_shadow) k_traverse_shadow_stream<16, LDS_THREADS, true><<<grid, LDS_THREADS, lds_bytes, s>>>(c->scene, c->state, c->queues, c->dev_stats.p, span);
+        else k_traverse_shadow_stream<16, LDS_THREADS, false><<<grid, LDS_THREADS, lds_bytes, s>>>(c->scene, c->state, c->queues, c->dev_stats.p, span);
+        k_shadow_resolve<<<blocks_q, RPT_BLOCK, 0, s>>>(c->state, c->queues, c->cfg);
+    } else if (c->scene.gpairs) {
+        if (c->fat_leaves) launch_shadow_gstream<STACK, true>(c, q_positions);
+        else launch_shadow_gstream<STACK, false>(c, q_positions);
+    } else {
+        const uint32_t nb = (q_positions + GLOBAL_THREADS - 1) / GLOBAL_THREADS;
+        k_traverse_shadow<32, GLOBAL_THREADS><<<nb, GLOBAL_THREADS, 0, s>>>(c->scene, c->state, c->queues, c->cfg, c->dev_stats.p);
     }
 }
 
@@ -143,7 +148,7 @@ void rpt_launch_shadow(rpt_ctx *c) {
 }
 
 hipError_t rpt_last_walk_attributes(hipFuncAttributes *out) {
-    return hipFuncGetAttributes(out, reinterpret_cast<const void *>(&k_traverse_nearest_stream<16, RPT_LDS_THREADS, RPT_NEAREST_LAST>));
+    return hipFuncGetAttributes(out, reinterpret_cast<const void *>(&k_traverse_nearest_stream<16, LDS_THREADS, RPT_NEAREST_LAST>));
 }
 
 /* rpt_debug_trace_rays: plain ray arrays through the reference-order walk (traverse_one), out of LDS where the scene lives there */

@@ -12,7 +12,7 @@ leaves: a lane that needs the other body PARKS on its node until that body is is
   exact body    today's inner step (slab_pair_lds<true>), issued for the parked lanes only;
   leaf body     unchanged.
 
-Per trip ONE body runs, the one with the most lanes ready (the kernel's RPT_LEAF_GREEDY_PCT = 100 rule, extended to three).  Costs in
+Per trip ONE body runs, the one with the most lanes ready (the kernels' walk rule, extended to three).  Costs in
 VALU wave-instructions per step (ISA counts of the built kernel): exact inner 75, leaf 70, refill look 120; filter inner 75 - 36
 (eleven... twelve planes x 3 instructions less) + the bound test, a parameter (48 ... 55).
 
