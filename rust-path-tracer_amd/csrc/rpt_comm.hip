@@ -118,8 +118,7 @@ struct rpt_comm {
     DevBuf<float4> gathered;         /* root: world x stride */
     DevBuf<uint32_t> map;            /* root: destination pixel of every element of `gathered` */
     DevBuf<float4> full_image;       /* root: row-major W x H */
-    float *host_full = nullptr;      /* root: pinned staging for rpt_read_gathered */
-    size_t host_full_floats = 0;
+    PinnedBuf<float> host_full;      /* root: pinned staging for rpt_read_gathered */
     uint64_t stride = 0;
     std::vector<uint64_t> sizes;
     uint32_t conf_w = 0, conf_h = 0;
@@ -127,26 +126,15 @@ struct rpt_comm {
     bool started = false;
 };
 
-void rpt_image_release(rpt_ctx *c) {
-    c->image.release();
-    if (c->host_image) (void)hipHostFree(c->host_image);
-    c->host_image = nullptr;
-    c->host_image_floats = 0;
-    c->untile_map.release();
-    c->untile_key = 0;
-}
-
 void rpt_comm_release(rpt_ctx *c) {
     rpt_comm *cm = c->comm;
     if (!cm) return;
     if (cm->stream) (void)hipStreamSynchronize(cm->stream);
     if (cm->comm && cm->owns_comm) (void)rccl().CommDestroy(cm->comm);
-    cm->send.release(); cm->gathered.release(); cm->map.release(); cm->full_image.release();
-    if (cm->host_full) (void)hipHostFree(cm->host_full);
     if (cm->staged) (void)hipEventDestroy(cm->staged);
     if (cm->sent) (void)hipEventDestroy(cm->sent);
     if (cm->stream) (void)hipStreamDestroy(cm->stream);
-    delete cm;
+    delete cm;                       /* (frees the gather buffers) */
     c->comm = nullptr;
 }
 
@@ -159,13 +147,7 @@ int ensure_image(rpt_ctx *c) {
         HIP_TRY(c, c->image.alloc(n));
         HIP_TRY(c, hipMemsetAsync(c->image.p, 0, n * sizeof(float4), c->stream));   /* other ranks' pixels stay zero for ever */
     }
-    if (c->host_image_floats != n * 4) {
-        if (c->host_image) (void)hipHostFree(c->host_image);
-        c->host_image = nullptr;
-        c->host_image_floats = 0;
-        HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&c->host_image), n * sizeof(float4), hipHostMallocDefault));
-        c->host_image_floats = n * 4;
-    }
+    if (c->host_image.n != n * 4) HIP_TRY(c, c->host_image.alloc(n * 4, hipHostMallocDefault));
     return RPT_OK;
 }
 
@@ -175,7 +157,7 @@ int enqueue_readback(rpt_ctx *c) {
     if (rc) return rc;
     if (c->n_pixels)
         k_untile<<<(c->n_pixels + RPT_BLOCK - 1) / RPT_BLOCK, RPT_BLOCK, 0, c->stream>>>(c->accum.p, c->pixel_xy.p, c->n_pixels, c->cfg.c.width, c->image.p);
-    HIP_TRY(c, hipMemcpyAsync(c->host_image, c->image.p, c->host_image_floats * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->host_image.p, c->image.p, c->host_image.n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     return RPT_OK;
 }
 
@@ -208,13 +190,7 @@ int comm_configure(rpt_ctx *c) {
         HIP_TRY(c, cm->full_image.alloc((size_t)W * H));
         if (!map.empty()) HIP_TRY(c, hipMemcpy(cm->map.p, map.data(), map.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         HIP_TRY(c, hipMemsetAsync(cm->full_image.p, 0, (size_t)W * H * sizeof(float4), cm->stream));   /* (on the stream that un-tiles into it: rpt_hip.hip, stream discipline) */
-        if (cm->host_full_floats != (size_t)W * H * 4) {
-            if (cm->host_full) (void)hipHostFree(cm->host_full);
-            cm->host_full = nullptr;
-            cm->host_full_floats = 0;
-            HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&cm->host_full), (size_t)W * H * sizeof(float4), hipHostMallocDefault));
-            cm->host_full_floats = (size_t)W * H * 4;
-        }
+        if (cm->host_full.n != (size_t)W * H * 4) HIP_TRY(c, cm->host_full.alloc((size_t)W * H * 4, hipHostMallocDefault));
     }
     cm->conf_w = W;
     cm->conf_h = H;
@@ -306,7 +282,7 @@ int rpt_read_accum(rpt_ctx *c, float *out, uint32_t *out_samples) {
     if (!out) return RPT_EINVAL;
     int rc = rpt_map_accum(c, &mapped, out_samples);
     if (rc) return rc;
-    memcpy(out, mapped, c->host_image_floats * sizeof(float));
+    memcpy(out, mapped, c->host_image.n * sizeof(float));
     return RPT_OK;
 }
 
@@ -318,7 +294,7 @@ int rpt_map_accum(rpt_ctx *c, const float **out, uint32_t *out_samples) {
     if (rc) return rc;
     rc = rpt_wait(c);                    /* one synchronisation; also verifies that asynchronous batches drained */
     if (rc) return rc;
-    *out = c->host_image;
+    *out = c->host_image.p;
     if (out_samples) *out_samples = c->samples;
     return RPT_OK;
 }
@@ -447,32 +423,24 @@ int rpt_debug_comm_selftest(rpt_ctx *c, uint32_t n_floats, uint64_t *mismatches_
     for (uint32_t i = 0; i < n_floats; ++i) host[i] = pattern(cm->rank, i);
     DevBuf<float> src, dst;
     HIP_TRY(c, src.alloc(n_floats));
-    if (dst.alloc(n_floats) != hipSuccess) { src.release(); c->error = "rpt_debug_comm_selftest: out of device memory"; return RPT_ENOMEM; }
-    int rc = RPT_OK;
-    auto body = [&]() -> int {
-        /* render stream: the payload is staged (as gather_stage's snapshot is), the comm stream waits for it */
-        if (cm->started) HIP_TRY(c, hipStreamWaitEvent(c->stream, cm->sent, 0));
-        HIP_TRY(c, hipMemcpyAsync(src.p, host.data(), (size_t)n_floats * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemsetAsync(dst.p, 0xff, (size_t)n_floats * sizeof(float), c->stream));
-        HIP_TRY(c, hipEventRecord(cm->staged, c->stream));
-        HIP_TRY(c, hipStreamWaitEvent(cm->stream, cm->staged, 0));
-        NCCL_TRY(c, rccl().GroupStart());
-        ncclResult_t r1 = rccl().Send(src.p, n_floats, ncclFloat, next, cm->comm, cm->stream);
-        ncclResult_t r2 = rccl().Recv(dst.p, n_floats, ncclFloat, prev, cm->comm, cm->stream);
-        ncclResult_t ge = rccl().GroupEnd();
-        NCCL_TRY(c, r1);
-        NCCL_TRY(c, r2);
-        NCCL_TRY(c, ge);
-        HIP_TRY(c, hipEventRecord(cm->sent, cm->stream));
-        HIP_TRY(c, hipMemcpyAsync(back.data(), dst.p, (size_t)n_floats * sizeof(float), hipMemcpyDeviceToHost, cm->stream));
-        HIP_TRY(c, hipStreamSynchronize(cm->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        return RPT_OK;
-    };
-    rc = body();
-    src.release();
-    dst.release();
-    if (rc) return rc;
+    if (dst.alloc(n_floats) != hipSuccess) { c->error = "rpt_debug_comm_selftest: out of device memory"; return RPT_ENOMEM; }
+    /* render stream: the payload is staged (as gather_stage's snapshot is), the comm stream waits for it */
+    if (cm->started) HIP_TRY(c, hipStreamWaitEvent(c->stream, cm->sent, 0));
+    HIP_TRY(c, hipMemcpyAsync(src.p, host.data(), (size_t)n_floats * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(dst.p, 0xff, (size_t)n_floats * sizeof(float), c->stream));
+    HIP_TRY(c, hipEventRecord(cm->staged, c->stream));
+    HIP_TRY(c, hipStreamWaitEvent(cm->stream, cm->staged, 0));
+    NCCL_TRY(c, rccl().GroupStart());
+    ncclResult_t r1 = rccl().Send(src.p, n_floats, ncclFloat, next, cm->comm, cm->stream);
+    ncclResult_t r2 = rccl().Recv(dst.p, n_floats, ncclFloat, prev, cm->comm, cm->stream);
+    ncclResult_t ge = rccl().GroupEnd();
+    NCCL_TRY(c, r1);
+    NCCL_TRY(c, r2);
+    NCCL_TRY(c, ge);
+    HIP_TRY(c, hipEventRecord(cm->sent, cm->stream));
+    HIP_TRY(c, hipMemcpyAsync(back.data(), dst.p, (size_t)n_floats * sizeof(float), hipMemcpyDeviceToHost, cm->stream));
+    HIP_TRY(c, hipStreamSynchronize(cm->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     uint64_t bad = 0;
     for (uint32_t i = 0; i < n_floats; ++i) {
         const float want = pattern((uint32_t)prev, i);
@@ -514,9 +482,9 @@ int rpt_read_gathered(rpt_ctx *c, float *out, uint32_t *out_samples) {
         return RPT_EINVAL;
     }
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(cm->host_full, cm->full_image.p, cm->host_full_floats * sizeof(float), hipMemcpyDeviceToHost, cm->stream));
+    HIP_TRY(c, hipMemcpyAsync(cm->host_full.p, cm->full_image.p, cm->host_full.n * sizeof(float), hipMemcpyDeviceToHost, cm->stream));
     HIP_TRY(c, hipStreamSynchronize(cm->stream));
-    memcpy(out, cm->host_full, cm->host_full_floats * sizeof(float));
+    memcpy(out, cm->host_full.p, cm->host_full.n * sizeof(float));
     if (out_samples) *out_samples = cm->gathered_samples;
     return RPT_OK;
 }

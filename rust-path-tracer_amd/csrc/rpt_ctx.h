@@ -10,6 +10,7 @@
 #include <chrono>
 #include <cstdio>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/rpt/rpt.h"
@@ -17,29 +18,69 @@
 #include "k_common.h"
 #include "shadow_order.h"
 
-#define HIP_TRY(ctx, expr)                                                                         \
+/* on failure of `expr`: `dest` = prefix + the HIP error, return RPT_EHIP (dest: the context's error, rpt_create_error() or a string of one call) */
+#define HIP_TRY_TO(dest, prefix, expr)                                                             \
     do {                                                                                           \
         hipError_t e_ = (expr);                                                                    \
         if (e_ != hipSuccess) {                                                                    \
-            (ctx)->error = std::string(#expr) + ": " + hipGetErrorString(e_);                      \
+            (dest) = std::string(prefix) + hipGetErrorString(e_);                                  \
             return RPT_EHIP;                                                                       \
         }                                                                                          \
     } while (0)
+#define HIP_TRY(ctx, expr) HIP_TRY_TO((ctx)->error, #expr ": ", expr)
 
-template <typename T> struct DevBuf {
+/* device (hipMalloc) or pinned host (hipHostMalloc, with its flags) memory */
+struct DeviceMem {
+    static hipError_t get(void **p, size_t bytes, unsigned) { return hipMalloc(p, bytes); }
+    static void put(void *p) { (void)hipFree(p); }
+};
+struct PinnedMem {
+    static hipError_t get(void **p, size_t bytes, unsigned flags) { return hipHostMalloc(p, bytes, flags); }
+    static void put(void *p) { (void)hipHostFree(p); }
+};
+
+/* `n` elements of T that the buffer owns: freed by its destructor, by `release` or by the next `alloc` (which frees BEFORE it allocates, so a
+ * resize never holds both; a failed or empty alloc leaves p == nullptr, n == 0); move-only */
+template <typename T, typename Mem> struct OwnedBuf {
     T *p = nullptr;
     size_t n = 0;
-    hipError_t alloc(size_t count) {
+    OwnedBuf() = default;
+    OwnedBuf(const OwnedBuf &) = delete;
+    OwnedBuf &operator=(const OwnedBuf &) = delete;
+    OwnedBuf(OwnedBuf &&o) noexcept : p(std::exchange(o.p, nullptr)), n(std::exchange(o.n, 0)) {}
+    OwnedBuf &operator=(OwnedBuf &&o) noexcept {
+        if (this != &o) {
+            release();
+            p = std::exchange(o.p, nullptr);
+            n = std::exchange(o.n, 0);
+        }
+        return *this;
+    }
+    ~OwnedBuf() { release(); }
+    hipError_t alloc(size_t count, unsigned flags = 0) {
         release();
-        n = count;
         if (!count) return hipSuccess;
-        return hipMalloc(reinterpret_cast<void **>(&p), count * sizeof(T));
+        const hipError_t e = Mem::get(reinterpret_cast<void **>(&p), count * sizeof(T), flags);
+        if (e != hipSuccess) p = nullptr;
+        else n = count;
+        return e;
     }
     void release() {
-        if (p) (void)hipFree(p);
+        if (p) Mem::put(p);
         p = nullptr;
         n = 0;
     }
+};
+template <typename T> using DevBuf = OwnedBuf<T, DeviceMem>;
+template <typename T> using PinnedBuf = OwnedBuf<T, PinnedMem>;
+
+/* ONE device allocation carved up 256-byte aligned: hipMalloc / hipFree cost 0.1-0.3 ms each, so a call that needs many scratch buffers takes them from one */
+struct Arena {
+    DevBuf<unsigned char> mem;
+    size_t used = 0;
+    static size_t pad(size_t bytes) { return (bytes + 255u) & ~(size_t)255u; }
+    hipError_t reserve(size_t bytes) { used = 0; return mem.alloc(bytes); }
+    template <typename T> T *take(size_t count) { T *p = reinterpret_cast<T *>(mem.p + used); used += pad(count * sizeof(T)); return p; }
 };
 
 constexpr int RPT_RING_LAG = 6;   /* most iterations the host may run ahead of the progress report it inspects (small launches) */
@@ -133,7 +174,7 @@ struct rpt_ctx {
     uint32_t call_samples = 0;  /* n_samples of the current / last rpt_render call (the shade stage of its first iteration derives what a slot owes) */
 
     /* scheduling: the traversal kernel reports each iteration's queue size into mapped pinned memory */
-    unsigned long long *host_ring = nullptr;       /* host view, RING entries */
+    PinnedBuf<unsigned long long> host_ring;       /* host view, RING entries */
     unsigned long long *host_ring_dev = nullptr;   /* device view of the same memory */
 
     /* stats */
@@ -150,8 +191,7 @@ struct rpt_ctx {
     /* read-back and multi-GPU gather (rpt_comm.hip) */
     rpt_comm *comm = nullptr;
     DevBuf<float4> image;                 /* row-major W x H accumulator image (device), built by k_untile */
-    float *host_image = nullptr;          /* pinned twin of it: rpt_read_accum is one DMA */
-    size_t host_image_floats = 0;
+    PinnedBuf<float> host_image;          /* pinned twin of it: rpt_read_accum is one DMA */
     DevBuf<uint32_t> untile_map;          /* rpt_untile: destination map, rebuilt only when (W, H, world, stride) changes */
     uint64_t untile_key = 0;
     uint32_t untile_n = 0;
@@ -166,9 +206,8 @@ void rpt_launch_trace_debug(rpt_ctx *c, bool any_hit, uint32_t n, const float *o
 hipError_t rpt_last_walk_attributes(hipFuncAttributes *out);      /* of k_traverse_nearest_stream<.., LAST>: its static LDS decides whether the flipped copy fits */
 /* rank-local slot order (rpt_hip.hip) */
 void rpt_build_pixel_order(uint32_t W, uint32_t H, uint32_t rank, uint32_t world, std::vector<uint32_t> &out);
-/* rpt_comm.hip: called by rpt_hip.hip when the context / its state goes away */
+/* rpt_comm.hip: called by rpt_hip.hip when the context goes away */
 void rpt_comm_release(rpt_ctx *c);
-void rpt_image_release(rpt_ctx *c);
 std::string &rpt_create_error();
 
 /* RPT_UPLOAD_TIMING=1: host-side section times of rpt_upload_scene / rpt_bvh_build_gpu on stderr (where the start-up time of a large scene goes) */

@@ -179,7 +179,8 @@ void release_state(rpt_ctx *c) {
     c->q_sky.release(); c->q_count.release(); c->ray_shards.release();
     c->sh_o.release(); c->sh_d.release(); c->sh_c.release();
     c->pixel_xy.release();
-    rpt_image_release(c);
+    c->image.release(); c->host_image.release(); c->untile_map.release();
+    c->untile_key = 0;
     c->has_state = false;
 }
 
@@ -487,20 +488,16 @@ __global__ __launch_bounds__(RPT_BLOCK) void k_node_flags(const rpt_bvh_node *no
 static int device_validate_tree(rpt_ctx *c, const rpt_bvh_node *d_nodes, size_t nn, size_t nt, NodeFacts &out) {
     DevBuf<uint32_t> depth_of;
     DevBuf<NodeFacts> facts;
-    hipError_t e = depth_of.alloc(nn);
-    if (e == hipSuccess) e = facts.alloc(1);
-    if (e == hipSuccess) e = hipMemsetAsync(depth_of.p, 0xff, nn * sizeof(uint32_t), nullptr);
-    if (e == hipSuccess) e = hipMemsetAsync(depth_of.p, 0, sizeof(uint32_t), nullptr);              /* the root: depth 0 */
-    if (e == hipSuccess) e = hipMemsetAsync(facts.p, 0, sizeof(NodeFacts), nullptr);
-    if (e == hipSuccess) {
-        const unsigned blocks = (unsigned)((nn + RPT_BLOCK - 1) / RPT_BLOCK);
-        for (uint32_t pass = 0; pass <= 32u; ++pass) k_validate_pass<<<blocks, RPT_BLOCK>>>(d_nodes, (uint32_t)nn, (uint32_t)nt, depth_of.p, pass, facts.p);
-        k_node_flags<<<blocks, RPT_BLOCK>>>(d_nodes, (uint32_t)nn, facts.p);
-        e = hipMemcpy(&out, facts.p, sizeof(out), hipMemcpyDeviceToHost);
-    }
-    if (e == hipSuccess) e = hipGetLastError();
-    depth_of.release(); facts.release();
-    HIP_TRY(c, e);
+    HIP_TRY(c, depth_of.alloc(nn));
+    HIP_TRY(c, facts.alloc(1));
+    HIP_TRY(c, hipMemsetAsync(depth_of.p, 0xff, nn * sizeof(uint32_t), nullptr));
+    HIP_TRY(c, hipMemsetAsync(depth_of.p, 0, sizeof(uint32_t), nullptr));              /* the root: depth 0 */
+    HIP_TRY(c, hipMemsetAsync(facts.p, 0, sizeof(NodeFacts), nullptr));
+    const unsigned blocks = (unsigned)((nn + RPT_BLOCK - 1) / RPT_BLOCK);
+    for (uint32_t pass = 0; pass <= 32u; ++pass) k_validate_pass<<<blocks, RPT_BLOCK>>>(d_nodes, (uint32_t)nn, (uint32_t)nt, depth_of.p, pass, facts.p);
+    k_node_flags<<<blocks, RPT_BLOCK>>>(d_nodes, (uint32_t)nn, facts.p);
+    HIP_TRY(c, hipMemcpy(&out, facts.p, sizeof(out), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipGetLastError());
     if (out.error & 1u) { c->error = "BVH child index out of bounds"; return RPT_ESCENE; }
     if (out.error & 2u) { c->error = "BVH leaf range out of bounds"; return RPT_ESCENE; }
     if (out.error & 4u) { c->error = "BVH is not a tree"; return RPT_ESCENE; }
@@ -625,50 +622,82 @@ static int device_order_probes(rpt_ctx *c, const float *d_cross_sq, uint32_t dep
     const uint32_t nt = c->scene.n_triangles, nn = c->scene.n_nodes, P = nn >= 3u ? (nn - 1u) / 2u : 0u;
     if (nt == 0u || (!lights && !want_last)) { so.probe_ms = lo.probe_ms = clock.ms(); return RPT_OK; }
     if (!pair_shaped || nn < 3u) { if (lights) so.why = "node pool is not pair-shaped"; so.probe_ms = lo.probe_ms = clock.ms(); return RPT_OK; }
+    constexpr const char *WHERE = "order probes: ";               /* prefix of the HIP error messages */
     /* ONE allocation, carved up (five hipMalloc / hipFree pairs were a third of the probe's 5 ms on a 1 M-triangle scene) */
-    DevBuf<unsigned char> arena;
-    auto pad = [](size_t bytes) { return (bytes + 255u) & ~(size_t)255u; };
-    const size_t o_tri = 0, o_sums = o_tri + pad((size_t)nt * sizeof(double)), o_level = o_sums + pad(3 * (size_t)nn * sizeof(double)),
-                 o_flips = o_level + pad((size_t)nn * sizeof(uint32_t)), o_counters = o_flips + pad(3 * (size_t)P), total = o_counters + pad(10 * sizeof(unsigned long long));
-    auto release = [&]() { arena.release(); };
-#define PROBE_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { release(); c->error = std::string("order probes: ") + hipGetErrorString(e_); return RPT_EHIP; } } while (0)
-    PROBE_TRY(arena.alloc(total));
-    struct { double *p; } tri_area{reinterpret_cast<double *>(arena.p + o_tri)}, sums{reinterpret_cast<double *>(arena.p + o_sums)};
-    struct { uint32_t *p; } level{reinterpret_cast<uint32_t *>(arena.p + o_level)};
-    struct { uint8_t *p; } flips{arena.p + o_flips};
-    struct { unsigned long long *p; } counters{reinterpret_cast<unsigned long long *>(arena.p + o_counters)};
-    PROBE_TRY(hipMemsetAsync(counters.p, 0, 10 * sizeof(unsigned long long), nullptr));
-    double *area_all = sums.p, *area_ne = sums.p + nn, *count = sums.p + 2 * (size_t)nn;
+    Arena arena;
+    const size_t bytes = Arena::pad((size_t)nt * sizeof(double)) + Arena::pad(3 * (size_t)nn * sizeof(double)) + Arena::pad((size_t)nn * sizeof(uint32_t)) +
+                         Arena::pad(3 * (size_t)P) + Arena::pad(10 * sizeof(unsigned long long));
+    HIP_TRY_TO(c->error, WHERE, arena.reserve(bytes));
+    double *tri_area = arena.take<double>(nt), *sums = arena.take<double>(3 * (size_t)nn);
+    uint32_t *level = arena.take<uint32_t>(nn);
+    uint8_t *flips = arena.take<uint8_t>(3 * (size_t)P);
+    unsigned long long *counters = arena.take<unsigned long long>(10);
+    HIP_TRY_TO(c->error, WHERE, hipMemsetAsync(counters, 0, 10 * sizeof(unsigned long long), nullptr));
+    double *area_all = sums, *area_ne = sums + nn, *count = sums + 2 * (size_t)nn;
     const View s{reinterpret_cast<const rpt_per_vertex_data *>(c->per_vertex.p), reinterpret_cast<const rpt_triangle *>(c->indices.p),
                  reinterpret_cast<const rpt_bvh_node *>(c->nodes.p), reinterpret_cast<const rpt_material_data *>(c->materials.p), c->light_pick.p, nt, nn,
-                 c->scene.n_light_pick, tri_area.p, area_all, area_ne, count, 0u, 1u, reinterpret_cast<const float4_like *>(c->tri_geom.p)};
+                 c->scene.n_light_pick, tri_area, area_all, area_ne, count, 0u, 1u, reinterpret_cast<const float4_like *>(c->tri_geom.p)};
     const unsigned node_blocks = (nn + RPT_BLOCK - 1) / RPT_BLOCK;
-    k_probe_tri_area<<<(nt + RPT_BLOCK - 1) / RPT_BLOCK, RPT_BLOCK>>>(d_cross_sq, nt, tri_area.p);
-    k_probe_leaves<<<node_blocks, RPT_BLOCK>>>(s, area_all, area_ne, count, level.p);
-    for (uint32_t pass = 1; pass <= depth; ++pass) k_probe_inner<<<node_blocks, RPT_BLOCK>>>(s, area_all, area_ne, count, level.p, pass);
-    uint8_t *flip1 = flips.p, *flip2 = want_last ? flips.p + P : nullptr, *flip3 = want_last ? flips.p + 2 * (size_t)P : nullptr;
+    k_probe_tri_area<<<(nt + RPT_BLOCK - 1) / RPT_BLOCK, RPT_BLOCK>>>(d_cross_sq, nt, tri_area);
+    k_probe_leaves<<<node_blocks, RPT_BLOCK>>>(s, area_all, area_ne, count, level);
+    for (uint32_t pass = 1; pass <= depth; ++pass) k_probe_inner<<<node_blocks, RPT_BLOCK>>>(s, area_all, area_ne, count, level, pass);
+    uint8_t *flip1 = flips, *flip2 = want_last ? flips + P : nullptr, *flip3 = want_last ? flips + 2 * (size_t)P : nullptr;
     k_probe_flips<<<(P + RPT_BLOCK - 1) / RPT_BLOCK, RPT_BLOCK>>>(s, P, flip1, flip2, flip3);
-    if (lights) k_probe_shadow<<<2 * SHADOW_PROBE_RAYS * PROBE_LANES / RPT_WAVE, RPT_WAVE>>>(s, flip1, counters.p);
-    if (want_last) k_probe_last<<<4 * LAST_PROBE_RAYS * PROBE_LANES / RPT_WAVE, RPT_WAVE>>>(s, flip1, flip2, flip3, counters.p);
+    if (lights) k_probe_shadow<<<2 * SHADOW_PROBE_RAYS * PROBE_LANES / RPT_WAVE, RPT_WAVE>>>(s, flip1, counters);
+    if (want_last) k_probe_last<<<4 * LAST_PROBE_RAYS * PROBE_LANES / RPT_WAVE, RPT_WAVE>>>(s, flip1, flip2, flip3, counters);
     unsigned long long h[10];
-    PROBE_TRY(hipMemcpy(h, counters.p, sizeof(h), hipMemcpyDeviceToHost));       /* (waits for the kernels) */
-    PROBE_TRY(hipGetLastError());
+    HIP_TRY_TO(c->error, WHERE, hipMemcpy(h, counters, sizeof(h), hipMemcpyDeviceToHost));       /* (waits for the kernels) */
+    HIP_TRY_TO(c->error, WHERE, hipGetLastError());
     if (lights) {
         decide_shadow(so, h[0], h[1], (uint32_t)h[2], (uint32_t)h[3], c->knobs.shadow_order);
         so.flip.assign(P, 0);
-        if (so.fixed) PROBE_TRY(hipMemcpy(so.flip.data(), flip1, P, hipMemcpyDeviceToHost));
+        if (so.fixed) HIP_TRY_TO(c->error, WHERE, hipMemcpy(so.flip.data(), flip1, P, hipMemcpyDeviceToHost));
     }
     if (want_last) {
         const uint64_t v[4] = {h[4], h[5], h[6], h[7]};
         decide_last(lo, v, (uint32_t)h[8], (uint32_t)h[9], c->knobs.last_order);
         if (lo.rule != 0) {
             lo.flip.assign(P, 0);
-            PROBE_TRY(hipMemcpy(lo.flip.data(), flips.p + (size_t)(lo.rule - 1) * P, P, hipMemcpyDeviceToHost));
+            HIP_TRY_TO(c->error, WHERE, hipMemcpy(lo.flip.data(), flips + (size_t)(lo.rule - 1) * P, P, hipMemcpyDeviceToHost));
         }
     }
-#undef PROBE_TRY
-    release();
+    arena.mem.release();                 /* (inside the probe time, which has always counted the free) */
     so.probe_ms = lo.probe_ms = clock.ms();
+    return RPT_OK;
+}
+
+/* The LDS traversal image of the context's node pool (`flip` null) or of its copy with the pairs `flip` marks flipped, into `dst`.  The primary image goes
+ * up if it fits RPT_LDS_SCENE_BYTES and sets the scene's lds_pairs / lds_vecs / lds_root; a flipped copy only if it has that same size, pairs and root (the
+ * walks address both alike), and only its first `keep` vectors.  `built`: whether `dst` now holds it. */
+static int upload_lds_image(rpt_ctx *c, const rpt_bvh_node *nodes, const std::vector<uint8_t> *flip, const std::vector<float4> &geom, size_t keep,
+                            DevBuf<float4> &dst, bool &built) {
+    DevScene &s = c->scene;
+    const std::vector<rpt_bvh_node> pool = flip ? flipped_nodes(nodes, s.n_nodes, *flip) : std::vector<rpt_bvh_node>();
+    std::vector<float4> image;
+    uint32_t pairs = 0, root = 0;
+    built = build_lds_image(flip ? pool.data() : nodes, s.n_nodes, geom, s.n_triangles, image, pairs, root) &&
+            (flip ? image.size() == (size_t)s.lds_vecs && pairs == s.lds_pairs && root == s.lds_root : image.size() * sizeof(float4) <= RPT_LDS_SCENE_BYTES);
+    if (!built) return RPT_OK;
+    const size_t n = std::min(keep, image.size());
+    HIP_TRY(c, dst.alloc(std::max<size_t>(1, n)));
+    if (n) HIP_TRY(c, hipMemcpy(dst.p, image.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+    if (!flip) { s.lds_pairs = pairs; s.lds_vecs = (uint32_t)image.size(); s.lds_root = root; }
+    return RPT_OK;
+}
+
+/* pair records + links of the streamed global-memory walks (k_traverse.h SceneViewPairsT) over the context's node pool, with the pairs `flip` marks
+ * flipped (null: none) */
+static int build_pair_records(rpt_ctx *c, uint32_t n_pairs, const std::vector<uint8_t> *flip, DevBuf<float4> &pairs, DevBuf<uint32_t> &links) {
+    DevBuf<uint8_t> d_flip;
+    if (flip) {
+        HIP_TRY(c, d_flip.alloc(std::max<size_t>(1, flip->size())));
+        HIP_TRY(c, hipMemcpy(d_flip.p, flip->data(), flip->size(), hipMemcpyHostToDevice));
+    }
+    HIP_TRY(c, pairs.alloc(std::max<size_t>(1, 4 * (size_t)n_pairs)));
+    HIP_TRY(c, links.alloc(c->scene.n_nodes));
+    k_build_pairs<<<(n_pairs + RPT_BLOCK - 1) / RPT_BLOCK, RPT_BLOCK>>>(c->nodes.p, d_flip.p, n_pairs, pairs.p, links.p);
+    if (flip) HIP_TRY(c, hipDeviceSynchronize());          /* (before d_flip is freed) */
+    else HIP_TRY(c, hipGetLastError());
     return RPT_OK;
 }
 
@@ -776,10 +805,14 @@ int rpt_create(int device_id, rpt_ctx **out) {
     c->device = device_id;
     e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) { g_create_error = std::string("hipStreamCreate: ") + hipGetErrorString(e); delete c; return RPT_EHIP; }
-    e = hipHostMalloc(reinterpret_cast<void **>(&c->host_ring), RING * sizeof(unsigned long long), hipHostMallocMapped);
-    if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void **>(&c->host_ring_dev), c->host_ring, 0);
-    if (e != hipSuccess) { g_create_error = std::string("hipHostMalloc(mapped): ") + hipGetErrorString(e); (void)hipStreamDestroy(c->stream); delete c; return RPT_EHIP; }
-    memset(c->host_ring, 0, RING * sizeof(unsigned long long));
+    if ((e = c->host_ring.alloc(RING, hipHostMallocMapped)) != hipSuccess ||
+        (e = hipHostGetDevicePointer(reinterpret_cast<void **>(&c->host_ring_dev), c->host_ring.p, 0)) != hipSuccess) {
+        g_create_error = std::string("hipHostMalloc(mapped): ") + hipGetErrorString(e);
+        (void)hipStreamDestroy(c->stream);
+        delete c;
+        return RPT_EHIP;
+    }
+    memset(c->host_ring.p, 0, RING * sizeof(unsigned long long));
     if (c->dev_stats.alloc(1) != hipSuccess || hipMemsetAsync(c->dev_stats.p, 0, sizeof(DevStats), c->stream) != hipSuccess) {
         g_create_error = "device allocation failed";
         rpt_destroy(c);
@@ -807,19 +840,12 @@ void rpt_destroy(rpt_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    rpt_comm_release(c);
-    release_state(c);
-    c->gpairs.release(); c->glinks.release(); c->lds_image_shadow.release(); c->lds_image_last.release(); c->gpairs_shadow.release(); c->glinks_shadow.release();
-    c->nodes.release(); c->lds_image.release(); c->tri_geom.release(); c->tri_isect.release(); c->tri_shade.release(); c->tri_tangent.release(); c->mat_lite.release();
-    c->per_vertex.release(); c->materials.release();
-    c->indices.release(); c->light_pick.release(); c->light_rec.release(); c->atlas.release(); c->skybox.release();
-    c->dev_stats.release();
+    rpt_comm_release(c);                 /* (destroys the RCCL communicator: before anything else goes) */
     for (hipEvent_t e : c->timing_events) (void)hipEventDestroy(e);
     for (auto &b : c->timing_pending) for (hipEvent_t e : b.ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->timing_pool) (void)hipEventDestroy(e);
-    if (c->host_ring) (void)hipHostFree(c->host_ring);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                            /* (frees every buffer of the context) */
 }
 
 int rpt_set_partition(rpt_ctx *c, uint32_t rank, uint32_t world_size) {
@@ -865,7 +891,6 @@ int rpt_upload_scene(rpt_ctx *c, const rpt_per_vertex_data *pv, size_t nv, const
     /* the node pool goes up first, into a buffer of its own: it is checked on the device (a tree, in range, at most 31 levels: device_validate_tree) before the
      * context's scene is touched — a rejected upload leaves the previous scene in place */
     DevBuf<float4> new_nodes;
-    struct NodesGuard { DevBuf<float4> &b; ~NodesGuard() { b.release(); } } nodes_guard{new_nodes};
     HIP_TRY(c, new_nodes.alloc(2 * nn));
     HIP_TRY(c, hipMemcpy(new_nodes.p, nodes, nn * sizeof(rpt_bvh_node), hipMemcpyHostToDevice));
     NodeFacts facts{};
@@ -910,9 +935,7 @@ int rpt_upload_scene(rpt_ctx *c, const rpt_per_vertex_data *pv, size_t nv, const
         if (mats[i].has_albedo_texture | mats[i].has_metallic_texture | mats[i].has_roughness_texture | mats[i].has_normal_texture) textured = 1;
     }
     sections.mark("derive_host");
-    c->nodes.release();
-    std::swap(c->nodes.p, new_nodes.p);
-    std::swap(c->nodes.n, new_nodes.n);
+    c->nodes = std::move(new_nodes);
     HIP_TRY(c, c->tri_geom.alloc(3 * nt));
     HIP_TRY(c, c->tri_shade.alloc(4 * nt));
     HIP_TRY(c, c->tri_isect.alloc(9 * nt));
@@ -922,8 +945,7 @@ int rpt_upload_scene(rpt_ctx *c, const rpt_per_vertex_data *pv, size_t nv, const
     HIP_TRY(c, c->materials.alloc(6 * nm));
     HIP_TRY(c, c->indices.alloc(nt));
     HIP_TRY(c, c->light_pick.alloc(nlp));
-    DevBuf<float> d_cross_sq;              /* |e1 x e2|^2 per triangle: the order probes' triangle areas (released on every return path below: see CrossSqGuard) */
-    struct CrossSqGuard { DevBuf<float> &b; ~CrossSqGuard() { b.release(); } } cross_sq_guard{d_cross_sq};
+    DevBuf<float> d_cross_sq;              /* |e1 x e2|^2 per triangle: the order probes' triangle areas (freed as soon as they ran) */
     HIP_TRY(c, d_cross_sq.alloc(nt));
     HIP_TRY(c, hipMemcpy(c->per_vertex.p, pv, nv * sizeof(rpt_per_vertex_data), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(c->indices.p, idx, nt * sizeof(rpt_triangle), hipMemcpyHostToDevice));
@@ -976,15 +998,10 @@ int rpt_upload_scene(rpt_ctx *c, const rpt_per_vertex_data *pv, size_t nv, const
     s.n_triangles = (uint32_t)nt;
     s.lds_scene = 0u; s.lds_image = nullptr; s.lds_pairs = s.lds_vecs = s.lds_root = 0u;
     if (lds_candidate) {
-        std::vector<float4> image;
-        uint32_t pairs = 0, root = 0;
-        if (build_lds_image(nodes, nn, geom, nt, image, pairs, root) && image.size() * sizeof(float4) <= RPT_LDS_SCENE_BYTES) {
-            HIP_TRY(c, c->lds_image.alloc(std::max<size_t>(1, image.size())));
-            if (!image.empty())
-                HIP_TRY(c, hipMemcpy(c->lds_image.p, image.data(), image.size() * sizeof(float4), hipMemcpyHostToDevice));
-            s.lds_scene = 1u; s.lds_image = c->lds_image.p;
-            s.lds_pairs = pairs; s.lds_vecs = (uint32_t)image.size(); s.lds_root = root;
-        }
+        bool built = false;
+        rc = upload_lds_image(c, nodes, nullptr, geom, SIZE_MAX, c->lds_image, built);
+        if (rc) return rc;
+        if (built) { s.lds_scene = 1u; s.lds_image = c->lds_image.p; }
     }
     sections.mark("atlas_lds_image");
     if (c->knobs.no_lds_scene) s.lds_scene = 0u;
@@ -993,10 +1010,8 @@ int rpt_upload_scene(rpt_ctx *c, const rpt_per_vertex_data *pv, size_t nv, const
     const bool pair_shaped = (nn & 1u) == 1u && nn >= 3 && nodes[0].triangle_count == 0u && (facts.flags & 2u) == 0u;      /* (= pool_is_pair_shaped(nodes, nn), its per-node conditions from k_node_flags) */
     const uint32_t n_pairs = pair_shaped ? (uint32_t)((nn - 1) / 2) : 0u;
     if (pair_shaped) {
-        HIP_TRY(c, c->gpairs.alloc(std::max<size_t>(1, 4 * (size_t)n_pairs)));
-        HIP_TRY(c, c->glinks.alloc(nn));
-        k_build_pairs<<<(n_pairs + RPT_BLOCK - 1) / RPT_BLOCK, RPT_BLOCK>>>(c->nodes.p, nullptr, n_pairs, c->gpairs.p, c->glinks.p);
-        HIP_TRY(c, hipGetLastError());
+        rc = build_pair_records(c, n_pairs, nullptr, c->gpairs, c->glinks);
+        if (rc) return rc;
         s.gpairs = c->gpairs.p; s.glinks = c->glinks.p;
     } else {
         /* a previous, pair-shaped scene's records are of no use to this one (36 bytes per node of the OLD scene otherwise stay until rpt_destroy) */
@@ -1030,28 +1045,13 @@ int rpt_upload_scene(rpt_ctx *c, const rpt_per_vertex_data *pv, size_t nv, const
     if (c->shadow_order.fixed) {
         bool built = false;
         if (s.lds_scene) {
-            const std::vector<rpt_bvh_node> pool = flipped_nodes(nodes, nn, c->shadow_order.flip);
-            std::vector<float4> image;
-            uint32_t pairs = 0, root = 0;
-            if (build_lds_image(pool.data(), nn, geom, nt, image, pairs, root) && image.size() == (size_t)s.lds_vecs && pairs == s.lds_pairs && root == s.lds_root) {
-                HIP_TRY(c, c->lds_image_shadow.alloc(std::max<size_t>(1, image.size())));
-                HIP_TRY(c, hipMemcpy(c->lds_image_shadow.p, image.data(), image.size() * sizeof(float4), hipMemcpyHostToDevice));
-                s.lds_image_shadow = c->lds_image_shadow.p;
-                built = true;
-            }
+            rc = upload_lds_image(c, nodes, &c->shadow_order.flip, geom, SIZE_MAX, c->lds_image_shadow, built);
+            if (rc) return rc;
+            if (built) s.lds_image_shadow = c->lds_image_shadow.p;
         }
         if (s.gpairs) {
-            DevBuf<uint8_t> d_flip;
-            HIP_TRY(c, d_flip.alloc(std::max<size_t>(1, c->shadow_order.flip.size())));
-            hipError_t e_f = hipMemcpy(d_flip.p, c->shadow_order.flip.data(), c->shadow_order.flip.size(), hipMemcpyHostToDevice);
-            if (e_f == hipSuccess) e_f = c->gpairs_shadow.alloc(std::max<size_t>(1, 4 * (size_t)n_pairs));
-            if (e_f == hipSuccess) e_f = c->glinks_shadow.alloc(nn);
-            if (e_f == hipSuccess) {
-                k_build_pairs<<<(n_pairs + RPT_BLOCK - 1) / RPT_BLOCK, RPT_BLOCK>>>(c->nodes.p, d_flip.p, n_pairs, c->gpairs_shadow.p, c->glinks_shadow.p);
-                e_f = hipDeviceSynchronize();                  /* (d_flip goes out of scope) */
-            }
-            d_flip.release();
-            HIP_TRY(c, e_f);
+            rc = build_pair_records(c, n_pairs, &c->shadow_order.flip, c->gpairs_shadow, c->glinks_shadow);
+            if (rc) return rc;
             s.gpairs_shadow = c->gpairs_shadow.p; s.glinks_shadow = c->glinks_shadow.p;
             built = true;
         }
@@ -1078,15 +1078,10 @@ int rpt_upload_scene(rpt_ctx *c, const rpt_per_vertex_data *pv, size_t nv, const
             }
         }
         if (c->last_order.rule != 0 && ((size_t)s.lds_vecs + flip_vecs) * sizeof(float4) <= lds_room) {
-            const std::vector<rpt_bvh_node> pool = flipped_nodes(nodes, nn, c->last_order.flip);
-            std::vector<float4> image;
-            uint32_t pairs = 0, root = 0;
-            if (build_lds_image(pool.data(), nn, geom, nt, image, pairs, root) && image.size() == (size_t)s.lds_vecs && pairs == s.lds_pairs && root == s.lds_root) {
-                HIP_TRY(c, c->lds_image_last.alloc(std::max<size_t>(1, flip_vecs)));
-                HIP_TRY(c, hipMemcpy(c->lds_image_last.p, image.data(), flip_vecs * sizeof(float4), hipMemcpyHostToDevice));
-                s.lds_image_last = c->lds_image_last.p;
-                s.last_flip_vecs = (uint32_t)flip_vecs;
-            }
+            bool built = false;
+            rc = upload_lds_image(c, nodes, &c->last_order.flip, geom, flip_vecs, c->lds_image_last, built);
+            if (rc) return rc;
+            if (built) { s.lds_image_last = c->lds_image_last.p; s.last_flip_vecs = (uint32_t)flip_vecs; }
         }
         if (!s.lds_image_last) c->last_order.rule = 0;
     }
@@ -1193,18 +1188,14 @@ int rpt_reset(rpt_ctx *c, const rpt_rng_state *seed, const float *accum_init, ui
         DevBuf<uint2> d_seed;
         DevBuf<float4> d_acc;
         HIP_TRY(c, d_seed.alloc(whole));
-        hipError_t e = hipMemcpy(d_seed.p, seed, whole * sizeof(uint2), hipMemcpyHostToDevice);
-        if (e == hipSuccess && accum_init) {
-            e = d_acc.alloc(whole);
-            if (e == hipSuccess) e = hipMemcpy(d_acc.p, accum_init, whole * sizeof(float4), hipMemcpyHostToDevice);
+        HIP_TRY(c, hipMemcpy(d_seed.p, seed, whole * sizeof(uint2), hipMemcpyHostToDevice));
+        if (accum_init) {
+            HIP_TRY(c, d_acc.alloc(whole));
+            HIP_TRY(c, hipMemcpy(d_acc.p, accum_init, whole * sizeof(float4), hipMemcpyHostToDevice));
         }
-        if (e == hipSuccess) {
-            k_reset_gather<<<(unsigned)((n + RPT_BLOCK - 1) / RPT_BLOCK), RPT_BLOCK, 0, c->stream>>>(c->pixel_xy.p, (uint32_t)n, W, d_seed.p, d_acc.p, c->rng.p, c->accum.p);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);             /* (the staging buffers go out of scope) */
-        d_seed.release(); d_acc.release();
-        HIP_TRY(c, e);
+        k_reset_gather<<<(unsigned)((n + RPT_BLOCK - 1) / RPT_BLOCK), RPT_BLOCK, 0, c->stream>>>(c->pixel_xy.p, (uint32_t)n, W, d_seed.p, d_acc.p, c->rng.p, c->accum.p);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipStreamSynchronize(c->stream));             /* (before the staging buffers are freed) */
     }
     HIP_TRY(c, hipMemsetAsync(c->dev_stats.p, 0, sizeof(DevStats), c->stream));
     HIP_TRY(c, hipMemsetAsync(c->ray_shards.p, 0, RPT_STAT_SHARDS * RPT_STAT_STRIDE * sizeof(unsigned long long), c->stream));
@@ -1306,7 +1297,7 @@ static int render_impl(rpt_ctx *c, uint32_t n_samples, bool allow_async) {
         if (rc) return rc;
     }
 
-    if (!async) for (int k = 0; k < RING; ++k) __atomic_store_n(&c->host_ring[k], 0ull, __ATOMIC_RELAXED);
+    if (!async) for (int k = 0; k < RING; ++k) __atomic_store_n(&c->host_ring.p[k], 0ull, __ATOMIC_RELAXED);
     c->call_samples = n_samples;
     /* A miss ends its path (lib.rs:79) and in a batch of known length nothing is started in its place: the misses of all iterations
      * wait in the queue for ONE sky launch after the last iteration (three launches less per batch) */
@@ -1376,7 +1367,7 @@ static int render_impl(rpt_ctx *c, uint32_t n_samples, bool allow_async) {
         if (known_iterations == 0 && it >= (uint64_t)lag) {
             /* the sky kernel of iteration j published (j + 1) << 32 | "work remains after iteration j" */
             uint64_t j = it - lag;
-            volatile unsigned long long *slot = &c->host_ring[j & (RING - 1)];
+            volatile unsigned long long *slot = &c->host_ring.p[j & (RING - 1)];
             unsigned long long v;
             uint64_t spins = 0;
             while (((v = *slot) >> 32) != ((j + 1) & 0xffffffffull)) {
@@ -1500,16 +1491,14 @@ int rpt_resolve(rpt_ctx *c, uint32_t tonemap_op, float *out_rgb) {
     const size_t n_out = (size_t)c->cfg.c.width * c->cfg.c.height * 3;
     DevBuf<float> dev;
     HIP_TRY(c, dev.alloc(n_out));
-    hipError_t e = hipMemsetAsync(dev.p, 0, n_out * sizeof(float), c->stream);
-    if (e == hipSuccess && c->n_pixels) {
+    HIP_TRY(c, hipMemsetAsync(dev.p, 0, n_out * sizeof(float), c->stream));
+    if (c->n_pixels) {
         k_resolve<<<(c->n_pixels + RPT_BLOCK - 1) / RPT_BLOCK, RPT_BLOCK, 0, c->stream>>>(c->accum.p, c->pixel_xy.p, c->n_pixels, c->cfg.c.width,
                                                                                       (float)c->samples, tonemap_op, dev.p);
-        e = hipGetLastError();
+        HIP_TRY(c, hipGetLastError());
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(out_rgb, dev.p, n_out * sizeof(float), hipMemcpyDeviceToHost);
-    dev.release();
-    HIP_TRY(c, e);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(out_rgb, dev.p, n_out * sizeof(float), hipMemcpyDeviceToHost));
     return RPT_OK;
 }
 
@@ -1540,47 +1529,33 @@ int rpt_debug_short_batch(rpt_ctx *c, int on) {
     return RPT_OK;
 }
 
+/* the operations of the math hooks: one statement for the kernel and for the host build of rpt_math.h (clang's, as tests/test_math.py needs) */
+RPT_HD float debug_math_op(int op, float x, float y) {
+    switch (op) {
+        case 0: return rptm::sinr(x);
+        case 1: return rptm::cosr(x);
+        case 2: return rptm::acosr(x);
+        case 3: return rptm::expr(x);
+        case 4: return rptm::powr(x, y);
+        case 5: return rptm::asinr(x);
+        case 6: return rptm::atan2r(x, y);
+        case 7: return rptm::sqrtr(x);
+        case 9: return rptm::slab_quotient(x, 0.0f, y);
+        case 10: return rptm::exp_sky(x);
+        case 11: return rptm::unorm8(x);
+        default: return x / y;
+    }
+}
+
 __global__ void k_debug_math(int op, const float *x, const float *y, float *out, size_t n) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    float r;
-    switch (op) {
-        case 0: r = rptm::sinr(x[i]); break;
-        case 1: r = rptm::cosr(x[i]); break;
-        case 2: r = rptm::acosr(x[i]); break;
-        case 3: r = rptm::expr(x[i]); break;
-        case 4: r = rptm::powr(x[i], y[i]); break;
-        case 5: r = rptm::asinr(x[i]); break;
-        case 6: r = rptm::atan2r(x[i], y[i]); break;
-        case 7: r = rptm::sqrtr(x[i]); break;
-        case 9: r = rptm::slab_quotient(x[i], 0.0f, y[i]); break;
-        case 10: r = rptm::exp_sky(x[i]); break;
-        case 11: r = rptm::unorm8(x[i]); break;
-        default: r = x[i] / y[i]; break;
-    }
-    out[i] = r;
+    out[i] = debug_math_op(op, x[i], y[i]);
 }
 
 int rpt_debug_math_host(int op, const float *x, const float *y, float *out, size_t n) {
     if (op < 0 || op > 11 || !x || !y || !out) return RPT_EINVAL;
-    for (size_t i = 0; i < n; ++i) {
-        float r;
-        switch (op) {
-            case 0: r = rptm::sinr(x[i]); break;
-            case 1: r = rptm::cosr(x[i]); break;
-            case 2: r = rptm::acosr(x[i]); break;
-            case 3: r = rptm::expr(x[i]); break;
-            case 4: r = rptm::powr(x[i], y[i]); break;
-            case 5: r = rptm::asinr(x[i]); break;
-            case 6: r = rptm::atan2r(x[i], y[i]); break;
-            case 7: r = rptm::sqrtr(x[i]); break;
-            case 9: r = rptm::slab_quotient(x[i], 0.0f, y[i]); break;
-            case 10: r = rptm::exp_sky(x[i]); break;
-            case 11: r = rptm::unorm8(x[i]); break;
-            default: r = x[i] / y[i]; break;
-        }
-        out[i] = r;
-    }
+    for (size_t i = 0; i < n; ++i) out[i] = debug_math_op(op, x[i], y[i]);
     return RPT_OK;
 }
 
@@ -1589,15 +1564,11 @@ int rpt_debug_math(rpt_ctx *c, int op, const float *x, const float *y, float *ou
     HIP_TRY(c, hipSetDevice(c->device));
     DevBuf<float> dx, dy, dout;
     HIP_TRY(c, dx.alloc(n)); HIP_TRY(c, dy.alloc(n)); HIP_TRY(c, dout.alloc(n));
-    hipError_t e = hipMemcpy(dx.p, x, n * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dy.p, y, n * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        k_debug_math<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(op, dx.p, dy.p, dout.p, n);
-        e = hipStreamSynchronize(c->stream);
-    }
-    if (e == hipSuccess) e = hipMemcpy(out, dout.p, n * 4, hipMemcpyDeviceToHost);
-    dx.release(); dy.release(); dout.release();
-    HIP_TRY(c, e);
+    HIP_TRY(c, hipMemcpy(dx.p, x, n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(dy.p, y, n * 4, hipMemcpyHostToDevice));
+    k_debug_math<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(op, dx.p, dy.p, dout.p, n);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(out, dout.p, n * 4, hipMemcpyDeviceToHost));
     return RPT_OK;
 }
 
@@ -1627,14 +1598,10 @@ int rpt_debug_math_sweep(rpt_ctx *c, int op, uint32_t lo_bits, uint64_t count, f
     DevBuf<unsigned long long> d;
     HIP_TRY(c, d.alloc(2));
     unsigned long long h[2] = {0ull, 0xffffffffull};
-    hipError_t e = hipMemcpy(d.p, h, sizeof(h), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        k_debug_math_sweep<<<4096, 256, 0, c->stream>>>(op, lo_bits, (unsigned long long)count, y, 1.0f / y, d.p);
-        e = hipStreamSynchronize(c->stream);
-    }
-    if (e == hipSuccess) e = hipMemcpy(h, d.p, sizeof(h), hipMemcpyDeviceToHost);
-    d.release();
-    HIP_TRY(c, e);
+    HIP_TRY(c, hipMemcpy(d.p, h, sizeof(h), hipMemcpyHostToDevice));
+    k_debug_math_sweep<<<4096, 256, 0, c->stream>>>(op, lo_bits, (unsigned long long)count, y, 1.0f / y, d.p);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(h, d.p, sizeof(h), hipMemcpyDeviceToHost));
     *mismatches_out = h[0];
     if (first_bad_bits_out) *first_bad_bits_out = (uint32_t)h[1];
     return RPT_OK;
@@ -1646,14 +1613,10 @@ int rpt_debug_bsdf(rpt_ctx *c, int kind, size_t n, const float *in, float *out) 
     HIP_TRY(c, hipSetDevice(c->device));
     DevBuf<float> din, dout;
     HIP_TRY(c, din.alloc(16 * n)); HIP_TRY(c, dout.alloc(8 * n));
-    hipError_t e = hipMemcpy(din.p, in, 64 * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        k_debug_bsdf<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(kind, n, din.p, dout.p);
-        e = hipStreamSynchronize(c->stream);
-    }
-    if (e == hipSuccess) e = hipMemcpy(out, dout.p, 32 * n, hipMemcpyDeviceToHost);
-    din.release(); dout.release();
-    HIP_TRY(c, e);
+    HIP_TRY(c, hipMemcpy(din.p, in, 64 * n, hipMemcpyHostToDevice));
+    k_debug_bsdf<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(kind, n, din.p, dout.p);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(out, dout.p, 32 * n, hipMemcpyDeviceToHost));
     return RPT_OK;
 }
 
@@ -1667,19 +1630,14 @@ int rpt_debug_trace_rays(rpt_ctx *c, int any_hit, size_t n, const float *origins
     DevBuf<uint32_t> d_tri, d_fl;
     HIP_TRY(c, d_o.alloc(3 * n)); HIP_TRY(c, d_d.alloc(3 * n)); HIP_TRY(c, d_m.alloc(n)); HIP_TRY(c, d_t.alloc(n));
     HIP_TRY(c, d_tri.alloc(n)); HIP_TRY(c, d_fl.alloc(n));
-    hipError_t e = hipMemcpy(d_o.p, origins, 12 * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_d.p, dirs, 12 * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess && max_t) e = hipMemcpy(d_m.p, max_t, 4 * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipStream_t s = c->stream;
-        rpt_launch_trace_debug(c, any_hit != 0, (uint32_t)n, d_o.p, d_d.p, d_m.p, d_t.p, d_tri.p, d_fl.p);
-        e = hipStreamSynchronize(s);
-    }
-    if (e == hipSuccess) e = hipMemcpy(out_t, d_t.p, 4 * n, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(out_tri, d_tri.p, 4 * n, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(out_flags, d_fl.p, 4 * n, hipMemcpyDeviceToHost);
-    d_o.release(); d_d.release(); d_m.release(); d_t.release(); d_tri.release(); d_fl.release();
-    HIP_TRY(c, e);
+    HIP_TRY(c, hipMemcpy(d_o.p, origins, 12 * n, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d_d.p, dirs, 12 * n, hipMemcpyHostToDevice));
+    if (max_t) HIP_TRY(c, hipMemcpy(d_m.p, max_t, 4 * n, hipMemcpyHostToDevice));
+    rpt_launch_trace_debug(c, any_hit != 0, (uint32_t)n, d_o.p, d_d.p, d_m.p, d_t.p, d_tri.p, d_fl.p);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(out_t, d_t.p, 4 * n, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(out_tri, d_tri.p, 4 * n, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(out_flags, d_fl.p, 4 * n, hipMemcpyDeviceToHost));
     return RPT_OK;
 }
 
@@ -1716,15 +1674,13 @@ int rpt_debug_trace_rays_production(rpt_ctx *c, size_t n, const float *origins, 
     k_debug_load_rays<<<(unsigned)((n + RPT_BLOCK - 1) / RPT_BLOCK), RPT_BLOCK, 0, s>>>(c->state, (uint32_t)n, d_o.p, d_d.p);
     rpt_launch_nearest(c, 0u, false, false);
     std::vector<float2> hits(n);
-    hipError_t e = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(hits.data(), c->hit.p, n * sizeof(float2), hipMemcpyDeviceToHost);
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpy(hits.data(), c->hit.p, n * sizeof(float2), hipMemcpyDeviceToHost));
     /* back to "nothing in flight" */
-    if (e == hipSuccess) e = hipMemsetAsync(c->q_count.p, 0, Q_WORDS * sizeof(uint32_t), s);
+    HIP_TRY(c, hipMemsetAsync(c->q_count.p, 0, Q_WORDS * sizeof(uint32_t), s));
     k_fill_idle<<<(c->n_slots + RPT_BLOCK - 1) / RPT_BLOCK, RPT_BLOCK, 0, s>>>(c->hit.p, c->n_slots);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    d_o.release(); d_d.release();
-    HIP_TRY(c, e);
+    HIP_TRY(c, hipStreamSynchronize(s));
     for (size_t i = 0; i < n; ++i) {
         uint32_t w;
         memcpy(&w, &hits[i].y, 4);

@@ -39,20 +39,6 @@ namespace {
 
 constexpr int LT_BLOCK = 256;
 
-/* the device memory of one call: ONE allocation per phase (hipMalloc / hipFree cost 0.1-0.3 ms each — seventeen of them were a fifth of a
- * 1 M-triangle build), carved up 256-byte aligned, released on every way out */
-struct Arena {
-    char *base = nullptr;
-    size_t size = 0, used = 0;
-    Arena() = default;
-    Arena(const Arena &) = delete;
-    Arena &operator=(const Arena &) = delete;
-    ~Arena() { if (base) (void)hipFree(base); }
-    static size_t pad(size_t bytes) { return (bytes + 255u) & ~(size_t)255u; }
-    hipError_t reserve(size_t bytes) { size = bytes; used = 0; return hipMalloc(reinterpret_cast<void **>(&base), bytes ? bytes : 256); }
-    template <typename T> T *take(size_t count) { T *p = reinterpret_cast<T *>(base + used); used += pad(count * sizeof(T)); return p; }
-};
-
 /* ---- stable LSD radix sort of (u32 key, u32 value) pairs: four passes over 8-bit digits, 1 024 pairs per workgroup ----------------------------------------
  * pass: k_rs_count (digits of a workgroup's tile) -> k_rs_scan (exclusive scan over [digit][workgroup]: where every tile's pairs of every digit go) -> k_rs_scatter
  * (tile in order, four rounds of 256: a pair's rank among the equal digits before it = lanes before it in its wave (ballots per digit bit), waves before it in the
@@ -249,6 +235,7 @@ extern "C" int rpt_light_table_build_gpu(int device_id, const float *vertices_xy
                                          const rpt_material_data *materials, size_t n_materials, rpt_light_pick_entry *entries_out, size_t entries_capacity,
                                          size_t *n_entries_out, uint32_t *n_emissive_out, double *ms_out /* nullable, 4 doubles: total, device passes, host chains, transfers */) {
     std::string &err = rpt_create_error();
+    constexpr const char *WHERE = "rpt_light_table_build_gpu: ";  /* prefix of the HIP error messages */
     if (!vertices_xyzw || !triangles || !materials || !entries_out || !n_entries_out || n_vertices == 0 || n_materials == 0 || entries_capacity == 0) {
         err = "rpt_light_table_build_gpu: null or empty argument";
         return RPT_EINVAL;
@@ -276,17 +263,12 @@ extern "C" int rpt_light_table_build_gpu(int device_id, const float *vertices_xy
     };
     if (n_triangles == 0) return sentinel(0u);
 
-#define LT_TRY(x)                                                                                       \
-    do {                                                                                                \
-        hipError_t e_ = (x);                                                                            \
-        if (e_ != hipSuccess) { err = std::string("rpt_light_table_build_gpu: ") + hipGetErrorString(e_); return RPT_EHIP; } \
-    } while (0)
     const uint32_t nt = (uint32_t)n_triangles, nb = (nt + LT_BLOCK - 1) / LT_BLOCK;
-    Arena phase1, phase2;
-    LT_TRY(hipSetDevice(device_id));
+    Arena phase1, phase2;               /* the device memory of the call: ONE allocation per phase (seventeen hipMalloc were a fifth of a 1 M-triangle build) */
+    HIP_TRY_TO(err, WHERE, hipSetDevice(device_id));
     std::vector<float4> emissive(n_materials);
     for (size_t m = 0; m < n_materials; ++m) emissive[m] = make_float4(materials[m].emissive[0], materials[m].emissive[1], materials[m].emissive[2], 0.0f);
-    LT_TRY(phase1.reserve(Arena::pad(n_vertices * sizeof(float4)) + Arena::pad((size_t)nt * sizeof(uint4)) + Arena::pad(n_materials * sizeof(float4)) +
+    HIP_TRY_TO(err, WHERE, phase1.reserve(Arena::pad(n_vertices * sizeof(float4)) + Arena::pad((size_t)nt * sizeof(uint4)) + Arena::pad(n_materials * sizeof(float4)) +
                           3 * Arena::pad((size_t)nt * sizeof(float)) + Arena::pad((size_t)nb * sizeof(uint32_t)) + Arena::pad(sizeof(LtScalars))));
     struct { float4 *p; } d_verts{phase1.take<float4>(n_vertices)}, d_emissive{nullptr};
     struct { uint4 *p; } d_tris{phase1.take<uint4>(nt)};
@@ -297,19 +279,19 @@ extern "C" int rpt_light_table_build_gpu(int device_id, const float *vertices_xy
     struct { rpt_light_pick_entry *p; } d_out{nullptr};
     struct { char *p; } d_tmp{nullptr};
     auto t0 = std::chrono::steady_clock::now();
-    LT_TRY(hipMemcpy(d_verts.p, vertices_xyzw, n_vertices * sizeof(float4), hipMemcpyHostToDevice));
-    LT_TRY(hipMemcpy(d_tris.p, triangles, (size_t)nt * sizeof(uint4), hipMemcpyHostToDevice));
-    LT_TRY(hipMemcpy(d_emissive.p, emissive.data(), n_materials * sizeof(float4), hipMemcpyHostToDevice));
-    LT_TRY(hipMemset(d_sc.p, 0, sizeof(LtScalars)));
+    HIP_TRY_TO(err, WHERE, hipMemcpy(d_verts.p, vertices_xyzw, n_vertices * sizeof(float4), hipMemcpyHostToDevice));
+    HIP_TRY_TO(err, WHERE, hipMemcpy(d_tris.p, triangles, (size_t)nt * sizeof(uint4), hipMemcpyHostToDevice));
+    HIP_TRY_TO(err, WHERE, hipMemcpy(d_emissive.p, emissive.data(), n_materials * sizeof(float4), hipMemcpyHostToDevice));
+    HIP_TRY_TO(err, WHERE, hipMemset(d_sc.p, 0, sizeof(LtScalars)));
     ms_transfer += since(t0);
 
     k_lt_power<<<nb, LT_BLOCK>>>(d_verts.p, d_tris.p, d_emissive.p, nt, d_area.p, d_power.p, d_sc.p);
     LtScalars sc;
     std::vector<float> power(nt);
     t0 = std::chrono::steady_clock::now();
-    LT_TRY(hipMemcpy(&sc, d_sc.p, sizeof(sc), hipMemcpyDeviceToHost));
+    HIP_TRY_TO(err, WHERE, hipMemcpy(&sc, d_sc.p, sizeof(sc), hipMemcpyDeviceToHost));
     if (sc.total_tris == 0u) return sentinel(0u);
-    LT_TRY(hipMemcpy(power.data(), d_power.p, (size_t)nt * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY_TO(err, WHERE, hipMemcpy(power.data(), d_power.p, (size_t)nt * sizeof(float), hipMemcpyDeviceToHost));
     ms_transfer += since(t0);
     /* steps 2 and 4 (:39-51, :59-64): both sums in index order (the 0.0 of a non-emissive triangle changes nothing: the sums are never -0.0) */
     t0 = std::chrono::steady_clock::now();
@@ -323,22 +305,22 @@ extern "C" int rpt_light_table_build_gpu(int device_id, const float *vertices_xy
         sc.average = prob_sum / (float)sc.total_tris;
     }
     ms_fill += since(t0);
-    LT_TRY(hipMemcpy(d_sc.p, &sc, sizeof(sc), hipMemcpyHostToDevice));
+    HIP_TRY_TO(err, WHERE, hipMemcpy(d_sc.p, &sc, sizeof(sc), hipMemcpyHostToDevice));
     k_lt_prob<<<nb, LT_BLOCK>>>(d_power.p, nt, d_prob.p, d_sc.p, d_counts.p);
     k_lt_scan<<<1, 1024>>>(d_counts.p, nb, d_sc.p);
-    LT_TRY(hipMemcpy(&sc, d_sc.p, sizeof(sc), hipMemcpyDeviceToHost));
+    HIP_TRY_TO(err, WHERE, hipMemcpy(&sc, d_sc.p, sizeof(sc), hipMemcpyDeviceToHost));
     if (sc.has_nan) { err = "rpt_light_table_build_gpu: a pick probability is NaN (NaN vertex, or a total power of 0 / inf): such a scene must be built by the host builder"; return RPT_ESCENE; }
     const uint32_t n = sc.n_bins;
     if (n == 0u) return sentinel(sc.total_tris);       /* every emissive triangle is degenerate: the reference would index bins[usize::MAX] and panic */
     if ((size_t)n > entries_capacity) { err = "rpt_light_table_build_gpu: the table needs " + std::to_string(n) + " entries"; return RPT_EINVAL; }
     const size_t tmp_bytes = lt_sort_tmp_bytes(n);
-    LT_TRY(phase2.reserve(7 * Arena::pad((size_t)n * sizeof(uint32_t)) + Arena::pad((size_t)n * sizeof(rpt_light_pick_entry)) + Arena::pad(tmp_bytes ? tmp_bytes : 1)));
+    HIP_TRY_TO(err, WHERE, phase2.reserve(7 * Arena::pad((size_t)n * sizeof(uint32_t)) + Arena::pad((size_t)n * sizeof(rpt_light_pick_entry)) + Arena::pad(tmp_bytes ? tmp_bytes : 1)));
     d_keys.p = phase2.take<uint32_t>(n); d_keys2.p = phase2.take<uint32_t>(n); d_vals.p = phase2.take<uint32_t>(n); d_vals2.p = phase2.take<uint32_t>(n);
     d_pa.p = phase2.take<float>(n); d_pb.p = phase2.take<float>(n); d_ib.p = phase2.take<uint32_t>(n);
     d_out.p = phase2.take<rpt_light_pick_entry>(n);
     d_tmp.p = phase2.take<char>(tmp_bytes ? tmp_bytes : 1);
     k_lt_bins<<<nb, LT_BLOCK>>>(d_prob.p, nt, d_counts.p, d_keys.p, d_vals.p);
-    LT_TRY(lt_radix_sort_pairs(reinterpret_cast<uint32_t *>(d_tmp.p), d_keys.p, d_keys2.p, d_vals.p, d_vals2.p, n));   /* stable; sorted pairs in (d_keys, d_vals) */
+    HIP_TRY_TO(err, WHERE, lt_radix_sort_pairs(reinterpret_cast<uint32_t *>(d_tmp.p), d_keys.p, d_keys2.p, d_vals.p, d_vals2.p, n));   /* stable; sorted pairs in (d_keys, d_vals) */
     const uint32_t nbn = (n + LT_BLOCK - 1) / LT_BLOCK;
     k_lt_unkey<<<nbn, LT_BLOCK>>>(d_keys.p, n, d_pa.p);
 
@@ -346,8 +328,8 @@ extern "C" int rpt_light_table_build_gpu(int device_id, const float *vertices_xy
     std::vector<float> pa(n), pb(n, 0.0f);
     std::vector<uint32_t> ia(n), ib(n, 0u);
     t0 = std::chrono::steady_clock::now();
-    LT_TRY(hipMemcpy(pa.data(), d_pa.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    LT_TRY(hipMemcpy(ia.data(), d_vals.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY_TO(err, WHERE, hipMemcpy(pa.data(), d_pa.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY_TO(err, WHERE, hipMemcpy(ia.data(), d_vals.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     ms_transfer += since(t0);
     t0 = std::chrono::steady_clock::now();
     {
@@ -367,18 +349,17 @@ extern "C" int rpt_light_table_build_gpu(int device_id, const float *vertices_xy
     }
     ms_fill += since(t0);
     t0 = std::chrono::steady_clock::now();
-    LT_TRY(hipMemcpy(d_pa.p, pa.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-    LT_TRY(hipMemcpy(d_pb.p, pb.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-    LT_TRY(hipMemcpy(d_ib.p, ib.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY_TO(err, WHERE, hipMemcpy(d_pa.p, pa.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY_TO(err, WHERE, hipMemcpy(d_pb.p, pb.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY_TO(err, WHERE, hipMemcpy(d_ib.p, ib.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
     ms_transfer += since(t0);
     k_lt_table<<<nbn, LT_BLOCK>>>(d_pa.p, d_pb.p, d_vals.p, d_ib.p, d_area.p, d_prob.p, n, d_out.p);
-    LT_TRY(hipGetLastError());
+    HIP_TRY_TO(err, WHERE, hipGetLastError());
     t0 = std::chrono::steady_clock::now();
-    LT_TRY(hipMemcpy(entries_out, d_out.p, (size_t)n * sizeof(rpt_light_pick_entry), hipMemcpyDeviceToHost));
+    HIP_TRY_TO(err, WHERE, hipMemcpy(entries_out, d_out.p, (size_t)n * sizeof(rpt_light_pick_entry), hipMemcpyDeviceToHost));
     ms_transfer += since(t0);           /* (includes the wait for k_lt_table) */
     *n_entries_out = n;
     if (n_emissive_out) *n_emissive_out = sc.total_tris;
     if (ms_out) { ms_out[0] = since(t_begin); ms_out[2] = ms_fill; ms_out[3] = ms_transfer; ms_out[1] = ms_out[0] - ms_fill - ms_transfer; }
-#undef LT_TRY
     return RPT_OK;
 }

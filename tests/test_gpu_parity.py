@@ -1197,18 +1197,49 @@ def test_contexts_on_different_threads(hipmod, oracle, rpt, world):
 
 def test_contexts_can_be_destroyed_with_work_in_flight_and_leak_nothing(hipmod, rpt, world):
     """rpt_destroy with an asynchronous batch (and a gather) still in flight completes it first; 60 create / upload /
-    configure / render / destroy cycles give every byte of device memory back."""
+    configure / render / destroy cycles give every byte of device memory back — refused calls among them (a node pool that is
+    not a tree, a NaN vertex for the device BVH and light-table builds) included, each refused after it allocated.  Every
+    cycle's own allocations are megabytes (a 120 k-node pool, 20 k-triangle builds, 64 k debug rays): a leak on any of these
+    paths would pass the 8 MiB bound within a few cycles."""
+    import copy
+    import importlib
     import torch
+    from scenes import scatter_scene
     w = world("DarkCornell")
     W, H = 256, 192
     cfg = rpt.default_config(W, H, nee=1)
     seeds = rpt.blue_noise_seeds(W, H)
+    big = scatter_scene()                                       # > 120 000 nodes
+    not_a_tree = copy.copy(big)
+    not_a_tree.nodes = big.nodes.copy()
+    not_a_tree.nodes["left_or_first"][int(np.nonzero(big.nodes["triangle_count"] == 0)[0][1])] = 0     # a cycle through the root
+    rng = np.random.default_rng(3)
+    n = 20_000
+    soup_v = np.concatenate([rng.normal(size=(3 * n, 3)).astype(np.float32), np.ones((3 * n, 1), np.float32)], 1)
+    soup_v[5, 1] = np.nan
+    soup_t = np.zeros(n, importlib.import_module("rust-path-tracer_amd._ffi").TRIANGLE_DTYPE)
+    idx = np.arange(3 * n, dtype=np.uint32).reshape(n, 3)
+    soup_t["v0"], soup_t["v1"], soup_t["v2"] = idx[:, 0], idx[:, 1], idx[:, 2]
+    m = w.materials
+    emitter = m[np.nonzero(np.any(m["emissive"][:, :3] != 0, axis=1))[0][:1]]    # every soup triangle emits: the NaN one included
+    origins = np.zeros((1 << 16, 3), np.float32)
+    dirs = rng.normal(size=(1 << 16, 3)).astype(np.float32)
+    dirs /= np.linalg.norm(dirs, axis=1, keepdims=True)
 
     def cycle(k):
         r = hipmod.Renderer(0)
         if k % 3 == 0:
             r.comm_init_local()
-        r.upload_scene(w); r.set_config(cfg); r.reset(seeds)
+        with pytest.raises(hipmod.RptError) as e:
+            r.upload_scene(not_a_tree)
+        assert e.value.code == -5 and "BVH" in str(e.value), str(e.value)          # (refused by the device check of the pool)
+        with pytest.raises(hipmod.RptError, match="NaN"):
+            hipmod.bvh_build_gpu(soup_v, soup_t.copy())
+        with pytest.raises(hipmod.RptError, match="NaN"):
+            hipmod.light_table_build_gpu(soup_v, soup_t, emitter)
+        r.upload_scene(w)
+        r.debug_trace_rays(False, origins, dirs)
+        r.set_config(cfg); r.reset(seeds)
         r.render_async(8)
         if k % 3 == 0:
             r.gather_async()
