@@ -122,7 +122,7 @@ struct DevScene {
     DevImage atlas, skybox;
 };
 
-/* constants of the traversal structures that the upload code (rpt_hip.hip) and the walk kernels (k_traverse.h, compiled in rpt_traverse.hip) share */
+/* constants of the traversal structures that the upload code (rpt_scene.hip) and the walk kernels (k_traverse.h, compiled in rpt_traverse.hip) share */
 #define LDS_DESC_DEAD 0x4000u      /* 16-bit child descriptor of the LDS image (k_traverse.h SceneViewLds): pair index, or LEAF | count << 9 | first triangle */
 #define LDS_DESC_LEAF 0x8000u
 #define RPT_LDS_SCENE_BYTES 32768  /* a traversal image up to this size lives in LDS (+ 32 KB of 16-bit stacks = the 64 KB of one of two workgroups per CU) */

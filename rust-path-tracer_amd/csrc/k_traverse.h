@@ -241,7 +241,7 @@ struct SceneViewPairsT {
     }
 };
 
-/* The LDS-resident image of a small scene, built once at upload (rpt_hip.hip, build_lds_image) and copied into
+/* The LDS-resident image of a small scene, built once at upload (rpt_scene.hip, build_lds_image) and copied into
  * LDS by every workgroup.  Measured on MI355X (tools/microbench/valu_rates.hip, SQ counters in profiles/): the
  * traversal kernel is VALU-ISSUE bound — fma/mul/add issue in ~2 cycles per wave64 instruction, everything else
  * (min/max, compares, selects, integer/address ops) in ~4 — so the image is laid out to delete instructions:
@@ -893,7 +893,7 @@ __global__ __launch_bounds__(THREADS) void k_traverse_nearest_stream(DevScene sc
     if (LAST)
         for (uint32_t k = threadIdx.x; k < sc.last_flip_vecs; k += THREADS) lds_scene[sc.lds_vecs + k] = sc.lds_image_last[k];
     if (FIRST) {
-        const uint32_t P2 = 2u * sc.lds_pairs;                 /* image layout (rpt_hip.hip build_lds_image): 2 P plane records per axis, x | y | z */
+        const uint32_t P2 = 2u * sc.lds_pairs;                 /* image layout (rpt_scene.hip build_lds_image): 2 P plane records per axis, x | y | z */
         for (uint32_t k = threadIdx.x; k < 3u * P2; k += THREADS) {
             const float4 v = sc.lds_image[k];
             const float o = k < P2 ? cam_x : (k < 2u * P2 ? cam_y : cam_z);

@@ -1,6 +1,7 @@
 /*
  * rpt_ctx.h — the context object behind the C ABI of include/rpt/rpt.h, shared by the translation units of
- * librpt_hip.so (rpt_hip.hip: upload + wavefront scheduling; rpt_comm.hip: multi-GPU gather over RCCL, read-back).
+ * librpt_hip.so (rpt_hip.hip: life cycle, state and wavefront scheduling; rpt_scene.hip: scene preparation; rpt_traverse.hip: the traversal stages;
+ * rpt_comm.hip: multi-GPU gather over RCCL, read-back; rpt_debug.hip: test hooks).
  */
 #ifndef RPT_CTX_H
 #define RPT_CTX_H
@@ -19,15 +20,10 @@
 #include "shadow_order.h"
 
 /* on failure of `expr`: `dest` = prefix + the HIP error, return RPT_EHIP (dest: the context's error, rpt_create_error() or a string of one call) */
-#define HIP_TRY_TO(dest, prefix, expr)                                                             \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            (dest) = std::string(prefix) + hipGetErrorString(e_);                                  \
-            return RPT_EHIP;                                                                       \
-        }                                                                                          \
-    } while (0)
+#define HIP_TRY_TO(dest, prefix, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (dest) = std::string(prefix) + hipGetErrorString(e_); return RPT_EHIP; } } while (0)
 #define HIP_TRY(ctx, expr) HIP_TRY_TO((ctx)->error, #expr ": ", expr)
+/* an RPT_* code other than RPT_OK from `expr` (which has stated the error itself) ends the caller with it */
+#define RPT_TRY(expr) do { const int rc_ = (expr); if (rc_) return rc_; } while (0)
 
 /* device (hipMalloc) or pinned host (hipHostMalloc, with its flags) memory */
 struct DeviceMem {
@@ -65,6 +61,11 @@ template <typename T, typename Mem> struct OwnedBuf {
         else n = count;
         return e;
     }
+    /* alloc(count) + the copy of that many elements' bytes from host memory (complete when it returns) */
+    hipError_t from_host(const void *src, size_t count) {
+        const hipError_t e = alloc(count);
+        return e != hipSuccess || !count ? e : hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice);
+    }
     void release() {
         if (p) Mem::put(p);
         p = nullptr;
@@ -74,6 +75,9 @@ template <typename T, typename Mem> struct OwnedBuf {
 template <typename T> using DevBuf = OwnedBuf<T, DeviceMem>;
 template <typename T> using PinnedBuf = OwnedBuf<T, PinnedMem>;
 
+/* workgroups of RPT_BLOCK threads that cover n items */
+constexpr unsigned rpt_blocks(size_t n) { return (unsigned)((n + RPT_BLOCK - 1) / RPT_BLOCK); }
+
 /* ONE device allocation carved up 256-byte aligned: hipMalloc / hipFree cost 0.1-0.3 ms each, so a call that needs many scratch buffers takes them from one */
 struct Arena {
     DevBuf<unsigned char> mem;
@@ -81,6 +85,46 @@ struct Arena {
     static size_t pad(size_t bytes) { return (bytes + 255u) & ~(size_t)255u; }
     hipError_t reserve(size_t bytes) { used = 0; return mem.alloc(bytes); }
     template <typename T> T *take(size_t count) { T *p = reinterpret_cast<T *>(mem.p + used); used += pad(count * sizeof(T)); return p; }
+};
+
+/* RPT_STAGE_TIMING: HIP events between the stage kernels, read into rpt_stats.kernel_ms once the stream has been drained.  Every event is recorded
+ * together with the stage that the time SINCE THE PREVIOUS EVENT belongs to (NONE: a starting mark, the time before it is nobody's), so reading them is one
+ * loop over consecutive pairs whatever the level, the number of iterations, and whether one batch or several asynchronous ones were recorded.  A mark names
+ * the levels it is taken at: level 1 = after every stage kernel, level 2 = only around the traversal kernel.  The events are the timer's own: read ones are
+ * kept for the next batch, all are destroyed with it — while the context's device is current (rpt_destroy calls clear() itself, before it destroys the stream). */
+struct StageTimer {
+    static constexpr int NONE = -1, AT_1 = 1, AT_2 = 2;
+    struct Mark { hipEvent_t event; int stage; };
+    int level = 0;                              /* 0 off, AT_1, AT_2 */
+    std::vector<Mark> recorded;                 /* not read yet, in stream order */
+    std::vector<hipEvent_t> idle;
+    hipError_t create_error = hipSuccess;       /* a failed hipEventCreate: marks stop until take_error() has reported it */
+    StageTimer() = default;
+    StageTimer(const StageTimer &) = delete;             /* (the events have one owner) */
+    ~StageTimer() { clear(); }
+    void mark(hipStream_t stream, int stage, int levels) {
+        if ((levels & level) == 0 || create_error != hipSuccess) return;
+        hipEvent_t e;
+        if (idle.empty()) { if ((create_error = hipEventCreate(&e)) != hipSuccess) return; }
+        else { e = idle.back(); idle.pop_back(); }
+        (void)hipEventRecord(e, stream);
+        recorded.push_back(Mark{e, stage});
+    }
+    hipError_t take_error() { return std::exchange(create_error, hipSuccess); }
+    /* after the stream has been synchronised */
+    void read_into(double *kernel_ms) {
+        float ms;
+        for (size_t k = 0; k < recorded.size(); ++k) {
+            if (k != 0 && recorded[k].stage != NONE && hipEventElapsedTime(&ms, recorded[k - 1].event, recorded[k].event) == hipSuccess) kernel_ms[recorded[k].stage] += ms;
+            idle.push_back(recorded[k].event);
+        }
+        recorded.clear();
+    }
+    void clear() {
+        for (const Mark &m : recorded) (void)hipEventDestroy(m.event);
+        for (hipEvent_t e : idle) (void)hipEventDestroy(e);
+        recorded.clear(); idle.clear();
+    }
 };
 
 constexpr int RPT_RING_LAG = 6;   /* most iterations the host may run ahead of the progress report it inspects (small launches) */
@@ -179,13 +223,7 @@ struct rpt_ctx {
 
     /* stats */
     rpt_stats stats{};
-    bool stage_timing = false;
-    int timing_level = 0;           /* RPT_STAGE_TIMING: 1 = an event after every stage kernel, 2 = only around the traversal kernel */
-    std::vector<hipEvent_t> timing_events;
-    /* batches enqueued by rpt_render_async whose stage timing has not been read back yet */
-    struct TimingBatch { std::vector<hipEvent_t> ev; uint64_t iterations; bool complete_timed; };
-    std::vector<TimingBatch> timing_pending;
-    std::vector<hipEvent_t> timing_pool;
+    StageTimer timing;              /* RPT_STAGE_TIMING (rpt_destroy empties it before the stream goes) */
     bool async_pending = false;
 
     /* read-back and multi-GPU gather (rpt_comm.hip) */
@@ -204,6 +242,10 @@ void rpt_launch_shadow(rpt_ctx *c);
 void rpt_launch_trace_debug(rpt_ctx *c, bool any_hit, uint32_t n, const float *origins, const float *dirs, const float *max_t, float *out_t, uint32_t *out_tri,
                             uint32_t *out_flags);
 hipError_t rpt_last_walk_attributes(hipFuncAttributes *out);      /* of k_traverse_nearest_stream<.., LAST>: its static LDS decides whether the flipped copy fits */
+/* rpt_hip.hip, for the production-trace hook of rpt_debug.hip: the per-slot arrays for a call over `n` slots (grown, never shrunk), and "nothing in
+ * flight" on the context's stream — queue counters zeroed, every slot of the current call idle (k_fill_idle is compiled in rpt_hip.hip only) */
+int ensure_slot_state(rpt_ctx *c, size_t n, bool need_shadow, bool need_mis);
+int rpt_idle_all_slots(rpt_ctx *c);
 /* rank-local slot order (rpt_hip.hip) */
 void rpt_build_pixel_order(uint32_t W, uint32_t H, uint32_t rank, uint32_t world, std::vector<uint32_t> &out);
 /* rpt_comm.hip: called by rpt_hip.hip when the context goes away */
@@ -216,10 +258,7 @@ struct SectionTimer {
     const char *title;
     std::chrono::steady_clock::time_point last;
     std::string line;
-    explicit SectionTimer(const char *t) : on(false), title(t) {
-        on = rpt_read_knobs().upload_timing;
-        last = std::chrono::steady_clock::now();
-    }
+    explicit SectionTimer(const char *t) : on(rpt_read_knobs().upload_timing), title(t), last(std::chrono::steady_clock::now()) {}
     void mark(const char *name) {
         if (!on) return;
         const auto now = std::chrono::steady_clock::now();

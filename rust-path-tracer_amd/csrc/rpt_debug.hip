@@ -1,0 +1,164 @@
+/*
+ * rpt_debug.hip — the test hooks of include/rpt/rpt_debug.h that run kernels of their own: the math functions, the BSDF
+ * pieces and single rays through the debug and the production traversal stages.
+ */
+#include <cstring>
+
+#include "rpt_ctx.h"
+#include "rpt_fastdiv.h"
+#include "k_bsdf_extra.h"
+
+extern "C" {
+
+/* the operations of the math hooks: one statement for the kernel and for the host build of rpt_math.h (clang's, as tests/test_math.py needs) */
+RPT_HD float debug_math_op(int op, float x, float y) {
+    switch (op) {
+        case 0: return rptm::sinr(x);
+        case 1: return rptm::cosr(x);
+        case 2: return rptm::acosr(x);
+        case 3: return rptm::expr(x);
+        case 4: return rptm::powr(x, y);
+        case 5: return rptm::asinr(x);
+        case 6: return rptm::atan2r(x, y);
+        case 7: return rptm::sqrtr(x);
+        case 9: return rptm::slab_quotient(x, 0.0f, y);
+        case 10: return rptm::exp_sky(x);
+        case 11: return rptm::unorm8(x);
+        default: return x / y;
+    }
+}
+
+__global__ void k_debug_math(int op, const float *x, const float *y, float *out, size_t n) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = debug_math_op(op, x[i], y[i]);
+}
+
+int rpt_debug_math_host(int op, const float *x, const float *y, float *out, size_t n) {
+    if (op < 0 || op > 11 || !x || !y || !out) return RPT_EINVAL;
+    for (size_t i = 0; i < n; ++i) out[i] = debug_math_op(op, x[i], y[i]);
+    return RPT_OK;
+}
+
+int rpt_debug_math(rpt_ctx *c, int op, const float *x, const float *y, float *out, size_t n) {
+    if (!c || op < 0 || op > 11 || !x || !y || !out) return RPT_EINVAL;
+    HIP_TRY(c, hipSetDevice(c->device));
+    DevBuf<float> dx, dy, dout;
+    HIP_TRY(c, dx.from_host(x, n)); HIP_TRY(c, dy.from_host(y, n)); HIP_TRY(c, dout.alloc(n));
+    k_debug_math<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(op, dx.p, dy.p, dout.p, n);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(out, dout.p, n * 4, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+
+/* Exhaustive check of a cheap exact operation against its IEEE form, over the bit patterns [lo_bits, lo_bits + count):
+ * op 0: rptm::sqrtr == the compiler's correctly rounded sqrtf (trivially, today: the hook experiments with cheaper roots used); op 1: rptm::div_const_nontiny(x, y, RN(1 / y)) == x / y;
+ * op 2: rptm::f2i32_sat (one v_cvt_i32_f32) == Rust's `f32 as i32` written out with its branches (results compared as bit patterns). */
+__global__ void k_debug_math_sweep(int op, uint32_t lo_bits, unsigned long long count, float y, float ry, unsigned long long *out) {
+    unsigned long long bad = 0ull;
+    uint32_t first = 0xffffffffu;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (unsigned long long)gridDim.x * blockDim.x) {
+        const uint32_t bits = lo_bits + (uint32_t)i;
+        const float x = rptm::u2f(bits);
+        const float fast = op == 0 ? rptm::sqrtr(x) : (op == 1 ? rptm::div_const_nontiny(x, y, ry) : rptm::u2f((uint32_t)rptm::f2i32_sat(x)));
+        const float ieee = op == 0 ? __builtin_sqrtf(x) : (op == 1 ? x / y : rptm::u2f((uint32_t)rptm::f2i32_sat_reference(x)));
+        const bool same = rptm::f2u(fast) == rptm::f2u(ieee) || (op != 2 && fast != fast && ieee != ieee);     /* (op 2 carries integers: bit patterns only) */
+        if (!same) { bad += 1ull; first = first < bits ? first : bits; }
+    }
+    if (bad != 0ull) {
+        atomicAdd(&out[0], bad);
+        atomicMin(&out[1], (unsigned long long)first);
+    }
+}
+
+int rpt_debug_math_sweep(rpt_ctx *c, int op, uint32_t lo_bits, uint64_t count, float y, uint64_t *mismatches_out, uint32_t *first_bad_bits_out) {
+    if (!c || op < 0 || op > 2 || !mismatches_out || count > 0x100000000ull) return RPT_EINVAL;
+    HIP_TRY(c, hipSetDevice(c->device));
+    DevBuf<unsigned long long> d;
+    HIP_TRY(c, d.alloc(2));
+    unsigned long long h[2] = {0ull, 0xffffffffull};
+    HIP_TRY(c, hipMemcpy(d.p, h, sizeof(h), hipMemcpyHostToDevice));
+    k_debug_math_sweep<<<4096, 256, 0, c->stream>>>(op, lo_bits, (unsigned long long)count, y, 1.0f / y, d.p);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(h, d.p, sizeof(h), hipMemcpyDeviceToHost));
+    *mismatches_out = h[0];
+    if (first_bad_bits_out) *first_bad_bits_out = (uint32_t)h[1];
+    return RPT_OK;
+}
+
+int rpt_debug_bsdf(rpt_ctx *c, int kind, size_t n, const float *in, float *out) {
+    if (!c || kind < 0 || kind > 3 || !in || !out) return RPT_EINVAL;
+    if (n == 0) return RPT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    DevBuf<float> din, dout;
+    HIP_TRY(c, din.from_host(in, 16 * n)); HIP_TRY(c, dout.alloc(8 * n));
+    k_debug_bsdf<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(kind, n, din.p, dout.p);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(out, dout.p, 32 * n, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+
+int rpt_debug_trace_rays(rpt_ctx *c, int any_hit, size_t n, const float *origins, const float *dirs, const float *max_t,
+                         float *out_t, uint32_t *out_tri, uint32_t *out_flags) {
+    if (!c || !origins || !dirs || !out_t || !out_tri || !out_flags || (any_hit && !max_t)) return RPT_EINVAL;
+    if (!c->has_scene) { c->error = "no scene"; return RPT_EINVAL; }
+    if (n == 0) return RPT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    DevBuf<float> d_o, d_d, d_m, d_t;
+    DevBuf<uint32_t> d_tri, d_fl;
+    HIP_TRY(c, d_o.from_host(origins, 3 * n)); HIP_TRY(c, d_d.from_host(dirs, 3 * n)); HIP_TRY(c, d_t.alloc(n));
+    HIP_TRY(c, d_tri.alloc(n)); HIP_TRY(c, d_fl.alloc(n));
+    HIP_TRY(c, max_t ? d_m.from_host(max_t, n) : d_m.alloc(n));
+    rpt_launch_trace_debug(c, any_hit != 0, (uint32_t)n, d_o.p, d_d.p, d_m.p, d_t.p, d_tri.p, d_fl.p);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(out_t, d_t.p, 4 * n, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(out_tri, d_tri.p, 4 * n, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(out_flags, d_fl.p, 4 * n, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+
+/* The same question through the PRODUCTION nearest-hit stage: the rays are written into the context's own slots as pending
+ * extension rays, the traversal stage is launched exactly as an iteration of rpt_render launches it for this scene and state
+ * (launch_nearest: persistent LDS stream / streamed global-memory walk with or without cooperative leaves / one-shot kernels,
+ * per the developer knobs), and the hit records it wrote are read back.  Needs a configuration (the slots); leaves the
+ * context as after rpt_reset with nothing rendered — call rpt_reset before rendering again. */
+__global__ __launch_bounds__(RPT_BLOCK) void k_debug_load_rays(DevState st, uint32_t n, const float *origins, const float *dirs) {
+    const uint32_t i = blockIdx.x * RPT_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    st.ray_a[i] = make_float4(origins[3 * i], origins[3 * i + 1], origins[3 * i + 2], dirs[3 * i]);
+    st.ray_b[i] = make_float2(dirs[3 * i + 1], dirs[3 * i + 2]);
+    st.hit[i] = make_float2(0.0f, __uint_as_float(HIT_PENDING));
+}
+
+int rpt_debug_trace_rays_production(rpt_ctx *c, size_t n, const float *origins, const float *dirs, float *out_t, uint32_t *out_tri, uint32_t *out_flags) {
+    if (!c || !origins || !dirs || !out_t || !out_tri || !out_flags) return RPT_EINVAL;
+    if (!c->has_scene || !c->has_state) { c->error = "rpt_debug_trace_rays_production: needs a scene and a configuration"; return RPT_EINVAL; }
+    if (n == 0) return RPT_OK;
+    if (n > c->n_slots) { c->error = "rpt_debug_trace_rays_production: more rays than the context has slots (" + std::to_string(c->n_slots) + ")"; return RPT_EINVAL; }
+    RPT_TRY(rpt_wait(c));
+    HIP_TRY(c, hipSetDevice(c->device));
+    RPT_TRY(ensure_slot_state(c, c->n_slots, false, false));
+    DevBuf<float> d_o, d_d;
+    HIP_TRY(c, d_o.from_host(origins, 3 * n)); HIP_TRY(c, d_d.from_host(dirs, 3 * n));
+    hipStream_t s = c->stream;
+    RPT_TRY(rpt_idle_all_slots(c));
+    k_debug_load_rays<<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(c->state, (uint32_t)n, d_o.p, d_d.p);
+    rpt_launch_nearest(c, 0u, false, false);
+    std::vector<float2> hits(n);
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpy(hits.data(), c->hit.p, n * sizeof(float2), hipMemcpyDeviceToHost));
+    RPT_TRY(rpt_idle_all_slots(c));             /* back to "nothing in flight" */
+    HIP_TRY(c, hipStreamSynchronize(s));
+    for (size_t i = 0; i < n; ++i) {
+        uint32_t w;
+        memcpy(&w, &hits[i].y, 4);
+        if (w == HIT_PENDING || w == HIT_IDLE) { c->error = "rpt_debug_trace_rays_production: ray " + std::to_string(i) + " was not traversed"; return RPT_EHIP; }
+        out_t[i] = hits[i].x;
+        out_tri[i] = (w == HIT_MISS) ? 0u : (w & 0x7fffffffu);
+        out_flags[i] = (w == HIT_MISS) ? 0u : (1u | ((w >> 31) << 1));
+    }
+    return RPT_OK;
+}
+
+}  // extern "C"

@@ -51,7 +51,7 @@
 #define SHADOW_PROBE_RAYS 4096     /* candidates; about half survive the "decides something" filter */
 #define SHADOW_FIXED_GAIN 0.95
 #define LAST_PROBE_RAYS 1024
-#define ORDER_PROBE_STACK 32       /* a validated pool is at most 31 levels deep (rpt_hip.hip validate_scene; intersection.rs:178) */
+#define ORDER_PROBE_STACK 32       /* a validated pool is at most 31 levels deep (rpt_scene.hip validate_scene; intersection.rs:178) */
 
 struct ShadowOrder {
     bool fixed = false;                 /* walk the flipped tree left-first */
@@ -111,7 +111,7 @@ RPT_HD bool emissive(const View &s, uint32_t t) {
     const float *e = s.mats[s.idx[t].material].emissive;
     return e[0] != 0.0f || e[1] != 0.0f || e[2] != 0.0f;
 }
-/* |(b - a) x (c - a)|^2 of a triangle, as rpt_hip.hip k_derive_triangles hands it out */
+/* |(b - a) x (c - a)|^2 of a triangle, as rpt_scene.hip k_derive_triangles hands it out */
 RPT_HD float triangle_cross_sq(const rpt_per_vertex_data *pv, const rpt_triangle &t) {
     const V a = vtx(pv[t.v0]), e1 = sub(vtx(pv[t.v1]), a), e2 = sub(vtx(pv[t.v2]), a);
     const float cx = e1.y * e2.z - e1.z * e2.y, cy = e1.z * e2.x - e1.x * e2.z, cz = e1.x * e2.y - e1.y * e2.x;
@@ -383,7 +383,7 @@ struct Clock {
 
 }  // namespace order_probe
 
-/* Host driver.  Expects a validated scene (rpt_hip.hip validate_scene: links in range, no cycles, leaf ranges inside the index buffer).  `pair_shaped`: children of
+/* Host driver.  Expects a validated scene (rpt_scene.hip validate_scene: links in range, no cycles, leaf ranges inside the index buffer).  `pair_shaped`: children of
  * every inner node are the nodes (2p + 1, 2p + 2) of one pair — what the flipped copies can express; otherwise near-first stays. */
 inline ShadowOrder choose_shadow_order(const rpt_per_vertex_data *pv, const rpt_triangle *idx, size_t nt, const rpt_bvh_node *nodes, size_t nn,
                                        const rpt_material_data *mats, const rpt_light_pick_entry *lp, size_t nlp, bool pair_shaped,

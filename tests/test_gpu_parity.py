@@ -429,9 +429,11 @@ def test_camera_rays_walk_planes_with_the_origin_already_subtracted(hipmod, orac
     assert np.array_equal(acc_g.view(np.uint32), acc_c.view(np.uint32))
 
 
-def test_the_library_chooses_the_order_of_the_last_rays_per_scene(monkeypatch, hipmod, rpt, world):
+def test_the_library_chooses_the_order_of_the_last_rays_per_scene(monkeypatch, hipmod, oracle, rpt, world):
     """rpt_last_bounce_order after rpt_upload_scene: DarkCornell (two emissive triangles, lives in LDS) walks those rays in a fixed order its probe favoured;
-    a scene that does not live in LDS keeps the whole walk; the decision is the host probe's (rpt_debug_last_order_host) and is re-taken on every upload."""
+    a scene that does not live in LDS keeps the whole walk; the decision is the host probe's (rpt_debug_last_order_host) and is re-taken on every upload.
+    The scene without flipped copies, uploaded into the context that just held one with all of them, renders the oracle's image: nothing of the previous
+    scene's optional structures is left bound."""
     monkeypatch.delenv("RPT_LAST_ORDER", raising=False)
     r = hipmod.Renderer(0)
     try:
@@ -441,8 +443,19 @@ def test_the_library_chooses_the_order_of_the_last_rays_per_scene(monkeypatch, h
         assert lo["mode"] == 1 + host["rule"] >= 2 and lo["emissive_triangles"] == 2 and lo["probe_rays"] == host["probe_rays"] > 500
         v = lo["probe_node_visits"]
         assert list(v.values()) == host["visits"] and min(list(v.values())[1:]) < 0.95 * v["near child first"]
+        assert r.shadow_order()["fixed"]
         r.upload_scene(world("PBRTest"))
-        assert r.last_bounce_order()["mode"] == 0
+        assert r.last_bounce_order()["mode"] == 0 and not r.shadow_order()["fixed"]
+        for W, H, spp, nee, over in [(128, 128, 2, 0, {}), (128, 96, 2, 1, {"min_bounces": 0, "max_bounces": 3})]:      # (PBRTest's two CASES)
+            cfg = rpt.default_config(W, H, nee=nee, **over)
+            seeds = rpt.blue_noise_seeds(W, H)
+            r.set_config(cfg); r.reset(seeds)
+            r.render(spp)
+            acc_g, _ = r.read_accum()
+            st_g = r.stats()
+            acc_c, _, st_c = oracle.trace_cpu(cfg, oracle.scene(world("PBRTest")), seeds, spp)
+            assert st_g["extension_rays"] == st_c.extension_rays and st_g["shadow_rays"] == st_c.shadow_rays and st_g["sky_evals"] == st_c.sky_evals
+            assert np.array_equal(acc_g.view(np.uint32), acc_c.view(np.uint32))
         r.upload_scene(world("DarkCornell"))
         assert r.last_bounce_order()["mode"] == lo["mode"]
     finally:
