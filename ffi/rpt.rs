@@ -23,6 +23,8 @@ pub const RPT_ESCENE: c_int = -5;
 pub const RPT_ENOMEM: c_int = -6;
 pub const RPT_COMM_ID_BYTES: usize = 128;
 pub const RPT_MULTI_ALLOW_SHARED_DEVICE: u32 = 1;
+pub const RPT_SHADOW_EXACT: u32 = 0;
+pub const RPT_SHADOW_SEGMENT: u32 = 1;
 
 #[repr(C)] pub struct rpt_ctx { _private: [u8; 0] }
 #[repr(C)] pub struct rpt_multi { _private: [u8; 0] }
@@ -51,6 +53,8 @@ extern "C" {
                                      materials: *const MaterialData, n_materials: usize, entries_out: *mut LightPickEntry, entries_capacity: usize,
                                      n_entries_out: *mut usize, n_emissive_out: *mut u32, ms_out: *mut f64) -> c_int;   // build_light_pick_table, src/light_pick.rs:24-122
     pub fn rpt_shadow_order(ctx: *mut rpt_ctx, fixed_out: *mut u32, visits_near_out: *mut f64, visits_fixed_out: *mut f64, probe_rays_out: *mut u32, probe_ms_out: *mut f64) -> c_int;   // which (bit-exact) order the shadow walks use
+    pub fn rpt_set_shadow_mode(ctx: *mut rpt_ctx, mode: u32) -> c_int;             // RPT_SHADOW_EXACT (default, the reference's any-hit walk) | RPT_SHADOW_SEGMENT (opt-in: boxes behind max_t are not entered)
+    pub fn rpt_shadow_mode(ctx: *mut rpt_ctx, mode_out: *mut u32) -> c_int;
     pub fn rpt_last_bounce_order(ctx: *mut rpt_ctx, mode_out: *mut u32, n_emissive_triangles_out: *mut u32, visits_out: *mut f64, probe_rays_out: *mut u32, probe_ms_out: *mut f64) -> c_int;   // how the last extension rays of a batch without NEE are walked
 
     // --- one GPU: what trace_gpu needs (each line: the reference call it replaces) -------------------------------
@@ -88,6 +92,7 @@ extern "C" {
         skybox_rgba32f: *const f32, sky_w: u32, sky_h: u32) -> c_int;
     pub fn rpt_multi_set_config(m: *mut rpt_multi, config: *const TracingConfig) -> c_int;
     pub fn rpt_multi_reset(m: *mut rpt_multi, rng_seed: *const UVec2, accum_init: *const Vec4, samples_init: u32) -> c_int;
+    pub fn rpt_multi_set_shadow_mode(m: *mut rpt_multi, mode: u32) -> c_int;       // rpt_set_shadow_mode on every rank
     pub fn rpt_multi_render(m: *mut rpt_multi, n_samples: u32) -> c_int;            // one batch on every GPU + the batch's single RCCL gather
     pub fn rpt_multi_wait(m: *mut rpt_multi) -> c_int;
     pub fn rpt_multi_read_accum(m: *mut rpt_multi, out: *mut Vec4, out_samples: *mut u32) -> c_int;   // the whole W x H image, from rank 0

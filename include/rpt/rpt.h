@@ -231,6 +231,7 @@ int rpt_multi_upload_scene(rpt_multi *m,
                            const float *skybox_rgba32f, uint32_t sky_w, uint32_t sky_h);
 int rpt_multi_set_config(rpt_multi *m, const rpt_tracing_config *config);
 int rpt_multi_reset(rpt_multi *m, const rpt_rng_state *rng_seed, const float *accum_init_rgba, uint32_t samples_init);
+int rpt_multi_set_shadow_mode(rpt_multi *m, uint32_t mode);  /* rpt_set_shadow_mode (below) on every rank */
 int rpt_multi_render(rpt_multi *m, uint32_t n_samples);
 int rpt_multi_wait(rpt_multi *m);
 int rpt_multi_read_accum(rpt_multi *m, float *out_rgba, uint32_t *out_samples);
@@ -253,6 +254,32 @@ int rpt_device_info(int device_id, uint32_t *compute_units_out, uint32_t *clock_
  * so the library may choose: fixed_out = 0 the reference's near-first order, 1 a fixed opaque-first order over a flipped copy of the tree —
  * chosen at rpt_upload_scene by the node visits of synthetic shadow rays under both (csrc/shadow_order.h).  The image is the same either way. */
 int rpt_shadow_order(rpt_ctx *ctx, uint32_t *fixed_out, double *visits_near_out, double *visits_fixed_out, uint32_t *probe_rays_out, double *probe_ms_out);
+/* Which any-hit walk the shadow rays of the batches enqueued from now on take.  Opt-in: the default, what bench.py measures and what every parity
+ * statement of this header is about, is RPT_SHADOW_EXACT.
+ *   RPT_SHADOW_EXACT    the reference's walk: boxes are pruned against result.t, which stays 1e6 until the first accept (intersection.rs:212-213), so an
+ *                       unoccluded shadow ray enters every box on its line to the far wall.  `.hit` is the reference's, bit for bit.
+ *   RPT_SHADOW_SEGMENT  a child box is entered iff the reference's test passes (tmax >= tmin && tmax > 0 && tmin < 1e6, intersection.rs:117) AND
+ *                       tmin <= max_t, max_t being the ray's own bound, the distance to the light point (light_pick.rs:141).  Nothing else changes: the triangle
+ *                       accept test (t > 0.001 && t < 1e6 && t <= max_t), the root (never box-tested), which rays are elided, the ray counts of rpt_stats.
+ *                       For max_t >= 1e6 it is the exact walk.
+ * Pruning only removes boxes, so a SEGMENT hit implies the reference's: an occlusion is never gained.  One can be lost, and the image differ from the
+ * reference's, only through a triangle whose computed t <= max_t lies in a box whose computed tmin > max_t (box-t and triangle-t round differently).  On the
+ * CPU model (tools/anyhit_order_sim.cpp sim_any_hit_segment) that happened for 0 of 10^6 adversarial rays over the four shipped scenes (tests/test_shadow_segment.py)
+ * and for 0 of the 12.0 M shadow rays two samples per pixel of DarkCornell 1024^2 and VeachMIS 1080p trace; the same model prices the walk at 40-50 % fewer
+ * wave-instructions per shadow ray (profiles/r10_anyhit_sim_segment.txt).
+ * Measured on one MI355X at 32 samples per pixel (tools/shadow_mode_ab.py, profiles/r10_shadow_segment_ab.txt; bench.py's figures are the EXACT mode's):
+ *   DarkCornell 1024^2 MIS   batch 20.5 -> 18.5 ms (-10 %), shadow stage 5.99 -> 3.76 ms    0 accumulator words differ (115 M shadow rays)
+ *   VeachMIS 1080p MIS       batch 28.9 -> 24.8 ms (-14 %), shadow stage 9.01 -> 4.56 ms    30 words = 10 of 2.07 M pixels differ (77 M shadow rays)
+ *   1 M-triangle stand-in    batch 324.7 -> 318.6 ms (-2 %), shadow stage 118.7 -> 112.6    12 words = 4 of 4.2 M pixels differ (397 M shadow rays)
+ * A pixel that differs lost one occlusion in 32 samples: it is brighter by one NEE term — VeachMIS's ten by 0.005 - 0.3 % of their value, more than the per-pixel
+ * 1e-4 of BASELINE.md's contract at those pixels; every other pixel is the EXACT image bit for bit, and each of the ten is a pixel where the CPU model of the rule
+ * loses the same occlusion (tests/test_gpu_shadow_segment.py, profiles/r10_shadow_segment_parity.txt; the stand-in's four were counted, not traced back).  So: inside the contract except at a handful of pixels per million,
+ * outside the bit-for-bit one.
+ * Callable at any time between batches: nothing is reallocated, the accumulator stays valid, batches already enqueued keep the mode they were enqueued
+ * with.  Any other value: RPT_EINVAL, the mode stays.  There is no environment variable for it: those (rpt_knobs) never change a result. */
+enum { RPT_SHADOW_EXACT = 0, RPT_SHADOW_SEGMENT = 1 };
+int rpt_set_shadow_mode(rpt_ctx *ctx, uint32_t mode);
+int rpt_shadow_mode(rpt_ctx *ctx, uint32_t *mode_out);
 /* How the LAST extension rays of a batch of known length are walked when the configuration has no NEE.  At bounce max_bounces - 1 the reference reads three
  * things off intersect_nearest (kernels/src/lib.rs:62-109): a miss adds the sky, a hit on the front of an emissive triangle adds its emission, any other hit
  * adds nothing — so a ray that passes the Moller-Trumbore test of no emissive triangle only has to answer "hit or miss", which the reference's own walk

@@ -39,7 +39,9 @@ int rpt_debug_math_sweep(rpt_ctx *ctx, int op, uint32_t lo_bits, uint64_t count,
                          uint32_t *first_bad_bits_out);
 /* Trace n rays through the uploaded BVH on the device. any_hit = 0: nearest
  * (kernels/src/intersection.rs:169-171) ; 1: any-hit with max_t
- * (:173-175).  Outputs per ray: t, triangle_index, flags (bit0 hit, bit1 backface). */
+ * (:173-175) ; 2: the segment-bounded any-hit walk of RPT_SHADOW_SEGMENT (rpt.h
+ * rpt_set_shadow_mode: a child box is entered only if also tmin <= max_t), through the
+ * same one-ray-per-lane kernel, .hit is what it answers.  Outputs per ray: t, triangle_index, flags (bit0 hit, bit1 backface). */
 int rpt_debug_trace_rays(rpt_ctx *ctx, int any_hit, size_t n,
                          const float *origins_xyz, const float *dirs_xyz, const float *max_t,
                          float *out_t, uint32_t *out_tri, uint32_t *out_flags);

@@ -22,7 +22,7 @@
  * + intersection.rs:173-234 with NEAREST_HIT = false) must match the reference in
  * `.hit` ONLY — light_pick.rs:148 reads nothing else: result.t stays 1e6 until the
  * first accept, which returns (:191-203), boxes are pruned against that constant
- * (:212-213: no "max_t" box pruning), so the set of boxes a ray may enter and with
+ * (:212-213: no "max_t" box pruning in the exact walk; the opt-in SEGMENT walks, shadow_segment_bound below, add it), so the set of boxes a ray may enter and with
  * it `.hit` are independent of the order siblings are visited in.  FIXED = true
  * walks a copy of the tree whose pairs were flipped at upload (shadow_order.h: the
  * preferred child in the left slot) left-first: no `tl > tr`, no swap.
@@ -365,9 +365,24 @@ __device__ __forceinline__ typename View::Cur walk_pop(const View &view, uint32_
     }
 }
 
-template <int STACK, bool ANY_HIT, bool FAST, bool FIXED = false, typename View, typename StackRef>
+/* RPT_SHADOW_SEGMENT (rpt.h rpt_set_shadow_mode), the opt-in any-hit walk that is NOT the reference's: a child box is entered iff the reference's test
+ * passes AND tmin <= max_t — a shadow ray is a segment, and only triangles with t <= max_t can be accepted, so boxes that begin behind the light point
+ * are left out.  The SEGMENT instantiations of the walks take this bound in the place of max_t: the value every t of the ray is compared against,
+ *     tmin <= max_t  <=>  tmin < bound     and     t < 1e6 && t <= max_t  <=>  t < bound
+ * (bound = the float after max_t, or 1e6 from max_t = 1e6 on, where the mode is the reference's walk; a NaN max_t stays NaN: nothing passes, as nothing
+ * passes t <= NaN).  result.t is 1e6 until the first accept and the walk ends there (intersection.rs:191-203), so the bound takes the place of the
+ * constant the slab test compares tmin against and of both comparisons of the triangle test: the bounded step has no instruction the exact one lacks. */
+__device__ __forceinline__ float shadow_segment_bound(float max_t) {
+    if (!(max_t < 1000000.0f)) return max_t >= 1000000.0f ? 1000000.0f : max_t;
+    if (max_t == 0.0f) return __uint_as_float(1u);
+    const uint32_t b = __float_as_uint(max_t);
+    return __uint_as_float(max_t > 0.0f ? b + 1u : b - 1u);
+}
+
+template <int STACK, bool ANY_HIT, bool FAST, bool FIXED = false, bool SEGMENT = false /* max_t holds shadow_segment_bound(max_t) */, typename View, typename StackRef>
 __device__ __forceinline__ void walk_run(const View &view, Walk<View> &w, F3 ro, F3 rd, F3 ird, float max_t, StackRef &stack, int budget) {
     static_assert(!FIXED || ANY_HIT, "only the any-hit walk may choose its order");
+    static_assert(!SEGMENT || ANY_HIT, "only a shadow ray is a segment");
     typedef typename View::Cur Cur;
     HitRecord res = w.res;
     int sp = w.sp;
@@ -390,19 +405,19 @@ __device__ __forceinline__ void walk_run(const View &view, Walk<View> &w, F3 ro,
                 const uint32_t c0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)cur);
                 if (rpt_ballot(cur == c0) == rpt_ballot(true)) {
                     view.children_uniform(c0, lmin, lmax, rmin, rmax);
-                    hit_l = slab_test<FAST>(lmin, lmax, ro, rd, ird, res.t, tl);
-                    hit_r = slab_test<FAST>(rmin, rmax, ro, rd, ird, res.t, tr);
+                    hit_l = slab_test<FAST>(lmin, lmax, ro, rd, ird, SEGMENT ? max_t : res.t, tl);
+                    hit_r = slab_test<FAST>(rmin, rmax, ro, rd, ird, SEGMENT ? max_t : res.t, tr);
                     asm volatile("" : "+v"(tl), "+v"(tr));      /* (or the optimiser sinks both branches' tests into ONE copy behind the branch) */
                 } else {
                     asm volatile("" ::: "memory");      /* (keeps the four vector loads on THIS side of the branch: hoisted above it they are issued on every step) */
                     view.children(cur, lmin, lmax, rmin, rmax);
-                    hit_l = slab_test<FAST>(lmin, lmax, ro, rd, ird, res.t, tl);
-                    hit_r = slab_test<FAST>(rmin, rmax, ro, rd, ird, res.t, tr);
+                    hit_l = slab_test<FAST>(lmin, lmax, ro, rd, ird, SEGMENT ? max_t : res.t, tl);
+                    hit_r = slab_test<FAST>(rmin, rmax, ro, rd, ird, SEGMENT ? max_t : res.t, tr);
                 }
             } else {
                 view.children(cur, lmin, lmax, rmin, rmax);
-                hit_l = slab_test<FAST>(lmin, lmax, ro, rd, ird, res.t, tl);
-                hit_r = slab_test<FAST>(rmin, rmax, ro, rd, ird, res.t, tr);
+                hit_l = slab_test<FAST>(lmin, lmax, ro, rd, ird, SEGMENT ? max_t : res.t, tl);
+                hit_r = slab_test<FAST>(rmin, rmax, ro, rd, ird, SEGMENT ? max_t : res.t, tr);
             }
             const bool swap = FIXED ? (hit_r && !hit_l) : (hit_r && (!hit_l || tl > tr));     /* strict: ties keep left first */
             if (hit_l || hit_r) {
@@ -465,7 +480,7 @@ __device__ __forceinline__ void walk_run(const View &view, Walk<View> &w, F3 ro,
                                 float t = 0.0f;
                                 bool bf = false;
                                 const bool acc = mine && moller_trumbore_regs(e1, e2, corner, bo, bd, t, bf) && t > 0.001f &&
-                                                 __float_as_uint(t) < best_bits && (!ANY_HIT || t <= b_max);
+                                                 __float_as_uint(t) < best_bits && (!ANY_HIT || (SEGMENT ? t < b_max : t <= b_max));
                                 unsigned long long am = rpt_ballot(acc);
                                 while (am != 0ull) {                                          /* scalar scan, lowest triangle first */
                                     const int l = __ffsll((long long)am) - 1;
@@ -519,7 +534,7 @@ __device__ __forceinline__ void walk_run(const View &view, Walk<View> &w, F3 ro,
                     uint32_t ti = first + i;
                     float t = 0.0f;
                     bool bf = false;
-                    if (moller_trumbore_view(view, ti, ro, rd, t, bf) && t > 0.001f && t < res.t && (!ANY_HIT || t <= max_t)) {
+                    if (moller_trumbore_view(view, ti, ro, rd, t, bf) && t > 0.001f && (SEGMENT ? t < max_t : (t < res.t && (!ANY_HIT || t <= max_t)))) {
                         /* result.t = result.t.min(t) with t < result.t already established (intersection.rs:195-199).  Kept a
                          * real branch: as two selects on vcc the update becomes back-to-back VOP2 v_cndmask, which gfx950 issues
                          * at ~22 cycles each (tools/microbench/valu_rates.hip) */
@@ -546,23 +561,23 @@ __device__ __forceinline__ void walk_run(const View &view, Walk<View> &w, F3 ro,
     w.res = res;
 }
 
-template <int STACK, bool ANY_HIT, bool FAST, bool FIXED = false, typename View, typename StackRef>
+template <int STACK, bool ANY_HIT, bool FAST, bool FIXED = false, bool SEGMENT = false, typename View, typename StackRef>
 __device__ __forceinline__ HitRecord traverse_loop(const View &view, F3 ro, F3 rd, F3 ird, float max_t, StackRef &stack) {
     Walk<View> w;
     walk_begin(view, w);
-    walk_run<STACK, ANY_HIT, FAST, FIXED>(view, w, ro, rd, ird, max_t, stack, 0x7fffffff);
+    walk_run<STACK, ANY_HIT, FAST, FIXED, SEGMENT>(view, w, ro, rd, ird, max_t, stack, 0x7fffffff);
     return w.res;
 }
 
-template <int STACK, bool ANY_HIT, typename View, typename StackT>
+template <int STACK, bool ANY_HIT, bool SEGMENT = false, typename View, typename StackT>
 __device__ __forceinline__ HitRecord traverse_one(const View &view, uint32_t fastdiv_ok, F3 ro, F3 rd, float max_t, StackT *stack) {
     bool fast = fastdiv_ok != 0u && rptm::fastdiv_divisor_ok(rd.x) && rptm::fastdiv_divisor_ok(rd.y) && rptm::fastdiv_divisor_ok(rd.z) &&
                 rptm::fastdiv_operand_ok(ro.x) && rptm::fastdiv_operand_ok(ro.y) && rptm::fastdiv_operand_ok(ro.z);
     if (fast) {
         F3 ird = f3(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z);
-        return traverse_loop<STACK, ANY_HIT, true>(view, ro, rd, ird, max_t, stack);
+        return traverse_loop<STACK, ANY_HIT, true, false, SEGMENT>(view, ro, rd, ird, max_t, stack);
     }
-    return traverse_loop<STACK, ANY_HIT, false>(view, ro, rd, rd, max_t, stack);
+    return traverse_loop<STACK, ANY_HIT, false, false, SEGMENT>(view, ro, rd, rd, max_t, stack);
 }
 
 /* The same walk over the LDS image (SceneViewLds).  SIGNED = the ray passed the exact-division guard: plane
@@ -621,11 +636,12 @@ __device__ __forceinline__ void lds_walk_begin(const SceneViewLds &view, LdsWalk
 /* PRESUB (the camera rays of a call's first iteration, k_traverse_nearest_stream FIRST): every ray of the launch has the SAME origin, and the workgroup
  * staged the plane records with that origin already subtracted — the very `plane - ro` (one IEEE subtraction of the same two floats) each lane would
  * compute at each of the twelve planes of a node pair.  The slab test then divides the staged value directly; the triangle test keeps the true origin. */
-template <int STACK, bool ANY_HIT, bool SIGNED, bool FIXED = false, bool MIXED = false, bool PRESUB = false>
+template <int STACK, bool ANY_HIT, bool SIGNED, bool FIXED = false, bool MIXED = false, bool PRESUB = false, bool SEGMENT = false /* as in walk_run */>
 __device__ __forceinline__ void lds_walk_run(const SceneViewLds &view, LdsWalk &w, F3 ro, F3 rd, F3 ird, float max_t, uint16_t *stack,
                                              int budget, const float4 *img_lane = nullptr, uint32_t stop_first = 0u, float order_bias = 0.0f) {
     static_assert(!FIXED || ANY_HIT, "only the any-hit walk may choose its order");
     static_assert(!MIXED || (!ANY_HIT && !FIXED), "MIXED is the nearest-hit walk with per-lane early exits");
+    static_assert(!SEGMENT || ANY_HIT, "only a shadow ray is a segment");
     const F3 ro_slab = PRESUB ? f3(0.0f, 0.0f, 0.0f) : ro;         /* x - (+0) is x, bit for bit: the subtraction folds away */
     const uint32_t P = view.pairs;
     const float4 *img = MIXED ? img_lane : view.img;
@@ -652,8 +668,8 @@ __device__ __forceinline__ void lds_walk_run(const SceneViewLds &view, LdsWalk &
             const float4 X = px[cur], Y = py[cur], Z = pz[cur];     /* (L.near, R.near, L.far, R.far) per axis */
             const uint32_t d = descs[cur];
             float tl, tr;
-            const bool hit_l = slab_pair_lds<SIGNED>(X.x, Y.x, Z.x, X.z, Y.z, Z.z, ro_slab, rd, ird, res.t, tl);
-            const bool hit_r = slab_pair_lds<SIGNED>(X.y, Y.y, Z.y, X.w, Y.w, Z.w, ro_slab, rd, ird, res.t, tr);
+            const bool hit_l = slab_pair_lds<SIGNED>(X.x, Y.x, Z.x, X.z, Y.z, Z.z, ro_slab, rd, ird, SEGMENT ? max_t : res.t, tl);
+            const bool hit_r = slab_pair_lds<SIGNED>(X.y, Y.y, Z.y, X.w, Y.w, Z.w, ro_slab, rd, ird, SEGMENT ? max_t : res.t, tr);
             const bool swap = FIXED ? (hit_r && !hit_l)
                             : MIXED ? (hit_r && (!hit_l || tl > tr + order_bias))
                                     : (hit_r && (!hit_l || tl > tr));     /* strict: ties keep left first */
@@ -678,7 +694,7 @@ __device__ __forceinline__ void lds_walk_run(const SceneViewLds &view, LdsWalk &
                 uint32_t ti = first + i;
                 float t = 0.0f;
                 bool bf = false;
-                if (moller_trumbore_view(view, ti, ro, rd, t, bf) && t > 0.001f && t < res.t && (!ANY_HIT || t <= max_t)) {
+                if (moller_trumbore_view(view, ti, ro, rd, t, bf) && t > 0.001f && (SEGMENT ? t < max_t : (t < res.t && (!ANY_HIT || t <= max_t)))) {
                     /* result.t = result.t.min(t) with t < result.t already established (intersection.rs:195-199).  Kept a
                      * real branch: as two selects on vcc the update becomes back-to-back VOP2 v_cndmask, which gfx950 issues
                      * at ~22 cycles each (tools/microbench/valu_rates.hip) */
@@ -701,11 +717,11 @@ __device__ __forceinline__ void lds_walk_run(const SceneViewLds &view, LdsWalk &
     w.res = res;
 }
 
-template <int STACK, bool ANY_HIT, bool SIGNED, bool FIXED = false>
+template <int STACK, bool ANY_HIT, bool SIGNED, bool FIXED = false, bool SEGMENT = false>
 __device__ __forceinline__ HitRecord traverse_loop_lds(const SceneViewLds &view, F3 ro, F3 rd, F3 ird, float max_t, uint16_t *stack) {
     LdsWalk w;
     lds_walk_begin(view, w);
-    lds_walk_run<STACK, ANY_HIT, SIGNED, FIXED>(view, w, ro, rd, ird, max_t, stack, 0x7fffffff);
+    lds_walk_run<STACK, ANY_HIT, SIGNED, FIXED, false, false, SEGMENT>(view, w, ro, rd, ird, max_t, stack, 0x7fffffff);
     return w.res;
 }
 
@@ -714,13 +730,13 @@ __device__ __forceinline__ bool fastdiv_ray_ok(uint32_t fastdiv_ok, F3 ro, F3 rd
            rptm::fastdiv_operand_ok(ro.x) && rptm::fastdiv_operand_ok(ro.y) && rptm::fastdiv_operand_ok(ro.z);
 }
 
-template <int STACK, bool ANY_HIT>
+template <int STACK, bool ANY_HIT, bool SEGMENT = false>
 __device__ __forceinline__ HitRecord traverse_one(const SceneViewLds &view, uint32_t fastdiv_ok, F3 ro, F3 rd, float max_t, uint16_t *stack) {
     if (fastdiv_ray_ok(fastdiv_ok, ro, rd)) {
         F3 ird = f3(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z);
-        return traverse_loop_lds<STACK, ANY_HIT, true>(view, ro, rd, ird, max_t, stack);
+        return traverse_loop_lds<STACK, ANY_HIT, true, false, SEGMENT>(view, ro, rd, ird, max_t, stack);
     }
-    return traverse_loop_lds<STACK, ANY_HIT, false>(view, ro, rd, rd, max_t, stack);
+    return traverse_loop_lds<STACK, ANY_HIT, false, false, SEGMENT>(view, ro, rd, rd, max_t, stack);
 }
 
 /* Small scenes live in LDS: when the traversal image (SceneViewLds) fits in RPT_LDS_SCENE_BYTES
@@ -991,125 +1007,6 @@ __global__ __launch_bounds__(THREADS) void k_traverse_nearest_stream(DevScene sc
     }
 }
 
-/* Shadow rays (kernels/src/light_pick.rs:141-148) of a scene the streamed walks cannot take, one ray per lane from global
- * memory: any-hit over the positions of the
- * shadow queue (k_common.h: sharded, dense up to the shards' tails); if unoccluded the pre-weighted NEE contribution is added to the
- * path's radiance (lib.rs:164).  A path that ended at this bounce (bit 31 of
- * the tag) is finished here: accumulated and, if samples remain, regenerated
- * in place (its slot becomes HIT_PENDING again). */
-template <int STACK, int THREADS>
-__global__ __launch_bounds__(THREADS) void k_traverse_shadow(DevScene sc, DevState st, DevQueues q, DevConfig cfg, DevStats *stats) {
-    __shared__ uint32_t lds_stack[THREADS / RPT_WAVE][STACK][RPT_WAVE];
-    if (q.count[Q_DRAINED] != 0u) return;                     /* surplus launch (grid-uniform) */
-    uint32_t i = blockIdx.x * THREADS + threadIdx.x;
-    uint32_t positions, n;
-    q_extent(q.shadow_cnt, positions, n);
-    if (i == 0u && n) atomicAdd(&stats->shadow_rays, (unsigned long long)n);
-    if (blockIdx.x * THREADS >= positions) return;             /* block-uniform */
-    const SceneViewGlobal view{sc.nodes, sc.tri_isect};
-    if (i >= positions || !q_filled(q.shadow_cnt, i)) return;
-    float4 o = q.sh_o[i], d = q.sh_d[i];
-    uint32_t tag = __float_as_uint(d.w);
-    uint32_t slot = tag & 0x7fffffffu;
-    bool finish = (tag >> 31) != 0u;
-    uint32_t *stack = &lds_stack[threadIdx.x / RPT_WAVE][0][threadIdx.x % RPT_WAVE];
-    HitRecord h = traverse_one<STACK, true>(view, sc.fastdiv_ok, f3(o.x, o.y, o.z), f3(d.x, d.y, d.z), o.w, stack);
-    bool visible = h.tri == HIT_MISS;
-    if (visible || finish) {
-        float4 r4 = st.rad[slot];
-        F3 radiance = f3(r4.x, r4.y, r4.z);
-        if (visible) {
-            float4 c = q.sh_c[i];
-            radiance = radiance + mask_nan3(f3(c.x, c.y, c.z));
-        }
-        if (finish) {
-            finish_in_side_stage(st, cfg, slot, radiance, __float_as_uint(r4.w));
-        } else {
-            r4.x = radiance.x; r4.y = radiance.y; r4.z = radiance.z;
-            st.rad[slot] = r4;
-        }
-    }
-}
-
-/* Shadow rays of an LDS-resident scene, streamed like the extension rays above (persistent workgroups, spans of the dense
- * shadow queue from a launch-wide counter, refill of finished lanes).  An any-hit walk cannot be pruned by max_t (the
- * reference prunes boxes against result.t = 1e6 until something is accepted, intersection.rs:212-213, and box-t / triangle-t
- * round differently), so an unoccluded ray crosses every box along its line while an occluded one may stop after two
- * visits: lane utilisation of the one-ray-per-lane kernel was 40 % (profiles/r02base_darkcornell_mis_pmc_sq.txt).
- * Lanes only record "occluded" in the unused .w of the entry's contribution record; k_shadow_resolve then adds the NEE
- * terms in one dense pass (all lanes busy, none of the walk's registers live). */
-template <int STACK, int THREADS, bool FIXED /* fixed left-first order over the flipped image (shadow_order.h) */>
-__attribute__((amdgpu_num_sgpr(RPT_LDS_WALK_SGPRS)))
-__global__ __launch_bounds__(THREADS) void k_traverse_shadow_stream(DevScene sc, DevState st, DevQueues q, DevStats *stats, uint32_t SPAN) {
-    constexpr uint32_t NW = THREADS / RPT_WAVE;
-    __shared__ uint16_t lds_stack[NW][STACK][RPT_WAVE];
-    __shared__ WgPool pool;
-    float4 *lds_scene = rpt_lds_dyn;
-    if (q.count[Q_DRAINED] != 0u) return;                      /* surplus launch (grid-uniform) */
-    uint32_t n, n_entries;                                     /* n: queue positions to hand out */
-    q_extent(q.shadow_cnt, n, n_entries);
-    uint32_t *global_next = &q.count[Q_SPOOL];                 /* zeroed by the shade stage of this iteration */
-    if (blockIdx.x == 0u && threadIdx.x == 0u && n_entries) atomicAdd(&stats->shadow_rays, (unsigned long long)n_entries);
-    const uint32_t lane = __lane_id(), wave = threadIdx.x / RPT_WAVE;
-    if (threadIdx.x == 0u) {
-        const uint32_t g = n ? atomicAdd(global_next, SPAN) : 0u;
-        pool.word = g < n ? ((unsigned long long)(g + SPAN < n ? g + SPAN : n) << 32) | g : 0x00000000f0000000ull;
-        pool.lock = 0u;
-    }
-    __syncthreads();
-    if ((uint32_t)(pool.word >> 32) == 0u) return;             /* block-uniform: nothing (left) to trace */
-    const SceneViewLds view = stage_scene_lds<THREADS>(sc, lds_scene, FIXED);
-    uint16_t *stack = &lds_stack[wave][0][lane];
-    F3 ro = f3(0, 0, 0), rd = f3(1, 1, 1), ird = f3(1, 1, 1);
-    float max_t = 0.0f;
-    LdsWalk w;
-    lds_walk_begin(view, w);
-    w.cur = LDS_DESC_DEAD;
-    uint32_t entry = 0u;
-    bool have = false;
-    bool pool_open = true;                                     /* wave-uniform */
-    for (;;) {
-        const unsigned long long idle_m = rpt_ballot(w.cur == LDS_DESC_DEAD);
-        const uint32_t n_idle = (uint32_t)__popcll(idle_m);
-        if (pool_open && n_idle >= (uint32_t)RPT_STREAM_REFILL) {
-            uint32_t base = 0u, got = 0u;
-            bool finished = false;
-            if (lane == 0u) base = wg_pool_take(&pool, global_next, n, SPAN, n_idle, got, finished);
-            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-            got = (uint32_t)__builtin_amdgcn_readfirstlane((int)got);
-            pool_open = __builtin_amdgcn_readfirstlane((int)finished) == 0;
-            if (w.cur == LDS_DESC_DEAD) {
-                if (have) {
-                    q.sh_c[entry].w = w.res.tri == HIT_MISS ? 0.0f : 1.0f;
-                    have = false;
-                }
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle_m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle_m, 0u));
-                if (rank < got && q_filled(q.shadow_cnt, base + rank)) {   /* (a position in the tail of a shard may be empty) */
-                    entry = base + rank;
-                    const float4 o = q.sh_o[entry], d = q.sh_d[entry];
-                    ro = f3(o.x, o.y, o.z); rd = f3(d.x, d.y, d.z);
-                    max_t = o.w;
-                    have = true;
-                    if (fastdiv_ray_ok(sc.fastdiv_ok, ro, rd)) {
-                        ird = f3(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z);
-                        lds_walk_begin(view, w);
-                    } else {
-                        w.res = traverse_loop_lds<STACK, true, false, FIXED>(view, ro, rd, rd, max_t, stack);   /* alone; recorded at the next refill */
-                    }
-                }
-            }
-            if (got != 0u || !pool_open) continue;
-            if (idle_m == ~0ull) { __builtin_amdgcn_s_sleep(8); continue; }   /* another wave is fetching the next span */
-        }
-        if (idle_m == ~0ull) {
-            if (!pool_open) break;                             /* nothing in flight and nothing left to hand out */
-            continue;
-        }
-        lds_walk_run<STACK, true, true, FIXED>(view, w, ro, rd, ird, max_t, stack, pool_open ? RPT_STREAM_TRIPS : 0x7fffffff);
-    }
-    if (have) q.sh_c[entry].w = w.res.tri == HIT_MISS ? 0.0f : 1.0f;
-}
-
 /* ---- streamed walks through GLOBAL memory (scenes too large for LDS) ----------------------------------------
  * Measured on MI355X (profiles/r02base_*): with one ray per lane the global-memory walk runs at 26 % (VeachMIS nearest),
  * 29 % (PBRTest) and 22 % (VeachMIS shadow) lane utilisation while two thirds of its wave cycles wait on L1/L2 — an
@@ -1267,94 +1164,16 @@ __global__ __launch_bounds__(RPT_BLOCK) void k_shadow_resolve(DevState st, DevQu
     shadow_resolve(st, q, cfg, i, __float_as_uint(q.sh_d[i].w), q.sh_c[i].w == 0.0f);
 }
 
-/* Shadow rays, streamed: the queue is dense already (up to the tails of its shards); a wave owns SPAN consecutive positions and refills lanes whose
- * any-hit walk has ended (found an occluder after two visits, or crossed the whole scene without one).  Lanes only note
- * "occluded" per entry in LDS while walking; the NEE terms are added afterwards in one dense pass over the span (all
- * lanes busy, and the registers of the walk are dead by then: 61 instead of 91 VGPRs). */
-template <int STACK, int WIDTH, bool COOP, bool FIXED /* fixed left-first order over the flipped pair array (shadow_order.h) */>
-__attribute__((amdgpu_waves_per_eu(gstream_waves(STACK, WIDTH, COOP), 8)))
- __global__ __launch_bounds__(RPT_WAVE) void k_traverse_shadow_gstream(DevScene sc, DevState st, DevQueues q, DevConfig cfg, DevStats *stats,
-                                                                      uint32_t SPAN) {
-    __shared__ WaveStack<STACK, WIDTH> lds_stack;
-    __shared__ uint8_t occluded[RPT_WAVE * RPT_GSTREAM_RAYS];
-    if (q.count[Q_DRAINED] != 0u) return;                      /* surplus launch (grid-uniform) */
-    const uint32_t lane = threadIdx.x;
-    uint32_t n, n_entries;                                     /* n: queue positions of the launch */
-    q_extent(q.shadow_cnt, n, n_entries);
-    if (blockIdx.x == 0u && lane == 0u && n_entries) atomicAdd(&stats->shadow_rays, (unsigned long long)n_entries);
-    const uint32_t begin = blockIdx.x * SPAN;
-    if (begin >= n) return;
-    const uint32_t end = begin + SPAN < n ? begin + SPAN : n;
-    {
-        typedef SceneViewPairsT<COOP> View;
-        const View view = FIXED ? View{sc.gpairs_shadow, sc.glinks_shadow, sc.tri_isect} : View{sc.gpairs, sc.glinks, sc.tri_isect};
-        auto stack = lds_stack.column(lane);
-        F3 ro = f3(0, 0, 0), rd = f3(1, 1, 1), ird = f3(1, 1, 1);
-        float max_t = 0.0f;
-        Walk<View> w;
-        walk_begin(view, w);
-        w.cur = View::dead();
-        uint32_t entry = 0u, next = begin;                     /* next: wave-uniform */
-        bool have = false;
-        for (;;) {
-            const unsigned long long idle_m = rpt_ballot(walk_dead(w));
-            const uint32_t n_idle = (uint32_t)__popcll(idle_m);
-            const bool more = next < end;                      /* wave-uniform */
-            if ((more && n_idle >= (uint32_t)RPT_GSTREAM_REFILL) || idle_m == ~0ull) {
-                if (walk_dead(w)) {
-                    if (have) {
-                        occluded[entry - begin] = w.res.tri == HIT_MISS ? (uint8_t)0 : (uint8_t)1;
-                        have = false;
-                    }
-                    const uint32_t at = next + __builtin_amdgcn_mbcnt_hi((uint32_t)(idle_m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle_m, 0u));
-                    if (at < end && q_filled(q.shadow_cnt, at)) {
-                        const float4 o = q.sh_o[at], d = q.sh_d[at];
-                        ro = f3(o.x, o.y, o.z); rd = f3(d.x, d.y, d.z);
-                        max_t = o.w;
-                        entry = at;
-                        have = true;
-                        if (fastdiv_ray_ok(sc.fastdiv_ok, ro, rd)) {
-                            ird = f3(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z);
-                            walk_begin(view, w);
-                        } else {
-                            w.res = traverse_loop<STACK, true, false, FIXED>(view, ro, rd, rd, max_t, stack);   /* alone; noted at the next refill */
-                        }
-                    }
-                }
-                if (!more) break;
-                next += n_idle;
-                continue;
-            }
-            walk_run<STACK, true, true, FIXED>(view, w, ro, rd, ird, max_t, stack, more ? RPT_GSTREAM_TRIPS : 0x7fffffff);
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    for (uint32_t base = begin; base < end; base += RPT_WAVE) {
-        const uint32_t e = base + lane;
-        if (e < end && q_filled(q.shadow_cnt, e)) shadow_resolve(st, q, cfg, e, __float_as_uint(q.sh_d[e].w), occluded[e - begin] == 0u);
-    }
-}
-
-/* Test hook: plain ray arrays in, hit arrays out (rpt_debug_trace_rays). */
-template <int STACK, bool ANY_HIT, bool LDS_SCENE, int THREADS>
-__global__ __launch_bounds__(THREADS) void k_trace_debug(DevScene sc, uint32_t n, const float *origins, const float *dirs,
-                                                         const float *max_t, float *out_t, uint32_t *out_tri, uint32_t *out_flags) {
-    /* LDS-resident scenes walk 16-bit descriptors: 16-bit stack entries (32 KB per 1024-thread workgroup, which with a
-     * <= 32 KB scene image is the 64 KB a workgroup may hold: 2 workgroups = 32 waves per CU) */
-    typedef typename StackElem<LDS_SCENE>::type StackT;
-    __shared__ StackT lds_stack[THREADS / RPT_WAVE][STACK][RPT_WAVE];
-    float4 *lds_scene = rpt_lds_dyn;
-    uint32_t i = blockIdx.x * THREADS + threadIdx.x;
-    const auto view = stage_scene<LDS_SCENE, THREADS>(sc, lds_scene);
-    if (i >= n) return;
-    F3 ro = f3(origins[3 * i], origins[3 * i + 1], origins[3 * i + 2]);
-    F3 rd = f3(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]);
-    StackT *stack = &lds_stack[threadIdx.x / RPT_WAVE][0][threadIdx.x % RPT_WAVE];
-    HitRecord h = traverse_one<STACK, ANY_HIT>(view, sc.fastdiv_ok, ro, rd, ANY_HIT ? max_t[i] : 0.0f, stack);
-    out_t[i] = h.t;
-    out_tri[i] = (h.tri == HIT_MISS) ? 0u : (h.tri & 0x7fffffffu);
-    out_flags[i] = (h.tri == HIT_MISS) ? 0u : (1u | ((h.tri >> 31) << 1));
-}
+/* the shadow kernels and the test hook: the exact walk under the kernels' own names, then their segment-bounded `_seg` twins (see the file's header) */
+#define RPT_SHADOW_KERNEL(name) name
+#define RPT_SHADOW_KERNEL_SEGMENT false
+#include "k_traverse_shadow_kernels.h"
+#undef RPT_SHADOW_KERNEL
+#undef RPT_SHADOW_KERNEL_SEGMENT
+#define RPT_SHADOW_KERNEL(name) name##_seg
+#define RPT_SHADOW_KERNEL_SEGMENT true
+#include "k_traverse_shadow_kernels.h"
+#undef RPT_SHADOW_KERNEL
+#undef RPT_SHADOW_KERNEL_SEGMENT
 
 #endif /* RPT_K_TRAVERSE_H */

@@ -622,6 +622,16 @@ int rpt_multi_set_config(rpt_multi *m, const rpt_tracing_config *cfg) {
     return RPT_OK;
 }
 
+int rpt_multi_set_shadow_mode(rpt_multi *m, uint32_t mode) {
+    if (!m) return RPT_EINVAL;
+    if (mode != RPT_SHADOW_EXACT && mode != RPT_SHADOW_SEGMENT) return multi_fail(m, m->ctx[0], rpt_set_shadow_mode(m->ctx[0], mode));   /* (no rank is changed) */
+    for (rpt_ctx *c : m->ctx) {
+        int rc = rpt_set_shadow_mode(c, mode);
+        if (rc) return multi_fail(m, c, rc);
+    }
+    return RPT_OK;
+}
+
 int rpt_multi_reset(rpt_multi *m, const rpt_rng_state *seed, const float *accum_init, uint32_t samples_init) {
     if (!m) return RPT_EINVAL;
     for (rpt_ctx *c : m->ctx) {

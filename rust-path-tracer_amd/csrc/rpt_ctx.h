@@ -199,6 +199,7 @@ struct rpt_ctx {
     uint32_t sky_wide_cfg = 32768;       /* up to this many queued misses the sky march runs 16 lanes per miss */
     bool test_short_batch = false;       /* rpt_debug_short_batch: enqueue one iteration too few in an asynchronous batch (proves that the completion checks notice) */
     int samples_in_flight_request = 0;   /* 0 = automatic */
+    uint32_t shadow_mode = RPT_SHADOW_EXACT;   /* rpt_set_shadow_mode: which any-hit walk rpt_launch_shadow enqueues (read at enqueue, nothing else depends on it) */
     uint64_t max_slots_budget = 160ull << 20;   /* automatic S: the most slots (pixels x samples in flight) a context allocates */
     std::vector<uint32_t> pixel_xy_host;
     DevBuf<uint32_t> pixel_xy;
@@ -239,7 +240,7 @@ struct rpt_ctx {
 void rpt_launch_nearest(rpt_ctx *c, uint32_t iteration, bool last_without_nee /* the last extension rays of a batch of known length, no NEE */,
                         bool camera_rays /* iteration 0 of a render call: every ray leaves cfg.cam_position */);
 void rpt_launch_shadow(rpt_ctx *c);
-void rpt_launch_trace_debug(rpt_ctx *c, bool any_hit, uint32_t n, const float *origins, const float *dirs, const float *max_t, float *out_t, uint32_t *out_tri,
+void rpt_launch_trace_debug(rpt_ctx *c, int any_hit /* 0 nearest, 1 any-hit, 2 segment-bounded any-hit */, uint32_t n, const float *origins, const float *dirs, const float *max_t, float *out_t, uint32_t *out_tri,
                             uint32_t *out_flags);
 hipError_t rpt_last_walk_attributes(hipFuncAttributes *out);      /* of k_traverse_nearest_stream<.., LAST>: its static LDS decides whether the flipped copy fits */
 /* rpt_hip.hip, for the production-trace hook of rpt_debug.hip: the per-slot arrays for a call over `n` slots (grown, never shrunk), and "nothing in

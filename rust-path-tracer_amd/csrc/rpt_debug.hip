@@ -109,7 +109,7 @@ int rpt_debug_trace_rays(rpt_ctx *c, int any_hit, size_t n, const float *origins
     HIP_TRY(c, d_o.from_host(origins, 3 * n)); HIP_TRY(c, d_d.from_host(dirs, 3 * n)); HIP_TRY(c, d_t.alloc(n));
     HIP_TRY(c, d_tri.alloc(n)); HIP_TRY(c, d_fl.alloc(n));
     HIP_TRY(c, max_t ? d_m.from_host(max_t, n) : d_m.alloc(n));
-    rpt_launch_trace_debug(c, any_hit != 0, (uint32_t)n, d_o.p, d_d.p, d_m.p, d_t.p, d_tri.p, d_fl.p);
+    rpt_launch_trace_debug(c, any_hit, (uint32_t)n, d_o.p, d_d.p, d_m.p, d_t.p, d_tri.p, d_fl.p);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipMemcpy(out_t, d_t.p, 4 * n, hipMemcpyDeviceToHost));
     HIP_TRY(c, hipMemcpy(out_tri, d_tri.p, 4 * n, hipMemcpyDeviceToHost));

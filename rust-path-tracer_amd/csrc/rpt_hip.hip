@@ -662,6 +662,20 @@ int rpt_set_samples_in_flight(rpt_ctx *c, int s) {
     return reapply_config(c);            /* re-derive the slot count */
 }
 
+/* nothing is allocated or invalidated: the mode is read when a batch's shadow stage is enqueued (rpt_traverse.hip launch_shadow) */
+int rpt_set_shadow_mode(rpt_ctx *c, uint32_t mode) {
+    if (!c) return RPT_EINVAL;
+    if (mode != RPT_SHADOW_EXACT && mode != RPT_SHADOW_SEGMENT) { c->error = "rpt_set_shadow_mode: mode must be RPT_SHADOW_EXACT (0) or RPT_SHADOW_SEGMENT (1)"; return RPT_EINVAL; }
+    c->shadow_mode = mode;
+    return RPT_OK;
+}
+
+int rpt_shadow_mode(rpt_ctx *c, uint32_t *mode_out) {
+    if (!c || !mode_out) return RPT_EINVAL;
+    *mode_out = c->shadow_mode;
+    return RPT_OK;
+}
+
 int rpt_rank_pixels(rpt_ctx *c, uint32_t rank, uint64_t *n) {
     if (!c || !n) return RPT_EINVAL;
     if (!c->has_config || rank >= c->world) { c->error = "no config / bad rank"; return RPT_EINVAL; }

@@ -96,14 +96,19 @@ void launch_nearest(rpt_ctx *c, uint32_t iteration, bool last_without_nee = fals
     }
 }
 
-/* the streamed global-memory any-hit walk (FIXED: over the flipped copy, left child first — shadow_order.h) */
+/* the streamed global-memory any-hit walk (FIXED: over the flipped copy, left child first — shadow_order.h; the `_seg` twins: the context is in
+ * RPT_SHADOW_SEGMENT mode, k_traverse.h shadow_segment_bound) */
 template <int STACK, bool COOP>
 static void launch_shadow_gstream(rpt_ctx *c, uint32_t q_positions) {
     const int width = gstream_stack_width<STACK>(c);
     const uint32_t span = gstream_span(c, (uint32_t)RPT_GSTREAM_RAYS), blocks = (q_positions + span - 1) / span;
+    const bool segment = c->shadow_mode == RPT_SHADOW_SEGMENT;
     with_stack_width<STACK>(width, [&](auto W) {
         constexpr int WIDTH = decltype(W)::value;
-        if (c->scene.gpairs_shadow) k_traverse_shadow_gstream<STACK, WIDTH, COOP, true><<<blocks, RPT_WAVE, 0, c->stream>>>(c->scene, c->state, c->queues, c->cfg, c->dev_stats.p, span);
+        if (segment) {
+            if (c->scene.gpairs_shadow) k_traverse_shadow_gstream_seg<STACK, WIDTH, COOP, true><<<blocks, RPT_WAVE, 0, c->stream>>>(c->scene, c->state, c->queues, c->cfg, c->dev_stats.p, span);
+            else k_traverse_shadow_gstream_seg<STACK, WIDTH, COOP, false><<<blocks, RPT_WAVE, 0, c->stream>>>(c->scene, c->state, c->queues, c->cfg, c->dev_stats.p, span);
+        } else if (c->scene.gpairs_shadow) k_traverse_shadow_gstream<STACK, WIDTH, COOP, true><<<blocks, RPT_WAVE, 0, c->stream>>>(c->scene, c->state, c->queues, c->cfg, c->dev_stats.p, span);
         else k_traverse_shadow_gstream<STACK, WIDTH, COOP, false><<<blocks, RPT_WAVE, 0, c->stream>>>(c->scene, c->state, c->queues, c->cfg, c->dev_stats.p, span);
     });
 }
@@ -114,10 +119,14 @@ void launch_shadow(rpt_ctx *c) {
     hipStream_t s = c->stream;
     const size_t lds_bytes = (size_t)c->scene.lds_vecs * sizeof(float4);
     const uint32_t q_positions = c->n_slots + RPT_Q_SLACK, blocks_q = (q_positions + RPT_BLOCK - 1) / RPT_BLOCK;
+    const bool segment = c->shadow_mode == RPT_SHADOW_SEGMENT;      /* read here, at enqueue: rpt_set_shadow_mode holds from the next batch on */
     if (STACK == 16 && c->scene.lds_scene) {
         uint32_t grid;
         const uint32_t span = lds_stream_span(c, grid);
-        if (c->scene.lds_image_shadow) k_traverse_shadow_stream<16, LDS_THREADS, true><<<grid, LDS_THREADS, lds_bytes, s>>>(c->scene, c->state, c->queues, c->dev_stats.p, span);
+        if (segment) {
+            if (c->scene.lds_image_shadow) k_traverse_shadow_stream_seg<16, LDS_THREADS, true><<<grid, LDS_THREADS, lds_bytes, s>>>(c->scene, c->state, c->queues, c->dev_stats.p, span);
+            else k_traverse_shadow_stream_seg<16, LDS_THREADS, false><<<grid, LDS_THREADS, lds_bytes, s>>>(c->scene, c->state, c->queues, c->dev_stats.p, span);
+        } else if (c->scene.lds_image_shadow) k_traverse_shadow_stream<16, LDS_THREADS, true><<<grid, LDS_THREADS, lds_bytes, s>>>(c->scene, c->state, c->queues, c->dev_stats.p, span);
         else k_traverse_shadow_stream<16, LDS_THREADS, false><<<grid, LDS_THREADS, lds_bytes, s>>>(c->scene, c->state, c->queues, c->dev_stats.p, span);
         k_shadow_resolve<<<blocks_q, RPT_BLOCK, 0, s>>>(c->state, c->queues, c->cfg);
     } else if (c->scene.gpairs) {
@@ -125,7 +134,8 @@ void launch_shadow(rpt_ctx *c) {
         else launch_shadow_gstream<STACK, false>(c, q_positions);
     } else {
         const uint32_t nb = (q_positions + GLOBAL_THREADS - 1) / GLOBAL_THREADS;
-        k_traverse_shadow<32, GLOBAL_THREADS><<<nb, GLOBAL_THREADS, 0, s>>>(c->scene, c->state, c->queues, c->cfg, c->dev_stats.p);
+        if (segment) k_traverse_shadow_seg<32, GLOBAL_THREADS><<<nb, GLOBAL_THREADS, 0, s>>>(c->scene, c->state, c->queues, c->cfg, c->dev_stats.p);
+        else k_traverse_shadow<32, GLOBAL_THREADS><<<nb, GLOBAL_THREADS, 0, s>>>(c->scene, c->state, c->queues, c->cfg, c->dev_stats.p);
     }
 }
 
@@ -151,17 +161,20 @@ hipError_t rpt_last_walk_attributes(hipFuncAttributes *out) {
     return hipFuncGetAttributes(out, reinterpret_cast<const void *>(&k_traverse_nearest_stream<16, LDS_THREADS, RPT_NEAREST_LAST>));
 }
 
-/* rpt_debug_trace_rays: plain ray arrays through the reference-order walk (traverse_one), out of LDS where the scene lives there */
-void rpt_launch_trace_debug(rpt_ctx *c, bool any_hit, uint32_t n, const float *o, const float *d, const float *max_t, float *out_t, uint32_t *out_tri, uint32_t *out_flags) {
+/* rpt_debug_trace_rays: plain ray arrays through the reference-order walk (traverse_one), out of LDS where the scene lives there
+ * (any_hit 2: the segment-bounded any-hit walk) */
+void rpt_launch_trace_debug(rpt_ctx *c, int any_hit, uint32_t n, const float *o, const float *d, const float *max_t, float *out_t, uint32_t *out_tri, uint32_t *out_flags) {
     hipStream_t s = c->stream;
     if (c->stack_cap == 16 && c->scene.lds_scene) {
         const unsigned bl = (n + LDS_THREADS - 1) / LDS_THREADS;
         const size_t lds_bytes = (size_t)c->scene.lds_vecs * sizeof(float4);
-        if (any_hit) k_trace_debug<16, true, true, LDS_THREADS><<<bl, LDS_THREADS, lds_bytes, s>>>(c->scene, n, o, d, max_t, out_t, out_tri, out_flags);
+        if (any_hit == 2) k_trace_debug_seg<16, true, true, LDS_THREADS><<<bl, LDS_THREADS, lds_bytes, s>>>(c->scene, n, o, d, max_t, out_t, out_tri, out_flags);
+        else if (any_hit) k_trace_debug<16, true, true, LDS_THREADS><<<bl, LDS_THREADS, lds_bytes, s>>>(c->scene, n, o, d, max_t, out_t, out_tri, out_flags);
         else k_trace_debug<16, false, true, LDS_THREADS><<<bl, LDS_THREADS, lds_bytes, s>>>(c->scene, n, o, d, max_t, out_t, out_tri, out_flags);
     } else {
         const unsigned blocks = (n + RPT_BLOCK - 1) / RPT_BLOCK;
-        if (any_hit) k_trace_debug<32, true, false, RPT_BLOCK><<<blocks, RPT_BLOCK, 0, s>>>(c->scene, n, o, d, max_t, out_t, out_tri, out_flags);
+        if (any_hit == 2) k_trace_debug_seg<32, true, false, RPT_BLOCK><<<blocks, RPT_BLOCK, 0, s>>>(c->scene, n, o, d, max_t, out_t, out_tri, out_flags);
+        else if (any_hit) k_trace_debug<32, true, false, RPT_BLOCK><<<blocks, RPT_BLOCK, 0, s>>>(c->scene, n, o, d, max_t, out_t, out_tri, out_flags);
         else k_trace_debug<32, false, false, RPT_BLOCK><<<blocks, RPT_BLOCK, 0, s>>>(c->scene, n, o, d, max_t, out_t, out_tri, out_flags);
     }
 }

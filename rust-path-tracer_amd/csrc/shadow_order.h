@@ -11,6 +11,9 @@
  * ANY visiting order gives the reference's `.hit` bit for bit (tests/test_anyhit_order.py: left-first, right-first, far-first, random
  * per (ray, node) and breadth-first against intersect_front_to_back<false> on 10^6 rays).  Nearest-hit walks have no such freedom: their
  * order decides ties in t (k_traverse.h header).
+ * (All of this is the EXACT walk, whose boxes are pruned against the constant 1e6 and never against the ray's max_t.  The opt-in RPT_SHADOW_SEGMENT walk —
+ * rpt.h rpt_set_shadow_mode, k_traverse.h shadow_segment_bound — also leaves out boxes with tmin > max_t; that predicate too reads the box and the ray
+ * alone, so its `.hit` is as independent of the visiting order, and it walks the order chosen here: the probe below is not re-run under the bounded rule.)
  *
  * What the freedom is worth (tools/anyhit_order_sim.py, profiles/r05_anyhit_order_sim.txt): an UNOCCLUDED ray visits the same nodes under
  * every order; an occluded ray stops at the first occluder it meets, and how soon that is depends on the scene.  Replayed on the real

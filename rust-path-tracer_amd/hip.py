@@ -24,8 +24,10 @@ EXPORTS = [
     "rpt_gathered_device_ptr", "rpt_multi_create", "rpt_multi_size", "rpt_multi_ctx", "rpt_multi_upload_scene", "rpt_multi_set_config",
     "rpt_multi_reset", "rpt_multi_render", "rpt_multi_wait", "rpt_multi_read_accum", "rpt_multi_get_stats", "rpt_multi_destroy",
     "rpt_multi_last_error", "rpt_comm_library", "rpt_debug_trace_rays_production", "rpt_build_fingerprint", "rpt_debug_comm_selftest", "rpt_device_info", "rpt_shadow_order", "rpt_debug_shadow_order_host", "rpt_last_bounce_order", "rpt_debug_last_order_host", "rpt_debug_short_batch",
+    "rpt_set_shadow_mode", "rpt_shadow_mode", "rpt_multi_set_shadow_mode",
 ]
 COMM_ID_BYTES = 128
+SHADOW_EXACT, SHADOW_SEGMENT = 0, 1          # rpt_set_shadow_mode
 MULTI_ALLOW_SHARED_DEVICE = 1
 
 
@@ -83,6 +85,10 @@ def lib():
         L.rpt_comm_init_local.argtypes = [C.c_void_p]
         L.rpt_device_info.argtypes = [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.rpt_shadow_order.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
+        if hasattr(L, "rpt_set_shadow_mode"):            # (RPT_HIP_LIB may name an older build for an A/B run: it renders in the exact mode only)
+            L.rpt_set_shadow_mode.argtypes = [C.c_void_p, C.c_uint32]
+            L.rpt_shadow_mode.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+            L.rpt_multi_set_shadow_mode.argtypes = [C.c_void_p, C.c_uint32]
         L.rpt_last_bounce_order.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
         L.rpt_debug_comm_selftest.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
         L.rpt_comm_world.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -285,6 +291,16 @@ class Renderer:
         self._check(lib().rpt_shadow_order(self._h, C.byref(f), C.byref(vn), C.byref(vf), C.byref(n), C.byref(ms)))
         return {"fixed": bool(f.value), "visits_near": vn.value, "visits_fixed": vf.value, "probe_rays": n.value, "probe_ms": ms.value}
 
+    def set_shadow_mode(self, mode):
+        """rpt_set_shadow_mode: SHADOW_EXACT (default: the reference's any-hit walk, bit for bit) or SHADOW_SEGMENT (boxes that begin behind the ray's max_t
+        are not entered: faster, an occlusion can in principle be lost); holds for the batches enqueued afterwards."""
+        self._check(lib().rpt_set_shadow_mode(self._h, mode))
+
+    def shadow_mode(self):
+        m = C.c_uint32()
+        self._check(lib().rpt_shadow_mode(self._h, C.byref(m)))
+        return m.value
+
     LAST_BOUNCE_MODES = ("whole walk", "hit or miss, near child first", "hit or miss, more opaque child first", "hit or miss, smaller subtree first",
                          "hit or miss, more opaque per node first")
 
@@ -348,6 +364,7 @@ class Renderer:
         return out
 
     def debug_trace_rays(self, any_hit, origins, dirs, max_t=None):
+        """any_hit: 0 / False nearest, 1 / True the reference's any-hit walk, 2 the segment-bounded any-hit walk (rpt_set_shadow_mode)"""
         origins = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
         dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
         n = len(origins)
@@ -355,7 +372,7 @@ class Renderer:
         t = np.zeros(n, np.float32)
         tri = np.zeros(n, np.uint32)
         flags = np.zeros(n, np.uint32)
-        self._check(lib().rpt_debug_trace_rays(self._h, int(bool(any_hit)), n, ptr(origins), ptr(dirs), ptr(max_t),
+        self._check(lib().rpt_debug_trace_rays(self._h, 2 if any_hit == 2 else int(bool(any_hit)), n, ptr(origins), ptr(dirs), ptr(max_t),
                                                ptr(t), ptr(tri), ptr(flags)))
         return t, tri, flags
 
@@ -456,6 +473,10 @@ class MultiRenderer:
     def set_config(self, config):
         self._check(lib().rpt_multi_set_config(self._h, C.byref(config)))
         self.config = config.copy()
+
+    def set_shadow_mode(self, mode):
+        """rpt_multi_set_shadow_mode: Renderer.set_shadow_mode on every rank"""
+        self._check(lib().rpt_multi_set_shadow_mode(self._h, mode))
 
     def reset(self, rng_seed, accum_init=None, samples_init=0):
         rng_seed = np.ascontiguousarray(rng_seed, RNG_DTYPE)

@@ -18,6 +18,9 @@
  * and reports, per variant: trips by kind, lanes per trip, wave-uniform share of the inner trips, vector-memory instructions per ray, and wave-instructions
  * per ray from per-body instruction counts (read off the disassembly of the shipped kernels, passed in by the driver).
  *
+ * The SEGMENT rule (rpt.h RPT_SHADOW_SEGMENT, the opt-in walk that is not the reference's): a child box is entered iff the reference's test passes AND
+ * tmin <= max_t.  sim_any_hit_segment and sim_wave_segment are sim_any_hit_order and sim_wave under it; every other export is the exact rule, as before.
+ *
  * Includes the oracle's translation unit for its box / triangle tests and its trace_pixel: analysis, like tools/traversal_sim.py — never the product.
  */
 #include "../oracle/rpt_oracle.cpp"
@@ -26,7 +29,7 @@
 
 namespace {
 
-struct SimRay { V3 o, d; float max_t; };
+struct SimRay { V3 o, d; float max_t; bool segment = false; /* walked under the segment rule (box_hit) */ };
 
 struct SimScene {
     Scene sc;
@@ -91,7 +94,8 @@ SimScene make_sim_scene(const oracle_scene *s) {
 inline bool box_hit(const Scene &sc, uint32_t node, const SimRay &r, float &dist) {
     const rpt_bvh_node &n = sc.nodes[node];
     dist = intersect_aabb(xyz(n.aabb_min), xyz(n.aabb_max), r.o, r.d, 1000000.0f);      /* any-hit: result.t is 1e6 until the walk returns */
-    return !rptm::isinfr(dist);
+    if (rptm::isinfr(dist)) return false;
+    return !r.segment || dist <= r.max_t;                                             /* a hit hands out tmin: the segment rule as rpt.h states it */
 }
 
 /* the same slab test, also handing out tmax (ordering rules only; the hit decision is intersect_aabb's) */
@@ -505,10 +509,11 @@ int sim_learn(const oracle_scene *scene, const float *rays8, uint32_t n, int fin
     return 0;
 }
 
-int sim_wave(const oracle_scene *scene, const float *rays8, uint32_t n, int order, int trips, int refill, uint64_t *out, uint8_t *hit_out) {
+/* sim_wave under the segment rule (segment != 0) or the exact one */
+int sim_wave_segment(const oracle_scene *scene, const float *rays8, uint32_t n, int order, int trips, int refill, uint64_t *out, uint8_t *hit_out, int segment) {
     if (cached != scene) { ss = make_sim_scene(scene); cached = scene; }
     std::vector<SimRay> rays(n);
-    for (uint32_t i = 0; i < n; ++i) rays[i] = SimRay{xyz(rays8 + 8 * i), xyz(rays8 + 8 * i + 3), rays8[8 * i + 6]};
+    for (uint32_t i = 0; i < n; ++i) rays[i] = SimRay{xyz(rays8 + 8 * i), xyz(rays8 + 8 * i + 3), rays8[8 * i + 6], segment != 0};
     SimOut o{};
     Params p{order >= 50 ? 8 : (order >= 30 ? 7 : (order >= 20 ? 2 : order)), trips, refill, order >= 50 ? order - 50 : (order >= 30 ? order - 30 : (order >= 20 ? order - 20 : 0))};
     order = p.order;
@@ -520,14 +525,18 @@ int sim_wave(const oracle_scene *scene, const float *rays8, uint32_t n, int orde
     return (int)(sizeof(o) / sizeof(uint64_t));
 }
 
+int sim_wave(const oracle_scene *scene, const float *rays8, uint32_t n, int order, int trips, int refill, uint64_t *out, uint8_t *hit_out) {
+    return sim_wave_segment(scene, rays8, n, order, trips, refill, out, hit_out, 0);
+}
+
 /* `.hit` of the any-hit query under an arbitrary visiting order (tests/test_anyhit_order.py): mode 0 the reference's walk itself (intersect_front_to_back<false>),
  * 1 left first, 2 right first, 3 far first, 4 a pseudo-random choice per (ray, node), 5 breadth-first over a queue instead of a stack */
-int sim_any_hit_order(const oracle_scene *scene, size_t n, const float *origins, const float *dirs, const float *max_t, int mode, uint32_t seed, uint8_t *hit_out) {
+static int any_hit_order(const oracle_scene *scene, size_t n, const float *origins, const float *dirs, const float *max_t, int mode, uint32_t seed, uint8_t *hit_out, bool segment) {
     Scene sc = make_scene(scene);
     Counters cnt;
     std::vector<uint32_t> work;
     for (size_t i = 0; i < n; ++i) {
-        SimRay r{xyz(origins + 3 * i), xyz(dirs + 3 * i), max_t[i]};
+        SimRay r{xyz(origins + 3 * i), xyz(dirs + 3 * i), max_t[i], segment};
         if (mode == 0) { hit_out[i] = intersect_front_to_back<false>(sc, r.o, r.d, r.max_t, cnt).hit ? 1 : 0; continue; }
         work.clear();
         work.push_back(0u);
@@ -554,6 +563,40 @@ int sim_any_hit_order(const oracle_scene *scene, size_t n, const float *origins,
                 const bool ha = right_first ? hr : hl, hb = right_first ? hl : hr;
                 if (mode == 5) { if (ha) work.push_back(a); if (hb) work.push_back(b); }
                 else { if (hb) work.push_back(b); if (ha) work.push_back(a); }
+            }
+        }
+        hit_out[i] = hit ? 1 : 0;
+    }
+    return 0;
+}
+
+int sim_any_hit_order(const oracle_scene *scene, size_t n, const float *origins, const float *dirs, const float *max_t, int mode, uint32_t seed, uint8_t *hit_out) {
+    return any_hit_order(scene, n, origins, dirs, max_t, mode, seed, hit_out, false);
+}
+
+/* sim_any_hit_order under the segment rule.  Modes 1-5 as there; mode 0 — there the reference's own function, which has no such rule — is the reference's
+ * near-first order (the near child is entered, the far one pushed) walked by this file's loop. */
+int sim_any_hit_segment(const oracle_scene *scene, size_t n, const float *origins, const float *dirs, const float *max_t, int mode, uint32_t seed, uint8_t *hit_out) {
+    if (mode != 0) return any_hit_order(scene, n, origins, dirs, max_t, mode, seed, hit_out, true);
+    Scene sc = make_scene(scene);
+    std::vector<uint32_t> work;
+    for (size_t i = 0; i < n; ++i) {
+        SimRay r{xyz(origins + 3 * i), xyz(dirs + 3 * i), max_t[i], true};
+        work.assign(1, 0u);
+        bool hit = false;
+        while (!hit && !work.empty()) {
+            const uint32_t node = work.back();
+            work.pop_back();
+            const rpt_bvh_node &nd = sc.nodes[node];
+            if (nd.triangle_count > 0) {
+                for (uint32_t k = 0; k < nd.triangle_count && !hit; ++k) hit = tri_accept(sc, nd.left_or_first + k, r);
+            } else {
+                float dl, dr;
+                const bool hl = box_hit(sc, nd.left_or_first, r, dl), hr = box_hit(sc, nd.left_or_first + 1, r, dr);
+                const bool right_first = hr && (!hl || dl > dr);
+                const uint32_t near = right_first ? nd.left_or_first + 1 : nd.left_or_first, far = right_first ? nd.left_or_first : nd.left_or_first + 1;
+                if (right_first ? hl : hr) work.push_back(far);
+                if (right_first ? hr : hl) work.push_back(near);
             }
         }
         hit_out[i] = hit ? 1 : 0;

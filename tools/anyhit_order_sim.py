@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Replay of the streamed any-hit (shadow) walks under the visiting orders the reference's `.hit` leaves free — see tools/anyhit_order_sim.cpp.
 
-usage: python tools/anyhit_order_sim.py [scene ...] [--blocks N] [--samples S] [--bounces 0,1,2,3]
+usage: python tools/anyhit_order_sim.py [scene ...] [--runs N] [--samples S] [--bounces 0,1,2,3] [--segment]
+--segment: every order under the segment rule of RPT_SHADOW_SEGMENT as well (a child box is entered only if also tmin <= max_t; rpt.h rpt_set_shadow_mode): the
+tables are the bounded walk's, and a last table per scene sets it against the exact walk (profiles/r10_anyhit_sim_segment.txt: --runs 12 --samples 4 --segment).
 Scenes: DarkCornell (LDS walk: trips 16 / refill 16), VeachMIS, scatter (global-memory walks: trips 8 / refill 24).
 Rays: the shadow rays the oracle's trace_pixel traces for S samples of runs of 8 x 8 pixel blocks, in the order the shade stage queues them
 (a wave's 64 slots = one block at one sample index; sample-major inside a block run), cut into spans of 512 queue positions = one wave's share.
@@ -84,6 +86,7 @@ def main():
     ap.add_argument("--samples", type=int, default=8)
     ap.add_argument("--bounces", default="0,1,2,3")
     ap.add_argument("--span", type=int, default=512)
+    ap.add_argument("--segment", action="store_true", help="replay the segment-bounded walk and compare it with the exact one")
     ap.add_argument("--all-rays", action="store_true", help="include the shadow rays whose NEE term is zero whatever the walk finds (the device elides them, k_shade.h)")
     args = ap.parse_args()
     sim = build()
@@ -99,6 +102,8 @@ def main():
         runs = [(int(rng.integers(0, W // 8 - 4)), int(rng.integers(0, H // 8))) for _ in range(args.runs)]
         print(f"\n=== {name} {W}x{H} nee = MIS: {args.runs} runs of 4 blocks x {args.samples} samples, spans of {args.span}; walk = {kind} (trips {trips}, refill at {refill} idle lanes)")
         total = {b: np.zeros((len(ORDERS), len(FIELDS)), np.float64) for b in ["all"]}
+        total_exact = np.zeros((len(ORDERS), len(FIELDS)), np.float64)         # --segment: the same spans under the exact rule
+        lost = gained = 0
         per_bounce = {}
         spans_of = {}
         for bounce in [int(b) for b in args.bounces.split(",")]:
@@ -128,7 +133,17 @@ def main():
                 for o in range(len(ORDERS)):
                     out = np.zeros(24, np.uint64)
                     hit = np.zeros(len(span), np.uint8)
-                    nf = sim.sim_wave(C.byref(sc), _p(span), C.c_uint32(len(span)), ORDER_CODE[o], trips, refill, _p(out), _p(hit))
+                    if args.segment:
+                        out_e = np.zeros(24, np.uint64)
+                        hit_e = np.zeros(len(span), np.uint8)
+                        sim.sim_wave(C.byref(sc), _p(span), C.c_uint32(len(span)), ORDER_CODE[o], trips, refill, _p(out_e), _p(hit_e))
+                        total_exact[o] += out_e[:len(FIELDS)].astype(np.float64)
+                        nf = sim.sim_wave_segment(C.byref(sc), _p(span), C.c_uint32(len(span)), ORDER_CODE[o], trips, refill, _p(out), _p(hit), 1)
+                        if o == 0:
+                            lost += int(((hit_e == 1) & (hit == 0)).sum())
+                            gained += int(((hit_e == 0) & (hit == 1)).sum())
+                    else:
+                        nf = sim.sim_wave(C.byref(sc), _p(span), C.c_uint32(len(span)), ORDER_CODE[o], trips, refill, _p(out), _p(hit))
                     assert nf == len(FIELDS), nf
                     if ref_hit is None:
                         ref_hit = hit
@@ -141,7 +156,35 @@ def main():
             total["all"] += acc
             total["all"][:, FIELDS.index("max_stack")] = ms
             report(f"bounce {bounce} ({len(spans)} spans)", acc, cost)
-        report("all bounces", total["all"], cost)
+        report("all bounces" + (" (segment rule)" if args.segment else ""), total["all"], cost)
+        if args.segment:
+            total_exact[:, FIELDS.index("max_stack")] = 0
+            compare(name, total_exact, total["all"], cost, lost, gained)
+
+
+def per_ray(a, o, oname, cost):
+    """wave-instructions and vector-memory instructions per ray of one order's totals (the per-body costs above)"""
+    f = {k: i for i, k in enumerate(FIELDS)}
+    rays = a[f["rays"]]
+    it, iu = a[f["inner_trips"]], a[f["inner_uniform"]]
+    lt, li = a[f["leaf_trips"]], a[f["leaf_iters"]]
+    fixed = o in (1, 2) or 7 <= o < 12 or o >= 24
+    body = cost["inner"] - (cost["order_saving"] if fixed else 0)
+    body_u = cost["inner_uniform"] - (cost["order_saving"] if fixed else 0)
+    inst = (it - iu) * body + iu * body_u + li * cost["tri"] + lt * cost["leaf"] + (it + lt) * cost["trip"] + a[f["refills"]] * cost["refill"]
+    vmem = (it - iu) * cost["vmem_inner"] + li * cost["vmem_tri"] + a[f["pop_trips"]] * cost["vmem_pop"]
+    return inst / rays, vmem / rays, a[f["visits_clear"]] / max(a[f["rays_clear"]], 1), a[f["visits_occluded"]] / max(a[f["occluded"]], 1)
+
+
+def compare(name, exact, segment, cost, lost, gained):
+    """the per-lane-stack orders the kernels can take (near first, more opaque first), exact rule -> segment rule"""
+    print(f"  {name}: exact walk -> segment-bounded walk, all bounces; .hit of the bounded walk against the exact one on these rays: lost {lost}, gained {gained}")
+    print(f"    {'order':18s} {'wave-inst/ray':>24s} {'visits clear':>16s} {'visits occluded':>16s} {'vmem/ray':>22s}")
+    for o in (0, 7):
+        ie, ve, ce, oe = per_ray(exact[o], o, ORDERS[o], cost)
+        i_s, vs, cs, os_ = per_ray(segment[o], o, ORDERS[o], cost)
+        vm = f"{ve:.2f} -> {vs:.2f} ({100 * (vs / ve - 1):+.0f} %)" if ve else "-"
+        print(f"    {ORDERS[o]:18s} {ie:7.1f} -> {i_s:5.1f} ({100 * (i_s / ie - 1):+.0f} %) {ce:7.1f} -> {cs:5.1f} {oe:7.1f} -> {os_:5.1f} {vm:>22s}")
 
 
 def report(title, acc, cost):
