@@ -218,6 +218,7 @@ struct DevQueues {
     uint32_t known_length;    /* the call enqueues exactly max_bounces iterations (no slot takes a second sample): every traversed path of iteration i is at bounce i */
     uint32_t sky_at_end;      /* a batch of known length: misses only END paths, so they wait in the queue for ONE sky launch after the last iteration */
     uint32_t sky_wide_limit;  /* up to this many queued misses the sky march runs 16 lanes per miss */
+    uint32_t sky_shard_shift; /* log2 of the slots a workgroup of this call's shade stage owns (8, packed variant 11): slot s is pushed into shard (s >> this) % RPT_Q_SHARDS */
     unsigned long long *ray_shards;  /* RPT_STAT_SHARDS x RPT_STAT_STRIDE: extension rays traced */
     unsigned long long *host_ring;   /* mapped pinned host memory: (iteration + 1) << 32 | extension-queue size */
     uint32_t ring_mask;

@@ -56,6 +56,25 @@ __device__ __forceinline__ void start_first_path(const DevState &st, const DevCo
     st.ray_b[slot] = make_float2(rd.y, rd.z);
     st.hit[slot] = make_float2(0.0f, __uint_as_float(HIT_PENDING));
 }
+/* The same for a slot that the first walk of a render call takes itself (k_traverse.h k_traverse_nearest_stream FIRST: no k_generate_first pass over the slots,
+ * no ray and hit word written only to be read back by the next launch).  `word` is the slot's hit word: anything but HIT_IDLE is a sample the previous call
+ * left in flight, counted where k_generate_first counts it.  Returns false for a slot that takes no sample in this call — the padding of the last chunk of 64
+ * pixels, k >= n_samples — which stays idle; else the camera ray is in (ro, rd) and in the slot's ray record, which every later stage reads. */
+__device__ __forceinline__ bool begin_first_path(const DevState &st, const DevConfig &cfg, DevStats *stats, uint32_t slot, uint32_t word, uint32_t n_samples,
+                                                 F3 &ro, F3 &rd) {
+    if (word != HIT_IDLE) atomicAdd(&stats->undrained, 1ull);
+    const uint32_t k = slot_k(st, slot), pix = slot_pix(st, slot);
+    if (pix >= st.n_pixels || k >= n_samples) {
+        if (word != HIT_IDLE) st.hit[slot] = make_float2(0.0f, __uint_as_float(HIT_IDLE));
+        return false;
+    }
+    const uint2 rs = st.rng[pix];
+    const uint32_t pxy = st.pixel_xy[pix];
+    camera_ray(cfg, pxy & 0xffffu, pxy >> 16, rs.x + k + rs.y, ro, rd);
+    st.ray_a[slot] = make_float4(ro.x, ro.y, ro.z, rd.x);
+    st.ray_b[slot] = make_float2(rd.y, rd.z);
+    return true;
+}
 /* samples slot `slot` owes after its first one in a call of n_samples (the slot has one: it was started) */
 __device__ __forceinline__ uint32_t first_path_todo(const DevState &st, uint32_t slot, uint32_t n_samples) {
     const uint32_t S = 1u << st.group_shift;

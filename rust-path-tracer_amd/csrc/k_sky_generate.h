@@ -197,12 +197,14 @@ __global__ __launch_bounds__(RPT_BLOCK) void k_sky(DevScene sc, DevState st, Dev
 
 /* Start of an rpt_render call: slot k of every pixel begins sample k; it will take samples k, k+S, ... of
  * the n_samples this call owes the pixel. */
-__global__ __launch_bounds__(RPT_BLOCK) void k_generate_first(DevState st, DevQueues q, DevConfig cfg, uint32_t n_samples, DevStats *stats) {
+/* counters_only (a one-workgroup launch): the call's first walk starts the paths itself (k_traverse.h k_traverse_nearest_stream FIRST, k_path.h begin_first_path)
+ * and this launch only opens the call — the persistent walk cannot zero the pool counter it is about to draw from. */
+__global__ __launch_bounds__(RPT_BLOCK) void k_generate_first(DevState st, DevQueues q, DevConfig cfg, uint32_t n_samples, DevStats *stats, uint32_t counters_only) {
     uint32_t slot = blockIdx.x * RPT_BLOCK + threadIdx.x;
     if (blockIdx.x == 0u)                                     /* queue counters and flags of the new call (no kernel of this call has run yet) */
         for (uint32_t k = threadIdx.x; k < (uint32_t)Q_COUNT; k += RPT_BLOCK) q.count[k] = 0u;
     if (blockIdx.x == 0u && threadIdx.x < RPT_Q_SHARDS) q.sky_cnt[threadIdx.x * RPT_Q_SHARD_STRIDE] = q.shadow_cnt[threadIdx.x * RPT_Q_SHARD_STRIDE] = 0u;
-    if (slot >= st.n_slots) return;
+    if (counters_only != 0u || slot >= st.n_slots) return;
     /* Every slot must have been left idle by the previous render call: an asynchronous batch enqueues a fixed number of
      * iterations (max_bounces, + 1 with several slots per pixel) without ever looking at a progress report, so this is
      * where a wrong bound would show — a sample still in flight here would be overwritten and lost. */

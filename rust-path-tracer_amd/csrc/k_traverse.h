@@ -883,7 +883,10 @@ template <int STACK, int THREADS, int MODE = RPT_NEAREST_PLAIN>
 __attribute__((amdgpu_num_sgpr(RPT_LDS_WALK_SGPRS)))
 __global__ __launch_bounds__(THREADS) void k_traverse_nearest_stream(DevScene sc, DevState st, DevQueues q, uint32_t iteration,
                                                                        uint32_t SPAN /* slots a workgroup fetches at a time */,
-                                                                       float cam_x, float cam_y, float cam_z /* FIRST: the origin of every ray of the launch */) {
+                                                                       float cam_x, float cam_y, float cam_z /* FIRST: the origin of every ray of the launch */,
+                                                                       DevConfig cfg, uint32_t gen_samples /* FIRST: the call's sample count when the walk starts the first
+                                                                       paths itself (wave-uniform; 0: the slots were prepared by k_generate_first, HIT_PENDING) */,
+                                                                       DevStats *stats) {
     constexpr bool LAST = MODE == RPT_NEAREST_LAST, FIRST = MODE == RPT_NEAREST_FIRST;
     constexpr uint32_t NW = THREADS / RPT_WAVE;
     __shared__ uint16_t lds_stack[NW][STACK][RPT_WAVE];
@@ -931,11 +934,55 @@ __global__ __launch_bounds__(THREADS) void k_traverse_nearest_stream(DevScene sc
     bool have = false;                                         /* this lane holds a ray whose result is not written yet */
     bool pool_open = true;                                     /* wave-uniform: the launch may still have slots */
     uint32_t traced = 0u;                                      /* wave-uniform */
-    /* LAST: a hit-or-miss lane that hit knows what the shade stage's last iteration would find out from the triangle's material — not an emitter, the sample
-     * is finished with the radiance it has — and with several slots per pixel says so itself (HIT_DONE: k_shade.h, the `else` of the last iteration) */
+    /* LAST with several slots per pixel: the walk ENDS its paths — no shade launch follows it (rpt_hip.hip launch_iteration).  Where a lane writes its result it does
+     * what the shade stage's last iteration did with it (k_shade.h shade_slot, `last_iteration`):
+     *   a hit-or-miss lane that hit: not an emitter, the sample is finished with the radiance it has — HIT_DONE;
+     *   a lane that walked to the end and hit: the emission of a front-facing emitter is added (lib.rs:86-100), then HIT_DONE;
+     *   a miss: the slot goes to the sky queue (last_park below) and waits there as HIT_PARKED for the batch's one k_sky launch.
+     * With one slot per pixel (done_here false) the hit record is written for the shade launch that follows, as in every other launch. */
     const bool done_here = LAST && st.group_shift != 0u;
-    auto last_word = [&](const HitRecord &r, uint32_t stopped) {
-        return (done_here && stopped != 0u && r.tri != HIT_MISS) ? make_float2(0.0f, __uint_as_float(HIT_DONE)) : make_float2(r.t, __uint_as_float(r.tri));
+    auto last_finish = [&](uint32_t s, const HitRecord &r, uint32_t stopped) -> bool {      /* true: a miss, to be parked */
+        if (!done_here) {
+            st.hit[s] = make_float2(r.t, __uint_as_float(r.tri));
+            return false;
+        }
+        if (r.tri == HIT_MISS) return true;
+        if (stopped == 0u) {
+            const uint32_t m = __float_as_uint(sc.tri_shade[4u * (r.tri & 0x7fffffffu) + 2u].w);
+            const float4 e4 = sc.textured != 0u ? sc.materials[6u * m] : sc.mat_lite[2u * m];
+            if ((e4.x != 0.0f || e4.y != 0.0f || e4.z != 0.0f) && (r.tri >> 31) == 0u) {
+                float4 r4 = st.rad[s];
+                const float4 tf = st.thr[s];
+                const F3 radiance = f3(r4.x, r4.y, r4.z) + mask_nan3(f3(tf.x, tf.y, tf.z) * f3(e4.x, e4.y, e4.z));
+                r4.x = radiance.x; r4.y = radiance.y; r4.z = radiance.z;
+                st.rad[s] = r4;                                 /* (samples owed: kept) */
+            }
+        }
+        st.hit[s] = make_float2(0.0f, __uint_as_float(HIT_DONE));
+        return false;
+    };
+    /* The sky queue's reservations, by the whole wave (every lane calls it, converged).  A slot is reserved in the shard the shade stage of this batch uses for
+     * it — workgroup b of k_shade pushes into shard b % RPT_Q_SHARDS and owns 1 << q.sky_shard_shift slots (256, packed variant 2 048) — and a slot misses at
+     * most once per batch, so a shard never receives more entries than its workgroups own slots: the bound RPT_Q_SLACK was sized for.  One returning atomic per
+     * wave and shard: the lanes of a wave took their slots in runs of consecutive ones, so a few shards cover them. */
+    auto last_park = [&](bool park, uint32_t s) {
+        const uint32_t shard = (s >> q.sky_shard_shift) % RPT_Q_SHARDS;
+        unsigned long long todo_m = rpt_ballot(park);
+        while (todo_m != 0ull) {                               /* wave-uniform */
+            const uint32_t leader = (uint32_t)__ffsll((long long)todo_m) - 1u;
+            const uint32_t sh = (uint32_t)__builtin_amdgcn_readlane((int)shard, (int)leader);
+            const bool mine = park && shard == sh;
+            const unsigned long long same = rpt_ballot(mine);
+            uint32_t e = 0u;
+            if (lane == leader) e = atomicAdd(&q.sky_cnt[sh * RPT_Q_SHARD_STRIDE], (uint32_t)__popcll(same));
+            e = (uint32_t)__builtin_amdgcn_readlane((int)e, (int)leader);
+            if (mine) {
+                e += __builtin_amdgcn_mbcnt_hi((uint32_t)(same >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)same, 0u));
+                q.sky[q_position(sh, e)] = s;
+                st.hit[s] = make_float2(0.0f, __uint_as_float(HIT_PARKED));
+            }
+            todo_m &= ~same;
+        }
     };
     for (;;) {
         const unsigned long long idle_m = rpt_ballot(w.cur == LDS_DESC_DEAD);
@@ -948,18 +995,37 @@ __global__ __launch_bounds__(THREADS) void k_traverse_nearest_stream(DevScene sc
             got = (uint32_t)__builtin_amdgcn_readfirstlane((int)got);
             pool_open = __builtin_amdgcn_readfirstlane((int)finished) == 0;
             bool took = false;
+            if (LAST) {
+                const bool writes = w.cur == LDS_DESC_DEAD && have;
+                bool park = false;
+                if (writes) {
+                    park = last_finish(slot, w.res, stop_first);
+                    have = false;
+                }
+                if (done_here) last_park(park, slot);
+            }
             if (w.cur == LDS_DESC_DEAD) {
-                if (have) {
-                    st.hit[slot] = last_word(w.res, stop_first);
+                if (!LAST && have) {
+                    st.hit[slot] = make_float2(w.res.t, __uint_as_float(w.res.tri));
                     have = false;
                 }
                 const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle_m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle_m, 0u));
                 if (rank < got) {
                     const uint32_t cand = base + rank;
-                    if (__float_as_uint(st.hit[cand].y) == HIT_PENDING) {
-                        const float4 ra = st.ray_a[cand];
-                        const float2 rb = st.ray_b[cand];
-                        ro = f3(ra.x, ra.y, ra.z); rd = f3(ra.w, rb.x, rb.y);
+                    const uint32_t word = __float_as_uint(st.hit[cand].y);
+                    bool pending;
+                    if (FIRST && gen_samples != 0u) {
+                        /* the slot's first path of the call begins here: its camera ray is a function of (slot, rng[pixel]) (k_path.h) */
+                        pending = begin_first_path(st, cfg, stats, cand, word, gen_samples, ro, rd);
+                    } else {
+                        pending = word == HIT_PENDING;
+                        if (pending) {
+                            const float4 ra = st.ray_a[cand];
+                            const float2 rb = st.ray_b[cand];
+                            ro = f3(ra.x, ra.y, ra.z); rd = f3(ra.w, rb.x, rb.y);
+                        }
+                    }
+                    if (pending) {
                         slot = cand;
                         took = true;
                         if (fastdiv_ray_ok(sc.fastdiv_ok, ro, rd)) {
@@ -983,7 +1049,14 @@ __global__ __launch_bounds__(THREADS) void k_traverse_nearest_stream(DevScene sc
                             LdsWalk alone;
                             lds_walk_begin(view, alone);
                             lds_walk_run<STACK, false, false, false, false, FIRST>(view, alone, ro, rd, rd, 0.0f, stack, 0x7fffffff);
-                            st.hit[cand] = make_float2(alone.res.t, __uint_as_float(alone.res.tri));
+                            if (LAST) {
+                                /* the reference's walk to its end; the lane stays idle and ends the path where it next writes (the next refill, or the tail) */
+                                w.res = alone.res;
+                                stop_first = 0u;
+                                have = true;
+                            } else {
+                                st.hit[cand] = make_float2(alone.res.t, __uint_as_float(alone.res.tri));
+                            }
                         }
                     }
                 }
@@ -999,7 +1072,13 @@ __global__ __launch_bounds__(THREADS) void k_traverse_nearest_stream(DevScene sc
         if (LAST) lds_walk_run<STACK, false, true, false, true>(view, w, ro, rd, ird, 0.0f, stack, pool_open ? RPT_STREAM_TRIPS : 0x7fffffff, img_lane, stop_first, order_bias);
         else lds_walk_run<STACK, false, true, false, false, FIRST>(view, w, ro, rd, ird, 0.0f, stack, pool_open ? RPT_STREAM_TRIPS : 0x7fffffff);
     }
-    if (have) st.hit[slot] = last_word(w.res, stop_first);
+    if (LAST) {
+        bool park = false;
+        if (have) park = last_finish(slot, w.res, stop_first);
+        if (done_here) last_park(park, slot);
+    } else if (have) {
+        st.hit[slot] = make_float2(w.res.t, __uint_as_float(w.res.tri));
+    }
     /* ray accounting + the alive flag, once per wave */
     if (lane == 0u && traced != 0u) {
         raise_flag(&q.count[Q_ALIVE0 + (iteration & 1u) * Q_LINE]);

@@ -216,6 +216,7 @@ struct rpt_ctx {
     DevState state{};
     DevQueues queues{};
     uint32_t samples = 0;
+    bool first_walk_starts = false;   /* the current / last render call was opened without a pass over the slots: its first walk starts the paths (rpt_first_walk_starts_paths) */
     uint32_t call_samples = 0;  /* n_samples of the current / last rpt_render call (the shade stage of its first iteration derives what a slot owes) */
 
     /* scheduling: the traversal kernel reports each iteration's queue size into mapped pinned memory */
@@ -237,8 +238,13 @@ struct rpt_ctx {
 };
 
 /* rpt_traverse.hip: the traversal stages (which walk kernel for the context's scene, on which grid) */
-void rpt_launch_nearest(rpt_ctx *c, uint32_t iteration, bool last_without_nee /* the last extension rays of a batch of known length, no NEE */,
-                        bool camera_rays /* iteration 0 of a render call: every ray leaves cfg.cam_position */);
+/* rpt_launch_nearest returns true when the launch it made also ENDED the paths it walked, so that no shade launch follows it in that iteration: the LAST
+ * walk of an LDS-resident scene with several slots per pixel (emission added, HIT_DONE / sky queue written by the walk itself).
+ * start_paths: iteration 0 of a call whose slots k_generate_first did not prepare (rpt_first_walk_starts_paths: the FIRST walk computes each slot's
+ * camera ray where it takes the slot; render_impl then opens the call with a one-workgroup k_generate_first that only zeroes the counters). */
+bool rpt_launch_nearest(rpt_ctx *c, uint32_t iteration, bool last_without_nee /* the last extension rays of a batch of known length, no NEE */,
+                        bool camera_rays /* iteration 0 of a render call: every ray leaves cfg.cam_position */, bool start_paths);
+bool rpt_first_walk_starts_paths(const rpt_ctx *c);
 void rpt_launch_shadow(rpt_ctx *c);
 void rpt_launch_trace_debug(rpt_ctx *c, int any_hit /* 0 nearest, 1 any-hit, 2 segment-bounded any-hit */, uint32_t n, const float *origins, const float *dirs, const float *max_t, float *out_t, uint32_t *out_tri,
                             uint32_t *out_flags);

@@ -143,7 +143,7 @@ int rpt_debug_trace_rays_production(rpt_ctx *c, size_t n, const float *origins, 
     hipStream_t s = c->stream;
     RPT_TRY(rpt_idle_all_slots(c));
     k_debug_load_rays<<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(c->state, (uint32_t)n, d_o.p, d_d.p);
-    rpt_launch_nearest(c, 0u, false, false);
+    rpt_launch_nearest(c, 0u, false, false, false);
     std::vector<float2> hits(n);
     HIP_TRY(c, hipStreamSynchronize(s));
     HIP_TRY(c, hipGetLastError());

@@ -157,19 +157,22 @@ static void launch_complete(rpt_ctx *c, uint32_t iteration, uint32_t final_pass)
                                                                                                                      c->dev_stats.p);
 }
 
+/* returns the shade launches it made: 1, or 0 where the walk ended its paths itself (rpt_launch_nearest) */
 template <int NEE, bool TEXTURED>
-void launch_iteration(rpt_ctx *c, uint32_t iteration, uint32_t blocks, bool complete_each, bool sky_now) {
+uint32_t launch_iteration(rpt_ctx *c, uint32_t iteration, uint32_t blocks, bool complete_each, bool sky_now) {
     hipStream_t s = c->stream;
     StageTimer &t = c->timing;
     t.mark(s, StageTimer::NONE, StageTimer::AT_2);
     /* the consumers of a side queue cover its POSITIONS: up to RPT_Q_SLACK more than there are slots (k_common.h) */
     const uint32_t blocks_q = rpt_blocks(c->n_slots + RPT_Q_SLACK);
     /* (the shade stage's last_iteration, k_shade.h: in a batch of known length iteration k is bounce k of every path) */
-    rpt_launch_nearest(c, iteration, NEE == RPT_NEE_NONE && c->queues.known_length != 0u && iteration != 0u && iteration + 1u >= c->cfg.c.max_bounces,
-                       iteration == 0u);
+    const bool ended = rpt_launch_nearest(c, iteration, NEE == RPT_NEE_NONE && c->queues.known_length != 0u && iteration != 0u && iteration + 1u >= c->cfg.c.max_bounces,
+                                          iteration == 0u, iteration == 0u && c->first_walk_starts);
     t.mark(s, RPT_STAGE_TRAVERSE, StageTimer::AT_1 | StageTimer::AT_2);
-    if (c->shade_compact) k_shade<NEE, TEXTURED, true><<<(c->n_slots + RPT_BLOCK * RPT_SHADE_ROUNDS - 1) / (RPT_BLOCK * RPT_SHADE_ROUNDS), RPT_BLOCK, 0, s>>>(c->scene, c->state, c->queues, c->cfg, iteration, c->dev_stats.p, c->call_samples);
-    else k_shade<NEE, TEXTURED, false><<<blocks, RPT_BLOCK, 0, s>>>(c->scene, c->state, c->queues, c->cfg, iteration, c->dev_stats.p, c->call_samples);
+    if (!ended) {                                           /* (ended: nothing is left for a shade stage, every path of the launch is HIT_DONE or waits in the sky queue) */
+        if (c->shade_compact) k_shade<NEE, TEXTURED, true><<<(c->n_slots + RPT_BLOCK * RPT_SHADE_ROUNDS - 1) / (RPT_BLOCK * RPT_SHADE_ROUNDS), RPT_BLOCK, 0, s>>>(c->scene, c->state, c->queues, c->cfg, iteration, c->dev_stats.p, c->call_samples);
+        else k_shade<NEE, TEXTURED, false><<<blocks, RPT_BLOCK, 0, s>>>(c->scene, c->state, c->queues, c->cfg, iteration, c->dev_stats.p, c->call_samples);
+    }
     /* generations are completed (and the next samples started) after every shade stage only where slots take more than one
      * sample in this call; a batch of known length completes them once, after its last iteration (render_impl) */
     if (complete_each) launch_complete(c, iteration, 0u);
@@ -181,24 +184,22 @@ void launch_iteration(rpt_ctx *c, uint32_t iteration, uint32_t blocks, bool comp
         else k_sky<false><<<blocks_q, RPT_BLOCK, 0, s>>>(c->scene, c->state, c->queues, c->cfg, iteration, c->dev_stats.p);
     }
     t.mark(s, RPT_STAGE_SKY, StageTimer::AT_1);
+    return ended ? 0u : 1u;
 }
 
 /* one iteration with the shade stage built for the context's NEE mode and scene (the walks pick their stack width themselves: rpt_traverse.hip) */
-static void dispatch_iteration(rpt_ctx *c, uint32_t iteration, uint32_t blocks, bool complete_each, bool sky_now) {
+static uint32_t dispatch_iteration(rpt_ctx *c, uint32_t iteration, uint32_t blocks, bool complete_each, bool sky_now) {
     const bool tex = c->scene.textured != 0u;
     switch (c->cfg.nee_mode) {
         case RPT_NEE_MIS:
-            if (tex) launch_iteration<RPT_NEE_MIS, true>(c, iteration, blocks, complete_each, sky_now);
-            else launch_iteration<RPT_NEE_MIS, false>(c, iteration, blocks, complete_each, sky_now);
-            break;
+            return tex ? launch_iteration<RPT_NEE_MIS, true>(c, iteration, blocks, complete_each, sky_now)
+                       : launch_iteration<RPT_NEE_MIS, false>(c, iteration, blocks, complete_each, sky_now);
         case RPT_NEE_DIRECT:
-            if (tex) launch_iteration<RPT_NEE_DIRECT, true>(c, iteration, blocks, complete_each, sky_now);
-            else launch_iteration<RPT_NEE_DIRECT, false>(c, iteration, blocks, complete_each, sky_now);
-            break;
+            return tex ? launch_iteration<RPT_NEE_DIRECT, true>(c, iteration, blocks, complete_each, sky_now)
+                       : launch_iteration<RPT_NEE_DIRECT, false>(c, iteration, blocks, complete_each, sky_now);
         default:
-            if (tex) launch_iteration<RPT_NEE_NONE, true>(c, iteration, blocks, complete_each, sky_now);
-            else launch_iteration<RPT_NEE_NONE, false>(c, iteration, blocks, complete_each, sky_now);
-            break;
+            return tex ? launch_iteration<RPT_NEE_NONE, true>(c, iteration, blocks, complete_each, sky_now)
+                       : launch_iteration<RPT_NEE_NONE, false>(c, iteration, blocks, complete_each, sky_now);
     }
 }
 
@@ -532,10 +533,10 @@ static int await_progress(rpt_ctx *c, uint64_t j, bool &drained) {
 }
 
 /* what a render call of `iterations` iterations adds to the statistics, enqueued or finished */
-static void count_batch(rpt_ctx *c, uint32_t n_samples, uint64_t iterations, std::chrono::steady_clock::time_point t0) {
+static void count_batch(rpt_ctx *c, uint32_t n_samples, uint64_t iterations, uint64_t shade_launches, std::chrono::steady_clock::time_point t0) {
     c->stats.iterations += iterations;
     c->stats.kernel_launches[RPT_STAGE_TRAVERSE] += iterations;
-    c->stats.kernel_launches[RPT_STAGE_SHADE] += iterations;
+    c->stats.kernel_launches[RPT_STAGE_SHADE] += shade_launches;      /* (one per iteration, but none behind a walk that ended its paths itself) */
     c->stats.kernel_launches[RPT_STAGE_SHADOW] += c->cfg.nee_mode != RPT_NEE_NONE ? iterations : 0;
     c->stats.kernel_launches[RPT_STAGE_SKY] += c->queues.sky_at_end ? 1u : iterations;
     c->samples += n_samples;
@@ -572,8 +573,14 @@ static int render_impl(rpt_ctx *c, uint32_t n_samples, bool allow_async) {
      * wait in the queue for ONE sky launch after the last iteration (three launches less per batch) */
     c->queues.sky_at_end = known_iterations != 0 ? 1u : 0u;
     c->queues.known_length = known_iterations != 0 ? 1u : 0u;
+    /* the shard of the sky queue a slot is pushed into: by its workgroup of the shade stage, whichever variant this call launches */
+    c->queues.sky_shard_shift = c->shade_compact ? 11u : 8u;
+    static_assert(RPT_BLOCK == 1 << 8 && RPT_BLOCK * RPT_SHADE_ROUNDS == 1 << 11, "sky_shard_shift: slots per workgroup of k_shade");
     t.mark(s, StageTimer::NONE, StageTimer::AT_1);
-    k_generate_first<<<blocks, RPT_BLOCK, 0, s>>>(c->state, c->queues, c->cfg, n_samples, c->dev_stats.p);
+    /* The stage that opens a render call.  Where the first walk starts the paths itself (an LDS-resident scene, several slots per pixel) it is ONE workgroup
+     * that zeroes the call's counters; else a pass over all slots that also writes every slot's camera ray. */
+    c->first_walk_starts = rpt_first_walk_starts_paths(c);
+    k_generate_first<<<c->first_walk_starts ? 1u : blocks, RPT_BLOCK, 0, s>>>(c->state, c->queues, c->cfg, n_samples, c->dev_stats.p, c->first_walk_starts ? 1u : 0u);
     c->stats.kernel_launches[RPT_STAGE_GENERATE] += 1;
     t.mark(s, RPT_STAGE_GENERATE, StageTimer::AT_1);
 
@@ -588,11 +595,11 @@ static int render_impl(rpt_ctx *c, uint32_t n_samples, bool allow_async) {
     /* SAFETY NET against a stuck pipeline (a bug), far above the worst case — every sample needs max_bounces iterations, one after
      * another — and above what deferral of sky work can cost */
     const uint64_t it_limit = (uint64_t)n_samples * (uint64_t)(c->cfg.c.max_bounces + 2u) * 16u + 4096u;
-    uint64_t it = 0;
+    uint64_t it = 0, shade_launches = 0;
     bool drained = c->cfg.c.max_bounces == 0u;
     while (!drained) {
         HIP_TRY_TO(c->error, "hipEventCreate(&e): ", t.take_error());
-        dispatch_iteration(c, (uint32_t)it, blocks, complete_each, it + 1 == planned /* (sky_at_end: the one sky launch of the batch) */);
+        shade_launches += dispatch_iteration(c, (uint32_t)it, blocks, complete_each, it + 1 == planned /* (sky_at_end: the one sky launch of the batch) */);
         it += 1;
         if (it == planned) {             /* (no report needed: nothing can be left) */
             /* every path of the batch has ended (max_bounces iterations, side stages included): the one completion of the batch */
@@ -611,7 +618,7 @@ static int render_impl(rpt_ctx *c, uint32_t n_samples, bool allow_async) {
     HIP_TRY_TO(c->error, "hipEventCreate(&e): ", t.take_error());
     if (async) {                         /* its stage times are read by rpt_wait */
         c->async_pending = true;
-        count_batch(c, n_samples, it, t0);
+        count_batch(c, n_samples, it, shade_launches, t0);
         return RPT_OK;
     }
     /* a call that enqueued a fixed number of iterations must have left every slot idle: cross-check of that bound */
@@ -619,7 +626,7 @@ static int render_impl(rpt_ctx *c, uint32_t n_samples, bool allow_async) {
         k_check_drained<<<blocks, RPT_BLOCK, 0, s>>>(c->hit.p, c->n_slots, c->dev_stats.p);
     HIP_TRY(c, hipStreamSynchronize(s));
     HIP_TRY(c, hipGetLastError());
-    count_batch(c, n_samples, it, t0);
+    count_batch(c, n_samples, it, shade_launches, t0);
     t.read_into(c->stats.kernel_ms);
     /* (an undrained count can only be non-zero for a call that enqueued a fixed number of iterations) */
     return refresh_device_stats(c, "wavefront not drained after its known number of iterations");

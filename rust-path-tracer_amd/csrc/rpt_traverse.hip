@@ -1,7 +1,7 @@
 /*
  * rpt_traverse.hip — the traversal stages of librpt_hip.so: which kernel of k_traverse.h walks the extension rays / the shadow rays of a context's scene,
  * and on which grid.  Its own translation unit since round 6 (the walk kernels are half of the library's compile time; the three units build in parallel).
- * Entry points (rpt_ctx.h): rpt_launch_nearest, rpt_launch_shadow, rpt_launch_trace_debug, rpt_last_walk_attributes.
+ * Entry points (rpt_ctx.h): rpt_launch_nearest, rpt_first_walk_starts_paths, rpt_launch_shadow, rpt_launch_trace_debug, rpt_last_walk_attributes.
  */
 #include <hip/hip_runtime.h>
 
@@ -73,20 +73,25 @@ static void launch_nearest_gstream(rpt_ctx *c, uint32_t iteration) {
  *   a scene whose traversal image lives in LDS : the persistent streamed LDS walk (FIRST: camera rays; LAST: the last rays of a batch without NEE)
  *   a pair-shaped node pool (every pool the reference's builder makes)  : the streamed global-memory walk over pair records
  *   any other tree (a foreign builder's pool)  : the generic one-ray-per-lane walk over the uploaded nodes */
+/* Returns true when the launch ENDS the paths it walked (the LAST walk with several slots per pixel: no shade launch follows it). */
 template <int STACK>
-void launch_nearest(rpt_ctx *c, uint32_t iteration, bool last_without_nee = false /* the last extension rays of a batch of known length, no NEE */,
-                    bool camera_rays = false /* iteration 0 of a render call: every ray leaves cfg.cam_position */) {
+bool launch_nearest(rpt_ctx *c, uint32_t iteration, bool last_without_nee = false /* the last extension rays of a batch of known length, no NEE */,
+                    bool camera_rays = false /* iteration 0 of a render call: every ray leaves cfg.cam_position */,
+                    bool start_paths = false /* camera_rays, and the slots were NOT prepared by k_generate_first: rpt_first_walk_starts_paths */) {
     hipStream_t s = c->stream;
+    DevStats *stats = c->dev_stats.p;
     if (STACK == 16 && c->scene.lds_scene) {
         const size_t lds_bytes = (size_t)c->scene.lds_vecs * sizeof(float4);
         uint32_t grid;
         const uint32_t span = lds_stream_span(c, grid);
         const float *cam = c->cfg.c.cam_position;
-        if (last_without_nee && c->scene.last_emit_n <= RPT_LAST_EMIT_MAX)
-            k_traverse_nearest_stream<16, LDS_THREADS, RPT_NEAREST_LAST><<<grid, LDS_THREADS, lds_bytes + (size_t)c->scene.last_flip_vecs * sizeof(float4), s>>>(c->scene, c->state, c->queues, iteration, span, 0.0f, 0.0f, 0.0f);
-        else if (camera_rays)
-            k_traverse_nearest_stream<16, LDS_THREADS, RPT_NEAREST_FIRST><<<grid, LDS_THREADS, lds_bytes, s>>>(c->scene, c->state, c->queues, iteration, span, cam[0], cam[1], cam[2]);
-        else k_traverse_nearest_stream<16, LDS_THREADS><<<grid, LDS_THREADS, lds_bytes, s>>>(c->scene, c->state, c->queues, iteration, span, 0.0f, 0.0f, 0.0f);
+        if (last_without_nee && c->scene.last_emit_n <= RPT_LAST_EMIT_MAX) {
+            k_traverse_nearest_stream<16, LDS_THREADS, RPT_NEAREST_LAST><<<grid, LDS_THREADS, lds_bytes + (size_t)c->scene.last_flip_vecs * sizeof(float4), s>>>(c->scene, c->state, c->queues, iteration, span, 0.0f, 0.0f, 0.0f, c->cfg, 0u, stats);
+            return c->state.group_shift != 0u;
+        }
+        if (camera_rays)
+            k_traverse_nearest_stream<16, LDS_THREADS, RPT_NEAREST_FIRST><<<grid, LDS_THREADS, lds_bytes, s>>>(c->scene, c->state, c->queues, iteration, span, cam[0], cam[1], cam[2], c->cfg, start_paths ? c->call_samples : 0u, stats);
+        else k_traverse_nearest_stream<16, LDS_THREADS><<<grid, LDS_THREADS, lds_bytes, s>>>(c->scene, c->state, c->queues, iteration, span, 0.0f, 0.0f, 0.0f, c->cfg, 0u, stats);
     } else if (c->scene.gpairs) {
         if (c->fat_leaves) launch_nearest_gstream<STACK, true>(c, iteration);
         else launch_nearest_gstream<STACK, false>(c, iteration);
@@ -94,6 +99,7 @@ void launch_nearest(rpt_ctx *c, uint32_t iteration, bool last_without_nee = fals
         const uint32_t nb = (c->n_slots + GLOBAL_THREADS - 1) / GLOBAL_THREADS;
         k_traverse_nearest<32, GLOBAL_THREADS><<<nb, GLOBAL_THREADS, 0, s>>>(c->scene, c->state, c->queues, iteration);
     }
+    return false;
 }
 
 /* the streamed global-memory any-hit walk (FIXED: over the flipped copy, left child first — shadow_order.h; the `_seg` twins: the context is in
@@ -141,12 +147,18 @@ void launch_shadow(rpt_ctx *c) {
 
 }  // namespace
 
-void rpt_launch_nearest(rpt_ctx *c, uint32_t iteration, bool last_without_nee, bool camera_rays) {
+bool rpt_launch_nearest(rpt_ctx *c, uint32_t iteration, bool last_without_nee, bool camera_rays, bool start_paths) {
     switch (c->stack_cap) {
-        case 16: launch_nearest<16>(c, iteration, last_without_nee, camera_rays); break;
-        case 24: launch_nearest<24>(c, iteration, last_without_nee, camera_rays); break;
-        default: launch_nearest<32>(c, iteration, last_without_nee, camera_rays); break;
+        case 16: return launch_nearest<16>(c, iteration, last_without_nee, camera_rays, start_paths);
+        case 24: return launch_nearest<24>(c, iteration, last_without_nee, camera_rays, start_paths);
+        default: return launch_nearest<32>(c, iteration, last_without_nee, camera_rays, start_paths);
     }
+}
+
+/* the walk of a render call's iteration 0 is the FIRST kernel and can start the call's first paths itself: an LDS-resident scene, several slots per pixel
+ * (with one, k_generate_first is also where max_bounces == 0 and the in-place restarts are handled) and at least one bounce */
+bool rpt_first_walk_starts_paths(const rpt_ctx *c) {
+    return c->stack_cap == 16 && c->scene.lds_scene != 0u && c->state.group_shift != 0u && c->cfg.c.max_bounces != 0u;
 }
 
 void rpt_launch_shadow(rpt_ctx *c) {
