@@ -25,6 +25,8 @@ pub const RPT_COMM_ID_BYTES: usize = 128;
 pub const RPT_MULTI_ALLOW_SHARED_DEVICE: u32 = 1;
 pub const RPT_SHADOW_EXACT: u32 = 0;
 pub const RPT_SHADOW_SEGMENT: u32 = 1;
+pub const RPT_DENOISE_ACCUM: u32 = 0;
+pub const RPT_DENOISE_GATHERED: u32 = 1;
 
 #[repr(C)] pub struct rpt_ctx { _private: [u8; 0] }
 #[repr(C)] pub struct rpt_multi { _private: [u8; 0] }
@@ -42,6 +44,26 @@ pub struct rpt_stats {
     pub kernel_ms: [f64; 8],
     pub kernel_launches: [u64; 8],
     pub shadow_rays_elided: u64,   // of shadow_rays: not walked, their NEE term is zero whatever the walk finds
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct rpt_denoise_params {
+    pub iterations: u32,          // 0..6 a-trous passes, step 2^i
+    pub normal_power_log2: u32,   // 0..10
+    pub sigma_color: f32,
+    pub sigma_plane: f32,
+    pub demodulate: u32,
+    pub reserved: [u32; 3],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct rpt_denoise_report {
+    pub device_ms: f64,
+    pub guides_ms: f64,
+    pub guides_rebuilt: u32,
+    pub reserved: u32,
 }
 
 extern "C" {
@@ -75,6 +97,10 @@ extern "C" {
     pub fn rpt_read_accum(ctx: *mut rpt_ctx, out: *mut Vec4, out_samples: *mut u32) -> c_int;      // output_buffer.read_blocking, trace.rs:198
     pub fn rpt_map_accum(ctx: *mut rpt_ctx, out: *mut *const Vec4, out_samples: *mut u32) -> c_int; // same without the copy (library-owned pinned buffer)
     pub fn rpt_resolve(ctx: *mut rpt_ctx, tonemap_op: u32, out_rgb: *mut f32) -> c_int;             // sum / samples + render.wgsl tonemappers
+    // the denoise step, trace.rs:205-213 (there OIDN): params null = defaults, report nullable; source RPT_DENOISE_ACCUM | RPT_DENOISE_GATHERED
+    pub fn rpt_denoise_params_default(out: *mut rpt_denoise_params);
+    pub fn rpt_denoise(ctx: *mut rpt_ctx, source: u32, params: *const rpt_denoise_params, tonemap_op: u32, out_rgb: *mut f32, report: *mut rpt_denoise_report) -> c_int;
+    pub fn rpt_read_guides(ctx: *mut rpt_ctx, albedo_rgb: *mut f32, normal_xyz: *mut f32, depth: *mut f32, position_xyz: *mut f32, kind: *mut u32) -> c_int;   // each nullable; albedo / normal = OIDN's auxiliary images
     pub fn rpt_get_stats(ctx: *mut rpt_ctx, out: *mut rpt_stats) -> c_int;
     pub fn rpt_destroy(ctx: *mut rpt_ctx);
 
@@ -96,6 +122,7 @@ extern "C" {
     pub fn rpt_multi_render(m: *mut rpt_multi, n_samples: u32) -> c_int;            // one batch on every GPU + the batch's single RCCL gather
     pub fn rpt_multi_wait(m: *mut rpt_multi) -> c_int;
     pub fn rpt_multi_read_accum(m: *mut rpt_multi, out: *mut Vec4, out_samples: *mut u32) -> c_int;   // the whole W x H image, from rank 0
+    pub fn rpt_multi_denoise(m: *mut rpt_multi, params: *const rpt_denoise_params, tonemap_op: u32, out_rgb: *mut f32, report: *mut rpt_denoise_report) -> c_int;   // waits, gathers, denoises on rank 0
     pub fn rpt_multi_get_stats(m: *mut rpt_multi, out: *mut rpt_stats) -> c_int;
     pub fn rpt_multi_last_error(m: *mut rpt_multi) -> *const c_char;
     pub fn rpt_multi_destroy(m: *mut rpt_multi);

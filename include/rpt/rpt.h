@@ -290,6 +290,55 @@ int rpt_shadow_mode(rpt_ctx *ctx, uint32_t *mode_out);
 int rpt_last_bounce_order(rpt_ctx *ctx, uint32_t *mode_out, uint32_t *n_emissive_triangles_out, double *visits_out /* [4], nullable */, uint32_t *probe_rays_out,
                           double *probe_ms_out);
 
+/* --- denoise (the third step of the reference's read-back: read, divide by the sample count, DENOISE — src/trace.rs:197-213, the "Denoise" checkbox of
+ * src/app.rs:245-249, there OIDN) --------------------------------------------------------------------------------------------------------------------
+ * Opt-in, after the accumulator; the wavefront pipeline, its parity statements and bench.py's figures are not touched.  Two parts (csrc/k_denoise.h):
+ *   guides   the first hit of the ray through every pixel's centre (camera_ray with the jitter replaced by (0.5, 0.5)), for the WHOLE image whatever the
+ *            context's partition: kind 0 miss / 1 surface / 2 emitter (material.emissive.xyz != 0, either face); albedo = what get_pbr_bsdf uses
+ *            (bsdf.rs:355-361; (1,1,1) for kinds 0 and 2); the normalised shading normal of lib.rs:125-141 ((0,0,0) on a miss or where it is zero / not
+ *            finite); depth = trace_result.t (1e6 on a miss); position = ro + rd * depth.  Cached on the context: rebuilt at the first use after
+ *            rpt_set_config or rpt_upload_scene, not per call.  These rays are not counted in rpt_stats.  rpt_read_guides hands them out — also the
+ *            albedo / normal auxiliary images a host-side OIDN takes.
+ *   filter   an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over mean = sum / samples: `iterations` passes of 5 x 5 taps at step 2^i,
+ *            weights from normal, plane distance and colour, between pixels of the same kind only; with `demodulate` the mean is divided by max(albedo, 0.01)
+ *            first and multiplied back at the end; then tonemap operator 0..6 as rpt_resolve.  iterations = 0 is exactly rpt_resolve(tonemap_op).
+ *            Deterministic, f32, no atomics: the device result equals the host build of the same header (rpt_debug_denoise_host) bit for bit and does not
+ *            depend on the number of GPUs.  The formulas: csrc/k_denoise.h dn_filter_pixel, DESIGN.md "Denoiser".
+ * rpt_denoise synchronises by itself and is synchronous on return; it leaves the accumulator, the rng, the counters and the shadow mode untouched and may be
+ * called between any two batches.  source:
+ *   RPT_DENOISE_ACCUM     the context's own accumulator; needs a partition of one rank (else RPT_EINVAL).
+ *   RPT_DENOISE_GATHERED  the image of the last gather, on rank 0 of a communicator (rpt_comm_init_local included): waits for that gather, uses its sample
+ *                         count, and filters on the gather's stream — a batch enqueued since keeps rendering.  RPT_EINVAL on other ranks or before any gather.
+ * RPT_EINVAL also for iterations > 6, normal_power_log2 > 10, a negative or non-finite sigma, tonemap_op > 6 and zero samples; the context stays usable.
+ * out_rgb: width*height*3 floats, row-major.  report (nullable): device_ms = the filter (pre-pass + passes, HIP events), guides_ms = the guide build of this
+ * call (0 when cached), guides_rebuilt 0 / 1.  There is no environment variable for any of it. */
+typedef struct rpt_denoise_params {
+    uint32_t iterations;          /* 0..6 passes, step 2^i */
+    uint32_t normal_power_log2;   /* 0..10: the normal weight max(0, n_p . n_q) is squared this many times */
+    float    sigma_color;         /* colour edge-stopping width, halved every pass; 0 = no colour term */
+    float    sigma_plane;         /* plane-distance width in pixel footprints */
+    uint32_t demodulate;          /* filter mean / max(albedo, 0.01) */
+    uint32_t reserved[3];
+} rpt_denoise_params;
+
+typedef struct rpt_denoise_report {
+    double   device_ms;
+    double   guides_ms;
+    uint32_t guides_rebuilt;
+    uint32_t reserved;
+} rpt_denoise_report;
+
+enum { RPT_DENOISE_ACCUM = 0, RPT_DENOISE_GATHERED = 1 };
+
+/* the parameters with the lowest summed error against converged images of the three shipped scenes (profiles/r11_denoise_quality.txt) */
+void rpt_denoise_params_default(rpt_denoise_params *out);
+int rpt_denoise(rpt_ctx *ctx, uint32_t source, const rpt_denoise_params *params /* NULL = defaults */, uint32_t tonemap_op, float *out_rgb,
+                rpt_denoise_report *report /* nullable */);
+/* width*height entries each, row-major; every pointer nullable.  Builds the guides if they are stale. */
+int rpt_read_guides(rpt_ctx *ctx, float *albedo_rgb, float *normal_xyz, float *depth, float *position_xyz, uint32_t *kind);
+/* waits, gathers as rpt_multi_read_accum does, and denoises on rank 0 */
+int rpt_multi_denoise(rpt_multi *m, const rpt_denoise_params *params, uint32_t tonemap_op, float *out_rgb, rpt_denoise_report *report);
+
 /* --- scene preparation on the device ---------------------- */
 /* BVHBuilder::new(vertices, indices).sah_samples(n).build()  (reference src/bvh.rs:59-324, the call at
  * src/asset.rs:196) on the GPU: reorders `triangles` in place and writes the node pool exactly as the sequential

@@ -63,6 +63,12 @@ int rpt_debug_bsdf(rpt_ctx *ctx, int kind, size_t n, const float *in, float *out
  * as ncclFloat and are compared on the host.  Needs rpt_comm_init; collective (every rank calls it). */
 int rpt_debug_comm_selftest(rpt_ctx *ctx, uint32_t n_floats, uint64_t *mismatches_out);
 
+/* The denoise filter of rpt_denoise on the HOST: the same header (csrc/k_denoise.h) in a plain loop over the pixels — no device needed, as rpt_debug_math_host.
+ * mean_rgb, albedo, normal, position: width*height*3 floats; depth: width*height floats; kind: width*height words (the layouts of rpt_read_guides); params
+ * NULL = defaults; out_rgb: width*height*3 floats.  RPT_EINVAL for the parameter values rpt_denoise refuses. */
+int rpt_debug_denoise_host(uint32_t width, uint32_t height, const float *mean_rgb, const float *albedo, const float *normal, const float *position,
+                           const float *depth, const uint32_t *kind, const rpt_denoise_params *params, uint32_t tonemap_op, float *out_rgb);
+
 /* Test aid: the next asynchronous batches of this context enqueue one iteration too few — proves that the completion checks (rpt_wait, the next
  * batch's k_generate_first) notice a sample left in flight instead of losing it. */
 int rpt_debug_short_batch(rpt_ctx *ctx, int on);

@@ -133,6 +133,11 @@ void rpt_tracing_state_set_config(rpt_tracing_state *s, const rpt_tracing_config
  * the same.  on = 0 selects the blocking loop rpt_render ; rpt_read_accum, the literal shape of src/trace.rs:182-204
  * (8 % slower on DarkCornell 1024^2).  Set before rpt_trace_gpu is called. */
 void rpt_tracing_state_set_overlap(rpt_tracing_state *s, int on);
+/* state.denoise (src/trace.rs:45, the "Denoise" checkbox of src/app.rs:245-249).  While it is on, an iteration of rpt_trace_gpu that does not flush publishes
+ * rpt_denoise(default parameters, tonemap operator 0) of the image it read instead of the plain mean — the reference's `&& !flush` (trace.rs:208): a camera
+ * drag shows the unfiltered 1-sample images.  The source is the gathered image in the overlapped loop (RPT_DENOISE_GATHERED: the filter runs beside the next
+ * batch), the accumulator in the blocking one.  May be switched while rpt_trace_gpu runs. */
+void rpt_tracing_state_set_denoise(rpt_tracing_state *s, int on);
 /* setup_trace(width, height, samples) (src/trace.rs:331-344) — but exact: the
  * render stops after precisely `samples` samples (the reference's watcher
  * thread can overshoot). */

@@ -32,7 +32,7 @@ struct rpt_tracing_state {
     rpt_tracing_config config;
     std::atomic<bool> running{false};
     std::atomic<uint32_t> samples{0};
-    std::atomic<bool> denoise{false};      /* kept for interface parity; OIDN is out of scope */
+    std::atomic<bool> denoise{false};      /* state.denoise (trace.rs:45): rpt_trace_gpu publishes rpt_denoise of an image instead of its plain mean */
     std::atomic<uint32_t> sync_rate{32};
     std::atomic<bool> use_blue_noise{true};
     std::atomic<bool> interacting{false};
@@ -243,6 +243,8 @@ void rpt_tracing_state_set_sync_rate(rpt_tracing_state *s, uint32_t r) { s->sync
 void rpt_tracing_state_set_dirty(rpt_tracing_state *s, int d) { s->dirty.store(d != 0, std::memory_order_relaxed); }
 /* state.interacting (src/trace.rs:50; the UI raises it while the camera is dragged, src/app.rs): every batch flushes while it is up */
 void rpt_tracing_state_set_interacting(rpt_tracing_state *s, int on) { if (s) s->interacting.store(on != 0, std::memory_order_relaxed); }
+/* state.denoise (src/trace.rs:45, the UI's "Denoise" checkbox): iterations that do not flush publish rpt_denoise(defaults, op 0) instead of the mean */
+void rpt_tracing_state_set_denoise(rpt_tracing_state *s, int on) { if (s) s->denoise.store(on != 0, std::memory_order_relaxed); }
 /* state.config.write() of the UI thread (src/app.rs) while trace_gpu runs: under the lock the render loop takes when it
  * re-reads the configuration on a flush (trace.rs:216-222); follow with rpt_tracing_state_set_dirty(s, 1) */
 void rpt_tracing_state_set_overlap(rpt_tracing_state *s, int on) { if (s) s->overlap.store(on != 0, std::memory_order_relaxed); }
@@ -335,6 +337,7 @@ struct HipApi {
     decltype(&rpt_comm_init_local) comm_init_local;
     decltype(&rpt_gather_async) gather_async;
     decltype(&rpt_read_gathered) read_gathered;
+    decltype(&rpt_denoise) denoise;
     decltype(&rpt_destroy) destroy;
     decltype(&rpt_last_error) last_error;
 };
@@ -363,7 +366,7 @@ bool load_hip_api(const char *path, HipApi &api) {
            sym(api.handle, "rpt_render", api.render) && sym(api.handle, "rpt_read_accum", api.read_accum) &&
            sym(api.handle, "rpt_render_async", api.render_async) && sym(api.handle, "rpt_comm_init_local", api.comm_init_local) &&
            sym(api.handle, "rpt_gather_async", api.gather_async) && sym(api.handle, "rpt_read_gathered", api.read_gathered) &&
-           sym(api.handle, "rpt_destroy", api.destroy) && sym(api.handle, "rpt_last_error", api.last_error);
+           sym(api.handle, "rpt_denoise", api.denoise) && sym(api.handle, "rpt_destroy", api.destroy) && sym(api.handle, "rpt_last_error", api.last_error);
 }
 }  // namespace
 
@@ -448,15 +451,23 @@ int rpt_trace_gpu(const char *scene_path, const char *skybox_path, rpt_tracing_s
     const bool overlap = state->overlap.load(std::memory_order_relaxed);
     if (overlap && (rc = api.comm_init_local(ctx))) return fail(rc);
     uint32_t in_flight = 0;                              /* overlap: samples of the batch that was enqueued but not read yet */
-    auto publish = [&](uint32_t samples_of_image) {
-        float sample_count = (float)samples_of_image;
-        for (size_t i = 0; i < pixel_count; ++i) {
-            image[3 * i + 0] = image_raw[4 * i + 0] / sample_count;
-            image[3 * i + 1] = image_raw[4 * i + 1] / sample_count;
-            image[3 * i + 2] = image_raw[4 * i + 2] / sample_count;
+    /* the image just read (image_raw) becomes the framebuffer: its mean, or — state.denoise, and the iteration does not flush (trace.rs:208) — the library's
+     * denoise step on the image the device still holds (the accumulator, or in the overlapped loop the gathered image this read came from) */
+    auto publish = [&](uint32_t samples_of_image, bool flushing) -> int {
+        if (state->denoise.load(std::memory_order_relaxed) && !flushing && samples_of_image != 0u) {
+            int drc = api.denoise(ctx, overlap ? RPT_DENOISE_GATHERED : RPT_DENOISE_ACCUM, nullptr, 0u, image.data(), nullptr);
+            if (drc) return drc;
+        } else {
+            float sample_count = (float)samples_of_image;
+            for (size_t i = 0; i < pixel_count; ++i) {
+                image[3 * i + 0] = image_raw[4 * i + 0] / sample_count;
+                image[3 * i + 1] = image_raw[4 * i + 1] / sample_count;
+                image[3 * i + 2] = image_raw[4 * i + 2] / sample_count;
+            }
         }
         std::lock_guard<std::mutex> g(state->lock);
         state->framebuffer = image;
+        return 0;
     };
     while (state->running.load(std::memory_order_relaxed)) {
         uint32_t n = state->sync_rate.load(std::memory_order_relaxed);
@@ -479,14 +490,14 @@ int rpt_trace_gpu(const char *scene_path, const char *skybox_path, rpt_tracing_s
             }
             uint32_t device_samples = 0;
             if ((rc = api.read_accum(ctx, image_raw.data(), &device_samples))) return fail(rc);
-            publish(state->samples.load(std::memory_order_relaxed));
+            if ((rc = publish(state->samples.load(std::memory_order_relaxed), flush))) return fail(rc);
         } else {
             if (n && (rc = api.render_async(ctx, n))) return fail(rc);          /* batch k+1 ... */
             if (in_flight) {                                                    /* ... while the image after batch k comes back */
                 uint32_t device_samples = 0;
                 if ((rc = api.read_gathered(ctx, image_raw.data(), &device_samples))) return fail(rc);
                 state->samples.store(device_samples, std::memory_order_relaxed);
-                publish(device_samples);
+                if ((rc = publish(device_samples, flush))) return fail(rc);
             }
             if (n && (rc = api.gather_async(ctx))) return fail(rc);             /* snapshot after batch k+1 */
             in_flight = n;
@@ -494,7 +505,7 @@ int rpt_trace_gpu(const char *scene_path, const char *skybox_path, rpt_tracing_s
                 uint32_t device_samples = 0;
                 if ((rc = api.read_gathered(ctx, image_raw.data(), &device_samples))) return fail(rc);
                 state->samples.store(device_samples, std::memory_order_relaxed);
-                publish(device_samples);
+                if ((rc = publish(device_samples, true))) return fail(rc);
             }
             if (!n && !flush) {                                                 /* nothing left to enqueue: the last image is in */
                 if (state->target_samples && state->samples.load(std::memory_order_relaxed) >= state->target_samples)
@@ -526,7 +537,7 @@ int rpt_trace_gpu(const char *scene_path, const char *skybox_path, rpt_tracing_s
         uint32_t device_samples = 0;
         if ((rc = api.read_gathered(ctx, image_raw.data(), &device_samples))) return fail(rc);
         state->samples.store(device_samples, std::memory_order_relaxed);
-        publish(device_samples);
+        if ((rc = publish(device_samples, false))) return fail(rc);
     }
     api.destroy(ctx);
     rpt_world_free(world);

@@ -42,19 +42,19 @@
 #define RPT_BLOCK 256
 #define RPT_MAX_SAMPLES_IN_FLIGHT 256u   /* most slots per pixel (k_complete.h counts a pixel's finished slots; rounds 1-5: a 32-bit mask) */
 
-/* ---- glam-order float3 helpers (device side) ----------------------------- */
+/* ---- glam-order float3 helpers (the arithmetic ones are RPT_HD: the post-accumulation code of k_tonemap.h / k_denoise.h also runs on the host) ---- */
 struct F3 { float x, y, z; };
-__device__ __forceinline__ F3 f3(float x, float y, float z) { return F3{x, y, z}; }
-__device__ __forceinline__ F3 f3s(float s) { return F3{s, s, s}; }
-__device__ __forceinline__ F3 operator+(F3 a, F3 b) { return F3{a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ F3 operator-(F3 a, F3 b) { return F3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ F3 operator*(F3 a, F3 b) { return F3{a.x * b.x, a.y * b.y, a.z * b.z}; }
-__device__ __forceinline__ F3 operator*(F3 a, float s) { return F3{a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ F3 operator*(float s, F3 a) { return F3{s * a.x, s * a.y, s * a.z}; }
-__device__ __forceinline__ F3 operator/(F3 a, float s) { return F3{a.x / s, a.y / s, a.z / s}; }
-__device__ __forceinline__ F3 operator-(F3 a) { return F3{-a.x, -a.y, -a.z}; }
+RPT_HD F3 f3(float x, float y, float z) { return F3{x, y, z}; }
+RPT_HD F3 f3s(float s) { return F3{s, s, s}; }
+RPT_HD F3 operator+(F3 a, F3 b) { return F3{a.x + b.x, a.y + b.y, a.z + b.z}; }
+RPT_HD F3 operator-(F3 a, F3 b) { return F3{a.x - b.x, a.y - b.y, a.z - b.z}; }
+RPT_HD F3 operator*(F3 a, F3 b) { return F3{a.x * b.x, a.y * b.y, a.z * b.z}; }
+RPT_HD F3 operator*(F3 a, float s) { return F3{a.x * s, a.y * s, a.z * s}; }
+RPT_HD F3 operator*(float s, F3 a) { return F3{s * a.x, s * a.y, s * a.z}; }
+RPT_HD F3 operator/(F3 a, float s) { return F3{a.x / s, a.y / s, a.z / s}; }
+RPT_HD F3 operator-(F3 a) { return F3{-a.x, -a.y, -a.z}; }
 /* Vec3::dot = (x*x' + y*y') + z*z' ; cross, length, normalize = v * (1/len) */
-__device__ __forceinline__ float dot3(F3 a, F3 b) { return (a.x * b.x) + (a.y * b.y) + (a.z * b.z); }
+RPT_HD float dot3(F3 a, F3 b) { return (a.x * b.x) + (a.y * b.y) + (a.z * b.z); }
 __device__ __forceinline__ F3 cross3(F3 a, F3 b) {
     return F3{a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x, a.x * b.y - b.x * a.y};
 }

@@ -138,6 +138,23 @@ void rpt_comm_release(rpt_ctx *c) {
     c->comm = nullptr;
 }
 
+/* rpt_denoise(RPT_DENOISE_GATHERED): the gathered image itself, once the gather that wrote it has completed */
+int rpt_comm_gathered_image(rpt_ctx *c, const float4 **image_out, uint32_t *samples_out, hipStream_t *stream_out) {
+    rpt_comm *cm = c->comm;
+    if (!cm || cm->rank != 0 || !cm->full_image.p || !cm->started) { c->error = "rpt_denoise: a gathered image exists on rank 0 of a communicator after the first gather"; return RPT_EINVAL; }
+    if (!c->has_config || cm->conf_w != c->cfg.c.width || cm->conf_h != c->cfg.c.height) {
+        c->error = "rpt_denoise: the configuration was resized since the last gather: call rpt_gather_async first";
+        return RPT_EINVAL;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(cm->stream));
+    HIP_TRY(c, hipGetLastError());
+    *image_out = cm->full_image.p;
+    *samples_out = cm->gathered_samples;
+    *stream_out = cm->stream;
+    return RPT_OK;
+}
+
 namespace {
 
 /* the row-major device image + its pinned host twin, sized for the current configuration */
@@ -673,6 +690,19 @@ int rpt_multi_read_accum(rpt_multi *m, float *out, uint32_t *out_samples) {
         if ((rc = rpt_multi_wait(m))) return rc;
     }
     rc = rpt_read_gathered(root, out, out_samples);
+    return rc ? multi_fail(m, root, rc) : RPT_OK;
+}
+
+int rpt_multi_denoise(rpt_multi *m, const rpt_denoise_params *params, uint32_t tonemap_op, float *out_rgb, rpt_denoise_report *report) {
+    if (!m || !out_rgb) return RPT_EINVAL;
+    int rc = rpt_multi_wait(m);
+    if (rc) return rc;
+    if (!m->gathered) {              /* as rpt_multi_read_accum: nothing rendered since the last reset */
+        if ((rc = multi_gather(m))) return rc;
+        if ((rc = rpt_multi_wait(m))) return rc;
+    }
+    rpt_ctx *root = m->ctx[0];
+    rc = rpt_denoise(root, RPT_DENOISE_GATHERED, params, tonemap_op, out_rgb, report);
     return rc ? multi_fail(m, root, rc) : RPT_OK;
 }
 

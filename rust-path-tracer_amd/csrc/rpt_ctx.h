@@ -1,7 +1,7 @@
 /*
  * rpt_ctx.h — the context object behind the C ABI of include/rpt/rpt.h, shared by the translation units of
  * librpt_hip.so (rpt_hip.hip: life cycle, state and wavefront scheduling; rpt_scene.hip: scene preparation; rpt_traverse.hip: the traversal stages;
- * rpt_comm.hip: multi-GPU gather over RCCL, read-back; rpt_debug.hip: test hooks).
+ * rpt_comm.hip: multi-GPU gather over RCCL, read-back; rpt_denoise.hip: guide buffers and the denoise filter; rpt_debug.hip: test hooks).
  */
 #ifndef RPT_CTX_H
 #define RPT_CTX_H
@@ -130,6 +130,18 @@ struct StageTimer {
 constexpr int RPT_RING_LAG = 6;   /* most iterations the host may run ahead of the progress report it inspects (small launches) */
 constexpr int RPT_RING = 16;      /* power of two, > RPT_RING_LAG */
 
+/* rpt_denoise.hip: what rpt_denoise / rpt_read_guides keep on a context — allocated on first use, released on destroy and on a resize.  The guides
+ * belong to (scene, configuration): rpt_upload_scene and rpt_set_config mark them stale, the next use rebuilds them. */
+struct DenoiseState {
+    DevBuf<float4> g0, g1, albedo;        /* row-major W x H: (normal | depth), (position | kind bits), (albedo | -) */
+    DevBuf<float4> ping, pong;            /* the two images the passes alternate between */
+    DevBuf<float> rgb;                    /* W x H x 3: the result, before it leaves the device */
+    DevBuf<uint32_t> order;               /* x | y << 16 of every pixel of the image in tile order (rank 0 of 1): a wave of guide rays is an 8 x 8 block */
+    uint32_t width = 0, height = 0;       /* what the buffers are sized for */
+    bool guides_valid = false;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   /* guides begin / end, filter begin / end (created with the buffers, destroyed by rpt_denoise_release) */
+};
+
 struct rpt_comm;                  /* rpt_comm.hip: RCCL communicator + gather buffers of one context */
 
 /* Every environment variable the library reads, read in ONE place (rpt_read_knobs, rpt_hip.hip; rpt_create copies them into the context).  None changes
@@ -235,6 +247,8 @@ struct rpt_ctx {
     DevBuf<uint32_t> untile_map;          /* rpt_untile: destination map, rebuilt only when (W, H, world, stride) changes */
     uint64_t untile_key = 0;
     uint32_t untile_n = 0;
+
+    DenoiseState dn;                      /* rpt_denoise.hip */
 };
 
 /* rpt_traverse.hip: the traversal stages (which walk kernel for the context's scene, on which grid) */
@@ -257,6 +271,11 @@ int rpt_idle_all_slots(rpt_ctx *c);
 void rpt_build_pixel_order(uint32_t W, uint32_t H, uint32_t rank, uint32_t world, std::vector<uint32_t> &out);
 /* rpt_comm.hip: called by rpt_hip.hip when the context goes away */
 void rpt_comm_release(rpt_ctx *c);
+/* rpt_comm.hip, for rpt_denoise(RPT_DENOISE_GATHERED): the image of the last gather on rank 0 of a communicator, once that gather has completed, its sample
+ * count and the stream the gather ran on (work on it is ordered after the gather and overlaps the batch on the context's own stream) */
+int rpt_comm_gathered_image(rpt_ctx *c, const float4 **image_out, uint32_t *samples_out, hipStream_t *stream_out);
+/* rpt_denoise.hip: the denoiser's buffers go (a resize), or buffers and events (the context goes away: while its device is current) */
+void rpt_denoise_release(rpt_ctx *c, bool events_too);
 std::string &rpt_create_error();
 
 /* RPT_UPLOAD_TIMING=1: host-side section times of rpt_upload_scene / rpt_bvh_build_gpu on stderr (where the start-up time of a large scene goes) */

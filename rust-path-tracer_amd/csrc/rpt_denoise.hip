@@ -1,0 +1,209 @@
+/*
+ * rpt_denoise.hip — the denoise step behind the C ABI (include/rpt/rpt.h rpt_denoise, rpt_read_guides, rpt_denoise_params_default) and its host build
+ * (rpt_debug.h rpt_debug_denoise_host): the guide buffers of a context — built with the one-ray-per-lane nearest-hit walk the debug hook launches
+ * (rpt_launch_trace_debug: LDS or global variant per scene, no new walk instantiated) and a small shading kernel — and the passes of k_denoise.h.
+ */
+#include <cstring>
+#include <vector>
+
+#include "rpt_ctx.h"
+#include "k_denoise.h"
+
+namespace {
+
+/* csrc/k_denoise.h; chosen on converged images of the shipped scenes: profiles/r11_denoise_quality.txt */
+constexpr rpt_denoise_params DN_DEFAULTS = {2u, 0u, 1.0f, 2.0f, 1u, {0u, 0u, 0u}};
+
+int check_params(const rpt_denoise_params &p, uint32_t tonemap_op, std::string &error) {
+    if (p.iterations > RPT_DN_MAX_ITERATIONS) { error = "rpt_denoise: iterations must be 0..6"; return RPT_EINVAL; }
+    if (p.normal_power_log2 > RPT_DN_MAX_NORMAL_POWER_LOG2) { error = "rpt_denoise: normal_power_log2 must be 0..10"; return RPT_EINVAL; }
+    if (!rptm::finiter(p.sigma_color) || !rptm::finiter(p.sigma_plane) || p.sigma_color < 0.0f || p.sigma_plane < 0.0f) {
+        error = "rpt_denoise: sigma_color and sigma_plane must be finite and >= 0";
+        return RPT_EINVAL;
+    }
+    if (tonemap_op > 6u) { error = "tonemap operator must be 0..6"; return RPT_EINVAL; }
+    return RPT_OK;
+}
+
+/* buffers + events for the current configuration (first use, or the first use after a resize released them) */
+int ensure_buffers(rpt_ctx *c) {
+    DenoiseState &d = c->dn;
+    const uint32_t W = c->cfg.c.width, H = c->cfg.c.height;
+    const size_t n = (size_t)W * H;
+    if (n > ((size_t)1 << 28)) { c->error = "rpt_denoise: images of more than 2^28 pixels are not supported"; return RPT_EINVAL; }
+    for (hipEvent_t &e : d.ev)
+        if (!e) HIP_TRY(c, hipEventCreate(&e));
+    if (d.width == W && d.height == H && d.g0.p) return RPT_OK;
+    rpt_denoise_release(c, false);
+    std::vector<uint32_t> order;
+    rpt_build_pixel_order(W, H, 0u, 1u, order);
+    if (order.size() != n) { c->error = "rpt_denoise: internal error (tile order does not cover the image)"; return RPT_EHIP; }
+    HIP_TRY(c, d.order.from_host(order.data(), n));
+    HIP_TRY(c, d.g0.alloc(n)); HIP_TRY(c, d.g1.alloc(n)); HIP_TRY(c, d.albedo.alloc(n));
+    HIP_TRY(c, d.ping.alloc(n)); HIP_TRY(c, d.pong.alloc(n)); HIP_TRY(c, d.rgb.alloc(3 * n));
+    d.width = W; d.height = H;
+    d.guides_valid = false;
+    return RPT_OK;
+}
+
+/* the guides of (scene, configuration), on the context's stream; *rebuilt = they were stale.  The rays and their hits live for this call only. */
+int ensure_guides(rpt_ctx *c, bool *rebuilt) {
+    DenoiseState &d = c->dn;
+    *rebuilt = false;
+    RPT_TRY(ensure_buffers(c));
+    if (d.guides_valid) return RPT_OK;
+    RPT_TRY(rpt_wait(c));                            /* the walk shares the context's stream (and LDS) with the batches */
+    const uint32_t n = d.width * d.height;
+    Arena rays;
+    HIP_TRY(c, rays.reserve(2 * Arena::pad(3 * (size_t)n * sizeof(float)) + 3 * Arena::pad((size_t)n * sizeof(uint32_t))));
+    float *origins = rays.take<float>(3 * (size_t)n), *dirs = rays.take<float>(3 * (size_t)n), *hit_t = rays.take<float>(n);
+    uint32_t *hit_tri = rays.take<uint32_t>(n), *hit_flags = rays.take<uint32_t>(n);
+    hipStream_t s = c->stream;
+    HIP_TRY(c, hipEventRecord(d.ev[0], s));
+    k_dn_camera_rays<<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(c->cfg, d.order.p, n, origins, dirs);
+    rpt_launch_trace_debug(c, 0, n, origins, dirs, nullptr, hit_t, hit_tri, hit_flags);
+    if (c->scene.textured) k_dn_shade_guides<true><<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(c->scene, d.width, d.order.p, n, origins, dirs, hit_t, hit_tri, hit_flags, d.g0.p, d.g1.p, d.albedo.p);
+    else k_dn_shade_guides<false><<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(c->scene, d.width, d.order.p, n, origins, dirs, hit_t, hit_tri, hit_flags, d.g0.p, d.g1.p, d.albedo.p);
+    HIP_TRY(c, hipEventRecord(d.ev[1], s));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(s));             /* (before the rays are freed) */
+    d.guides_valid = true;
+    *rebuilt = true;
+    return RPT_OK;
+}
+
+void launch_pass(hipStream_t s, const DnPass &ps, bool last, const float4 *src, const DenoiseState &d, float4 *dst, uint32_t demodulated, uint32_t tonemap_op) {
+    const dim3 grid((ps.width + 63u) / 64u, (ps.height + 3u) / 4u);
+    if (last) k_dn_pass<true><<<grid, 256, 0, s>>>(ps, src, d.g0.p, d.g1.p, dst, d.albedo.p, demodulated, tonemap_op, d.rgb.p);
+    else k_dn_pass<false><<<grid, 256, 0, s>>>(ps, src, d.g0.p, d.g1.p, dst, d.albedo.p, demodulated, tonemap_op, d.rgb.p);
+}
+
+}  // namespace
+
+void rpt_denoise_release(rpt_ctx *c, bool events_too) {
+    DenoiseState &d = c->dn;
+    d.g0.release(); d.g1.release(); d.albedo.release(); d.ping.release(); d.pong.release(); d.rgb.release(); d.order.release();
+    d.width = d.height = 0;
+    d.guides_valid = false;
+    if (events_too)
+        for (hipEvent_t &e : d.ev)
+            if (e) { (void)hipEventDestroy(e); e = nullptr; }
+}
+
+extern "C" {
+
+void rpt_denoise_params_default(rpt_denoise_params *out) {
+    if (out) *out = DN_DEFAULTS;
+}
+
+int rpt_denoise(rpt_ctx *c, uint32_t source, const rpt_denoise_params *params, uint32_t tonemap_op, float *out_rgb, rpt_denoise_report *report) {
+    if (!c || !out_rgb) return RPT_EINVAL;
+    const rpt_denoise_params p = params ? *params : DN_DEFAULTS;
+    RPT_TRY(check_params(p, tonemap_op, c->error));
+    if (source != RPT_DENOISE_ACCUM && source != RPT_DENOISE_GATHERED) { c->error = "rpt_denoise: source must be RPT_DENOISE_ACCUM or RPT_DENOISE_GATHERED"; return RPT_EINVAL; }
+    if (!c->has_scene || !c->has_config || !c->has_state) { c->error = "rpt_denoise: needs a scene and a configuration"; return RPT_EINVAL; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const float4 *sums = nullptr;
+    const uint32_t *order = nullptr;
+    uint32_t samples = 0;
+    hipStream_t s = c->stream;
+    if (source == RPT_DENOISE_ACCUM) {
+        if (c->world != 1u) { c->error = "rpt_denoise: RPT_DENOISE_ACCUM needs a partition of one rank (this context is one of " + std::to_string(c->world) + "): gather, then RPT_DENOISE_GATHERED on rank 0"; return RPT_EINVAL; }
+        RPT_TRY(rpt_wait(c));
+        sums = c->accum.p; order = c->pixel_xy.p; samples = c->samples;
+    } else {
+        RPT_TRY(rpt_comm_gathered_image(c, &sums, &samples, &s));
+    }
+    if (samples == 0u) { c->error = "rpt_denoise: the image has zero samples"; return RPT_EINVAL; }
+    bool rebuilt = false;
+    RPT_TRY(ensure_guides(c, &rebuilt));
+    DenoiseState &d = c->dn;
+    const uint32_t W = d.width, H = d.height, n = W * H;
+    const bool demodulated = p.iterations != 0u && p.demodulate != 0u;
+    HIP_TRY(c, hipEventRecord(d.ev[2], s));
+    k_dn_prepare<<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(sums, order, n, W, (float)samples, demodulated ? d.albedo.p : nullptr, d.ping.p);
+    if (p.iterations == 0u) k_dn_resolve<<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(d.ping.p, n, tonemap_op, d.rgb.p);
+    float4 *src = d.ping.p, *dst = d.pong.p;
+    for (uint32_t i = 0; i < p.iterations; ++i) {
+        const DnPass ps = dn_pass(W, H, i, p.normal_power_log2, p.sigma_color, p.sigma_plane);
+        launch_pass(s, ps, i + 1u == p.iterations, src, d, dst, demodulated ? 1u : 0u, tonemap_op);
+        std::swap(src, dst);
+    }
+    HIP_TRY(c, hipEventRecord(d.ev[3], s));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(out_rgb, d.rgb.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (report) {
+        float ms = 0.0f;
+        *report = rpt_denoise_report{};
+        if (hipEventElapsedTime(&ms, d.ev[2], d.ev[3]) == hipSuccess) report->device_ms = ms;
+        if (rebuilt && hipEventElapsedTime(&ms, d.ev[0], d.ev[1]) == hipSuccess) report->guides_ms = ms;
+        report->guides_rebuilt = rebuilt ? 1u : 0u;
+    }
+    return RPT_OK;
+}
+
+int rpt_read_guides(rpt_ctx *c, float *albedo_rgb, float *normal_xyz, float *depth, float *position_xyz, uint32_t *kind) {
+    if (!c) return RPT_EINVAL;
+    if (!c->has_scene || !c->has_config || !c->has_state) { c->error = "rpt_read_guides: needs a scene and a configuration"; return RPT_EINVAL; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    bool rebuilt = false;
+    RPT_TRY(ensure_guides(c, &rebuilt));
+    const DenoiseState &d = c->dn;
+    const uint32_t n = d.width * d.height;
+    const size_t rgb_bytes = Arena::pad(3 * (size_t)n * sizeof(float)), word_bytes = Arena::pad((size_t)n * sizeof(uint32_t));
+    const size_t bytes = (albedo_rgb ? rgb_bytes : 0) + (normal_xyz ? rgb_bytes : 0) + (position_xyz ? rgb_bytes : 0) + (depth ? word_bytes : 0) + (kind ? word_bytes : 0);
+    if (bytes == 0) return RPT_OK;                   /* nothing asked for: the guides are built, that is all */
+    Arena planes;                                    /* only the planes the caller takes */
+    HIP_TRY(c, planes.reserve(bytes));
+    float *d_albedo = albedo_rgb ? planes.take<float>(3 * (size_t)n) : nullptr, *d_normal = normal_xyz ? planes.take<float>(3 * (size_t)n) : nullptr;
+    float *d_position = position_xyz ? planes.take<float>(3 * (size_t)n) : nullptr, *d_depth = depth ? planes.take<float>(n) : nullptr;
+    uint32_t *d_kind = kind ? planes.take<uint32_t>(n) : nullptr;
+    k_dn_unpack_guides<<<rpt_blocks(n), RPT_BLOCK, 0, c->stream>>>(d.g0.p, d.g1.p, d.albedo.p, n, d_albedo, d_normal, d_depth, d_position, d_kind);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (albedo_rgb) HIP_TRY(c, hipMemcpy(albedo_rgb, d_albedo, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    if (normal_xyz) HIP_TRY(c, hipMemcpy(normal_xyz, d_normal, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    if (position_xyz) HIP_TRY(c, hipMemcpy(position_xyz, d_position, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    if (depth) HIP_TRY(c, hipMemcpy(depth, d_depth, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    if (kind) HIP_TRY(c, hipMemcpy(kind, d_kind, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+
+/* the filter on the host: the loop the kernels of k_denoise.h are, over the same RPT_HD functions */
+int rpt_debug_denoise_host(uint32_t width, uint32_t height, const float *mean_rgb, const float *albedo, const float *normal, const float *position, const float *depth,
+                           const uint32_t *kind, const rpt_denoise_params *params, uint32_t tonemap_op, float *out_rgb) {
+    if (!mean_rgb || !albedo || !normal || !position || !depth || !kind || !out_rgb || width == 0u || height == 0u || width > 65535u || height > 65535u) return RPT_EINVAL;
+    const rpt_denoise_params p = params ? *params : DN_DEFAULTS;
+    std::string error;
+    if (check_params(p, tonemap_op, error)) { rpt_create_error() = error; return RPT_EINVAL; }
+    const size_t n = (size_t)width * height;
+    const bool demodulated = p.iterations != 0u && p.demodulate != 0u;
+    std::vector<float4> g0(n), g1(n), a(n), ping(n), pong(n);
+    for (size_t i = 0; i < n; ++i) {
+        g0[i] = make_float4(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], depth[i]);
+        g1[i] = make_float4(position[3 * i], position[3 * i + 1], position[3 * i + 2], rptm::u2f(kind[i]));
+        a[i] = make_float4(albedo[3 * i], albedo[3 * i + 1], albedo[3 * i + 2], 0.0f);
+        F3 c = f3(mean_rgb[3 * i], mean_rgb[3 * i + 1], mean_rgb[3 * i + 2]);
+        if (demodulated) c = dn_demodulate(c, f3(a[i].x, a[i].y, a[i].z));
+        ping[i] = make_float4(c.x, c.y, c.z, 0.0f);
+    }
+    std::vector<float4> *src = &ping, *dst = &pong;
+    for (uint32_t i = 0; i < p.iterations; ++i) {
+        const DnPass ps = dn_pass(width, height, i, p.normal_power_log2, p.sigma_color, p.sigma_plane);
+        for (uint32_t y = 0; y < height; ++y)
+            for (uint32_t x = 0; x < width; ++x) {
+                const F3 e = dn_filter_pixel(ps, src->data(), g0.data(), g1.data(), x, y);
+                (*dst)[(size_t)y * width + x] = make_float4(e.x, e.y, e.z, 0.0f);
+            }
+        std::swap(src, dst);
+    }
+    for (size_t i = 0; i < n; ++i) {
+        const float4 e = (*src)[i];
+        const F3 c = dn_finish_pixel(f3(e.x, e.y, e.z), f3(a[i].x, a[i].y, a[i].z), demodulated, tonemap_op);
+        out_rgb[3 * i] = c.x; out_rgb[3 * i + 1] = c.y; out_rgb[3 * i + 2] = c.z;
+    }
+    return RPT_OK;
+}
+
+}  // extern "C"

@@ -328,6 +328,7 @@ void rpt_destroy(rpt_ctx *c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     rpt_comm_release(c);                 /* (destroys the RCCL communicator: before anything else goes) */
+    rpt_denoise_release(c, true);
     c->timing.clear();                   /* (its events go while the device is current and the stream they were recorded on exists) */
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;                            /* (frees every buffer of the context) */
@@ -377,9 +378,11 @@ int rpt_set_config(rpt_ctx *c, const rpt_tracing_config *cfg) {
     rotation_x(cfg->cam_rotation[0], rx);
     mat3_mul_host(ry, rx, c->cfg.euler);
     rotation_y(rptm::atan2r(cfg->sun_direction[2], cfg->sun_direction[0]), c->cfg.sky_rot);
+    c->dn.guides_valid = false;          /* the denoiser's guides are the first hits of THIS camera: rebuilt at their next use */
     if (resized || !c->has_state) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         release_state(c);
+        if (resized) rpt_denoise_release(c, false);
         rpt_build_pixel_order(cfg->width, cfg->height, c->rank, c->world, c->pixel_xy_host);
         c->n_pixels = (uint32_t)c->pixel_xy_host.size();
         /* Samples of one pixel in flight.  The GPU holds 8 192 waves = 0.5 M paths at once and ray costs inside a

@@ -687,6 +687,7 @@ int rpt_upload_scene(rpt_ctx *c, const rpt_per_vertex_data *pv, size_t nv, const
     c->bvh_depth = u.facts.max_depth;
     c->stack_cap = c->bvh_depth <= 15 ? 16 : (c->bvh_depth <= 23 ? 24 : 32);
     c->has_scene = true;
+    c->dn.guides_valid = false;          /* the denoiser's guides are first hits in THIS scene */
     return RPT_OK;
 }
 

@@ -25,10 +25,35 @@ EXPORTS = [
     "rpt_multi_reset", "rpt_multi_render", "rpt_multi_wait", "rpt_multi_read_accum", "rpt_multi_get_stats", "rpt_multi_destroy",
     "rpt_multi_last_error", "rpt_comm_library", "rpt_debug_trace_rays_production", "rpt_build_fingerprint", "rpt_debug_comm_selftest", "rpt_device_info", "rpt_shadow_order", "rpt_debug_shadow_order_host", "rpt_last_bounce_order", "rpt_debug_last_order_host", "rpt_debug_short_batch",
     "rpt_set_shadow_mode", "rpt_shadow_mode", "rpt_multi_set_shadow_mode",
+    "rpt_denoise_params_default", "rpt_denoise", "rpt_read_guides", "rpt_multi_denoise", "rpt_debug_denoise_host",
 ]
 COMM_ID_BYTES = 128
 SHADOW_EXACT, SHADOW_SEGMENT = 0, 1          # rpt_set_shadow_mode
 MULTI_ALLOW_SHARED_DEVICE = 1
+DENOISE_ACCUM, DENOISE_GATHERED = 0, 1       # rpt_denoise: which image
+GUIDE_MISS, GUIDE_SURFACE, GUIDE_EMITTER = 0, 1, 2
+
+
+class DenoiseParams(C.Structure):
+    """rpt_denoise_params (include/rpt/rpt.h)"""
+    _fields_ = [("iterations", C.c_uint32), ("normal_power_log2", C.c_uint32), ("sigma_color", C.c_float), ("sigma_plane", C.c_float),
+                ("demodulate", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class DenoiseReport(C.Structure):
+    """rpt_denoise_report"""
+    _fields_ = [("device_ms", C.c_double), ("guides_ms", C.c_double), ("guides_rebuilt", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def denoise_params(**changes):
+    """rpt_denoise_params_default, with the named fields replaced: denoise_params(iterations=3, demodulate=0)"""
+    p = DenoiseParams()
+    lib().rpt_denoise_params_default(C.byref(p))
+    for k, v in changes.items():
+        if k not in ("iterations", "normal_power_log2", "sigma_color", "sigma_plane", "demodulate"):
+            raise TypeError(f"rpt_denoise_params has no field {k}")
+        setattr(p, k, v)
+    return p
 
 
 def lib_path():
@@ -111,6 +136,12 @@ def lib():
         L.rpt_multi_destroy.restype = None
         L.rpt_multi_last_error.argtypes = [C.c_void_p]
         L.rpt_multi_last_error.restype = C.c_char_p
+        L.rpt_denoise_params_default.argtypes = [C.POINTER(DenoiseParams)]
+        L.rpt_denoise_params_default.restype = None
+        L.rpt_denoise.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DenoiseParams), C.c_uint32, C.c_void_p, C.POINTER(DenoiseReport)]
+        L.rpt_read_guides.argtypes = [C.c_void_p] + [C.c_void_p] * 5
+        L.rpt_multi_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_uint32, C.c_void_p, C.POINTER(DenoiseReport)]
+        L.rpt_debug_denoise_host.argtypes = [C.c_uint32, C.c_uint32] + [C.c_void_p] * 6 + [C.POINTER(DenoiseParams), C.c_uint32, C.c_void_p]
         _lib = L
     return _lib
 
@@ -237,6 +268,24 @@ class Renderer:
         out = np.zeros((self.config.height, self.config.width, 3), np.float32)
         self._check(lib().rpt_resolve(self._h, tonemap_op, ptr(out)))
         return out
+
+    # -- rpt_denoise <-> the denoise step of the read-back (reference: src/trace.rs:205-213)
+    def denoise(self, source=DENOISE_ACCUM, params=None, tonemap_op=0, with_report=False):
+        """rpt_denoise: the mean image filtered by the guided a-trous filter, then tonemapped, as (H, W, 3) float32 (params None: the defaults;
+        with_report: also {"device_ms", "guides_ms", "guides_rebuilt"})."""
+        out = np.zeros((self.config.height, self.config.width, 3), np.float32)
+        rep = DenoiseReport()
+        self._check(lib().rpt_denoise(self._h, source, None if params is None else C.byref(params), tonemap_op, ptr(out), C.byref(rep)))
+        return (out, _report_dict(rep)) if with_report else out
+
+    def guides(self):
+        """rpt_read_guides: the first-hit guide buffers of the current scene and camera:
+        {"albedo", "normal", "position": (H, W, 3) float32, "depth": (H, W) float32, "kind": (H, W) uint32 (GUIDE_MISS / SURFACE / EMITTER)}"""
+        h, w = self.config.height, self.config.width
+        g = {"albedo": np.zeros((h, w, 3), np.float32), "normal": np.zeros((h, w, 3), np.float32), "depth": np.zeros((h, w), np.float32),
+             "position": np.zeros((h, w, 3), np.float32), "kind": np.zeros((h, w), np.uint32)}
+        self._check(lib().rpt_read_guides(self._h, ptr(g["albedo"]), ptr(g["normal"]), ptr(g["depth"]), ptr(g["position"]), ptr(g["kind"])))
+        return g
 
     def read_rng(self):
         out = np.zeros(self.config.height * self.config.width, RNG_DTYPE)
@@ -498,6 +547,13 @@ class MultiRenderer:
         self._check(lib().rpt_multi_read_accum(self._h, ptr(out), C.byref(samples)))
         return out, samples.value
 
+    def denoise(self, params=None, tonemap_op=0, with_report=False):
+        """rpt_multi_denoise: waits, gathers if need be, and denoises the whole image on rank 0 (see Renderer.denoise)"""
+        out = np.zeros((self.config.height, self.config.width, 3), np.float32)
+        rep = DenoiseReport()
+        self._check(lib().rpt_multi_denoise(self._h, None if params is None else C.byref(params), tonemap_op, ptr(out), C.byref(rep)))
+        return (out, _report_dict(rep)) if with_report else out
+
     def stats(self):
         s = Stats()
         self._check(lib().rpt_multi_get_stats(self._h, C.byref(s)))
@@ -556,6 +612,26 @@ def debug_math_host(op, x, y=None):
     rc = lib().rpt_debug_math_host(op, ptr(x), ptr(y), ptr(out), x.size)
     if rc != 0:
         raise RptError(rc, "rpt_debug_math_host")
+    return out
+
+
+def _report_dict(rep):
+    return {"device_ms": rep.device_ms, "guides_ms": rep.guides_ms, "guides_rebuilt": rep.guides_rebuilt}
+
+
+def denoise_host(mean_rgb, albedo, normal, position, depth, kind, params=None, tonemap_op=0):
+    """rpt_debug_denoise_host: the filter of Renderer.denoise run on the host from the same header (no GPU needed).  mean_rgb, albedo, normal,
+    position: (H, W, 3); depth, kind: (H, W) — the layouts of Renderer.guides()."""
+    mean_rgb = np.ascontiguousarray(mean_rgb, np.float32)
+    h, w = mean_rgb.shape[:2]
+    planes = [np.ascontiguousarray(a, np.float32) for a in (albedo, normal, position, depth)]
+    kind = np.ascontiguousarray(kind, np.uint32)
+    assert mean_rgb.shape == (h, w, 3) and all(a.shape == (h, w, 3) for a in planes[:3]) and planes[3].shape == (h, w) and kind.shape == (h, w)
+    out = np.zeros((h, w, 3), np.float32)
+    rc = lib().rpt_debug_denoise_host(w, h, ptr(mean_rgb), ptr(planes[0]), ptr(planes[1]), ptr(planes[2]), ptr(planes[3]), ptr(kind),
+                                      None if params is None else C.byref(params), tonemap_op, ptr(out))
+    if rc != 0:
+        raise RptError(rc, lib().rpt_last_error(None).decode())
     return out
 
 

@@ -41,6 +41,7 @@ def lib():
         L.rpt_tracing_state_set_dirty.argtypes = [C.c_void_p, C.c_int]
         L.rpt_tracing_state_set_overlap.argtypes = [C.c_void_p, C.c_int]
         L.rpt_tracing_state_set_interacting.argtypes = [C.c_void_p, C.c_int]
+        L.rpt_tracing_state_set_denoise.argtypes = [C.c_void_p, C.c_int]
         L.rpt_tracing_state_copy_framebuffer.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.rpt_tracing_state_set_config.argtypes = [C.c_void_p, C.POINTER(TracingConfig)]
         L.rpt_tracing_state_new.argtypes = [C.c_uint32, C.c_uint32]
@@ -238,6 +239,10 @@ class TracingState:
     def set_interacting(self, on=True):
         """state.interacting (src/trace.rs:50): while up, every batch flushes (camera drag)."""
         lib().rpt_tracing_state_set_interacting(self._h, C.c_int(1 if on else 0))
+
+    def set_denoise(self, on=True):
+        """state.denoise (src/trace.rs:45): trace_gpu publishes the denoised image (rpt_denoise, defaults) on iterations that do not flush."""
+        lib().rpt_tracing_state_set_denoise(self._h, C.c_int(1 if on else 0))
 
     def set_overlap(self, on=True):
         """trace_gpu reads batch k back while batch k+1 renders (rpt_tracing_state_set_overlap)."""
