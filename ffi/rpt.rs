@@ -66,6 +66,33 @@ pub struct rpt_denoise_report {
     pub reserved: u32,
 }
 
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct rpt_noise_counts {
+    pub pixels: u64,     // pixels the context owns
+    pub measured: u64,   // of those: two samples or more in the moments record
+    pub above: u64,      // of those: !(noise_rel <= threshold)
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct rpt_noise_target {
+    pub threshold: f32,
+    pub min_samples: u32,
+    pub max_samples: u32,
+    pub batch_samples: u32,
+    pub max_above: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct rpt_noise_result {
+    pub samples_rendered: u32,
+    pub converged: u32,
+    pub counts: rpt_noise_counts,
+    pub ms: f64,
+}
+
 extern "C" {
     pub fn rpt_abi_version() -> c_int;                                              // == 3
     pub fn rpt_build_fingerprint() -> *const c_char;                                // fingerprint of the kernel sources the library was built from
@@ -101,6 +128,13 @@ extern "C" {
     pub fn rpt_denoise_params_default(out: *mut rpt_denoise_params);
     pub fn rpt_denoise(ctx: *mut rpt_ctx, source: u32, params: *const rpt_denoise_params, tonemap_op: u32, out_rgb: *mut f32, report: *mut rpt_denoise_report) -> c_int;
     pub fn rpt_read_guides(ctx: *mut rpt_ctx, albedo_rgb: *mut f32, normal_xyz: *mut f32, depth: *mut f32, position_xyz: *mut f32, kind: *mut u32) -> c_int;   // each nullable; albedo / normal = OIDN's auxiliary images
+    // opt-in per-pixel sample moments (sum Y, sum Y^2, n, max Y), the noise estimate from them, and "render until the image is this clean"
+    pub fn rpt_set_moments(ctx: *mut rpt_ctx, on: u32) -> c_int;                    // default 0; on: allocates and zeroes the record
+    pub fn rpt_moments(ctx: *mut rpt_ctx, on_out: *mut u32) -> c_int;
+    pub fn rpt_read_moments(ctx: *mut rpt_ctx, out_xyzw: *mut Vec4) -> c_int;       // width*height, row-major; other ranks' pixels zero
+    pub fn rpt_read_noise(ctx: *mut rpt_ctx, rel_out: *mut f32) -> c_int;           // standard error of the mean luminance / (|mean| + 0.01)
+    pub fn rpt_noise_count(ctx: *mut rpt_ctx, threshold: f32, out: *mut rpt_noise_counts) -> c_int;   // integers: a process-per-GPU host all-reduces them itself
+    pub fn rpt_render_to_noise(ctx: *mut rpt_ctx, target: *const rpt_noise_target, out: *mut rpt_noise_result) -> c_int;
     pub fn rpt_get_stats(ctx: *mut rpt_ctx, out: *mut rpt_stats) -> c_int;
     pub fn rpt_destroy(ctx: *mut rpt_ctx);
 
@@ -123,6 +157,10 @@ extern "C" {
     pub fn rpt_multi_wait(m: *mut rpt_multi) -> c_int;
     pub fn rpt_multi_read_accum(m: *mut rpt_multi, out: *mut Vec4, out_samples: *mut u32) -> c_int;   // the whole W x H image, from rank 0
     pub fn rpt_multi_denoise(m: *mut rpt_multi, params: *const rpt_denoise_params, tonemap_op: u32, out_rgb: *mut f32, report: *mut rpt_denoise_report) -> c_int;   // waits, gathers, denoises on rank 0
+    pub fn rpt_multi_set_moments(m: *mut rpt_multi, on: u32) -> c_int;              // rpt_set_moments on every rank
+    pub fn rpt_multi_read_moments(m: *mut rpt_multi, out_xyzw: *mut Vec4) -> c_int; // the ranks' records merged on the host
+    pub fn rpt_multi_noise_count(m: *mut rpt_multi, threshold: f32, out: *mut rpt_noise_counts) -> c_int;   // summed over the ranks
+    pub fn rpt_multi_render_to_noise(m: *mut rpt_multi, target: *const rpt_noise_target, out: *mut rpt_noise_result) -> c_int;
     pub fn rpt_multi_get_stats(m: *mut rpt_multi, out: *mut rpt_stats) -> c_int;
     pub fn rpt_multi_last_error(m: *mut rpt_multi) -> *const c_char;
     pub fn rpt_multi_destroy(m: *mut rpt_multi);

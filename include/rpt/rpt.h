@@ -232,6 +232,7 @@ int rpt_multi_upload_scene(rpt_multi *m,
 int rpt_multi_set_config(rpt_multi *m, const rpt_tracing_config *config);
 int rpt_multi_reset(rpt_multi *m, const rpt_rng_state *rng_seed, const float *accum_init_rgba, uint32_t samples_init);
 int rpt_multi_set_shadow_mode(rpt_multi *m, uint32_t mode);  /* rpt_set_shadow_mode (below) on every rank */
+/* (rpt_multi_set_moments, rpt_multi_read_moments, rpt_multi_noise_count, rpt_multi_render_to_noise: with the moments, below) */
 int rpt_multi_render(rpt_multi *m, uint32_t n_samples);
 int rpt_multi_wait(rpt_multi *m);
 int rpt_multi_read_accum(rpt_multi *m, float *out_rgba, uint32_t *out_samples);
@@ -338,6 +339,77 @@ int rpt_denoise(rpt_ctx *ctx, uint32_t source, const rpt_denoise_params *params 
 int rpt_read_guides(rpt_ctx *ctx, float *albedo_rgb, float *normal_xyz, float *depth, float *position_xyz, uint32_t *kind);
 /* waits, gathers as rpt_multi_read_accum does, and denoises on rank 0 */
 int rpt_multi_denoise(rpt_multi *m, const rpt_denoise_params *params, uint32_t tonemap_op, float *out_rgb, rpt_denoise_report *report);
+
+/* --- per-pixel sample moments, noise estimate, render to a noise target (no reference equivalent: `samples` is the only progress figure of the reference's
+ * TracingState, src/trace.rs:40-50) ------------------------------------------------------------------------------------------------------------------
+ * Opt-in; the default pipeline, its parity statements and bench.py's figures are not touched, and the image does not depend on it, bit for bit.
+ * With moments on a context keeps one more float4 per owned pixel beside the accumulator, updated once per finished sample, in sample order, with the radiance r
+ * that the accumulator gets (csrc/k_moments.h, f32, no contraction):
+ *     Y = (0.2126f * r.x + 0.7152f * r.y) + 0.0722f * r.z
+ *     m.x += Y          sum of luminance                  m.z += 1          samples since the moments were last zeroed
+ *     m.y += (Y * Y)    product rounded, then added       m.w  = Y > m.w ? Y : m.w     the brightest sample (a NaN never enters)
+ * The f32 sum order is part of the result, as for the accumulator: the record equals a sequential restatement word for word (tests/test_gpu_moments.py).
+ * They are added by a second completion kernel (csrc/k_complete.h k_complete_moments) that is launched instead of k_complete while moments are on; every
+ * other kernel is the same.  A sample must pass through that kernel, so a render call with moments on keeps at least two slots per pixel busy (a
+ * one-sample call uses slot 0 of 2); a context that can only have one — after rpt_set_samples_in_flight(ctx, 1), or with an image too large for two slots
+ * per pixel — refuses to render with moments on (RPT_EINVAL, the message says so; rpt_set_samples_in_flight(ctx, 0) or rpt_set_moments(ctx, 0) is the way
+ * out) and stays usable.
+ * Cost, DERIVED, NOT YET MEASURED on a device (tools/moments_probe.py --cost is the measurement; profiles/r12_moments.txt says what has been run): the
+ * completion reads 32 x 16 B of radiance and moves 32 B of accumulator per pixel and 32-spp batch; the moments add 32 B (+6 % of that stage's traffic) and four VALU
+ * operations per sample; the stage is about 2 % of a batch, so a batch should move by about 0.1 %.  With moments off the completion kernel is the same kernel,
+ * instruction for instruction.
+ *
+ * rpt_set_moments   may be called between any two batches; synchronises.  Turning it on allocates and zeroes the record (on while on: nothing happens),
+ *                   turning it off frees it.  Leaves the accumulator, the rng, rpt_stats and the shadow mode untouched.
+ * The moments are zeroed when they are turned on, by rpt_reset, and by every configuration change that invalidates the accumulator (a resize,
+ * rpt_set_partition, rpt_set_samples_in_flight).  rpt_reset with accum_init resumes the accumulator but NOT the moments: m.z then counts only the samples
+ * rendered since, while the accumulator's .w continues from samples_init.
+ *
+ * noise_rel(m), with n = m.z: +inf if n < 2 or m.x or m.y is not finite; else
+ *     mean = m.x / n;  ss = m.y - (m.x * m.x) / n;  v = ss / (n * (n - 1));  sem = sqrt(v > 0 ? v : 0);  rel = sem / (|mean| + 0.01f)
+ * — the standard error of the pixel's mean luminance relative to that mean, with a floor that keeps black pixels finite.
+ * A LIMIT OF EVERY EMPIRICAL-VARIANCE CRITERION: a pixel whose samples so far were all equal has rel = 0 and looks converged.  On DarkCornell without NEE
+ * at 100 x 70, 6453 of 7000 pixels have zero variance after 8 samples (most have not seen the light yet) and only 507 are above any threshold; after 128
+ * samples 4511 are above 0.1.  That is what rpt_noise_target.min_samples is for (DESIGN.md "Moments and noise estimate").
+ *
+ * rpt_read_moments  width*height float4, row-major; rpt_read_noise: noise_rel of every pixel, width*height floats.  Both synchronise and un-tile as
+ *                   rpt_read_accum does; other ranks' pixels are zero.
+ * rpt_noise_count   pixels = the pixels this context owns, measured = those with n >= 2, above = the measured ones with !(rel <= threshold).  One kernel
+ *                   with integer atomics behind whatever is enqueued, 24 bytes read back.  Integers: order-independent and additive over ranks —
+ *                   rpt_multi_noise_count is the sum over its contexts; a process-per-GPU caller (rpt_comm_*) all-reduces the three integers itself
+ *                   (nothing is added to the gather).  threshold: >= 0, +inf allowed.
+ * rpt_render_to_noise   turns moments on if they are off (and leaves them on), then renders batches of batch_samples through rpt_render_async, the last one
+ *                   clipped so that max_samples is not exceeded; after each batch, once at least min_samples have been rendered by this call, it counts
+ *                   (same stream, one small read-back per batch) and stops with converged = 1 when measured == pixels && above <= max_above, or with
+ *                   converged = 0 at max_samples.  The accumulator is bit for bit that of plain rendering of samples_rendered samples: the image never
+ *                   depends on how samples are split into calls.  counts = the last count; ms = host clock over the whole call.
+ *                   RPT_EINVAL for batch_samples == 0, max_samples < min_samples, a negative or NaN threshold.
+ * rpt_multi_*       the same on every rank; rpt_multi_read_moments merges the ranks' images on the host (the pixels are disjoint; off the hot path).
+ * RPT_EINVAL from the read and count entry points while moments are off, and for null pointers. */
+int rpt_set_moments(rpt_ctx *ctx, uint32_t on);      /* default 0 */
+int rpt_moments(rpt_ctx *ctx, uint32_t *on_out);
+int rpt_read_moments(rpt_ctx *ctx, float *out_xyzw); /* width*height float4, row-major; other ranks' pixels zero */
+int rpt_read_noise(rpt_ctx *ctx, float *rel_out);    /* width*height floats, row-major; other ranks' pixels zero */
+
+typedef struct rpt_noise_counts { uint64_t pixels, measured, above; } rpt_noise_counts;
+int rpt_noise_count(rpt_ctx *ctx, float threshold, rpt_noise_counts *out);
+
+typedef struct rpt_noise_target {
+    float threshold;
+    uint32_t min_samples, max_samples, batch_samples;
+    uint64_t max_above;
+} rpt_noise_target;
+typedef struct rpt_noise_result {
+    uint32_t samples_rendered, converged;
+    rpt_noise_counts counts;
+    double ms;
+} rpt_noise_result;
+int rpt_render_to_noise(rpt_ctx *ctx, const rpt_noise_target *target, rpt_noise_result *out);
+
+int rpt_multi_set_moments(rpt_multi *m, uint32_t on);
+int rpt_multi_read_moments(rpt_multi *m, float *out_xyzw);
+int rpt_multi_noise_count(rpt_multi *m, float threshold, rpt_noise_counts *out);
+int rpt_multi_render_to_noise(rpt_multi *m, const rpt_noise_target *target, rpt_noise_result *out);
 
 /* --- scene preparation on the device ---------------------- */
 /* BVHBuilder::new(vertices, indices).sah_samples(n).build()  (reference src/bvh.rs:59-324, the call at

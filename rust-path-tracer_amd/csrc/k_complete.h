@@ -6,6 +6,7 @@
 #define RPT_K_COMPLETE_H
 
 #include "k_path.h"
+#include "k_moments.h"
 
 /* Completion of generations: ONE WAVE PER CHUNK of 64 pixels, lane = pixel.  When all S slots of a pixel are finished (HIT_DONE) or have
  * nothing left (HIT_IDLE) and at least one is finished, their radiances are added to the accumulator IN SLOT ORDER (= sample order,
@@ -24,7 +25,10 @@
  * pixel in flight (a rank that owns 1/8 of an image fills its launches with 8 x the samples per pixel).
  * History: round 2 completed inside the shade stage (a DPP chain across lanes, 0.45 ms of a DarkCornell batch); rounds 3-5 one THREAD per
  * pixel looping over its slots — coalesced only at q_shift = 0: 5.6 ms instead of 0.9 per 2048^2 x 32 slots on the large-scene layout.
- * A batch of known length (no slot takes a second sample) runs this once, after its last iteration; otherwise it follows every shade stage. */
+ * A batch of known length (no slot takes a second sample) runs this once, after its last iteration; otherwise it follows every shade stage.
+ * Two kernels share the text (k_complete_body.h, compiled twice): k_complete, and k_complete_moments for a context with moments on (rpt_set_moments), which adds
+ * every sample it adds to the accumulator to the pixel's moments record too (k_moments.h mo_add) — from the same registers / tile column, in the same
+ * order: one more float4 load and store per completing pixel, four VALU operations per sample. */
 #define RPT_COMPLETE_ROWS 32u          /* samples of a pixel staged per pass */
 #define RPT_COMPLETE_PITCH 65u         /* float4 per tile row: 64 pixels + 1 (the transposing stores of a q_shift > 0 row would share a bank) */
 __host__ __device__ __forceinline__ uint32_t complete_rows(uint32_t S) { return S < RPT_COMPLETE_ROWS ? S : RPT_COMPLETE_ROWS; }
@@ -53,27 +57,6 @@ __device__ __forceinline__ void complete_status_rows(const DevState &st, uint32_
             if (bits != 0u) top = ((row & ((1u << (gs - qs)) - 1u)) << qs) + 32u - (uint32_t)__clz((int)bits);    /* (rows ascend: the last one wins) */
         }
     }
-}
-/* pass 2 at q_shift = 0 (every shipped scene): row k of the chunk IS sample k of its 64 pixels with the lane's own pixel in its own lane — nothing to
- * transpose, no tile: G rows in flight, added in order straight from the registers; finished slots (k < n_done: the prefix) that owe nothing go idle. */
-template <uint32_t G>
-__device__ __forceinline__ bool complete_direct_rows(const DevState &st, uint32_t base, uint32_t k0, uint32_t lane, bool ok, uint32_t n_done, float4 &acc) {
-    float rx[G], ry[G], rz[G], rw[G];
-    bool restart = false;
-#pragma unroll
-    for (uint32_t i = 0u; i < G; ++i) {
-        const float4 r = st.rad[base + ((k0 + i) << 6) + lane];
-        rx[i] = r.x; ry[i] = r.y; rz[i] = r.z; rw[i] = r.w;
-    }
-#pragma unroll
-    for (uint32_t i = 0u; i < G; ++i) {
-        const bool mine = ok && k0 + i < n_done;
-        if (mine) { acc.x += rx[i]; acc.y += ry[i]; acc.z += rz[i]; acc.w += 1.0f; }
-        const uint32_t todo = __float_as_uint(rw[i]);
-        if (mine && todo == 0u) st.hit[base + ((k0 + i) << 6) + lane] = make_float2(0.0f, __uint_as_float(HIT_IDLE));
-        restart = restart || rpt_ballot(mine && todo != 0u) != 0ull;
-    }
-    return restart;
 }
 /* Row t of a block of `rows` samples starting at sample kb: for every pixel group, rows >> qs consecutive rows of the chunk. */
 __device__ __forceinline__ uint32_t complete_block_slot(const DevState &st, uint32_t base, uint32_t kb, uint32_t t, uint32_t rows, uint32_t rows_log, uint32_t lane) {
@@ -124,92 +107,24 @@ __device__ __forceinline__ bool complete_restart_rows(const DevState &st, const 
     }
     return started;
 }
-__global__ __launch_bounds__(RPT_WAVE) void k_complete(DevState st, DevQueues q, DevConfig cfg, uint32_t iteration, uint32_t final_pass,
-                                                       DevStats *stats) {
-    /* a surplus launch of the run-ahead returns at once (grid-uniform) — but not the one completion of a batch of known length:
-     * "drained" there only says that no RAY was left in an earlier iteration, the finished samples still wait to be added */
-    if (!final_pass && q.count[Q_DRAINED] != 0u) return;
-    extern __shared__ float4 complete_lds[];
-    const uint32_t gs = st.group_shift, qs = st.q_shift, S = 1u << gs, rows = complete_rows(S);
-    float4 *tile = complete_lds;
-    unsigned long long *row_done = reinterpret_cast<unsigned long long *>(complete_lds + rows * RPT_COMPLETE_PITCH);
-    const uint32_t lane = threadIdx.x, base = blockIdx.x << (6u + gs), pix = (blockIdx.x << 6) | lane;
-    const bool in_image = pix < st.n_pixels;
-    /* the rows that hold this lane's pixel (row >> (gs - qs) == its group), and where its Q slots sit in such a row's ballots */
-    const uint32_t my_group = lane >> (6u - qs), my_shift = (lane & ((64u >> qs) - 1u)) << qs;
-    const unsigned long long q_mask = (1ull << (1u << qs)) - 1ull;             /* (Q <= 32) */
-    uint32_t n_done = 0u, n_busy = 0u, top = 0u;
-    bool nothing_to_do = false;
-    if (S >= 8u) {
-        for (uint32_t j0 = 0u; j0 < S && !nothing_to_do; j0 += 8u) {
-            complete_status_rows<8>(st, base, j0, lane, row_done, my_group, my_shift, q_mask, n_done, n_busy, top);
-            /* between the iterations of a call whose slots take several samples most pixels have a sample in flight: nothing to do for the chunk */
-            nothing_to_do = !final_pass && rpt_ballot(in_image && n_busy == 0u) == 0ull;
-        }
-    } else if (S == 4u) complete_status_rows<4>(st, base, 0u, lane, row_done, my_group, my_shift, q_mask, n_done, n_busy, top);
-    else complete_status_rows<2>(st, base, 0u, lane, row_done, my_group, my_shift, q_mask, n_done, n_busy, top);
-    if (nothing_to_do) return;
-    const bool ok = in_image && n_busy == 0u && n_done != 0u && top == n_done;
-    if (final_pass && in_image && (n_busy != 0u || top != n_done)) {
-        /* the one completion of a batch of known length found a sample still in flight: the bound on its iterations was wrong (must never
-         * happen; rpt_wait / rpt_render report it) — or finished slots that are no prefix.  Counted like k_check_drained would: slots not idle. */
-        atomicAdd(&stats->undrained, (unsigned long long)(n_done + n_busy));
-    }
-    const unsigned long long ok_mask = rpt_ballot(ok);
-    bool started = false;
-    if (ok_mask != 0ull) {
-        float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        uint2 rs = make_uint2(0u, 0u);
-        if (ok) { acc = st.accum[pix]; rs = st.rng[pix]; }
-        const uint32_t new_n = rs.x + n_done;
-        uint32_t most = ok ? n_done : 0u;                                   /* the chunk's longest prefix (wave-uniform) */
-        for (uint32_t o = 32u; o != 0u; o >>= 1) { const uint32_t other = (uint32_t)__shfl_xor((int)most, (int)o, RPT_WAVE); most = other > most ? other : most; }
-        const uint32_t rows_log = 31u - (uint32_t)__clz((int)rows);
-        __syncthreads();                                                    /* row_done written */
-        if (qs == 0u) {
-            const uint32_t G = S >= 8u ? 8u : S;
-            for (uint32_t k0 = 0u; k0 < most; k0 += G) {
-                bool restart;
-                if (G == 8u) restart = complete_direct_rows<8>(st, base, k0, lane, ok, n_done, acc);
-                else if (G == 4u) restart = complete_direct_rows<4>(st, base, k0, lane, ok, n_done, acc);
-                else restart = complete_direct_rows<2>(st, base, k0, lane, ok, n_done, acc);
-                if (restart) {                                              /* (never in the one completion of a batch of known length) */
-#pragma unroll 1
-                    for (uint32_t k = k0; k < k0 + G; ++k) {
-                        const uint32_t slot = base + (k << 6) + lane, todo = __float_as_uint(st.rad[slot].w);
-                        if (ok && k < n_done && todo != 0u) {
-                            start_path(st, cfg, slot, new_n + k, rs.y, todo - 1u);      /* slot k takes the samples k, k + S, ... */
-                            started = true;
-                        }
-                    }
-                }
-            }
-        } else
-        for (uint32_t kb = 0u; kb < most; kb += rows) {
-            /* the rows that hold samples [kb, kb + rows) of all 64 pixels: for every pixel group, rows >> qs consecutive rows */
-            bool restart = false;
-            if (rows >= 8u) {
-                for (uint32_t t0 = 0u; t0 < rows; t0 += 8u) restart |= complete_stage_rows<8>(st, base, kb, t0, rows, rows_log, lane, tile, row_done, ok_mask);
-            } else if (rows == 4u) restart = complete_stage_rows<4>(st, base, kb, 0u, rows, rows_log, lane, tile, row_done, ok_mask);
-            else restart = complete_stage_rows<2>(st, base, kb, 0u, rows, rows_log, lane, tile, row_done, ok_mask);
-            __syncthreads();
-            const uint32_t here = most - kb < rows ? most - kb : rows;
-            for (uint32_t kl = 0u; kl < here; ++kl) {
-                const float4 r = tile[kl * RPT_COMPLETE_PITCH + lane];
-                if (ok && kb + kl < n_done) { acc.x += r.x; acc.y += r.y; acc.z += r.z; acc.w += 1.0f; }
-            }
-            if (restart) started |= complete_restart_rows(st, cfg, base, kb, rows, rows_log, lane, tile, row_done, ok_mask, new_n, rs.y);
-            __syncthreads();
-        }
-        if (ok) {
-            st.accum[pix] = acc;
-            rs.x = new_n;
-            st.rng[pix] = rs;
-        }
-    }
-    /* tell the host that new samples were started (one plain store per wave, every writer stores 1) */
-    const unsigned long long any = rpt_ballot(started);
-    if (any != 0ull && lane == (uint32_t)__ffsll((long long)any) - 1u) raise_flag(&q.count[Q_REGEN0 + (iteration & 1u) * Q_LINE]);
-}
+/* The kernels: one text (k_complete_body.h: the kernel and the q_shift = 0 row helper it calls) compiled twice; RPT_MOM(...) there is its argument in
+ * the moments build and nothing in the plain one, so the plain k_complete is compiled from the text it always had.  k_complete stays a plain kernel under that
+ * name, not a template instantiation (tests/test_kernel_resources.py finds the completion kernels by the prefix "k_complete"); k_complete_moments is launched
+ * instead of it by a context with moments on.  The moments pointer is an argument of that kernel, not a field of DevState, which every stage kernel takes:
+ * no other kernel changes. */
+#define RPT_COMPLETE_KERNEL k_complete
+#define RPT_COMPLETE_DIRECT_ROWS complete_direct_rows
+#define RPT_MOM(...)
+#include "k_complete_body.h"
+#undef RPT_COMPLETE_KERNEL
+#undef RPT_COMPLETE_DIRECT_ROWS
+#undef RPT_MOM
+#define RPT_COMPLETE_KERNEL k_complete_moments
+#define RPT_COMPLETE_DIRECT_ROWS complete_direct_rows_moments
+#define RPT_MOM(...) __VA_ARGS__
+#include "k_complete_body.h"
+#undef RPT_COMPLETE_KERNEL
+#undef RPT_COMPLETE_DIRECT_ROWS
+#undef RPT_MOM
 
 #endif /* RPT_K_COMPLETE_H */

@@ -706,6 +706,62 @@ int rpt_multi_denoise(rpt_multi *m, const rpt_denoise_params *params, uint32_t t
     return rc ? multi_fail(m, root, rc) : RPT_OK;
 }
 
+/* rpt_set_moments on every rank */
+int rpt_multi_set_moments(rpt_multi *m, uint32_t on) {
+    if (!m) return RPT_EINVAL;
+    for (rpt_ctx *c : m->ctx) {
+        int rc = rpt_set_moments(c, on);
+        if (rc) return multi_fail(m, c, rc);
+    }
+    return RPT_OK;
+}
+
+/* the ranks' images merged on the host: their pixels are disjoint (off the hot path, called rarely — nothing is added to the gather) */
+int rpt_multi_read_moments(rpt_multi *m, float *out_xyzw) {
+    if (!m || !out_xyzw) return RPT_EINVAL;
+    int rc = rpt_multi_wait(m);
+    if (rc) return rc;
+    std::vector<float> one;
+    for (size_t r = 0; r < m->ctx.size(); ++r) {
+        rpt_ctx *c = m->ctx[r];
+        if (r == 0) {                    /* (rank 0's image is the canvas: zeros where it owns nothing) */
+            if ((rc = rpt_read_moments(c, out_xyzw))) return multi_fail(m, c, rc);
+            one.resize((size_t)c->cfg.c.width * c->cfg.c.height * 4);
+            continue;
+        }
+        if ((rc = rpt_read_moments(c, one.data()))) return multi_fail(m, c, rc);
+        const uint32_t W = c->cfg.c.width;
+        for (uint32_t pxy : c->pixel_xy_host) {
+            const size_t at = ((size_t)(pxy >> 16) * W + (pxy & 0xffffu)) * 4;
+            memcpy(out_xyzw + at, one.data() + at, 4 * sizeof(float));
+        }
+    }
+    return RPT_OK;
+}
+
+/* integers: the sum over the ranks */
+int rpt_multi_noise_count(rpt_multi *m, float threshold, rpt_noise_counts *out) {
+    if (!m || !out) return RPT_EINVAL;
+    rpt_noise_counts sum{};
+    for (rpt_ctx *c : m->ctx) {
+        rpt_noise_counts k;
+        int rc = rpt_noise_count(c, threshold, &k);
+        if (rc) return multi_fail(m, c, rc);
+        sum.pixels += k.pixels; sum.measured += k.measured; sum.above += k.above;
+    }
+    *out = sum;
+    return RPT_OK;
+}
+
+/* rpt_render_to_noise over rpt_multi_render (a batch on every GPU + its gather) and rpt_multi_noise_count */
+int rpt_multi_render_to_noise(rpt_multi *m, const rpt_noise_target *target, rpt_noise_result *out) {
+    if (!m || !target || !out) return RPT_EINVAL;
+    int rc = rpt_multi_set_moments(m, 1u);
+    if (rc) return rc;
+    return rpt_render_to_noise_with(target, out, m->error, [](void *who, uint32_t n) { return rpt_multi_render(static_cast<rpt_multi *>(who), n); },
+                                    [](void *who, float threshold, rpt_noise_counts *k) { return rpt_multi_noise_count(static_cast<rpt_multi *>(who), threshold, k); }, m);
+}
+
 int rpt_multi_get_stats(rpt_multi *m, rpt_stats *out) {
     if (!m || !out) return RPT_EINVAL;
     rpt_stats sum{};

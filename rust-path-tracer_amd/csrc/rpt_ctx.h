@@ -1,7 +1,8 @@
 /*
  * rpt_ctx.h — the context object behind the C ABI of include/rpt/rpt.h, shared by the translation units of
  * librpt_hip.so (rpt_hip.hip: life cycle, state and wavefront scheduling; rpt_scene.hip: scene preparation; rpt_traverse.hip: the traversal stages;
- * rpt_comm.hip: multi-GPU gather over RCCL, read-back; rpt_denoise.hip: guide buffers and the denoise filter; rpt_debug.hip: test hooks).
+ * rpt_comm.hip: multi-GPU gather over RCCL, read-back; rpt_denoise.hip: guide buffers and the denoise filter; rpt_moments.hip: sample moments, noise estimate,
+ * render to a noise target; rpt_debug.hip: test hooks).
  */
 #ifndef RPT_CTX_H
 #define RPT_CTX_H
@@ -221,6 +222,9 @@ struct rpt_ctx {
     DevBuf<float2> ray_b, hit;
     DevBuf<float4> ray_a, thr, rad, mis_a, mis_b, accum;
     DevBuf<uint2> rng;
+    bool moments_on = false;             /* rpt_set_moments: render calls launch k_complete_moments and keep at least two slots per pixel busy (plan_slots) */
+    DevBuf<float4> moments;              /* moments on: one record per owned pixel beside `accum`, same order (k_moments.h); zeroed whenever the accumulator is invalidated */
+    DevBuf<unsigned long long> noise_counts;   /* rpt_noise_count: pixels, measured, above — allocated at its first use */
     DevBuf<uint32_t> q_sky, q_count;
     DevBuf<unsigned long long> ray_shards;
     DevBuf<float4> sh_o, sh_d, sh_c;
@@ -274,6 +278,11 @@ void rpt_comm_release(rpt_ctx *c);
 /* rpt_comm.hip, for rpt_denoise(RPT_DENOISE_GATHERED): the image of the last gather on rank 0 of a communicator, once that gather has completed, its sample
  * count and the stream the gather ran on (work on it is ordered after the gather and overlaps the batch on the context's own stream) */
 int rpt_comm_gathered_image(rpt_ctx *c, const float4 **image_out, uint32_t *samples_out, hipStream_t *stream_out);
+/* rpt_moments.hip: the moments record of a context with moments on, for its current pixel count: allocated if need be and zeroed on the context's stream */
+int rpt_moments_reset(rpt_ctx *c);
+/* rpt_moments.hip, for rpt_multi_render_to_noise (rpt_comm.hip): the loop of rpt_render_to_noise over the caller's "render n more samples" and "count" */
+int rpt_render_to_noise_with(const rpt_noise_target *target, rpt_noise_result *out, std::string &error, int (*render)(void *, uint32_t), int (*count)(void *, float, rpt_noise_counts *),
+                             void *who);
 /* rpt_denoise.hip: the denoiser's buffers go (a resize), or buffers and events (the context goes away: while its device is current) */
 void rpt_denoise_release(rpt_ctx *c, bool events_too);
 std::string &rpt_create_error();

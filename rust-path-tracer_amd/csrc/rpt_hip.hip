@@ -103,7 +103,7 @@ void mat3_mul_host(const float *a, const float *b, float *out) {   /* Mat3 * Mat
 void release_state(rpt_ctx *c) {
     c->ray_a.release(); c->ray_b.release(); c->hit.release(); c->thr.release(); c->rad.release();
     c->mis_a.release(); c->mis_b.release();
-    c->accum.release(); c->rng.release();
+    c->accum.release(); c->rng.release(); c->moments.release();
     c->q_sky.release(); c->q_count.release(); c->ray_shards.release();
     c->sh_o.release(); c->sh_d.release(); c->sh_c.release();
     c->pixel_xy.release();
@@ -153,6 +153,11 @@ static uint32_t padded_pixels(uint32_t n_pixels) { return (n_pixels + 63u) & ~63
 
 /* one wave per chunk of 64 pixels (k_complete.h) */
 static void launch_complete(rpt_ctx *c, uint32_t iteration, uint32_t final_pass) {
+    if (c->moments_on) {             /* (rpt_set_moments: the same completion, the samples added to the moments record too) */
+        k_complete_moments<<<padded_pixels(c->n_pixels) / RPT_WAVE, RPT_WAVE, complete_lds_bytes(1u << c->group_shift, c->state.q_shift), c->stream>>>(c->state, c->queues, c->cfg, iteration,
+                                                                                                                                 final_pass, c->dev_stats.p, c->moments.p);
+        return;
+    }
     k_complete<<<padded_pixels(c->n_pixels) / RPT_WAVE, RPT_WAVE, complete_lds_bytes(1u << c->group_shift, c->state.q_shift), c->stream>>>(c->state, c->queues, c->cfg, iteration, final_pass,
                                                                                                                      c->dev_stats.p);
 }
@@ -421,6 +426,7 @@ int rpt_set_config(rpt_ctx *c, const rpt_tracing_config *cfg) {
             HIP_TRY(c, hipMemsetAsync(c->rng.p, 0, c->n_pixels * sizeof(uint2), c->stream));
         }
         c->samples = 0;
+        RPT_TRY(rpt_moments_reset(c));       /* (moments on: a record for the new pixel count, zeroed like the accumulator) */
     }
     c->has_config = true;
     return RPT_OK;
@@ -447,6 +453,7 @@ int rpt_reset(rpt_ctx *c, const rpt_rng_state *seed, const float *accum_init, ui
     }
     HIP_TRY(c, hipMemsetAsync(c->dev_stats.p, 0, sizeof(DevStats), c->stream));
     HIP_TRY(c, hipMemsetAsync(c->ray_shards.p, 0, RPT_STAT_SHARDS * RPT_STAT_STRIDE * sizeof(unsigned long long), c->stream));
+    RPT_TRY(rpt_moments_reset(c));           /* (not resumed: with accum_init the record counts the samples rendered from here on) */
     c->samples = accum_init ? samples_init : 0u;
     c->stats = rpt_stats{};
     return RPT_OK;
@@ -501,10 +508,24 @@ int rpt_stream(rpt_ctx *c, void **stream_out) {
     return RPT_OK;
 }
 
-/* slots per pixel of THIS call — no more than it has samples for — and the per-slot state at that size */
+/* slots per pixel of THIS call — no more than it has samples for — and the per-slot state at that size.  With moments on at least two: with ONE slot per
+ * pixel a sample is accumulated inline by the side stages (k_path.h finish_in_side_stage), which know nothing of the moments record; with two, a one-sample
+ * call uses slot 0 of 2 (as a 5-sample call uses 5 of 8) and its sample passes through the completion kernel. */
 static int plan_slots(rpt_ctx *c, uint32_t n_samples) {
     uint32_t shift = 0;
     while (shift < c->max_group_shift && (1u << shift) < n_samples) shift += 1;
+    if (c->moments_on && shift == 0u) {
+        if (c->max_group_shift == 0u) {
+            c->error = "moments are on and this context keeps one sample of a pixel in flight (rpt_set_samples_in_flight(1), or an image too large for two slots per pixel): "
+                       "the moments are added by the completion kernel, which needs at least two; call rpt_set_samples_in_flight(0) or (>= 2), or rpt_set_moments(ctx, 0)";
+            return RPT_EINVAL;
+        }
+        shift = 1u;
+    }
+    if (c->moments_on && c->moments.n != c->n_pixels) {      /* (an allocation of the record failed earlier: k_complete_moments must not be launched without it) */
+        c->error = "moments are on but their record is not allocated (an earlier allocation failed): call rpt_set_moments(ctx, 0)";
+        return RPT_ENOMEM;
+    }
     c->group_shift = shift;
     c->n_slots = padded_pixels(c->n_pixels) << shift;
     c->state.group_shift = shift;

@@ -26,6 +26,8 @@ EXPORTS = [
     "rpt_multi_last_error", "rpt_comm_library", "rpt_debug_trace_rays_production", "rpt_build_fingerprint", "rpt_debug_comm_selftest", "rpt_device_info", "rpt_shadow_order", "rpt_debug_shadow_order_host", "rpt_last_bounce_order", "rpt_debug_last_order_host", "rpt_debug_short_batch",
     "rpt_set_shadow_mode", "rpt_shadow_mode", "rpt_multi_set_shadow_mode",
     "rpt_denoise_params_default", "rpt_denoise", "rpt_read_guides", "rpt_multi_denoise", "rpt_debug_denoise_host",
+    "rpt_set_moments", "rpt_moments", "rpt_read_moments", "rpt_read_noise", "rpt_noise_count", "rpt_render_to_noise",
+    "rpt_multi_set_moments", "rpt_multi_read_moments", "rpt_multi_noise_count", "rpt_multi_render_to_noise", "rpt_debug_noise_host",
 ]
 COMM_ID_BYTES = 128
 SHADOW_EXACT, SHADOW_SEGMENT = 0, 1          # rpt_set_shadow_mode
@@ -43,6 +45,29 @@ class DenoiseParams(C.Structure):
 class DenoiseReport(C.Structure):
     """rpt_denoise_report"""
     _fields_ = [("device_ms", C.c_double), ("guides_ms", C.c_double), ("guides_rebuilt", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class NoiseCounts(C.Structure):
+    """rpt_noise_counts"""
+    _fields_ = [("pixels", C.c_uint64), ("measured", C.c_uint64), ("above", C.c_uint64)]
+
+
+class NoiseTarget(C.Structure):
+    """rpt_noise_target"""
+    _fields_ = [("threshold", C.c_float), ("min_samples", C.c_uint32), ("max_samples", C.c_uint32), ("batch_samples", C.c_uint32), ("max_above", C.c_uint64)]
+
+
+class NoiseResult(C.Structure):
+    """rpt_noise_result"""
+    _fields_ = [("samples_rendered", C.c_uint32), ("converged", C.c_uint32), ("counts", NoiseCounts), ("ms", C.c_double)]
+
+
+def _counts_dict(k):
+    return {"pixels": k.pixels, "measured": k.measured, "above": k.above}
+
+
+def _noise_result_dict(res):
+    return {"samples_rendered": res.samples_rendered, "converged": res.converged, "counts": _counts_dict(res.counts), "ms": res.ms}
 
 
 def denoise_params(**changes):
@@ -142,6 +167,18 @@ def lib():
         L.rpt_read_guides.argtypes = [C.c_void_p] + [C.c_void_p] * 5
         L.rpt_multi_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_uint32, C.c_void_p, C.POINTER(DenoiseReport)]
         L.rpt_debug_denoise_host.argtypes = [C.c_uint32, C.c_uint32] + [C.c_void_p] * 6 + [C.POINTER(DenoiseParams), C.c_uint32, C.c_void_p]
+        if hasattr(L, "rpt_set_moments"):                # (RPT_HIP_LIB may name an older build for an A/B run: it has no moments)
+            L.rpt_set_moments.argtypes = [C.c_void_p, C.c_uint32]
+            L.rpt_moments.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+            L.rpt_read_moments.argtypes = [C.c_void_p, C.c_void_p]
+            L.rpt_read_noise.argtypes = [C.c_void_p, C.c_void_p]
+            L.rpt_noise_count.argtypes = [C.c_void_p, C.c_float, C.POINTER(NoiseCounts)]
+            L.rpt_render_to_noise.argtypes = [C.c_void_p, C.POINTER(NoiseTarget), C.POINTER(NoiseResult)]
+            L.rpt_multi_set_moments.argtypes = [C.c_void_p, C.c_uint32]
+            L.rpt_multi_read_moments.argtypes = [C.c_void_p, C.c_void_p]
+            L.rpt_multi_noise_count.argtypes = [C.c_void_p, C.c_float, C.POINTER(NoiseCounts)]
+            L.rpt_multi_render_to_noise.argtypes = [C.c_void_p, C.POINTER(NoiseTarget), C.POINTER(NoiseResult)]
+            L.rpt_debug_noise_host.argtypes = [C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.POINTER(NoiseCounts)]
         _lib = L
     return _lib
 
@@ -286,6 +323,42 @@ class Renderer:
              "position": np.zeros((h, w, 3), np.float32), "kind": np.zeros((h, w), np.uint32)}
         self._check(lib().rpt_read_guides(self._h, ptr(g["albedo"]), ptr(g["normal"]), ptr(g["depth"]), ptr(g["position"]), ptr(g["kind"])))
         return g
+
+    # -- per-pixel sample moments and the noise estimate (no reference equivalent; include/rpt/rpt.h "per-pixel sample moments")
+    def set_moments(self, on=True):
+        """rpt_set_moments: keep (sum Y, sum Y^2, n, max Y) of every pixel's samples beside the accumulator; turning it on zeroes the record.  The image does not
+        depend on it.  A renderer with one sample of a pixel in flight (set_samples_in_flight(1)) refuses to render while it is on."""
+        self._check(lib().rpt_set_moments(self._h, 1 if on else 0))
+
+    def moments_on(self):
+        on = C.c_uint32()
+        self._check(lib().rpt_moments(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def read_moments(self):
+        """rpt_read_moments: (H, W, 4) float32 — sum of luminance, sum of its square, samples since the record was zeroed, brightest sample; other ranks' pixels 0"""
+        out = np.zeros((self.config.height, self.config.width, 4), np.float32)
+        self._check(lib().rpt_read_moments(self._h, ptr(out)))
+        return out
+
+    def read_noise(self):
+        """rpt_read_noise: (H, W) float32, the standard error of every pixel's mean luminance relative to that mean (inf below two samples); other ranks' pixels 0"""
+        out = np.zeros((self.config.height, self.config.width), np.float32)
+        self._check(lib().rpt_read_noise(self._h, ptr(out)))
+        return out
+
+    def noise_count(self, threshold):
+        """rpt_noise_count: {"pixels": owned, "measured": with two samples or more, "above": measured with not (rel <= threshold)}"""
+        k = NoiseCounts()
+        self._check(lib().rpt_noise_count(self._h, threshold, C.byref(k)))
+        return _counts_dict(k)
+
+    def render_to_noise(self, threshold, max_above=0, batch_samples=32, min_samples=32, max_samples=1024):
+        """rpt_render_to_noise: batches of batch_samples until every pixel is measured and at most max_above are above threshold (counted from min_samples on),
+        or max_samples are rendered: {"samples_rendered", "converged", "counts", "ms"}.  Turns moments on and leaves them on."""
+        t, res = NoiseTarget(threshold, min_samples, max_samples, batch_samples, max_above), NoiseResult()
+        self._check(lib().rpt_render_to_noise(self._h, C.byref(t), C.byref(res)))
+        return _noise_result_dict(res)
 
     def read_rng(self):
         out = np.zeros(self.config.height * self.config.width, RNG_DTYPE)
@@ -547,6 +620,35 @@ class MultiRenderer:
         self._check(lib().rpt_multi_read_accum(self._h, ptr(out), C.byref(samples)))
         return out, samples.value
 
+    def set_moments(self, on=True):
+        """rpt_multi_set_moments: Renderer.set_moments on every rank"""
+        self._check(lib().rpt_multi_set_moments(self._h, 1 if on else 0))
+
+    def moments_on(self):
+        return self.rank_view(0).moments_on()
+
+    def read_moments(self):
+        """rpt_multi_read_moments: the whole (H, W, 4) image, the ranks' records merged on the host"""
+        out = np.zeros((self.config.height, self.config.width, 4), np.float32)
+        self._check(lib().rpt_multi_read_moments(self._h, ptr(out)))
+        return out
+
+    def read_noise(self):
+        """noise_host of read_moments(): the whole (H, W) image (there is no multi-GPU entry point for it: the arithmetic is the same header on the host)"""
+        return noise_host(self.read_moments())[0]
+
+    def noise_count(self, threshold):
+        """rpt_multi_noise_count: Renderer.noise_count summed over the ranks"""
+        k = NoiseCounts()
+        self._check(lib().rpt_multi_noise_count(self._h, threshold, C.byref(k)))
+        return _counts_dict(k)
+
+    def render_to_noise(self, threshold, max_above=0, batch_samples=32, min_samples=32, max_samples=1024):
+        """rpt_multi_render_to_noise: Renderer.render_to_noise over every GPU (each batch gathered as render() gathers it)"""
+        t, res = NoiseTarget(threshold, min_samples, max_samples, batch_samples, max_above), NoiseResult()
+        self._check(lib().rpt_multi_render_to_noise(self._h, C.byref(t), C.byref(res)))
+        return _noise_result_dict(res)
+
     def denoise(self, params=None, tonemap_op=0, with_report=False):
         """rpt_multi_denoise: waits, gathers if need be, and denoises the whole image on rank 0 (see Renderer.denoise)"""
         out = np.zeros((self.config.height, self.config.width, 3), np.float32)
@@ -633,6 +735,19 @@ def denoise_host(mean_rgb, albedo, normal, position, depth, kind, params=None, t
     if rc != 0:
         raise RptError(rc, lib().rpt_last_error(None).decode())
     return out
+
+
+def noise_host(moments, threshold=0.0):
+    """rpt_debug_noise_host: noise_rel of every record of `moments` (..., 4) and the counts of Renderer.noise_count, on the host from the same header
+    (no GPU needed): (rel with the leading shape of moments, {"pixels", "measured", "above"})"""
+    moments = np.ascontiguousarray(moments, np.float32)
+    assert moments.shape[-1] == 4
+    rel = np.zeros(moments.shape[:-1], np.float32)
+    k = NoiseCounts()
+    rc = lib().rpt_debug_noise_host(ptr(moments), rel.size, threshold, ptr(rel), C.byref(k))
+    if rc != 0:
+        raise RptError(rc, lib().rpt_last_error(None).decode())
+    return rel, _counts_dict(k)
 
 
 def light_table_build_gpu(vertices_xyzw, triangles, materials, device=0):
