@@ -149,6 +149,8 @@ struct DevState {
     uint32_t group_shift; /* log2 S, S = samples of one pixel in flight (slots per pixel) */
     uint32_t q_shift;     /* log2 Q <= group_shift, Q = samples of one pixel in ONE wave (a wave = 64 / Q pixels x Q samples) */
 };
+/* where pixel pxy = x | y << 16 (an entry of pixel_xy, or of a gather's map) sits in a row-major image `width` pixels wide */
+RPT_HD size_t rpt_pixel_index(uint32_t pxy, uint32_t width) { return (size_t)(pxy >> 16) * width + (pxy & 0xffffu); }
 
 /* flags word: bits 0-7 bounce, bit 8 last sampled lobe (1 = specular), bits 16-21 LDS dimension */
 #define FLAG_BOUNCE(f) ((f) & 0xffu)

@@ -145,7 +145,7 @@ __global__ __launch_bounds__(RPT_BLOCK) void k_dn_shade_guides(DevScene sc, uint
     const uint32_t i = blockIdx.x * RPT_BLOCK + threadIdx.x;
     if (i >= n) return;
     const uint32_t pxy = order[i];
-    const size_t at = (size_t)(pxy >> 16) * width + (pxy & 0xffffu);
+    const size_t at = rpt_pixel_index(pxy, width);
     const size_t j = 3u * (size_t)i;
     const F3 ro = f3(origins[j], origins[j + 1u], origins[j + 2u]), rd = f3(dirs[j], dirs[j + 1u], dirs[j + 2u]);
     const float t = hit_t[i];
@@ -215,7 +215,7 @@ __global__ __launch_bounds__(RPT_BLOCK) void k_dn_prepare(const float4 *sums, co
     const uint32_t i = blockIdx.x * RPT_BLOCK + threadIdx.x;
     if (i >= n) return;
     size_t at = i;
-    if (order) { const uint32_t pxy = order[i]; at = (size_t)(pxy >> 16) * width + (pxy & 0xffffu); }
+    if (order) at = rpt_pixel_index(order[i], width);
     const float4 a = sums[i];
     F3 c = f3(a.x / sample_count, a.y / sample_count, a.z / sample_count);
     if (albedo) c = dn_demodulate(c, xyz4(albedo[at]));

@@ -14,7 +14,6 @@
 #define RPT_K_SKY_GENERATE_H
 
 #include "k_shade.h"
-#include "k_tonemap.h"
 
 /* ---- kernels/src/skybox.rs ------------------------------------------------- */
 #define SKY_EARTH_RADIUS 6360e3f
@@ -244,23 +243,6 @@ __global__ __launch_bounds__(RPT_BLOCK) void k_check_drained(const float2 *hit, 
     const bool busy = i < n && __float_as_uint(hit[i].y) != HIT_IDLE;
     const unsigned long long m = rpt_ballot(busy);
     if (m != 0ull && __lane_id() == (uint32_t)__ffsll((long long)m) - 1u) atomicAdd(&stats->undrained, (unsigned long long)__popcll(m));
-}
-
-/* ---- post-accumulation step --------------------------------------------------------
- * mean = sum / sample_count (src/trace.rs:199-204) followed by one of the display tonemappers of
- * src/resources/render.wgsl:36-117 (operator selection :131-153).  Pure f32 rational curves, written in
- * the shader's operation order; input = the tile-major accumulator block, output = row-major RGB. */
-/* (the curves themselves: k_tonemap.h, shared with the denoiser and its host build) */
-__global__ __launch_bounds__(RPT_BLOCK) void k_resolve(const float4 *accum, const uint32_t *pixel_xy, uint32_t n_pixels, uint32_t width,
-                                                       float sample_count, uint32_t op, float *out_rgb) {
-    uint32_t i = blockIdx.x * RPT_BLOCK + threadIdx.x;
-    if (i >= n_pixels) return;
-    float4 a = accum[i];
-    F3 mean = f3(a.x / sample_count, a.y / sample_count, a.z / sample_count);
-    F3 c = tonemap(op, mean);
-    uint32_t pxy = pixel_xy[i];
-    size_t at = ((size_t)(pxy >> 16) * width + (pxy & 0xffffu)) * 3u;
-    out_rgb[at] = c.x; out_rgb[at + 1] = c.y; out_rgb[at + 2] = c.z;
 }
 
 #endif /* RPT_K_SKY_GENERATE_H */

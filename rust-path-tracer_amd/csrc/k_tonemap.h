@@ -1,6 +1,6 @@
 /*
  * k_tonemap.h — the display tonemappers of src/resources/render.wgsl:36-117 (operator selection :131-153): pure f32 rational
- * curves, written in the shader's operation order.  RPT_HD: rpt_resolve (k_sky_generate.h k_resolve) and the last pass of the
+ * curves, written in the shader's operation order.  RPT_HD: rpt_resolve (k_image_order.h PixelResolve) and the last pass of the
  * denoiser (k_denoise.h) apply them on the device, the denoiser's host build (rpt_debug_denoise_host) on the host, same bits.
  */
 #ifndef RPT_K_TONEMAP_H

@@ -23,6 +23,7 @@
 #include <set>
 
 #include "rpt_ctx.h"
+#include "k_image_order.h"
 
 namespace {
 
@@ -94,16 +95,6 @@ RcclApi &rccl() {
 
 static_assert(sizeof(ncclUniqueId) == RPT_COMM_ID_BYTES, "rpt.h: RPT_COMM_ID_BYTES must equal sizeof(ncclUniqueId)");
 
-/* scatter of tile-major accumulator blocks into a row-major image; map[i] = y << 16 | x of element i, 0xffffffff = padding */
-__global__ __launch_bounds__(RPT_BLOCK) void k_untile(const float4 *blocks, const uint32_t *map, uint32_t n_total, uint32_t width,
-                                                      float4 *image) {
-    uint32_t i = blockIdx.x * RPT_BLOCK + threadIdx.x;
-    if (i >= n_total) return;
-    uint32_t pxy = map[i];
-    if (pxy == 0xffffffffu) return;
-    image[(size_t)(pxy >> 16) * width + (pxy & 0xffffu)] = blocks[i];
-}
-
 }  // namespace
 
 struct rpt_comm {
@@ -173,7 +164,7 @@ int enqueue_readback(rpt_ctx *c) {
     int rc = ensure_image(c);
     if (rc) return rc;
     if (c->n_pixels)
-        k_untile<<<(c->n_pixels + RPT_BLOCK - 1) / RPT_BLOCK, RPT_BLOCK, 0, c->stream>>>(c->accum.p, c->pixel_xy.p, c->n_pixels, c->cfg.c.width, c->image.p);
+        k_scatter_pixels<<<rpt_blocks(c->n_pixels), RPT_BLOCK, 0, c->stream>>>(c->pixel_xy.p, c->n_pixels, c->cfg.c.width, PixelCopy<float4>{c->accum.p, c->image.p});
     HIP_TRY(c, hipMemcpyAsync(c->host_image.p, c->image.p, c->host_image.n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     return RPT_OK;
 }
@@ -281,7 +272,7 @@ int gather_finish(rpt_ctx *c) {
     if (cm->rank == 0) {
         if (cm->sizes[0]) HIP_TRY(c, hipMemcpyAsync(cm->gathered.p, cm->send.p, cm->sizes[0] * sizeof(float4), hipMemcpyDeviceToDevice, cm->stream));
         const uint32_t n = (uint32_t)((size_t)cm->world * cm->stride);
-        if (n) k_untile<<<(n + RPT_BLOCK - 1) / RPT_BLOCK, RPT_BLOCK, 0, cm->stream>>>(cm->gathered.p, cm->map.p, n, c->cfg.c.width, cm->full_image.p);
+        if (n) k_scatter_pixels<<<rpt_blocks(n), RPT_BLOCK, 0, cm->stream>>>(cm->map.p, n, c->cfg.c.width, PixelCopy<float4>{cm->gathered.p, cm->full_image.p});
     }
     HIP_TRY(c, hipEventRecord(cm->sent, cm->stream));
     cm->started = true;
@@ -347,8 +338,8 @@ int rpt_untile(rpt_ctx *c, const void *dev_blocks, uint64_t block_stride_pixels,
         c->untile_key = key;
     }
     if (c->untile_n)
-        k_untile<<<(c->untile_n + RPT_BLOCK - 1) / RPT_BLOCK, RPT_BLOCK, 0, c->stream>>>(reinterpret_cast<const float4 *>(dev_blocks), c->untile_map.p,
-                                                                                      c->untile_n, c->cfg.c.width, reinterpret_cast<float4 *>(dev_out_image));
+        k_scatter_pixels<<<rpt_blocks(c->untile_n), RPT_BLOCK, 0, c->stream>>>(c->untile_map.p, c->untile_n, c->cfg.c.width,
+                                                                               PixelCopy<float4>{reinterpret_cast<const float4 *>(dev_blocks), reinterpret_cast<float4 *>(dev_out_image)});
     HIP_TRY(c, hipGetLastError());
     return RPT_OK;
 }
@@ -529,7 +520,6 @@ int multi_gather(rpt_multi *m) {
     for (rpt_ctx *c : m->ctx)
         if ((rc = gather_stage(c))) return multi_fail(m, c, rc);
     if (!m->shared_device) {
-        rpt_ctx *c0 = m->ctx[0];
         if (rccl().GroupStart() != ncclSuccess) { m->error = "ncclGroupStart failed"; return RPT_EHIP; }
         rc = RPT_OK;
         rpt_ctx *failed = nullptr;
@@ -538,7 +528,6 @@ int multi_gather(rpt_multi *m) {
         ncclResult_t ge = rccl().GroupEnd();
         if (rc) return multi_fail(m, failed, rc);
         if (ge != ncclSuccess) { m->error = std::string("ncclGroupEnd: ") + rccl().GetErrorString(ge); return RPT_EHIP; }
-        (void)c0;
     } else {
         /* ranks on one device: the root's comm stream copies every peer's snapshot once that peer has staged it */
         rpt_ctx *root = m->ctx[0];
@@ -732,7 +721,7 @@ int rpt_multi_read_moments(rpt_multi *m, float *out_xyzw) {
         if ((rc = rpt_read_moments(c, one.data()))) return multi_fail(m, c, rc);
         const uint32_t W = c->cfg.c.width;
         for (uint32_t pxy : c->pixel_xy_host) {
-            const size_t at = ((size_t)(pxy >> 16) * W + (pxy & 0xffffu)) * 4;
+            const size_t at = rpt_pixel_index(pxy, W) * 4;
             memcpy(out_xyzw + at, one.data() + at, 4 * sizeof(float));
         }
     }

@@ -2,7 +2,8 @@
  * rpt_ctx.h — the context object behind the C ABI of include/rpt/rpt.h, shared by the translation units of
  * librpt_hip.so (rpt_hip.hip: life cycle, state and wavefront scheduling; rpt_scene.hip: scene preparation; rpt_traverse.hip: the traversal stages;
  * rpt_comm.hip: multi-GPU gather over RCCL, read-back; rpt_denoise.hip: guide buffers and the denoise filter; rpt_moments.hip: sample moments, noise estimate,
- * render to a noise target; rpt_debug.hip: test hooks).
+ * render to a noise target; rpt_debug.hip: test hooks).  k_image_order.h: the one kernel and the one read-out routine that turn the tile-major pixel order
+ * into a row-major image, for every unit that hands one to the caller.
  */
 #ifndef RPT_CTX_H
 #define RPT_CTX_H
@@ -246,7 +247,7 @@ struct rpt_ctx {
 
     /* read-back and multi-GPU gather (rpt_comm.hip) */
     rpt_comm *comm = nullptr;
-    DevBuf<float4> image;                 /* row-major W x H accumulator image (device), built by k_untile */
+    DevBuf<float4> image;                 /* row-major W x H accumulator image (device), built by k_scatter_pixels (k_image_order.h) */
     PinnedBuf<float> host_image;          /* pinned twin of it: rpt_read_accum is one DMA */
     DevBuf<uint32_t> untile_map;          /* rpt_untile: destination map, rebuilt only when (W, H, world, stride) changes */
     uint64_t untile_key = 0;

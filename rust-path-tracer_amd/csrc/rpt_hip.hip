@@ -20,6 +20,7 @@
 #include "k_shade.h"             /* (the walk kernels of k_traverse.h are compiled in rpt_traverse.hip) */
 #include "k_complete.h"
 #include "k_sky_generate.h"
+#include "k_image_order.h"
 
 /* (read afresh by every rpt_create / scene-preparation call: a test process changes its environment between contexts) */
 rpt_knobs rpt_read_knobs() {
@@ -260,8 +261,7 @@ __global__ __launch_bounds__(RPT_BLOCK) void k_reset_gather(const uint32_t *pixe
                                                             uint2 *rng, float4 *accum) {
     const uint32_t s = blockIdx.x * RPT_BLOCK + threadIdx.x;
     if (s >= n_pixels) return;
-    const uint32_t pxy = pixel_xy[s];
-    const size_t i = (size_t)(pxy >> 16) * width + (pxy & 0xffffu);
+    const size_t i = rpt_pixel_index(pixel_xy[s], width);
     rng[s] = seed[i];
     accum[s] = accum_init ? accum_init[i] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
@@ -666,17 +666,8 @@ int rpt_render_async(rpt_ctx *c, uint32_t n_samples) { return render_impl(c, n_s
 int rpt_read_rng(rpt_ctx *c, rpt_rng_state *out) {
     if (!c || !out) return RPT_EINVAL;
     if (!c->has_state) { c->error = "nothing to read: no config"; return RPT_EINVAL; }
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const uint32_t W = c->cfg.c.width, H = c->cfg.c.height;
-    std::vector<uint2> rng(c->n_pixels);
-    if (c->n_pixels) HIP_TRY(c, hipMemcpy(rng.data(), c->rng.p, c->n_pixels * sizeof(uint2), hipMemcpyDeviceToHost));
-    memset(out, 0, (size_t)W * H * sizeof(rpt_rng_state));
-    for (size_t s = 0; s < c->n_pixels; ++s) {
-        uint32_t pxy = c->pixel_xy_host[s];
-        out[(size_t)(pxy >> 16) * W + (pxy & 0xffffu)] = rpt_rng_state{rng[s].x, rng[s].y};
-    }
-    return RPT_OK;
+    static_assert(sizeof(rpt_rng_state) == sizeof(uint2), "rpt_read_rng copies the device's uint2 image into the caller's rpt_rng_state");
+    return rpt_read_out(c, PixelCopy<uint2>{c->rng.p, nullptr}, out);
 }
 
 int rpt_local_pixels(rpt_ctx *c, uint64_t *n) {
@@ -733,19 +724,7 @@ int rpt_resolve(rpt_ctx *c, uint32_t tonemap_op, float *out_rgb) {
     if (!c || !out_rgb) return RPT_EINVAL;
     if (!c->has_state) { c->error = "nothing to resolve: no config"; return RPT_EINVAL; }
     if (tonemap_op > 6u) { c->error = "tonemap operator must be 0..6"; return RPT_EINVAL; }
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n_out = (size_t)c->cfg.c.width * c->cfg.c.height * 3;
-    DevBuf<float> dev;
-    HIP_TRY(c, dev.alloc(n_out));
-    HIP_TRY(c, hipMemsetAsync(dev.p, 0, n_out * sizeof(float), c->stream));
-    if (c->n_pixels) {
-        k_resolve<<<rpt_blocks(c->n_pixels), RPT_BLOCK, 0, c->stream>>>(c->accum.p, c->pixel_xy.p, c->n_pixels, c->cfg.c.width,
-                                                                                      (float)c->samples, tonemap_op, dev.p);
-        HIP_TRY(c, hipGetLastError());
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(out_rgb, dev.p, n_out * sizeof(float), hipMemcpyDeviceToHost));
-    return RPT_OK;
+    return rpt_read_out(c, PixelResolve{c->accum.p, (float)c->samples, tonemap_op, nullptr}, out_rgb);
 }
 
 int rpt_get_stats(rpt_ctx *c, rpt_stats *out) {

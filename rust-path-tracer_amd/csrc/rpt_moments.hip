@@ -1,32 +1,17 @@
 /*
  * rpt_moments.hip — per-pixel sample moments behind the C ABI (include/rpt/rpt.h rpt_set_moments, rpt_moments, rpt_read_moments, rpt_read_noise,
  * rpt_noise_count, rpt_render_to_noise) and the host build of the noise estimate (rpt_debug.h rpt_debug_noise_host).  The record itself is kept by the
- * completion kernel of a context with moments on (k_complete.h k_complete_moments, launched by rpt_hip.hip); here are its life cycle, the read-outs —
- * un-tiled as rpt_read_accum un-tiles the accumulator — the count kernel and the render loop that stops at a noise target.  Arithmetic: k_moments.h.
+ * completion kernel of a context with moments on (k_complete.h k_complete_moments, launched by rpt_hip.hip); here are its life cycle, the read-outs
+ * (k_image_order.h rpt_read_out), the count kernel and the render loop that stops at a noise target.  Arithmetic: k_moments.h.
  */
 #include <chrono>
 #include <vector>
 
 #include "rpt_ctx.h"
+#include "k_image_order.h"
 #include "k_moments.h"
 
 namespace {
-
-/* the records of this rank's pixels (tile-major) into a row-major image; other ranks' pixels keep the zeros the image was filled with */
-__global__ __launch_bounds__(RPT_BLOCK) void k_moments_untile(const float4 *moments, const uint32_t *pixel_xy, uint32_t n_pixels, uint32_t width, float4 *image) {
-    const uint32_t s = blockIdx.x * RPT_BLOCK + threadIdx.x;
-    if (s >= n_pixels) return;
-    const uint32_t pxy = pixel_xy[s];
-    image[(size_t)(pxy >> 16) * width + (pxy & 0xffffu)] = moments[s];
-}
-
-/* the same for noise_rel of every record */
-__global__ __launch_bounds__(RPT_BLOCK) void k_noise_untile(const float4 *moments, const uint32_t *pixel_xy, uint32_t n_pixels, uint32_t width, float *image) {
-    const uint32_t s = blockIdx.x * RPT_BLOCK + threadIdx.x;
-    if (s >= n_pixels) return;
-    const uint32_t pxy = pixel_xy[s];
-    image[(size_t)(pxy >> 16) * width + (pxy & 0xffffu)] = noise_rel(moments[s]);
-}
 
 /* counts[0] += pixels, [1] += measured, [2] += measured with !(rel <= threshold): one ballot per wave and count, one integer atomic per wave and
  * non-zero count — integers, so the result does not depend on the order the waves arrive in */
@@ -145,35 +130,13 @@ int rpt_moments(rpt_ctx *c, uint32_t *on_out) {
 int rpt_read_moments(rpt_ctx *c, float *out_xyzw) {
     if (!c || !out_xyzw) return RPT_EINVAL;
     RPT_TRY(need_moments(c, "rpt_read_moments"));
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n = (size_t)c->cfg.c.width * c->cfg.c.height;
-    DevBuf<float4> image;
-    HIP_TRY(c, image.alloc(n));
-    HIP_TRY(c, hipMemsetAsync(image.p, 0, n * sizeof(float4), c->stream));
-    if (c->n_pixels) {
-        k_moments_untile<<<rpt_blocks(c->n_pixels), RPT_BLOCK, 0, c->stream>>>(c->moments.p, c->pixel_xy.p, c->n_pixels, c->cfg.c.width, image.p);
-        HIP_TRY(c, hipGetLastError());
-    }
-    RPT_TRY(rpt_wait(c));
-    HIP_TRY(c, hipMemcpy(out_xyzw, image.p, n * sizeof(float4), hipMemcpyDeviceToHost));
-    return RPT_OK;
+    return rpt_read_out(c, PixelCopy<float4>{c->moments.p, nullptr}, out_xyzw);
 }
 
 int rpt_read_noise(rpt_ctx *c, float *rel_out) {
     if (!c || !rel_out) return RPT_EINVAL;
     RPT_TRY(need_moments(c, "rpt_read_noise"));
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n = (size_t)c->cfg.c.width * c->cfg.c.height;
-    DevBuf<float> image;
-    HIP_TRY(c, image.alloc(n));
-    HIP_TRY(c, hipMemsetAsync(image.p, 0, n * sizeof(float), c->stream));
-    if (c->n_pixels) {
-        k_noise_untile<<<rpt_blocks(c->n_pixels), RPT_BLOCK, 0, c->stream>>>(c->moments.p, c->pixel_xy.p, c->n_pixels, c->cfg.c.width, image.p);
-        HIP_TRY(c, hipGetLastError());
-    }
-    RPT_TRY(rpt_wait(c));
-    HIP_TRY(c, hipMemcpy(rel_out, image.p, n * sizeof(float), hipMemcpyDeviceToHost));
-    return RPT_OK;
+    return rpt_read_out(c, PixelNoise{c->moments.p, nullptr}, rel_out);
 }
 
 int rpt_noise_count(rpt_ctx *c, float threshold, rpt_noise_counts *out) {

@@ -230,6 +230,44 @@ def test_partition_and_multi_gpu(hipmod, oracle, rpt, world, tiles):
         m.close()
 
 
+def test_partition_read_outs(hipmod, oracle, rpt, world):
+    """200 x 130, rank 1 of 3, 8 samples — the rank owns two whole 64 x 64 tiles, an 8 x 64 one of the right edge and a 64 x 2 one of the bottom edge: every
+    row-major read-out of the partitioned context holds the oracle's values on the rank's own pixels and zeros elsewhere, and after an asynchronous batch
+    resolve and read_rng return without an explicit wait what they return after one"""
+    w, h = 200, 130
+    b = bank(oracle, rpt, world, "DarkCornell", w, h)
+    check_bank_against_the_oracle(oracle, world, "DarkCornell", b, 8)
+    xy = hipmod.tile_order(w, h, 1, 3)
+    own = np.zeros((h, w), bool)
+    own[xy >> 16, xy & 0xFFFF] = True
+    assert own.sum() == 2 * 64 * 64 + 8 * 64 + 64 * 2 and own[:64, 64:128].all() and own[64:128, :64].all() and own[64:128, 192:].all() and own[128:, 128:192].all()
+    want_acc, want_rng = b.accum(8), np.asarray(b.rng(8)).reshape(h, w)
+    want_rgb = {op: oracle.resolve(want_acc, 8.0, op) for op in (0, 4)}
+
+    def read_rng(r):
+        rng = r.read_rng().reshape(h, w)
+        assert np.array_equal(rng[own], want_rng[own]) and not rng[~own].view(np.uint32).any()
+        return rng
+
+    def resolve(r, op=0):
+        rgb = r.resolve(op)
+        assert same_words(rgb[own], want_rgb[op][own]) and not rgb[~own].view(np.uint32).any(), op
+        return rgb
+
+    with fresh(hipmod, world, "DarkCornell", b, moments=False, partition=(1, 3)) as r:
+        r.render_async(8)
+        r.wait()
+        acc, n = r.read_accum()
+        assert n == 8 and same_words(acc[own], want_acc[own]) and not acc[~own].view(np.uint32).any()
+        waited = {read_rng: read_rng(r), resolve: resolve(r)}
+        resolve(r, 4)                                     # ACES (Hill): a curved operator
+    for first, second in ((resolve, read_rng), (read_rng, resolve)):
+        with fresh(hipmod, world, "DarkCornell", b, moments=False, partition=(1, 3)) as r:
+            r.render_async(8)                             # no wait: the read-out has to
+            for read in (first, second):
+                assert read(r).tobytes() == waited[read].tobytes()
+
+
 @pytest.mark.parametrize("scene", ["DarkCornell", "VeachMIS"])
 def test_noise(hipmod, oracle, rpt, world, scene):
     b = bank(oracle, rpt, world, scene)
