@@ -2,7 +2,8 @@
 
 Layouts follow the reference's `shared_structs` crate
 (reference: shared_structs/src/lib.rs:12-191); numpy dtypes of the same layouts
-are provided so buffers can be inspected / generated from Python.
+are provided so buffers can be inspected / generated from Python.  bind() is the
+one place where a function of either library gets its prototype.
 """
 import ctypes as C
 import os
@@ -84,3 +85,19 @@ def ptr(arr):
         return None
     assert arr.flags["C_CONTIGUOUS"]
     return C.c_void_p(arr.ctypes.data)
+
+
+def bind(L, prototypes, allow_missing):
+    """restype and argtypes of every entry of `prototypes` = {name: (restype, [argtypes])} on the loaded library L, which is returned.  A name L lacks is
+    skipped when allow_missing (calling it later raises AttributeError as for any unknown symbol); otherwise all such names are refused in one error."""
+    missing = []
+    for name, (restype, argtypes) in prototypes.items():
+        try:
+            fn = getattr(L, name)
+        except AttributeError:
+            missing.append(name)
+            continue
+        fn.restype, fn.argtypes = restype, argtypes
+    if missing and not allow_missing:
+        raise RuntimeError(f"{getattr(L, '_name', 'the library')} lacks {len(missing)} declared function(s): {', '.join(sorted(missing))}")
+    return L

@@ -15,20 +15,6 @@ from ._ffi import RNG_DTYPE, Stats, TracingConfig, ptr
 
 _lib = None
 
-EXPORTS = [
-    "rpt_abi_version", "rpt_create", "rpt_set_partition", "rpt_set_samples_in_flight", "rpt_upload_scene", "rpt_set_config", "rpt_reset",
-    "rpt_render", "rpt_render_async", "rpt_wait", "rpt_stream", "rpt_read_accum", "rpt_resolve", "rpt_read_rng", "rpt_local_pixels", "rpt_local_block_device_ptr",
-    "rpt_rank_pixels", "rpt_tile_order", "rpt_untile", "rpt_get_stats", "rpt_destroy", "rpt_last_error",
-    "rpt_comm_init_local", "rpt_debug_math", "rpt_debug_math_host", "rpt_debug_math_sweep", "rpt_debug_trace_rays", "rpt_debug_bsdf", "rpt_bvh_build_gpu", "rpt_light_table_build_gpu",
-    "rpt_map_accum", "rpt_comm_unique_id", "rpt_comm_init", "rpt_comm_world", "rpt_gather_async", "rpt_gather_wait", "rpt_read_gathered",
-    "rpt_gathered_device_ptr", "rpt_multi_create", "rpt_multi_size", "rpt_multi_ctx", "rpt_multi_upload_scene", "rpt_multi_set_config",
-    "rpt_multi_reset", "rpt_multi_render", "rpt_multi_wait", "rpt_multi_read_accum", "rpt_multi_get_stats", "rpt_multi_destroy",
-    "rpt_multi_last_error", "rpt_comm_library", "rpt_debug_trace_rays_production", "rpt_build_fingerprint", "rpt_debug_comm_selftest", "rpt_device_info", "rpt_shadow_order", "rpt_debug_shadow_order_host", "rpt_last_bounce_order", "rpt_debug_last_order_host", "rpt_debug_short_batch",
-    "rpt_set_shadow_mode", "rpt_shadow_mode", "rpt_multi_set_shadow_mode",
-    "rpt_denoise_params_default", "rpt_denoise", "rpt_read_guides", "rpt_multi_denoise", "rpt_debug_denoise_host",
-    "rpt_set_moments", "rpt_moments", "rpt_read_moments", "rpt_read_noise", "rpt_noise_count", "rpt_render_to_noise",
-    "rpt_multi_set_moments", "rpt_multi_read_moments", "rpt_multi_noise_count", "rpt_multi_render_to_noise", "rpt_debug_noise_host",
-]
 COMM_ID_BYTES = 128
 SHADOW_EXACT, SHADOW_SEGMENT = 0, 1          # rpt_set_shadow_mode
 MULTI_ALLOW_SHARED_DEVICE = 1
@@ -86,100 +72,104 @@ def lib_path():
     return os.environ.get("RPT_HIP_LIB") or os.path.join(_ffi.LIB_DIR, "librpt_hip.so")
 
 
+_SCENE = [C.c_void_p, C.c_size_t] * 5 + [C.c_void_p, C.c_uint32, C.c_uint32] * 2      # rpt_upload_scene after the handle: five buffers with counts, atlas, skybox
+_OUT_U32, _OUT_U64, _OUT_SIZE, _OUT_F64, _OUT_PTR = (C.POINTER(t) for t in (C.c_uint32, C.c_uint64, C.c_size_t, C.c_double, C.c_void_p))
+
+# every function of include/rpt/rpt.h and rpt_debug.h, in their order: name -> (return type, [parameter types]); tests/test_contracts.py holds it against the headers.
+# (rpt_ctx * and rpt_multi * are c_void_p; so is every buffer a numpy array is handed to through ptr())
+PROTOTYPES = {
+    "rpt_create": (C.c_int, [C.c_int, _OUT_PTR]),
+    "rpt_set_partition": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "rpt_set_samples_in_flight": (C.c_int, [C.c_void_p, C.c_int]),
+    "rpt_upload_scene": (C.c_int, [C.c_void_p] + _SCENE),
+    "rpt_set_config": (C.c_int, [C.c_void_p, C.POINTER(TracingConfig)]),
+    "rpt_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "rpt_render": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rpt_render_async": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rpt_wait": (C.c_int, [C.c_void_p]),
+    "rpt_stream": (C.c_int, [C.c_void_p, _OUT_PTR]),
+    "rpt_read_accum": (C.c_int, [C.c_void_p, C.c_void_p, _OUT_U32]),
+    "rpt_map_accum": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_float)), _OUT_U32]),
+    "rpt_resolve": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "rpt_read_rng": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rpt_tile_order": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, _OUT_SIZE]),
+    "rpt_local_pixels": (C.c_int, [C.c_void_p, _OUT_U64]),
+    "rpt_local_block_device_ptr": (C.c_int, [C.c_void_p, _OUT_PTR]),
+    "rpt_rank_pixels": (C.c_int, [C.c_void_p, C.c_uint32, _OUT_U64]),
+    "rpt_untile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "rpt_comm_unique_id": (C.c_int, [C.c_void_p]),
+    "rpt_comm_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
+    "rpt_comm_init_local": (C.c_int, [C.c_void_p]),
+    "rpt_comm_world": (C.c_int, [C.c_void_p, _OUT_U32, _OUT_U32]),
+    "rpt_comm_library": (C.c_char_p, []),
+    "rpt_gather_async": (C.c_int, [C.c_void_p]),
+    "rpt_gather_wait": (C.c_int, [C.c_void_p]),
+    "rpt_read_gathered": (C.c_int, [C.c_void_p, C.c_void_p, _OUT_U32]),
+    "rpt_gathered_device_ptr": (C.c_int, [C.c_void_p, _OUT_PTR]),
+    "rpt_multi_create": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_uint32, _OUT_PTR]),
+    "rpt_multi_size": (C.c_int, [C.c_void_p]),
+    "rpt_multi_ctx": (C.c_void_p, [C.c_void_p, C.c_int]),
+    "rpt_multi_upload_scene": (C.c_int, [C.c_void_p] + _SCENE),
+    "rpt_multi_set_config": (C.c_int, [C.c_void_p, C.POINTER(TracingConfig)]),
+    "rpt_multi_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "rpt_multi_set_shadow_mode": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rpt_multi_render": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rpt_multi_wait": (C.c_int, [C.c_void_p]),
+    "rpt_multi_read_accum": (C.c_int, [C.c_void_p, C.c_void_p, _OUT_U32]),
+    "rpt_multi_get_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
+    "rpt_multi_destroy": (None, [C.c_void_p]),
+    "rpt_multi_last_error": (C.c_char_p, [C.c_void_p]),
+    "rpt_get_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
+    "rpt_destroy": (None, [C.c_void_p]),
+    "rpt_last_error": (C.c_char_p, [C.c_void_p]),
+    "rpt_abi_version": (C.c_int, []),
+    "rpt_build_fingerprint": (C.c_char_p, []),
+    "rpt_device_info": (C.c_int, [C.c_int, _OUT_U32, _OUT_U32]),
+    "rpt_shadow_order": (C.c_int, [C.c_void_p, _OUT_U32, _OUT_F64, _OUT_F64, _OUT_U32, _OUT_F64]),
+    "rpt_set_shadow_mode": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rpt_shadow_mode": (C.c_int, [C.c_void_p, _OUT_U32]),
+    "rpt_last_bounce_order": (C.c_int, [C.c_void_p, _OUT_U32, _OUT_U32, _OUT_F64, _OUT_U32, _OUT_F64]),
+    "rpt_denoise_params_default": (None, [C.POINTER(DenoiseParams)]),
+    "rpt_denoise": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(DenoiseParams), C.c_uint32, C.c_void_p, C.POINTER(DenoiseReport)]),
+    "rpt_read_guides": (C.c_int, [C.c_void_p] + [C.c_void_p] * 5),
+    "rpt_multi_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.c_uint32, C.c_void_p, C.POINTER(DenoiseReport)]),
+    "rpt_set_moments": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rpt_moments": (C.c_int, [C.c_void_p, _OUT_U32]),
+    "rpt_read_moments": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rpt_read_noise": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rpt_noise_count": (C.c_int, [C.c_void_p, C.c_float, C.POINTER(NoiseCounts)]),
+    "rpt_render_to_noise": (C.c_int, [C.c_void_p, C.POINTER(NoiseTarget), C.POINTER(NoiseResult)]),
+    "rpt_multi_set_moments": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rpt_multi_read_moments": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rpt_multi_noise_count": (C.c_int, [C.c_void_p, C.c_float, C.POINTER(NoiseCounts)]),
+    "rpt_multi_render_to_noise": (C.c_int, [C.c_void_p, C.POINTER(NoiseTarget), C.POINTER(NoiseResult)]),
+    "rpt_bvh_build_gpu": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, _OUT_SIZE, _OUT_F64]),
+    "rpt_light_table_build_gpu": (C.c_int, [C.c_int] + [C.c_void_p, C.c_size_t] * 4 + [_OUT_SIZE, _OUT_U32, _OUT_F64]),
+    "rpt_debug_math": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rpt_debug_math_host": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rpt_debug_shadow_order_host": (C.c_int, [C.c_void_p, C.c_size_t] * 5 + [_OUT_U32, _OUT_F64, _OUT_F64, _OUT_U32, C.c_void_p]),
+    "rpt_debug_last_order_host": (C.c_int, [C.c_void_p, C.c_size_t] * 4 + [_OUT_U32, _OUT_F64, _OUT_U32, C.c_void_p]),
+    "rpt_debug_math_sweep": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_float, _OUT_U64, _OUT_U32]),
+    "rpt_debug_trace_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t] + [C.c_void_p] * 6),
+    "rpt_debug_trace_rays_production": (C.c_int, [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5),
+    "rpt_debug_bsdf": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "rpt_debug_comm_selftest": (C.c_int, [C.c_void_p, C.c_uint32, _OUT_U64]),
+    "rpt_debug_denoise_host": (C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 6 + [C.POINTER(DenoiseParams), C.c_uint32, C.c_void_p]),
+    "rpt_debug_noise_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.POINTER(NoiseCounts)]),
+    "rpt_debug_short_batch": (C.c_int, [C.c_void_p, C.c_int]),
+}
+EXPORTS = sorted(PROTOTYPES)
+
+
 def lib():
+    """librpt_hip.so with the prototypes of PROTOTYPES.  The in-tree library must have every one of them; the build RPT_HIP_LIB names may be an older one
+    (an A/B run against a library without shadow modes or moments): what it lacks is left out, and calling it raises AttributeError."""
     global _lib
     if _lib is None:
         path = lib_path()
         if not os.path.exists(path):
             raise RuntimeError(f"{path} is missing: run `make hip` (or __graft_entry__.build()); there is no CPU fallback")
-        L = C.CDLL(path)
-        L.rpt_last_error.restype = C.c_char_p
-        L.rpt_last_error.argtypes = [C.c_void_p]
-        L.rpt_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-        L.rpt_destroy.argtypes = [C.c_void_p]
-        L.rpt_destroy.restype = None
-        L.rpt_set_partition.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
-        L.rpt_set_samples_in_flight.argtypes = [C.c_void_p, C.c_int]
-        L.rpt_upload_scene.argtypes = [C.c_void_p] + [C.c_void_p, C.c_size_t] * 5 + [C.c_void_p, C.c_uint32, C.c_uint32] * 2
-        L.rpt_set_config.argtypes = [C.c_void_p, C.POINTER(TracingConfig)]
-        L.rpt_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
-        L.rpt_render.argtypes = [C.c_void_p, C.c_uint32]
-        L.rpt_render_async.argtypes = [C.c_void_p, C.c_uint32]
-        L.rpt_wait.argtypes = [C.c_void_p]
-        L.rpt_stream.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-        L.rpt_read_accum.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
-        L.rpt_read_rng.argtypes = [C.c_void_p, C.c_void_p]
-        L.rpt_resolve.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
-        L.rpt_local_pixels.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-        L.rpt_local_block_device_ptr.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-        L.rpt_rank_pixels.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
-        L.rpt_untile.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
-        L.rpt_tile_order.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
-                                     C.POINTER(C.c_size_t)]
-        L.rpt_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
-        L.rpt_debug_math.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-        L.rpt_debug_math_host.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-        L.rpt_debug_math_sweep.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_float, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
-        L.rpt_debug_trace_rays.argtypes = [C.c_void_p, C.c_int, C.c_size_t] + [C.c_void_p] * 6
-        L.rpt_debug_trace_rays_production.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5
-        L.rpt_bvh_build_gpu.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t,
-                                        C.POINTER(C.c_size_t), C.POINTER(C.c_double)]
-        L.rpt_debug_bsdf.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]
-        L.rpt_map_accum.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32)]
-        L.rpt_comm_unique_id.argtypes = [C.c_void_p]
-        L.rpt_build_fingerprint.restype = C.c_char_p
-        L.rpt_build_fingerprint.argtypes = []
-        L.rpt_comm_library.restype = C.c_char_p
-        L.rpt_comm_library.argtypes = []
-        L.rpt_comm_init.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
-        L.rpt_comm_init_local.argtypes = [C.c_void_p]
-        L.rpt_device_info.argtypes = [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-        L.rpt_shadow_order.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
-        if hasattr(L, "rpt_set_shadow_mode"):            # (RPT_HIP_LIB may name an older build for an A/B run: it renders in the exact mode only)
-            L.rpt_set_shadow_mode.argtypes = [C.c_void_p, C.c_uint32]
-            L.rpt_shadow_mode.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
-            L.rpt_multi_set_shadow_mode.argtypes = [C.c_void_p, C.c_uint32]
-        L.rpt_last_bounce_order.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
-        L.rpt_debug_comm_selftest.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
-        L.rpt_comm_world.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-        L.rpt_gather_async.argtypes = [C.c_void_p]
-        L.rpt_gather_wait.argtypes = [C.c_void_p]
-        L.rpt_read_gathered.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
-        L.rpt_gathered_device_ptr.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-        L.rpt_multi_create.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_uint32, C.POINTER(C.c_void_p)]
-        L.rpt_multi_size.argtypes = [C.c_void_p]
-        L.rpt_multi_ctx.argtypes = [C.c_void_p, C.c_int]
-        L.rpt_multi_ctx.restype = C.c_void_p
-        L.rpt_multi_upload_scene.argtypes = [C.c_void_p] + [C.c_void_p, C.c_size_t] * 5 + [C.c_void_p, C.c_uint32, C.c_uint32] * 2
-        L.rpt_multi_set_config.argtypes = [C.c_void_p, C.POINTER(TracingConfig)]
-        L.rpt_multi_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
-        L.rpt_multi_render.argtypes = [C.c_void_p, C.c_uint32]
-        L.rpt_multi_wait.argtypes = [C.c_void_p]
-        L.rpt_multi_read_accum.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
-        L.rpt_multi_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
-        L.rpt_multi_destroy.argtypes = [C.c_void_p]
-        L.rpt_multi_destroy.restype = None
-        L.rpt_multi_last_error.argtypes = [C.c_void_p]
-        L.rpt_multi_last_error.restype = C.c_char_p
-        L.rpt_denoise_params_default.argtypes = [C.POINTER(DenoiseParams)]
-        L.rpt_denoise_params_default.restype = None
-        L.rpt_denoise.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DenoiseParams), C.c_uint32, C.c_void_p, C.POINTER(DenoiseReport)]
-        L.rpt_read_guides.argtypes = [C.c_void_p] + [C.c_void_p] * 5
-        L.rpt_multi_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.c_uint32, C.c_void_p, C.POINTER(DenoiseReport)]
-        L.rpt_debug_denoise_host.argtypes = [C.c_uint32, C.c_uint32] + [C.c_void_p] * 6 + [C.POINTER(DenoiseParams), C.c_uint32, C.c_void_p]
-        if hasattr(L, "rpt_set_moments"):                # (RPT_HIP_LIB may name an older build for an A/B run: it has no moments)
-            L.rpt_set_moments.argtypes = [C.c_void_p, C.c_uint32]
-            L.rpt_moments.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
-            L.rpt_read_moments.argtypes = [C.c_void_p, C.c_void_p]
-            L.rpt_read_noise.argtypes = [C.c_void_p, C.c_void_p]
-            L.rpt_noise_count.argtypes = [C.c_void_p, C.c_float, C.POINTER(NoiseCounts)]
-            L.rpt_render_to_noise.argtypes = [C.c_void_p, C.POINTER(NoiseTarget), C.POINTER(NoiseResult)]
-            L.rpt_multi_set_moments.argtypes = [C.c_void_p, C.c_uint32]
-            L.rpt_multi_read_moments.argtypes = [C.c_void_p, C.c_void_p]
-            L.rpt_multi_noise_count.argtypes = [C.c_void_p, C.c_float, C.POINTER(NoiseCounts)]
-            L.rpt_multi_render_to_noise.argtypes = [C.c_void_p, C.POINTER(NoiseTarget), C.POINTER(NoiseResult)]
-            L.rpt_debug_noise_host.argtypes = [C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.POINTER(NoiseCounts)]
-        _lib = L
+        _lib = _ffi.bind(C.CDLL(path), PROTOTYPES, allow_missing=bool(os.environ.get("RPT_HIP_LIB")))
     return _lib
 
 
@@ -189,14 +179,138 @@ class RptError(RuntimeError):
         self.code = code
 
 
-class Renderer:
+_COUNTERS = ("samples", "extension_rays", "shadow_rays", "shadow_rays_elided", "sky_evals", "light_index_clamped", "iterations")
+
+
+class _Handle:
+    """What Renderer (an rpt_ctx, prefix rpt_) and MultiRenderer (an rpt_multi, prefix rpt_multi_) share: the handle, its error text, and the entry
+    points whose C signatures are equal after the handle.  `_call("render", n)` is rpt_render(h, n) or rpt_multi_render(h, n), checked."""
+    _prefix = None
+
+    def _fn(self, name):
+        return getattr(lib(), self._prefix + name)
+
+    def _open(self, create, *args):
+        self._h = C.c_void_p()
+        rc = create(*args, C.byref(self._h))
+        if rc != 0:
+            raise RptError(rc, self._fn("last_error")(None).decode())
+
+    def _check(self, rc):
+        if rc != 0:
+            raise RptError(rc, self._fn("last_error")(self._h).decode())
+
+    def _call(self, name, *args):
+        self._check(self._fn(name)(self._h, *args))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if not getattr(self, "_borrowed", False):
+                self._fn("destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _image(self, *channels, dtype=np.float32):
+        """zeros of (H, W) + channels for a read-out of the configured size"""
+        return np.zeros((self.config.height, self.config.width) + channels, dtype)
+
+    # -- rpt_upload_scene <-> World::into_gpu (reference: src/asset.rs:226-235)
+    def upload_scene(self, world, skybox_f32=None):
+        atlas = getattr(world, "atlas", None)
+        aw = ah = sw = sh = 0
+        if atlas is not None:
+            atlas = np.ascontiguousarray(atlas, np.uint8)
+            ah, aw = atlas.shape[:2]
+        if skybox_f32 is not None:
+            skybox_f32 = np.ascontiguousarray(skybox_f32, np.float32)
+            sh, sw = skybox_f32.shape[:2]
+        self._call("upload_scene", ptr(world.per_vertex), len(world.per_vertex), ptr(world.indices), len(world.indices),
+                   ptr(world.nodes), len(world.nodes), ptr(world.materials), len(world.materials),
+                   ptr(world.light_pick), len(world.light_pick), ptr(atlas), aw, ah, ptr(skybox_f32), sw, sh)
+
+    # -- rpt_set_config <-> config_buffer write (reference: src/trace.rs:168,219)
+    def set_config(self, config):
+        self._call("set_config", C.byref(config))
+        self.config = config.copy()
+
+    # -- rpt_reset <-> rng/output buffer creation + flush (reference: src/trace.rs:164-170,219-221)
+    def reset(self, rng_seed, accum_init=None, samples_init=0):
+        rng_seed = np.ascontiguousarray(rng_seed, RNG_DTYPE)
+        if accum_init is not None:
+            accum_init = np.ascontiguousarray(accum_init, np.float32)
+        self._call("reset", ptr(rng_seed), ptr(accum_init), samples_init)
+
+    # -- rpt_render <-> the enqueue/poll loop (reference: src/trace.rs:182-194)
+    def render(self, n_samples):
+        self._call("render", n_samples)
+
+    def wait(self):
+        self._call("wait")
+
+    # -- rpt_read_accum <-> output_buffer.read_blocking (reference: src/trace.rs:198)
+    def read_accum(self, out=None):
+        if out is None:
+            out = self._image(4)
+        assert out.dtype == np.float32 and out.size == self.config.height * self.config.width * 4 and out.flags["C_CONTIGUOUS"]
+        samples = C.c_uint32()
+        self._call("read_accum", ptr(out), C.byref(samples))
+        return out, samples.value
+
+    def _denoise(self, source, params, tonemap_op, with_report):
+        """source: what rpt_denoise takes between the handle and params, as a tuple (rpt_multi_denoise: nothing)"""
+        out, rep = self._image(3), DenoiseReport()
+        self._call("denoise", *source, None if params is None else C.byref(params), tonemap_op, ptr(out), C.byref(rep))
+        return (out, _report_dict(rep)) if with_report else out
+
+    def set_shadow_mode(self, mode):
+        """rpt_set_shadow_mode (rpt_multi_: on every rank): SHADOW_EXACT (default: the reference's any-hit walk, bit for bit) or SHADOW_SEGMENT (boxes that begin
+        behind the ray's max_t are not entered: faster, an occlusion can in principle be lost); holds for the batches enqueued afterwards."""
+        self._call("set_shadow_mode", mode)
+
+    # -- per-pixel sample moments and the noise estimate (no reference equivalent; include/rpt/rpt.h "per-pixel sample moments")
+    def set_moments(self, on=True):
+        """rpt_set_moments (rpt_multi_: on every rank): keep (sum Y, sum Y^2, n, max Y) of every pixel's samples beside the accumulator; turning it on zeroes the
+        record.  The image does not depend on it.  A renderer with one sample of a pixel in flight (set_samples_in_flight(1)) refuses to render while it is on."""
+        self._call("set_moments", 1 if on else 0)
+
+    def read_moments(self):
+        """rpt_read_moments: (H, W, 4) float32 — sum of luminance, sum of its square, samples since the record was zeroed, brightest sample; other ranks' pixels 0
+        (rpt_multi_: the whole image, the ranks' records merged on the host)"""
+        out = self._image(4)
+        self._call("read_moments", ptr(out))
+        return out
+
+    def noise_count(self, threshold):
+        """rpt_noise_count (rpt_multi_: summed over the ranks): {"pixels": owned, "measured": with two samples or more, "above": measured with not (rel <= threshold)}"""
+        k = NoiseCounts()
+        self._call("noise_count", threshold, C.byref(k))
+        return _counts_dict(k)
+
+    def render_to_noise(self, threshold, max_above=0, batch_samples=32, min_samples=32, max_samples=1024):
+        """rpt_render_to_noise: batches of batch_samples until every pixel is measured and at most max_above are above threshold (counted from min_samples on),
+        or max_samples are rendered: {"samples_rendered", "converged", "counts", "ms"}.  Turns moments on and leaves them on.
+        (rpt_multi_: over every GPU, each batch gathered as render() gathers it)"""
+        t, res = NoiseTarget(threshold, min_samples, max_samples, batch_samples, max_above), NoiseResult()
+        self._call("render_to_noise", C.byref(t), C.byref(res))
+        return _noise_result_dict(res)
+
+    def _get_stats(self):
+        s = Stats()
+        self._call("get_stats", C.byref(s))
+        return s
+
+
+class Renderer(_Handle):
     """One rpt_ctx on one GPU (one process per GPU in multi-GPU runs)."""
+    _prefix = "rpt_"
 
     def __init__(self, device_id=0, rank=0, world_size=1):
-        self._h = C.c_void_p()
-        rc = lib().rpt_create(device_id, C.byref(self._h))
-        if rc != 0:
-            raise RptError(rc, lib().rpt_last_error(None).decode())
+        self._open(lib().rpt_create, device_id)
         self.rank, self.world_size = rank, world_size
         if world_size != 1:
             self._check(lib().rpt_set_partition(self._h, rank, world_size))
@@ -210,71 +324,26 @@ class Renderer:
         self.rank, self.world_size, self.config = rank, world_size, config
         return self
 
-    def _check(self, rc):
-        if rc != 0:
-            raise RptError(rc, lib().rpt_last_error(self._h).decode())
-
     def set_partition(self, rank, world_size):
         """rpt_set_partition: this context renders the tiles of `rank` of `world_size` (state is re-allocated at the next reset)."""
         self._check(lib().rpt_set_partition(self._h, rank, world_size))
         self.rank, self.world_size = rank, world_size
 
-    def close(self):
-        if getattr(self, "_h", None):
-            if not getattr(self, "_borrowed", False):
-                lib().rpt_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def set_samples_in_flight(self, samples):
         """0 = automatic. Never changes the result (tests/test_gpu_parity.py::test_samples_in_flight_invisible)."""
         self._check(lib().rpt_set_samples_in_flight(self._h, samples))
 
-    # -- rpt_upload_scene <-> World::into_gpu (reference: src/asset.rs:226-235)
-    def upload_scene(self, world, skybox_f32=None):
-        atlas = getattr(world, "atlas", None)
-        aw = ah = sw = sh = 0
-        if atlas is not None:
-            atlas = np.ascontiguousarray(atlas, np.uint8)
-            ah, aw = atlas.shape[:2]
-        if skybox_f32 is not None:
-            skybox_f32 = np.ascontiguousarray(skybox_f32, np.float32)
-            sh, sw = skybox_f32.shape[:2]
-        self._check(lib().rpt_upload_scene(
-            self._h, ptr(world.per_vertex), len(world.per_vertex), ptr(world.indices), len(world.indices),
-            ptr(world.nodes), len(world.nodes), ptr(world.materials), len(world.materials),
-            ptr(world.light_pick), len(world.light_pick), ptr(atlas), aw, ah, ptr(skybox_f32), sw, sh))
-
-    # -- rpt_set_config <-> config_buffer write (reference: src/trace.rs:168,219)
-    def set_config(self, config):
-        self._check(lib().rpt_set_config(self._h, C.byref(config)))
-        self.config = config.copy()
-
-    # -- rpt_reset <-> rng/output buffer creation + flush (reference: src/trace.rs:164-170,219-221)
     def reset(self, rng_seed, accum_init=None, samples_init=0):
+        """(the sizes are checked here; a MultiRenderer leaves that to rpt_multi_reset)"""
         rng_seed = np.ascontiguousarray(rng_seed, RNG_DTYPE)
         assert rng_seed.size == self.config.width * self.config.height
-        if accum_init is not None:
-            accum_init = np.ascontiguousarray(accum_init, np.float32)
-            assert accum_init.size == rng_seed.size * 4
-        self._check(lib().rpt_reset(self._h, ptr(rng_seed), ptr(accum_init), samples_init))
-
-    # -- rpt_render <-> the enqueue/poll loop (reference: src/trace.rs:182-194)
-    def render(self, n_samples):
-        self._check(lib().rpt_render(self._h, n_samples))
+        assert accum_init is None or np.size(accum_init) == rng_seed.size * 4
+        super().reset(rng_seed, accum_init, samples_init)
 
     def render_async(self, n_samples):
         """rpt_render_async: returns once the batch is enqueued when its iteration count is known (n_samples <= slots per
         pixel), else behaves like render()."""
         self._check(lib().rpt_render_async(self._h, n_samples))
-
-    def wait(self):
-        self._check(lib().rpt_wait(self._h))
 
     def stream_ptr(self):
         """The hipStream_t the library enqueues on (wrap with torch.cuda.ExternalStream to order work after a batch)."""
@@ -282,27 +351,17 @@ class Renderer:
         self._check(lib().rpt_stream(self._h, C.byref(p)))
         return p.value
 
-    # -- rpt_read_accum <-> output_buffer.read_blocking (reference: src/trace.rs:198)
-    def read_accum(self, out=None):
-        if out is None:
-            out = np.zeros((self.config.height, self.config.width, 4), np.float32)
-        assert out.dtype == np.float32 and out.size == self.config.height * self.config.width * 4 and out.flags["C_CONTIGUOUS"]
-        samples = C.c_uint32()
-        self._check(lib().rpt_read_accum(self._h, ptr(out), C.byref(samples)))
-        return out, samples.value
-
     def map_accum(self):
         """rpt_map_accum: the library's own pinned read-back buffer as an (H, W, 4) array — no copy; valid until the
         next read_accum / map_accum / set_config on this renderer."""
         p = C.POINTER(C.c_float)()
         samples = C.c_uint32()
         self._check(lib().rpt_map_accum(self._h, C.byref(p), C.byref(samples)))
-        h, w = self.config.height, self.config.width
-        return np.ctypeslib.as_array(p, shape=(h, w, 4)), samples.value
+        return np.ctypeslib.as_array(p, shape=(self.config.height, self.config.width, 4)), samples.value
 
     def resolve(self, tonemap_op=0):
         """mean radiance (+ display tonemap 0..6, reference: src/resources/render.wgsl:131-153) as (H, W, 3) float32."""
-        out = np.zeros((self.config.height, self.config.width, 3), np.float32)
+        out = self._image(3)
         self._check(lib().rpt_resolve(self._h, tonemap_op, ptr(out)))
         return out
 
@@ -310,55 +369,25 @@ class Renderer:
     def denoise(self, source=DENOISE_ACCUM, params=None, tonemap_op=0, with_report=False):
         """rpt_denoise: the mean image filtered by the guided a-trous filter, then tonemapped, as (H, W, 3) float32 (params None: the defaults;
         with_report: also {"device_ms", "guides_ms", "guides_rebuilt"})."""
-        out = np.zeros((self.config.height, self.config.width, 3), np.float32)
-        rep = DenoiseReport()
-        self._check(lib().rpt_denoise(self._h, source, None if params is None else C.byref(params), tonemap_op, ptr(out), C.byref(rep)))
-        return (out, _report_dict(rep)) if with_report else out
+        return self._denoise((source,), params, tonemap_op, with_report)
 
     def guides(self):
         """rpt_read_guides: the first-hit guide buffers of the current scene and camera:
         {"albedo", "normal", "position": (H, W, 3) float32, "depth": (H, W) float32, "kind": (H, W) uint32 (GUIDE_MISS / SURFACE / EMITTER)}"""
-        h, w = self.config.height, self.config.width
-        g = {"albedo": np.zeros((h, w, 3), np.float32), "normal": np.zeros((h, w, 3), np.float32), "depth": np.zeros((h, w), np.float32),
-             "position": np.zeros((h, w, 3), np.float32), "kind": np.zeros((h, w), np.uint32)}
+        g = {"albedo": self._image(3), "normal": self._image(3), "depth": self._image(), "position": self._image(3), "kind": self._image(dtype=np.uint32)}
         self._check(lib().rpt_read_guides(self._h, ptr(g["albedo"]), ptr(g["normal"]), ptr(g["depth"]), ptr(g["position"]), ptr(g["kind"])))
         return g
-
-    # -- per-pixel sample moments and the noise estimate (no reference equivalent; include/rpt/rpt.h "per-pixel sample moments")
-    def set_moments(self, on=True):
-        """rpt_set_moments: keep (sum Y, sum Y^2, n, max Y) of every pixel's samples beside the accumulator; turning it on zeroes the record.  The image does not
-        depend on it.  A renderer with one sample of a pixel in flight (set_samples_in_flight(1)) refuses to render while it is on."""
-        self._check(lib().rpt_set_moments(self._h, 1 if on else 0))
 
     def moments_on(self):
         on = C.c_uint32()
         self._check(lib().rpt_moments(self._h, C.byref(on)))
         return bool(on.value)
 
-    def read_moments(self):
-        """rpt_read_moments: (H, W, 4) float32 — sum of luminance, sum of its square, samples since the record was zeroed, brightest sample; other ranks' pixels 0"""
-        out = np.zeros((self.config.height, self.config.width, 4), np.float32)
-        self._check(lib().rpt_read_moments(self._h, ptr(out)))
-        return out
-
     def read_noise(self):
         """rpt_read_noise: (H, W) float32, the standard error of every pixel's mean luminance relative to that mean (inf below two samples); other ranks' pixels 0"""
-        out = np.zeros((self.config.height, self.config.width), np.float32)
+        out = self._image()
         self._check(lib().rpt_read_noise(self._h, ptr(out)))
         return out
-
-    def noise_count(self, threshold):
-        """rpt_noise_count: {"pixels": owned, "measured": with two samples or more, "above": measured with not (rel <= threshold)}"""
-        k = NoiseCounts()
-        self._check(lib().rpt_noise_count(self._h, threshold, C.byref(k)))
-        return _counts_dict(k)
-
-    def render_to_noise(self, threshold, max_above=0, batch_samples=32, min_samples=32, max_samples=1024):
-        """rpt_render_to_noise: batches of batch_samples until every pixel is measured and at most max_above are above threshold (counted from min_samples on),
-        or max_samples are rendered: {"samples_rendered", "converged", "counts", "ms"}.  Turns moments on and leaves them on."""
-        t, res = NoiseTarget(threshold, min_samples, max_samples, batch_samples, max_above), NoiseResult()
-        self._check(lib().rpt_render_to_noise(self._h, C.byref(t), C.byref(res)))
-        return _noise_result_dict(res)
 
     def read_rng(self):
         out = np.zeros(self.config.height * self.config.width, RNG_DTYPE)
@@ -366,10 +395,8 @@ class Renderer:
         return out
 
     def stats(self):
-        s = Stats()
-        self._check(lib().rpt_get_stats(self._h, C.byref(s)))
-        d = {k: getattr(s, k) for k in ("samples", "extension_rays", "shadow_rays", "shadow_rays_elided", "sky_evals", "light_index_clamped",
-                                         "iterations", "render_ms")}
+        s = self._get_stats()
+        d = {k: getattr(s, k) for k in _COUNTERS + ("render_ms",)}
         d["shadow_rays_traced"] = d["shadow_rays"] - d["shadow_rays_elided"]       # walked on the device; shadow_rays counts as the reference does
         d["kernel_ms"] = {n: s.kernel_ms[i] for i, n in enumerate(_ffi.STAGE_NAMES)}
         d["kernel_launches"] = {n: s.kernel_launches[i] for i, n in enumerate(_ffi.STAGE_NAMES)}
@@ -392,7 +419,7 @@ class Renderer:
         return p.value
 
     def untile(self, dev_blocks_ptr, dev_out_ptr, block_stride_pixels=0):
-        self._check(lib().rpt_untile(self._h, C.c_void_p(dev_blocks_ptr), block_stride_pixels, C.c_void_p(dev_out_ptr)))
+        self._check(lib().rpt_untile(self._h, dev_blocks_ptr, block_stride_pixels, dev_out_ptr))
 
     # -- the gather inside the library (RCCL): rpt_comm_init / rpt_gather_async / rpt_read_gathered
     def comm_init(self, unique_id, rank, world_size):
@@ -412,11 +439,6 @@ class Renderer:
         vn, vf, ms = C.c_double(), C.c_double(), C.c_double()
         self._check(lib().rpt_shadow_order(self._h, C.byref(f), C.byref(vn), C.byref(vf), C.byref(n), C.byref(ms)))
         return {"fixed": bool(f.value), "visits_near": vn.value, "visits_fixed": vf.value, "probe_rays": n.value, "probe_ms": ms.value}
-
-    def set_shadow_mode(self, mode):
-        """rpt_set_shadow_mode: SHADOW_EXACT (default: the reference's any-hit walk, bit for bit) or SHADOW_SEGMENT (boxes that begin behind the ray's max_t
-        are not entered: faster, an occlusion can in principle be lost); holds for the batches enqueued afterwards."""
-        self._check(lib().rpt_set_shadow_mode(self._h, mode))
 
     def shadow_mode(self):
         m = C.c_uint32()
@@ -454,7 +476,7 @@ class Renderer:
 
     def read_gathered(self, out=None):
         if out is None:
-            out = np.zeros((self.config.height, self.config.width, 4), np.float32)
+            out = self._image(4)
         samples = C.c_uint32()
         self._check(lib().rpt_read_gathered(self._h, ptr(out), C.byref(samples)))
         return out, samples.value
@@ -462,7 +484,6 @@ class Renderer:
     # -- test hooks (include/rpt/rpt_debug.h)
     def debug_short_batch(self, on=True):
         """rpt_debug_short_batch: asynchronous batches enqueue one iteration too few (the completion checks must notice)."""
-        lib().rpt_debug_short_batch.argtypes = [C.c_void_p, C.c_int]
         self._check(lib().rpt_debug_short_batch(self._h, 1 if on else 0))
 
     def debug_math(self, op, x, y=None):
@@ -538,32 +559,15 @@ def comm_library():
     return lib().rpt_comm_library().decode()
 
 
-class MultiRenderer:
+class MultiRenderer(_Handle):
     """rpt_multi_*: ONE process driving several GPUs (ncclCommInitAll) — the entry points a single render thread like
     the reference's (src/trace.rs:136-224) calls; the caller sees one W x H image."""
+    _prefix = "rpt_multi_"
 
     def __init__(self, device_ids, allow_shared_device=False):
         ids = (C.c_int * len(device_ids))(*device_ids)
-        self._h = C.c_void_p()
-        rc = lib().rpt_multi_create(ids, len(device_ids), MULTI_ALLOW_SHARED_DEVICE if allow_shared_device else 0, C.byref(self._h))
-        if rc != 0:
-            raise RptError(rc, lib().rpt_multi_last_error(None).decode())
+        self._open(lib().rpt_multi_create, ids, len(device_ids), MULTI_ALLOW_SHARED_DEVICE if allow_shared_device else 0)
         self.config = None
-
-    def _check(self, rc):
-        if rc != 0:
-            raise RptError(rc, lib().rpt_multi_last_error(self._h).decode())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().rpt_multi_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def size(self):
         return lib().rpt_multi_size(self._h)
@@ -574,92 +578,23 @@ class MultiRenderer:
 
     def ctx_handle(self, rank):
         """rpt_multi_ctx: the borrowed rpt_ctx of one rank (for rpt_set_samples_in_flight / rpt_get_stats per GPU)."""
-        lib().rpt_multi_ctx.restype = C.c_void_p
-        lib().rpt_multi_ctx.argtypes = [C.c_void_p, C.c_int]
         return C.c_void_p(lib().rpt_multi_ctx(self._h, rank))
-
-    def upload_scene(self, world, skybox_f32=None):
-        atlas = getattr(world, "atlas", None)
-        aw = ah = sw = sh = 0
-        if atlas is not None:
-            atlas = np.ascontiguousarray(atlas, np.uint8)
-            ah, aw = atlas.shape[:2]
-        if skybox_f32 is not None:
-            skybox_f32 = np.ascontiguousarray(skybox_f32, np.float32)
-            sh, sw = skybox_f32.shape[:2]
-        self._check(lib().rpt_multi_upload_scene(
-            self._h, ptr(world.per_vertex), len(world.per_vertex), ptr(world.indices), len(world.indices),
-            ptr(world.nodes), len(world.nodes), ptr(world.materials), len(world.materials),
-            ptr(world.light_pick), len(world.light_pick), ptr(atlas), aw, ah, ptr(skybox_f32), sw, sh))
-
-    def set_config(self, config):
-        self._check(lib().rpt_multi_set_config(self._h, C.byref(config)))
-        self.config = config.copy()
-
-    def set_shadow_mode(self, mode):
-        """rpt_multi_set_shadow_mode: Renderer.set_shadow_mode on every rank"""
-        self._check(lib().rpt_multi_set_shadow_mode(self._h, mode))
-
-    def reset(self, rng_seed, accum_init=None, samples_init=0):
-        rng_seed = np.ascontiguousarray(rng_seed, RNG_DTYPE)
-        if accum_init is not None:
-            accum_init = np.ascontiguousarray(accum_init, np.float32)
-        self._check(lib().rpt_multi_reset(self._h, ptr(rng_seed), ptr(accum_init), samples_init))
-
-    def render(self, n_samples):
-        self._check(lib().rpt_multi_render(self._h, n_samples))
-
-    def wait(self):
-        self._check(lib().rpt_multi_wait(self._h))
-
-    def read_accum(self, out=None):
-        if out is None:
-            out = np.zeros((self.config.height, self.config.width, 4), np.float32)
-        assert out.dtype == np.float32 and out.size == self.config.height * self.config.width * 4 and out.flags["C_CONTIGUOUS"]
-        samples = C.c_uint32()
-        self._check(lib().rpt_multi_read_accum(self._h, ptr(out), C.byref(samples)))
-        return out, samples.value
-
-    def set_moments(self, on=True):
-        """rpt_multi_set_moments: Renderer.set_moments on every rank"""
-        self._check(lib().rpt_multi_set_moments(self._h, 1 if on else 0))
 
     def moments_on(self):
         return self.rank_view(0).moments_on()
-
-    def read_moments(self):
-        """rpt_multi_read_moments: the whole (H, W, 4) image, the ranks' records merged on the host"""
-        out = np.zeros((self.config.height, self.config.width, 4), np.float32)
-        self._check(lib().rpt_multi_read_moments(self._h, ptr(out)))
-        return out
 
     def read_noise(self):
         """noise_host of read_moments(): the whole (H, W) image (there is no multi-GPU entry point for it: the arithmetic is the same header on the host)"""
         return noise_host(self.read_moments())[0]
 
-    def noise_count(self, threshold):
-        """rpt_multi_noise_count: Renderer.noise_count summed over the ranks"""
-        k = NoiseCounts()
-        self._check(lib().rpt_multi_noise_count(self._h, threshold, C.byref(k)))
-        return _counts_dict(k)
-
-    def render_to_noise(self, threshold, max_above=0, batch_samples=32, min_samples=32, max_samples=1024):
-        """rpt_multi_render_to_noise: Renderer.render_to_noise over every GPU (each batch gathered as render() gathers it)"""
-        t, res = NoiseTarget(threshold, min_samples, max_samples, batch_samples, max_above), NoiseResult()
-        self._check(lib().rpt_multi_render_to_noise(self._h, C.byref(t), C.byref(res)))
-        return _noise_result_dict(res)
-
     def denoise(self, params=None, tonemap_op=0, with_report=False):
         """rpt_multi_denoise: waits, gathers if need be, and denoises the whole image on rank 0 (see Renderer.denoise)"""
-        out = np.zeros((self.config.height, self.config.width, 3), np.float32)
-        rep = DenoiseReport()
-        self._check(lib().rpt_multi_denoise(self._h, None if params is None else C.byref(params), tonemap_op, ptr(out), C.byref(rep)))
-        return (out, _report_dict(rep)) if with_report else out
+        return self._denoise((), params, tonemap_op, with_report)
 
     def stats(self):
-        s = Stats()
-        self._check(lib().rpt_multi_get_stats(self._h, C.byref(s)))
-        return {k: getattr(s, k) for k in ("samples", "extension_rays", "shadow_rays", "shadow_rays_elided", "sky_evals", "light_index_clamped", "iterations")}
+        """rpt_multi_get_stats: the counters summed over the GPUs (no times: rank_view(k).stats() has each GPU's)"""
+        s = self._get_stats()
+        return {k: getattr(s, k) for k in _COUNTERS}
 
 
 def tile_order(width, height, rank, world_size):
@@ -680,11 +615,8 @@ def last_order_host(world):
     r, n = C.c_uint32(), C.c_uint32()
     v = (C.c_double * 4)()
     flip = np.zeros(max(1, (len(world.nodes) - 1) // 2), np.uint8)
-    L = lib()
-    L.rpt_debug_last_order_host.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                            C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_void_p]
-    rc = L.rpt_debug_last_order_host(ptr(world.per_vertex), len(world.per_vertex), ptr(world.indices), len(world.indices), ptr(world.nodes), len(world.nodes),
-                                     ptr(world.materials), len(world.materials), C.byref(r), v, C.byref(n), ptr(flip))
+    rc = lib().rpt_debug_last_order_host(ptr(world.per_vertex), len(world.per_vertex), ptr(world.indices), len(world.indices), ptr(world.nodes), len(world.nodes),
+                                         ptr(world.materials), len(world.materials), C.byref(r), v, C.byref(n), ptr(flip))
     if rc != 0:
         raise RptError(rc, "rpt_debug_last_order_host")
     return {"rule": r.value, "visits": [v[k] for k in range(4)], "probe_rays": n.value, "flip": flip}
@@ -695,12 +627,9 @@ def shadow_order_host(world):
     f, n = C.c_uint32(), C.c_uint32()
     vn, vf = C.c_double(), C.c_double()
     flip = np.zeros(max(1, (len(world.nodes) - 1) // 2), np.uint8)
-    L = lib()
-    L.rpt_debug_shadow_order_host.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                              C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_void_p]
-    rc = L.rpt_debug_shadow_order_host(ptr(world.per_vertex), len(world.per_vertex), ptr(world.indices), len(world.indices), ptr(world.nodes), len(world.nodes),
-                                       ptr(world.materials), len(world.materials), ptr(world.light_pick), len(world.light_pick),
-                                       C.byref(f), C.byref(vn), C.byref(vf), C.byref(n), ptr(flip))
+    rc = lib().rpt_debug_shadow_order_host(ptr(world.per_vertex), len(world.per_vertex), ptr(world.indices), len(world.indices), ptr(world.nodes), len(world.nodes),
+                                           ptr(world.materials), len(world.materials), ptr(world.light_pick), len(world.light_pick),
+                                           C.byref(f), C.byref(vn), C.byref(vf), C.byref(n), ptr(flip))
     if rc != 0:
         raise RptError(rc, "rpt_debug_shadow_order_host")
     return {"fixed": bool(f.value), "visits_near": vn.value, "visits_fixed": vf.value, "probe_rays": n.value, "flip": flip}
@@ -760,13 +689,10 @@ def light_table_build_gpu(vertices_xyzw, triangles, materials, device=0):
     table = np.empty(max(1, len(t)), LIGHT_PICK_DTYPE)          # (np.zeros would fault in 28 bytes per triangle of pages the call overwrites)
     n, n_em = C.c_size_t(0), C.c_uint32(0)
     ms = (C.c_double * 4)()
-    L = lib()
-    L.rpt_light_table_build_gpu.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                            C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
-    rc = L.rpt_light_table_build_gpu(device, v.ctypes.data, len(v), t.ctypes.data, len(t), m.ctypes.data, len(m), table.ctypes.data, len(table),
-                                     C.byref(n), C.byref(n_em), ms)
+    rc = lib().rpt_light_table_build_gpu(device, v.ctypes.data, len(v), t.ctypes.data, len(t), m.ctypes.data, len(m), table.ctypes.data, len(table),
+                                         C.byref(n), C.byref(n_em), ms)
     if rc != 0:
-        raise RptError(rc, L.rpt_last_error(None).decode())
+        raise RptError(rc, lib().rpt_last_error(None).decode())
     return table[: n.value], n_em.value, {"total": ms[0], "device": ms[1], "host_chains": ms[2], "transfers": ms[3]}
 
 

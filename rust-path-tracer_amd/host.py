@@ -17,48 +17,51 @@ from ._ffi import (BVH_NODE_DTYPE, LIGHT_PICK_DTYPE, MATERIAL_DTYPE, PER_VERTEX_
 
 _lib = None
 
+# every function of include/rpt/rpt_host.h, in its order: name -> (return type, [parameter types]); tests/test_contracts.py holds it against the header
+PROTOTYPES = {
+    "rpt_world_load": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]),
+    "rpt_world_load_ex": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "rpt_skybox_load": (C.c_int, [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "rpt_host_free": (None, [C.c_void_p]),
+    "rpt_world_from_buffers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "rpt_world_view_get": (C.c_int, [C.c_void_p, C.POINTER(WorldView)]),
+    "rpt_world_save": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "rpt_world_load_cache": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]),
+    "rpt_write_png": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]),
+    "rpt_world_free": (None, [C.c_void_p]),
+    "rpt_bvh_build": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "rpt_host_set_bvh_builder": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
+    "rpt_light_table_build": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "rpt_blue_noise_seeds": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "rpt_blue_noise_tile": (C.c_int, [C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "rpt_tracing_config_default": (None, [C.POINTER(TracingConfig)]),
+    "rpt_tracing_state_new": (C.c_void_p, [C.c_uint32, C.c_uint32]),
+    "rpt_tracing_state_free": (None, [C.c_void_p]),
+    "rpt_tracing_state_config": (C.POINTER(TracingConfig), [C.c_void_p]),
+    "rpt_tracing_state_framebuffer": (C.POINTER(C.c_float), [C.c_void_p, C.POINTER(C.c_size_t)]),
+    "rpt_tracing_state_copy_framebuffer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rpt_tracing_state_samples": (C.c_uint32, [C.c_void_p]),
+    "rpt_tracing_state_set_running": (None, [C.c_void_p, C.c_int]),
+    "rpt_tracing_state_set_sync_rate": (None, [C.c_void_p, C.c_uint32]),
+    "rpt_tracing_state_set_dirty": (None, [C.c_void_p, C.c_int]),
+    "rpt_tracing_state_set_interacting": (None, [C.c_void_p, C.c_int]),
+    "rpt_tracing_state_set_config": (None, [C.c_void_p, C.POINTER(TracingConfig)]),
+    "rpt_tracing_state_set_overlap": (None, [C.c_void_p, C.c_int]),
+    "rpt_tracing_state_set_denoise": (None, [C.c_void_p, C.c_int]),
+    "rpt_setup_trace": (C.c_void_p, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    "rpt_trace_gpu": (C.c_int, [C.c_char_p, C.c_char_p, C.c_void_p, C.c_int, C.c_char_p]),
+    "rpt_host_last_error": (C.c_char_p, []),
+}
+
 
 def lib():
-    """Load librpt_host.so (built in-tree by `make host` / __graft_entry__.build())."""
+    """Load librpt_host.so (built in-tree by `make host` / __graft_entry__.build()) and give every function of PROTOTYPES its prototype."""
     global _lib
     if _lib is None:
         path = os.environ.get("RPT_HOST_LIB") or os.path.join(_ffi.LIB_DIR, "librpt_host.so")   # (RPT_HOST_LIB: a sanitizer build, tools/fuzz_glb.py)
         if not os.path.exists(path):
             raise RuntimeError(f"{path} is missing: run `make host` (or __graft_entry__.build())")
-        L = C.CDLL(path)
-        L.rpt_host_last_error.restype = C.c_char_p
-        L.rpt_tracing_state_new.restype = C.c_void_p
-        L.rpt_setup_trace.restype = C.c_void_p
-        L.rpt_tracing_state_config.restype = C.POINTER(TracingConfig)
-        L.rpt_tracing_state_config.argtypes = [C.c_void_p]
-        L.rpt_tracing_state_framebuffer.restype = C.POINTER(C.c_float)
-        L.rpt_tracing_state_framebuffer.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
-        L.rpt_tracing_state_samples.restype = C.c_uint32
-        L.rpt_tracing_state_samples.argtypes = [C.c_void_p]
-        L.rpt_tracing_state_free.argtypes = [C.c_void_p]
-        L.rpt_tracing_state_set_sync_rate.argtypes = [C.c_void_p, C.c_uint32]
-        L.rpt_tracing_state_set_running.argtypes = [C.c_void_p, C.c_int]
-        L.rpt_tracing_state_set_dirty.argtypes = [C.c_void_p, C.c_int]
-        L.rpt_tracing_state_set_overlap.argtypes = [C.c_void_p, C.c_int]
-        L.rpt_tracing_state_set_interacting.argtypes = [C.c_void_p, C.c_int]
-        L.rpt_tracing_state_set_denoise.argtypes = [C.c_void_p, C.c_int]
-        L.rpt_tracing_state_copy_framebuffer.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        L.rpt_tracing_state_set_config.argtypes = [C.c_void_p, C.POINTER(TracingConfig)]
-        L.rpt_tracing_state_new.argtypes = [C.c_uint32, C.c_uint32]
-        L.rpt_trace_gpu.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_int, C.c_char_p]
-        L.rpt_world_load.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
-        L.rpt_world_load_ex.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_void_p)]
-        L.rpt_skybox_load.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-        L.rpt_host_free.argtypes = [C.c_void_p]
-        L.rpt_host_free.restype = None
-        L.rpt_world_view_get.argtypes = [C.c_void_p, C.POINTER(WorldView)]
-        L.rpt_world_free.argtypes = [C.c_void_p]
-        L.rpt_world_save.argtypes = [C.c_void_p, C.c_char_p]
-        L.rpt_world_load_cache.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
-        L.rpt_world_from_buffers.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
-                                             C.c_size_t, C.POINTER(C.c_void_p)]
-        L.rpt_write_png.argtypes = [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]
-        _lib = L
+        _lib = _ffi.bind(C.CDLL(path), PROTOTYPES, allow_missing=False)
     return _lib
 
 
@@ -127,7 +130,7 @@ class World:
         """World::from_path (reference: src/asset.rs:55-224).  emissive_strength=True honours
         KHR_materials_emissive_strength instead of the reference's fixed x15 (opt-in: not the reference's behaviour)."""
         h = C.c_void_p()
-        _check(lib().rpt_world_load_ex(os.fsencode(path), C.c_uint32(1 if emissive_strength else 0), C.byref(h)))
+        _check(lib().rpt_world_load_ex(os.fsencode(path), 1 if emissive_strength else 0, C.byref(h)))
         return cls._from_handle(h)
 
     @classmethod
@@ -161,9 +164,8 @@ class World:
         triangles = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 4)
         materials = np.ascontiguousarray(materials, MATERIAL_DTYPE)
         h = C.c_void_p()
-        _check(lib().rpt_world_from_buffers(ptr(vertices), ptr(normals), ptr(uvs), C.c_size_t(len(vertices)),
-                                            ptr(triangles), C.c_size_t(len(triangles)), ptr(materials),
-                                            C.c_size_t(len(materials)), C.byref(h)))
+        _check(lib().rpt_world_from_buffers(ptr(vertices), ptr(normals), ptr(uvs), len(vertices), ptr(triangles), len(triangles),
+                                            ptr(materials), len(materials), C.byref(h)))
         return cls._from_handle(h)
 
 
@@ -174,7 +176,7 @@ def fixture(name):
 def write_png(path, rgb, srgb=True):
     """8-bit PNG of a resolved (H, W, 3) float frame, sRGB-encoded like the reference's saved renders."""
     rgb = np.ascontiguousarray(rgb, np.float32)
-    _check(lib().rpt_write_png(os.fsencode(path), ptr(rgb), C.c_uint32(rgb.shape[1]), C.c_uint32(rgb.shape[0]), int(bool(srgb))))
+    _check(lib().rpt_write_png(os.fsencode(path), ptr(rgb), rgb.shape[1], rgb.shape[0], int(bool(srgb))))
 
 
 def load_skybox(path):
@@ -192,16 +194,14 @@ def load_skybox(path):
 def blue_noise_tile(png_path=None):
     out = np.zeros(256 * 256, np.uint8)
     w, h = C.c_uint32(), C.c_uint32()
-    _check(lib().rpt_blue_noise_tile(os.fsencode(png_path or fixture("bluenoise.png")), ptr(out), C.c_size_t(out.size),
-                                     C.byref(w), C.byref(h)))
+    _check(lib().rpt_blue_noise_tile(os.fsencode(png_path or fixture("bluenoise.png")), ptr(out), out.size, C.byref(w), C.byref(h)))
     return out[: w.value * h.value].reshape(h.value, w.value)
 
 
 def blue_noise_seeds(width, height, png_path=None):
     """rng[i] = (0, seed(x % 256, y % 256)) as a (H*W,) RNG_DTYPE array (reference: src/trace.rs:150-157)."""
     out = np.zeros(width * height, RNG_DTYPE)
-    _check(lib().rpt_blue_noise_seeds(os.fsencode(png_path or fixture("bluenoise.png")), C.c_uint32(width),
-                                      C.c_uint32(height), ptr(out)))
+    _check(lib().rpt_blue_noise_seeds(os.fsencode(png_path or fixture("bluenoise.png")), width, height, ptr(out)))
     return out
 
 
@@ -228,25 +228,25 @@ class TracingState:
         return out.reshape(cfg.height, cfg.width, 3)
 
     def set_sync_rate(self, n):
-        lib().rpt_tracing_state_set_sync_rate(self._h, C.c_uint32(n))
+        lib().rpt_tracing_state_set_sync_rate(self._h, n)
 
     def set_running(self, running):
-        lib().rpt_tracing_state_set_running(self._h, C.c_int(1 if running else 0))
+        lib().rpt_tracing_state_set_running(self._h, 1 if running else 0)
 
     def set_dirty(self, dirty=True):
-        lib().rpt_tracing_state_set_dirty(self._h, C.c_int(1 if dirty else 0))
+        lib().rpt_tracing_state_set_dirty(self._h, 1 if dirty else 0)
 
     def set_interacting(self, on=True):
         """state.interacting (src/trace.rs:50): while up, every batch flushes (camera drag)."""
-        lib().rpt_tracing_state_set_interacting(self._h, C.c_int(1 if on else 0))
+        lib().rpt_tracing_state_set_interacting(self._h, 1 if on else 0)
 
     def set_denoise(self, on=True):
         """state.denoise (src/trace.rs:45): trace_gpu publishes the denoised image (rpt_denoise, defaults) on iterations that do not flush."""
-        lib().rpt_tracing_state_set_denoise(self._h, C.c_int(1 if on else 0))
+        lib().rpt_tracing_state_set_denoise(self._h, 1 if on else 0)
 
     def set_overlap(self, on=True):
         """trace_gpu reads batch k back while batch k+1 renders (rpt_tracing_state_set_overlap)."""
-        lib().rpt_tracing_state_set_overlap(self._h, C.c_int(1 if on else 0))
+        lib().rpt_tracing_state_set_overlap(self._h, 1 if on else 0)
 
     def set_config(self, config):
         """state.config.write() while trace_gpu runs on another thread (locked copy); follow with set_dirty()."""
@@ -263,7 +263,7 @@ class TracingState:
 
 def setup_trace(width, height, samples):
     """setup_trace(width, height, samples) (reference: src/trace.rs:331-344), exact sample count."""
-    return TracingState(C.c_void_p(lib().rpt_setup_trace(C.c_uint32(width), C.c_uint32(height), C.c_uint32(samples))))
+    return TracingState(C.c_void_p(lib().rpt_setup_trace(width, height, samples)))
 
 
 def trace_gpu(scene_path, skybox_path, state, device_id=0):
@@ -278,15 +278,11 @@ def bvh_build(vertices_xyzw, triangles, sah_samples=128):
     t = np.ascontiguousarray(triangles, TRIANGLE_DTYPE).copy()
     nodes = np.zeros(max(1, 2 * len(t) - 1), BVH_NODE_DTYPE)
     n_nodes = C.c_size_t(0)
-    L = lib()
-    L.rpt_bvh_build.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-    _check(L.rpt_bvh_build(v.ctypes.data, len(v), t.ctypes.data, len(t), sah_samples, nodes.ctypes.data, len(nodes), C.byref(n_nodes)))
+    _check(lib().rpt_bvh_build(v.ctypes.data, len(v), t.ctypes.data, len(t), sah_samples, nodes.ctypes.data, len(nodes), C.byref(n_nodes)))
     return nodes[: n_nodes.value].copy(), t
 
 
 def set_bvh_builder(use_gpu, hip_library_path=None, device=0):
     """Choose the BVH builder behind World.from_path / from_buffers: the host restatement (default) or the device build
     (rpt_bvh_build_gpu).  Same output either way."""
-    L = lib()
-    L.rpt_host_set_bvh_builder.argtypes = [C.c_int, C.c_char_p, C.c_int]
-    _check(L.rpt_host_set_bvh_builder(1 if use_gpu else 0, os.fsencode(hip_library_path) if hip_library_path else None, device))
+    _check(lib().rpt_host_set_bvh_builder(1 if use_gpu else 0, os.fsencode(hip_library_path) if hip_library_path else None, device))

@@ -16,6 +16,83 @@ def _declared(header):
     return sorted(set(re.findall(r"\b(rpt_[a-z0-9_]+)\s*\(", text)))
 
 
+_SCALARS = {"int": C.c_int, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double}
+_RETURNS = {"void": None, "int": C.c_int, "uint32_t": C.c_uint32}
+
+
+def _is_pointer(t):
+    return t in (C.c_void_p, C.c_char_p) or (isinstance(t, type) and issubclass(t, C._Pointer))
+
+
+def _prototypes(*headers):
+    """{name: (return type, [parameter, ...])} of every function the headers declare, as C text without comments and parameter comments"""
+    text = "".join(open(os.path.join(ROOT, "include", "rpt", h)).read() for h in headers)
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+    found = {}
+    for ret, name, params in re.findall(r"([\w\s*]+?)\b(rpt_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        assert name not in found, name
+        params = [" ".join(p.split()) for p in params.split(",")]
+        found[name] = (" ".join(ret.split()), [] if params == ["void"] else params)
+    return found
+
+
+def _check_table_against_headers(table, *headers):
+    declared = _prototypes(*headers)
+    assert sorted(declared) == sorted(n for h in headers for n in _declared(h))       # the declaration pattern left no function out
+    assert sorted(table) == sorted(declared)                                           # every function has an entry, and nothing else has
+    bad = []
+    for name, (ret, params) in declared.items():
+        restype, argtypes = table[name]
+        ok = _is_pointer(restype) if "*" in ret else ret in _RETURNS and restype is _RETURNS[ret]
+        if not ok:
+            bad.append((name, "returns", ret, restype))
+        if len(argtypes) != len(params):
+            bad.append((name, "takes", params, argtypes))
+            continue
+        for p, t in zip(params, argtypes):
+            if "*" in p or "[" in p:
+                ok = _is_pointer(t)
+            else:
+                words = [w for w in p.split() if w != "const"]
+                ok = len(words) == 2 and t is _SCALARS.get(words[0])                   # "type name": any other by-value type fails here
+            if not ok:
+                bad.append((name, p, t))
+    assert not bad, bad
+
+
+def test_hip_prototypes_are_the_headers(hipmod):
+    """hip.PROTOTYPES against rpt.h + rpt_debug.h: every function, its parameter count, each parameter's kind (a pointer as a pointer type; int, uint32_t,
+    uint64_t, size_t, float, double as exactly that ctypes type) and the return type.  An integer argument without a prototype travels as a C int."""
+    _check_table_against_headers(hipmod.PROTOTYPES, "rpt.h", "rpt_debug.h")
+    assert hipmod.EXPORTS == sorted(hipmod.PROTOTYPES)
+
+
+def test_host_prototypes_are_the_header(rpt):
+    _check_table_against_headers(rpt.host.PROTOTYPES, "rpt_host.h")
+
+
+def test_bind_sets_prototypes_and_reports_every_missing_name(rpt):
+    """_ffi.bind against a stand-in for a loaded library that has two of four functions"""
+    import types
+    table = {"f_int": (C.c_int, [C.c_void_p, C.c_uint32]), "f_void": (None, []), "f_new": (C.c_char_p, [C.c_int]), "f_newer": (C.c_int, [C.c_float])}
+
+    def stand_in():
+        return types.SimpleNamespace(f_int=types.SimpleNamespace(), f_void=types.SimpleNamespace(restype=C.c_int), untouched=types.SimpleNamespace())
+
+    with pytest.raises(RuntimeError) as e:
+        rpt._ffi.bind(stand_in(), table, allow_missing=False)
+    assert "f_new" in str(e.value) and "f_newer" in str(e.value) and "f_int" not in str(e.value)
+    L = stand_in()
+    assert rpt._ffi.bind(L, table, allow_missing=True) is L
+    assert L.f_int.restype is C.c_int and L.f_int.argtypes == [C.c_void_p, C.c_uint32]
+    assert L.f_void.restype is None and L.f_void.argtypes == []
+    assert not hasattr(L, "f_new") and not hasattr(L, "f_newer") and not hasattr(L.untouched, "argtypes")
+    L = stand_in()
+    del table["f_new"], table["f_newer"]
+    assert rpt._ffi.bind(L, table, allow_missing=False) is L and L.f_int.argtypes == [C.c_void_p, C.c_uint32]
+
+
 def test_struct_layouts_match_reference(rpt):
     """shared_structs/src/lib.rs:12-191 sizes and offsets."""
     f = rpt._ffi

@@ -116,7 +116,6 @@ def _host_builder(rpt):
     def build(v, t, m):
         out = np.zeros(max(1, len(t)), ffi.LIGHT_PICK_DTYPE)
         n = C.c_size_t(0)
-        L.rpt_light_table_build.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         rc = L.rpt_light_table_build(v.ctypes.data, len(v), np.ascontiguousarray(t).ctypes.data, len(t), np.ascontiguousarray(m).ctypes.data, len(m),
                                      out.ctypes.data, len(out), C.byref(n))
         assert rc == 0

@@ -18,7 +18,6 @@ ffi = importlib.import_module("rust-path-tracer_amd._ffi")
 from scenes import scatter_scene  # noqa: E402
 
 L = host.lib()
-L.rpt_light_table_build.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
 for n in (100_000, 1_000_000):
     w = scatter_scene(n)
     v = np.ascontiguousarray(w.per_vertex["vertex"], np.float32).reshape(-1, 4)
