@@ -161,7 +161,8 @@ RPT_HD size_t rpt_pixel_index(uint32_t pxy, uint32_t width) { return (size_t)(px
 #define HIT_PENDING 0xfffffffeu   /* a ray is waiting for the traversal stage                                          */
 #define HIT_PARKED 0xfffffffdu    /* waiting in the sky / shadow queue                                                 */
 #define HIT_DONE 0xfffffffcu      /* sample finished, radiance final in rad.xyz; waits for its siblings */
-#define HIT_IDLE 0xfffffffbu      /* the slot has no sample left to take in this render call                           */
+#define HIT_DONE_ZERO 0xfffffffbu /* sample finished with radiance (+0, +0, +0) and nothing owed: its rad record was NOT written (DevQueues::implicit_zero) */
+#define HIT_IDLE 0xfffffffau      /* the slot has no sample left to take in this render call; every word below it is a triangle */
 
 /* ---- queues ---------------------------------------------------------------- */
 /* counter words: per iteration parity, "the traversal pass traced a ray" and
@@ -221,6 +222,10 @@ struct DevQueues {
     uint32_t sky_at_end;      /* a batch of known length: misses only END paths, so they wait in the queue for ONE sky launch after the last iteration */
     uint32_t sky_wide_limit;  /* up to this many queued misses the sky march runs 16 lanes per miss */
     uint32_t sky_shard_shift; /* log2 of the slots a workgroup of this call's shade stage owns (8, packed variant 11): slot s is pushed into shard (s >> this) % RPT_Q_SHARDS */
+    uint32_t implicit_zero;   /* a batch of known length without NEE, several slots per pixel: radiance changes only where a path ends and no slot owes a second
+                                 sample, so the rad record of a LIVE path would be sixteen zero bytes — it is not kept.  A path that ends with something added
+                                 writes its record and HIT_DONE, one that ends with nothing writes HIT_DONE_ZERO alone (k_shade.h, k_traverse.h last_finish,
+                                 k_sky, k_complete.h).  (Sits in what was the padding before ray_shards: no other field moves.) */
     unsigned long long *ray_shards;  /* RPT_STAT_SHARDS x RPT_STAT_STRIDE: extension rays traced */
     unsigned long long *host_ring;   /* mapped pinned host memory: (iteration + 1) << 32 | extension-queue size */
     uint32_t ring_mask;

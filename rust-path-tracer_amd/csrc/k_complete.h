@@ -33,23 +33,28 @@
 #define RPT_COMPLETE_PITCH 65u         /* float4 per tile row: 64 pixels + 1 (the transposing stores of a q_shift > 0 row would share a bank) */
 __host__ __device__ __forceinline__ uint32_t complete_rows(uint32_t S) { return S < RPT_COMPLETE_ROWS ? S : RPT_COMPLETE_ROWS; }
 __host__ __device__ __forceinline__ size_t complete_lds_bytes(uint32_t S, uint32_t q_shift) {
-    return q_shift == 0u ? 0u : (size_t)complete_rows(S) * RPT_COMPLETE_PITCH * sizeof(float4) + (size_t)S * sizeof(unsigned long long);
+    /* own_rad (a byte per lane and eight rows), and for q_shift > 0 the tile and row_done in front of it */
+    return (size_t)((S + 7u) / 8u) * RPT_WAVE + (q_shift == 0u ? 0u : (size_t)complete_rows(S) * RPT_COMPLETE_PITCH * sizeof(float4) + (size_t)S * sizeof(unsigned long long));
 }
 /* pass 1 of k_complete for G consecutive rows of the chunk (G loads in flight): the row's "finished" ballot goes to LDS for pass 2, the lane
- * takes the bits of its own pixel out of the rows that hold it */
+ * takes the bits of its own pixel out of the rows that hold it.
+ * A finished slot is HIT_DONE (its radiance record was written) or HIT_DONE_ZERO (radiance +0, nothing owed, NO record: k_common.h).  Pass 2 loads the record
+ * of the first kind only, so pass 1 also keeps which slots are HIT_DONE, in LDS: one byte per lane and eight rows, bit i = the lane's slot of row j0 + i
+ * (own_rad: the call's rows are one such group, G <= 8 and j0 a multiple of 8) — a lane of pass 2 looks at the rows in the lane it looked at them here. */
 template <uint32_t G>
-__device__ __forceinline__ void complete_status_rows(const DevState &st, uint32_t base, uint32_t j0, uint32_t lane, unsigned long long *row_done, uint32_t my_group,
-                                                     uint32_t my_shift, unsigned long long q_mask, uint32_t &n_done, uint32_t &n_busy, uint32_t &top) {
+__device__ __forceinline__ void complete_status_rows(const DevState &st, uint32_t base, uint32_t j0, uint32_t lane, unsigned long long *row_done, uint8_t *own_rad, uint32_t my_group, uint32_t my_shift, unsigned long long q_mask, uint32_t &n_done, uint32_t &n_busy, uint32_t &top) {
     const uint32_t gs = st.group_shift, qs = st.q_shift;
     uint32_t w[G];
 #pragma unroll
     for (uint32_t i = 0u; i < G; ++i) w[i] = __float_as_uint(st.hit[base + ((j0 + i) << 6) + lane].y);
+    uint32_t own = 0u;
 #pragma unroll
     for (uint32_t i = 0u; i < G; ++i) {
         const uint32_t row = j0 + i;
-        const bool done = w[i] == HIT_DONE;
+        const bool has_rad = w[i] == HIT_DONE, done = has_rad || w[i] == HIT_DONE_ZERO;
         const unsigned long long md = rpt_ballot(done), mb = rpt_ballot(!done && w[i] != HIT_IDLE);
         if (qs != 0u && lane == 0u) row_done[row] = md;               /* (q_shift = 0: pass 2 needs no masks, the finished slots of a pixel are its first n_done) */
+        own |= (has_rad ? 1u : 0u) << i;
         if ((row >> (gs - qs)) == my_group) {
             const uint32_t bits = (uint32_t)((md >> my_shift) & q_mask);
             n_done += (uint32_t)__popc(bits);
@@ -57,6 +62,7 @@ __device__ __forceinline__ void complete_status_rows(const DevState &st, uint32_
             if (bits != 0u) top = ((row & ((1u << (gs - qs)) - 1u)) << qs) + 32u - (uint32_t)__clz((int)bits);    /* (rows ascend: the last one wins) */
         }
     }
+    own_rad[(j0 >> 3) * RPT_WAVE + lane] = (uint8_t)own;
 }
 /* Row t of a block of `rows` samples starting at sample kb: for every pixel group, rows >> qs consecutive rows of the chunk. */
 __device__ __forceinline__ uint32_t complete_block_slot(const DevState &st, uint32_t base, uint32_t kb, uint32_t t, uint32_t rows, uint32_t rows_log, uint32_t lane) {
@@ -64,18 +70,31 @@ __device__ __forceinline__ uint32_t complete_block_slot(const DevState &st, uint
     const uint32_t g = t >> (rows_log - qs), jl = (kb >> qs) + (t & ((rows >> qs) - 1u));
     return base + (((g << (gs - qs)) | jl) << 6) + lane;
 }
-/* pass 2 of k_complete for G rows of such a block (G loads in flight): the radiance records into the tile [sample - kb][pixel], the finished slots of the
+/* which rows of such a block hold a HIT_DONE slot in this lane: bit t = row t of the block, gathered from own_rad (one pass over the block's rows ahead of
+ * its loads: a byte read per row inside complete_stage_rows kept eight more registers alive, 92 and 100 VGPRs) */
+__device__ __forceinline__ uint32_t complete_block_rad_bits(const DevState &st, uint32_t base, uint32_t kb, uint32_t rows, uint32_t rows_log, uint32_t lane, const uint8_t *own_rad) {
+    uint32_t bits = 0u;
+#pragma unroll 1
+    for (uint32_t t = 0u; t < rows; ++t) {
+        const uint32_t row = (complete_block_slot(st, base, kb, t, rows, rows_log, lane) - base) >> 6;
+        bits |= (((uint32_t)own_rad[(row >> 3) * RPT_WAVE + lane] >> (row & 7u)) & 1u) << t;
+    }
+    return bits;
+}
+/* pass 2 of k_complete for G rows of such a block (G loads in flight): the radiance records into the tile [sample - kb][pixel] — loaded by the HIT_DONE lanes
+ * of a row only (rad_bits; a row without one issues no load), (+0, +0, +0, owes 0) for every other lane — the finished slots of the
  * completing pixels that owe nothing more marked idle.  Returns (wave-uniform) whether some finished slot owes another sample (complete_restart_rows). */
 template <uint32_t G>
 __device__ __forceinline__ bool complete_stage_rows(const DevState &st, uint32_t base, uint32_t kb, uint32_t t0, uint32_t rows, uint32_t rows_log, uint32_t lane, float4 *tile,
-                                                    const unsigned long long *row_done, unsigned long long ok_mask) {
+                                                    const unsigned long long *row_done, uint32_t rad_bits, unsigned long long ok_mask) {
     float rx[G], ry[G], rz[G], rw[G];              /* (scalars: an array of float4 stays in scratch behind its 16-byte copies) */
     uint32_t slot_of[G];
     bool restart = false;
 #pragma unroll
     for (uint32_t i = 0u; i < G; ++i) {
         slot_of[i] = complete_block_slot(st, base, kb, t0 + i, rows, rows_log, lane);
-        const float4 r = st.rad[slot_of[i]];
+        float4 r = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0u));
+        if (((rad_bits >> (t0 + i)) & 1u) != 0u) r = st.rad[slot_of[i]];
         rx[i] = r.x; ry[i] = r.y; rz[i] = r.z; rw[i] = r.w;
     }
 #pragma unroll

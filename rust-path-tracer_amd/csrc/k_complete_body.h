@@ -5,14 +5,18 @@
  * RPT_COMPLETE_DIRECT_ROWS names the row helper of the build.  No include guard: k_complete.h defines the three macros around each inclusion.
  */
 /* pass 2 at q_shift = 0 (every shipped scene): row k of the chunk IS sample k of its 64 pixels with the lane's own pixel in its own lane — nothing to
- * transpose, no tile: G rows in flight, added in order straight from the registers; finished slots (k < n_done: the prefix) that owe nothing go idle. */
+ * transpose, no tile: G rows in flight, added in order straight from the registers; finished slots (k < n_done: the prefix) that owe nothing go idle.
+ * `rad_bits` (own_rad, pass 1): bit i says that the lane's slot k0 + i is HIT_DONE and has a radiance record; a finished slot without one (HIT_DONE_ZERO) adds
+ * (+0, +0, +0) and owes nothing.  Only the lanes with a record load: a row that has none issues no load. */
 template <uint32_t G>
-__device__ __forceinline__ bool RPT_COMPLETE_DIRECT_ROWS(const DevState &st, uint32_t base, uint32_t k0, uint32_t lane, bool ok, uint32_t n_done, float4 &acc RPT_MOM(, float4 &mom)) {
+__device__ __forceinline__ bool RPT_COMPLETE_DIRECT_ROWS(const DevState &st, uint32_t base, uint32_t k0, uint32_t lane, bool ok, uint32_t n_done, uint32_t rad_bits,
+                                                         float4 &acc RPT_MOM(, float4 &mom)) {
     float rx[G], ry[G], rz[G], rw[G];
     bool restart = false;
 #pragma unroll
     for (uint32_t i = 0u; i < G; ++i) {
-        const float4 r = st.rad[base + ((k0 + i) << 6) + lane];
+        float4 r = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0u));
+        if (ok && k0 + i < n_done && ((rad_bits >> i) & 1u) != 0u) r = st.rad[base + ((k0 + i) << 6) + lane];
         rx[i] = r.x; ry[i] = r.y; rz[i] = r.z; rw[i] = r.w;
     }
 #pragma unroll
@@ -35,6 +39,9 @@ __global__ __launch_bounds__(RPT_WAVE) void RPT_COMPLETE_KERNEL(DevState st, Dev
     const uint32_t gs = st.group_shift, qs = st.q_shift, S = 1u << gs, rows = complete_rows(S);
     float4 *tile = complete_lds;
     unsigned long long *row_done = reinterpret_cast<unsigned long long *>(complete_lds + rows * RPT_COMPLETE_PITCH);
+    /* which slots are HIT_DONE, whose radiance record pass 2 loads: per lane a byte for every eight rows (q_shift = 0 has neither tile nor row_done:
+     * complete_lds_bytes).  (In registers they are 256 bits per lane at S = 256, eight VGPRs, and k_complete_moments has 94 of the 96 it is held to.) */
+    uint8_t *own_rad = qs == 0u ? reinterpret_cast<uint8_t *>(complete_lds) : reinterpret_cast<uint8_t *>(row_done + S);
     const uint32_t lane = threadIdx.x, base = blockIdx.x << (6u + gs), pix = (blockIdx.x << 6) | lane;
     const bool in_image = pix < st.n_pixels;
     /* the rows that hold this lane's pixel (row >> (gs - qs) == its group), and where its Q slots sit in such a row's ballots */
@@ -44,12 +51,12 @@ __global__ __launch_bounds__(RPT_WAVE) void RPT_COMPLETE_KERNEL(DevState st, Dev
     bool nothing_to_do = false;
     if (S >= 8u) {
         for (uint32_t j0 = 0u; j0 < S && !nothing_to_do; j0 += 8u) {
-            complete_status_rows<8>(st, base, j0, lane, row_done, my_group, my_shift, q_mask, n_done, n_busy, top);
+            complete_status_rows<8>(st, base, j0, lane, row_done, own_rad, my_group, my_shift, q_mask, n_done, n_busy, top);
             /* between the iterations of a call whose slots take several samples most pixels have a sample in flight: nothing to do for the chunk */
             nothing_to_do = !final_pass && rpt_ballot(in_image && n_busy == 0u) == 0ull;
         }
-    } else if (S == 4u) complete_status_rows<4>(st, base, 0u, lane, row_done, my_group, my_shift, q_mask, n_done, n_busy, top);
-    else complete_status_rows<2>(st, base, 0u, lane, row_done, my_group, my_shift, q_mask, n_done, n_busy, top);
+    } else if (S == 4u) complete_status_rows<4>(st, base, 0u, lane, row_done, own_rad, my_group, my_shift, q_mask, n_done, n_busy, top);
+    else complete_status_rows<2>(st, base, 0u, lane, row_done, own_rad, my_group, my_shift, q_mask, n_done, n_busy, top);
     if (nothing_to_do) return;
     const bool ok = in_image && n_busy == 0u && n_done != 0u && top == n_done;
     if (final_pass && in_image && (n_busy != 0u || top != n_done)) {
@@ -69,19 +76,22 @@ __global__ __launch_bounds__(RPT_WAVE) void RPT_COMPLETE_KERNEL(DevState st, Dev
         uint32_t most = ok ? n_done : 0u;                                   /* the chunk's longest prefix (wave-uniform) */
         for (uint32_t o = 32u; o != 0u; o >>= 1) { const uint32_t other = (uint32_t)__shfl_xor((int)most, (int)o, RPT_WAVE); most = other > most ? other : most; }
         const uint32_t rows_log = 31u - (uint32_t)__clz((int)rows);
-        __syncthreads();                                                    /* row_done written */
+        __syncthreads();                                                    /* row_done, own_rad written */
         if (qs == 0u) {
             const uint32_t G = S >= 8u ? 8u : S;
             for (uint32_t k0 = 0u; k0 < most; k0 += G) {
                 bool restart;
-                if (G == 8u) restart = RPT_COMPLETE_DIRECT_ROWS<8>(st, base, k0, lane, ok, n_done, acc RPT_MOM(, mom));
-                else if (G == 4u) restart = RPT_COMPLETE_DIRECT_ROWS<4>(st, base, k0, lane, ok, n_done, acc RPT_MOM(, mom));
-                else restart = RPT_COMPLETE_DIRECT_ROWS<2>(st, base, k0, lane, ok, n_done, acc RPT_MOM(, mom));
+                const uint32_t rad_bits = own_rad[(k0 >> 3) * RPT_WAVE + lane];        /* (k0 is a multiple of 8, or 0 with G = S < 8) */
+                if (G == 8u) restart = RPT_COMPLETE_DIRECT_ROWS<8>(st, base, k0, lane, ok, n_done, rad_bits, acc RPT_MOM(, mom));
+                else if (G == 4u) restart = RPT_COMPLETE_DIRECT_ROWS<4>(st, base, k0, lane, ok, n_done, rad_bits, acc RPT_MOM(, mom));
+                else restart = RPT_COMPLETE_DIRECT_ROWS<2>(st, base, k0, lane, ok, n_done, rad_bits, acc RPT_MOM(, mom));
                 if (restart) {                                              /* (never in the one completion of a batch of known length) */
 #pragma unroll 1
                     for (uint32_t k = k0; k < k0 + G; ++k) {
-                        const uint32_t slot = base + (k << 6) + lane, todo = __float_as_uint(st.rad[slot].w);
-                        if (ok && k < n_done && todo != 0u) {
+                        const uint32_t slot = base + (k << 6) + lane;
+                        const bool has_rad = ok && k < n_done && ((rad_bits >> (k - k0)) & 1u) != 0u;
+                        const uint32_t todo = has_rad ? __float_as_uint(st.rad[slot].w) : 0u;
+                        if (todo != 0u) {
                             start_path(st, cfg, slot, new_n + k, rs.y, todo - 1u);      /* slot k takes the samples k, k + S, ... */
                             started = true;
                         }
@@ -92,10 +102,11 @@ __global__ __launch_bounds__(RPT_WAVE) void RPT_COMPLETE_KERNEL(DevState st, Dev
         for (uint32_t kb = 0u; kb < most; kb += rows) {
             /* the rows that hold samples [kb, kb + rows) of all 64 pixels: for every pixel group, rows >> qs consecutive rows */
             bool restart = false;
+            const uint32_t rad_bits = complete_block_rad_bits(st, base, kb, rows, rows_log, lane, own_rad);
             if (rows >= 8u) {
-                for (uint32_t t0 = 0u; t0 < rows; t0 += 8u) restart |= complete_stage_rows<8>(st, base, kb, t0, rows, rows_log, lane, tile, row_done, ok_mask);
-            } else if (rows == 4u) restart = complete_stage_rows<4>(st, base, kb, 0u, rows, rows_log, lane, tile, row_done, ok_mask);
-            else restart = complete_stage_rows<2>(st, base, kb, 0u, rows, rows_log, lane, tile, row_done, ok_mask);
+                for (uint32_t t0 = 0u; t0 < rows; t0 += 8u) restart |= complete_stage_rows<8>(st, base, kb, t0, rows, rows_log, lane, tile, row_done, rad_bits, ok_mask);
+            } else if (rows == 4u) restart = complete_stage_rows<4>(st, base, kb, 0u, rows, rows_log, lane, tile, row_done, rad_bits, ok_mask);
+            else restart = complete_stage_rows<2>(st, base, kb, 0u, rows, rows_log, lane, tile, row_done, rad_bits, ok_mask);
             __syncthreads();
             const uint32_t here = most - kb < rows ? most - kb : rows;
             for (uint32_t kl = 0u; kl < here; ++kl) {

@@ -99,5 +99,12 @@ __device__ __forceinline__ void finish_in_side_stage(const DevState &st, const D
         st.hit[slot] = make_float2(0.0f, __uint_as_float(HIT_DONE));
     }
 }
+/* The same where live paths keep no radiance record (DevQueues::implicit_zero: several slots per pixel, nothing owed): a path that ends with `added` on top of
+ * its zero radiance writes the record it never had.  The sum with +0.0 stays: it turns a -0.0 term into the +0.0 that loading the zeros and adding gave. */
+__device__ __forceinline__ void finish_from_zero(const DevState &st, uint32_t slot, F3 added) {
+    const F3 radiance = f3s(0.0f) + added;
+    st.rad[slot] = make_float4(radiance.x, radiance.y, radiance.z, __uint_as_float(0u));
+    st.hit[slot] = make_float2(0.0f, __uint_as_float(HIT_DONE));
+}
 
 #endif /* RPT_K_PATH_H */

@@ -193,6 +193,9 @@ __device__ __forceinline__ void shade_slot(const DevScene &sc, const DevState &s
                                            uint32_t n_samples, bool &elided /* an NEE evaluation whose shadow ray decides nothing: not queued */,
                                            bool last_iteration /* wave-uniform: every path of this launch is at its last bounce and has a radiance record */) {
     const uint32_t hit_tri = __float_as_uint(hw.y);
+    /* wave-uniform: live paths of this batch keep no radiance record (DevQueues::implicit_zero — their radiance is +0 and they owe nothing): a continuing path
+     * writes none, a path that ends with nothing added ends as HIT_DONE_ZERO, one that ends on an emitter's front writes 0 + its term and never loads */
+    const bool zero_rad = NEE == RPT_NEE_NONE && q.implicit_zero != 0u;
     if (NEE == RPT_NEE_NONE && last_iteration && active && hit_tri != HIT_MISS) {
         /* The last bounce of every path of this launch, without NEE (see `last` below): all the stage can still do for a hit is add the emission of a
          * front-facing emitter (lib.rs:86-100) and end the path — so it reads the hit word it was handed, the triangle's material index and emission, and
@@ -202,7 +205,14 @@ __device__ __forceinline__ void shade_slot(const DevScene &sc, const DevState &s
         const uint32_t m = __float_as_uint(sc.tri_shade[4u * tri_index + 2u].w);
         const float4 e4 = TEXTURED ? sc.materials[6u * m] : sc.mat_lite[2u * m];
         const bool emits = (e4.x != 0.0f || e4.y != 0.0f || e4.z != 0.0f) && (hit_tri >> 31) == 0u;
-        if (emits || st.group_shift == 0u) {
+        if (zero_rad) {
+            if (emits) {
+                const float4 tf = st.thr[slot];
+                finish_from_zero(st, slot, mask_nan3(f3(tf.x, tf.y, tf.z) * f3(e4.x, e4.y, e4.z)));
+            } else {
+                st.hit[slot] = make_float2(0.0f, __uint_as_float(HIT_DONE_ZERO));
+            }
+        } else if (emits || st.group_shift == 0u) {
             const float4 r4 = st.rad[slot];
             F3 radiance = f3(r4.x, r4.y, r4.z);
             if (emits) {
@@ -225,7 +235,7 @@ __device__ __forceinline__ void shade_slot(const DevScene &sc, const DevState &s
             st.hit[slot] = make_float2(0.0f, __uint_as_float(HIT_PARKED));
             if (first) {                             /* k_sky reads the path state */
                 st.thr[slot] = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(RPT_FRESH_FLAGS));
-                st.rad[slot] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(first_path_todo(st, slot, n_samples)));
+                if (!zero_rad) st.rad[slot] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(first_path_todo(st, slot, n_samples)));
             }
         } else {
             const float4 tf = first ? make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(RPT_FRESH_FLAGS)) : st.thr[slot];
@@ -235,9 +245,12 @@ __device__ __forceinline__ void shade_slot(const DevScene &sc, const DevState &s
             F3 radiance = f3s(0.0f);
             uint32_t todo = 0u;
             bool rad_loaded = false;
+            bool added = false;                      /* zero_rad: something was added to the path's zero radiance */
             auto load_rad = [&]() {
                 if (!rad_loaded) {
-                    if (first) {
+                    if (zero_rad) {
+                        /* radiance 0, nothing owed */
+                    } else if (first) {
                         todo = first_path_todo(st, slot, n_samples);     /* radiance 0 */
                     } else {
                         const float4 r4 = st.rad[slot];
@@ -267,6 +280,7 @@ __device__ __forceinline__ void shade_slot(const DevScene &sc, const DevState &s
                 } else if (!nee || bounce == 0u || last_spec) {                          /* :97-100 */
                     load_rad();
                     radiance = radiance + mask_nan3(throughput * emissive);
+                    added = true;
                     done = true;
                 } else if (NEE == RPT_NEE_MIS) {                                         /* :104-108, last lobe is diffuse here */
                     /* last_light_sample / last_bsdf_sample (lib.rs:59-60): the light sample is carried as the table entry it
@@ -522,13 +536,15 @@ __device__ __forceinline__ void shade_slot(const DevScene &sc, const DevState &s
                 }
             }
 
-            if (done && !emit_shadow) {
+            if (zero_rad && done && !added) {
+                st.hit[slot] = make_float2(0.0f, __uint_as_float(HIT_DONE_ZERO));      /* a back-facing emitter, the last bounce, the roulette: nothing to record */
+            } else if (done && !emit_shadow) {
                 /* the path ends here with nothing pending: one slot per pixel — accumulated and restarted on the spot; several —
                  * parked as HIT_DONE for k_complete */
                 load_rad();
                 finish_in_side_stage(st, cfg, slot, radiance, todo);
             } else {
-                if (first) {                         /* the path goes on (or waits for its shadow ray): its radiance record begins here */
+                if (first && !zero_rad) {            /* the path goes on (or waits for its shadow ray): its radiance record begins here */
                     load_rad();
                     st.rad[slot] = make_float4(radiance.x, radiance.y, radiance.z, __uint_as_float(todo));
                 }

@@ -145,6 +145,9 @@ __global__ __launch_bounds__(RPT_BLOCK) void k_sky(DevScene sc, DevState st, Dev
      * 133 instead of 92 VGPRs (its constants are hoisted), so scenes with many misses keep one thread per entry; the host
      * picks the variant from the share of samples that ended in the sky so far (refresh_device_stats). */
     const uint32_t stride = STRIDED ? gridDim.x * RPT_BLOCK : 0u;
+    /* a miss of a batch that keeps no radiance record of a live path (DevQueues::implicit_zero) starts from zero radiance and owes nothing; it ends with
+     * something added, so its record and HIT_DONE are written as ever */
+    const bool zero_rad = q.implicit_zero != 0u;
     if (cfg.c.has_skybox == 0u && positions <= q.sky_wide_limit) {
         /* few misses: 16 lanes per miss (block-uniform branch) */
         for (uint32_t m = i >> 4; m < positions; m += stride >> 4) {
@@ -159,7 +162,7 @@ __global__ __launch_bounds__(RPT_BLOCK) void k_sky(DevScene sc, DevState st, Dev
             F3 ro = f3(ra.x, ra.y, ra.z), rd = f3(ra.w, rb.x, rb.y);
             F3 sky = sky_scatter_wide(cfg.c.sun_direction, ro, rd, j, g0);
             if (j == 0u) {
-                const float4 tf = st.thr[slot], r4 = st.rad[slot];
+                const float4 tf = st.thr[slot], r4 = zero_rad ? make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0u)) : st.rad[slot];
                 F3 throughput = f3(tf.x, tf.y, tf.z), radiance = f3(r4.x, r4.y, r4.z);
                 radiance = radiance + throughput * sky;                                       /* lib.rs:69 */
                 finish_in_side_stage(st, cfg, slot, radiance, __float_as_uint(r4.w));
@@ -177,7 +180,7 @@ __global__ __launch_bounds__(RPT_BLOCK) void k_sky(DevScene sc, DevState st, Dev
         float4 ra = st.ray_a[slot];
         float2 rb = st.ray_b[slot];
         F3 ro = f3(ra.x, ra.y, ra.z), rd = f3(ra.w, rb.x, rb.y);
-        const float4 tf = st.thr[slot], r4 = st.rad[slot];
+        const float4 tf = st.thr[slot], r4 = zero_rad ? make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0u)) : st.rad[slot];
         F3 throughput = f3(tf.x, tf.y, tf.z), radiance = f3(r4.x, r4.y, r4.z);
         if (cfg.c.has_skybox == 0u) {
             radiance = radiance + throughput * sky_scatter(cfg.c.sun_direction, ro, rd);      /* lib.rs:69 */

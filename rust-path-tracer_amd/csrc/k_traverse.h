@@ -936,11 +936,14 @@ __global__ __launch_bounds__(THREADS) void k_traverse_nearest_stream(DevScene sc
     uint32_t traced = 0u;                                      /* wave-uniform */
     /* LAST with several slots per pixel: the walk ENDS its paths — no shade launch follows it (rpt_hip.hip launch_iteration).  Where a lane writes its result it does
      * what the shade stage's last iteration did with it (k_shade.h shade_slot, `last_iteration`):
-     *   a hit-or-miss lane that hit: not an emitter, the sample is finished with the radiance it has — HIT_DONE;
-     *   a lane that walked to the end and hit: the emission of a front-facing emitter is added (lib.rs:86-100), then HIT_DONE;
+     *   a hit-or-miss lane that hit: not an emitter, the sample is finished with the zero radiance it has — HIT_DONE_ZERO;
+     *   a lane that walked to the end and hit: the front of an emitter adds its emission (lib.rs:86-100) — the radiance record is written, HIT_DONE; any other
+     *   hit is HIT_DONE_ZERO;
      *   a miss: the slot goes to the sky queue (last_park below) and waits there as HIT_PARKED for the batch's one k_sky launch.
+     * Such a batch keeps no radiance record of a live path (DevQueues::implicit_zero: the launch is LAST only in a batch of known length without NEE, so the
+     * flag says "several slots per pixel" here): nothing is read, 0 + the term is written.
      * With one slot per pixel (done_here false) the hit record is written for the shade launch that follows, as in every other launch. */
-    const bool done_here = LAST && st.group_shift != 0u;
+    const bool done_here = LAST && q.implicit_zero != 0u;
     auto last_finish = [&](uint32_t s, const HitRecord &r, uint32_t stopped) -> bool {      /* true: a miss, to be parked */
         if (!done_here) {
             st.hit[s] = make_float2(r.t, __uint_as_float(r.tri));
@@ -951,14 +954,12 @@ __global__ __launch_bounds__(THREADS) void k_traverse_nearest_stream(DevScene sc
             const uint32_t m = __float_as_uint(sc.tri_shade[4u * (r.tri & 0x7fffffffu) + 2u].w);
             const float4 e4 = sc.textured != 0u ? sc.materials[6u * m] : sc.mat_lite[2u * m];
             if ((e4.x != 0.0f || e4.y != 0.0f || e4.z != 0.0f) && (r.tri >> 31) == 0u) {
-                float4 r4 = st.rad[s];
                 const float4 tf = st.thr[s];
-                const F3 radiance = f3(r4.x, r4.y, r4.z) + mask_nan3(f3(tf.x, tf.y, tf.z) * f3(e4.x, e4.y, e4.z));
-                r4.x = radiance.x; r4.y = radiance.y; r4.z = radiance.z;
-                st.rad[s] = r4;                                 /* (samples owed: kept) */
+                finish_from_zero(st, s, mask_nan3(f3(tf.x, tf.y, tf.z) * f3(e4.x, e4.y, e4.z)));
+                return false;
             }
         }
-        st.hit[s] = make_float2(0.0f, __uint_as_float(HIT_DONE));
+        st.hit[s] = make_float2(0.0f, __uint_as_float(HIT_DONE_ZERO));
         return false;
     };
     /* The sky queue's reservations, by the whole wave (every lane calls it, converged).  A slot is reserved in the shard the shade stage of this batch uses for

@@ -145,7 +145,7 @@ int alloc_pixel_state(rpt_ctx *c) {
     q.sky_wide_limit = (uint32_t)std::min<size_t>(c->n_slots / 16, c->sky_wide_cfg);
     /* 1 = shade misses in the iteration that found them.  (Letting them pile up removed most of the near-empty sky launches on closed scenes, but the
      * parked pixels finish later and lengthen the tail: DarkCornell 3650 Mrays/s deferred vs 3928 eager in round 1; the knob went in round 6.) */
-    q.sky_threshold = 1u; q.sky_at_end = 0u; q.known_length = 0u;
+    q.sky_threshold = 1u; q.sky_at_end = 0u; q.known_length = 0u; q.implicit_zero = 0u;
     c->has_state = true;
     return RPT_OK;
 }
@@ -597,6 +597,10 @@ static int render_impl(rpt_ctx *c, uint32_t n_samples, bool allow_async) {
      * wait in the queue for ONE sky launch after the last iteration (three launches less per batch) */
     c->queues.sky_at_end = known_iterations != 0 ? 1u : 0u;
     c->queues.known_length = known_iterations != 0 ? 1u : 0u;
+    /* Without NEE a path's radiance changes only where the path ends, and in a batch of known length no slot owes a second sample (k_path.h first_path_todo is 0
+     * for 1 <= n_samples - k <= S): the radiance record of a live path would be sixteen zero bytes.  With several slots per pixel — where a finished sample waits
+     * for k_complete — it is not kept: the stages write it only for a path that ends with something added (k_common.h HIT_DONE_ZERO) */
+    c->queues.implicit_zero = (known_iterations != 0 && c->cfg.nee_mode == RPT_NEE_NONE && c->group_shift != 0u) ? 1u : 0u;
     /* the shard of the sky queue a slot is pushed into: by its workgroup of the shade stage, whichever variant this call launches */
     c->queues.sky_shard_shift = c->shade_compact ? 11u : 8u;
     static_assert(RPT_BLOCK == 1 << 8 && RPT_BLOCK * RPT_SHADE_ROUNDS == 1 << 11, "sky_shard_shift: slots per workgroup of k_shade");

@@ -87,7 +87,7 @@ bool launch_nearest(rpt_ctx *c, uint32_t iteration, bool last_without_nee = fals
         const float *cam = c->cfg.c.cam_position;
         if (last_without_nee && c->scene.last_emit_n <= RPT_LAST_EMIT_MAX) {
             k_traverse_nearest_stream<16, LDS_THREADS, RPT_NEAREST_LAST><<<grid, LDS_THREADS, lds_bytes + (size_t)c->scene.last_flip_vecs * sizeof(float4), s>>>(c->scene, c->state, c->queues, iteration, span, 0.0f, 0.0f, 0.0f, c->cfg, 0u, stats);
-            return c->state.group_shift != 0u;
+            return c->queues.implicit_zero != 0u;            /* (the kernel's done_here: last_without_nee and several slots per pixel) */
         }
         if (camera_rays)
             k_traverse_nearest_stream<16, LDS_THREADS, RPT_NEAREST_FIRST><<<grid, LDS_THREADS, lds_bytes, s>>>(c->scene, c->state, c->queues, iteration, span, cam[0], cam[1], cam[2], c->cfg, start_paths ? c->call_samples : 0u, stats);

@@ -2,7 +2,8 @@
 `--kernel-trace --stats` averages over every launch of the process — set-up and warm-up batches at a cold clock, the
 read-back loop — while bench.py's `roofline.avg_launch_ms` covers the timed region only; this is the like-for-like figure.
 A batch starts at a k_generate_first; bench.py runs 2 set-up + W warm-up batches, then the K timed ones.
-usage: trace_region.py KERNEL_TRACE_CSV --warmup W --steps K"""
+usage: trace_region.py KERNEL_TRACE_CSV --warmup W --steps K [--by-position]
+--by-position: a kernel launched several times per batch is listed once per position ("k_shade<...> #0": the first shade launch of every batch)."""
 import argparse, csv, collections
 
 ap = argparse.ArgumentParser()
@@ -10,19 +11,25 @@ ap.add_argument("trace")
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--steps", type=int, default=8)
 ap.add_argument("--setup", type=int, default=2)
+ap.add_argument("--by-position", action="store_true")
 a, _ = ap.parse_known_args()
 rows = []
 with open(a.trace) as f:
     for r in csv.DictReader(f):
         rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]))
 rows.sort()
+seen = {}
 batch, first, last = -1, a.setup + a.warmup, a.setup + a.warmup + a.steps
 acc = collections.OrderedDict()
 for s, e, name in rows:
     if name.startswith("k_generate_first"):
         batch += 1
+        seen = {}
     if first <= batch < last:
         short = name.split("(")[0]
+        if a.by_position:
+            seen[short] = seen.get(short, -1) + 1
+            short = f"{short} #{seen[short]}"
         n, t = acc.get(short, (0, 0))
         acc[short] = (n + 1, t + (e - s))
 print(f"# batches {first}..{last - 1} of the run (after {a.setup} set-up + {a.warmup} warm-up): the {a.steps} timed ones")
