@@ -163,7 +163,8 @@ class Oracle:
         return out
 
     def bsdf(self, kind, items):
-        """Lambertian / Glass (kernels/src/bsdf.rs:46-176) restated: (n, 16) float32 in -> (n, 8) out (see oracle_bsdf)."""
+        """Lambertian / Glass (kernels/src/bsdf.rs:46-176) restated, kinds 0-3, and the PBR BSDF of trace_pixel itself (bsdf.rs:185-387), kinds 4 sample,
+        5 evaluate, 6 pdf: (n, 16) float32 in -> (n, 8) out (the layouts are beside oracle_bsdf)."""
         items = np.ascontiguousarray(items, np.float32).reshape(-1, 16)
         out = np.zeros((len(items), 8), np.float32)
         rc = self.lib.oracle_bsdf(C.c_int(kind), C.c_size_t(len(items)), _p(items), _p(out))

@@ -491,8 +491,9 @@ struct PBR {
         return evaluate_specular_fast(view_direction, normal, sample_direction, cos_theta, d_term, specular_weight, ks);
     }
 
-    BSDFSample sample(V3 view_direction, V3 normal, RngState &rng) const {
-        V3 rng_sample = rng.gen_r3();
+    BSDFSample sample(V3 view_direction, V3 normal, RngState &rng) const { return sample_with(view_direction, normal, rng.gen_r3()); }
+    /* bsdf.rs:272-334 after its gen_r3(): the random numbers as an argument, so that the test hook oracle_bsdf can feed the same function any r */
+    BSDFSample sample_with(V3 view_direction, V3 normal, V3 rng_sample) const {
         float specular_weight = specular_weight_of(view_direction, normal);
         V3 sampled_direction;
         Lobe sampled_lobe;
@@ -1198,8 +1199,44 @@ float oracle_lds(uint32_t n, uint32_t dimension, uint32_t offset, uint32_t *out_
  * SURVEY.md 8f N4), restated for completeness of the kernels crate: one item = view(3) normal(3) r(3) albedo(3) ior
  * roughness pad(2) -> pdf, lobe (u32 bits), spectrum(3), direction(3).
  * kind 0: Lambertian::sample   1: Glass::sample   2: Lambertian::{evaluate, pdf} with sample_direction = r
- * kind 3: Glass::{evaluate, pdf} with lobe = (u32) r.x */
+ * kind 3: Glass::{evaluate, pdf} with lobe = (u32) r.x
+ * The PBR BSDF every image goes through (bsdf.rs:185-387), by the very get_pbr_bsdf / PBR::{sample, evaluate, pdf} trace_pixel calls, untextured; the
+ * same 16 floats read as view(3) normal(3) r(3) albedo(3) metallic roughness specular_weight_clamp(2) (metallic in the ior slot, the clamp in the pad):
+ * kind 4: PBR::sample with r as the three random numbers  -> pdf, lobe, spectrum(3), direction(3)
+ * kind 5: PBR::evaluate with sample_direction = r          -> 0, 0, spectrum of the diffuse lobe(3), spectrum of the specular lobe(3)
+ * kind 6: PBR::pdf with sample_direction = r               -> pdf of the diffuse lobe, 0, pdf of the specular lobe, 0... */
+static void oracle_pbr_item(int kind, const float *p, float *o) {
+    rpt_material_data material;
+    rpt_tracing_config config;
+    std::memset(&material, 0, sizeof(material));
+    std::memset(&config, 0, sizeof(config));
+    material.albedo[0] = p[9]; material.albedo[1] = p[10]; material.albedo[2] = p[11];
+    material.metallic[0] = p[12];
+    material.roughness[0] = p[13];
+    config.specular_weight_clamp[0] = p[14]; config.specular_weight_clamp[1] = p[15];
+    const Image none{nullptr, 0, 0};
+    const PBR bsdf = get_pbr_bsdf(config, material, V2{0.0f, 0.0f}, none);
+    const V3 view = xyz(p), normal = xyz(p + 3), r = xyz(p + 6);
+    for (int k = 0; k < 8; ++k) o[k] = 0.0f;
+    if (kind == 4) {
+        BSDFSample s = bsdf.sample_with(view, normal, r);
+        o[0] = s.pdf; o[1] = rptm::u2f((uint32_t)s.sampled_lobe);
+        o[2] = s.spectrum.x; o[3] = s.spectrum.y; o[4] = s.spectrum.z;
+        o[5] = s.sampled_direction.x; o[6] = s.sampled_direction.y; o[7] = s.sampled_direction.z;
+    } else if (kind == 5) {
+        V3 d = bsdf.evaluate(view, normal, r, DiffuseReflection), s = bsdf.evaluate(view, normal, r, SpecularReflection);
+        o[2] = d.x; o[3] = d.y; o[4] = d.z; o[5] = s.x; o[6] = s.y; o[7] = s.z;
+    } else {
+        o[0] = bsdf.pdf(view, normal, r, DiffuseReflection);
+        o[2] = bsdf.pdf(view, normal, r, SpecularReflection);
+    }
+}
 int oracle_bsdf(int kind, size_t n, const float *in, float *out) {
+    if (kind >= 4 && kind <= 6) {
+        for (size_t i = 0; i < n; ++i) oracle_pbr_item(kind, in + 16 * i, out + 8 * i);
+        return 0;
+    }
+    if (kind < 0 || kind > 6) return -1;
     auto cartesian = [](V3 up, V3 &right, V3 &forward) {                     /* util.rs:34-40 */
         V3 temp_vec = normalize(cross(up, v3(0.1f, 0.5f, 0.9f)));
         right = normalize(cross(temp_vec, up));

@@ -4,7 +4,7 @@
  * and util.rs:233-236 fresnel_schlick_scalar).  SURVEY.md 8f N4: dead code in the reference (get_pbr_bsdf is the only
  * constructor trace_pixel calls, lib.rs:144), kept here in the reference's operation order so that a material flag can
  * select them the day the reference does; reachable today through the rpt_debug_bsdf test hook only, which
- * tests/test_gpu_bsdf_extra.py compares with the oracle's restatement bit for bit.
+ * tests/test_bsdf_extra.py compares with the oracle's restatement bit for bit.
  */
 #ifndef RPT_K_BSDF_EXTRA_H
 #define RPT_K_BSDF_EXTRA_H

@@ -381,3 +381,113 @@ def pack_rects(n_textures, atlas=4096):
         q.extend([(x, y, hw, hh), (x + hw, y, hw, hh), (x, y + hh, hw, hh), (x + hw, y + hh, hw, hh)])
     leafs = sorted(q, key=lambda r: -r[2])          # stable, by width descending
     return leafs[:n_textures]
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------------------------
+# Probe scenes of the float64 second opinion (tests/f64_ref.py): at most eight triangles, untextured, built as World objects directly.  The quads
+# reach far outside every view used, and the lamp sits well inside the frame, so that few samples decide anything by a hair.
+# ----------------------------------------------------------------------------------------------------------------------------------------------------
+PROBE_MATERIALS = {            # name -> (roughness, metallic, albedo); "zero" has an albedo channel of exactly 0
+    "r0.5_m0": (0.5, 0.0, (0.8, 0.6, 0.4)), "r1_m0_zero": (1.0, 0.0, (0.7, 0.0, 0.9)), "r0.05_m1": (0.05, 1.0, (0.9, 0.7, 0.5)),
+    "r1e-3_m0.5": (1e-3, 0.5, (0.6, 0.8, 0.7)), "r0_m1": (0.0, 1.0, (1.0, 0.8, 0.6))}
+PROBE_VIEWS = {                # about 45 degrees onto the slab, and grazing: the camera looks 1 degree below the horizon from a height of 0.25
+    "45": dict(cam_position=(0.0, 2.0, 0.0, 0.0), cam_rotation=(0.7853982, 0.0, 0.0, 0.0)),
+    "grazing": dict(cam_position=(0.0, 0.25, 0.0, 0.0), cam_rotation=(0.01745329, 0.0, 0.0, 0.0)),
+    "corner": dict(cam_position=(0.3, 1.5, -2.0, 0.0), cam_rotation=(0.35, 0.1, 0.0, 0.0))}
+
+
+def _probe_quad(v, n, t, corners, normal, material):
+    k = len(v)
+    v += [list(map(float, c)) for c in corners]
+    n += [list(map(float, normal))] * 4
+    t += [[k, k + 1, k + 2, material], [k, k + 2, k + 3, material]]
+
+
+def _probe_world(v, n, t, materials):
+    rpt = importlib.import_module("rust-path-tracer_amd")
+    m = np.zeros(len(materials), rpt._ffi.MATERIAL_DTYPE)
+    for i, (roughness, metallic, albedo, emissive) in enumerate(materials):
+        m["albedo"][i] = list(albedo) + [1.0]
+        m["roughness"][i, :] = roughness
+        m["metallic"][i, :] = metallic
+        m["emissive"][i] = list(emissive) + [1.0 if any(emissive) else 0.0]
+    return rpt.World.from_buffers(np.array(v, np.float32), np.array(n, np.float32), None, np.array(t, np.uint32), m)
+
+
+_LAMP = (1.0, 0.0, (0.0, 0.0, 0.0), (10.0, 9.0, 8.0))
+
+
+def probe_slab(material, lamp=False):
+    """One quad of 200 x 200 in the plane y = 0, normal up, placed so that its diagonal (the two triangles' common edge) stays outside both views;
+    with lamp, ONE emissive triangle 1 above it whose front faces the slab (emitters are single sided: the 45-degree camera, above it, sees its black
+    back; the grazing camera, below it, its front)."""
+    v, n, t = [], [], []
+    roughness, metallic, albedo = PROBE_MATERIALS[material]
+    _probe_quad(v, n, t, [(-100, 0, -160), (-100, 0, 40), (100, 0, 40), (100, 0, -160)], (0, 1, 0), 0)
+    materials = [(roughness, metallic, albedo, (0.0, 0.0, 0.0))]
+    if lamp:
+        k = len(v)
+        v += [[-0.6, 1.0, 1.4], [0.6, 1.0, 1.4], [0.0, 1.0, 2.4]]
+        n += [[0.0, -1.0, 0.0]] * 3
+        t += [[k, k + 1, k + 2, 1]]
+        materials.append(_LAMP)
+    return _probe_world(v, n, t, materials)
+
+
+def probe_corner():
+    """A floor and a wall of two different materials, a lamp above the floor and a small plate between them that shadows part of the floor: seven
+    triangles.  Paths bounce between floor and wall; the rest of the sphere is sky."""
+    v, n, t = [], [], []
+    _probe_quad(v, n, t, [(-60, 0, -60), (-60, 0, 3), (60, 0, 3), (60, 0, -60)], (0, 1, 0), 0)
+    _probe_quad(v, n, t, [(-60, 0, 3), (-60, 60, 3), (60, 60, 3), (60, 0, 3)], (0, 0, -1), 1)
+    _probe_quad(v, n, t, [(-0.35, 0.9, 1.3), (-0.35, 0.9, 1.9), (0.45, 0.9, 1.9), (0.45, 0.9, 1.3)], (0, 1, 0), 0)
+    k = len(v)
+    v += [[-0.7, 2.0, 0.9], [0.7, 2.0, 0.9], [0.0, 2.0, 2.2]]
+    n += [[0.0, -1.0, 0.0]] * 3
+    t += [[k, k + 1, k + 2, 2]]
+    return _probe_world(v, n, t, [(0.6, 0.0, (0.7, 0.6, 0.5), (0.0, 0.0, 0.0)), (0.3, 0.8, (0.9, 0.5, 0.3), (0.0, 0.0, 0.0)), _LAMP])
+
+
+def _probe_cases():
+    cases = {}
+    for material in PROBE_MATERIALS:
+        for view in ("45", "grazing"):
+            cases[f"sky-{material}-{view}"] = dict(scene=("slab", material, False), view=view, config=dict(nee=0, min_bounces=3, max_bounces=3))
+    lamp = dict(min_bounces=3, max_bounces=3)
+    for nee in (0, 1, 2):
+        for view in ("45", "grazing"):
+            cases[f"lamp-r0.5_m0-{view}-nee{nee}"] = dict(scene=("slab", "r0.5_m0", True), view=view, config=dict(nee=nee, **lamp))
+    for material in list(PROBE_MATERIALS)[1:]:
+        cases[f"lamp-{material}-45-nee1"] = dict(scene=("slab", material, True), view="45", config=dict(nee=1, **lamp))
+    cases["lamp-r0.5_m0-45-nee1-clamp01"] = dict(scene=("slab", "r0.5_m0", True), view="45", config=dict(nee=1, specular_weight_clamp=(0.0, 1.0), **lamp))
+    cases["lamp-r0.5_m0-45-nee1-50x37"] = dict(scene=("slab", "r0.5_m0", True), view="45", config=dict(nee=1, **lamp), size=(50, 37))
+    cases["sky-r0.05_m1-45-clamp01"] = dict(scene=("slab", "r0.05_m1", False), view="45",
+                                            config=dict(nee=0, min_bounces=3, max_bounces=3, specular_weight_clamp=(0.0, 1.0)))
+    cases["sky-r1e-3_m0.5-grazing-50x37"] = dict(scene=("slab", "r1e-3_m0.5", False), view="grazing", config=dict(nee=0, min_bounces=3, max_bounces=3),
+                                                 size=(50, 37))
+    # Roulette matters where min_bounces < max_bounces - 1: a draw after the last bounce reaches no radiance.  With NEE a bounce takes up to 8 of the
+    # sequence's 31 dimensions, so max_bounces = 3 is the longest NEE path the reference's table (and rpt_set_config) allows with min_bounces = 0.
+    # Four NEE bounces fit only with min_bounces = 2 (31 dimensions; min_bounces = 1 would need 32): that case covers the full dimension budget and
+    # MIS at depth 4, NOT roulette, whose one draw comes after its last bounce.  Roulette with its 1 / prob is covered by corner-nee1-3bounces and
+    # by the five-bounce cases, which run without NEE, the lamp found by the BSDF alone.
+    cases["corner-nee1-3bounces"] = dict(scene=("corner",), view="corner", config=dict(nee=1, min_bounces=0, max_bounces=3))
+    cases["corner-nee1-4bounces-min2"] = dict(scene=("corner",), view="corner", config=dict(nee=1, min_bounces=2, max_bounces=4))
+    cases["corner-nee0-5bounces-50x37"] = dict(scene=("corner",), view="corner", config=dict(nee=0, min_bounces=0, max_bounces=5), size=(50, 37))
+    cases["corner-nee0-5bounces"] = dict(scene=("corner",), view="corner", config=dict(nee=0, min_bounces=0, max_bounces=5))
+    return cases
+
+
+PROBE_CASES = _probe_cases()
+PROBE_SIZE, PROBE_SPP = (64, 48), 8
+
+
+def probe_world(case):
+    kind = PROBE_CASES[case]["scene"]
+    return probe_corner() if kind[0] == "corner" else probe_slab(kind[1], kind[2])
+
+
+def probe_config(case):
+    rpt = importlib.import_module("rust-path-tracer_amd")
+    c = PROBE_CASES[case]
+    w, h = c.get("size", PROBE_SIZE)
+    return rpt.default_config(w, h, has_skybox=0, **PROBE_VIEWS[c["view"]], **c["config"])
