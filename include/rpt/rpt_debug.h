@@ -57,6 +57,11 @@ int rpt_debug_trace_rays_production(rpt_ctx *ctx, size_t n, const float *origins
  * pad(2); 8 floats out: pdf, lobe (u32 bits), spectrum(3), direction(3).  kind 0 Lambertian::sample, 1 Glass::sample,
  * 2 Lambertian::{evaluate, pdf} (sample_direction = r), 3 Glass::{evaluate, pdf} (lobe = (u32) r.x). */
 int rpt_debug_bsdf(rpt_ctx *ctx, int kind, size_t n, const float *in, float *out);
+/* The image sampler of the shade stage, the sky stage and the denoiser's guides (csrc/k_shade.h sample_by_lod: the CPU polyfill's bilinear, wrapping lookup,
+ * shared_structs/src/image_polyfill.rs:32-55) on an image of the hook's own, one coordinate per thread: texels are width * height RGBA8 words (is_u8 != 0:
+ * an atlas, texel = (r, g, b, 255) / 255) or width * height float Vec4s (a skybox), within the sizes rpt_upload_scene accepts; coords_uv 2 floats and
+ * out_rgba 4 floats per coordinate.  Needs no scene and leaves the context as it was. */
+int rpt_debug_sample_image(rpt_ctx *ctx, int is_u8, const void *texels, uint32_t width, uint32_t height, size_t n, const float *coords_uv, float *out_rgba);
 /* The gather's point-to-point calls against the collective library the process resolved (rpt_comm_library), without a second GPU:
  * inside one ncclGroupStart / ncclGroupEnd this rank posts ncclRecv from rank - 1 and ncclSend to rank + 1 (one rank: to and from
  * itself) on the communicator's second stream, ordered by the same events as rpt_gather_async; n_floats of a known pattern travel

@@ -171,6 +171,18 @@ class Oracle:
         assert rc == 0
         return out
 
+    def sample_image(self, image, coords_uv):
+        """Image::sample_by_lod of the CPU polyfill (shared_structs/src/image_polyfill.rs:32-55), the function trace_pixel calls, on an image of its own:
+        (h, w, 4) uint8 (an atlas: texel = (r, g, b, 255) / 255) or float32 (a skybox), coords (n, 2) -> (n, 4) float32."""
+        image = np.ascontiguousarray(image)
+        assert image.ndim == 3 and image.shape[2] == 4 and image.dtype in (np.uint8, np.float32)
+        coords = np.ascontiguousarray(coords_uv, np.float32).reshape(-1, 2)
+        out = np.zeros((len(coords), 4), np.float32)
+        rc = self.lib.oracle_sample_image(_p(image), C.c_int(image.dtype == np.uint8), C.c_uint32(image.shape[1]), C.c_uint32(image.shape[0]),
+                                          C.c_size_t(len(coords)), _p(coords), _p(out))
+        assert rc == 0
+        return out
+
     def sky(self, sun_direction4, origin3, dirs):
         sun = np.ascontiguousarray(sun_direction4, np.float32)
         org = np.ascontiguousarray(origin3, np.float32)

@@ -1306,6 +1306,27 @@ int oracle_bsdf(int kind, size_t n, const float *in, float *out) {
     return 0;
 }
 
+/* The sampler trace_pixel uses (sample_by_lod above) on n coordinates of an image of its own, for unit tests: texels are width * height RGBA8 words
+ * (is_u8 != 0; turned into the CPU atlas texel (r, g, b, 255) / 255 of src/asset.rs:266-273, as oracle_ffi.py builds the atlas of a scene) or
+ * width * height float Vec4s; coords_uv 2 floats and out_rgba 4 floats per coordinate. */
+int oracle_sample_image(const void *texels, int is_u8, uint32_t width, uint32_t height, size_t n, const float *coords_uv, float *out_rgba) {
+    if (!texels || width == 0 || height == 0 || !coords_uv || !out_rgba) return -1;
+    std::vector<float> converted;
+    const float *f = (const float *)texels;
+    if (is_u8) {
+        const uint8_t *b = (const uint8_t *)texels;
+        converted.resize((size_t)width * height * 4);
+        for (size_t i = 0; i < converted.size(); ++i) converted[i] = (i & 3) == 3 ? 1.0f : (float)b[i] / 255.0f;
+        f = converted.data();
+    }
+    const Image img{f, width, height};
+    for (size_t i = 0; i < n; ++i) {
+        V4 s = sample_by_lod(img, V2{coords_uv[2 * i], coords_uv[2 * i + 1]});
+        out_rgba[4 * i] = s.x; out_rgba[4 * i + 1] = s.y; out_rgba[4 * i + 2] = s.z; out_rgba[4 * i + 3] = s.w;
+    }
+    return 0;
+}
+
 int oracle_math(int op, const float *x, const float *y, float *out, size_t n) {
     for (size_t i = 0; i < n; ++i) {
         float r;

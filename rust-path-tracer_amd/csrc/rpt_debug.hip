@@ -1,12 +1,21 @@
 /*
  * rpt_debug.hip — the test hooks of include/rpt/rpt_debug.h that run kernels of their own: the math functions, the BSDF
- * pieces and single rays through the debug and the production traversal stages.
+ * pieces, the image sampler and single rays through the debug and the production traversal stages.
  */
 #include <cstring>
 
 #include "rpt_ctx.h"
 #include "rpt_fastdiv.h"
 #include "k_bsdf_extra.h"
+#include "k_shade.h"             /* sample_by_lod: the function the shade stage, the sky stage and the denoiser's guides inline (k_shade itself is not instantiated) */
+
+/* one coordinate per thread through the production sampler, on an image of the hook's own */
+template <bool IS_U8>
+__global__ __launch_bounds__(256) void k_debug_sample_image(DevImage img, size_t n, const float2 *coords, float4 *out) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    out[i] = sample_by_lod<IS_U8>(img, coords[i].x, coords[i].y);
+}
 
 extern "C" {
 
@@ -95,6 +104,28 @@ int rpt_debug_bsdf(rpt_ctx *c, int kind, size_t n, const float *in, float *out) 
     k_debug_bsdf<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(kind, n, din.p, dout.p);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipMemcpy(out, dout.p, 32 * n, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+
+int rpt_debug_sample_image(rpt_ctx *c, int is_u8, const void *texels, uint32_t width, uint32_t height, size_t n, const float *coords_uv, float *out_rgba) {
+    if (!c || !texels || !coords_uv || !out_rgba || width == 0u || height == 0u) return RPT_EINVAL;
+    /* the limits of rpt_upload_scene: texel indices are 32-bit in sample_by_lod */
+    if ((uint64_t)width * height > (is_u8 ? (1ull << 30) : (1ull << 28)) || n > 0xffffffffull) return RPT_EINVAL;
+    if (n == 0) return RPT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n_texels = (size_t)width * height;
+    DevBuf<uchar4> d_u8;
+    DevBuf<float4> d_f32, d_out;
+    DevBuf<float2> d_uv;
+    if (is_u8) HIP_TRY(c, d_u8.from_host(static_cast<const uchar4 *>(texels), n_texels));
+    else HIP_TRY(c, d_f32.from_host(static_cast<const float4 *>(texels), n_texels));
+    HIP_TRY(c, d_uv.from_host(reinterpret_cast<const float2 *>(coords_uv), n)); HIP_TRY(c, d_out.alloc(n));
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    if (is_u8) k_debug_sample_image<true><<<blocks, 256, 0, c->stream>>>(DevImage{d_u8.p, width, height}, n, d_uv.p, d_out.p);
+    else k_debug_sample_image<false><<<blocks, 256, 0, c->stream>>>(DevImage{d_f32.p, width, height}, n, d_uv.p, d_out.p);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(out_rgba, d_out.p, n * sizeof(float4), hipMemcpyDeviceToHost));
     return RPT_OK;
 }
 

@@ -153,6 +153,7 @@ PROTOTYPES = {
     "rpt_debug_trace_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t] + [C.c_void_p] * 6),
     "rpt_debug_trace_rays_production": (C.c_int, [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5),
     "rpt_debug_bsdf": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "rpt_debug_sample_image": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]),
     "rpt_debug_comm_selftest": (C.c_int, [C.c_void_p, C.c_uint32, _OUT_U64]),
     "rpt_debug_denoise_host": (C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 6 + [C.POINTER(DenoiseParams), C.c_uint32, C.c_void_p]),
     "rpt_debug_noise_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.POINTER(NoiseCounts)]),
@@ -504,6 +505,15 @@ class Renderer(_Handle):
         items = np.ascontiguousarray(items, np.float32).reshape(-1, 16)
         out = np.zeros((len(items), 8), np.float32)
         self._check(lib().rpt_debug_bsdf(self._h, kind, len(items), ptr(items), ptr(out)))
+        return out
+
+    def debug_sample_image(self, image, coords_uv):
+        """rpt_debug_sample_image: the kernels' sample_by_lod on an image of its own, (h, w, 4) uint8 (an atlas) or float32 (a skybox); coords (n, 2) -> (n, 4)."""
+        image = np.ascontiguousarray(image)
+        assert image.ndim == 3 and image.shape[2] == 4 and image.dtype in (np.uint8, np.float32)
+        coords = np.ascontiguousarray(coords_uv, np.float32).reshape(-1, 2)
+        out = np.zeros((len(coords), 4), np.float32)
+        self._check(lib().rpt_debug_sample_image(self._h, int(image.dtype == np.uint8), ptr(image), image.shape[1], image.shape[0], len(coords), ptr(coords), ptr(out)))
         return out
 
     def debug_trace_rays(self, any_hit, origins, dirs, max_t=None):

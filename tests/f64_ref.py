@@ -1,6 +1,6 @@
-"""A second opinion on the scalar physics: the reference's shading, sky, light sampling, path loop and tonemap restated in numpy float64, vectorised over
-samples, from the reference's formulas (kernels/src/{lib,bsdf,util,skybox,light_pick,rng,intersection}.rs, src/resources/render.wgsl) and from nothing
-else.  It shares no code with the C++ CPU restatement the suite calls its checker, with the device's math header or with the package's native
+"""A second opinion on the scalar physics: the reference's shading (textured or not), normal mapping, image sampler, procedural and image sky, light
+sampling, path loop and tonemap restated in numpy float64, vectorised over samples, from the reference's formulas
+(kernels/src/{lib,bsdf,util,skybox,light_pick,rng,intersection}.rs, shared_structs/src/image_polyfill.rs, src/resources/render.wgsl) and from nothing else.  It shares no code with the C++ CPU restatement the suite calls its checker, with the device's math header or with the package's native
 libraries; the transcendental functions are numpy's.  That checker and, through probe scenes, the production kernels are held to this file within a
 tolerance (tests/test_f64_reference.py, tests/test_gpu_f64_probes.py).
 
@@ -10,6 +10,11 @@ coefficients ...) has the literal's float32 value; the random numbers are the re
 Margins.  Every discrete decision of a path also yields the distance by which it was taken, in the units of the compared quantity (random numbers,
 weights and barycentric coordinates as they are; distances along a ray relative to max(1, t); determinants relative to |edge1| |edge2|).  A sample
 whose smallest margin is below a threshold may legitimately take the other branch in float32; callers flag it and do not compare it.
+
+Textures.  The uv wrap of a textured hit is a decision like any other (margin: the distance of each uv component to its nearest integer).  The
+bilinear sampler is continuous across texel boundaries and across the modulo seam, so those carry no margin.  The image sky takes its row from an
+arcsine, which is ill-conditioned at the poles (a float32 y in error by 1e-7 moves v by 1e-7 / sqrt(1 - y^2)); trace reports the largest |y| of a
+sample's sky lookup and callers flag a sample too close to a pole.
 
 Small cosines.  float32 keeps the cosine of two unit vectors to about 1e-7 absolutely.  The specular pdf divides by halfway . view, which a near-mirror
 bounce at grazing incidence makes small: there the reference's expression is ill-conditioned (1e-7 / cosine^2 relatively).  pbr_sample and trace report
@@ -192,13 +197,72 @@ def lerp(a, b, t):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
+# image_polyfill.rs: the sampler
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+I32_MIN, I32_MAX = -2 ** 31, 2 ** 31 - 1
+
+
+def as_i32(x32):
+    """Rust's `f32 as i32` of float32 values -> int64 array: NaN -> 0, everything beyond the range (the infinities included) saturates"""
+    x = np.asarray(x32, np.float32).astype(np.float64)
+    return np.where(np.isnan(x), 0.0, np.clip(x, float(I32_MIN), float(I32_MAX))).astype(np.int64)
+
+
+def texel_values(image):
+    """(h, w, 4) texels in float64: an RGBA8 atlas as u8 / 255 with w = 1 (src/asset.rs builds the CPU image so), a float image as it is"""
+    image = np.asarray(image)
+    if image.dtype == np.uint8:
+        t = image.astype(np.float64) / 255.0
+        t[..., 3] = 1.0
+        return t
+    assert image.dtype == np.float32
+    return image.astype(np.float64)
+
+
+def sample_by_lod(image, width, height, coord):
+    """Image::sample_by_lod of the CPU polyfill (image_polyfill.rs:32-55): bilinear, WRAPPING (sample_raw takes every coordinate modulo the extent),
+    with NO half-texel offset: texel k sits at coordinate k / extent exactly.  The reference's GPU path samples through a hardware clamp-to-edge
+    sampler instead; the CPU polyfill is what the oracle and the kernels follow, and what is restated here.
+    image (height, width, 4) uint8 or float32, coord (n, 2) -> (value (n, 4), texels (n, 4, 2): the integer (x, y) of c00, c01, c10, c11, raw (n, 2, 2):
+    floor_uv and ceil_uv as the i32 they are before sample_raw reduces them).
+    The value is float64; the addressing is integer exact: floor and ceil of the FLOAT32 scaled coordinate (the number the reference holds) through the
+    saturating cast `as i32`, sign-extended to 64 bits (`as usize`) and reduced by an unsigned remainder.  A scaled coordinate beyond the float32 range
+    is an infinity there: its fract() is NaN and so is the value."""
+    texels = texel_values(image).reshape(height, width, 4)
+    coord = np.asarray(coord, np.float64)
+    with np.errstate(all="ignore"):
+        scaled = coord * np.array([float(np.float32(width)), float(np.float32(height))])
+        scaled32 = scaled.astype(np.float32)
+        scaled = np.where(np.isinf(scaled32), scaled32.astype(np.float64), scaled)
+        frac = scaled - np.floor(scaled)                                          # Vec2::fract = self - self.floor()
+    lo, hi = as_i32(np.floor(scaled32)), as_i32(np.ceil(scaled32))                # floor_uv, ceil_uv
+    extent = np.array([width, height], np.uint64)
+    lo_u, hi_u = lo.view(np.uint64) % extent, hi.view(np.uint64) % extent         # `as usize` keeps the two's complement; % is unsigned
+    lo_u, hi_u = lo_u.astype(np.int64), hi_u.astype(np.int64)
+
+    def raw(x, y):
+        return texels[y, x]
+
+    c00, c01 = raw(lo_u[:, 0], lo_u[:, 1]), raw(lo_u[:, 0], hi_u[:, 1])
+    c10, c11 = raw(hi_u[:, 0], lo_u[:, 1]), raw(hi_u[:, 0], hi_u[:, 1])
+    with np.errstate(all="ignore"):
+        tx, ty = frac[:, 0:1], frac[:, 1:2]
+        a = c00 + (c10 - c00) * tx                                                # Vec4::lerp: a + (b - a) * s
+        b = c01 + (c11 - c01) * tx
+        value = a + (b - a) * ty
+    index = np.stack([np.stack([lo_u[:, 0], lo_u[:, 1]], -1), np.stack([lo_u[:, 0], hi_u[:, 1]], -1),
+                      np.stack([hi_u[:, 0], lo_u[:, 1]], -1), np.stack([hi_u[:, 0], hi_u[:, 1]], -1)], 1)
+    return value, index, np.stack([lo, hi], 1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
 # bsdf.rs: PBR.  albedo (..., 3); roughness, metallic (...,) already through get_pbr_bsdf's guards (pbr_guards); clamp = (lo, hi)
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
 DIFFUSE, SPECULAR = 0, 1
 
 
 def pbr_guards(roughness, metallic):
-    """get_pbr_bsdf, untextured: roughness.max(EPS), metallic.min(1 - EPS) (the difference taken in f32, as the reference's f32 expression)"""
+    """get_pbr_bsdf after its texture lookups: roughness.max(EPS), metallic.min(1 - EPS) (the difference taken in f32, as the reference's f32 expression)"""
     return np.maximum(roughness, EPS), np.minimum(metallic, f32(np.float32(1.0) - np.float32(0.001)))
 
 
@@ -323,10 +387,13 @@ def sky(sun_direction4, origin, direction):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
-# the scene: plain float64 / integer arrays taken from the struct arrays of a World (untextured materials only)
+# the scene: plain float64 / integer arrays taken from the struct arrays of a World, its RGBA8 atlas (world.atlas, if any material has a texture flag)
+# and the float image of the sky (skybox, if the configuration has has_skybox = 1).  A material's albedo / roughness / metallic / normals field holds the
+# factor (untextured) or the atlas rectangle (x, y, width, height in atlas coordinates: textured); roughness and metallic are kept WITHOUT the guards of
+# get_pbr_bsdf, which act after the lookup.
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
 class Scene:
-    def __init__(self, world):
+    def __init__(self, world, skybox=None):
         f = np.float64
         self.vertex = world.per_vertex["vertex"][:, :3].astype(f)
         self.normal = world.per_vertex["normal"][:, :3].astype(f)
@@ -334,9 +401,14 @@ class Scene:
         self.tri = np.stack([t["v0"], t["v1"], t["v2"]], 1).astype(np.int64)
         self.material = t["material"].astype(np.int64)
         m = world.materials
-        assert not (m["has_albedo_texture"].any() or m["has_metallic_texture"].any() or m["has_roughness_texture"].any() or m["has_normal_texture"].any())
-        self.emissive, self.albedo = m["emissive"][:, :3].astype(f), m["albedo"][:, :3].astype(f)
-        self.roughness, self.metallic = pbr_guards(m["roughness"][:, 0].astype(f), m["metallic"][:, 0].astype(f))
+        self.uv, self.tangent = world.per_vertex["uv0"].astype(f), world.per_vertex["tangent"][:, :3].astype(f)
+        self.emissive = m["emissive"][:, :3].astype(f)
+        self.rect = {k: m[k].astype(f) for k in ("albedo", "roughness", "metallic", "normals")}           # (n_materials, 4): factor or rectangle
+        self.flag = {k: m[f"has_{n}_texture"] != 0 for k, n in (("albedo", "albedo"), ("roughness", "roughness"), ("metallic", "metallic"), ("normals", "normal"))}
+        self.textured = self.flag["albedo"] | self.flag["roughness"] | self.flag["metallic"] | self.flag["normals"]
+        self.atlas = getattr(world, "atlas", None)
+        assert self.atlas is not None or not self.textured.any(), "a texture flag without an atlas"
+        self.skybox = skybox
         self.is_emitter = (self.emissive != 0.0).any(1)
         lp = world.light_pick
         self.light = {k: lp[k].astype(np.int64 if "index" in k else f) for k in lp.dtype.names}
@@ -478,20 +550,41 @@ def _update(old, new, mask):
     return {k: np.where(col(mask) if np.ndim(new[k]) > 1 else mask, new[k], old[k]) for k in old}
 
 
-def trace(cfg, world, px, py, n, offset):
+def _lookup(sc, field, mat, uv):
+    """the atlas at the material's rectangle of `field`: material.field.xy + uv * material.field.zw -> (n, 4)"""
+    r = sc.rect[field][mat]
+    h, w = sc.atlas.shape[:2]
+    return sample_by_lod(sc.atlas, w, h, r[:, 0:2] + uv * r[:, 2:4])[0]
+
+
+def image_sky(cfg, skybox, direction):
+    """lib.rs:72-77 -> (rgb (n, 3) before the throughput, |rotated.y| (n,)).  The arcsine's argument is held inside [-1, 1]: a float64 unit vector may
+    exceed it by a rounding, and a sample that close to a pole is flagged anyway (the module's head)."""
+    sun = [float(cfg.sun_direction[k]) for k in range(4)]
+    rotation = np.arctan2(sun[2], sun[0])
+    rotated = direction @ rotation_y(rotation).T
+    u = 0.5 + np.arctan2(rotated[:, 2], rotated[:, 0]) / (2.0 * PI)
+    v = 1.0 - (0.5 + np.arcsin(np.clip(rotated[:, 1], -1.0, 1.0)) / PI)
+    intensity = sun[3] * f32(np.float32(1.0) / np.float32(15.0))
+    h, w = skybox.shape[:2]
+    return sample_by_lod(skybox, w, h, np.stack([u, v], -1))[0][:, :3] * intensity, np.abs(rotated[:, 1])
+
+
+def trace(cfg, world, px, py, n, offset, skybox=None):
     """trace_pixel for the samples (px, py, rng n, rng offset), each an (N,) array -> (radiance (N, 3), margin (N,), min_cosine (N,): the smallest
-    halfway . view of the path's specular bounces)"""
-    sc = world if isinstance(world, Scene) else Scene(world)
+    halfway . view of the path's specular bounces, sky_y (N,): |rotated.y| of the sample's lookup in the image sky, 0 if it made none)"""
+    sc = world if isinstance(world, Scene) else Scene(world, skybox)
+    assert cfg.has_skybox == 0 or sc.skybox is not None, "has_skybox = 1 needs the image"
     N = len(px)
     nee_mode = cfg.nee if cfg.nee <= 2 else 0
     nee, mis = nee_mode != 0, nee_mode == 1
     clamp = (float(cfg.specular_weight_clamp[0]), float(cfg.specular_weight_clamp[1]))
-    assert cfg.has_skybox == 0, "the image skybox is not restated"
     rng = Rng(n, offset)
     every = np.ones(N, bool)
     with np.errstate(all="ignore"):
         origin, direction = camera_rays(cfg, np.asarray(px, np.float64), np.asarray(py, np.float64), rng.r2(every))
         throughput, radiance, margin, alive, min_cosine = np.ones((N, 3)), np.zeros((N, 3)), np.full(N, INF), every.copy(), np.full(N, INF)
+        sky_y = np.zeros(N)
         last_bsdf = dict(pdf=np.zeros(N), lobe=np.zeros(N, np.int64), spectrum=np.zeros((N, 3)), direction=np.zeros((N, 3)))
         last_light = dict(area=np.zeros(N), normal=np.zeros((N, 3)), pick_pdf=np.zeros(N), emission=np.zeros((N, 3)), triangle=np.zeros(N, np.int64),
                           throughput=np.zeros((N, 3)))
@@ -507,8 +600,12 @@ def trace(cfg, world, px, py, n, offset):
             decide(m_hit, alive)
             point = origin + direction * col(t)
             miss = alive & ~hit
-            if miss.any():
+            if miss.any() and cfg.has_skybox == 0:
                 radiance = radiance + np.where(col(miss), throughput * sky(cfg.sun_direction, origin, direction), 0.0)
+            elif miss.any():
+                rgb, y = image_sky(cfg, sc.skybox, direction)
+                radiance = radiance + np.where(col(miss), throughput * rgb, 0.0)
+                sky_y = np.where(miss, y, sky_y)
             alive = alive & hit
 
             mat = sc.material[tri]
@@ -523,7 +620,28 @@ def trace(cfg, world, px, py, n, offset):
             idx = sc.tri[tri]
             bary = barycentric(point, sc.a[tri], sc.b[tri], sc.c[tri])
             normal = bary[:, 0:1] * sc.normal[idx[:, 0]] + bary[:, 1:2] * sc.normal[idx[:, 1]] + bary[:, 2:3] * sc.normal[idx[:, 2]]
-            bsdf = dict(albedo=sc.albedo[mat], roughness=sc.roughness[mat], metallic=sc.metallic[mat])
+            uv = bary[:, 0:1] * sc.uv[idx[:, 0]] + bary[:, 1:2] * sc.uv[idx[:, 1]] + bary[:, 2:3] * sc.uv[idx[:, 2]]
+            outside = ((uv < 0.0) | (uv > 1.0)).any(1)                        # uv.clamp(0, 1) != uv: EITHER component, and then the whole Vec2 is wrapped
+            uv = np.where(col(outside), uv - np.floor(uv), uv)
+            textured = alive & sc.textured[mat]
+            if textured.any():
+                decide(np.abs(uv - np.rint(uv)).min(1), textured)
+                if sc.flag["normals"].any():                                      # lib.rs:132-141
+                    normal_map = _lookup(sc, "normals", mat, uv) * 2.0 - 1.0
+                    tangent = bary[:, 0:1] * sc.tangent[idx[:, 0]] + bary[:, 1:2] * sc.tangent[idx[:, 1]] + bary[:, 2:3] * sc.tangent[idx[:, 2]]
+                    mapped = normalize(tangent * normal_map[:, 0:1] + cross(tangent, normal) * normal_map[:, 1:2] + normal * normal_map[:, 2:3])
+                    normal = np.where(col(sc.flag["normals"][mat]), mapped, normal)
+            # get_pbr_bsdf (bsdf.rs:354-379): albedo .xyz, roughness and metallic .x of their own rectangles, then the guards
+            albedo, roughness, metallic = sc.rect["albedo"][mat][:, :3], sc.rect["roughness"][mat][:, 0], sc.rect["metallic"][mat][:, 0]
+            if textured.any():
+                if sc.flag["albedo"].any():
+                    albedo = np.where(col(sc.flag["albedo"][mat]), _lookup(sc, "albedo", mat, uv)[:, :3], albedo)
+                if sc.flag["roughness"].any():
+                    roughness = np.where(sc.flag["roughness"][mat], _lookup(sc, "roughness", mat, uv)[:, 0], roughness)
+                if sc.flag["metallic"].any():
+                    metallic = np.where(sc.flag["metallic"][mat], _lookup(sc, "metallic", mat, uv)[:, 0], metallic)
+            roughness, metallic = pbr_guards(roughness, metallic)
+            bsdf = dict(albedo=albedo, roughness=roughness, metallic=metallic)
             s = pbr_sample(-direction, normal, rng.r3(alive), bsdf["albedo"], bsdf["roughness"], bsdf["metallic"], clamp)
             decide(s.pop("margin"), alive)
             min_cosine = np.where(alive, np.minimum(min_cosine, s.pop("min_cosine")), min_cosine)
@@ -546,19 +664,19 @@ def trace(cfg, world, px, py, n, offset):
                 decide(np.abs(r - prob), alive)
                 alive = alive & ~(r > prob)
                 throughput = np.where(col(alive), throughput * col(1.0 / prob), throughput)
-    return radiance, margin, min_cosine
+    return radiance, margin, min_cosine, sky_y
 
 
-def trace_image(cfg, world, seeds, first_sample, n_samples):
-    """samples first_sample .. of every pixel of the image -> (radiance (n_samples, H, W, 3), margin (n_samples, H, W), min_cosine (n_samples, H, W));
+def trace_image(cfg, world, seeds, first_sample, n_samples, skybox=None):
+    """samples first_sample .. of every pixel of the image -> (radiance (n_samples, H, W, 3), margin, min_cosine, sky_y (n_samples, H, W) each);
     seeds: the (H*W,) records (n, offset) of sample 0"""
     W, H = cfg.width, cfg.height
-    sc = Scene(world)
+    sc = Scene(world, skybox)
     py, px = np.divmod(np.arange(W * H), W)
-    out = [], [], []
+    out = [], [], [], []
     for k in range(first_sample, first_sample + n_samples):
-        r, m, c = trace(cfg, sc, px, py, seeds["n"].astype(np.uint64) + np.uint64(k), seeds["offset"])
-        for o, a in zip(out, (r.reshape(H, W, 3), m.reshape(H, W), c.reshape(H, W))):
+        r, m, c, y = trace(cfg, sc, px, py, seeds["n"].astype(np.uint64) + np.uint64(k), seeds["offset"])
+        for o, a in zip(out, (r.reshape(H, W, 3), m.reshape(H, W), c.reshape(H, W), y.reshape(H, W))):
             o.append(a)
     return tuple(np.stack(o) for o in out)
 

@@ -54,8 +54,8 @@ def same_bits(a, b):
 class SampleBank:
     """every sample's radiance of one (scene, config, seeds), from the oracle, computed once and extended on demand"""
 
-    def __init__(self, oracle, cfg, world, seeds):
-        self.oracle, self.cfg, self.scene = oracle, cfg, oracle.scene(world)
+    def __init__(self, oracle, cfg, world, seeds, skybox_f32=None):
+        self.oracle, self.cfg, self.scene = oracle, cfg, oracle.scene(world, skybox_f32=skybox_f32)
         self.rngs = [np.ascontiguousarray(seeds).copy()]        # rngs[k]: the state after k samples
         self.radiance, self.stats = [], []
 

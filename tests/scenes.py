@@ -384,8 +384,9 @@ def pack_rects(n_textures, atlas=4096):
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------------------------
-# Probe scenes of the float64 second opinion (tests/f64_ref.py): at most eight triangles, untextured, built as World objects directly.  The quads
-# reach far outside every view used, and the lamp sits well inside the frame, so that few samples decide anything by a hair.
+# Probe scenes of the float64 second opinion (tests/f64_ref.py): at most eight triangles, built as World objects directly.  The quads of the untextured
+# probes reach far outside every view used, and the lamp sits well inside the frame, so that few samples decide anything by a hair.  The textured slab
+# is small, so that its uvs vary over the view; its edges and its diagonal are in view.
 # ----------------------------------------------------------------------------------------------------------------------------------------------------
 PROBE_MATERIALS = {            # name -> (roughness, metallic, albedo); "zero" has an albedo channel of exactly 0
     "r0.5_m0": (0.5, 0.0, (0.8, 0.6, 0.4)), "r1_m0_zero": (1.0, 0.0, (0.7, 0.0, 0.9)), "r0.05_m1": (0.05, 1.0, (0.9, 0.7, 0.5)),
@@ -393,7 +394,9 @@ PROBE_MATERIALS = {            # name -> (roughness, metallic, albedo); "zero" h
 PROBE_VIEWS = {                # about 45 degrees onto the slab, and grazing: the camera looks 1 degree below the horizon from a height of 0.25
     "45": dict(cam_position=(0.0, 2.0, 0.0, 0.0), cam_rotation=(0.7853982, 0.0, 0.0, 0.0)),
     "grazing": dict(cam_position=(0.0, 0.25, 0.0, 0.0), cam_rotation=(0.01745329, 0.0, 0.0, 0.0)),
-    "corner": dict(cam_position=(0.3, 1.5, -2.0, 0.0), cam_rotation=(0.35, 0.1, 0.0, 0.0))}
+    "corner": dict(cam_position=(0.3, 1.5, -2.0, 0.0), cam_rotation=(0.35, 0.1, 0.0, 0.0)),
+    # up into the sky, from 12 to 86 degrees above the horizon: nothing in front
+    "up": dict(cam_position=(0.0, 2.0, 0.0, 0.0), cam_rotation=(-0.85, 0.4, 0.0, 0.0))}
 
 
 def _probe_quad(v, n, t, corners, normal, material):
@@ -448,6 +451,116 @@ def probe_corner():
     return _probe_world(v, n, t, [(0.6, 0.0, (0.7, 0.6, 0.5), (0.0, 0.0, 0.0)), (0.3, 0.8, (0.9, 0.5, 0.3), (0.0, 0.0, 0.0)), _LAMP])
 
 
+# ---- textured probes --------------------------------------------------------------------------------------------------------------------------------
+PROBE_ATLASES = {"32x32": (32, 32), "24x20": (24, 20)}          # (width, height): a power of two, and neither extent one
+PROBE_TEXTURE_SETS = {"albedo": ("albedo",), "rough-metal": ("roughness", "metallic"), "normal": ("normals",),
+                      "all": ("albedo", "roughness", "metallic", "normals")}
+PROBE_SKYBOXES = {"16x8": (16, 8), "7x5": (7, 5)}
+# sun_direction of the image-sky probes: only x and z (the rotation about y, atan2(z, x)) and w (the intensity, w / 15) are read.  "zero": no rotation;
+# "seam": rotated so that the image's column seam (u = 0 | 1, the direction -x after the rotation) crosses the views
+PROBE_SUNS = {"zero": (0.8, 0.6, 0.0, 12.0), "seam": (0.1, 0.3, -0.9, 12.0)}
+
+
+def probe_atlas(kind):
+    """A small asymmetric RGBA8 atlas of four rectangles, one in each quadrant: albedo top left, roughness top right, metallic bottom left, normal map
+    bottom right.  A rectangle is its quadrant less the last column and row, so that uv = 1 lands ON the rectangle's last texel and every footprint
+    of a uv in [0, 1] stays inside the quadrant (the polyfill sampler has no half-texel offset: a rectangle that fills its quadrant blends its last
+    texel with the neighbouring rectangle's first).  Albedo and metallic texels are random, so rows, columns and channels all differ; metallic stays
+    below 0.8 in the channel the reference reads (.x; the other channels hold other numbers).  Roughness (.x: 0.39 .. 0.7) and the normal map are ramps
+    of a few codes per texel with a pattern on them, never the same in two rows, two columns or two channels; the normal stays near +z, tilted towards
+    +x and -y by 4 to 14 degrees.  They are smooth because the float32 error of the interpolated uv, times the map's slope, is an error of the shading
+    normal or of the sampled specular direction, which a small cosine between the two amplifies: random texels there would make that error, not a
+    misreading, the largest difference (3e-3 to 1e-2 where these give 1e-3).
+    -> (atlas (h, w, 4) uint8, {field: (x, y, width, height) in atlas coordinates})"""
+    w, h = PROBE_ATLASES[kind]
+    rng = np.random.default_rng(w * 100 + h)
+    atlas = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
+    hw, hh = w // 2, h // 2
+    atlas[:hh, :hw, :3] = rng.integers(40, 241, (hh, hw, 3))
+    row, column = np.mgrid[0:hh, 0:w - hw]
+    atlas[:hh, hw:, 0] = 100 + 3 * column + 2 * row + (row * column) % 3
+    atlas[hh:, :hw, 0] = rng.integers(0, 201, (h - hh, hw))
+    row, column = np.mgrid[0:h - hh, 0:w - hw]
+    atlas[hh:, hw:, 0] = 137 + column + (row % 3)
+    atlas[hh:, hw:, 1] = 119 - row - 2 * (column % 2)
+    atlas[hh:, hw:, 2] = 251 - (row + 2 * column) % 5
+    f = np.float32
+    rect = lambda x, y, rw, rh: [f(x) / f(w), f(y) / f(h), f(rw - 1) / f(w), f(rh - 1) / f(h)]
+    return atlas, {"albedo": rect(0, 0, hw, hh), "roughness": rect(hw, 0, w - hw, hh), "metallic": rect(0, hh, hw, h - hh),
+                   "normals": rect(hw, hh, w - hw, h - hh)}
+
+
+def probe_textured_slab(textures, atlas_kind, uv_range=(0.0, 1.0), lamp=False):
+    """One quad of 16 x 16 in the plane y = 0 under the 45-degree view, its uvs running over uv_range in both directions; the material's factors are
+    those of "r0.5_m0" where a texture does not replace them.  Tangents: roughly +x, but of lengths 0.7 .. 1.6 and leaning into the normal and
+    towards z by amounts that differ from vertex to vertex: the reference normalises only the mapped normal."""
+    v, n, t = [], [], []
+    _probe_quad(v, n, t, [(-8, 0, -2), (-8, 0, 14), (8, 0, 14), (8, 0, -2)], (0, 1, 0), 0)
+    lo, hi = uv_range
+    uv_of = lambda p: [lo + (hi - lo) * (p[0] + 8.0) / 16.0, lo + (hi - lo) * (p[2] + 2.0) / 16.0]
+    materials = [PROBE_MATERIALS["r0.5_m0"][:2] + (PROBE_MATERIALS["r0.5_m0"][2], (0.0, 0.0, 0.0))]
+    if lamp:
+        k = len(v)
+        v += [[-0.6, 1.0, 1.4], [0.6, 1.0, 1.4], [0.0, 1.0, 2.4]]
+        n += [[0.0, -1.0, 0.0]] * 3
+        t += [[k, k + 1, k + 2, 1]]
+        materials.append(_LAMP)
+    rpt = importlib.import_module("rust-path-tracer_amd")
+    m = np.zeros(len(materials), rpt._ffi.MATERIAL_DTYPE)
+    for i, (roughness, metallic, albedo, emissive) in enumerate(materials):
+        m["albedo"][i] = list(albedo) + [1.0]
+        m["roughness"][i, :] = roughness
+        m["metallic"][i, :] = metallic
+        m["emissive"][i] = list(emissive) + [1.0 if any(emissive) else 0.0]
+    atlas, rects = probe_atlas(atlas_kind)
+    for field in PROBE_TEXTURE_SETS[textures]:
+        m[field][0] = rects[field]
+        m["has_normal_texture" if field == "normals" else f"has_{field}_texture"][0] = 1
+    w = rpt.World.from_buffers(np.array(v, np.float32), np.array(n, np.float32), np.array([uv_of(p) for p in v], np.float32), np.array(t, np.uint32), m)
+    p = w.per_vertex["vertex"][:, :3]
+    # a function of the position, so that it does not depend on the order the vertices are kept in
+    tangent = np.stack([0.7 + 0.9 * (p[:, 2] > 0), 0.25 * np.sign(p[:, 0]) * (p[:, 2] > 0) + 0.1, 0.3 * np.sign(p[:, 0]) - 0.1], 1)
+    w.per_vertex["tangent"][:, :3] = tangent.astype(np.float32)
+    w.atlas = atlas
+    return w
+
+
+def probe_skybox(case):
+    """the float image of an image-sky probe, (h, w, 4) float32 with random texels in 0 .. 2 (rows, columns and channels all differ), or None"""
+    kind = PROBE_CASES[case].get("skybox")
+    if kind is None:
+        return None
+    w, h = PROBE_SKYBOXES[kind]
+    sky = np.random.default_rng(w * 100 + h).uniform(0.0, 2.0, (h, w, 4)).astype(np.float32)
+    sky[..., 3] = 1.0
+    return sky
+
+
+def _textured_probe_cases():
+    """the probes behind f64_probes.TEXTURED_TOL and IMAGE_SKY_TOL"""
+    cases = {}
+    three = dict(min_bounces=3, max_bounces=3)
+    # a slab for each texture flag and one with all four; the two atlases alternate, and each is used with all four textures once
+    for textures, atlas in (("albedo", "32x32"), ("rough-metal", "24x20"), ("normal", "32x32"), ("all", "24x20")):
+        cases[f"tex-{textures}-{atlas}-nee1"] = dict(scene=("tslab", textures, atlas, (0.0, 1.0), True), view="45", config=dict(nee=1, **three), group="textured")
+    cases["tex-all-32x32-sky"] = dict(scene=("tslab", "all", "32x32", (0.0, 1.0), False), view="45", config=dict(nee=0, **three), group="textured")
+    # the wrap is taken, negative uvs included
+    cases["tex-all-24x20-wrap-nee1"] = dict(scene=("tslab", "all", "24x20", (-0.8, 1.9), True), view="45", config=dict(nee=1, **three), group="textured")
+    cases["tex-all-32x32-wrap-sky"] = dict(scene=("tslab", "all", "32x32", (-0.8, 1.9), False), view="45", config=dict(nee=0, **three), group="textured")
+    # the image sky: every pixel a lookup (both images, both rotations), and bounced rays that reach it from the corner scene
+    for sky, sun in (("16x8", "zero"), ("7x5", "seam"), ("16x8", "seam"), ("7x5", "zero")):
+        cases[f"imgsky-up-{sky}-{sun}"] = dict(scene=("slab", "r0.5_m0", False), view="up", config=dict(nee=0, **three), skybox=sky, sun=sun, group="image_sky",
+                                                   all_sky=True)
+    cases["imgsky-corner-16x8-seam-nee1"] = dict(scene=("corner",), view="corner", config=dict(nee=1, min_bounces=0, max_bounces=3), skybox="16x8", sun="seam",
+                                                 group="image_sky")
+    cases["imgsky-corner-7x5-zero-nee0"] = dict(scene=("corner",), view="corner", config=dict(nee=0, min_bounces=0, max_bounces=5), skybox="7x5", sun="zero",
+                                                group="image_sky")
+    # (a textured probe by its figure: the slab's lookups, not the sky's, set its difference)
+    cases["imgsky-tex-all-24x20-7x5-seam"] = dict(scene=("tslab", "all", "24x20", (-0.8, 1.9), False), view="45", config=dict(nee=0, **three), skybox="7x5",
+                                                  sun="seam", group="textured")
+    return cases
+
+
 def _probe_cases():
     cases = {}
     for material in PROBE_MATERIALS:
@@ -474,6 +587,7 @@ def _probe_cases():
     cases["corner-nee1-4bounces-min2"] = dict(scene=("corner",), view="corner", config=dict(nee=1, min_bounces=2, max_bounces=4))
     cases["corner-nee0-5bounces-50x37"] = dict(scene=("corner",), view="corner", config=dict(nee=0, min_bounces=0, max_bounces=5), size=(50, 37))
     cases["corner-nee0-5bounces"] = dict(scene=("corner",), view="corner", config=dict(nee=0, min_bounces=0, max_bounces=5))
+    cases.update(_textured_probe_cases())
     return cases
 
 
@@ -483,6 +597,8 @@ PROBE_SIZE, PROBE_SPP = (64, 48), 8
 
 def probe_world(case):
     kind = PROBE_CASES[case]["scene"]
+    if kind[0] == "tslab":
+        return probe_textured_slab(*kind[1:])
     return probe_corner() if kind[0] == "corner" else probe_slab(kind[1], kind[2])
 
 
@@ -490,4 +606,44 @@ def probe_config(case):
     rpt = importlib.import_module("rust-path-tracer_amd")
     c = PROBE_CASES[case]
     w, h = c.get("size", PROBE_SIZE)
-    return rpt.default_config(w, h, has_skybox=0, **PROBE_VIEWS[c["view"]], **c["config"])
+    sky = dict(has_skybox=1, sun_direction=PROBE_SUNS[c["sun"]]) if "skybox" in c else dict(has_skybox=0)
+    return rpt.default_config(w, h, **sky, **PROBE_VIEWS[c["view"]], **c["config"])
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------------------------
+# Inputs of the sampler's function-level tests (tests/test_f64_reference.py on the CPU, tests/test_gpu_sampler.py on the device)
+# ----------------------------------------------------------------------------------------------------------------------------------------------------
+SAMPLER_EXTENTS = [(1, 1), (1, 7), (7, 1), (2, 2), (3, 5), (64, 64), (63, 65), (64, 48)]         # (width, height)
+
+
+def sampler_image(width, height, is_u8):
+    """(height, width, 4) random texels, every row, column and channel different: uint8 in 64 .. 255, or float32 in 0.5 .. 2.  Texels stay away from
+    0 so that the comparison is relative to the value, not to the floor."""
+    rng = np.random.default_rng(1000 * width + height + (500 if is_u8 else 0))
+    if is_u8:
+        return rng.integers(64, 256, (height, width, 4), dtype=np.uint8)
+    return rng.uniform(0.5, 2.0, (height, width, 4)).astype(np.float32)
+
+
+def sampler_coords(width, height):
+    """(n, 2) float32, about 26 000: random in [-2, 3]^2; the grid k / extent (where ceil equals floor) over three periods; exactly 0 and 1 and their
+    float32 neighbours on both sides; -0.0 and denormals; +-1e10, +-3e38, +-inf and NaN; every special value in either component, against every
+    special value and against random ones"""
+    f = np.float32
+    rng = np.random.default_rng(77 * width + height)
+    random = rng.uniform(-2.0, 3.0, (20_000, 2)).astype(f)
+    gx = (np.arange(-width, 2 * width + 1, dtype=f) / f(width)).astype(f)
+    gy = (np.arange(-height, 2 * height + 1, dtype=f) / f(height)).astype(f)
+    grid = np.stack(np.meshgrid(gx, gy, indexing="ij"), -1).reshape(-1, 2)
+    grid = grid[rng.permutation(len(grid))[:4000]]
+    grid_x = np.stack([rng.choice(gx, 500), rng.uniform(-2.0, 3.0, 500).astype(f)], 1)
+    grid_y = np.stack([rng.uniform(-2.0, 3.0, 500).astype(f), rng.choice(gy, 500)], 1)
+    zero, one, inf = f(0.0), f(1.0), f(np.inf)
+    special = np.array([zero, -zero, one, np.nextafter(zero, one), np.nextafter(zero, -one), np.nextafter(one, zero), np.nextafter(one, f(2.0)),
+                        f(1e-45), f(-1e-45), f(1e-40), f(-1e-40), f(1e10), f(-1e10), f(3e38), f(-3e38), inf, -inf, f(np.nan),
+                        np.nextafter(f(-1.0), zero), np.nextafter(f(-1.0), f(-2.0)), f(-1.0), f(2.0), np.nextafter(f(2.0), zero)], f)
+    pairs = np.stack(np.meshgrid(special, special, indexing="ij"), -1).reshape(-1, 2)
+    k = len(special)
+    with_random_x = np.stack([np.repeat(special, 12), rng.uniform(-2.0, 3.0, 12 * k).astype(f)], 1)
+    with_random_y = np.stack([rng.uniform(-2.0, 3.0, 12 * k).astype(f), np.repeat(special, 12)], 1)
+    return np.ascontiguousarray(np.concatenate([random, grid, grid_x, grid_y, pairs, with_random_x, with_random_y]).astype(f))

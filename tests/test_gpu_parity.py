@@ -487,6 +487,51 @@ def test_textured_scene_and_image_skybox_parity(renderer, oracle, rpt, nee, has_
     assert acc_c[..., :3].std() > 0.05          # the textures really modulate the image
 
 
+def _textured_scene_cropped():
+    """textured_scene with its 64 x 64 atlas cropped to 60 x 52 and every rectangle rescaled to the texels it had: (x, y, w, h) in texels stay, the
+    quadrants that began at 32 now reach 28 and 20 texels to the new edge"""
+    from scenes import textured_scene
+    w, _ = textured_scene()
+    aw, ah = 60, 52
+    w.atlas = np.ascontiguousarray(w.atlas[:ah, :aw])
+    m = w.materials.copy()
+    f = np.float32
+    for field in ("albedo", "roughness", "metallic", "normals"):
+        flag = m["has_normal_texture" if field == "normals" else f"has_{field}_texture"] != 0
+        r = m[field][flag] * f(64.0)                                    # back to texels (exact: the rectangles are multiples of 1 / 2)
+        x1, y1 = np.minimum(r[:, 0] + r[:, 2], f(aw)), np.minimum(r[:, 1] + r[:, 3], f(ah))
+        m[field][flag] = np.stack([r[:, 0] / f(aw), r[:, 1] / f(ah), (x1 - r[:, 0]) / f(aw), (y1 - r[:, 1]) / f(ah)], 1)
+    w.materials = m
+    return w
+
+
+@pytest.mark.parametrize("which", ["atlas-60x52", "skybox-15x7"])
+def test_non_power_of_two_images_parity(renderer, oracle, rpt, which):
+    """test_textured_scene_and_image_skybox_parity on images that are no power of two in either extent, as a skybox file of any size is: the sampler's
+    general addressing (csrc/k_shade.h image_wrap without the mask) inside the shade stage and the sky stage.  Same size and sample count."""
+    from scenes import textured_scene
+    w, skybox = textured_scene()
+    if which == "atlas-60x52":
+        w = _textured_scene_cropped()
+        assert w.atlas.shape == (52, 60, 4)
+    else:
+        skybox = np.ascontiguousarray(skybox[:7, :15])
+    W, H, spp = 160, 96, 6
+    cfg = rpt.default_config(W, H, nee=1, has_skybox=1, cam_position=(0.0, 1.6, -4.0, 0.0), cam_rotation=(0.05, 0.1, 0.0, 0.0))
+    seeds = rpt.blue_noise_seeds(W, H)
+    renderer.upload_scene(w, skybox_f32=skybox)
+    renderer.set_config(cfg)
+    renderer.reset(seeds)
+    renderer.render(spp)
+    acc_g, _ = renderer.read_accum()
+    st_g = renderer.stats()
+    acc_c, _, st_c = oracle.trace_cpu(cfg, oracle.scene(w, skybox_f32=skybox), seeds, spp)
+    assert st_c.error_flags == 0 and st_c.sky_evals > 0 and st_g["sky_evals"] == st_c.sky_evals
+    assert st_g["extension_rays"] == st_c.extension_rays and st_g["shadow_rays"] == st_c.shadow_rays
+    assert np.array_equal(acc_g.view(np.uint32), acc_c.view(np.uint32))
+    assert acc_c[..., :3].std() > 0.05
+
+
 def test_full_size_baseline_config_properties(hipmod, oracle, rpt, world):
     """BASELINE config[1] at full size (DarkCornell 1024x1024) through size-independent properties: every pixel got
     exactly spp samples, two runs agree bitwise, batch splitting is invisible, ray accounting is consistent, and a
