@@ -38,6 +38,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "k_common.h"
 
 #define BVB_THREADS 256
 #define BVB_MAX_BINS 128
@@ -159,7 +160,7 @@ template <int THREADS>
 __device__ __forceinline__ uint32_t bvb_block_rank(bool flag, uint32_t *wave_tot, uint32_t &block_total) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     unsigned long long m = __builtin_amdgcn_ballot_w64(flag);
-    uint32_t within = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    uint32_t within = rpt_lane_rank(m);
     __syncthreads();                       /* wave_tot free again */
     if (lane == 0u) wave_tot[wave] = (uint32_t)__popcll(m);
     __syncthreads();

@@ -80,6 +80,10 @@ struct DevImage {
 /* wave64 ballot of a bool that already lives in an SGPR mask: HIP's __ballot(int) first materialises the
  * predicate as 0/1 in a VGPR and compares it again (two extra VALU instructions per ballot). */
 __device__ __forceinline__ unsigned long long rpt_ballot(bool pred) { return __builtin_amdgcn_ballot_w64(pred); }
+/* this lane's rank among the lanes of `mask` (a ballot): how many of its bits lie below the lane */
+__device__ __forceinline__ uint32_t rpt_lane_rank(unsigned long long mask) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
 
 #define RPT_LAST_EMIT_MAX 4
 struct DevScene {
@@ -102,15 +106,15 @@ struct DevScene {
     uint32_t n_light_pick;
     uint32_t n_nodes, n_triangles;
     uint32_t lds_scene;            /* the traversal image fits in RPT_LDS_SCENE_BYTES: traverse out of LDS */
-    const float4 *lds_image;       /* LDS-resident traversal image (k_traverse.h SceneViewLds), lds_vecs float4 */
+    const float4 *lds_image;       /* LDS-resident traversal image (k_walk.h SceneViewLds), lds_vecs float4 */
     uint32_t lds_pairs, lds_vecs, lds_root;
-    const float4 *gpairs;          /* streamed global-memory walks: one 64-byte record per child pair (k_traverse.h SceneViewPairsT), or null */
+    const float4 *gpairs;          /* streamed global-memory walks: one 64-byte record per child pair (k_walk.h SceneViewPairsT), or null */
     const uint32_t *glinks;        /* triangle_count << 24 | left child / first triangle, per node */
     uint32_t shadow_fixed;         /* the any-hit walks use a fixed left-first order over the flipped copies below (shadow_order.h) */
     const float4 *lds_image_shadow;
     const float4 *gpairs_shadow;
     const uint32_t *glinks_shadow;
-    /* the last extension rays of a batch without NEE (k_traverse.h k_traverse_nearest_stream LAST): the triangles whose material emits, when there are at most
+    /* the last extension rays of a batch without NEE (k_traverse_nearest.h k_traverse_nearest_stream LAST): the triangles whose material emits, when there are at most
      * RPT_LAST_EMIT_MAX of them (last_emit_n > RPT_LAST_EMIT_MAX: too many, the launch is the plain one), and the size of the flipped copy's pair records
      * staged behind the LDS image (0: not staged) */
     uint32_t last_emit_n, last_emit_tri[RPT_LAST_EMIT_MAX];
@@ -123,7 +127,7 @@ struct DevScene {
 };
 
 /* constants of the traversal structures that the upload code (rpt_scene.hip) and the walk kernels (k_traverse.h, compiled in rpt_traverse.hip) share */
-#define LDS_DESC_DEAD 0x4000u      /* 16-bit child descriptor of the LDS image (k_traverse.h SceneViewLds): pair index, or LEAF | count << 9 | first triangle */
+#define LDS_DESC_DEAD 0x4000u      /* 16-bit child descriptor of the LDS image (k_walk.h SceneViewLds): pair index, or LEAF | count << 9 | first triangle */
 #define LDS_DESC_LEAF 0x8000u
 #define RPT_LDS_SCENE_BYTES 32768  /* a traversal image up to this size lives in LDS (+ 32 KB of 16-bit stacks = the 64 KB of one of two workgroups per CU) */
 #define RPT_COOP_LEAF_MIN 6        /* leaves with more triangles than this are tested by the whole wave (global-memory scenes) */
@@ -163,6 +167,8 @@ RPT_HD size_t rpt_pixel_index(uint32_t pxy, uint32_t width) { return (size_t)(px
 #define HIT_DONE 0xfffffffcu      /* sample finished, radiance final in rad.xyz; waits for its siblings */
 #define HIT_DONE_ZERO 0xfffffffbu /* sample finished with radiance (+0, +0, +0) and nothing owed: its rad record was NOT written (DevQueues::implicit_zero) */
 #define HIT_IDLE 0xfffffffau      /* the slot has no sample left to take in this render call; every word below it is a triangle */
+/* a slot changes its stage: one of the states above into its hit word (hit_t means nothing in any of them) */
+__device__ __forceinline__ void set_hit_word(const DevState &st, uint32_t slot, uint32_t word) { st.hit[slot] = make_float2(0.0f, __uint_as_float(word)); }
 
 /* ---- queues ---------------------------------------------------------------- */
 /* counter words: per iteration parity, "the traversal pass traced a ray" and
@@ -224,7 +230,7 @@ struct DevQueues {
     uint32_t sky_shard_shift; /* log2 of the slots a workgroup of this call's shade stage owns (8, packed variant 11): slot s is pushed into shard (s >> this) % RPT_Q_SHARDS */
     uint32_t implicit_zero;   /* a batch of known length without NEE, several slots per pixel: radiance changes only where a path ends and no slot owes a second
                                  sample, so the rad record of a LIVE path would be sixteen zero bytes — it is not kept.  A path that ends with something added
-                                 writes its record and HIT_DONE, one that ends with nothing writes HIT_DONE_ZERO alone (k_shade.h, k_traverse.h last_finish,
+                                 writes its record and HIT_DONE, one that ends with nothing writes HIT_DONE_ZERO alone (k_shade.h, k_traverse_nearest.h last_finish,
                                  k_sky, k_complete.h).  (Sits in what was the padding before ray_shards: no other field moves.) */
     unsigned long long *ray_shards;  /* RPT_STAT_SHARDS x RPT_STAT_STRIDE: extension rays traced */
     unsigned long long *host_ring;   /* mapped pinned host memory: (iteration + 1) << 32 | extension-queue size */
@@ -284,7 +290,7 @@ __device__ __forceinline__ uint32_t wave_push(uint32_t *counter, bool pred) {
     uint32_t base = 0u;
     if (lane == leader) base = atomicAdd(counter, total);
     base = (uint32_t)__shfl((int)base, (int)leader, RPT_WAVE);
-    uint32_t prefix = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+    uint32_t prefix = rpt_lane_rank(mask);
     return base + prefix;
 }
 
@@ -313,7 +319,7 @@ __device__ __forceinline__ uint32_t block_push(uint32_t *counter, bool pred, uin
     __syncthreads();
     uint32_t base = scratch[NW];
     for (uint32_t w = 0; w < wave; ++w) base += scratch[w];
-    uint32_t prefix = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+    uint32_t prefix = rpt_lane_rank(mask);
     __syncthreads();     /* scratch may be reused by the next push */
     return base + prefix;
 }

@@ -103,7 +103,7 @@ __device__ __forceinline__ bool complete_stage_rows(const DevState &st, uint32_t
         tile[(k - kb) * RPT_COMPLETE_PITCH + p] = make_float4(rx[i], ry[i], rz[i], rw[i]);
         const bool mine = ((row_done[(slot - base) >> 6] >> lane) & 1ull) != 0ull && ((ok_mask >> p) & 1ull) != 0ull;
         const uint32_t todo = __float_as_uint(rw[i]);
-        if (mine && todo == 0u) st.hit[slot] = make_float2(0.0f, __uint_as_float(HIT_IDLE));
+        if (mine && todo == 0u) set_hit_word(st, slot, HIT_IDLE);
         restart = restart || rpt_ballot(mine && todo != 0u) != 0ull;
     }
     return restart;

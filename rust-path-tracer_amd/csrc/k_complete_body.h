@@ -25,7 +25,7 @@ __device__ __forceinline__ bool RPT_COMPLETE_DIRECT_ROWS(const DevState &st, uin
         if (mine) { acc.x += rx[i]; acc.y += ry[i]; acc.z += rz[i]; acc.w += 1.0f; }
         RPT_MOM(if (mine) mo_add(mom, rx[i], ry[i], rz[i]);)
         const uint32_t todo = __float_as_uint(rw[i]);
-        if (mine && todo == 0u) st.hit[base + ((k0 + i) << 6) + lane] = make_float2(0.0f, __uint_as_float(HIT_IDLE));
+        if (mine && todo == 0u) st.hit[base + ((k0 + i) << 6) + lane] = make_float2(0.0f, __uint_as_float(HIT_IDLE));      /* (written out: through set_hit_word this unrolled loop compiles to other code) */
         restart = restart || rpt_ballot(mine && todo != 0u) != 0ull;
     }
     return restart;

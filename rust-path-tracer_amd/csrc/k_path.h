@@ -38,7 +38,7 @@ __device__ __forceinline__ void start_path(const DevState &st, const DevConfig &
     camera_ray(cfg, pxy & 0xffffu, pxy >> 16, n + offset, ro, rd);
     st.ray_a[slot] = make_float4(ro.x, ro.y, ro.z, rd.x);
     st.ray_b[slot] = make_float2(rd.y, rd.z);
-    st.hit[slot] = make_float2(0.0f, __uint_as_float(HIT_PENDING));
+    set_hit_word(st, slot, HIT_PENDING);
     st.thr[slot] = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(MAKE_FLAGS(0u, 0u, 2u)));
     st.rad[slot] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(todo_after));
 }
@@ -54,9 +54,9 @@ __device__ __forceinline__ void start_first_path(const DevState &st, const DevCo
     camera_ray(cfg, pxy & 0xffffu, pxy >> 16, n + offset, ro, rd);
     st.ray_a[slot] = make_float4(ro.x, ro.y, ro.z, rd.x);
     st.ray_b[slot] = make_float2(rd.y, rd.z);
-    st.hit[slot] = make_float2(0.0f, __uint_as_float(HIT_PENDING));
+    set_hit_word(st, slot, HIT_PENDING);
 }
-/* The same for a slot that the first walk of a render call takes itself (k_traverse.h k_traverse_nearest_stream FIRST: no k_generate_first pass over the slots,
+/* The same for a slot that the first walk of a render call takes itself (k_traverse_nearest.h k_traverse_nearest_stream FIRST: no k_generate_first pass over the slots,
  * no ray and hit word written only to be read back by the next launch).  `word` is the slot's hit word: anything but HIT_IDLE is a sample the previous call
  * left in flight, counted where k_generate_first counts it.  Returns false for a slot that takes no sample in this call — the padding of the last chunk of 64
  * pixels, k >= n_samples — which stays idle; else the camera ray is in (ro, rd) and in the slot's ray record, which every later stage reads. */
@@ -65,7 +65,7 @@ __device__ __forceinline__ bool begin_first_path(const DevState &st, const DevCo
     if (word != HIT_IDLE) atomicAdd(&stats->undrained, 1ull);
     const uint32_t k = slot_k(st, slot), pix = slot_pix(st, slot);
     if (pix >= st.n_pixels || k >= n_samples) {
-        if (word != HIT_IDLE) st.hit[slot] = make_float2(0.0f, __uint_as_float(HIT_IDLE));
+        if (word != HIT_IDLE) set_hit_word(st, slot, HIT_IDLE);
         return false;
     }
     const uint2 rs = st.rng[pix];
@@ -92,11 +92,11 @@ __device__ __forceinline__ void finish_in_side_stage(const DevState &st, const D
         uint2 rs = st.rng[slot];
         rs.x += 1u;
         st.rng[slot] = rs;
-        if (todo == 0u) st.hit[slot] = make_float2(0.0f, __uint_as_float(HIT_IDLE));
+        if (todo == 0u) set_hit_word(st, slot, HIT_IDLE);
         else start_path(st, cfg, slot, rs.x, rs.y, todo - 1u);
     } else {
         st.rad[slot] = make_float4(radiance.x, radiance.y, radiance.z, __uint_as_float(todo));
-        st.hit[slot] = make_float2(0.0f, __uint_as_float(HIT_DONE));
+        set_hit_word(st, slot, HIT_DONE);
     }
 }
 /* The same where live paths keep no radiance record (DevQueues::implicit_zero: several slots per pixel, nothing owed): a path that ends with `added` on top of
@@ -104,7 +104,7 @@ __device__ __forceinline__ void finish_in_side_stage(const DevState &st, const D
 __device__ __forceinline__ void finish_from_zero(const DevState &st, uint32_t slot, F3 added) {
     const F3 radiance = f3s(0.0f) + added;
     st.rad[slot] = make_float4(radiance.x, radiance.y, radiance.z, __uint_as_float(0u));
-    st.hit[slot] = make_float2(0.0f, __uint_as_float(HIT_DONE));
+    set_hit_word(st, slot, HIT_DONE);
 }
 
 #endif /* RPT_K_PATH_H */

@@ -210,7 +210,7 @@ __device__ __forceinline__ void shade_slot(const DevScene &sc, const DevState &s
                 const float4 tf = st.thr[slot];
                 finish_from_zero(st, slot, mask_nan3(f3(tf.x, tf.y, tf.z) * f3(e4.x, e4.y, e4.z)));
             } else {
-                st.hit[slot] = make_float2(0.0f, __uint_as_float(HIT_DONE_ZERO));
+                set_hit_word(st, slot, HIT_DONE_ZERO);
             }
         } else if (emits || st.group_shift == 0u) {
             const float4 r4 = st.rad[slot];
@@ -221,7 +221,7 @@ __device__ __forceinline__ void shade_slot(const DevScene &sc, const DevState &s
             }
             finish_in_side_stage(st, cfg, slot, radiance, __float_as_uint(r4.w));
         } else {
-            st.hit[slot] = make_float2(0.0f, __uint_as_float(HIT_DONE));
+            set_hit_word(st, slot, HIT_DONE);
         }
         return;
     }
@@ -232,7 +232,7 @@ __device__ __forceinline__ void shade_slot(const DevScene &sc, const DevState &s
         const float hit_t = hw.x;
         if (hit_tri == HIT_MISS) {
             to_sky = true;                           /* lib.rs:66-79: shaded by k_sky, which also ends the path */
-            st.hit[slot] = make_float2(0.0f, __uint_as_float(HIT_PARKED));
+            set_hit_word(st, slot, HIT_PARKED);
             if (first) {                             /* k_sky reads the path state */
                 st.thr[slot] = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(RPT_FRESH_FLAGS));
                 if (!zero_rad) st.rad[slot] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(first_path_todo(st, slot, n_samples)));
@@ -537,7 +537,7 @@ __device__ __forceinline__ void shade_slot(const DevScene &sc, const DevState &s
             }
 
             if (zero_rad && done && !added) {
-                st.hit[slot] = make_float2(0.0f, __uint_as_float(HIT_DONE_ZERO));      /* a back-facing emitter, the last bounce, the roulette: nothing to record */
+                set_hit_word(st, slot, HIT_DONE_ZERO);      /* a back-facing emitter, the last bounce, the roulette: nothing to record */
             } else if (done && !emit_shadow) {
                 /* the path ends here with nothing pending: one slot per pixel — accumulated and restarted on the spot; several —
                  * parked as HIT_DONE for k_complete */
@@ -552,11 +552,11 @@ __device__ __forceinline__ void shade_slot(const DevScene &sc, const DevState &s
                     st.thr[slot] = make_float4(throughput.x, throughput.y, throughput.z, __uint_as_float(new_flags));
                     st.ray_a[slot] = make_float4(new_o.x, new_o.y, new_o.z, new_d.x);
                     st.ray_b[slot] = make_float2(new_d.y, new_d.z);
-                    st.hit[slot] = make_float2(0.0f, __uint_as_float(HIT_PENDING));
+                    set_hit_word(st, slot, HIT_PENDING);
                     sh_d.w = __uint_as_float(slot);
                 } else {
                     /* the shadow stage adds the NEE term and then finishes the path */
-                    st.hit[slot] = make_float2(0.0f, __uint_as_float(HIT_PARKED));
+                    set_hit_word(st, slot, HIT_PARKED);
                     sh_d.w = __uint_as_float(slot | 0x80000000u);
                 }
             }
@@ -587,7 +587,7 @@ __device__ __forceinline__ uint32_t block_rank(bool pred, uint32_t *scratch, uin
     }
     total = sum;
     __syncthreads();     /* scratch may be reused */
-    return base + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+    return base + rpt_lane_rank(mask);
 }
 
 /* the same for two disjoint predicates in one pass (one pair of barriers): ranks and totals of both */
@@ -604,8 +604,8 @@ __device__ __forceinline__ void block_rank2(bool a, bool b, uint32_t *scratch, u
     }
     total_a = sum & 0xffffu; total_b = sum >> 16;
     __syncthreads();     /* scratch may be reused */
-    rank_a = (base & 0xffffu) + __builtin_amdgcn_mbcnt_hi((uint32_t)(ma >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ma, 0u));
-    rank_b = (base >> 16) + __builtin_amdgcn_mbcnt_hi((uint32_t)(mb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mb, 0u));
+    rank_a = (base & 0xffffu) + rpt_lane_rank(ma);
+    rank_b = (base >> 16) + rpt_lane_rank(mb);
 }
 
 /* side-queue emission of one pass over up to 256 slots: wave64 ballot + mbcnt prefix, one atomic per workgroup

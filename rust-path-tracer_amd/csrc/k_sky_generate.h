@@ -200,7 +200,7 @@ __global__ __launch_bounds__(RPT_BLOCK) void k_sky(DevScene sc, DevState st, Dev
 
 /* Start of an rpt_render call: slot k of every pixel begins sample k; it will take samples k, k+S, ... of
  * the n_samples this call owes the pixel. */
-/* counters_only (a one-workgroup launch): the call's first walk starts the paths itself (k_traverse.h k_traverse_nearest_stream FIRST, k_path.h begin_first_path)
+/* counters_only (a one-workgroup launch): the call's first walk starts the paths itself (k_traverse_nearest.h k_traverse_nearest_stream FIRST, k_path.h begin_first_path)
  * and this launch only opens the call — the persistent walk cannot zero the pool counter it is about to draw from. */
 __global__ __launch_bounds__(RPT_BLOCK) void k_generate_first(DevState st, DevQueues q, DevConfig cfg, uint32_t n_samples, DevStats *stats, uint32_t counters_only) {
     uint32_t slot = blockIdx.x * RPT_BLOCK + threadIdx.x;
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(RPT_BLOCK) void k_generate_first(DevState st, DevQu
     if (__float_as_uint(st.hit[slot].y) != HIT_IDLE) atomicAdd(&stats->undrained, 1ull);
     const uint32_t S = 1u << st.group_shift, k = slot_k(st, slot), pix = slot_pix(st, slot);
     if (pix >= st.n_pixels) {                                 /* padding of the last chunk of 64 pixels: never holds a path */
-        st.hit[slot] = make_float2(0.0f, __uint_as_float(HIT_IDLE));
+        set_hit_word(st, slot, HIT_IDLE);
         return;
     }
     uint2 rs = st.rng[pix];
@@ -227,11 +227,11 @@ __global__ __launch_bounds__(RPT_BLOCK) void k_generate_first(DevState st, DevQu
             rs.x += n_samples;
             st.rng[pix] = rs;
         }
-        st.hit[slot] = make_float2(0.0f, __uint_as_float(HIT_IDLE));
+        set_hit_word(st, slot, HIT_IDLE);
         return;
     }
     uint32_t count = n_samples > k ? (n_samples - k + S - 1u) / S : 0u;
-    if (count == 0u) st.hit[slot] = make_float2(0.0f, __uint_as_float(HIT_IDLE));
+    if (count == 0u) set_hit_word(st, slot, HIT_IDLE);
     else start_first_path(st, cfg, slot, rs.x + k, rs.y);      /* (owes count - 1 more: first_path_todo) */
 }
 

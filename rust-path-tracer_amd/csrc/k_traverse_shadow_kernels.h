@@ -2,7 +2,7 @@
  * k_traverse_shadow_kernels.h — the kernels that walk shadow rays (and the one-ray-per-lane test hook), written ONCE and compiled TWICE: k_traverse.h
  * includes this file with
  *     RPT_SHADOW_KERNEL(name) = name,        RPT_SHADOW_KERNEL_SEGMENT = false   the reference's any-hit walk, under the names the kernels always had
- *     RPT_SHADOW_KERNEL(name) = name##_seg,  RPT_SHADOW_KERNEL_SEGMENT = true    the segment-bounded walk of RPT_SHADOW_SEGMENT (k_traverse.h
+ *     RPT_SHADOW_KERNEL(name) = name##_seg,  RPT_SHADOW_KERNEL_SEGMENT = true    the segment-bounded walk of RPT_SHADOW_SEGMENT (k_walk.h
  *                                                                                shadow_segment_bound; rpt.h rpt_set_shadow_mode)
  * so that the exact kernels keep their names, their template argument lists and their code.  (One text, not a body template behind two thin __global__
  * functions: through such a wrapper the compiler schedules the exact kernels differently — one to five instructions more in every one of them — and the
@@ -24,29 +24,13 @@ __global__ __launch_bounds__(THREADS) void RPT_SHADOW_KERNEL(k_traverse_shadow)(
     q_extent(q.shadow_cnt, positions, n);
     if (i == 0u && n) atomicAdd(&stats->shadow_rays, (unsigned long long)n);
     if (blockIdx.x * THREADS >= positions) return;             /* block-uniform */
-    const SceneViewGlobal view{sc.nodes, sc.tri_isect};
+    const SceneViewGlobal view{{sc.tri_isect}, sc.nodes};
     if (i >= positions || !q_filled(q.shadow_cnt, i)) return;
     float4 o = q.sh_o[i], d = q.sh_d[i];
     uint32_t tag = __float_as_uint(d.w);
-    uint32_t slot = tag & 0x7fffffffu;
-    bool finish = (tag >> 31) != 0u;
     uint32_t *stack = &lds_stack[threadIdx.x / RPT_WAVE][0][threadIdx.x % RPT_WAVE];
     HitRecord h = traverse_one<STACK, true, SEGMENT>(view, sc.fastdiv_ok, f3(o.x, o.y, o.z), f3(d.x, d.y, d.z), SEGMENT ? shadow_segment_bound(o.w) : o.w, stack);
-    bool visible = h.tri == HIT_MISS;
-    if (visible || finish) {
-        float4 r4 = st.rad[slot];
-        F3 radiance = f3(r4.x, r4.y, r4.z);
-        if (visible) {
-            float4 c = q.sh_c[i];
-            radiance = radiance + mask_nan3(f3(c.x, c.y, c.z));
-        }
-        if (finish) {
-            finish_in_side_stage(st, cfg, slot, radiance, __float_as_uint(r4.w));
-        } else {
-            r4.x = radiance.x; r4.y = radiance.y; r4.z = radiance.z;
-            st.rad[slot] = r4;
-        }
-    }
+    shadow_resolve(st, q, cfg, i, tag, h.tri == HIT_MISS);
 }
 
 /* Shadow rays of an LDS-resident scene, streamed like the extension rays above (persistent workgroups, spans of the dense
@@ -72,7 +56,7 @@ __global__ __launch_bounds__(THREADS) void RPT_SHADOW_KERNEL(k_traverse_shadow_s
     const uint32_t lane = __lane_id(), wave = threadIdx.x / RPT_WAVE;
     if (threadIdx.x == 0u) {
         const uint32_t g = n ? atomicAdd(global_next, SPAN) : 0u;
-        pool.word = g < n ? ((unsigned long long)(g + SPAN < n ? g + SPAN : n) << 32) | g : 0x00000000f0000000ull;
+        pool.word = wg_pool_span(g, SPAN, n);
         pool.lock = 0u;
     }
     __syncthreads();
@@ -82,13 +66,13 @@ __global__ __launch_bounds__(THREADS) void RPT_SHADOW_KERNEL(k_traverse_shadow_s
     F3 ro = f3(0, 0, 0), rd = f3(1, 1, 1), ird = f3(1, 1, 1);
     float max_t = 0.0f;
     LdsWalk w;
-    lds_walk_begin(view, w);
-    w.cur = LDS_DESC_DEAD;
+    walk_begin(view, w);
+    w.cur = SceneViewLds::dead();
     uint32_t entry = 0u;
     bool have = false;
     bool pool_open = true;                                     /* wave-uniform */
     for (;;) {
-        const unsigned long long idle_m = rpt_ballot(w.cur == LDS_DESC_DEAD);
+        const unsigned long long idle_m = rpt_ballot(walk_dead(w));
         const uint32_t n_idle = (uint32_t)__popcll(idle_m);
         if (pool_open && n_idle >= (uint32_t)RPT_STREAM_REFILL) {
             uint32_t base = 0u, got = 0u;
@@ -97,12 +81,12 @@ __global__ __launch_bounds__(THREADS) void RPT_SHADOW_KERNEL(k_traverse_shadow_s
             base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
             got = (uint32_t)__builtin_amdgcn_readfirstlane((int)got);
             pool_open = __builtin_amdgcn_readfirstlane((int)finished) == 0;
-            if (w.cur == LDS_DESC_DEAD) {
+            if (walk_dead(w)) {
                 if (have) {
                     q.sh_c[entry].w = w.res.tri == HIT_MISS ? 0.0f : 1.0f;
                     have = false;
                 }
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle_m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle_m, 0u));
+                const uint32_t rank = rpt_lane_rank(idle_m);
                 if (rank < got && q_filled(q.shadow_cnt, base + rank)) {   /* (a position in the tail of a shard may be empty) */
                     entry = base + rank;
                     const float4 o = q.sh_o[entry], d = q.sh_d[entry];
@@ -111,9 +95,9 @@ __global__ __launch_bounds__(THREADS) void RPT_SHADOW_KERNEL(k_traverse_shadow_s
                     have = true;
                     if (fastdiv_ray_ok(sc.fastdiv_ok, ro, rd)) {
                         ird = f3(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z);
-                        lds_walk_begin(view, w);
+                        walk_begin(view, w);
                     } else {
-                        w.res = traverse_loop_lds<STACK, true, false, FIXED, SEGMENT>(view, ro, rd, rd, max_t, stack);   /* alone; recorded at the next refill */
+                        w.res = traverse_loop<STACK, true, false, FIXED, SEGMENT>(view, ro, rd, rd, max_t, stack);   /* alone; recorded at the next refill */
                     }
                 }
             }
@@ -150,7 +134,7 @@ __attribute__((amdgpu_waves_per_eu(gstream_waves(STACK, WIDTH, COOP), 8)))
     const uint32_t end = begin + SPAN < n ? begin + SPAN : n;
     {
         typedef SceneViewPairsT<COOP> View;
-        const View view = FIXED ? View{sc.gpairs_shadow, sc.glinks_shadow, sc.tri_isect} : View{sc.gpairs, sc.glinks, sc.tri_isect};
+        const View view = FIXED ? View{{sc.tri_isect}, sc.gpairs_shadow, sc.glinks_shadow} : View{{sc.tri_isect}, sc.gpairs, sc.glinks};
         auto stack = lds_stack.column(lane);
         F3 ro = f3(0, 0, 0), rd = f3(1, 1, 1), ird = f3(1, 1, 1);
         float max_t = 0.0f;
@@ -169,7 +153,7 @@ __attribute__((amdgpu_waves_per_eu(gstream_waves(STACK, WIDTH, COOP), 8)))
                         occluded[entry - begin] = w.res.tri == HIT_MISS ? (uint8_t)0 : (uint8_t)1;
                         have = false;
                     }
-                    const uint32_t at = next + __builtin_amdgcn_mbcnt_hi((uint32_t)(idle_m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle_m, 0u));
+                    const uint32_t at = next + rpt_lane_rank(idle_m);
                     if (at < end && q_filled(q.shadow_cnt, at)) {
                         const float4 o = q.sh_o[at], d = q.sh_d[at];
                         ro = f3(o.x, o.y, o.z); rd = f3(d.x, d.y, d.z);

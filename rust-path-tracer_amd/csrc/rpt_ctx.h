@@ -189,7 +189,7 @@ struct rpt_ctx {
     DevBuf<float4> nodes, tri_geom, tri_shade, tri_tangent, mat_lite, per_vertex, materials, lds_image, light_rec;
     DevBuf<uint4> indices;
     DevBuf<float> tri_isect;
-    DevBuf<float4> gpairs;                     /* pair records + links of the streamed global-memory walks (k_traverse.h SceneViewPairsT) */
+    DevBuf<float4> gpairs;                     /* pair records + links of the streamed global-memory walks (k_walk.h SceneViewPairsT) */
     DevBuf<uint32_t> glinks;
     DevBuf<float4> lds_image_shadow, gpairs_shadow;   /* the same tree with its pairs flipped for the fixed-order any-hit walks (shadow_order.h) */
     DevBuf<uint32_t> glinks_shadow;

@@ -158,7 +158,7 @@ __global__ __launch_bounds__(RPT_BLOCK) void k_debug_load_rays(DevState st, uint
     if (i >= n) return;
     st.ray_a[i] = make_float4(origins[3 * i], origins[3 * i + 1], origins[3 * i + 2], dirs[3 * i]);
     st.ray_b[i] = make_float2(dirs[3 * i + 1], dirs[3 * i + 2]);
-    st.hit[i] = make_float2(0.0f, __uint_as_float(HIT_PENDING));
+    set_hit_word(st, i, HIT_PENDING);
 }
 
 int rpt_debug_trace_rays_production(rpt_ctx *c, size_t n, const float *origins, const float *dirs, float *out_t, uint32_t *out_tri, uint32_t *out_flags) {

@@ -201,7 +201,7 @@ __global__ __launch_bounds__(LT_BLOCK) void k_lt_bins(const float *prob, uint32_
     uint32_t base = block_offsets[blockIdx.x];
     for (uint32_t w = 0; w < wave; ++w) base += wave_cnt[w];
     if (bin) {
-        const uint32_t at = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        const uint32_t at = base + rpt_lane_rank(m);
         keys[at] = lt_key(prob[i]);
         vals[at] = i;
     }

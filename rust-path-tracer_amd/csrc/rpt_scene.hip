@@ -64,7 +64,7 @@ int validate_scene(rpt_ctx *ctx, const rpt_per_vertex_data *pv, size_t nv, const
     return RPT_OK;
 }
 
-/* The LDS-resident traversal image of a small scene (layout and rationale: k_traverse.h, SceneViewLds):
+/* The LDS-resident traversal image of a small scene (layout and rationale: k_walk.h, SceneViewLds):
  *   float4 K_A[P], K_B[P] for K = x, y, z   (L.lo, R.lo, L.hi, R.hi) and (L.hi, R.hi, L.lo, R.lo)
  *   u32    D[P] (padded to 16 bytes)        desc(L) | desc(R) << 16
  *   float4 a[T], e1[T], e2[T]
@@ -110,7 +110,7 @@ bool build_lds_image(const rpt_bvh_node *nodes, size_t nn, const std::vector<flo
 
 }  // namespace
 
-/* The 64-byte pair records + per-node links of the streamed global-memory walks (k_traverse.h SceneViewPairsT) from the uploaded node pool; with `flip`
+/* The 64-byte pair records + per-node links of the streamed global-memory walks (k_walk.h SceneViewPairsT) from the uploaded node pool; with `flip`
  * (shadow_order.h) the two nodes of a flipped pair exchange slots: the copy the fixed-order shadow walks read.  (On the host this loop took 27 ms for 2 M nodes.) */
 __global__ __launch_bounds__(RPT_BLOCK) void k_build_pairs(const float4 *nodes, const uint8_t *flip, uint32_t n_pairs, float4 *pairs, uint32_t *links) {
     const uint32_t p = blockIdx.x * RPT_BLOCK + threadIdx.x;
@@ -218,7 +218,7 @@ static int device_validate_tree(rpt_ctx *c, const rpt_bvh_node *d_nodes, size_t 
     return RPT_OK;
 }
 
-/* what the pair records of the streamed global-memory walks (k_traverse.h SceneViewPairsT) and the flipped copies can express: children of every inner node
+/* what the pair records of the streamed global-memory walks (k_walk.h SceneViewPairsT) and the flipped copies can express: children of every inner node
  * are the nodes (2p + 1, 2p + 2) of one pair — every pool the reference's builder makes (src/bvh.rs:296-320) —, leaves of fewer than 255 triangles, links in 24 bits.
  * `every_node_fits`: no node of the pool has bit 2 of NodeFacts::flags (k_node_flags on the device, the loop below on the host) */
 static bool pool_is_pair_shaped(const rpt_bvh_node *nodes, size_t nn, bool every_node_fits) {
@@ -418,7 +418,7 @@ static int upload_lds_image(rpt_ctx *c, const Upload &u, const std::vector<uint8
     return RPT_OK;
 }
 
-/* pair records + links of the streamed global-memory walks (k_traverse.h SceneViewPairsT) over the context's node pool, with the pairs `flip` marks
+/* pair records + links of the streamed global-memory walks (k_walk.h SceneViewPairsT) over the context's node pool, with the pairs `flip` marks
  * flipped (null: none) */
 static int build_pair_records(rpt_ctx *c, const Upload &u, const std::vector<uint8_t> *flip, DevBuf<float4> &pairs, DevBuf<uint32_t> &links) {
     const uint32_t n_pairs = u.n_pairs;
@@ -563,7 +563,7 @@ static int upload_images(rpt_ctx *c, Upload &u) {
     return RPT_OK;
 }
 
-/* what the walks read instead of the node pool: the LDS image of a small scene, the pair records of the streamed global-memory walks (k_traverse.h) */
+/* what the walks read instead of the node pool: the LDS image of a small scene, the pair records of the streamed global-memory walks (k_walk.h) */
 static int build_walk_structures(rpt_ctx *c, Upload &u) {
     DevScene &s = c->scene;
     s.lds_scene = 0u; s.lds_pairs = s.lds_vecs = s.lds_root = 0u;
@@ -579,7 +579,7 @@ static int build_walk_structures(rpt_ctx *c, Upload &u) {
     return RPT_OK;
 }
 
-/* The last extension rays of a batch without NEE only have to say "hit or miss" unless they can end on an emitter (k_traverse.h
+/* The last extension rays of a batch without NEE only have to say "hit or miss" unless they can end on an emitter (k_traverse_nearest.h
  * k_traverse_nearest_stream LAST): the triangles whose material emits (lib.rs:86: emissive.xyz() != 0, a NaN counts), if they are few enough to test
  * each ray against.  Then both order decisions by probe rays, as kernels over the buffers just uploaded (shadow_order.h; round 5 walked the rays on the
  * host: 17 - 40 ms of a 1 M-triangle upload). */
@@ -627,7 +627,7 @@ static int upload_last_copy(rpt_ctx *c, Upload &u) {
     s.last_flip_vecs = 0u;
     if (u.want_last) {
         const size_t flip_vecs = 6 * (size_t)s.lds_pairs + ((size_t)s.lds_pairs + 3) / 4;
-        /* room: two 1 024-thread workgroups per CU (k_traverse.h), i.e. half of what THIS device's CU holds (160 KB on MI355X; a partitioned or older device
+        /* room: two 1 024-thread workgroups per CU (k_walk_stream.h), i.e. half of what THIS device's CU holds (160 KB on MI355X; a partitioned or older device
          * reports less and simply gets no flipped copy), minus the kernel's static LDS as the code object states it */
         size_t lds_room = 0;
         hipDeviceProp_t prop;

@@ -103,7 +103,7 @@ bool launch_nearest(rpt_ctx *c, uint32_t iteration, bool last_without_nee = fals
 }
 
 /* the streamed global-memory any-hit walk (FIXED: over the flipped copy, left child first — shadow_order.h; the `_seg` twins: the context is in
- * RPT_SHADOW_SEGMENT mode, k_traverse.h shadow_segment_bound) */
+ * RPT_SHADOW_SEGMENT mode, k_walk.h shadow_segment_bound) */
 template <int STACK, bool COOP>
 static void launch_shadow_gstream(rpt_ctx *c, uint32_t q_positions) {
     const int width = gstream_stack_width<STACK>(c);

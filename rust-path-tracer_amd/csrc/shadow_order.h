@@ -12,7 +12,7 @@
  * per (ray, node) and breadth-first against intersect_front_to_back<false> on 10^6 rays).  Nearest-hit walks have no such freedom: their
  * order decides ties in t (k_traverse.h header).
  * (All of this is the EXACT walk, whose boxes are pruned against the constant 1e6 and never against the ray's max_t.  The opt-in RPT_SHADOW_SEGMENT walk —
- * rpt.h rpt_set_shadow_mode, k_traverse.h shadow_segment_bound — also leaves out boxes with tmin > max_t; that predicate too reads the box and the ray
+ * rpt.h rpt_set_shadow_mode, k_walk.h shadow_segment_bound — also leaves out boxes with tmin > max_t; that predicate too reads the box and the ray
  * alone, so its `.hit` is as independent of the visiting order, and it walks the order chosen here: the probe below is not re-run under the bounded rule.)
  *
  * What the freedom is worth (tools/anyhit_order_sim.py, profiles/r05_anyhit_order_sim.txt): an UNOCCLUDED ray visits the same nodes under
@@ -65,7 +65,7 @@ struct ShadowOrder {
     const char *why = "no lights";
 };
 
-/* ---- the hit-or-miss lanes of the last extension rays (k_traverse.h k_traverse_nearest_stream LAST) -------------------------------------------------
+/* ---- the hit-or-miss lanes of the last extension rays (k_traverse_nearest.h k_traverse_nearest_stream LAST) -------------------------------------------------
  * Without NEE the last extension ray of a path that cannot end on an emitter only has to say "hit or miss": the part of the reference's walk up to its first
  * accepted triangle, which is an any-hit walk (result.t is 1e6 throughout) and as free in its order as a shadow query.  These rays are not shadow rays — they
  * leave a surface in a direction the BSDF drew, and in a closed scene all of them hit — so the order is chosen on rays of their kind: points by area on the

@@ -104,7 +104,7 @@ def test_a_flipped_tree_is_the_same_tree(sim, hipmod, oracle, rpt, world):
 
 @pytest.mark.parametrize("scene", ["DarkCornell", "PBRTest"])
 def test_the_nearest_walk_says_hit_at_its_first_accept_in_any_order(sim, oracle, rpt, world, scene):
-    """What the last extension rays of a batch without NEE rest on (k_traverse.h k_traverse_nearest_stream LAST): intersect_nearest's `.hit`
+    """What the last extension rays of a batch without NEE rest on (k_traverse_nearest.h k_traverse_nearest_stream LAST): intersect_nearest's `.hit`
     (intersection.rs:169-171) is decided at the first triangle its walk accepts — result.t is 1e6 until then, exactly the any-hit walk with
     max_t = 1e6 — so it equals the any-hit answer under EVERY visiting order; and a ray whose nearest hit is an emissive triangle passes that
     triangle's Moller-Trumbore test (so a ray that passes none cannot end on one)."""

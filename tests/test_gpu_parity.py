@@ -1060,7 +1060,7 @@ def test_randomised_configurations_equal_the_oracle(seed):
 def test_unsplittable_fat_leaf_parity(renderer, oracle, rpt, nee, n_stack):
     """n_stack triangles with one centroid stay ONE leaf (tests/scenes.py fat_leaf_scene): too fat for the LDS image.  220: the streamed
     global-memory walk with the wave-cooperative leaf test over several rounds of 64 lanes; 300: more than the 254 triangles a link of the
-    walk's pair records can count (k_traverse.h SceneViewPairsT), so the scene keeps the one-shot generic walks over the reference's own node
+    walk's pair records can count (k_walk.h SceneViewPairsT), so the scene keeps the one-shot generic walks over the reference's own node
     array — image, rng and ray counts equal the oracle's, and so does every single ray."""
     from scenes import fat_leaf_scene
     w = fat_leaf_scene(n_stack)

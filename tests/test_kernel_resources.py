@@ -39,7 +39,7 @@ def _find(table, prefix):
 def test_streamed_lds_walks_fit_two_workgroups_per_cu(resources, kernel):
     for vgpr, sgpr, scratch, lds in _find(resources, kernel):
         assert vgpr <= 64 and scratch == 0
-        assert sgpr <= 80                     # 82 halves the occupancy (k_traverse.h RPT_LDS_WALK_SGPRS): measured, not reported by the occupancy API
+        assert sgpr <= 80                     # 82 halves the occupancy (k_walk_stream.h RPT_LDS_WALK_SGPRS): measured, not reported by the occupancy API
         assert lds <= 32 * 1024 + 64          # 16-bit stacks of 16 waves + the pool; the scene image (<= 32 KB) is dynamic
 
 
@@ -93,7 +93,7 @@ def test_no_stage_kernel_of_the_shipped_scenes_spills(resources):
 
 
 def test_scalar_cache_path_of_the_global_walks_survives_the_compiler(tmp_path):
-    """The wave-uniform node visit of the streamed nearest-hit walk (k_traverse.h children_uniform) lives on two things the optimiser undid when it
+    """The wave-uniform node visit of the streamed nearest-hit walk (k_walk.h children_uniform) lives on two things the optimiser undid when it
     was first written: the scalar load with scalar-operand slab tests behind it (sunk into a common tail it needs fourteen v_mov), and the vector
     loads staying on the other side of the branch (hoisted above it they are issued on every step).  Checked in the ISA of the built library: the
     kernel holds s_load_dwordx16, v_sub_f32 with a scalar first operand right behind it, and no vector load between the uniformity test and it."""

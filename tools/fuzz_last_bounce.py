@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Randomised differential test (GPU box) aimed at the hit-or-miss walks of a batch's last extension rays (k_traverse.h k_traverse_nearest_stream LAST):
+"""Randomised differential test (GPU box) aimed at the hit-or-miss walks of a batch's last extension rays (k_traverse_nearest.h k_traverse_nearest_stream LAST):
 no NEE, scenes that live in LDS (DarkCornell, with random further materials made emissive — 2 .. many emissive triangles, NaN and negative emission
 included — and the open textured scene with and without its image skybox), random size / camera / bounce limits / sample counts on both sides of the
 known-length limit / samples in flight / sun, and the order forced to each of its five settings or left to the probe.  The HIP path must equal the

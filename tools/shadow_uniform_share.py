@@ -2,7 +2,7 @@
 """Would the SHADOW walks of a mid-size scene become wave-uniform if their rays were dealt grouped by light?  (CPU analysis, no GPU.)
 
 The any-hit walks of VeachMIS keep the texture-address unit 87 % busy (profiles/r04_veachmis_pmc_ta.txt) and are its dominant kernel.  The nearest-hit walks
-got a scalar-cache path for wave-uniform node visits (k_traverse.h children_uniform); shadow rays of a wave start on neighbouring surface points but aim at
+got a scalar-cache path for wave-uniform node visits (k_walk.h children_uniform); shadow rays of a wave start on neighbouring surface points but aim at
 RANDOM light triangles.  This replays the any-hit walks of the bounce-0 shadow rays of random 8 x 8 pixel blocks, S samples each, dealt to 64-lane waves
   slot    as the queue holds them today: a wave = the block at one sample index
   light   the block's S x 64 rays sorted by light-table index (the table follows triangle order: one emitter's triangles are contiguous), then cut into waves
