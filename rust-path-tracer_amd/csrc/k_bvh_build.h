@@ -231,7 +231,7 @@ __device__ __forceinline__ uint32_t bvb_count_left(const BvbArgs &a, uint32_t be
  * bvh.rs:214-229 grows the bin's box by the triangle's three vertices: nine coordinates, eighteen min / max folds.  The fold over a triangle's own three vertices
  * is taken once, by k_bvb_init (BvbRec; bvb_rec_keys: six keys per triangle, the same for every axis): 7 LDS atomics per triangle and axis instead of 19.  What
  * they cost is decided by how many lanes of a wave meet on one address — an LDS atomic is served lane by lane —, hence bvb_scatter_index below, and the wave's
- * own fold (bvb_wave_fold) before anything that every thread of a workgroup would add to the same word (the node's bounds). */
+ * own fold (bvb_range_bounds) before anything that every thread of a workgroup would add to the same word (the node's bounds). */
 __device__ __forceinline__ void bvb_rec_keys(const float4 &mn, const float4 &mx, uint32_t i, bool valid, unsigned long long k6[6]) {
     for (int j = 0; j < 3; ++j) { k6[j] = BVB_MIN_IDENT; k6[3 + j] = BVB_MAX_IDENT; }
     if (!valid) return;
@@ -246,14 +246,31 @@ __device__ __forceinline__ unsigned long long bvb_shfl_xor_u64(unsigned long lon
     const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d, 64);
     return ((unsigned long long)hi << 32) | lo;
 }
-__device__ __forceinline__ void bvb_wave_fold(const unsigned long long k6[6], unsigned long long out[6]) {
-    for (int j = 0; j < 6; ++j) out[j] = k6[j];
-    for (int d = 32; d >= 1; d >>= 1)
+/* six running keys and the six centroid codes beside them (ord(min) x3, ord(max) x3), folded over the W lanes of a group: the wave (W = 64) or its aligned
+ * eight-lane groups (W = 8); every lane of the group ends up holding the group's fold */
+template <int W>
+__device__ __forceinline__ void bvb_group_fold(unsigned long long red[6], uint32_t cb[6]) {
+    for (int d = W / 2; d >= 1; d >>= 1)
         for (int j = 0; j < 3; ++j) {
-            const unsigned long long a = bvb_shfl_xor_u64(out[j], d), b = bvb_shfl_xor_u64(out[3 + j], d);
-            out[j] = a < out[j] ? a : out[j];
-            out[3 + j] = b > out[3 + j] ? b : out[3 + j];
+            const unsigned long long x = bvb_shfl_xor_u64(red[j], d), y = bvb_shfl_xor_u64(red[3 + j], d);
+            red[j] = x < red[j] ? x : red[j];
+            red[3 + j] = y > red[3 + j] ? y : red[3 + j];
+            const uint32_t lo = (uint32_t)__shfl_xor((int)cb[j], d, 64), hi = (uint32_t)__shfl_xor((int)cb[3 + j], d, 64);
+            cb[j] = lo < cb[j] ? lo : cb[j];
+            cb[3 + j] = hi > cb[3 + j] ? hi : cb[3 + j];
         }
+}
+/* update_node_aabb over a group whose lanes hold one triangle each (keys k6, centroid cc; !have: none): the fold of the keys and of the centroid codes */
+template <int W>
+__device__ __forceinline__ void bvb_group_bounds(const unsigned long long k6[6], const float cc[3], bool have, unsigned long long red[6], uint32_t cb[6]) {
+    for (int j = 0; j < 3; ++j) {
+        uint32_t nz;
+        const uint32_t o = bvb_ord(cc[j], nz);
+        cb[j] = have ? o : 0xffffffffu;
+        cb[3 + j] = have ? o : 0u;
+    }
+    for (int j = 0; j < 6; ++j) red[j] = k6[j];
+    bvb_group_fold<W>(red, cb);
 }
 /* the element a thread takes in the bin pass: NOT its neighbour's neighbour.  In spatially ordered input (a scene file's meshes, an earlier build's leaf order)
  * the 64 triangles at consecutive positions fall into one or two bins of every axis, and an LDS atomic on one address is served lane by lane: the bin pass took
@@ -359,37 +376,36 @@ __device__ __forceinline__ void bvb_wave_sweep(const unsigned long long (*key)[6
     best_i = cost == __builtin_inff() ? 0u : at;
 }
 
-/* THREADS = 1024 for levels whose largest node has 16 384+ triangles or that have fewer than 64 nodes (a workgroup walks its node's whole range), 256 below, 64 — one
- * wave per node — for levels whose largest node has at most 256 triangles (nodes of up to 64 go to k_bvb_small, of up to 8 to k_bvb_tiny) */
+/* ---- the steps of a split, one copy each ---------------------------------------------------------------------------------------------------------------------
+ * Node bounds and centroid bounds, binning, the sweep (bvb_wave_sweep above), the choice of axis with the leaf test, the closed-form partition: the four split
+ * kernels below are these steps over a range of positions (k_bvb_level: the node's; k_bvb_team: a workgroup's chunk of it) or out of registers (k_bvb_small,
+ * k_bvb_tiny: a lane per triangle). */
+
+/* position -> triangle -> what the build reads of it (BvbRec): box and centroid, zeros when !have */
+__device__ __forceinline__ void bvb_fetch(const BvbArgs &a, uint32_t pos, bool have, uint32_t &tri, float4 &r_mn, float4 &r_mx, float cc[3]) {
+    tri = 0u;
+    r_mn = make_float4(0, 0, 0, 0); r_mx = make_float4(0, 0, 0, 0);
+    cc[0] = 0.0f; cc[1] = 0.0f; cc[2] = 0.0f;
+    if (have) {
+        tri = a.order[pos];
+        r_mn = a.recs[tri].mn; r_mx = a.recs[tri].mx;
+        const float4 ce = a.recs[tri].ce;
+        cc[0] = ce.x; cc[1] = ce.y; cc[2] = ce.z;
+    }
+}
+
+/* update_node_aabb (bvh.rs:85-103) and the centroid bounds over positions [begin, end) of the node that starts at `first` (an element's sequence number is its
+ * position - first), sequential tie-breaking reproduced by the keys: the workgroup's fold into s_red[6] (keys) and s_cb[6] (centroid bounds: ord(min) x3,
+ * ord(max) x3), both complete for every thread on return; every thread calls */
 template <int THREADS>
-__global__ __launch_bounds__(THREADS) void k_bvb_level(BvbArgs a, uint32_t level_begin, uint32_t skip_upto) {
-    constexpr uint32_t AXES = THREADS >= 192 ? 3u : 1u;            /* axes binned at once */
-    __shared__ unsigned long long s_key[AXES][BVB_MAX_BINS][6];   /* [axis][bin]: min x,y,z  max x,y,z */
-    __shared__ uint32_t s_cnt[AXES][BVB_MAX_BINS];
-    __shared__ unsigned long long s_red[6];
-    __shared__ uint32_t s_cb[6];                                  /* centroid bounds: ord(min) x3, ord(max) x3 */
-    __shared__ float s_best_cost[3];
-    __shared__ uint32_t s_best_i[3];
-    __shared__ uint32_t s_wave_tot[THREADS / 64];
-    __shared__ float s_split;
-    __shared__ int s_axis;
-
+__device__ __forceinline__ void bvb_range_bounds(const BvbArgs &a, uint32_t first, uint32_t begin, uint32_t end, unsigned long long *s_red, uint32_t *s_cb) {
     const uint32_t tid = threadIdx.x;
-    const uint32_t node_id = level_begin + blockIdx.x;
-    BvbNode &node = a.nodes[node_id];
-    if (node.pad[0] != 0u) return;                 /* already split at this level by a team (k_bvb_team) */
-    const uint32_t first = node.first, count = node.count, S = a.bins;
-    const uint32_t last = first + count - 1u;
-    if (count <= skip_upto) return;                /* a node k_bvb_tiny has taken (0: none) */
-
-    /* ---- update_node_aabb (bvh.rs:85-103), sequential tie-breaking reproduced by the keys */
-    if (tid < 6u) s_red[tid] = tid < 3u ? BVB_MIN_IDENT : BVB_MAX_IDENT;
-    if (tid < 3u) { s_cb[tid] = 0xffffffffu; s_cb[3u + tid] = 0u; }
+    if (tid < 6u) { s_red[tid] = tid < 3u ? BVB_MIN_IDENT : BVB_MAX_IDENT; s_cb[tid] = tid < 3u ? 0xffffffffu : 0u; }
     __syncthreads();
     {
         unsigned long long kmin[3] = {BVB_MIN_IDENT, BVB_MIN_IDENT, BVB_MIN_IDENT}, kmax[3] = {BVB_MAX_IDENT, BVB_MAX_IDENT, BVB_MAX_IDENT};
         uint32_t cmin[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, cmax[3] = {0u, 0u, 0u};
-        for (uint32_t i = tid; i < count; i += THREADS) {
+        for (uint32_t i = begin - first + tid; i < end - first; i += THREADS) {
             const uint32_t tri = a.order[first + i];
             const float4 r_mn = a.recs[tri].mn, r_mx = a.recs[tri].mx, ce = a.recs[tri].ce;
             unsigned long long k6[6];
@@ -426,6 +442,242 @@ __global__ __launch_bounds__(THREADS) void k_bvb_level(BvbArgs a, uint32_t level
             }
     }
     __syncthreads();
+}
+
+/* n bins (of one axis, or of all of them: [axis][bin] is one run of bins) to the identities, by the THREADS threads of the workgroup */
+template <int THREADS>
+__device__ __forceinline__ void bvb_bins_clear(unsigned long long (*key)[6], uint32_t *cnt, uint32_t n) {
+    for (uint32_t k = threadIdx.x; k < n; k += THREADS) {
+        for (int j = 0; j < 6; ++j) key[k][j] = j < 3 ? BVB_MIN_IDENT : BVB_MAX_IDENT;
+        cnt[k] = 0u;
+    }
+}
+
+/* which axes are binned at all, and centroid -> bin (bvh.rs:214-229): scale = S / (bmax - bmin), bin = (c - bmin) * scale `as usize` (saturating), then min(S - 1) */
+__device__ __forceinline__ void bvb_axis_scales(const float bmin[3], const float bmax[3], uint32_t S, bool axis_on[3], float scale[3]) {
+    for (int j = 0; j < 3; ++j) {
+        axis_on[j] = !(bmin[j] == bmax[j]);
+        scale[j] = (float)S / (bmax[j] - bmin[j]);
+    }
+}
+__device__ __forceinline__ uint32_t bvb_bin_of(float c, float bmin, float scale, uint32_t S) {
+    const float x = (c - bmin) * scale;
+    uint32_t si = x > 0.0f ? (x >= (float)S ? S - 1u : (uint32_t)x) : 0u;      /* `as usize` then min(S-1) */
+    if (si > S - 1u) si = S - 1u;
+    return si;
+}
+
+/* the bin pass over the n positions from `begin` of the node that starts at `first`: position dealt to the thread (bvb_scatter_index), fetch, six keys, into
+ * its bin of every live axis — all three at once (AXES = 3) or axis `pass` through the one set of bins (AXES = 1) */
+template <int THREADS, uint32_t AXES>
+__device__ __forceinline__ void bvb_bin_pass(const BvbArgs &a, uint32_t first, uint32_t begin, uint32_t n, uint32_t pass, const bool axis_on[3], const float bmin[3],
+                                             const float scale[3], uint32_t S, unsigned long long (*s_key)[BVB_MAX_BINS][6], uint32_t (*s_cnt)[BVB_MAX_BINS]) {
+    const uint32_t tid = threadIdx.x, deal_mask = bvb_mask_for(n);
+    for (uint32_t base = 0; base < n; base += THREADS) {
+        const bool have = base + tid < n;
+        const uint32_t pos = begin + (have ? bvb_scatter_index(base + tid, n, deal_mask) : 0u);
+        const uint32_t i = pos - first;
+        uint32_t tri;
+        float4 r_mn, r_mx;
+        float cc[3];
+        bvb_fetch(a, pos, have, tri, r_mn, r_mx, cc);
+        unsigned long long k6[6];
+        bvb_rec_keys(r_mn, r_mx, i, have, k6);
+        for (uint32_t slot = 0; slot < AXES; ++slot) {
+            const uint32_t ax = AXES == 3u ? slot : pass;
+            if (!axis_on[ax]) continue;
+            bvb_bin_add(s_key[slot], s_cnt[slot], have, bvb_bin_of(cc[ax], bmin[ax], scale[ax], S), k6);
+        }
+    }
+}
+
+/* waves 0, 1, 2 sweep one axis each (bvb_wave_sweep) and leave its best candidate in s_best_cost / s_best_i */
+__device__ __forceinline__ void bvb_sweep_three_axes(const unsigned long long (*s_key)[BVB_MAX_BINS][6], const uint32_t (*s_cnt)[BVB_MAX_BINS], uint32_t S,
+                                                     const bool axis_on[3], float *s_best_cost, uint32_t *s_best_i) {
+    const uint32_t tid = threadIdx.x;
+    if (tid < 192u) {
+        const uint32_t ax = tid >> 6;
+        float best_cost = __builtin_inff();
+        uint32_t best_i = 0u;
+        if (axis_on[ax]) bvb_wave_sweep(s_key[ax], s_cnt[ax], S, best_cost, best_i);
+        if ((tid & 63u) == 0u) { s_best_cost[ax] = best_cost; s_best_i[ax] = best_i; }
+    }
+}
+
+/* the plane behind candidate i of an axis (bvh.rs:252), and the axis of least cost so far: an axis takes over only with a cost BELOW the earlier axes' */
+__device__ __forceinline__ float bvb_split_plane(float bmin, float bmax, uint32_t S, uint32_t i) {
+    const float scale2 = (bmax - bmin) / (float)S;
+    return bmin + scale2 * (float)(i + 1u);
+}
+__device__ __forceinline__ void bvb_take_axis(int ax, float best_cost, uint32_t best_i, const float bmin[3], const float bmax[3], uint32_t S, float &cost, int &axis, float &split) {
+    if (best_cost < cost) {
+        cost = best_cost;
+        axis = ax;
+        split = bvb_split_plane(bmin[ax], bmax[ax], S, best_i);
+    }
+}
+/* bvh.rs:272-277: splitting must cost less than the node as a leaf */
+__device__ __forceinline__ bool bvb_stays_leaf(const float nmn[3], const float nmx[3], uint32_t count, float cost) {
+    BvbBox nb;
+    for (int j = 0; j < 3; ++j) { nb.mn[j] = nmn[j]; nb.mx[j] = nmx[j]; }
+    const float parent_cost = bvb_area(nb) * (float)count;
+    return parent_cost <= cost;
+}
+/* one thread, after the three sweeps: the split's axis (-1: the node stays a leaf) and plane */
+__device__ __forceinline__ void bvb_choose_split(const float *s_best_cost, const uint32_t *s_best_i, const float bmin[3], const float bmax[3], const float nmn[3],
+                                                 const float nmx[3], uint32_t count, uint32_t S, int &axis_out, float &split_out) {
+    int axis = 0;
+    float split = 0.0f, cost = __builtin_inff();
+    for (int ax = 0; ax < 3; ++ax) bvb_take_axis(ax, s_best_cost[ax], s_best_i[ax], bmin, bmax, S, cost, axis, split);
+    axis_out = bvb_stays_leaf(nmn, nmx, count, cost) ? -1 : axis;
+    split_out = split;
+}
+
+/* ---- the partition (bvh.rs:281-292) in closed form (file header), every quantity from L(p) = left-side elements before p (bvb_count_left: the word in a.lpre
+ * counts from the start of the counting workgroup's range, pref_l = the left-side elements before that range — 0 for a workgroup that has the whole node):
+ * hole rank of a prefix position p = (p - first) - L(p);  for a suffix position q: m(q) = nl - L(q + 1) left-side elements above it, rb(q) = (last - q) - m(q)
+ * right-side elements above it.  prefix = [first, first + nl), suffix = [first + nl, last]; each pass takes the part of it that lies in [lo, hi), and what
+ * another workgroup of a team may have written is read at agent scope (AGENT). */
+template <bool AGENT>
+__device__ __forceinline__ uint32_t bvb_ld(const uint32_t *p) {
+    if (AGENT) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return *p;
+}
+/* the rank (from `last` downwards) of a suffix right-side element with m left-side and rb right-side elements above it: after min(m + 1, H) holes — except in
+ * the tail below the lowest suffix left-side element, where the element AT the split position is met first */
+__device__ __forceinline__ uint32_t bvb_suffix_right_rank(uint32_t m, uint32_t H, uint32_t rb, bool at_split, uint32_t base_rb) {
+    uint32_t rank;
+    if (m == H) rank = at_split ? H + base_rb : H + rb + 1u;
+    else rank = (m + 1u) + rb;
+    return rank;
+}
+/* pass B1: rb_at_L[m] = right-side elements above the m-th left-side element of the suffix (counted from the top) */
+template <int THREADS>
+__device__ __forceinline__ void bvb_part_b1(const BvbArgs &a, uint32_t lo, uint32_t hi, uint32_t first, uint32_t last, uint32_t nl, uint32_t pref_l) {
+    const uint32_t split_pos = first + nl;
+    for (uint32_t q = (lo > split_pos ? lo : split_pos) + threadIdx.x; q < hi; q += THREADS) {
+        const uint32_t w = a.lpre[q];
+        if (w & 1u) {
+            const uint32_t m = nl - (pref_l + (w >> 1) + 1u);
+            a.tmp_b[first + m] = (last - q) - m;
+        }
+    }
+}
+/* pass F: the prefix */
+template <int THREADS, bool AGENT>
+__device__ __forceinline__ void bvb_part_f(const BvbArgs &a, uint32_t lo, uint32_t hi, uint32_t first, uint32_t last, uint32_t nl, uint32_t pref_l) {
+    const uint32_t split_pos = first + nl;
+    for (uint32_t p = lo + threadIdx.x; p < hi && p < split_pos; p += THREADS) {
+        const uint32_t w = a.lpre[p];
+        if (w & 1u) {
+            a.order_tmp[p] = a.order[p];
+        } else {
+            const uint32_t hole = (p - first) - (pref_l + (w >> 1));
+            const uint32_t rank = hole + (hole >= 1u ? bvb_ld<AGENT>(&a.tmp_b[first + hole - 1u]) : 0u);
+            a.order_tmp[last - rank] = a.order[p];
+            a.tmp_a[first + hole] = p;
+        }
+    }
+}
+/* pass B2: the suffix, now every destination is known */
+template <int THREADS, bool AGENT>
+__device__ __forceinline__ void bvb_part_b2(const BvbArgs &a, uint32_t lo, uint32_t hi, uint32_t first, uint32_t last, uint32_t nl, uint32_t pref_l, uint32_t H,
+                                            uint32_t base_rb) {
+    const uint32_t split_pos = first + nl;
+    for (uint32_t q = (lo > split_pos ? lo : split_pos) + threadIdx.x; q < hi; q += THREADS) {
+        const uint32_t w = a.lpre[q];
+        const uint32_t l_before = pref_l + (w >> 1);
+        if (w & 1u) {
+            const uint32_t m = nl - (l_before + 1u);
+            a.order_tmp[bvb_ld<AGENT>(&a.tmp_a[first + m])] = a.order[q];
+        } else {
+            const uint32_t m = nl - l_before;
+            const uint32_t rb = (last - q) - m;
+            a.order_tmp[last - bvb_suffix_right_rank(m, H, rb, q == split_pos, base_rb)] = a.order[q];
+        }
+    }
+}
+/* the new order of [lo, hi) back into a.order */
+template <int THREADS, bool AGENT>
+__device__ __forceinline__ void bvb_part_copy_back(const BvbArgs &a, uint32_t lo, uint32_t hi) {
+    for (uint32_t pos = lo + threadIdx.x; pos < hi; pos += THREADS) a.order[pos] = bvb_ld<AGENT>(&a.order_tmp[pos]);
+}
+
+/* The same partition for a group of W lanes (the wave, or its eight-lane group from lane g0) that holds one element per lane — lane l of the group has element
+ * first + l (triangle tri; act: it has one; L: it goes left): the running counts are bits of a ballot.  Moves the elements in a.order and returns nl; every
+ * lane of the workgroup calls (s_rb, s_hole_at: 64 words each). */
+template <int W> struct BvbGroupBits { typedef uint32_t type; };
+template <> struct BvbGroupBits<64> { typedef unsigned long long type; };
+__device__ __forceinline__ uint32_t bvb_popc(uint32_t m) { return (uint32_t)__popc(m); }
+__device__ __forceinline__ uint32_t bvb_popc(unsigned long long m) { return (uint32_t)__popcll(m); }
+template <int W>
+__device__ __forceinline__ uint32_t bvb_ballot_partition(const BvbArgs &a, uint32_t first, uint32_t count, uint32_t tri, bool act, bool L, uint32_t l, uint32_t g0,
+                                                         uint32_t *s_rb, uint32_t *s_hole_at) {
+    typedef typename BvbGroupBits<W>::type M;
+    constexpr uint32_t BITS = 8u * (uint32_t)sizeof(M);
+    const M full = ~(M)0 >> (BITS - (uint32_t)W);
+    const M grp_l = (M)(__builtin_amdgcn_ballot_w64(L) >> g0) & full, grp = (M)(__builtin_amdgcn_ballot_w64(act) >> g0) & full;
+    const uint32_t nl = bvb_popc(grp_l);
+    const M below_nl = nl >= BITS ? ~(M)0 : (((M)1 << nl) - (M)1);
+    const M pre_r = grp & ~grp_l & below_nl, suf_l = grp_l & ~below_nl, suf_r = grp & ~grp_l & ~below_nl;
+    const M above = (l + 1u >= BITS ? (M)0 : (~(M)0 << (l + 1u))) & full, under = ((M)1 << l) - (M)1;
+    const uint32_t H = bvb_popc(suf_l);
+    const bool in_prefix = l < nl;
+    const uint32_t m = bvb_popc(suf_l & above), rb = bvb_popc(suf_r & above);        /* suffix lanes: left / right elements above */
+    const uint32_t hole = bvb_popc(pre_r & under);                                 /* prefix lanes: holes below */
+    if (act && !in_prefix && L) s_rb[g0 + m] = rb;
+    if (act && in_prefix && !L) s_hole_at[g0 + hole] = l;
+    __syncthreads();
+    if (act) {
+        const uint32_t last_i = count - 1u;
+        uint32_t dest = l;                                            /* a left-side element of the prefix stays */
+        if (in_prefix && !L) {
+            dest = last_i - (hole + (hole >= 1u ? s_rb[g0 + hole - 1u] : 0u));
+        } else if (!in_prefix && L) {
+            dest = s_hole_at[g0 + m];
+        } else if (!in_prefix) {
+            const uint32_t base_rb = H >= 1u ? s_rb[g0 + H - 1u] : 0u;
+            dest = last_i - bvb_suffix_right_rank(m, H, rb, l == nl, base_rb);
+        }
+        a.order[first + dest] = tri;
+    }
+    return nl;
+}
+
+/* bvh.rs:296-320: the two children of a node that was split after its nl-th triangle, at build-order ids id and id + 1 */
+__device__ __forceinline__ void bvb_make_children(const BvbArgs &a, uint32_t id, uint32_t first, uint32_t count, uint32_t nl) {
+    BvbNode l{}, r{};
+    l.first = first;      l.count = nl;         l.left = BVB_NONE;
+    r.first = first + nl; r.count = count - nl; r.left = BVB_NONE;
+    a.nodes[id] = l;
+    a.nodes[id + 1u] = r;
+}
+
+/* THREADS = 1024 for levels whose largest node has 16 384+ triangles or that have fewer than 64 nodes (a workgroup walks its node's whole range), 256 below, 64 — one
+ * wave per node — for levels whose largest node has at most 256 triangles (nodes of up to 64 go to k_bvb_small, of up to 8 to k_bvb_tiny) */
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void k_bvb_level(BvbArgs a, uint32_t level_begin, uint32_t skip_upto) {
+    constexpr uint32_t AXES = THREADS >= 192 ? 3u : 1u;            /* axes binned at once */
+    __shared__ unsigned long long s_key[AXES][BVB_MAX_BINS][6];   /* [axis][bin]: min x,y,z  max x,y,z */
+    __shared__ uint32_t s_cnt[AXES][BVB_MAX_BINS];
+    __shared__ unsigned long long s_red[6];
+    __shared__ uint32_t s_cb[6];                                  /* centroid bounds: ord(min) x3, ord(max) x3 */
+    __shared__ float s_best_cost[3];
+    __shared__ uint32_t s_best_i[3];
+    __shared__ uint32_t s_wave_tot[THREADS / 64];
+    __shared__ float s_split;
+    __shared__ int s_axis;
+
+    const uint32_t tid = threadIdx.x;
+    const uint32_t node_id = level_begin + blockIdx.x;
+    BvbNode &node = a.nodes[node_id];
+    if (node.pad[0] != 0u) return;                 /* already split at this level by a team (k_bvb_team) */
+    const uint32_t first = node.first, count = node.count, S = a.bins;
+    const uint32_t last = first + count - 1u;
+    if (count <= skip_upto) return;                /* a node k_bvb_tiny has taken (0: none) */
+
+    /* ---- update_node_aabb (bvh.rs:85-103), sequential tie-breaking reproduced by the keys */
+    bvb_range_bounds<THREADS>(a, first, first, first + count, s_red, s_cb);
     if (tid < 3u) {
         node.mn[tid] = bvb_key_value(s_red[tid]);
         node.mx[tid] = bvb_key_value(s_red[3u + tid]);
@@ -439,49 +691,14 @@ __global__ __launch_bounds__(THREADS) void k_bvb_level(BvbArgs a, uint32_t level
      * time through ONE set of bins (6 KB instead of 18 KB of LDS: more than twice the nodes in flight per CU, and a small node is all latency) */
     float scale[3];
     bool axis_on[3];
-    for (int j = 0; j < 3; ++j) {
-        axis_on[j] = !(bmin[j] == bmax[j]);
-        scale[j] = (float)S / (bmax[j] - bmin[j]);
-    }
-    const uint32_t deal_mask = bvb_mask_for(count);
+    bvb_axis_scales(bmin, bmax, S, axis_on, scale);
     for (uint32_t pass = 0; pass < 3u / AXES; ++pass) {
-        for (uint32_t k = tid; k < AXES * BVB_MAX_BINS; k += THREADS) {
-            const uint32_t slot = k / BVB_MAX_BINS, b = k % BVB_MAX_BINS;
-            for (int j = 0; j < 6; ++j) s_key[slot][b][j] = j < 3 ? BVB_MIN_IDENT : BVB_MAX_IDENT;
-            s_cnt[slot][b] = 0u;
-        }
+        bvb_bins_clear<THREADS>(s_key[0], s_cnt[0], AXES * BVB_MAX_BINS);
         __syncthreads();
-        for (uint32_t base = 0; base < count; base += THREADS) {
-            const bool have = base + tid < count;
-            const uint32_t i = have ? bvb_scatter_index(base + tid, count, deal_mask) : 0u;
-            float4 r_mn = make_float4(0, 0, 0, 0), r_mx = make_float4(0, 0, 0, 0);
-            float cc[3] = {0.0f, 0.0f, 0.0f};
-            if (have) {
-                const uint32_t tri = a.order[first + i];
-                r_mn = a.recs[tri].mn; r_mx = a.recs[tri].mx;
-                const float4 ce = a.recs[tri].ce;
-                cc[0] = ce.x; cc[1] = ce.y; cc[2] = ce.z;
-            }
-            unsigned long long k6[6];
-            bvb_rec_keys(r_mn, r_mx, i, have, k6);
-            for (uint32_t slot = 0; slot < AXES; ++slot) {
-                const uint32_t ax = AXES == 3u ? slot : pass;
-                if (!axis_on[ax]) continue;
-                const float x = (cc[ax] - bmin[ax]) * scale[ax];
-                uint32_t si = x > 0.0f ? (x >= (float)S ? S - 1u : (uint32_t)x) : 0u;      /* `as usize` then min(S-1) */
-                if (si > S - 1u) si = S - 1u;
-                bvb_bin_add(s_key[slot], s_cnt[slot], have, si, k6);
-            }
-        }
+        bvb_bin_pass<THREADS, AXES>(a, first, first, count, pass, axis_on, bmin, scale, S, s_key, s_cnt);
         __syncthreads();
         if (AXES == 3u) {
-            if (tid < 192u) {                                  /* waves 0, 1, 2: one axis each (bvb_wave_sweep) */
-                const uint32_t ax = tid >> 6;
-                float best_cost = __builtin_inff();
-                uint32_t best_i = 0u;
-                if (axis_on[ax]) bvb_wave_sweep(s_key[ax], s_cnt[ax], S, best_cost, best_i);
-                if ((tid & 63u) == 0u) { s_best_cost[ax] = best_cost; s_best_i[ax] = best_i; }
-            }
+            bvb_sweep_three_axes(s_key, s_cnt, S, axis_on, s_best_cost, s_best_i);
         } else {
             float best_cost = __builtin_inff();
             uint32_t best_i = 0u;
@@ -491,23 +708,7 @@ __global__ __launch_bounds__(THREADS) void k_bvb_level(BvbArgs a, uint32_t level
         }
     }
     __syncthreads();
-    if (tid == 0u) {
-        int axis = 0;
-        float split = 0.0f, cost = __builtin_inff();
-        for (int ax = 0; ax < 3; ++ax) {
-            if (s_best_cost[ax] < cost) {
-                cost = s_best_cost[ax];
-                axis = ax;
-                const float scale2 = (bmax[ax] - bmin[ax]) / (float)S;
-                split = bmin[ax] + scale2 * (float)(s_best_i[ax] + 1u);
-            }
-        }
-        BvbBox nb;
-        for (int j = 0; j < 3; ++j) { nb.mn[j] = nmn[j]; nb.mx[j] = nmx[j]; }
-        const float parent_cost = bvb_area(nb) * (float)count;
-        s_axis = parent_cost <= cost ? -1 : axis;                 /* bvh.rs:272-277 */
-        s_split = split;
-    }
+    if (tid == 0u) bvb_choose_split(s_best_cost, s_best_i, bmin, bmax, nmn, nmx, count, S, s_axis, s_split);
     __syncthreads();
     const int axis = s_axis;
     if (axis < 0) {
@@ -516,57 +717,23 @@ __global__ __launch_bounds__(THREADS) void k_bvb_level(BvbArgs a, uint32_t level
     }
     const float split = s_split;
 
-    /* ---- the partition (bvh.rs:281-292) in closed form (file header), every quantity from L(p) = left-side elements before p (bvb_count_left):
-     * hole rank of a prefix position p = (p - first) - L(p);  for a suffix position q: m(q) = nl - L(q + 1) left-side elements above it, rb(q) = (last - q) - m(q)
-     * right-side elements above it */
+    /* ---- the partition: the counting pass, then B1 / F / B2 over the whole range */
     const uint32_t nl = bvb_count_left<THREADS>(a, first, first + count, axis, split, s_wave_tot);
     __syncthreads();
     __threadfence_block();
     const uint32_t split_pos = first + nl;                         /* prefix = [first, split_pos), suffix = [split_pos, last] */
     const uint32_t H = nl - (nl < count ? (a.lpre[split_pos] >> 1) : nl);      /* holes: right-side elements in the prefix */
-    /* pass B1: rb_at_L[m] = right-side elements above the m-th left-side element of the suffix (counted from the top) */
-    for (uint32_t q = split_pos + tid; q <= last; q += THREADS) {
-        const uint32_t w = a.lpre[q];
-        if (w & 1u) {
-            const uint32_t m = nl - ((w >> 1) + 1u);
-            a.tmp_b[first + m] = (last - q) - m;
-        }
-    }
+    bvb_part_b1<THREADS>(a, first, first + count, first, last, nl, 0u);
     __syncthreads();
     __threadfence_block();
     const uint32_t base_rb = H >= 1u ? a.tmp_b[first + H - 1u] : 0u;
-    /* pass F: the prefix */
-    for (uint32_t p = first + tid; p < split_pos; p += THREADS) {
-        const uint32_t w = a.lpre[p];
-        if (w & 1u) {
-            a.order_tmp[p] = a.order[p];
-        } else {
-            const uint32_t hole = (p - first) - (w >> 1);
-            const uint32_t rank = hole + (hole >= 1u ? a.tmp_b[first + hole - 1u] : 0u);
-            a.order_tmp[last - rank] = a.order[p];
-            a.tmp_a[first + hole] = p;
-        }
-    }
+    bvb_part_f<THREADS, false>(a, first, first + count, first, last, nl, 0u);
     __syncthreads();
     __threadfence_block();
-    /* pass B2: the suffix, now every destination is known */
-    for (uint32_t q = split_pos + tid; q <= last; q += THREADS) {
-        const uint32_t w = a.lpre[q];
-        if (w & 1u) {
-            const uint32_t m = nl - ((w >> 1) + 1u);
-            a.order_tmp[a.tmp_a[first + m]] = a.order[q];
-        } else {
-            const uint32_t m = nl - (w >> 1);
-            const uint32_t rb = (last - q) - m;
-            uint32_t rank;
-            if (m == H) rank = (q == split_pos) ? H + base_rb : H + rb + 1u;
-            else rank = (m + 1u) + rb;
-            a.order_tmp[last - rank] = a.order[q];
-        }
-    }
+    bvb_part_b2<THREADS, false>(a, first, first + count, first, last, nl, 0u, H, base_rb);
     __syncthreads();
     __threadfence_block();
-    for (uint32_t i = tid; i < count; i += THREADS) a.order[first + i] = a.order_tmp[first + i];
+    bvb_part_copy_back<THREADS, false>(a, first, first + count);
 
     /* bvh.rs:294-296: with an empty side the node stays a leaf, its triangles already permuted; otherwise k_bvb_children makes the two children */
     if (tid == 0u) node.pad[1] = (nl == 0u || nl == count) ? 0u : nl;
@@ -603,11 +770,7 @@ __global__ __launch_bounds__(1024) void k_bvb_children(BvbArgs a, uint32_t level
         const uint32_t id = s_base + 2u * rank;
         a.nodes[node_id].left = id;
         a.nodes[node_id].pad[1] = 0u;
-        BvbNode l{}, r{};
-        l.first = first;      l.count = nl;         l.left = BVB_NONE;
-        r.first = first + nl; r.count = count - nl; r.left = BVB_NONE;
-        a.nodes[id] = l;
-        a.nodes[id + 1u] = r;
+        bvb_make_children(a, id, first, count, nl);
     }
 }
 
@@ -633,32 +796,15 @@ __global__ __launch_bounds__(64) void k_bvb_small(BvbArgs a, uint32_t level_begi
         return;
     }
     const bool have = lane < count;
-    uint32_t tri = 0u;
-    float4 r_mn = make_float4(0, 0, 0, 0), r_mx = make_float4(0, 0, 0, 0);
-    float cc[3] = {0.0f, 0.0f, 0.0f};
-    if (have) {
-        tri = a.order[first + lane];
-        r_mn = a.recs[tri].mn; r_mx = a.recs[tri].mx;
-        const float4 ce = a.recs[tri].ce;
-        cc[0] = ce.x; cc[1] = ce.y; cc[2] = ce.z;
-    }
+    uint32_t tri;
+    float4 r_mn, r_mx;
+    float cc[3];
+    bvb_fetch(a, first + lane, have, tri, r_mn, r_mx, cc);
     /* ---- update_node_aabb: the fold of the wave's keys */
     unsigned long long k6[6], red[6];
-    bvb_rec_keys(r_mn, r_mx, lane, have, k6);
-    bvb_wave_fold(k6, red);
     uint32_t cb[6];
-    for (int j = 0; j < 3; ++j) {
-        uint32_t nz;
-        const uint32_t o = bvb_ord(cc[j], nz);
-        cb[j] = have ? o : 0xffffffffu;
-        cb[3 + j] = have ? o : 0u;
-    }
-    for (int d = 32; d >= 1; d >>= 1)
-        for (int j = 0; j < 3; ++j) {
-            const uint32_t lo = (uint32_t)__shfl_xor((int)cb[j], d, 64), hi = (uint32_t)__shfl_xor((int)cb[3 + j], d, 64);
-            cb[j] = lo < cb[j] ? lo : cb[j];
-            cb[3 + j] = hi > cb[3 + j] ? hi : cb[3 + j];
-        }
+    bvb_rec_keys(r_mn, r_mx, lane, have, k6);
+    bvb_group_bounds<64>(k6, cc, have, red, cb);
     if (lane < 3u) {
         node.mn[lane] = bvb_key_value(lane == 0u ? red[0] : (lane == 1u ? red[1] : red[2]));
         node.mx[lane] = bvb_key_value(lane == 0u ? red[3] : (lane == 1u ? red[4] : red[5]));
@@ -673,69 +819,24 @@ __global__ __launch_bounds__(64) void k_bvb_small(BvbArgs a, uint32_t level_begi
     float split = 0.0f, cost = __builtin_inff();
     for (int ax = 0; ax < 3; ++ax) {
         if (bmin[ax] == bmax[ax]) continue;                          /* (uniform: every lane holds the same bounds) */
-        for (uint32_t b = lane; b < BVB_MAX_BINS; b += 64u) {
-            for (int j = 0; j < 6; ++j) s_key[b][j] = j < 3 ? BVB_MIN_IDENT : BVB_MAX_IDENT;
-            s_cnt[b] = 0u;
-        }
+        bvb_bins_clear<64>(s_key, s_cnt, BVB_MAX_BINS);
         __syncthreads();
-        if (have) {
-            const float x = (cc[ax] - bmin[ax]) * ((float)S / (bmax[ax] - bmin[ax]));
-            uint32_t si = x > 0.0f ? (x >= (float)S ? S - 1u : (uint32_t)x) : 0u;
-            if (si > S - 1u) si = S - 1u;
-            for (int j = 0; j < 3; ++j) { atomicMin(&s_key[si][j], k6[j]); atomicMax(&s_key[si][3 + j], k6[3 + j]); }
-            atomicAdd(&s_cnt[si], 1u);
-        }
+        if (have) bvb_bin_add(s_key, s_cnt, true, bvb_bin_of(cc[ax], bmin[ax], (float)S / (bmax[ax] - bmin[ax]), S), k6);
         __syncthreads();
         float best_cost;
         uint32_t best_i;
         bvb_wave_sweep(s_key, s_cnt, S, best_cost, best_i);
         __syncthreads();
-        if (best_cost < cost) {
-            cost = best_cost;
-            axis = ax;
-            const float scale2 = (bmax[ax] - bmin[ax]) / (float)S;
-            split = bmin[ax] + scale2 * (float)(best_i + 1u);
-        }
+        bvb_take_axis(ax, best_cost, best_i, bmin, bmax, S, cost, axis, split);
     }
-    {
-        BvbBox nb;
-        for (int j = 0; j < 3; ++j) { nb.mn[j] = nmn[j]; nb.mx[j] = nmx[j]; }
-        if (bvb_area(nb) * (float)count <= cost) {                   /* bvh.rs:272-277 */
-            if (lane == 0u) node.left = BVB_NONE;
-            return;
-        }
+    if (bvb_stays_leaf(nmn, nmx, count, cost)) {
+        if (lane == 0u) node.left = BVB_NONE;
+        return;
     }
     /* ---- the partition in closed form (file header), its running counts as ballots */
     const float c = axis == 0 ? cc[0] : (axis == 1 ? cc[1] : cc[2]);
     const bool L = have && c < split;
-    const unsigned long long all_l = __builtin_amdgcn_ballot_w64(L), all = __builtin_amdgcn_ballot_w64(have);
-    const uint32_t nl = (uint32_t)__popcll(all_l);
-    const unsigned long long below_nl = nl >= 64u ? ~0ull : ((1ull << nl) - 1ull);
-    const unsigned long long pre_r = all & ~all_l & below_nl, suf_l = all_l & ~below_nl, suf_r = all & ~all_l & ~below_nl;
-    const unsigned long long above = lane >= 63u ? 0ull : (~0ull << (lane + 1u)), under = (1ull << lane) - 1ull;
-    const uint32_t H = (uint32_t)__popcll(suf_l);
-    const bool in_prefix = lane < nl;
-    const uint32_t m = (uint32_t)__popcll(suf_l & above), rb = (uint32_t)__popcll(suf_r & above);        /* suffix lanes: left / right elements above */
-    const uint32_t hole = (uint32_t)__popcll(pre_r & under);                                             /* prefix lanes: holes below */
-    if (have && !in_prefix && L) s_rb[m] = rb;
-    if (have && in_prefix && !L) s_hole_at[hole] = lane;
-    __syncthreads();
-    uint32_t dest = lane;                                             /* a left-side element of the prefix stays */
-    if (have) {
-        const uint32_t last_i = count - 1u;
-        if (in_prefix && !L) {
-            dest = last_i - (hole + (hole >= 1u ? s_rb[hole - 1u] : 0u));
-        } else if (!in_prefix && L) {
-            dest = s_hole_at[m];
-        } else if (!in_prefix) {
-            const uint32_t base_rb = H >= 1u ? s_rb[H - 1u] : 0u;
-            uint32_t rank;
-            if (m == H) rank = lane == nl ? H + base_rb : H + rb + 1u;
-            else rank = (m + 1u) + rb;
-            dest = last_i - rank;
-        }
-        a.order[first + dest] = tri;
-    }
+    const uint32_t nl = bvb_ballot_partition<64>(a, first, count, tri, have, L, lane, 0u, s_rb, s_hole_at);
     if (lane == 0u) node.pad[1] = (nl == 0u || nl == count) ? 0u : nl;          /* -> k_bvb_children */
 }
 
@@ -764,35 +865,15 @@ __global__ __launch_bounds__(64) void k_bvb_tiny(BvbArgs a, uint32_t level_begin
     }
     const uint32_t S = a.bins;
     const bool have = mine && l < count;
-    uint32_t tri = 0u;
-    float4 r_mn = make_float4(0, 0, 0, 0), r_mx = make_float4(0, 0, 0, 0);
-    float cc[3] = {0.0f, 0.0f, 0.0f};
-    if (have) {
-        tri = a.order[first + l];
-        r_mn = a.recs[tri].mn; r_mx = a.recs[tri].mx;
-        const float4 ce = a.recs[tri].ce;
-        cc[0] = ce.x; cc[1] = ce.y; cc[2] = ce.z;
-    }
+    uint32_t tri;
+    float4 r_mn, r_mx;
+    float cc[3];
+    bvb_fetch(a, first + l, have, tri, r_mn, r_mx, cc);
     /* ---- update_node_aabb over the group */
     unsigned long long k6[6], red[6];
-    bvb_rec_keys(r_mn, r_mx, l, have, k6);
     uint32_t cb[6];
-    for (int j = 0; j < 3; ++j) {
-        uint32_t nz;
-        const uint32_t o = bvb_ord(cc[j], nz);
-        cb[j] = have ? o : 0xffffffffu;
-        cb[3 + j] = have ? o : 0u;
-    }
-    for (int j = 0; j < 6; ++j) red[j] = k6[j];
-    for (int d = 4; d >= 1; d >>= 1)
-        for (int j = 0; j < 3; ++j) {
-            const unsigned long long x = bvb_shfl_xor_u64(red[j], d), y = bvb_shfl_xor_u64(red[3 + j], d);
-            red[j] = x < red[j] ? x : red[j];
-            red[3 + j] = y > red[3 + j] ? y : red[3 + j];
-            const uint32_t lo = (uint32_t)__shfl_xor((int)cb[j], d, 64), hi = (uint32_t)__shfl_xor((int)cb[3 + j], d, 64);
-            cb[j] = lo < cb[j] ? lo : cb[j];
-            cb[3 + j] = hi > cb[3 + j] ? hi : cb[3 + j];
-        }
+    bvb_rec_keys(r_mn, r_mx, l, have, k6);
+    bvb_group_bounds<8>(k6, cc, have, red, cb);
     float bmin[3], bmax[3], nmn[3], nmx[3];
     for (int j = 0; j < 3; ++j) {
         bmin[j] = bvb_unord(cb[j], 0u); bmax[j] = bvb_unord(cb[3 + j], 0u);
@@ -810,11 +891,7 @@ __global__ __launch_bounds__(64) void k_bvb_tiny(BvbArgs a, uint32_t level_begin
         const bool on = mine && !(bmin[ax] == bmax[ax]);
         if (__builtin_amdgcn_ballot_w64(on) == 0ull) continue;
         uint32_t si = 0u;
-        if (on && have) {
-            const float x = (cc[ax] - bmin[ax]) * ((float)S / (bmax[ax] - bmin[ax]));
-            si = x > 0.0f ? (x >= (float)S ? S - 1u : (uint32_t)x) : 0u;
-            if (si > S - 1u) si = S - 1u;
-        }
+        if (on && have) si = bvb_bin_of(cc[ax], bmin[ax], (float)S / (bmax[ax] - bmin[ax]), S);
         /* bins the sweep skips: least x of the bin's triangles is +inf */
         bool excluded = false;
         if (__builtin_amdgcn_ballot_w64(on && have && bvb_key_value(k6[0]) == __builtin_inff()) != 0ull) {
@@ -868,52 +945,17 @@ __global__ __launch_bounds__(64) void k_bvb_tiny(BvbArgs a, uint32_t level_begin
             const uint32_t oa = (uint32_t)__shfl_xor((int)at, d, 64);
             if (oc < c_here || (oc == c_here && oc != __builtin_inff() && oa < at)) { c_here = oc; at = oa; }
         }
-        if (c_here < cost) {
-            cost = c_here;
-            axis = ax;
-            const float scale2 = (bmax[ax] - bmin[ax]) / (float)S;
-            split = bmin[ax] + scale2 * (float)(at + 1u);
-        }
+        bvb_take_axis(ax, c_here, at, bmin, bmax, S, cost, axis, split);
     }
     bool splits = false;
     if (mine) {
-        BvbBox nb;
-        for (int j = 0; j < 3; ++j) { nb.mn[j] = nmn[j]; nb.mx[j] = nmx[j]; }
-        splits = !(bvb_area(nb) * (float)count <= cost);             /* bvh.rs:272-277 */
+        splits = !bvb_stays_leaf(nmn, nmx, count, cost);
         if (!splits && l == 0u) node->left = BVB_NONE;
     }
     /* ---- the partition in closed form, the running counts as bits of a ballot */
     const float c = axis == 0 ? cc[0] : (axis == 1 ? cc[1] : cc[2]);
     const bool L = splits && have && c < split;
-    const uint32_t grp_l = (uint32_t)(__builtin_amdgcn_ballot_w64(L) >> g0) & 0xffu;
-    const uint32_t grp = (uint32_t)(__builtin_amdgcn_ballot_w64(splits && have) >> g0) & 0xffu;
-    const uint32_t nl = (uint32_t)__popc(grp_l);
-    const uint32_t below_nl = (1u << nl) - 1u;
-    const uint32_t pre_r = grp & ~grp_l & below_nl, suf_l = grp_l & ~below_nl, suf_r = grp & ~grp_l & ~below_nl;
-    const uint32_t above = (~0u << (l + 1u)) & 0xffu, under = (1u << l) - 1u;
-    const uint32_t H = (uint32_t)__popc(suf_l);
-    const bool in_prefix = l < nl;
-    const uint32_t m = (uint32_t)__popc(suf_l & above), rb_above = (uint32_t)__popc(suf_r & above);
-    const uint32_t hole = (uint32_t)__popc(pre_r & under);
-    if (splits && have && !in_prefix && L) s_rb[g0 + m] = rb_above;
-    if (splits && have && in_prefix && !L) s_hole_at[g0 + hole] = l;
-    __syncthreads();
-    if (splits && have) {
-        const uint32_t last_i = count - 1u;
-        uint32_t dest = l;
-        if (in_prefix && !L) {
-            dest = last_i - (hole + (hole >= 1u ? s_rb[g0 + hole - 1u] : 0u));
-        } else if (!in_prefix && L) {
-            dest = s_hole_at[g0 + m];
-        } else if (!in_prefix) {
-            const uint32_t base_rb = H >= 1u ? s_rb[g0 + H - 1u] : 0u;
-            uint32_t rank;
-            if (m == H) rank = l == nl ? H + base_rb : H + rb_above + 1u;
-            else rank = (m + 1u) + rb_above;
-            dest = last_i - rank;
-        }
-        a.order[first + dest] = tri;
-    }
+    const uint32_t nl = bvb_ballot_partition<8>(a, first, count, tri, splits && have, L, l, g0, s_rb, s_hole_at);
     if (splits && l == 0u) node->pad[1] = (nl == 0u || nl == count) ? 0u : nl;          /* -> k_bvb_children (bvh.rs:294-296: an empty side, and the node stays a leaf) */
 }
 
@@ -999,49 +1041,7 @@ __global__ __launch_bounds__(BVB_TEAM_THREADS) void k_bvb_team(BvbArgs a, BvbTea
     uint32_t phase = 0u;
 
     /* ---- pass 1: update_node_aabb keys + centroid bounds over the chunk */
-    if (tid < 6u) { s_red[tid] = tid < 3u ? BVB_MIN_IDENT : BVB_MAX_IDENT; s_cb[tid] = tid < 3u ? 0xffffffffu : 0u; }
-    __syncthreads();
-    {
-        unsigned long long kmin[3] = {BVB_MIN_IDENT, BVB_MIN_IDENT, BVB_MIN_IDENT}, kmax[3] = {BVB_MAX_IDENT, BVB_MAX_IDENT, BVB_MAX_IDENT};
-        uint32_t cmin[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, cmax[3] = {0u, 0u, 0u};
-        for (uint32_t pos = c_begin + tid; pos < c_end; pos += THREADS) {
-            const uint32_t i = pos - first;
-            const uint32_t tri = a.order[pos];
-            const float4 r_mn = a.recs[tri].mn, r_mx = a.recs[tri].mx, ce = a.recs[tri].ce;
-            unsigned long long k6[6];
-            bvb_rec_keys(r_mn, r_mx, i, true, k6);
-            for (int j = 0; j < 3; ++j) {
-                kmin[j] = k6[j] < kmin[j] ? k6[j] : kmin[j];
-                kmax[j] = k6[3 + j] > kmax[j] ? k6[3 + j] : kmax[j];
-            }
-            const float cc[3] = {ce.x, ce.y, ce.z};
-            for (int j = 0; j < 3; ++j) {
-                uint32_t nz;
-                uint32_t o = bvb_ord(cc[j], nz);
-                cmin[j] = o < cmin[j] ? o : cmin[j];
-                cmax[j] = o > cmax[j] ? o : cmax[j];
-            }
-        }
-        /* the wave's fold by shuffles, then ONE lane per wave into the workgroup's words: an LDS atomic on one address is served lane by lane — 1 024 threads
-         * x 12 of them were 0.10 of the 0.24 ms a 16 k-triangle node took */
-        for (int d = 32; d >= 1; d >>= 1)
-            for (int j = 0; j < 3; ++j) {
-                const unsigned long long x = bvb_shfl_xor_u64(kmin[j], d), y = bvb_shfl_xor_u64(kmax[j], d);
-                kmin[j] = x < kmin[j] ? x : kmin[j];
-                kmax[j] = y > kmax[j] ? y : kmax[j];
-                const uint32_t lo = (uint32_t)__shfl_xor((int)cmin[j], d, 64), hi = (uint32_t)__shfl_xor((int)cmax[j], d, 64);
-                cmin[j] = lo < cmin[j] ? lo : cmin[j];
-                cmax[j] = hi > cmax[j] ? hi : cmax[j];
-            }
-        if ((tid & 63u) == 0u)
-            for (int j = 0; j < 3; ++j) {
-                atomicMin(&s_red[j], kmin[j]);
-                atomicMax(&s_red[3 + j], kmax[j]);
-                atomicMin(&s_cb[j], cmin[j]);
-                atomicMax(&s_cb[3 + j], cmax[j]);
-            }
-    }
-    __syncthreads();
+    bvb_range_bounds<THREADS>(a, first, c_begin, c_end, s_red, s_cb);
     if (tid < 3u) {
         atomicMin(&T.red[tid], s_red[tid]);
         atomicMax(&T.red[3u + tid], s_red[3u + tid]);
@@ -1059,41 +1059,12 @@ __global__ __launch_bounds__(BVB_TEAM_THREADS) void k_bvb_team(BvbArgs a, BvbTea
     if (member == 0u && tid < 3u) { node.mn[tid] = nmn[tid]; node.mx[tid] = nmx[tid]; }
 
     /* ---- pass 2: bins of the chunk in LDS, merged into the team's bins */
-    for (uint32_t k = tid; k < 3u * BVB_MAX_BINS; k += THREADS) {
-        const uint32_t ax = k / BVB_MAX_BINS, b = k % BVB_MAX_BINS;
-        for (int j = 0; j < 6; ++j) s_key[ax][b][j] = j < 3 ? BVB_MIN_IDENT : BVB_MAX_IDENT;
-        s_cnt[ax][b] = 0u;
-    }
+    bvb_bins_clear<THREADS>(s_key[0], s_cnt[0], 3u * BVB_MAX_BINS);
     __syncthreads();
     float scale[3];
     bool axis_on[3];
-    for (int j = 0; j < 3; ++j) {
-        axis_on[j] = !(bmin[j] == bmax[j]);
-        scale[j] = (float)S / (bmax[j] - bmin[j]);
-    }
-    const uint32_t c_n = c_end - c_begin, deal_mask = bvb_mask_for(c_n);
-    for (uint32_t base = 0; base < c_n; base += THREADS) {
-        const bool have = base + tid < c_n;
-        const uint32_t pos = c_begin + (have ? bvb_scatter_index(base + tid, c_n, deal_mask) : 0u);
-        const uint32_t i = pos - first;
-        float4 r_mn = make_float4(0, 0, 0, 0), r_mx = make_float4(0, 0, 0, 0);
-        float cc[3] = {0.0f, 0.0f, 0.0f};
-        if (have) {
-            const uint32_t tri = a.order[pos];
-            r_mn = a.recs[tri].mn; r_mx = a.recs[tri].mx;
-            const float4 ce = a.recs[tri].ce;
-            cc[0] = ce.x; cc[1] = ce.y; cc[2] = ce.z;
-        }
-        unsigned long long k6[6];
-        bvb_rec_keys(r_mn, r_mx, i, have, k6);
-        for (int ax = 0; ax < 3; ++ax) {
-            if (!axis_on[ax]) continue;
-            const float x = (cc[ax] - bmin[ax]) * scale[ax];
-            uint32_t si = x > 0.0f ? (x >= (float)S ? S - 1u : (uint32_t)x) : 0u;
-            if (si > S - 1u) si = S - 1u;
-            bvb_bin_add(s_key[ax], s_cnt[ax], have, si, k6);
-        }
-    }
+    bvb_axis_scales(bmin, bmax, S, axis_on, scale);
+    bvb_bin_pass<THREADS, 3u>(a, first, c_begin, c_end - c_begin, 0u, axis_on, bmin, scale, S, s_key, s_cnt);
     __syncthreads();
     for (uint32_t k = tid; k < 3u * BVB_MAX_BINS; k += THREADS) {
         const uint32_t ax = k / BVB_MAX_BINS, b = k % BVB_MAX_BINS;
@@ -1116,31 +1087,9 @@ __global__ __launch_bounds__(BVB_TEAM_THREADS) void k_bvb_team(BvbArgs a, BvbTea
             s_cnt[ax][b] = __hip_atomic_load(&T.cnt[ax][b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         __syncthreads();
-        if (tid < 192u) {                                      /* waves 0, 1, 2: one axis each (bvb_wave_sweep) */
-            const uint32_t ax = tid >> 6;
-            float best_cost = __builtin_inff();
-            uint32_t best_i = 0u;
-            if (axis_on[ax]) bvb_wave_sweep(s_key[ax], s_cnt[ax], S, best_cost, best_i);
-            if ((tid & 63u) == 0u) { s_best_cost[ax] = best_cost; s_best_i[ax] = best_i; }
-        }
+        bvb_sweep_three_axes(s_key, s_cnt, S, axis_on, s_best_cost, s_best_i);
         __syncthreads();
-        if (tid == 0u) {
-            int axis = 0;
-            float split = 0.0f, cost = __builtin_inff();
-            for (int ax = 0; ax < 3; ++ax) {
-                if (s_best_cost[ax] < cost) {
-                    cost = s_best_cost[ax];
-                    axis = ax;
-                    const float scale2 = (bmax[ax] - bmin[ax]) / (float)S;
-                    split = bmin[ax] + scale2 * (float)(s_best_i[ax] + 1u);
-                }
-            }
-            BvbBox nb;
-            for (int j = 0; j < 3; ++j) { nb.mn[j] = nmn[j]; nb.mx[j] = nmx[j]; }
-            const float parent_cost = bvb_area(nb) * (float)count;
-            T.axis = parent_cost <= cost ? -1 : axis;
-            T.split = split;
-        }
+        if (tid == 0u) bvb_choose_split(s_best_cost, s_best_i, bmin, bmax, nmn, nmx, count, S, T.axis, T.split);
     }
     bvb_team_sync(&T.barrier, phase, team_size);
     const int axis = T.axis;
@@ -1174,47 +1123,16 @@ __global__ __launch_bounds__(BVB_TEAM_THREADS) void k_bvb_team(BvbArgs a, BvbTea
     const uint32_t H = nl - l_in_prefix;
 
     /* ---- pass 6 (B1): rb_at_L for the suffix left-side elements of this chunk */
-    for (uint32_t q = (c_begin > split_pos ? c_begin : split_pos) + tid; q < c_end; q += THREADS) {
-        const uint32_t w = a.lpre[q];
-        if (w & 1u) {
-            const uint32_t m = nl - (pref_l + (w >> 1) + 1u);
-            a.tmp_b[first + m] = (last - q) - m;
-        }
-    }
+    bvb_part_b1<THREADS>(a, c_begin, c_end, first, last, nl, pref_l);
     bvb_team_sync(&T.barrier, phase, team_size);
-    const uint32_t base_rb = H >= 1u ? __hip_atomic_load(&a.tmp_b[first + H - 1u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+    const uint32_t base_rb = H >= 1u ? bvb_ld<true>(&a.tmp_b[first + H - 1u]) : 0u;
     /* ---- pass 7 (F): the prefix */
-    for (uint32_t p = c_begin + tid; p < c_end && p < split_pos; p += THREADS) {
-        const uint32_t w = a.lpre[p];
-        if (w & 1u) {
-            a.order_tmp[p] = a.order[p];
-        } else {
-            const uint32_t hole = (p - first) - (pref_l + (w >> 1));
-            const uint32_t rank = hole + (hole >= 1u ? __hip_atomic_load(&a.tmp_b[first + hole - 1u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u);
-            a.order_tmp[last - rank] = a.order[p];
-            a.tmp_a[first + hole] = p;
-        }
-    }
+    bvb_part_f<THREADS, true>(a, c_begin, c_end, first, last, nl, pref_l);
     bvb_team_sync(&T.barrier, phase, team_size);
     /* ---- pass 8 (B2): the suffix */
-    for (uint32_t q = (c_begin > split_pos ? c_begin : split_pos) + tid; q < c_end; q += THREADS) {
-        const uint32_t w = a.lpre[q];
-        const uint32_t l_before = pref_l + (w >> 1);
-        if (w & 1u) {
-            const uint32_t m = nl - (l_before + 1u);
-            a.order_tmp[__hip_atomic_load(&a.tmp_a[first + m], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)] = a.order[q];
-        } else {
-            const uint32_t m = nl - l_before;
-            const uint32_t rb = (last - q) - m;
-            uint32_t rank;
-            if (m == H) rank = (q == split_pos) ? H + base_rb : H + rb + 1u;
-            else rank = (m + 1u) + rb;
-            a.order_tmp[last - rank] = a.order[q];
-        }
-    }
+    bvb_part_b2<THREADS, true>(a, c_begin, c_end, first, last, nl, pref_l, H, base_rb);
     bvb_team_sync(&T.barrier, phase, team_size);
-    for (uint32_t pos = c_begin + tid; pos < c_end; pos += THREADS)
-        a.order[pos] = __hip_atomic_load(&a.order_tmp[pos], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    bvb_part_copy_back<THREADS, true>(a, c_begin, c_end);
     if (member == 0u && tid == 0u) {
         node.pad[0] = 1u;
         if (nl == 0u || nl == count) {
@@ -1222,8 +1140,7 @@ __global__ __launch_bounds__(BVB_TEAM_THREADS) void k_bvb_team(BvbArgs a, BvbTea
         } else {
             const uint32_t id = atomicAdd(a.node_count, 2u);
             node.left = id;
-            a.nodes[id].first = first;          a.nodes[id].count = nl;              a.nodes[id].left = BVB_NONE;   a.nodes[id].pad[0] = 0u;   a.nodes[id].pad[1] = 0u;
-            a.nodes[id + 1u].first = first + nl; a.nodes[id + 1u].count = count - nl; a.nodes[id + 1u].left = BVB_NONE; a.nodes[id + 1u].pad[0] = 0u; a.nodes[id + 1u].pad[1] = 0u;
+            bvb_make_children(a, id, first, count, nl);
         }
     }
 }

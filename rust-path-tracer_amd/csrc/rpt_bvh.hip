@@ -13,6 +13,20 @@
 #include "rpt_ctx.h"
 #include "k_bvh_build.h"
 
+/* the split kernels of one level [begin, end) whose largest node (not yet split by a team) has level_max triangles */
+static void bvb_launch_level(const BvbArgs &a, uint32_t begin, uint32_t end, uint32_t level_max) {
+    if (end - begin < 64u || level_max >= BVB_WIDE_MIN_COUNT) k_bvb_level<1024><<<end - begin, 1024>>>(a, begin, 0u);    /* few nodes, or big ones */
+    else if (level_max <= 256u) {
+        /* small nodes: those of up to 8 triangles eight to a wave, the others one wave each — out of registers up to 64 triangles
+         * (measured: 64 / 256 / 1024 as the limit of the one-wave kernel) */
+        k_bvb_tiny<<<(end - begin + 7u) / 8u, 64>>>(a, begin, end);
+        if (level_max > BVB_TINY) {
+            if (level_max <= 64u) k_bvb_small<<<end - begin, 64>>>(a, begin, BVB_TINY);
+            else k_bvb_level<64><<<end - begin, 64>>>(a, begin, BVB_TINY);
+        }
+    } else k_bvb_level<BVB_THREADS><<<end - begin, BVB_THREADS>>>(a, begin, 0u);
+}
+
 extern "C" {
 
 /* BVHBuilder::new(vertices, indices).sah_samples(n).build() (src/bvh.rs:59-324) on the device: same node pool, same
@@ -52,12 +66,8 @@ int rpt_bvh_build_gpu(int device_id, const float *vertices_xyzw, size_t n_vertic
     DevBuf<uint32_t> d_inner, d_rank, d_oidx;
     DevBuf<rpt_bvh_node> d_out;
     std::vector<std::pair<uint32_t, uint32_t>> levels;          /* build-order id ranges, root level first */
-    const bool use_teams = true;
     uint32_t team_min = BVB_TEAM_MIN_COUNT;           /* RPT_BVH_TEAM_MIN: test aid, lets small nodes take the team path */
     if (const int forced = rpt_read_knobs().bvh_team_min) team_min = (uint32_t)forced;
-    const uint32_t team_chunk = BVB_TEAM_CHUNK;
-    std::vector<BvbNode> bn;
-    std::vector<uint32_t> order;
     struct Events {                                     /* the two timing events, destroyed on every way out */
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
         ~Events() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); }
@@ -112,7 +122,7 @@ int rpt_bvh_build_gpu(int device_id, const float *vertices_xyzw, size_t n_vertic
     while (begin < end) {                               /* one launch per tree level */
         bool teams_here = false;
         /* the big nodes of this level (if any) are split by teams of workgroups first: one workgroup per BVB_TEAM_CHUNK triangles */
-        if (use_teams && resident >= 2u && end - begin <= 4096u && level_max >= team_min) {
+        if (resident >= 2u && end - begin <= 4096u && level_max >= team_min) {
             level_nodes.resize(end - begin);
             HIP_TRY_TO(err, WHERE, hipMemcpy(level_nodes.data(), d_nodes.p + begin, (size_t)(end - begin) * sizeof(BvbNode), hipMemcpyDeviceToHost));
             team_refs.clear();
@@ -120,7 +130,7 @@ int rpt_bvh_build_gpu(int device_id, const float *vertices_xyzw, size_t n_vertic
             for (uint32_t k = 0; k < end - begin && team_refs.size() < BVB_MAX_TEAMS; ++k) {
                 if (level_nodes[k].count < team_min) continue;
                 uint32_t size = 2u;
-                while (size < BVB_TEAM && (size_t)size * team_chunk < level_nodes[k].count) size *= 2u;
+                while (size < BVB_TEAM && (size_t)size * BVB_TEAM_CHUNK < level_nodes[k].count) size *= 2u;
                 while (size > 2u && block_team.size() + size > resident) size /= 2u;
                 if (block_team.size() + size > resident) break;
                 team_refs.push_back(BvbTeamRef{begin + k, size, (uint32_t)block_team.size()});
@@ -134,16 +144,7 @@ int rpt_bvh_build_gpu(int device_id, const float *vertices_xyzw, size_t n_vertic
                 teams_here = true;                      /* (their children are not in level_max: the next level keeps the wide workgroups) */
             }
         }
-        if (end - begin < 64u || level_max >= BVB_WIDE_MIN_COUNT) k_bvb_level<1024><<<end - begin, 1024>>>(a, begin, 0u);    /* few nodes, or big ones */
-        else if (level_max <= 256u) {
-            /* small nodes: those of up to 8 triangles eight to a wave, the others one wave each — out of registers up to 64 triangles
-             * (measured: 64 / 256 / 1024 as the limit of the one-wave kernel) */
-            k_bvb_tiny<<<(end - begin + 7u) / 8u, 64>>>(a, begin, end);
-            if (level_max > BVB_TINY) {
-                if (level_max <= 64u) k_bvb_small<<<end - begin, 64>>>(a, begin, BVB_TINY);
-                else k_bvb_level<64><<<end - begin, 64>>>(a, begin, BVB_TINY);
-            }
-        } else k_bvb_level<BVB_THREADS><<<end - begin, BVB_THREADS>>>(a, begin, 0u);
+        bvb_launch_level(a, begin, end, level_max);
         k_bvb_children<<<(end - begin + 1023u) / 1024u, 1024>>>(a, begin, end);
         uint32_t total[3] = {0u, 0u, 0u};
         HIP_TRY_TO(err, WHERE, hipMemcpy(total, d_count.p, sizeof total, hipMemcpyDeviceToHost));
@@ -181,7 +182,7 @@ int rpt_bvh_build_gpu(int device_id, const float *vertices_xyzw, size_t n_vertic
         k_bvb_place<<<(le - lb + BVB_THREADS - 1) / BVB_THREADS, BVB_THREADS>>>(d_nodes.p, d_inner.p, d_rank.p, d_oidx.p, d_out.p, lb, le);
     }
     sections.mark("renumber_device");
-    order.resize(nt);
+    std::vector<uint32_t> order(nt);
     HIP_TRY_TO(err, WHERE, hipMemcpy(nodes_out, d_out.p, (size_t)end * sizeof(rpt_bvh_node), hipMemcpyDeviceToHost));
     HIP_TRY_TO(err, WHERE, hipMemcpy(order.data(), d_order.p, (size_t)nt * 4, hipMemcpyDeviceToHost));
     *n_nodes_out = end;

@@ -272,3 +272,21 @@ def test_big_nodes_without_teams(monkeypatch):
         hn, ht = _oracle_build(v, t.copy())
         gn, gt, _ = hip.bvh_build_gpu(v, t.copy())
         _assert_same(gn, gt, hn, ht)
+
+
+@pytest.mark.parametrize("team_min", [None, "2", "300"])
+def test_gpu_build_down_every_split_path(monkeypatch, oracle, team_min):
+    """The one case whose tree sends nodes down every split kernel, across their size limits, through a counting pass of several trips and — with the
+    team threshold lowered — through teams whose chunks are shorter than, as long as and longer than a workgroup (tests/bvh_cases.py; that it does is
+    asserted on the oracle's trees by tests/test_bvh_dispatch.py)."""
+    from bvh_cases import DISPATCH_BINS, dispatch_case
+    if team_min is None:
+        monkeypatch.delenv("RPT_BVH_TEAM_MIN", raising=False)
+    else:
+        monkeypatch.setenv("RPT_BVH_TEAM_MIN", team_min)
+    rpt, hip, host = _mods()
+    v, t, built = dispatch_case(oracle)
+    for bins in DISPATCH_BINS:
+        on, ot = built[bins]
+        gn, gt, _ = hip.bvh_build_gpu(v, t.copy(), bins)
+        _assert_same(gn, gt, on, ot)
