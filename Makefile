@@ -12,7 +12,7 @@ CXX      ?= g++
 
 HOST_SRCS := $(CSRC)/host/host_api.cpp $(CSRC)/host/glb_scene.cpp $(CSRC)/host/bvh_build.cpp \
              $(CSRC)/host/light_table.cpp $(CSRC)/host/bluenoise.cpp $(CSRC)/host/image_io.cpp $(CSRC)/host/textures.cpp $(CSRC)/host/obj_scene.cpp $(CSRC)/host/jpeg_decode.cpp
-HIP_SRCS  := $(CSRC)/rpt_hip.hip $(CSRC)/rpt_scene.hip $(CSRC)/rpt_traverse.hip $(CSRC)/rpt_comm.hip $(CSRC)/rpt_lights.hip $(CSRC)/rpt_bvh.hip $(CSRC)/rpt_denoise.hip $(CSRC)/rpt_moments.hip $(CSRC)/rpt_debug.hip
+HIP_SRCS  := $(CSRC)/rpt_hip.hip $(CSRC)/rpt_scene.hip $(CSRC)/rpt_traverse.hip $(CSRC)/rpt_comm.hip $(CSRC)/rpt_lights.hip $(CSRC)/rpt_bvh.hip $(CSRC)/rpt_denoise.hip $(CSRC)/rpt_moments.hip $(CSRC)/rpt_adaptive.hip $(CSRC)/rpt_debug.hip
 HIP_OBJS  := $(patsubst $(CSRC)/%.hip,build/%.o,$(HIP_SRCS))
 HIP_DEPS  := $(wildcard $(CSRC)/*.h) $(wildcard $(CSRC)/*.hip) $(wildcard include/rpt/*.h)
 

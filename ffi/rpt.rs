@@ -93,6 +93,18 @@ pub struct rpt_noise_result {
     pub ms: f64,
 }
 
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct rpt_adaptive_result {
+    pub passes: u32,             // masked passes made
+    pub converged: u32,          // 1: every pixel measured and at most max_above left above the threshold
+    pub min_pixel_samples: u32,  // the range of the moments' counts over the owned pixels
+    pub max_pixel_samples: u32,
+    pub pixel_samples: u64,      // rendered by the call, uniform phase included
+    pub counts: rpt_noise_counts,
+    pub ms: f64,
+}
+
 extern "C" {
     pub fn rpt_abi_version() -> c_int;                                              // == 3
     pub fn rpt_build_fingerprint() -> *const c_char;                                // fingerprint of the kernel sources the library was built from
@@ -135,6 +147,10 @@ extern "C" {
     pub fn rpt_read_noise(ctx: *mut rpt_ctx, rel_out: *mut f32) -> c_int;           // standard error of the mean luminance / (|mean| + 0.01)
     pub fn rpt_noise_count(ctx: *mut rpt_ctx, threshold: f32, out: *mut rpt_noise_counts) -> c_int;   // integers: a process-per-GPU host all-reduces them itself
     pub fn rpt_render_to_noise(ctx: *mut rpt_ctx, target: *const rpt_noise_target, out: *mut rpt_noise_result) -> c_int;
+    // chosen pixels: n more samples where the row-major byte mask is non-zero; per-pixel sample counts to a noise target; 1 while every owned pixel has the same count
+    pub fn rpt_render_pixels(ctx: *mut rpt_ctx, mask: *const u8, n_samples: u32) -> c_int;
+    pub fn rpt_render_adaptive(ctx: *mut rpt_ctx, target: *const rpt_noise_target, out: *mut rpt_adaptive_result) -> c_int;
+    pub fn rpt_counts_uniform(ctx: *mut rpt_ctx, uniform_out: *mut u32) -> c_int;
     pub fn rpt_get_stats(ctx: *mut rpt_ctx, out: *mut rpt_stats) -> c_int;
     pub fn rpt_destroy(ctx: *mut rpt_ctx);
 
@@ -161,6 +177,8 @@ extern "C" {
     pub fn rpt_multi_read_moments(m: *mut rpt_multi, out_xyzw: *mut Vec4) -> c_int; // the ranks' records merged on the host
     pub fn rpt_multi_noise_count(m: *mut rpt_multi, threshold: f32, out: *mut rpt_noise_counts) -> c_int;   // summed over the ranks
     pub fn rpt_multi_render_to_noise(m: *mut rpt_multi, target: *const rpt_noise_target, out: *mut rpt_noise_result) -> c_int;
+    pub fn rpt_multi_render_pixels(m: *mut rpt_multi, mask: *const u8, n_samples: u32) -> c_int;       // each rank among its own pixels + the gather
+    pub fn rpt_multi_render_adaptive(m: *mut rpt_multi, target: *const rpt_noise_target, out: *mut rpt_adaptive_result) -> c_int;   // above and selected summed over the ranks
     pub fn rpt_multi_get_stats(m: *mut rpt_multi, out: *mut rpt_stats) -> c_int;
     pub fn rpt_multi_last_error(m: *mut rpt_multi) -> *const c_char;
     pub fn rpt_multi_destroy(m: *mut rpt_multi);

@@ -411,6 +411,63 @@ int rpt_multi_read_moments(rpt_multi *m, float *out_xyzw);
 int rpt_multi_noise_count(rpt_multi *m, float threshold, rpt_noise_counts *out);
 int rpt_multi_render_to_noise(rpt_multi *m, const rpt_noise_target *target, rpt_noise_result *out);
 
+/* --- chosen pixels: masked passes, per-pixel sample counts to a noise target (no reference equivalent) --------------------------------------------------
+ * Opt-in; a context that never makes a masked or adaptive call runs the same kernels as before, and bench.py's figures are not touched.
+ * A sample depends only on its pixel's (x, y), its rng (n, offset) and the scene, and samples are added in sample order: a pixel that has received N samples
+ * BY ANY ROUTE — uniform calls, masked passes, in any split — holds bit for bit what the reference holds after N samples (accumulator with .w = N, rng.n
+ * advanced by N, moments).  tests/test_gpu_adaptive.py holds every case to that.
+ * A masked pass (csrc/k_adaptive.h, rpt_adaptive.hip): a flag per owned pixel; the flagged pixels compacted in ascending pixel order (count per workgroup,
+ * scan, scatter: the survivors keep the tile-major order and nothing depends on the order waves arrive in); their (pixel_xy, rng, accum, moments) copied
+ * into compact arrays; the unchanged pipeline on those arrays, exactly as on a rank that owns that many pixels — with as many samples of a pixel in flight
+ * as fit in the slots a whole-image call of this context may allocate (up to 256; rpt_set_samples_in_flight(n > 0) holds for a pass too), so a few thousand
+ * pixels still fill the GPU; the records copied back, stream-ordered behind the batch.  The number of selected pixels comes back as one 4-byte read, the
+ * pass's only synchronisation; nothing selected: nothing is launched, the call succeeds.  A pass whose batch has a known length (rpt_render_async) returns
+ * once enqueued, otherwise it is synchronous; every read-out synchronises anyway.  A pass that selects EVERY owned pixel is the uniform call it amounts to.
+ *
+ * rpt_render_pixels   n_samples more samples for the owned pixels whose mask byte is non-zero (mask: width*height bytes, row-major; other ranks' pixels
+ *                     ignored).  rpt_stats.samples grows by selected pixels x n_samples.
+ * Sample counts then differ between pixels.  accum.w and rng.n carry each pixel's own count; rpt_read_accum's out_samples keeps reporting the samples EVERY
+ * owned pixel received through uniform calls (a uniform rpt_render after a masked pass adds n to every pixel and to that figure).  rpt_counts_uniform:
+ * 0 once a masked or adaptive pass has rendered for fewer than all owned pixels, 1 again after rpt_reset or whatever invalidates the accumulator.  While it
+ * is 0, rpt_resolve and rpt_denoise(RPT_DENOISE_ACCUM) divide every pixel by its own .w (a pixel with .w == 0 resolves to 0); rpt_gather_async snapshots
+ * the flag beside the sample count and rpt_denoise(RPT_DENOISE_GATHERED) / rpt_multi_denoise honour the snapshot (one process per GPU: the root snapshots
+ * ITS flag — ranks that were masked differently must tell it; rpt_multi: any rank's).  While it is 1 both are the code and the results they always were.
+ *
+ * rpt_render_adaptive   per-pixel sample counts to a noise target.  Reuses rpt_noise_target and its refusals; turns moments on if they are off and leaves
+ *                     them on.  Uniform phase: exactly min_samples for every pixel, in batches of at most batch_samples (rpt_render_async).  Then, before
+ *                     each masked pass, one kernel selects the pixels with
+ *                         !(noise_rel(m) <= threshold) && m.z + batch_samples <= max_samples        (m.z: the pixel's own count in the moments record)
+ *                     — an unmeasured pixel is selected — and counts as rpt_noise_count does; the call stops with converged = 1 when every pixel is
+ *                     measured and above <= max_above, with converged = 0 when nothing is selected, and otherwise renders batch_samples for the selected.
+ *                     A pixel's record changes only when it is sampled, so a pixel at or below the threshold is never selected again, and (max_above = 0,
+ *                     moments zeroed before the call) its final count has a CLOSED FORM: the first count of the schedule min_samples, min_samples +
+ *                     batch_samples, ... at which its noise was at or below the threshold, else the last count of the schedule that is <= max_samples.
+ *                     The passes made = the most steps any pixel took.  With max_above > 0 the call stops at the first pass before which at most that many
+ *                     were above.  m.z counts from where the moments were last zeroed (rpt_set_moments, rpt_reset): call it on a fresh record.
+ *                     STOPPING ON AN EMPIRICAL VARIANCE BIASES THE ESTIMATE: a pixel stops when its samples so far happen to agree, which favours
+ *                     low estimates of bright, rare contributions — the limit stated above for min_samples, here per pixel.  A pixel whose first
+ *                     min_samples samples were all equal stops at min_samples.
+ *                     out: passes = masked passes made; min / max_pixel_samples = the range of m.z over the owned pixels; pixel_samples = what this call
+ *                     rendered, uniform phase included; counts = the last count (the state at return); ms = host clock over the call.
+ * rpt_multi_*         the same on every rank: each selects among its own pixels, above and selected are summed over the ranks, every rank's pass is
+ *                     enqueued before any is waited for, and the image is gathered once at the end.  Round-robin tiles do not balance a noise map: the
+ *                     ranks finish a pass at different times.
+ * RPT_EINVAL, the context stays usable: a null mask, target or out; calls before scene, config or reset; the target refusals of rpt_render_to_noise.  A
+ * context that can keep only one slot per pixel for the whole image is not refused as such: a pass's view has its own slot count. */
+int rpt_render_pixels(rpt_ctx *ctx, const uint8_t *mask, uint32_t n_samples);
+
+typedef struct rpt_adaptive_result {
+    uint32_t passes, converged;            /* masked passes made; 1 = every pixel measured and at most max_above left above the threshold */
+    uint32_t min_pixel_samples, max_pixel_samples;   /* of the moments' counts (m.z) over the owned pixels */
+    uint64_t pixel_samples;                /* pixel-samples this call rendered, uniform phase included */
+    rpt_noise_counts counts;               /* as rpt_noise_count at the end */
+    double ms;
+} rpt_adaptive_result;
+int rpt_render_adaptive(rpt_ctx *ctx, const rpt_noise_target *target, rpt_adaptive_result *out);
+int rpt_counts_uniform(rpt_ctx *ctx, uint32_t *uniform_out);
+int rpt_multi_render_pixels(rpt_multi *m, const uint8_t *mask, uint32_t n_samples);
+int rpt_multi_render_adaptive(rpt_multi *m, const rpt_noise_target *target, rpt_adaptive_result *out);
+
 /* --- scene preparation on the device ---------------------- */
 /* BVHBuilder::new(vertices, indices).sah_samples(n).build()  (reference src/bvh.rs:59-324, the call at
  * src/asset.rs:196) on the GPU: reorders `triangles` in place and writes the node pool exactly as the sequential

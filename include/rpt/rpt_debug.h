@@ -78,6 +78,12 @@ int rpt_debug_denoise_host(uint32_t width, uint32_t height, const float *mean_rg
  * sum Y^2, n, max Y) — no device needed.  rel_out (n floats) and counts_out are nullable; counts_out->pixels = n.  RPT_EINVAL for a negative or NaN threshold. */
 int rpt_debug_noise_host(const float *moments_xyzw, size_t n, float threshold, float *rel_out, rpt_noise_counts *counts_out);
 
+/* The selection rule of rpt_render_adaptive and the ordered compaction of a masked pass on the HOST: the same header (csrc/k_adaptive.h) in a plain loop
+ * over n moments records — no device needed.  flags_out (n bytes: 1 = selected), active_out (room for n indices: the selected records' indices, ascending)
+ * and n_active_out are nullable.  RPT_EINVAL for a negative or NaN threshold. */
+int rpt_debug_adaptive_select_host(const float *moments_xyzw, size_t n, float threshold, uint32_t batch_samples, uint32_t max_samples, uint8_t *flags_out,
+                                   uint32_t *active_out, size_t *n_active_out);
+
 /* Test aid: the next asynchronous batches of this context enqueue one iteration too few — proves that the completion checks (rpt_wait, the next
  * batch's k_generate_first) notice a sample left in flight instead of losing it. */
 int rpt_debug_short_batch(rpt_ctx *ctx, int on);

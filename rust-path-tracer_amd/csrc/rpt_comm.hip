@@ -114,6 +114,7 @@ struct rpt_comm {
     std::vector<uint64_t> sizes;
     uint32_t conf_w = 0, conf_h = 0;
     uint32_t gathered_samples = 0;
+    bool gathered_nonuniform = false; /* the context's counts_nonuniform when the gathered image was snapshotted (rpt_multi: of any rank) */
     bool started = false;
 };
 
@@ -130,7 +131,7 @@ void rpt_comm_release(rpt_ctx *c) {
 }
 
 /* rpt_denoise(RPT_DENOISE_GATHERED): the gathered image itself, once the gather that wrote it has completed */
-int rpt_comm_gathered_image(rpt_ctx *c, const float4 **image_out, uint32_t *samples_out, hipStream_t *stream_out) {
+int rpt_comm_gathered_image(rpt_ctx *c, const float4 **image_out, uint32_t *samples_out, bool *nonuniform_out, hipStream_t *stream_out) {
     rpt_comm *cm = c->comm;
     if (!cm || cm->rank != 0 || !cm->full_image.p || !cm->started) { c->error = "rpt_denoise: a gathered image exists on rank 0 of a communicator after the first gather"; return RPT_EINVAL; }
     if (!c->has_config || cm->conf_w != c->cfg.c.width || cm->conf_h != c->cfg.c.height) {
@@ -142,6 +143,7 @@ int rpt_comm_gathered_image(rpt_ctx *c, const float4 **image_out, uint32_t *samp
     HIP_TRY(c, hipGetLastError());
     *image_out = cm->full_image.p;
     *samples_out = cm->gathered_samples;
+    *nonuniform_out = cm->gathered_nonuniform;
     *stream_out = cm->stream;
     return RPT_OK;
 }
@@ -248,6 +250,7 @@ int gather_stage(rpt_ctx *c) {
     HIP_TRY(c, hipEventRecord(cm->staged, c->stream));
     HIP_TRY(c, hipStreamWaitEvent(cm->stream, cm->staged, 0));
     cm->gathered_samples = c->samples;
+    cm->gathered_nonuniform = c->counts_nonuniform;
     return RPT_OK;
 }
 
@@ -517,8 +520,12 @@ int multi_fail(rpt_multi *m, rpt_ctx *c, int rc) {
 
 int multi_gather(rpt_multi *m) {
     int rc;
-    for (rpt_ctx *c : m->ctx)
+    bool nonuniform = false;
+    for (rpt_ctx *c : m->ctx) {
         if ((rc = gather_stage(c))) return multi_fail(m, c, rc);
+        nonuniform = nonuniform || c->counts_nonuniform;
+    }
+    m->ctx[0]->comm->gathered_nonuniform = nonuniform;       /* (the image holds every rank's pixels) */
     if (!m->shared_device) {
         if (rccl().GroupStart() != ncclSuccess) { m->error = "ncclGroupStart failed"; return RPT_EHIP; }
         rc = RPT_OK;
@@ -766,6 +773,97 @@ int rpt_multi_get_stats(rpt_multi *m, rpt_stats *out) {
     }
     *out = sum;
     return RPT_OK;
+}
+
+}  // extern "C"
+
+/* ---- masked and adaptive passes on every rank (rpt_adaptive.hip has the steps of one rank) ---- */
+namespace {
+
+/* the select enqueued on EVERY rank, then the results read: the ranks' selects overlap, and so do their passes below */
+int multi_select(rpt_multi *m, const uint8_t *mask, const rpt_noise_target *target, rpt_adaptive_selection *sum_out, uint64_t *pixels_out) {
+    int rc;
+    for (rpt_ctx *c : m->ctx)
+        if ((rc = rpt_adaptive_select(c, mask, target))) return multi_fail(m, c, rc);
+    rpt_adaptive_selection sum{0u, 0xffffffffu, 0u, rpt_noise_counts{0, 0, 0}};
+    uint64_t pixels = 0, active = 0;
+    for (rpt_ctx *c : m->ctx) {
+        rpt_adaptive_selection one{};
+        if ((rc = rpt_adaptive_selected(c, target != nullptr, &one))) return multi_fail(m, c, rc);
+        active += one.n_active; pixels += c->n_pixels;
+        if (target && c->n_pixels) {
+            sum.z_min = std::min(sum.z_min, one.z_min); sum.z_max = std::max(sum.z_max, one.z_max);
+            sum.counts.pixels += one.counts.pixels; sum.counts.measured += one.counts.measured; sum.counts.above += one.counts.above;
+        }
+    }
+    if (active > 0xffffffffull) { m->error = "masked pass: more than 2^32 pixels selected"; return RPT_EINVAL; }
+    sum.n_active = (uint32_t)active;
+    *sum_out = sum;
+    *pixels_out = pixels;
+    return RPT_OK;
+}
+
+/* every rank's pass enqueued before any is waited for.  When the ranks together render only some pixels of the image, no rank's pass counts as a uniform
+ * call (its context's sample count must stay the image's) and every rank's counts are non-uniform. */
+int multi_pass(rpt_multi *m, uint32_t n_samples, bool whole_image) {
+    for (rpt_ctx *c : m->ctx) {
+        int rc = rpt_adaptive_pass(c, n_samples, whole_image);
+        if (rc) return multi_fail(m, c, rc);
+        if (!whole_image) c->counts_nonuniform = true;
+    }
+    return RPT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+/* rpt_render_pixels on every rank (each among its own pixels) + the single gather, as rpt_multi_render */
+int rpt_multi_render_pixels(rpt_multi *m, const uint8_t *mask, uint32_t n_samples) {
+    if (!m) return RPT_EINVAL;
+    if (!mask) { m->error = "rpt_multi_render_pixels: null mask"; return RPT_EINVAL; }
+    for (rpt_ctx *c : m->ctx)
+        if (!c->has_scene || !c->has_config || !c->has_state || !c->has_seeds) { m->error = "scene, config and reset must precede rpt_multi_render_pixels"; return RPT_EINVAL; }
+    if (n_samples == 0u) return RPT_OK;
+    rpt_adaptive_selection sel{};
+    uint64_t pixels = 0;
+    int rc = multi_select(m, mask, nullptr, &sel, &pixels);
+    if (rc) return rc;
+    if (sel.n_active == 0u) return RPT_OK;
+    if ((rc = multi_pass(m, n_samples, sel.n_active == pixels))) return rc;
+    return multi_gather(m);
+}
+
+/* rpt_render_adaptive over every rank: above and selected are sums over the ranks; one gather at the end */
+int rpt_multi_render_adaptive(rpt_multi *m, const rpt_noise_target *target, rpt_adaptive_result *out) {
+    if (!m || !target || !out) return RPT_EINVAL;
+    int rc = rpt_noise_check_target(*target, m->error, "rpt_multi_render_adaptive");
+    if (rc) return rc;
+    for (rpt_ctx *c : m->ctx)
+        if (!c->has_scene || !c->has_config || !c->has_state || !c->has_seeds) { m->error = "scene, config and reset must precede rpt_multi_render_adaptive"; return RPT_EINVAL; }
+    if ((rc = rpt_multi_set_moments(m, 1u))) return rc;
+    struct Who { rpt_multi *m; bool whole_image; } who{m, true};
+    const rpt_adaptive_driver driver = {
+        [](void *w, uint32_t n, uint64_t *rendered) {
+            rpt_multi *m = static_cast<Who *>(w)->m;
+            *rendered = 0;
+            for (rpt_ctx *c : m->ctx) {
+                int rc = rpt_render_async(c, n);
+                if (rc) return multi_fail(m, c, rc);
+                *rendered += (uint64_t)c->n_pixels * n;
+            }
+            return (int)RPT_OK;
+        },
+        [](void *w, const rpt_noise_target *t, rpt_adaptive_selection *sel) {
+            Who *who = static_cast<Who *>(w);
+            uint64_t pixels = 0;
+            int rc = multi_select(who->m, nullptr, t, sel, &pixels);
+            who->whole_image = !rc && sel->n_active == pixels;
+            return rc;
+        },
+        [](void *w, uint32_t n) { Who *who = static_cast<Who *>(w); return multi_pass(who->m, n, who->whole_image); }};
+    if ((rc = rpt_render_adaptive_with(target, out, driver, &who))) return rc;
+    return multi_gather(m);
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
  * rpt_ctx.h — the context object behind the C ABI of include/rpt/rpt.h, shared by the translation units of
  * librpt_hip.so (rpt_hip.hip: life cycle, state and wavefront scheduling; rpt_scene.hip: scene preparation; rpt_traverse.hip: the traversal stages;
  * rpt_comm.hip: multi-GPU gather over RCCL, read-back; rpt_denoise.hip: guide buffers and the denoise filter; rpt_moments.hip: sample moments, noise estimate,
- * render to a noise target; rpt_debug.hip: test hooks).  k_image_order.h: the one kernel and the one read-out routine that turn the tile-major pixel order
+ * render to a noise target; rpt_adaptive.hip: masked passes over chosen pixels, per-pixel counts to a noise target; rpt_debug.hip: test hooks).  k_image_order.h: the one kernel and the one read-out routine that turn the tile-major pixel order
  * into a row-major image, for every unit that hands one to the caller.
  */
 #ifndef RPT_CTX_H
@@ -146,6 +146,33 @@ struct DenoiseState {
 
 struct rpt_comm;                  /* rpt_comm.hip: RCCL communicator + gather buffers of one context */
 
+/* The pixels a render call works on when they are not the context's own: the compact copies a masked pass made of the selected pixels' records
+ * (rpt_adaptive.hip).  render_impl (rpt_hip.hip) swaps them in for the call — state.{pixel_xy, rng, accum, n_pixels}, n_pixels, the moments record the
+ * completion kernel and plan_slots look at, max_group_shift / max_slots — and puts the context's own back on every exit path. */
+struct PixelView {
+    const uint32_t *pixel_xy;
+    uint2 *rng;
+    float4 *accum;
+    float4 *moments;                      /* null unless moments are on */
+    uint32_t n_pixels;
+    uint32_t max_group_shift;             /* log2 of the most slots per pixel the view may keep busy (rpt_adaptive.hip view_max_shift) */
+};
+
+/* rpt_adaptive.hip: what masked passes keep on a context — allocated at first use, grown and never shrunk, released with the pixel state and on destroy */
+struct AdaptiveState {
+    DevBuf<uint8_t> mask, flags;          /* the caller's row-major mask as uploaded; one flag byte per owned pixel */
+    DevBuf<uint32_t> wg_count, wg_offset; /* flagged pixels per workgroup of 256 pixels, and their exclusive scan */
+    DevBuf<unsigned long long> result;    /* an AdResult (k_adaptive.h): n_active, the noise counts, the range of m.z */
+    DevBuf<uint32_t> active, pixel_xy;    /* the compact arrays: active[i] = the pixel entry i came from, and the copies of its records */
+    DevBuf<uint2> rng;
+    DevBuf<float4> accum, moments;
+    uint32_t n_active = 0;                /* of the last selection read (rpt_adaptive_selected): what the next pass gathers */
+    void release() {
+        mask.release(); flags.release(); wg_count.release(); wg_offset.release(); result.release();
+        active.release(); pixel_xy.release(); rng.release(); accum.release(); moments.release();
+    }
+};
+
 /* Every environment variable the library reads, read in ONE place (rpt_read_knobs, rpt_hip.hip; rpt_create copies them into the context).  None changes
  * a result (tests/test_gpu_parity.py::test_developer_knobs_do_not_change_the_image); they exist for tests that must reach a code path a shipped scene
  * does not take, and for the bench's stage timing.  Rounds 1-5 had thirty — every A/B of a tuning round left one behind, with the losing code path kept alive
@@ -220,6 +247,7 @@ struct rpt_ctx {
 
     /* state */
     bool has_state = false;
+    bool has_seeds = false;              /* rpt_reset has seeded the pixel state that is allocated now (the masked entry points insist on it) */
     DevBuf<float2> ray_b, hit;
     DevBuf<float4> ray_a, thr, rad, mis_a, mis_b, accum;
     DevBuf<uint2> rng;
@@ -232,7 +260,11 @@ struct rpt_ctx {
     DevBuf<DevStats> dev_stats;
     DevState state{};
     DevQueues queues{};
-    uint32_t samples = 0;
+    uint32_t samples = 0;                /* the samples EVERY owned pixel received through uniform calls (what rpt_read_accum reports) */
+    bool counts_nonuniform = false;      /* a masked pass gave samples to some owned pixels only: accum.w differs between pixels, the read-outs divide by it
+                                            (k_adaptive.h mean_own).  Cleared by rpt_reset and by whatever invalidates the accumulator. */
+    const PixelView *view = nullptr;     /* set for the duration of a masked pass's render call */
+    AdaptiveState ad;
     bool first_walk_starts = false;   /* the current / last render call was opened without a pass over the slots: its first walk starts the paths (rpt_first_walk_starts_paths) */
     uint32_t call_samples = 0;  /* n_samples of the current / last rpt_render call (the shade stage of its first iteration derives what a slot owes) */
 
@@ -277,13 +309,35 @@ void rpt_build_pixel_order(uint32_t W, uint32_t H, uint32_t rank, uint32_t world
 /* rpt_comm.hip: called by rpt_hip.hip when the context goes away */
 void rpt_comm_release(rpt_ctx *c);
 /* rpt_comm.hip, for rpt_denoise(RPT_DENOISE_GATHERED): the image of the last gather on rank 0 of a communicator, once that gather has completed, its sample
- * count and the stream the gather ran on (work on it is ordered after the gather and overlaps the batch on the context's own stream) */
-int rpt_comm_gathered_image(rpt_ctx *c, const float4 **image_out, uint32_t *samples_out, hipStream_t *stream_out);
+ * count, whether the counts were non-uniform when it was snapshotted, and the stream the gather ran on (work on it is ordered after the gather and overlaps the batch on the context's own stream) */
+int rpt_comm_gathered_image(rpt_ctx *c, const float4 **image_out, uint32_t *samples_out, bool *nonuniform_out, hipStream_t *stream_out);
 /* rpt_moments.hip: the moments record of a context with moments on, for its current pixel count: allocated if need be and zeroed on the context's stream */
 int rpt_moments_reset(rpt_ctx *c);
 /* rpt_moments.hip, for rpt_multi_render_to_noise (rpt_comm.hip): the loop of rpt_render_to_noise over the caller's "render n more samples" and "count" */
 int rpt_render_to_noise_with(const rpt_noise_target *target, rpt_noise_result *out, std::string &error, int (*render)(void *, uint32_t), int (*count)(void *, float, rpt_noise_counts *),
                              void *who);
+/* rpt_hip.hip, for rpt_adaptive.hip: n_samples more samples for the pixels of `view` through the pipeline of rpt_render_async (returns once enqueued when the
+ * batch's length is known).  Counts view->n_pixels x n_samples into rpt_stats.samples and nothing into the context's uniform sample count. */
+int rpt_render_view(rpt_ctx *c, uint32_t n_samples, const PixelView *view);
+/* rpt_adaptive.hip, for the rpt_multi_* forms (rpt_comm.hip): the three steps of a masked pass on one rank, so that several ranks' passes overlap.
+ * select: flags, counts and scan enqueued on the context's stream (mask != null: the byte mask; else the selection rule on the moments with `target`);
+ * selected: waits and reads what was selected; pass: gather what was last read as selected, n_samples through rpt_render_view, scatter back (nothing when nothing was). */
+struct rpt_adaptive_selection { uint32_t n_active, z_min, z_max; rpt_noise_counts counts; };
+int rpt_adaptive_select(rpt_ctx *c, const uint8_t *mask, const rpt_noise_target *target);
+int rpt_adaptive_selected(rpt_ctx *c, bool with_counts, rpt_adaptive_selection *out);
+int rpt_adaptive_pass(rpt_ctx *c, uint32_t n_samples, bool uniform_ok /* a pass that selected every owned pixel may run as the uniform call it is */);
+/* rpt_moments.hip: the refusals of a noise target, named after the entry point `who` */
+int rpt_noise_check_target(const rpt_noise_target &t, std::string &error, const char *who);
+/* the loop of rpt_render_adaptive / rpt_multi_render_adaptive over the caller's "n uniform samples", "select and report" and "render the selected" */
+struct rpt_adaptive_driver {
+    int (*render)(void *who, uint32_t n_samples, uint64_t *pixel_samples_out);
+    int (*select)(void *who, const rpt_noise_target *target, rpt_adaptive_selection *out);
+    int (*pass)(void *who, uint32_t n_samples);
+};
+/* rpt_resolve while the counts are non-uniform: every pixel's sum by its own accum.w (its kernel is compiled in rpt_adaptive.hip, so that the code object of
+ * rpt_hip.hip — the pipeline's kernels — is the one it was) */
+int rpt_resolve_own(rpt_ctx *c, uint32_t tonemap_op, float *out_rgb);
+int rpt_render_adaptive_with(const rpt_noise_target *target, rpt_adaptive_result *out, const rpt_adaptive_driver &driver, void *who);
 /* rpt_denoise.hip: the denoiser's buffers go (a resize), or buffers and events (the context goes away: while its device is current) */
 void rpt_denoise_release(rpt_ctx *c, bool events_too);
 std::string &rpt_create_error();

@@ -8,6 +8,7 @@
 
 #include "rpt_ctx.h"
 #include "k_denoise.h"
+#include "k_adaptive.h"
 
 namespace {
 
@@ -72,6 +73,17 @@ int ensure_guides(rpt_ctx *c, bool *rebuilt) {
     return RPT_OK;
 }
 
+/* k_dn_prepare while the counts are non-uniform: every pixel's sum by its own count (k_adaptive.h mean_own) */
+__global__ __launch_bounds__(RPT_BLOCK) void k_dn_prepare_own(const float4 *sums, const uint32_t *order, uint32_t n, uint32_t width, const float4 *albedo /* null: no demodulation */, float4 *out) {
+    const uint32_t i = blockIdx.x * RPT_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    size_t at = i;
+    if (order) at = rpt_pixel_index(order[i], width);
+    F3 c = mean_own(sums[i]);
+    if (albedo) c = dn_demodulate(c, xyz4(albedo[at]));
+    out[at] = make_float4(c.x, c.y, c.z, 0.0f);
+}
+
 void launch_pass(hipStream_t s, const DnPass &ps, bool last, const float4 *src, const DenoiseState &d, float4 *dst, uint32_t demodulated, uint32_t tonemap_op) {
     const dim3 grid((ps.width + 63u) / 64u, (ps.height + 3u) / 4u);
     if (last) k_dn_pass<true><<<grid, 256, 0, s>>>(ps, src, d.g0.p, d.g1.p, dst, d.albedo.p, demodulated, tonemap_op, d.rgb.p);
@@ -106,22 +118,24 @@ int rpt_denoise(rpt_ctx *c, uint32_t source, const rpt_denoise_params *params, u
     const float4 *sums = nullptr;
     const uint32_t *order = nullptr;
     uint32_t samples = 0;
+    bool own_counts = false;             /* counts are non-uniform: every pixel by its own accum.w */
     hipStream_t s = c->stream;
     if (source == RPT_DENOISE_ACCUM) {
         if (c->world != 1u) { c->error = "rpt_denoise: RPT_DENOISE_ACCUM needs a partition of one rank (this context is one of " + std::to_string(c->world) + "): gather, then RPT_DENOISE_GATHERED on rank 0"; return RPT_EINVAL; }
         RPT_TRY(rpt_wait(c));
-        sums = c->accum.p; order = c->pixel_xy.p; samples = c->samples;
+        sums = c->accum.p; order = c->pixel_xy.p; samples = c->samples; own_counts = c->counts_nonuniform;
     } else {
-        RPT_TRY(rpt_comm_gathered_image(c, &sums, &samples, &s));
+        RPT_TRY(rpt_comm_gathered_image(c, &sums, &samples, &own_counts, &s));
     }
-    if (samples == 0u) { c->error = "rpt_denoise: the image has zero samples"; return RPT_EINVAL; }
+    if (samples == 0u && !own_counts) { c->error = "rpt_denoise: the image has zero samples"; return RPT_EINVAL; }
     bool rebuilt = false;
     RPT_TRY(ensure_guides(c, &rebuilt));
     DenoiseState &d = c->dn;
     const uint32_t W = d.width, H = d.height, n = W * H;
     const bool demodulated = p.iterations != 0u && p.demodulate != 0u;
     HIP_TRY(c, hipEventRecord(d.ev[2], s));
-    k_dn_prepare<<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(sums, order, n, W, (float)samples, demodulated ? d.albedo.p : nullptr, d.ping.p);
+    if (own_counts) k_dn_prepare_own<<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(sums, order, n, W, demodulated ? d.albedo.p : nullptr, d.ping.p);
+    else k_dn_prepare<<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(sums, order, n, W, (float)samples, demodulated ? d.albedo.p : nullptr, d.ping.p);
     if (p.iterations == 0u) k_dn_resolve<<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(d.ping.p, n, tonemap_op, d.rgb.p);
     float4 *src = d.ping.p, *dst = d.pong.p;
     for (uint32_t i = 0; i < p.iterations; ++i) {

@@ -108,9 +108,11 @@ void release_state(rpt_ctx *c) {
     c->q_sky.release(); c->q_count.release(); c->ray_shards.release();
     c->sh_o.release(); c->sh_d.release(); c->sh_c.release();
     c->pixel_xy.release();
+    c->ad.release();
     c->image.release(); c->host_image.release(); c->untile_map.release();
     c->untile_key = 0;
     c->has_state = false;
+    c->has_seeds = false;
 }
 
 /* Stream discipline: the context's stream is NON-BLOCKING, so nothing on the legacy default stream is ordered against it.
@@ -154,9 +156,9 @@ static uint32_t padded_pixels(uint32_t n_pixels) { return (n_pixels + 63u) & ~63
 
 /* one wave per chunk of 64 pixels (k_complete.h) */
 static void launch_complete(rpt_ctx *c, uint32_t iteration, uint32_t final_pass) {
-    if (c->moments_on) {             /* (rpt_set_moments: the same completion, the samples added to the moments record too) */
+    if (c->moments_on) {             /* (rpt_set_moments: the same completion, the samples added to the moments record too — the view's compact one in a masked pass) */
         k_complete_moments<<<padded_pixels(c->n_pixels) / RPT_WAVE, RPT_WAVE, complete_lds_bytes(1u << c->group_shift, c->state.q_shift), c->stream>>>(c->state, c->queues, c->cfg, iteration,
-                                                                                                                                 final_pass, c->dev_stats.p, c->moments.p);
+                                                                                                                                 final_pass, c->dev_stats.p, c->view ? c->view->moments : c->moments.p);
         return;
     }
     k_complete<<<padded_pixels(c->n_pixels) / RPT_WAVE, RPT_WAVE, complete_lds_bytes(1u << c->group_shift, c->state.q_shift), c->stream>>>(c->state, c->queues, c->cfg, iteration, final_pass,
@@ -426,6 +428,7 @@ int rpt_set_config(rpt_ctx *c, const rpt_tracing_config *cfg) {
             HIP_TRY(c, hipMemsetAsync(c->rng.p, 0, c->n_pixels * sizeof(uint2), c->stream));
         }
         c->samples = 0;
+        c->counts_nonuniform = false;
         RPT_TRY(rpt_moments_reset(c));       /* (moments on: a record for the new pixel count, zeroed like the accumulator) */
     }
     c->has_config = true;
@@ -455,6 +458,8 @@ int rpt_reset(rpt_ctx *c, const rpt_rng_state *seed, const float *accum_init, ui
     HIP_TRY(c, hipMemsetAsync(c->ray_shards.p, 0, RPT_STAT_SHARDS * RPT_STAT_STRIDE * sizeof(unsigned long long), c->stream));
     RPT_TRY(rpt_moments_reset(c));           /* (not resumed: with accum_init the record counts the samples rendered from here on) */
     c->samples = accum_init ? samples_init : 0u;
+    c->counts_nonuniform = false;
+    c->has_seeds = true;
     c->stats = rpt_stats{};
     return RPT_OK;
 }
@@ -522,7 +527,7 @@ static int plan_slots(rpt_ctx *c, uint32_t n_samples) {
         }
         shift = 1u;
     }
-    if (c->moments_on && c->moments.n != c->n_pixels) {      /* (an allocation of the record failed earlier: k_complete_moments must not be launched without it) */
+    if (c->moments_on && (c->view ? c->view->moments == nullptr : c->moments.n != c->n_pixels)) {      /* (an allocation of the record failed earlier: k_complete_moments must not be launched without it) */
         c->error = "moments are on but their record is not allocated (an earlier allocation failed): call rpt_set_moments(ctx, 0)";
         return RPT_ENOMEM;
     }
@@ -563,15 +568,45 @@ static void count_batch(rpt_ctx *c, uint32_t n_samples, uint64_t iterations, uin
     c->stats.kernel_launches[RPT_STAGE_SHADE] += shade_launches;      /* (one per iteration, but none behind a walk that ended its paths itself) */
     c->stats.kernel_launches[RPT_STAGE_SHADOW] += c->cfg.nee_mode != RPT_NEE_NONE ? iterations : 0;
     c->stats.kernel_launches[RPT_STAGE_SKY] += c->queues.sky_at_end ? 1u : iterations;
-    c->samples += n_samples;
+    if (!c->view) c->samples += n_samples;        /* (a masked pass: its pixels' own counts move, accum.w and rng.n, not the context's uniform one) */
     c->stats.samples += (uint64_t)c->n_pixels * n_samples;
     c->stats.render_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-static int render_impl(rpt_ctx *c, uint32_t n_samples, bool allow_async) {
+/* A masked pass's pixels in place of the context's own for one render call (rpt_ctx.h PixelView): everything the pipeline derives from the pixel count —
+ * slots, q-shift, "at least two slots" with moments, known length or polled, implicit_zero, who starts the paths — then follows from the view exactly as
+ * it does for a rank that owns few pixels.  The destructor puts the context's own back: every exit path of render_impl passes through it. */
+struct ViewScope {
+    rpt_ctx *c;
+    const uint32_t *pixel_xy;
+    uint2 *rng;
+    float4 *accum;
+    uint32_t n_pixels, max_group_shift, max_slots;
+    ViewScope(rpt_ctx *ctx, const PixelView *v) : c(ctx), pixel_xy(ctx->state.pixel_xy), rng(ctx->state.rng), accum(ctx->state.accum), n_pixels(ctx->n_pixels),
+                                                  max_group_shift(ctx->max_group_shift), max_slots(ctx->max_slots) {
+        if (!v) return;
+        c->view = v;
+        c->state.pixel_xy = v->pixel_xy; c->state.rng = v->rng; c->state.accum = v->accum; c->state.n_pixels = v->n_pixels;
+        c->n_pixels = v->n_pixels;
+        c->max_group_shift = v->max_group_shift;
+        c->max_slots = padded_pixels(v->n_pixels) << v->max_group_shift;
+    }
+    ViewScope(const ViewScope &) = delete;
+    ~ViewScope() {
+        if (!c->view) return;
+        c->view = nullptr;
+        c->state.pixel_xy = pixel_xy; c->state.rng = rng; c->state.accum = accum; c->state.n_pixels = n_pixels;
+        c->n_pixels = n_pixels;
+        c->max_group_shift = max_group_shift;
+        c->max_slots = max_slots;
+    }
+};
+
+static int render_impl(rpt_ctx *c, uint32_t n_samples, bool allow_async, const PixelView *view = nullptr) {
     if (!c) return RPT_EINVAL;
     if (!c->has_scene || !c->has_config || !c->has_state) { c->error = "scene, config and reset must precede rpt_render"; return RPT_EINVAL; }
-    if (n_samples == 0 || c->n_pixels == 0) { c->samples += n_samples; return RPT_OK; }
+    const ViewScope scope(c, view);
+    if (n_samples == 0 || c->n_pixels == 0) { if (!view) c->samples += n_samples; return RPT_OK; }
     if ((uint64_t)n_samples + (1u << c->max_group_shift) >= 0x100000000ull) { c->error = "n_samples too large"; return RPT_EINVAL; }
     RPT_TRY(plan_slots(c, n_samples));
     /* KNOWN LENGTH OR POLLED.  When no slot gets a second sample in this call (n_samples <= slots per pixel) nothing is regenerated: every path
@@ -728,6 +763,7 @@ int rpt_resolve(rpt_ctx *c, uint32_t tonemap_op, float *out_rgb) {
     if (!c || !out_rgb) return RPT_EINVAL;
     if (!c->has_state) { c->error = "nothing to resolve: no config"; return RPT_EINVAL; }
     if (tonemap_op > 6u) { c->error = "tonemap operator must be 0..6"; return RPT_EINVAL; }
+    if (c->counts_nonuniform) return rpt_resolve_own(c, tonemap_op, out_rgb);     /* (every pixel by its own accum.w: rpt_adaptive.hip) */
     return rpt_read_out(c, PixelResolve{c->accum.p, (float)c->samples, tonemap_op, nullptr}, out_rgb);
 }
 
@@ -759,3 +795,6 @@ int rpt_debug_short_batch(rpt_ctx *c, int on) {
 }
 
 }  // extern "C"
+
+/* rpt_adaptive.hip: the batch of a masked pass, on the compact copies of the selected pixels' records */
+int rpt_render_view(rpt_ctx *c, uint32_t n_samples, const PixelView *view) { return render_impl(c, n_samples, true, view); }

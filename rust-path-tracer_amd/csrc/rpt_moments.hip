@@ -40,13 +40,6 @@ int need_moments(rpt_ctx *c, const char *who) {
 
 bool bad_threshold(float t) { return !(t >= 0.0f); }       /* negative or NaN (+inf is a threshold: nothing is above it but a NaN) */
 
-int check_target(const rpt_noise_target &t, std::string &error) {
-    if (t.batch_samples == 0u) { error = "rpt_render_to_noise: batch_samples must be > 0"; return RPT_EINVAL; }
-    if (t.max_samples < t.min_samples) { error = "rpt_render_to_noise: max_samples must be >= min_samples"; return RPT_EINVAL; }
-    if (bad_threshold(t.threshold)) { error = "rpt_render_to_noise: threshold must be >= 0"; return RPT_EINVAL; }
-    return RPT_OK;
-}
-
 /* the count on the context's stream behind whatever is enqueued, one wait, 24 bytes back */
 int count_impl(rpt_ctx *c, float threshold, rpt_noise_counts *out) {
     HIP_TRY(c, hipSetDevice(c->device));
@@ -87,6 +80,13 @@ static int render_to_noise_loop(const rpt_noise_target &t, rpt_noise_result *out
     return RPT_OK;
 }
 
+int rpt_noise_check_target(const rpt_noise_target &t, std::string &error, const char *who) {
+    if (t.batch_samples == 0u) { error = std::string(who) + ": batch_samples must be > 0"; return RPT_EINVAL; }
+    if (t.max_samples < t.min_samples) { error = std::string(who) + ": max_samples must be >= min_samples"; return RPT_EINVAL; }
+    if (bad_threshold(t.threshold)) { error = std::string(who) + ": threshold must be >= 0"; return RPT_EINVAL; }
+    return RPT_OK;
+}
+
 int rpt_moments_reset(rpt_ctx *c) {
     if (!c->moments_on) return RPT_OK;
     if (c->moments.n != c->n_pixels) HIP_TRY(c, c->moments.alloc(c->n_pixels));
@@ -97,7 +97,7 @@ int rpt_moments_reset(rpt_ctx *c) {
 /* rpt_multi_render_to_noise (rpt_comm.hip owns rpt_multi): the same loop over its render and count */
 int rpt_render_to_noise_with(const rpt_noise_target *target, rpt_noise_result *out, std::string &error, int (*render)(void *, uint32_t), int (*count)(void *, float, rpt_noise_counts *),
                              void *who) {
-    RPT_TRY(check_target(*target, error));
+    RPT_TRY(rpt_noise_check_target(*target, error, "rpt_render_to_noise"));
     const float threshold = target->threshold;
     return render_to_noise_loop(*target, out, [=](uint32_t n) { return render(who, n); }, [=](rpt_noise_counts *k) { return count(who, threshold, k); });
 }
@@ -148,7 +148,7 @@ int rpt_noise_count(rpt_ctx *c, float threshold, rpt_noise_counts *out) {
 
 int rpt_render_to_noise(rpt_ctx *c, const rpt_noise_target *target, rpt_noise_result *out) {
     if (!c || !target || !out) return RPT_EINVAL;
-    RPT_TRY(check_target(*target, c->error));
+    RPT_TRY(rpt_noise_check_target(*target, c->error, "rpt_render_to_noise"));
     if (!c->has_scene || !c->has_config || !c->has_state) { c->error = "scene, config and reset must precede rpt_render_to_noise"; return RPT_EINVAL; }
     RPT_TRY(rpt_set_moments(c, 1u));
     const float threshold = target->threshold;

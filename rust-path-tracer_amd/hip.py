@@ -48,6 +48,12 @@ class NoiseResult(C.Structure):
     _fields_ = [("samples_rendered", C.c_uint32), ("converged", C.c_uint32), ("counts", NoiseCounts), ("ms", C.c_double)]
 
 
+class AdaptiveResult(C.Structure):
+    """rpt_adaptive_result"""
+    _fields_ = [("passes", C.c_uint32), ("converged", C.c_uint32), ("min_pixel_samples", C.c_uint32), ("max_pixel_samples", C.c_uint32),
+                ("pixel_samples", C.c_uint64), ("counts", NoiseCounts), ("ms", C.c_double)]
+
+
 def _counts_dict(k):
     return {"pixels": k.pixels, "measured": k.measured, "above": k.above}
 
@@ -143,6 +149,11 @@ PROTOTYPES = {
     "rpt_multi_read_moments": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rpt_multi_noise_count": (C.c_int, [C.c_void_p, C.c_float, C.POINTER(NoiseCounts)]),
     "rpt_multi_render_to_noise": (C.c_int, [C.c_void_p, C.POINTER(NoiseTarget), C.POINTER(NoiseResult)]),
+    "rpt_render_pixels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "rpt_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(NoiseTarget), C.POINTER(AdaptiveResult)]),
+    "rpt_counts_uniform": (C.c_int, [C.c_void_p, _OUT_U32]),
+    "rpt_multi_render_pixels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "rpt_multi_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(NoiseTarget), C.POINTER(AdaptiveResult)]),
     "rpt_bvh_build_gpu": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, _OUT_SIZE, _OUT_F64]),
     "rpt_light_table_build_gpu": (C.c_int, [C.c_int] + [C.c_void_p, C.c_size_t] * 4 + [_OUT_SIZE, _OUT_U32, _OUT_F64]),
     "rpt_debug_math": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -157,6 +168,7 @@ PROTOTYPES = {
     "rpt_debug_comm_selftest": (C.c_int, [C.c_void_p, C.c_uint32, _OUT_U64]),
     "rpt_debug_denoise_host": (C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 6 + [C.POINTER(DenoiseParams), C.c_uint32, C.c_void_p]),
     "rpt_debug_noise_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.POINTER(NoiseCounts)]),
+    "rpt_debug_adaptive_select_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, _OUT_SIZE]),
     "rpt_debug_short_batch": (C.c_int, [C.c_void_p, C.c_int]),
 }
 EXPORTS = sorted(PROTOTYPES)
@@ -300,6 +312,23 @@ class _Handle:
         self._call("render_to_noise", C.byref(t), C.byref(res))
         return _noise_result_dict(res)
 
+    # -- chosen pixels (include/rpt/rpt.h "chosen pixels")
+    def render_pixels(self, mask, n_samples):
+        """rpt_render_pixels (rpt_multi_: every rank among its own pixels, then the gather): n_samples more samples for the pixels whose entry of `mask`
+        (H, W), any dtype, is non-zero.  Returns once enqueued when the batch's length is known, as render_async."""
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+        assert mask.size == self.config.height * self.config.width
+        self._call("render_pixels", ptr(mask), n_samples)
+
+    def render_adaptive(self, threshold, max_above=0, batch_samples=8, min_samples=8, max_samples=256):
+        """rpt_render_adaptive: min_samples for every pixel, then passes of batch_samples for the pixels whose noise is not yet at or below threshold and
+        that stay within max_samples, until at most max_above are above or nothing is selected: {"passes", "converged", "min_pixel_samples",
+        "max_pixel_samples", "pixel_samples", "counts", "ms"}.  Turns moments on and leaves them on."""
+        t, res = NoiseTarget(threshold, min_samples, max_samples, batch_samples, max_above), AdaptiveResult()
+        self._call("render_adaptive", C.byref(t), C.byref(res))
+        return {"passes": res.passes, "converged": res.converged, "min_pixel_samples": res.min_pixel_samples, "max_pixel_samples": res.max_pixel_samples,
+                "pixel_samples": res.pixel_samples, "counts": _counts_dict(res.counts), "ms": res.ms}
+
     def _get_stats(self):
         s = Stats()
         self._call("get_stats", C.byref(s))
@@ -383,6 +412,13 @@ class Renderer(_Handle):
         on = C.c_uint32()
         self._check(lib().rpt_moments(self._h, C.byref(on)))
         return bool(on.value)
+
+    def counts_uniform(self):
+        """rpt_counts_uniform: False once a masked or adaptive pass has rendered for fewer than all owned pixels (resolve and denoise then divide every pixel
+        by its own count), True again after reset"""
+        u = C.c_uint32()
+        self._check(lib().rpt_counts_uniform(self._h, C.byref(u)))
+        return bool(u.value)
 
     def read_noise(self):
         """rpt_read_noise: (H, W) float32, the standard error of every pixel's mean luminance relative to that mean (inf below two samples); other ranks' pixels 0"""
@@ -593,6 +629,10 @@ class MultiRenderer(_Handle):
     def moments_on(self):
         return self.rank_view(0).moments_on()
 
+    def counts_uniform(self):
+        """rpt_counts_uniform of every rank"""
+        return all(self.rank_view(k).counts_uniform() for k in range(self.size()))
+
     def read_noise(self):
         """noise_host of read_moments(): the whole (H, W) image (there is no multi-GPU entry point for it: the arithmetic is the same header on the host)"""
         return noise_host(self.read_moments())[0]
@@ -687,6 +727,20 @@ def noise_host(moments, threshold=0.0):
     if rc != 0:
         raise RptError(rc, lib().rpt_last_error(None).decode())
     return rel, _counts_dict(k)
+
+
+def adaptive_select_host(moments, threshold, batch_samples, max_samples):
+    """rpt_debug_adaptive_select_host: the selection rule of render_adaptive over the records `moments` (..., 4) and their ordered compaction, on the host
+    from the same header (no GPU needed): (flags uint8 with the leading shape of moments, the selected records' flat indices in ascending order)"""
+    moments = np.ascontiguousarray(moments, np.float32)
+    assert moments.shape[-1] == 4
+    flags = np.zeros(moments.shape[:-1], np.uint8)
+    active = np.zeros(flags.size, np.uint32)
+    n = C.c_size_t()
+    rc = lib().rpt_debug_adaptive_select_host(ptr(moments), flags.size, threshold, batch_samples, max_samples, ptr(flags), ptr(active), C.byref(n))
+    if rc != 0:
+        raise RptError(rc, lib().rpt_last_error(None).decode())
+    return flags, active[: n.value]
 
 
 def light_table_build_gpu(vertices_xyzw, triangles, materials, device=0):
