@@ -59,6 +59,14 @@ pub struct rpt_denoise_params {
 
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
+pub struct rpt_denoise_var_params {
+    pub base: rpt_denoise_params,
+    pub sigma_variance: f32,      // width of the luminance term in standard errors of the pixel's mean; 0 = term off
+    pub reserved: [u32; 3],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
 pub struct rpt_denoise_report {
     pub device_ms: f64,
     pub guides_ms: f64,
@@ -139,6 +147,9 @@ extern "C" {
     // the denoise step, trace.rs:205-213 (there OIDN): params null = defaults, report nullable; source RPT_DENOISE_ACCUM | RPT_DENOISE_GATHERED
     pub fn rpt_denoise_params_default(out: *mut rpt_denoise_params);
     pub fn rpt_denoise(ctx: *mut rpt_ctx, source: u32, params: *const rpt_denoise_params, tonemap_op: u32, out_rgb: *mut f32, report: *mut rpt_denoise_report) -> c_int;
+    // rpt_denoise with the variance-guided luminance term: moments null = the context's own record (ACCUM only), else a width*height Vec4 image; out_variance nullable
+    pub fn rpt_denoise_var_params_default(out: *mut rpt_denoise_var_params);
+    pub fn rpt_denoise_variance(ctx: *mut rpt_ctx, source: u32, moments_xyzw: *const f32, params: *const rpt_denoise_var_params, tonemap_op: u32, out_rgb: *mut f32, out_variance: *mut f32, report: *mut rpt_denoise_report) -> c_int;
     pub fn rpt_read_guides(ctx: *mut rpt_ctx, albedo_rgb: *mut f32, normal_xyz: *mut f32, depth: *mut f32, position_xyz: *mut f32, kind: *mut u32) -> c_int;   // each nullable; albedo / normal = OIDN's auxiliary images
     // opt-in per-pixel sample moments (sum Y, sum Y^2, n, max Y), the noise estimate from them, and "render until the image is this clean"
     pub fn rpt_set_moments(ctx: *mut rpt_ctx, on: u32) -> c_int;                    // default 0; on: allocates and zeroes the record
@@ -173,6 +184,7 @@ extern "C" {
     pub fn rpt_multi_wait(m: *mut rpt_multi) -> c_int;
     pub fn rpt_multi_read_accum(m: *mut rpt_multi, out: *mut Vec4, out_samples: *mut u32) -> c_int;   // the whole W x H image, from rank 0
     pub fn rpt_multi_denoise(m: *mut rpt_multi, params: *const rpt_denoise_params, tonemap_op: u32, out_rgb: *mut f32, report: *mut rpt_denoise_report) -> c_int;   // waits, gathers, denoises on rank 0
+    pub fn rpt_multi_denoise_variance(m: *mut rpt_multi, params: *const rpt_denoise_var_params, tonemap_op: u32, out_rgb: *mut f32, out_variance: *mut f32, report: *mut rpt_denoise_report) -> c_int;   // moments merged on the host, then as rpt_multi_denoise
     pub fn rpt_multi_set_moments(m: *mut rpt_multi, on: u32) -> c_int;              // rpt_set_moments on every rank
     pub fn rpt_multi_read_moments(m: *mut rpt_multi, out_xyzw: *mut Vec4) -> c_int; // the ranks' records merged on the host
     pub fn rpt_multi_noise_count(m: *mut rpt_multi, threshold: f32, out: *mut rpt_noise_counts) -> c_int;   // summed over the ranks

@@ -411,6 +411,46 @@ int rpt_multi_read_moments(rpt_multi *m, float *out_xyzw);
 int rpt_multi_noise_count(rpt_multi *m, float threshold, rpt_noise_counts *out);
 int rpt_multi_render_to_noise(rpt_multi *m, const rpt_noise_target *target, rpt_noise_result *out);
 
+/* --- variance-guided denoise: the filter of rpt_denoise with one more edge-stopping term, driven by the per-pixel moments (Schied et al. 2017) ---------
+ * Opt-in, a second entry point: rpt_denoise, its kernels and its defaults are what they were.  From a moments record m of a pixel (n = m.z) the pre-pass takes
+ * the empirical variance of the pixel's MEAN luminance (csrc/k_moments.h mo_variance_of_mean; the square of noise_rel's standard error, not divided by the mean):
+ *     v = max(0, m.y - (m.x * m.x) / n) / (n * (n - 1))          UNKNOWN, written +inf, if n < 2 or m.x or m.y is not finite
+ * and, where the mean is demodulated, divides it by Ya * Ya, Ya = the luminance of max(albedo, 0.01): v is in the units of the filtered image's luminance,
+ * squared.  The mean itself is rpt_denoise's (by the uniform count, or by every pixel's own .w while rpt_counts_uniform is 0).  Pass i, centre p
+ * (csrc/k_denoise.h dn_filter_pixel_var, DESIGN.md "Denoiser"):
+ *     vbar_p = the 3 x 3 Gaussian {1/4, 1/2, 1/4}^2 of the pass's input variance around p (distance 1 at every step) over the taps inside the image, of p's
+ *              kind and of known variance, divided by the kernel weights used; unknown if there is no such tap
+ *     d_l    = |Y(e_p) - Y(e_q)| / (sigma_variance * sqrt(vbar_p) + 1e-6)     added to d_x + d_c of tap q, if sigma_variance != 0 and vbar_p is known
+ *     v_out  = sum(w^2 v_q) / sum(w)^2 over the joined taps of known variance, the centre included; known iff the centre's was
+ * Every other rule is rpt_denoise's.  With sigma_variance == 0, or where vbar_p is unknown (every record unmeasured, say), no term is added and the image is
+ * rpt_denoise(base)'s bit for bit.  A pixel whose neighbourhood has zero variance — all samples equal, which an empirical variance reads as converged —
+ * joins only taps of (almost) equal luminance: sigma_variance * 0 + 1e-6 is the width.  sigma_variance = +inf is allowed: where vbar_p > 0 the width is
+ * +inf and d_l = 0; where vbar_p == 0 the width is inf * 0 = NaN, d_l and w are NaN, and by rpt_denoise's rule (a weight that is not > 0 never joins) no
+ * tap joins: such a pixel passes through unchanged.
+ * After rpt_reset with accum_init the moments count only the samples rendered since, while the accumulator continues: v is then the variance of the mean
+ * of the samples SINCE THE RESET, a larger figure than that of the whole accumulator's mean.
+ *
+ * moments_xyzw == NULL   the context's own record, on the device, no host trip.  Only with RPT_DENOISE_ACCUM; RPT_EINVAL while moments are off.
+ * moments_xyzw != NULL   a width*height float4 row-major image — what rpt_read_moments / rpt_multi_read_moments return — uploaded for this call; with either
+ *                        source.  The way a process-per-GPU caller filters a gathered image: moments are not part of the gather.
+ * out_variance (nullable, width*height floats): the last pass's v_out, in the filter's units (demodulated where demodulation was applied; iterations == 0:
+ *                        the pre-pass's v, never demodulated); unknown = +inf.
+ * RPT_EINVAL for a negative or NaN sigma_variance, a null out_rgb, and for everything rpt_denoise refuses; the context stays usable.  Synchronous on
+ * return; leaves the accumulator, the rng, the moments, rpt_stats, the shadow mode and the cached guides untouched.
+ * rpt_multi_denoise_variance merges the ranks' records on the host as rpt_multi_read_moments does (OFF THE HOT PATH: a read-back and an upload of 16 bytes
+ * per pixel on every call), gathers as rpt_multi_denoise does, and filters on rank 0.
+ * Defaults: the lowest summed error of the grid of profiles/r14_denoise_variance_quality.txt. */
+typedef struct rpt_denoise_var_params {
+    rpt_denoise_params base;      /* as rpt_denoise */
+    float    sigma_variance;      /* width of the luminance term in standard errors; 0 = term off */
+    uint32_t reserved[3];
+} rpt_denoise_var_params;
+void rpt_denoise_var_params_default(rpt_denoise_var_params *out);
+int rpt_denoise_variance(rpt_ctx *ctx, uint32_t source, const float *moments_xyzw /* nullable */, const rpt_denoise_var_params *params /* NULL = defaults */,
+                         uint32_t tonemap_op, float *out_rgb, float *out_variance /* nullable, width*height */, rpt_denoise_report *report /* nullable */);
+int rpt_multi_denoise_variance(rpt_multi *m, const rpt_denoise_var_params *params, uint32_t tonemap_op, float *out_rgb, float *out_variance,
+                               rpt_denoise_report *report);
+
 /* --- chosen pixels: masked passes, per-pixel sample counts to a noise target (no reference equivalent) --------------------------------------------------
  * Opt-in; a context that never makes a masked or adaptive call runs the same kernels as before, and bench.py's figures are not touched.
  * A sample depends only on its pixel's (x, y), its rng (n, offset) and the scene, and samples are added in sample order: a pixel that has received N samples

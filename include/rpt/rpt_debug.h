@@ -74,6 +74,13 @@ int rpt_debug_comm_selftest(rpt_ctx *ctx, uint32_t n_floats, uint64_t *mismatche
 int rpt_debug_denoise_host(uint32_t width, uint32_t height, const float *mean_rgb, const float *albedo, const float *normal, const float *position,
                            const float *depth, const uint32_t *kind, const rpt_denoise_params *params, uint32_t tonemap_op, float *out_rgb);
 
+/* The variance-guided filter of rpt_denoise_variance on the HOST: the same headers (csrc/k_denoise.h, k_moments.h) in a plain loop — no device needed.  The
+ * planes of rpt_debug_denoise_host and moments_xyzw: width*height records of 4 floats (what rpt_read_moments returns); params NULL = defaults; out_rgb:
+ * width*height*3 floats; out_variance (nullable): width*height floats, unknown = +inf.  RPT_EINVAL for the parameter values rpt_denoise_variance refuses. */
+int rpt_debug_denoise_variance_host(uint32_t width, uint32_t height, const float *mean_rgb, const float *albedo, const float *normal, const float *position,
+                                    const float *depth, const uint32_t *kind, const float *moments_xyzw, const rpt_denoise_var_params *params, uint32_t tonemap_op,
+                                    float *out_rgb, float *out_variance);
+
 /* noise_rel and the counts of rpt_noise_count on the HOST: the same header (csrc/k_moments.h) in a plain loop over n moments records (4 floats each: sum Y,
  * sum Y^2, n, max Y) — no device needed.  rel_out (n floats) and counts_out are nullable; counts_out->pixels = n.  RPT_EINVAL for a negative or NaN threshold. */
 int rpt_debug_noise_host(const float *moments_xyzw, size_t n, float threshold, float *rel_out, rpt_noise_counts *counts_out);

@@ -12,12 +12,16 @@
  *   any other triangle           1      get_pbr_bsdf's (bsdf.rs:355-361) the same                                t       ro + rd * t
  * packed for the filter as two float4 per pixel: (normal | depth) and (position | kind bits); the albedo is its own image (read by the pre-pass
  * and by the last pass only).  A tap of a pass reads 48 bytes: colour + the two guide records.
+ *
+ * A second filter beside the first (rpt_denoise_variance): dn_filter_pixel_var, the same pass with a luminance term that the per-pixel variance of the mean
+ * (k_moments.h) drives; the variance rides in the colour record's fourth lane.  The first filter's functions and kernels are not touched by it.
  */
 #ifndef RPT_K_DENOISE_H
 #define RPT_K_DENOISE_H
 
 #include "k_shade.h"             /* load_material, sample_by_lod, the tri_shade records: the guides shade a hit as the shade stage does (k_shade itself is not instantiated) */
 #include "k_tonemap.h"
+#include "k_moments.h"           /* mo_luminance, mo_variance_of_mean: the variance-guided filter (dn_filter_pixel_var) */
 
 #define RPT_DN_KIND_MISS 0u
 #define RPT_DN_KIND_SURFACE 1u
@@ -114,6 +118,120 @@ RPT_HD F3 dn_filter_pixel(const DnPass &ps, const float4 *colour, const float4 *
 }
 /* after the last pass: back to radiance, then the display operator */
 RPT_HD F3 dn_finish_pixel(F3 e, F3 albedo, bool demodulated, uint32_t tonemap_op) { return tonemap(tonemap_op, demodulated ? dn_remodulate(e, albedo) : e); }
+
+/* ---- the variance-guided filter (rpt_denoise_variance): dn_filter_pixel with one more edge-stopping term, driven by the per-pixel variance of the mean
+ * luminance that the moments record gives (k_moments.h mo_variance_of_mean; Schied et al. 2017).  The variance travels in the .w lane of the colour image
+ * (a tap still reads 48 bytes) and is filtered along with the colour.  Its unit is that of the filtered luminance squared: radiance^2, or — with
+ * demodulation — radiance^2 / Ya^2, Ya = the luminance of max(albedo, 0.01).  +inf stands for "unknown" (mo_variance_known). ------------------------------ */
+struct DnVarOut { F3 e; float v; };
+
+/* the pre-pass's variance of a pixel: the record's, divided by Ya^2 where the mean was demodulated (an unknown one stays unknown) */
+RPT_HD float dn_prepare_variance(const float4 &m, bool demodulated, F3 albedo) {
+    float v = mo_variance_of_mean(m);
+    if (demodulated && mo_variance_known(v)) {
+        const F3 a = dn_albedo_floor(albedo);
+        const float Ya = mo_luminance(a.x, a.y, a.z);
+        v = v / (Ya * Ya);
+    }
+    return v;
+}
+
+/* vbar_p: the 3 x 3 Gaussian {1/4, 1/2, 1/4}^2 of the pass's INPUT variance around p, taps at distance 1 whatever the pass's step, dy outer, dx inner, both
+ * ascending, over the taps that are inside the image, of p's kind and of known variance (the centre is one of them when its variance is known), divided by
+ * the sum of the kernel weights used (the products and their sums are exact).  No tap: unknown. */
+RPT_HD float dn_prefilter_variance(const DnPass &ps, const float4 *colour, const float4 *g1, uint32_t x, uint32_t y, uint32_t kind_p) {
+    float acc = 0.0f, ksum = 0.0f;
+    for (int dy = -1; dy <= 1; ++dy) {
+        const int qy = (int)y + dy;
+        if (qy < 0 || qy >= (int)ps.height) continue;
+        const float hy = dy == 0 ? 0.5f : 0.25f;
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int qx = (int)x + dx;
+            if (qx < 0 || qx >= (int)ps.width) continue;
+            const size_t aq = (size_t)qy * ps.width + (size_t)qx;
+            if (rptm::f2u(g1[aq].w) != kind_p) continue;
+            const float v_q = colour[aq].w;
+            if (!mo_variance_known(v_q)) continue;
+            const float k = (dx == 0 ? 0.5f : 0.25f) * hy;
+            acc = acc + k * v_q;
+            ksum = ksum + k;
+        }
+    }
+    return ksum > 0.0f ? acc / ksum : rptm::u2f(0x7f800000u);
+}
+
+/* One pixel of one pass of the variance-guided filter: dn_filter_pixel, every rule of it, and
+ *   d_l   = |Y(e_p) - Y(e_q)| / (sigma_variance sqrt(vbar_p) + 1e-6)        Y = mo_luminance; added to d after d_c: w = (k w_n) expr(-(d_x + d_c + d_l))
+ * when sigma_variance != 0 and vbar_p is known; otherwise NO term is added and the colour is dn_filter_pixel's, bit for bit.
+ * The variance that goes out with the colour is sum(w^2 v_q) / sum(w)^2 over the taps that joined and whose variance is known, the centre (w = 9/64)
+ * included; it is known iff the centre's was.  A pixel that passes through unchanged keeps its variance. */
+RPT_HD DnVarOut dn_filter_pixel_var(const DnPass &ps, float sigma_variance, const float4 *colour, const float4 *g0, const float4 *g1, uint32_t x, uint32_t y) {
+    const size_t at = (size_t)y * ps.width + x;
+    const float4 cp = colour[at];
+    const F3 e_p = f3(cp.x, cp.y, cp.z);
+    const float v_p = cp.w;
+    if (!dn_finite3(e_p)) return DnVarOut{e_p, v_p};
+    const float4 a0 = g0[at], a1 = g1[at];
+    const F3 n_p = f3(a0.x, a0.y, a0.z), x_p = f3(a1.x, a1.y, a1.z);
+    const uint32_t kind_p = rptm::f2u(a1.w);
+    const float plane = ps.plane_scale * a0.w;
+    const float ep2 = dot3(e_p, e_p);
+    bool lum_term = false;
+    float lum_width = 0.0f, Y_p = 0.0f;
+    if (sigma_variance != 0.0f) {
+        const float vbar = dn_prefilter_variance(ps, colour, g1, x, y, kind_p);
+        if (mo_variance_known(vbar)) {
+            lum_term = true;
+            lum_width = sigma_variance * rptm::sqrtr(vbar) + 1e-6f;
+            Y_p = mo_luminance(e_p.x, e_p.y, e_p.z);
+        }
+    }
+    F3 sum = f3s(0.0f);
+    float wsum = 0.0f, vsum = 0.0f;
+    bool joined = false;
+    for (int dy = -2; dy <= 2; ++dy) {
+        const int qy = (int)y + dy * (int)ps.step;
+        if (qy < 0 || qy >= (int)ps.height) continue;
+        const float hy = dy == 0 ? 0.375f : ((dy == 1 || dy == -1) ? 0.25f : 0.0625f);
+        for (int dx = -2; dx <= 2; ++dx) {
+            const int qx = (int)x + dx * (int)ps.step;
+            if (qx < 0 || qx >= (int)ps.width) continue;
+            const float hx = dx == 0 ? 0.375f : ((dx == 1 || dx == -1) ? 0.25f : 0.0625f);
+            const float k = hx * hy;
+            F3 e_q = e_p;
+            float w = k, v_q = v_p;
+            if (dx != 0 || dy != 0) {
+                const size_t aq = (size_t)qy * ps.width + (size_t)qx;
+                const float4 b1 = g1[aq];
+                if (rptm::f2u(b1.w) != kind_p) continue;
+                const float4 cq = colour[aq];
+                e_q = f3(cq.x, cq.y, cq.z);
+                v_q = cq.w;
+                if (!dn_finite3(e_q)) continue;
+                float w_n = 1.0f, d = 0.0f;
+                if (kind_p != RPT_DN_KIND_MISS) {
+                    const float4 b0 = g0[aq];
+                    w_n = rptm::fmaxr(0.0f, dot3(n_p, f3(b0.x, b0.y, b0.z)));
+                    for (uint32_t r = 0; r < ps.normal_power_log2; ++r) w_n = w_n * w_n;
+                    d = rptm::absr(dot3(n_p, f3(b1.x, b1.y, b1.z) - x_p)) / plane;
+                }
+                if (ps.sigma2 != 0.0f) {
+                    const F3 diff = e_p - e_q;
+                    d = d + dot3(diff, diff) / (ps.sigma2 * ((ep2 + dot3(e_q, e_q)) + 1e-12f));
+                }
+                if (lum_term) d = d + rptm::absr(Y_p - mo_luminance(e_q.x, e_q.y, e_q.z)) / lum_width;
+                w = (k * w_n) * rptm::expr(-d);
+                if (!(w > 0.0f)) continue;
+                joined = true;
+            }
+            sum = sum + w * e_q;
+            wsum = wsum + w;
+            if (mo_variance_known(v_q)) vsum = vsum + (w * w) * v_q;
+        }
+    }
+    if (!joined) return DnVarOut{e_p, v_p};
+    return DnVarOut{f3(sum.x / wsum, sum.y / wsum, sum.z / wsum), mo_variance_known(v_p) ? vsum / (wsum * wsum) : rptm::u2f(0x7f800000u)};
+}
 
 /* ---- guides ------------------------------------------------------------------------------------------------------------------------------------------ */
 /* camera_ray (k_path.h, lib.rs:36-51) through the pixel CENTRE: the jitter replaced by (0.5, 0.5) */
@@ -247,6 +365,32 @@ __global__ __launch_bounds__(RPT_BLOCK) void k_dn_resolve(const float4 *mean, ui
     const F3 c = tonemap(tonemap_op, xyz4(mean[i]));
     const size_t j = 3u * (size_t)i;
     out_rgb[j] = c.x; out_rgb[j + 1u] = c.y; out_rgb[j + 2u] = c.z;
+}
+
+/* ---- the variance-guided filter's kernels (rpt_denoise_variance) ------------------------------------------------------------------------------------- */
+/* one pass, the mapping of k_dn_pass (a wave a 64 x 1 row segment, a workgroup 64 x 4 pixels).  The nine step-1 variance reads of neighbouring lanes
+ * overlap and are left to the cache: at step 1 they are taps of the 5 x 5 loop, at every step they are rows the workgroup reads as whole lines. */
+template <bool LAST>
+__global__ __launch_bounds__(256) void k_dn_pass_var(DnPass ps, float sigma_variance, const float4 *src, const float4 *g0, const float4 *g1, float4 *dst, const float4 *albedo,
+                                                     uint32_t demodulated, uint32_t tonemap_op, float *out_rgb, float *out_variance) {
+    const uint32_t x = blockIdx.x * 64u + (threadIdx.x & 63u), y = blockIdx.y * 4u + (threadIdx.x >> 6);
+    if (x >= ps.width || y >= ps.height) return;
+    const DnVarOut o = dn_filter_pixel_var(ps, sigma_variance, src, g0, g1, x, y);
+    const size_t at = (size_t)y * ps.width + x;
+    if (LAST) {
+        const F3 c = dn_finish_pixel(o.e, xyz4(albedo[at]), demodulated != 0u, tonemap_op);
+        out_rgb[3u * at] = c.x; out_rgb[3u * at + 1u] = c.y; out_rgb[3u * at + 2u] = c.z;
+        out_variance[at] = o.v;
+    } else {
+        dst[at] = make_float4(o.e.x, o.e.y, o.e.z, o.v);
+    }
+}
+
+/* iterations == 0: the prepared variance as a plane (the colour goes through k_dn_resolve) */
+__global__ __launch_bounds__(RPT_BLOCK) void k_dn_variance_plane(const float4 *mean, uint32_t n, float *out_variance) {
+    const uint32_t i = blockIdx.x * RPT_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    out_variance[i] = mean[i].w;
 }
 
 /* rpt_read_guides: the packed records as the planes a caller (OIDN's auxiliary images, the tests) takes; every destination nullable */

@@ -44,6 +44,17 @@ RPT_HD float noise_rel(const float4 &m) {
     return sem / (__builtin_fabsf(mean) + RPT_NOISE_MEAN_FLOOR);
 }
 
+/* The empirical variance of the pixel's MEAN luminance (the square of noise_rel's standard error, in radiance units): max(0, sum(Y^2) - sum(Y)^2 / n) /
+ * (n (n - 1)), the operations of noise_rel's `ss` and `v` lines in their order.  +inf — "unknown" — for a record that is not measured or whose sums are
+ * not finite; a known variance is finite and >= 0 (mo_variance_known).  What rpt_denoise_variance filters by (k_denoise.h). */
+RPT_HD float mo_variance_of_mean(const float4 &m) {
+    const float n = m.z;
+    if (!mo_measured(m) || !rptm::finiter(m.x) || !rptm::finiter(m.y)) return rptm::u2f(0x7f800000u);
+    const float ss = m.y - (m.x * m.x) / n;
+    return (ss > 0.0f ? ss : 0.0f) / (n * (n - 1.0f));
+}
+RPT_HD bool mo_variance_known(float v) { return rptm::finiter(v); }
+
 /* what rpt_noise_count counts of a measured record: NOT (rel <= threshold), so a NaN counts as above */
 RPT_HD bool noise_above(float rel, float threshold) { return !(rel <= threshold); }
 

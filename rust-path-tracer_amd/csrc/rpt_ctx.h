@@ -138,6 +138,8 @@ struct DenoiseState {
     DevBuf<float4> g0, g1, albedo;        /* row-major W x H: (normal | depth), (position | kind bits), (albedo | -) */
     DevBuf<float4> ping, pong;            /* the two images the passes alternate between */
     DevBuf<float> rgb;                    /* W x H x 3: the result, before it leaves the device */
+    DevBuf<float> variance;               /* W x H: the variance plane of rpt_denoise_variance (allocated by its first call) */
+    DevBuf<float4> moments_in;            /* W x H, row-major: a caller's moments image, uploaded per call of rpt_denoise_variance (allocated by the first such call) */
     DevBuf<uint32_t> order;               /* x | y << 16 of every pixel of the image in tile order (rank 0 of 1): a wave of guide rays is an 8 x 8 block */
     uint32_t width = 0, height = 0;       /* what the buffers are sized for */
     bool guides_valid = false;

@@ -1,6 +1,6 @@
 /*
- * rpt_denoise.hip — the denoise step behind the C ABI (include/rpt/rpt.h rpt_denoise, rpt_read_guides, rpt_denoise_params_default) and its host build
- * (rpt_debug.h rpt_debug_denoise_host): the guide buffers of a context — built with the one-ray-per-lane nearest-hit walk the debug hook launches
+ * rpt_denoise.hip — the denoise step behind the C ABI (include/rpt/rpt.h rpt_denoise, rpt_denoise_variance, rpt_read_guides, rpt_denoise_params_default,
+ * rpt_denoise_var_params_default) and its host builds (rpt_debug.h rpt_debug_denoise_host, rpt_debug_denoise_variance_host): the guide buffers of a context — built with the one-ray-per-lane nearest-hit walk the debug hook launches
  * (rpt_launch_trace_debug: LDS or global variant per scene, no new walk instantiated) and a small shading kernel — and the passes of k_denoise.h.
  */
 #include <cstring>
@@ -15,6 +15,9 @@ namespace {
 /* csrc/k_denoise.h; chosen on converged images of the shipped scenes: profiles/r11_denoise_quality.txt */
 constexpr rpt_denoise_params DN_DEFAULTS = {2u, 0u, 1.0f, 2.0f, 1u, {0u, 0u, 0u}};
 
+/* the grid of profiles/r14_denoise_variance_quality.txt (tools/denoise_probe.py --quality) */
+constexpr rpt_denoise_var_params DN_VAR_DEFAULTS = {DN_DEFAULTS, 0.0f, {0u, 0u, 0u}};
+
 int check_params(const rpt_denoise_params &p, uint32_t tonemap_op, std::string &error) {
     if (p.iterations > RPT_DN_MAX_ITERATIONS) { error = "rpt_denoise: iterations must be 0..6"; return RPT_EINVAL; }
     if (p.normal_power_log2 > RPT_DN_MAX_NORMAL_POWER_LOG2) { error = "rpt_denoise: normal_power_log2 must be 0..10"; return RPT_EINVAL; }
@@ -23,6 +26,12 @@ int check_params(const rpt_denoise_params &p, uint32_t tonemap_op, std::string &
         return RPT_EINVAL;
     }
     if (tonemap_op > 6u) { error = "tonemap operator must be 0..6"; return RPT_EINVAL; }
+    return RPT_OK;
+}
+
+int check_var_params(const rpt_denoise_var_params &p, uint32_t tonemap_op, std::string &error) {
+    RPT_TRY(check_params(p.base, tonemap_op, error));
+    if (!(p.sigma_variance >= 0.0f)) { error = "rpt_denoise_variance: sigma_variance must be >= 0 (+inf allowed)"; return RPT_EINVAL; }
     return RPT_OK;
 }
 
@@ -90,11 +99,60 @@ void launch_pass(hipStream_t s, const DnPass &ps, bool last, const float4 *src, 
     else k_dn_pass<false><<<grid, 256, 0, s>>>(ps, src, d.g0.p, d.g1.p, dst, d.albedo.p, demodulated, tonemap_op, d.rgb.p);
 }
 
+/* pre-pass: k_dn_prepare / k_dn_prepare_own (OWN: every pixel by its own .w) with the variance of the mean in the .w lane.  `order` != null: element i of
+ * `sums` is pixel order[i]; the moments are in that order too (the context's record, beside its accumulator) unless moments_row_major (a caller's image) */
+template <bool OWN>
+__global__ __launch_bounds__(RPT_BLOCK) void k_dn_prepare_var(const float4 *sums, const float4 *moments, const uint32_t *order, uint32_t moments_row_major, uint32_t n, uint32_t width,
+                                                              float sample_count, const float4 *albedo /* null: no demodulation */, float4 *out) {
+    const uint32_t i = blockIdx.x * RPT_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    size_t at = i;
+    if (order) at = rpt_pixel_index(order[i], width);
+    const float4 a = sums[i];
+    F3 c = OWN ? mean_own(a) : f3(a.x / sample_count, a.y / sample_count, a.z / sample_count);
+    F3 al = f3s(1.0f);
+    if (albedo) { al = xyz4(albedo[at]); c = dn_demodulate(c, al); }
+    const float v = dn_prepare_variance(moments[moments_row_major ? at : (size_t)i], albedo != nullptr, al);
+    out[at] = make_float4(c.x, c.y, c.z, v);
+}
+
+void launch_pass_var(hipStream_t s, const DnPass &ps, float sigma_variance, bool last, const float4 *src, const DenoiseState &d, float4 *dst, uint32_t demodulated, uint32_t tonemap_op) {
+    const dim3 grid((ps.width + 63u) / 64u, (ps.height + 3u) / 4u);
+    if (last) k_dn_pass_var<true><<<grid, 256, 0, s>>>(ps, sigma_variance, src, d.g0.p, d.g1.p, dst, d.albedo.p, demodulated, tonemap_op, d.rgb.p, d.variance.p);
+    else k_dn_pass_var<false><<<grid, 256, 0, s>>>(ps, sigma_variance, src, d.g0.p, d.g1.p, dst, d.albedo.p, demodulated, tonemap_op, d.rgb.p, d.variance.p);
+}
+
+/* the image a call filters: the context's accumulator (tile-major, `order` = its pixels) or the last gather's (row-major, on the gather's stream) */
+struct DnSource {
+    const float4 *sums = nullptr;
+    const uint32_t *order = nullptr;
+    uint32_t samples = 0;
+    bool own_counts = false;             /* counts are non-uniform: every pixel by its own accum.w */
+    hipStream_t stream = nullptr;
+};
+int open_source(rpt_ctx *c, uint32_t source, DnSource *out) {
+    if (source != RPT_DENOISE_ACCUM && source != RPT_DENOISE_GATHERED) { c->error = "rpt_denoise: source must be RPT_DENOISE_ACCUM or RPT_DENOISE_GATHERED"; return RPT_EINVAL; }
+    if (!c->has_scene || !c->has_config || !c->has_state) { c->error = "rpt_denoise: needs a scene and a configuration"; return RPT_EINVAL; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    DnSource src;
+    src.stream = c->stream;
+    if (source == RPT_DENOISE_ACCUM) {
+        if (c->world != 1u) { c->error = "rpt_denoise: RPT_DENOISE_ACCUM needs a partition of one rank (this context is one of " + std::to_string(c->world) + "): gather, then RPT_DENOISE_GATHERED on rank 0"; return RPT_EINVAL; }
+        RPT_TRY(rpt_wait(c));
+        src.sums = c->accum.p; src.order = c->pixel_xy.p; src.samples = c->samples; src.own_counts = c->counts_nonuniform;
+    } else {
+        RPT_TRY(rpt_comm_gathered_image(c, &src.sums, &src.samples, &src.own_counts, &src.stream));
+    }
+    if (src.samples == 0u && !src.own_counts) { c->error = "rpt_denoise: the image has zero samples"; return RPT_EINVAL; }
+    *out = src;
+    return RPT_OK;
+}
+
 }  // namespace
 
 void rpt_denoise_release(rpt_ctx *c, bool events_too) {
     DenoiseState &d = c->dn;
-    d.g0.release(); d.g1.release(); d.albedo.release(); d.ping.release(); d.pong.release(); d.rgb.release(); d.order.release();
+    d.g0.release(); d.g1.release(); d.albedo.release(); d.ping.release(); d.pong.release(); d.rgb.release(); d.order.release(); d.variance.release(); d.moments_in.release();
     d.width = d.height = 0;
     d.guides_valid = false;
     if (events_too)
@@ -112,22 +170,13 @@ int rpt_denoise(rpt_ctx *c, uint32_t source, const rpt_denoise_params *params, u
     if (!c || !out_rgb) return RPT_EINVAL;
     const rpt_denoise_params p = params ? *params : DN_DEFAULTS;
     RPT_TRY(check_params(p, tonemap_op, c->error));
-    if (source != RPT_DENOISE_ACCUM && source != RPT_DENOISE_GATHERED) { c->error = "rpt_denoise: source must be RPT_DENOISE_ACCUM or RPT_DENOISE_GATHERED"; return RPT_EINVAL; }
-    if (!c->has_scene || !c->has_config || !c->has_state) { c->error = "rpt_denoise: needs a scene and a configuration"; return RPT_EINVAL; }
-    HIP_TRY(c, hipSetDevice(c->device));
-    const float4 *sums = nullptr;
-    const uint32_t *order = nullptr;
-    uint32_t samples = 0;
-    bool own_counts = false;             /* counts are non-uniform: every pixel by its own accum.w */
-    hipStream_t s = c->stream;
-    if (source == RPT_DENOISE_ACCUM) {
-        if (c->world != 1u) { c->error = "rpt_denoise: RPT_DENOISE_ACCUM needs a partition of one rank (this context is one of " + std::to_string(c->world) + "): gather, then RPT_DENOISE_GATHERED on rank 0"; return RPT_EINVAL; }
-        RPT_TRY(rpt_wait(c));
-        sums = c->accum.p; order = c->pixel_xy.p; samples = c->samples; own_counts = c->counts_nonuniform;
-    } else {
-        RPT_TRY(rpt_comm_gathered_image(c, &sums, &samples, &own_counts, &s));
-    }
-    if (samples == 0u && !own_counts) { c->error = "rpt_denoise: the image has zero samples"; return RPT_EINVAL; }
+    DnSource in;
+    RPT_TRY(open_source(c, source, &in));
+    const float4 *sums = in.sums;
+    const uint32_t *order = in.order;
+    const uint32_t samples = in.samples;
+    const bool own_counts = in.own_counts;
+    hipStream_t s = in.stream;
     bool rebuilt = false;
     RPT_TRY(ensure_guides(c, &rebuilt));
     DenoiseState &d = c->dn;
@@ -146,6 +195,69 @@ int rpt_denoise(rpt_ctx *c, uint32_t source, const rpt_denoise_params *params, u
     HIP_TRY(c, hipEventRecord(d.ev[3], s));
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(out_rgb, d.rgb.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (report) {
+        float ms = 0.0f;
+        *report = rpt_denoise_report{};
+        if (hipEventElapsedTime(&ms, d.ev[2], d.ev[3]) == hipSuccess) report->device_ms = ms;
+        if (rebuilt && hipEventElapsedTime(&ms, d.ev[0], d.ev[1]) == hipSuccess) report->guides_ms = ms;
+        report->guides_rebuilt = rebuilt ? 1u : 0u;
+    }
+    return RPT_OK;
+}
+
+void rpt_denoise_var_params_default(rpt_denoise_var_params *out) {
+    if (out) *out = DN_VAR_DEFAULTS;
+}
+
+int rpt_denoise_variance(rpt_ctx *c, uint32_t source, const float *moments_xyzw, const rpt_denoise_var_params *params, uint32_t tonemap_op, float *out_rgb, float *out_variance,
+                         rpt_denoise_report *report) {
+    if (!c) return RPT_EINVAL;
+    if (!out_rgb) { c->error = "rpt_denoise_variance: out_rgb is null"; return RPT_EINVAL; }
+    const rpt_denoise_var_params vp = params ? *params : DN_VAR_DEFAULTS;
+    const rpt_denoise_params &p = vp.base;
+    RPT_TRY(check_var_params(vp, tonemap_op, c->error));
+    if (!moments_xyzw) {                 /* the context's own record: it lies beside the accumulator, and only there */
+        if (source == RPT_DENOISE_GATHERED) { c->error = "rpt_denoise_variance: moments are not part of the gather: RPT_DENOISE_GATHERED needs a moments image (rpt_read_moments / rpt_multi_read_moments)"; return RPT_EINVAL; }
+        if (!c->moments_on) { c->error = "rpt_denoise_variance: moments are off (rpt_set_moments(ctx, 1) first, or pass a moments image)"; return RPT_EINVAL; }
+    }
+    DnSource in;
+    RPT_TRY(open_source(c, source, &in));
+    hipStream_t s = in.stream;
+    bool rebuilt = false;
+    RPT_TRY(ensure_guides(c, &rebuilt));
+    DenoiseState &d = c->dn;
+    const uint32_t W = d.width, H = d.height, n = W * H;
+    if (d.variance.n != n) HIP_TRY(c, d.variance.alloc(n));
+    const float4 *moments = c->moments.p;
+    if (moments_xyzw) {                  /* uploaded for this call (the previous call's kernels have drained: every call is synchronous on return) */
+        if (d.moments_in.n != n) HIP_TRY(c, d.moments_in.alloc(n));
+        HIP_TRY(c, hipMemcpy(d.moments_in.p, moments_xyzw, (size_t)n * sizeof(float4), hipMemcpyHostToDevice));
+        moments = d.moments_in.p;
+    } else if (c->moments.n != n) {      /* (one rank owns every pixel: checked by open_source) */
+        c->error = "rpt_denoise_variance: internal error (the moments record does not cover the image)";
+        return RPT_EHIP;
+    }
+    const uint32_t row_major = moments_xyzw ? 1u : 0u;
+    const bool demodulated = p.iterations != 0u && p.demodulate != 0u;
+    const float4 *albedo = demodulated ? d.albedo.p : nullptr;
+    HIP_TRY(c, hipEventRecord(d.ev[2], s));
+    if (in.own_counts) k_dn_prepare_var<true><<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(in.sums, moments, in.order, row_major, n, W, 0.0f, albedo, d.ping.p);
+    else k_dn_prepare_var<false><<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(in.sums, moments, in.order, row_major, n, W, (float)in.samples, albedo, d.ping.p);
+    if (p.iterations == 0u) {
+        k_dn_resolve<<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(d.ping.p, n, tonemap_op, d.rgb.p);
+        k_dn_variance_plane<<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(d.ping.p, n, d.variance.p);
+    }
+    float4 *src = d.ping.p, *dst = d.pong.p;
+    for (uint32_t i = 0; i < p.iterations; ++i) {
+        const DnPass ps = dn_pass(W, H, i, p.normal_power_log2, p.sigma_color, p.sigma_plane);
+        launch_pass_var(s, ps, vp.sigma_variance, i + 1u == p.iterations, src, d, dst, demodulated ? 1u : 0u, tonemap_op);
+        std::swap(src, dst);
+    }
+    HIP_TRY(c, hipEventRecord(d.ev[3], s));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(out_rgb, d.rgb.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (out_variance) HIP_TRY(c, hipMemcpyAsync(out_variance, d.variance.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     if (report) {
         float ms = 0.0f;
@@ -216,6 +328,46 @@ int rpt_debug_denoise_host(uint32_t width, uint32_t height, const float *mean_rg
         const float4 e = (*src)[i];
         const F3 c = dn_finish_pixel(f3(e.x, e.y, e.z), f3(a[i].x, a[i].y, a[i].z), demodulated, tonemap_op);
         out_rgb[3 * i] = c.x; out_rgb[3 * i + 1] = c.y; out_rgb[3 * i + 2] = c.z;
+    }
+    return RPT_OK;
+}
+
+/* the variance-guided filter on the host: the loop k_dn_prepare_var / k_dn_pass_var are, over the same RPT_HD functions */
+int rpt_debug_denoise_variance_host(uint32_t width, uint32_t height, const float *mean_rgb, const float *albedo, const float *normal, const float *position, const float *depth,
+                                    const uint32_t *kind, const float *moments_xyzw, const rpt_denoise_var_params *params, uint32_t tonemap_op, float *out_rgb, float *out_variance) {
+    if (!mean_rgb || !albedo || !normal || !position || !depth || !kind || !moments_xyzw || !out_rgb || width == 0u || height == 0u || width > 65535u || height > 65535u) return RPT_EINVAL;
+    const rpt_denoise_var_params vp = params ? *params : DN_VAR_DEFAULTS;
+    const rpt_denoise_params &p = vp.base;
+    std::string error;
+    if (check_var_params(vp, tonemap_op, error)) { rpt_create_error() = error; return RPT_EINVAL; }
+    const size_t n = (size_t)width * height;
+    const bool demodulated = p.iterations != 0u && p.demodulate != 0u;
+    std::vector<float4> g0(n), g1(n), a(n), ping(n), pong(n);
+    for (size_t i = 0; i < n; ++i) {
+        g0[i] = make_float4(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], depth[i]);
+        g1[i] = make_float4(position[3 * i], position[3 * i + 1], position[3 * i + 2], rptm::u2f(kind[i]));
+        a[i] = make_float4(albedo[3 * i], albedo[3 * i + 1], albedo[3 * i + 2], 0.0f);
+        const F3 al = f3(a[i].x, a[i].y, a[i].z);
+        F3 c = f3(mean_rgb[3 * i], mean_rgb[3 * i + 1], mean_rgb[3 * i + 2]);
+        if (demodulated) c = dn_demodulate(c, al);
+        const float4 m = make_float4(moments_xyzw[4 * i], moments_xyzw[4 * i + 1], moments_xyzw[4 * i + 2], moments_xyzw[4 * i + 3]);
+        ping[i] = make_float4(c.x, c.y, c.z, dn_prepare_variance(m, demodulated, al));
+    }
+    std::vector<float4> *src = &ping, *dst = &pong;
+    for (uint32_t i = 0; i < p.iterations; ++i) {
+        const DnPass ps = dn_pass(width, height, i, p.normal_power_log2, p.sigma_color, p.sigma_plane);
+        for (uint32_t y = 0; y < height; ++y)
+            for (uint32_t x = 0; x < width; ++x) {
+                const DnVarOut o = dn_filter_pixel_var(ps, vp.sigma_variance, src->data(), g0.data(), g1.data(), x, y);
+                (*dst)[(size_t)y * width + x] = make_float4(o.e.x, o.e.y, o.e.z, o.v);
+            }
+        std::swap(src, dst);
+    }
+    for (size_t i = 0; i < n; ++i) {
+        const float4 e = (*src)[i];
+        const F3 c = dn_finish_pixel(f3(e.x, e.y, e.z), f3(a[i].x, a[i].y, a[i].z), demodulated, tonemap_op);
+        out_rgb[3 * i] = c.x; out_rgb[3 * i + 1] = c.y; out_rgb[3 * i + 2] = c.z;
+        if (out_variance) out_variance[i] = e.w;
     }
     return RPT_OK;
 }

@@ -28,6 +28,11 @@ class DenoiseParams(C.Structure):
                 ("demodulate", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
+class DenoiseVarParams(C.Structure):
+    """rpt_denoise_var_params"""
+    _fields_ = [("base", DenoiseParams), ("sigma_variance", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
 class DenoiseReport(C.Structure):
     """rpt_denoise_report"""
     _fields_ = [("device_ms", C.c_double), ("guides_ms", C.c_double), ("guides_rebuilt", C.c_uint32), ("reserved", C.c_uint32)]
@@ -70,6 +75,20 @@ def denoise_params(**changes):
         if k not in ("iterations", "normal_power_log2", "sigma_color", "sigma_plane", "demodulate"):
             raise TypeError(f"rpt_denoise_params has no field {k}")
         setattr(p, k, v)
+    return p
+
+
+def denoise_var_params(**changes):
+    """rpt_denoise_var_params_default, with the named fields replaced; the fields of rpt_denoise_params go into .base: denoise_var_params(sigma_variance=4, iterations=5)"""
+    p = DenoiseVarParams()
+    lib().rpt_denoise_var_params_default(C.byref(p))
+    for k, v in changes.items():
+        if k == "sigma_variance":
+            p.sigma_variance = v
+        elif k in ("iterations", "normal_power_log2", "sigma_color", "sigma_plane", "demodulate"):
+            setattr(p.base, k, v)
+        else:
+            raise TypeError(f"rpt_denoise_var_params has no field {k}")
     return p
 
 
@@ -149,6 +168,9 @@ PROTOTYPES = {
     "rpt_multi_read_moments": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rpt_multi_noise_count": (C.c_int, [C.c_void_p, C.c_float, C.POINTER(NoiseCounts)]),
     "rpt_multi_render_to_noise": (C.c_int, [C.c_void_p, C.POINTER(NoiseTarget), C.POINTER(NoiseResult)]),
+    "rpt_denoise_var_params_default": (None, [C.POINTER(DenoiseVarParams)]),
+    "rpt_denoise_variance": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(DenoiseVarParams), C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(DenoiseReport)]),
+    "rpt_multi_denoise_variance": (C.c_int, [C.c_void_p, C.POINTER(DenoiseVarParams), C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(DenoiseReport)]),
     "rpt_render_pixels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "rpt_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(NoiseTarget), C.POINTER(AdaptiveResult)]),
     "rpt_counts_uniform": (C.c_int, [C.c_void_p, _OUT_U32]),
@@ -167,6 +189,7 @@ PROTOTYPES = {
     "rpt_debug_sample_image": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]),
     "rpt_debug_comm_selftest": (C.c_int, [C.c_void_p, C.c_uint32, _OUT_U64]),
     "rpt_debug_denoise_host": (C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 6 + [C.POINTER(DenoiseParams), C.c_uint32, C.c_void_p]),
+    "rpt_debug_denoise_variance_host": (C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 7 + [C.POINTER(DenoiseVarParams), C.c_uint32, C.c_void_p, C.c_void_p]),
     "rpt_debug_noise_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.POINTER(NoiseCounts)]),
     "rpt_debug_adaptive_select_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, _OUT_SIZE]),
     "rpt_debug_short_batch": (C.c_int, [C.c_void_p, C.c_int]),
@@ -279,6 +302,12 @@ class _Handle:
         out, rep = self._image(3), DenoiseReport()
         self._call("denoise", *source, None if params is None else C.byref(params), tonemap_op, ptr(out), C.byref(rep))
         return (out, _report_dict(rep)) if with_report else out
+
+    def _denoise_variance(self, source, params, tonemap_op, with_report):
+        """source: what rpt_denoise_variance takes between the handle and params, as a tuple (rpt_multi_denoise_variance: nothing)"""
+        out, var, rep = self._image(3), self._image(), DenoiseReport()
+        self._call("denoise_variance", *source, None if params is None else C.byref(params), tonemap_op, ptr(out), ptr(var), C.byref(rep))
+        return (out, var, _report_dict(rep)) if with_report else (out, var)
 
     def set_shadow_mode(self, mode):
         """rpt_set_shadow_mode (rpt_multi_: on every rank): SHADOW_EXACT (default: the reference's any-hit walk, bit for bit) or SHADOW_SEGMENT (boxes that begin
@@ -400,6 +429,15 @@ class Renderer(_Handle):
         """rpt_denoise: the mean image filtered by the guided a-trous filter, then tonemapped, as (H, W, 3) float32 (params None: the defaults;
         with_report: also {"device_ms", "guides_ms", "guides_rebuilt"})."""
         return self._denoise((source,), params, tonemap_op, with_report)
+
+    def denoise_variance(self, source=DENOISE_ACCUM, moments=None, params=None, tonemap_op=0, with_report=False):
+        """rpt_denoise_variance: denoise() with the luminance term that the per-pixel variance of the mean drives (params: denoise_var_params(), None: the
+        defaults).  moments None: the renderer's own record (set_moments first; DENOISE_ACCUM only); else an (H, W, 4) image as read_moments() returns.
+        Returns (rgb (H, W, 3), variance (H, W): the filtered variance of the mean luminance, inf = unknown)[, report]."""
+        if moments is not None:
+            moments = np.ascontiguousarray(moments, np.float32)
+            assert moments.shape == (self.config.height, self.config.width, 4)
+        return self._denoise_variance((source, ptr(moments)), params, tonemap_op, with_report)
 
     def guides(self):
         """rpt_read_guides: the first-hit guide buffers of the current scene and camera:
@@ -641,6 +679,10 @@ class MultiRenderer(_Handle):
         """rpt_multi_denoise: waits, gathers if need be, and denoises the whole image on rank 0 (see Renderer.denoise)"""
         return self._denoise((), params, tonemap_op, with_report)
 
+    def denoise_variance(self, params=None, tonemap_op=0, with_report=False):
+        """rpt_multi_denoise_variance: the ranks' moments merged on the host, the gather of denoise(), the filter on rank 0 (see Renderer.denoise_variance)"""
+        return self._denoise_variance((), params, tonemap_op, with_report)
+
     def stats(self):
         """rpt_multi_get_stats: the counters summed over the GPUs (no times: rank_view(k).stats() has each GPU's)"""
         s = self._get_stats()
@@ -714,6 +756,22 @@ def denoise_host(mean_rgb, albedo, normal, position, depth, kind, params=None, t
     if rc != 0:
         raise RptError(rc, lib().rpt_last_error(None).decode())
     return out
+
+
+def denoise_variance_host(mean_rgb, albedo, normal, position, depth, kind, moments, params=None, tonemap_op=0):
+    """rpt_debug_denoise_variance_host: the filter of Renderer.denoise_variance run on the host from the same headers (no GPU needed).  The planes of
+    denoise_host and moments (H, W, 4) as read_moments() returns them: (rgb (H, W, 3), variance (H, W))."""
+    mean_rgb = np.ascontiguousarray(mean_rgb, np.float32)
+    h, w = mean_rgb.shape[:2]
+    planes = [np.ascontiguousarray(a, np.float32) for a in (albedo, normal, position, depth)]
+    kind, moments = np.ascontiguousarray(kind, np.uint32), np.ascontiguousarray(moments, np.float32)
+    assert mean_rgb.shape == (h, w, 3) and all(a.shape == (h, w, 3) for a in planes[:3]) and planes[3].shape == (h, w) and kind.shape == (h, w) and moments.shape == (h, w, 4)
+    out, var = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32)
+    rc = lib().rpt_debug_denoise_variance_host(w, h, ptr(mean_rgb), ptr(planes[0]), ptr(planes[1]), ptr(planes[2]), ptr(planes[3]), ptr(kind), ptr(moments),
+                                               None if params is None else C.byref(params), tonemap_op, ptr(out), ptr(var))
+    if rc != 0:
+        raise RptError(rc, lib().rpt_last_error(None).decode())
+    return out, var
 
 
 def noise_host(moments, threshold=0.0):

@@ -4,11 +4,19 @@
   python tools/denoise_probe.py --quality [out]     no GPU: the parameter grid against converged CPU-oracle images of DarkCornell (nee 0), VeachMIS (nee 1)
                                                     and PBRTest (nee 0) at 128 x 128 (8 spp noisy, 1024 spp converged); writes the table and the grid point with
                                                     the lowest summed error ratio — the defaults of rpt_denoise_params_default — to profiles/r11_denoise_quality.txt
+  python tools/denoise_probe.py --quality-variance [out]   no GPU: the same oracle images and the moments record of the 8-spp image's samples; rpt_denoise_variance's grid
+                                                    sigma_variance x iterations x sigma_color (the other parameters at rpt_denoise's defaults; sigma_variance = 0, the
+                                                    plain filter, with every base setting) to profiles/r14_denoise_variance_quality.txt; its lowest summed ratio is
+                                                    what rpt_denoise_var_params_default ships
   python tools/denoise_probe.py --gpu [out]         one MI355X: per workload (DarkCornell 1024^2, VeachMIS 1080p MIS, PBRTest 2048^2 textured) the 32-spp batch
                                                     time, guides_ms (median of 9 rebuilds), device_ms with cached guides (median of 25 calls after warm-up, device
                                                     events), the pass at step 1 and the pass at step 16 (5 passes - 4 passes), and rel-L2 of the noisy and the
                                                     denoised 32-spp image against a 4096-spp GPU render; writes profiles/r11_denoise.txt, above the record of the
                                                     wave-mapping comparison the file keeps.  (--workload NAME: one child run of it.)
+  python tools/denoise_probe.py --gpu-variance [out]   one MI355X: per workload the 32-spp batch time (moments off, and on), device_ms of rpt_denoise and of
+                                                    rpt_denoise_variance (own record on the device; the term off = the shipped default, and on at sigma_variance 4)
+                                                    side by side, same base parameters, guides cached, device events, median of 25 calls; writes
+                                                    profiles/r14_denoise_variance.txt, above the notes the file keeps at its foot
 """
 import hashlib
 import importlib
@@ -77,6 +85,61 @@ def quality(out_path):
     print("\n".join(lines[:8]))
 
 
+VAR_GRID = {"sigma_variance": (0.0, 0.5, 1.0, 2.0, 4.0, 8.0, 16.0, 32.0), "iterations": (1, 2, 3, 4, 5, 6), "sigma_color": (0.0, 0.5, 1.0, 2.0, 4.0)}
+
+
+def quality_variance(out_path):
+    from oracle_ffi import Oracle
+    import denoise_var_ref
+    from denoise_ref import QUALITY
+    rpt = importlib.import_module("rust-path-tracer_amd")
+    hip = importlib.import_module("rust-path-tracer_amd.hip")
+    orc = Oracle("rpt_math")
+    worlds = {}
+    world = lambda name: worlds.setdefault(name, rpt.World.from_path(rpt.fixture(name + ".glb")))
+    sets = []
+    for scene, nee in QUALITY:
+        t0 = time.time()
+        noisy, conv, g, moments, _ = denoise_var_ref.quality_inputs(rpt, world, orc, scene, nee)
+        sets.append((scene, nee, noisy, conv, g, rel_l2(noisy, conv), moments))
+        print(f"{scene}: oracle images in {time.time() - t0:.0f} s, rel-L2 of the 8-spp mean {sets[-1][5]:.4f}", flush=True)
+    run = lambda p, s: hip.denoise_variance_host(s[2], s[4]["albedo"], s[4]["normal"], s[4]["position"], s[4]["depth"], s[4]["kind"], s[6], p, 0)[0]
+    rows = []
+    keys = list(VAR_GRID)
+    for values in itertools.product(*(VAR_GRID[k] for k in keys)):
+        p = hip.denoise_var_params(**dict(zip(keys, values)))
+        ratios = [rel_l2(run(p, s), s[3]) / s[5] for s in sets]
+        rows.append((sum(ratios), values, ratios))
+    rows.sort(key=lambda r: r[0])
+    show = lambda r: ", ".join(f"{s[0]} {x:.3f}" for s, x in zip(sets, r[2])) + f"  (sum {r[0]:.3f})"
+    d, b = hip.denoise_var_params(), hip.denoise_params()
+    shipped = (d.sigma_variance, d.base.iterations, d.base.sigma_color)
+    plain = (0.0, b.iterations, b.sigma_color)
+    find = lambda point: [r for r in rows if tuple(float(v) for v in r[1]) == tuple(float(v) for v in point)]
+    measured = [int((s[6][..., 2] >= 2).sum()) for s in sets]
+    zero = [int((denoise_var_ref.variance_of_mean(s[6]) == 0).sum()) for s in sets]
+    lines = ["Variance-guided denoise (rpt_denoise_variance) against converged CPU-oracle images (tools/denoise_probe.py --quality-variance): the inputs of",
+             "r11_denoise_quality.txt (128 x 128, the oracle's 8-spp mean, rel-L2 against its 1024-spp mean; ratio = denoised / noisy) and the moments record of the 8-spp",
+             "image's samples (tests/denoise_var_ref.py quality_inputs), filtered by rpt_debug_denoise_variance_host over the numpy guides.  normal_power_log2 "
+             f"{b.normal_power_log2}, sigma_plane {b.sigma_plane:g}, demodulate {b.demodulate}: rpt_denoise's defaults.", "",
+             "rel-L2 of the 8-spp mean: " + ", ".join(f"{s[0]} (nee {s[1]}) {s[5]:.4f}" for s in sets),
+             "pixels of 16384 with a zero empirical variance after 8 samples: " + ", ".join(f"{s[0]} {z}" for s, z in zip(sets, zero)) +
+             "  (measured: " + ", ".join(str(m) for m in measured) + ")", "",
+             f"lowest summed ratio of the grid: {dict(zip(keys, rows[0][1]))}  ->  " + show(rows[0])]
+    for name, point in (("rpt_denoise_var_params_default", shipped), ("rpt_denoise's defaults (the plain filter: sigma_variance 0)", plain)):
+        hit = find(point)
+        lines.append(f"{name}: {dict(zip(keys, point))}  ->  " + (show(hit[0]) if hit else "not a grid point"))
+    lines.append("best point per sigma_variance:")
+    for sv in VAR_GRID["sigma_variance"]:
+        r = [r for r in rows if r[1][0] == sv][0]
+        lines.append(f"  sigma_variance {sv:g}: iterations {r[1][1]} sigma_color {r[1][2]:g}  ->  " + show(r))
+    lines += ["", "grid (sorted by the summed ratio): " + " ".join(keys) + " | " + " ".join(s[0] for s in sets) + " | sum"]
+    for total, values, ratios in rows:
+        lines.append("  " + " ".join(f"{v:g}" for v in values) + " | " + " ".join(f"{r:.3f}" for r in ratios) + f" | {total:.3f}")
+    open(out_path, "w").write("\n".join(lines) + "\n")
+    print("\n".join(lines[:22]))
+
+
 def gpu_child(workload):
     """one workload, in a process of its own; prints one JSON line"""
     rpt = importlib.import_module("rust-path-tracer_amd")
@@ -138,6 +201,88 @@ def gpu_child(workload):
     print("RESULT " + json.dumps(out), flush=True)
 
 
+def gpu_variance_child(workload):
+    """rpt_denoise and rpt_denoise_variance side by side on one workload, in a process of its own; prints one JSON line"""
+    rpt = importlib.import_module("rust-path-tracer_amd")
+    hip = importlib.import_module("rust-path-tracer_amd.hip")
+    scene, W, H, nee, textured = WORKLOADS[workload]
+    if textured:
+        from scenes import pbrtest_textured_scene
+        made = pbrtest_textured_scene()
+        world = made[0] if isinstance(made, tuple) else made
+    else:
+        world = rpt.World.from_path(rpt.fixture(scene + ".glb"))
+    r = hip.Renderer(0)
+    r.upload_scene(world)
+    r.set_config(rpt.default_config(W, H, nee=nee))
+    seeds = rpt.blue_noise_seeds(W, H)
+    out = {"workload": workload, "width": W, "height": H}
+
+    def batch():
+        times = []
+        for _ in range(6):                               # the first is the warm-up (allocations, clocks)
+            r.reset(seeds)
+            t0 = time.perf_counter()
+            r.render(32)
+            times.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(times[1:]))
+    out["batch_ms"] = batch()
+    r.set_moments(True)
+    out["batch_ms_moments"] = batch()                    # leaves 32 spp and their moments
+    median = lambda call: float(np.median([call()[-1]["device_ms"] for _ in range(28)][3:]))
+    d = hip.denoise_var_params()
+    out["defaults"] = {"sigma_variance": d.sigma_variance, "iterations": d.base.iterations, "sigma_color": d.base.sigma_color}
+    digest = hashlib.sha256()
+    for it in (d.base.iterations, 1, 5):
+        plain, off, on = hip.denoise_params(iterations=it), hip.denoise_var_params(iterations=it, sigma_variance=0.0), hip.denoise_var_params(iterations=it, sigma_variance=4.0)
+        a, b, c = r.denoise(params=plain), r.denoise_variance(params=off)[0], r.denoise_variance(params=on)
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))              # the term off: rpt_denoise's bytes
+        digest.update(c[0].tobytes() + c[1].tobytes())
+        out[f"plain_ms_{it}"] = median(lambda: r.denoise(params=plain, with_report=True))
+        out[f"var_off_ms_{it}"] = median(lambda: r.denoise_variance(params=off, with_report=True))
+        out[f"var_on_ms_{it}"] = median(lambda: r.denoise_variance(params=on, with_report=True))
+    out["iterations"] = d.base.iterations
+    out["output_sha256"] = digest.hexdigest()[:16]
+    r.close()
+    print("RESULT " + json.dumps(out), flush=True)
+
+
+FOOT_RECORD = "notes kept by hand"
+
+
+def gpu_variance(out_path):
+    results = []
+    for workload in WORKLOADS:
+        run = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload-variance", workload], capture_output=True, text=True, timeout=300)
+        line = [l for l in run.stdout.splitlines() if l.startswith("RESULT ")]
+        if run.returncode != 0 or not line:
+            print(run.stdout[-2000:], run.stderr[-2000:])
+            raise SystemExit(f"{workload} failed with status {run.returncode}: nothing more is started on the GPU")
+        results.append(json.loads(line[0][7:]))
+        print(line[0], flush=True)
+    n = results[0]["iterations"]
+    lines = ["rpt_denoise_variance beside rpt_denoise on one MI355X (tools/denoise_probe.py --gpu-variance): 32-spp batches; the same base parameters for both calls",
+             f"(rpt_denoise's defaults but for the number of passes); rpt_denoise_variance reads the context's own moments record on the device.  shipped defaults {json.dumps(results[0]['defaults'])}.",
+             "device_ms: HIP events around pre-pass + passes, guides cached, median of 25 calls after 3 warm-up calls; batch: host clock around rpt_render(32), median of 5 after a warm-up.",
+             "term off: sigma_variance 0 (k_dn_pass_var without the 3 x 3 variance reads; the image is rpt_denoise's, checked bitwise in this run); term on: sigma_variance 4.", ""]
+    worst = 0.0
+    for res in results:
+        lines.append(f"{res['workload']} {res['width']}x{res['height']}: batch {res['batch_ms']:.2f} ms (moments on {res['batch_ms_moments']:.2f} ms); output sha256 {res['output_sha256']}")
+        for it in (n, 1, 5):
+            p, off, on = res[f"plain_ms_{it}"], res[f"var_off_ms_{it}"], res[f"var_on_ms_{it}"]
+            lines.append(f"    {it} pass{'es' if it > 1 else '  '}: rpt_denoise {p:.3f} ms | rpt_denoise_variance term off {off:.3f} ms ({off / p:.2f} x), term on {on:.3f} ms ({on / p:.2f} x) = "
+                         f"{100 * on / res['batch_ms']:.1f} % of the batch")
+        worst = max(worst, res[f"var_on_ms_{n}"] / res["batch_ms"], res[f"var_off_ms_{n}"] / res["batch_ms"])
+    lines += ["", f"condition (rpt_denoise_variance at the shipped number of passes, guides cached, < the 32-spp batch it follows): worst share {100 * worst:.1f} % -> {'HELD' if worst < 1 else 'MISSED'}"]
+    if os.path.exists(out_path):
+        old = open(out_path).read().splitlines()
+        at = [k for k, l in enumerate(old) if l.startswith(FOOT_RECORD)]
+        if at:
+            lines += [""] + old[at[0]:]
+    open(out_path, "w").write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
 MAPPING_RECORD = "wave mapping of a pass"
 
 
@@ -173,10 +318,16 @@ def gpu(out_path):
 
 if __name__ == "__main__":
     a = sys.argv[1:]
-    if "--workload" in a:
+    if "--workload-variance" in a:
+        gpu_variance_child(a[a.index("--workload-variance") + 1])
+    elif a and a[0] == "--gpu-variance":
+        gpu_variance(a[1] if len(a) > 1 else os.path.join(ROOT, "profiles", "r14_denoise_variance.txt"))
+    elif "--workload" in a:
         gpu_child(a[a.index("--workload") + 1])
     elif a and a[0] == "--quality":
         quality(a[1] if len(a) > 1 else os.path.join(ROOT, "profiles", "r11_denoise_quality.txt"))
+    elif a and a[0] == "--quality-variance":
+        quality_variance(a[1] if len(a) > 1 else os.path.join(ROOT, "profiles", "r14_denoise_variance_quality.txt"))
     elif a and a[0] == "--gpu":
         gpu(a[1] if len(a) > 1 else os.path.join(ROOT, "profiles", "r11_denoise.txt"))
     else:
