@@ -76,6 +76,25 @@ pub struct rpt_denoise_report {
 
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
+pub struct rpt_temporal_params {
+    pub filter: rpt_denoise_var_params,   // the passes: as rpt_denoise_variance
+    pub max_history: f32,         // cap on the reprojected sample count; 0 = history never used
+    pub normal_min: f32,          // a history tap joins only if n_p . n_q >= normal_min
+    pub plane_max: f32,           // ... and lies within this many footprints of the centre's tangent plane
+    pub reserved: [u32; 5],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct rpt_temporal_report {
+    pub base: rpt_denoise_report,
+    pub pixels_with_history: u64,
+    pub history_state: u32,       // 0 none yet, 1 used, 2 dropped by this call
+    pub reserved: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
 pub struct rpt_noise_counts {
     pub pixels: u64,     // pixels the context owns
     pub measured: u64,   // of those: two samples or more in the moments record
@@ -150,6 +169,10 @@ extern "C" {
     // rpt_denoise with the variance-guided luminance term: moments null = the context's own record (ACCUM only), else a width*height Vec4 image; out_variance nullable
     pub fn rpt_denoise_var_params_default(out: *mut rpt_denoise_var_params);
     pub fn rpt_denoise_variance(ctx: *mut rpt_ctx, source: u32, moments_xyzw: *const f32, params: *const rpt_denoise_var_params, tonemap_op: u32, out_rgb: *mut f32, out_variance: *mut f32, report: *mut rpt_denoise_report) -> c_int;
+    // rpt_denoise_variance with the previous view's history reprojected and blended in front of the passes; out_history (nullable): the blended sample count per pixel
+    pub fn rpt_temporal_params_default(out: *mut rpt_temporal_params);
+    pub fn rpt_denoise_temporal(ctx: *mut rpt_ctx, source: u32, moments_xyzw: *const f32, params: *const rpt_temporal_params, tonemap_op: u32, out_rgb: *mut f32, out_variance: *mut f32, out_history: *mut f32, report: *mut rpt_temporal_report) -> c_int;
+    pub fn rpt_temporal_reset(ctx: *mut rpt_ctx) -> c_int;                          // forget and free the history
     pub fn rpt_read_guides(ctx: *mut rpt_ctx, albedo_rgb: *mut f32, normal_xyz: *mut f32, depth: *mut f32, position_xyz: *mut f32, kind: *mut u32) -> c_int;   // each nullable; albedo / normal = OIDN's auxiliary images
     // opt-in per-pixel sample moments (sum Y, sum Y^2, n, max Y), the noise estimate from them, and "render until the image is this clean"
     pub fn rpt_set_moments(ctx: *mut rpt_ctx, on: u32) -> c_int;                    // default 0; on: allocates and zeroes the record
@@ -185,6 +208,8 @@ extern "C" {
     pub fn rpt_multi_read_accum(m: *mut rpt_multi, out: *mut Vec4, out_samples: *mut u32) -> c_int;   // the whole W x H image, from rank 0
     pub fn rpt_multi_denoise(m: *mut rpt_multi, params: *const rpt_denoise_params, tonemap_op: u32, out_rgb: *mut f32, report: *mut rpt_denoise_report) -> c_int;   // waits, gathers, denoises on rank 0
     pub fn rpt_multi_denoise_variance(m: *mut rpt_multi, params: *const rpt_denoise_var_params, tonemap_op: u32, out_rgb: *mut f32, out_variance: *mut f32, report: *mut rpt_denoise_report) -> c_int;   // moments merged on the host, then as rpt_multi_denoise
+    pub fn rpt_multi_denoise_temporal(m: *mut rpt_multi, params: *const rpt_temporal_params, tonemap_op: u32, out_rgb: *mut f32, out_variance: *mut f32, out_history: *mut f32, report: *mut rpt_temporal_report) -> c_int;   // the history lives on rank 0
+    pub fn rpt_multi_temporal_reset(m: *mut rpt_multi) -> c_int;
     pub fn rpt_multi_set_moments(m: *mut rpt_multi, on: u32) -> c_int;              // rpt_set_moments on every rank
     pub fn rpt_multi_read_moments(m: *mut rpt_multi, out_xyzw: *mut Vec4) -> c_int; // the ranks' records merged on the host
     pub fn rpt_multi_noise_count(m: *mut rpt_multi, threshold: f32, out: *mut rpt_noise_counts) -> c_int;   // summed over the ranks

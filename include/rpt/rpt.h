@@ -451,6 +451,57 @@ int rpt_denoise_variance(rpt_ctx *ctx, uint32_t source, const float *moments_xyz
 int rpt_multi_denoise_variance(rpt_multi *m, const rpt_denoise_var_params *params, uint32_t tonemap_op, float *out_rgb, float *out_variance,
                                rpt_denoise_report *report);
 
+/* --- temporal reuse: rpt_denoise_variance with the previous view's history reprojected and blended in front of the passes ------------------------------
+ * Opt-in, a third entry point: rpt_denoise, rpt_denoise_variance, their kernels and their defaults are what they were.  The reference zeroes the
+ * accumulator whenever the camera moves and shows the unfiltered image of those frames (src/trace.rs:187-222); this call gives such a frame the samples and
+ * the variance of the view before it.  The formulas: csrc/k_temporal.h tp_pixel, DESIGN.md "Denoiser".
+ *
+ * History (kept on the context, 56 bytes per pixel and slot, two slots, allocated at first use): per pixel the blended colour e_h in the filter's units
+ * (demodulated where the passes demodulate), an f32 sample count N (0 = none) and the per-sample first and second luminance moments mu1, mu2, beside a copy
+ * of the guide records and the camera of the view it was made under.  IT IS THE BLENDED IMAGE BEFORE THE PASSES, NOT THE FILTERED ONE.
+ * Two slots: LAST, what the most recent call produced, and PREVIOUS, the history from before the current accumulator epoch.  An epoch ends at rpt_reset and at
+ * whatever else invalidates the accumulator; the first call of a new epoch promotes LAST to PREVIOUS; every call of an epoch blends the current accumulator
+ * with the same PREVIOUS (a second call after more samples does not count its own samples twice) and overwrites LAST.
+ * The history is dropped (history_state = 2, the call runs without it) on a change of width or height, on rpt_upload_scene, and when the passes demodulate
+ * (base.demodulate != 0 with base.iterations != 0) where the slot's did not or the reverse.  rpt_temporal_reset forgets and frees it; so do a resize and destroy.
+ *
+ * Per pixel p: its world position x_p is projected into the previous view (the pinhole camera inverted in closed form; misses by the rotation alone), the
+ * four bilinear taps there join if they hold history (N > 0), are of p's kind and — for hits — pass  n_p . n_q >= normal_min  and
+ * |n_p . (x_q - x_p)| / ((2 / width) t_p) <= plane_max  (footprints of p off its tangent plane); joined weights below 0.01 in sum: no history.  The taps'
+ * weighted means e_r, mu1_r, mu2_r and N_r = min(weighted mean of N, max_history) blend with the current mean e_cur and moments record m (n_cur = m.z):
+ *     T = N_r + n_cur,  e = (N_r e_r + n_cur e_cur) / T,  mu1 = (N_r mu1_r + m.x) / T,  mu2 = (N_r mu2_r + m.y) / T,
+ *     v = max(0, mu2 - mu1 mu1) / (T - 1)    (unknown, +inf, if T < 2; divided by Ya^2 where demodulated)
+ * and (e, v) goes through the unchanged passes of rpt_denoise_variance (`filter`).  A pixel without history — and every pixel of a call without a PREVIOUS
+ * slot — is rpt_denoise_variance's bit for bit, colour and variance.  A current mean that is not finite passes through and leaves no history.
+ *
+ * moments_xyzw, out_variance, source: as rpt_denoise_variance.  out_history (nullable, width*height floats): T per pixel (> n_cur exactly where history
+ * was reused).  rpt_multi_denoise_temporal: as rpt_multi_denoise_variance; the history lives on rank 0.
+ * RPT_EINVAL for everything rpt_denoise_variance refuses, for a negative or NaN max_history or plane_max (+inf allowed) and for a normal_min that is NaN or
+ * outside [-1, 1]; the context stays usable and its history is untouched.  Synchronous on return; leaves the accumulator, the rng, the moments, rpt_stats,
+ * the shadow mode and the cached guides untouched.
+ * Defaults: the lowest summed error of the grid of profiles/r15_temporal_quality.txt. */
+typedef struct rpt_temporal_params {
+    rpt_denoise_var_params filter;   /* the passes: as rpt_denoise_variance */
+    float    max_history;            /* cap on the reprojected sample count N_r; 0 = history never used */
+    float    normal_min;             /* a history tap joins only if n_p . n_q >= normal_min */
+    float    plane_max;              /* ... and |n_p . (x_q - x_p)| / ((2 / width) * t_p) <= plane_max  (footprints) */
+    uint32_t reserved[5];
+} rpt_temporal_params;
+typedef struct rpt_temporal_report {
+    rpt_denoise_report base;         /* device_ms includes the temporal kernel */
+    uint64_t pixels_with_history;    /* pixels whose N_r > 0 */
+    uint32_t history_state;          /* 0 none yet, 1 used, 2 dropped by this call (resize / scene / demodulate changed) */
+    uint32_t reserved;
+} rpt_temporal_report;
+void rpt_temporal_params_default(rpt_temporal_params *out);
+int rpt_denoise_temporal(rpt_ctx *ctx, uint32_t source, const float *moments_xyzw /* nullable */, const rpt_temporal_params *params /* NULL = defaults */,
+                         uint32_t tonemap_op, float *out_rgb, float *out_variance /* nullable, width*height */, float *out_history /* nullable, width*height */,
+                         rpt_temporal_report *report /* nullable */);
+int rpt_temporal_reset(rpt_ctx *ctx);
+int rpt_multi_denoise_temporal(rpt_multi *m, const rpt_temporal_params *params, uint32_t tonemap_op, float *out_rgb, float *out_variance, float *out_history,
+                               rpt_temporal_report *report);
+int rpt_multi_temporal_reset(rpt_multi *m);
+
 /* --- chosen pixels: masked passes, per-pixel sample counts to a noise target (no reference equivalent) --------------------------------------------------
  * Opt-in; a context that never makes a masked or adaptive call runs the same kernels as before, and bench.py's figures are not touched.
  * A sample depends only on its pixel's (x, y), its rng (n, offset) and the scene, and samples are added in sample order: a pixel that has received N samples

@@ -81,6 +81,18 @@ int rpt_debug_denoise_variance_host(uint32_t width, uint32_t height, const float
                                     const float *depth, const uint32_t *kind, const float *moments_xyzw, const rpt_denoise_var_params *params, uint32_t tonemap_op,
                                     float *out_rgb, float *out_variance);
 
+/* rpt_denoise_temporal on the HOST: the same headers (csrc/k_temporal.h, k_denoise.h) in a plain loop — no device needed.  The current view's planes and
+ * moments as rpt_debug_denoise_variance_host takes them; camera: the current view (position, rotation, width and height are read); prev_camera NULL = no
+ * history, else the previous view's camera, its guide planes prev_normal, prev_position, prev_kind and its history records prev_history: width*height
+ * records of 6 floats (e_h.r, e_h.g, e_h.b, N, mu1, mu2).  params NULL = defaults.  out_variance, out_history (T per pixel), out_records (the new history,
+ * 6 floats per pixel) and pixels_with_history_out are nullable.  RPT_EINVAL for the parameter values rpt_denoise_temporal refuses and for a camera whose
+ * width or height is not the image's. */
+int rpt_debug_denoise_temporal_host(uint32_t width, uint32_t height, const float *mean_rgb, const float *albedo, const float *normal, const float *position,
+                                    const float *depth, const uint32_t *kind, const float *moments_xyzw, const rpt_tracing_config *camera,
+                                    const rpt_tracing_config *prev_camera, const float *prev_normal, const float *prev_position, const uint32_t *prev_kind,
+                                    const float *prev_history, const rpt_temporal_params *params, uint32_t tonemap_op, float *out_rgb, float *out_variance,
+                                    float *out_history, float *out_records, uint64_t *pixels_with_history_out);
+
 /* noise_rel and the counts of rpt_noise_count on the HOST: the same header (csrc/k_moments.h) in a plain loop over n moments records (4 floats each: sum Y,
  * sum Y^2, n, max Y) — no device needed.  rel_out (n floats) and counts_out are nullable; counts_out->pixels = n.  RPT_EINVAL for a negative or NaN threshold. */
 int rpt_debug_noise_host(const float *moments_xyzw, size_t n, float threshold, float *rel_out, rpt_noise_counts *counts_out);

@@ -752,6 +752,29 @@ int rpt_multi_denoise_variance(rpt_multi *m, const rpt_denoise_var_params *param
     return rc ? multi_fail(m, root, rc) : RPT_OK;
 }
 
+/* rpt_multi_denoise_variance with rpt_denoise_temporal on rank 0, where the history lives */
+int rpt_multi_denoise_temporal(rpt_multi *m, const rpt_temporal_params *params, uint32_t tonemap_op, float *out_rgb, float *out_variance, float *out_history, rpt_temporal_report *report) {
+    if (!m) return RPT_EINVAL;
+    if (!out_rgb) { m->error = "rpt_denoise_temporal: out_rgb is null"; return RPT_EINVAL; }
+    rpt_ctx *root = m->ctx[0];
+    if (!root->has_config) { m->error = "rpt_denoise_temporal: needs a scene and a configuration"; return RPT_EINVAL; }
+    std::vector<float> moments((size_t)root->cfg.c.width * root->cfg.c.height * 4);
+    int rc = rpt_multi_read_moments(m, moments.data());              /* (waits; RPT_EINVAL while moments are off) */
+    if (rc) return rc;
+    if (!m->gathered) {              /* as rpt_multi_read_accum: nothing rendered since the last reset */
+        if ((rc = multi_gather(m))) return rc;
+        if ((rc = rpt_multi_wait(m))) return rc;
+    }
+    rc = rpt_denoise_temporal(root, RPT_DENOISE_GATHERED, moments.data(), params, tonemap_op, out_rgb, out_variance, out_history, report);
+    return rc ? multi_fail(m, root, rc) : RPT_OK;
+}
+
+int rpt_multi_temporal_reset(rpt_multi *m) {
+    if (!m) return RPT_EINVAL;
+    const int rc = rpt_temporal_reset(m->ctx[0]);
+    return rc ? multi_fail(m, m->ctx[0], rc) : RPT_OK;
+}
+
 /* integers: the sum over the ranks */
 int rpt_multi_noise_count(rpt_multi *m, float threshold, rpt_noise_counts *out) {
     if (!m || !out) return RPT_EINVAL;

@@ -132,6 +132,17 @@ struct StageTimer {
 constexpr int RPT_RING_LAG = 6;   /* most iterations the host may run ahead of the progress report it inspects (small launches) */
 constexpr int RPT_RING = 16;      /* power of two, > RPT_RING_LAG */
 
+/* one history slot of rpt_denoise_temporal (k_temporal.h): 56 bytes per pixel, row-major, and the view it was made under */
+struct TemporalSlot {
+    DevBuf<float4> h, g0, g1;             /* (e_h | N), and copies of the guide records (normal | depth), (position | kind bits) */
+    DevBuf<float2> mu;                    /* (mu1, mu2) */
+    float ro[3] = {0.0f, 0.0f, 0.0f}, euler[9] = {};   /* that view's camera position and DevConfig::euler */
+    uint64_t epoch = 0;                   /* rpt_ctx::accum_epoch of the call that wrote it */
+    bool demodulated = false;             /* e_h is divided by the albedo */
+    bool valid = false;
+    void release() { h.release(); g0.release(); g1.release(); mu.release(); valid = false; }
+};
+
 /* rpt_denoise.hip: what rpt_denoise / rpt_read_guides keep on a context — allocated on first use, released on destroy and on a resize.  The guides
  * belong to (scene, configuration): rpt_upload_scene and rpt_set_config mark them stale, the next use rebuilds them. */
 struct DenoiseState {
@@ -143,6 +154,13 @@ struct DenoiseState {
     DevBuf<uint32_t> order;               /* x | y << 16 of every pixel of the image in tile order (rank 0 of 1): a wave of guide rays is an 8 x 8 block */
     uint32_t width = 0, height = 0;       /* what the buffers are sized for */
     bool guides_valid = false;
+    /* rpt_denoise_temporal (k_temporal.h): the two history slots, allocated at its first use, freed by rpt_temporal_reset, a resize and destroy */
+    TemporalSlot last, previous;          /* what the most recent call produced; the history from before the current accumulator epoch */
+    DevBuf<float> history_t;              /* W x H: T per pixel, before it leaves the device */
+    DevBuf<uint32_t> inverse;             /* W x H: the element of `order` that is row-major pixel i (the fused kernel reads the tile-major accumulator by rows) */
+    DevBuf<unsigned long long> with_history;   /* the kernel's count of pixels that reused history */
+    bool scene_changed = false;           /* rpt_upload_scene since the last call of rpt_denoise_temporal: that call drops the history */
+    bool history_dropped = false;         /* a resize freed a valid history: the next call reports it */
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   /* guides begin / end, filter begin / end (created with the buffers, destroyed by rpt_denoise_release) */
 };
 
@@ -263,6 +281,7 @@ struct rpt_ctx {
     DevState state{};
     DevQueues queues{};
     uint32_t samples = 0;                /* the samples EVERY owned pixel received through uniform calls (what rpt_read_accum reports) */
+    uint64_t accum_epoch = 0;            /* counts what invalidates the accumulator (rpt_reset, a resize): rpt_denoise_temporal promotes its history once per epoch */
     bool counts_nonuniform = false;      /* a masked pass gave samples to some owned pixels only: accum.w differs between pixels, the read-outs divide by it
                                             (k_adaptive.h mean_own).  Cleared by rpt_reset and by whatever invalidates the accumulator. */
     const PixelView *view = nullptr;     /* set for the duration of a masked pass's render call */
@@ -342,6 +361,8 @@ int rpt_resolve_own(rpt_ctx *c, uint32_t tonemap_op, float *out_rgb);
 int rpt_render_adaptive_with(const rpt_noise_target *target, rpt_adaptive_result *out, const rpt_adaptive_driver &driver, void *who);
 /* rpt_denoise.hip: the denoiser's buffers go (a resize), or buffers and events (the context goes away: while its device is current) */
 void rpt_denoise_release(rpt_ctx *c, bool events_too);
+/* rpt_hip.hip: DevConfig::euler of a configuration's cam_rotation */
+void rpt_camera_matrix(const float *cam_rotation, float *euler_out);
 std::string &rpt_create_error();
 
 /* RPT_UPLOAD_TIMING=1: host-side section times of rpt_upload_scene / rpt_bvh_build_gpu on stderr (where the start-up time of a large scene goes) */

@@ -1,6 +1,7 @@
 /*
  * rpt_denoise.hip — the denoise step behind the C ABI (include/rpt/rpt.h rpt_denoise, rpt_denoise_variance, rpt_read_guides, rpt_denoise_params_default,
- * rpt_denoise_var_params_default) and its host builds (rpt_debug.h rpt_debug_denoise_host, rpt_debug_denoise_variance_host): the guide buffers of a context — built with the one-ray-per-lane nearest-hit walk the debug hook launches
+ * rpt_denoise_var_params_default, rpt_denoise_temporal, rpt_temporal_reset, rpt_temporal_params_default) and its host builds (rpt_debug.h rpt_debug_denoise_host,
+ * rpt_debug_denoise_variance_host, rpt_debug_denoise_temporal_host): the guide buffers of a context — built with the one-ray-per-lane nearest-hit walk the debug hook launches
  * (rpt_launch_trace_debug: LDS or global variant per scene, no new walk instantiated) and a small shading kernel — and the passes of k_denoise.h.
  */
 #include <cstring>
@@ -9,6 +10,7 @@
 #include "rpt_ctx.h"
 #include "k_denoise.h"
 #include "k_adaptive.h"
+#include "k_temporal.h"
 
 namespace {
 
@@ -17,6 +19,9 @@ constexpr rpt_denoise_params DN_DEFAULTS = {2u, 0u, 1.0f, 2.0f, 1u, {0u, 0u, 0u}
 
 /* the grid of profiles/r14_denoise_variance_quality.txt (tools/denoise_probe.py --quality) */
 constexpr rpt_denoise_var_params DN_VAR_DEFAULTS = {DN_DEFAULTS, 0.0f, {0u, 0u, 0u}};
+
+/* the grid of profiles/r15_temporal_quality.txt (tools/denoise_probe.py --quality-temporal): with a history the variance term pays, so it is on here */
+constexpr rpt_temporal_params TP_DEFAULTS = {{DN_DEFAULTS, 32.0f, {0u, 0u, 0u}}, 8.0f, 0.5f, 0.5f, {0u, 0u, 0u, 0u, 0u}};
 
 int check_params(const rpt_denoise_params &p, uint32_t tonemap_op, std::string &error) {
     if (p.iterations > RPT_DN_MAX_ITERATIONS) { error = "rpt_denoise: iterations must be 0..6"; return RPT_EINVAL; }
@@ -32,6 +37,13 @@ int check_params(const rpt_denoise_params &p, uint32_t tonemap_op, std::string &
 int check_var_params(const rpt_denoise_var_params &p, uint32_t tonemap_op, std::string &error) {
     RPT_TRY(check_params(p.base, tonemap_op, error));
     if (!(p.sigma_variance >= 0.0f)) { error = "rpt_denoise_variance: sigma_variance must be >= 0 (+inf allowed)"; return RPT_EINVAL; }
+    return RPT_OK;
+}
+
+int check_temporal_params(const rpt_temporal_params &p, uint32_t tonemap_op, std::string &error) {
+    RPT_TRY(check_var_params(p.filter, tonemap_op, error));
+    if (!(p.max_history >= 0.0f) || !(p.plane_max >= 0.0f)) { error = "rpt_denoise_temporal: max_history and plane_max must be >= 0 (+inf allowed)"; return RPT_EINVAL; }
+    if (!(p.normal_min >= -1.0f && p.normal_min <= 1.0f)) { error = "rpt_denoise_temporal: normal_min must be in [-1, 1]"; return RPT_EINVAL; }
     return RPT_OK;
 }
 
@@ -148,11 +160,95 @@ int open_source(rpt_ctx *c, uint32_t source, DnSource *out) {
     return RPT_OK;
 }
 
+/* the moments a call filters by: the context's own record (beside its accumulator, in its order) or the caller's row-major image, uploaded for this call
+ * (the previous call's kernels have drained: every call is synchronous on return).  `who`: the entry point, for the error text. */
+int check_moments_source(rpt_ctx *c, uint32_t source, const float *moments_xyzw, const char *who) {
+    if (moments_xyzw) return RPT_OK;
+    /* the context's own record: it lies beside the accumulator, and only there */
+    if (source == RPT_DENOISE_GATHERED) { c->error = std::string(who) + ": moments are not part of the gather: RPT_DENOISE_GATHERED needs a moments image (rpt_read_moments / rpt_multi_read_moments)"; return RPT_EINVAL; }
+    if (!c->moments_on) { c->error = std::string(who) + ": moments are off (rpt_set_moments(ctx, 1) first, or pass a moments image)"; return RPT_EINVAL; }
+    return RPT_OK;
+}
+int open_moments(rpt_ctx *c, const float *moments_xyzw, uint32_t n, const char *who, const float4 **out) {
+    DenoiseState &d = c->dn;
+    if (d.variance.n != n) HIP_TRY(c, d.variance.alloc(n));
+    *out = c->moments.p;
+    if (moments_xyzw) {
+        if (d.moments_in.n != n) HIP_TRY(c, d.moments_in.alloc(n));
+        HIP_TRY(c, hipMemcpy(d.moments_in.p, moments_xyzw, (size_t)n * sizeof(float4), hipMemcpyHostToDevice));
+        *out = d.moments_in.p;
+    } else if (c->moments.n != n) {      /* (one rank owns every pixel: checked by open_source) */
+        c->error = std::string(who) + ": internal error (the moments record does not cover the image)";
+        return RPT_EHIP;
+    }
+    return RPT_OK;
+}
+
+/* the passes of the variance-guided filter over the prepared image in d.ping, into d.rgb and d.variance (iterations == 0: resolve only) */
+void launch_var_passes(hipStream_t s, DenoiseState &d, const rpt_denoise_var_params &vp, bool demodulated, uint32_t tonemap_op) {
+    const rpt_denoise_params &p = vp.base;
+    const uint32_t W = d.width, H = d.height, n = W * H;
+    if (p.iterations == 0u) {
+        k_dn_resolve<<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(d.ping.p, n, tonemap_op, d.rgb.p);
+        k_dn_variance_plane<<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(d.ping.p, n, d.variance.p);
+    }
+    float4 *src = d.ping.p, *dst = d.pong.p;
+    for (uint32_t i = 0; i < p.iterations; ++i) {
+        const DnPass ps = dn_pass(W, H, i, p.normal_power_log2, p.sigma_color, p.sigma_plane);
+        launch_pass_var(s, ps, vp.sigma_variance, i + 1u == p.iterations, src, d, dst, demodulated ? 1u : 0u, tonemap_op);
+        std::swap(src, dst);
+    }
+}
+
+/* the host build of those passes: ping holds the prepared (e | v) */
+void host_var_passes(uint32_t width, uint32_t height, const rpt_denoise_var_params &vp, bool demodulated, uint32_t tonemap_op, std::vector<float4> &ping, const std::vector<float4> &g0,
+                     const std::vector<float4> &g1, const std::vector<float4> &a, float *out_rgb, float *out_variance) {
+    const rpt_denoise_params &p = vp.base;
+    const size_t n = (size_t)width * height;
+    std::vector<float4> pong(n);
+    std::vector<float4> *src = &ping, *dst = &pong;
+    for (uint32_t i = 0; i < p.iterations; ++i) {
+        const DnPass ps = dn_pass(width, height, i, p.normal_power_log2, p.sigma_color, p.sigma_plane);
+        for (uint32_t y = 0; y < height; ++y)
+            for (uint32_t x = 0; x < width; ++x) {
+                const DnVarOut o = dn_filter_pixel_var(ps, vp.sigma_variance, src->data(), g0.data(), g1.data(), x, y);
+                (*dst)[(size_t)y * width + x] = make_float4(o.e.x, o.e.y, o.e.z, o.v);
+            }
+        std::swap(src, dst);
+    }
+    for (size_t i = 0; i < n; ++i) {
+        const float4 e = (*src)[i];
+        const F3 c = dn_finish_pixel(f3(e.x, e.y, e.z), f3(a[i].x, a[i].y, a[i].z), demodulated, tonemap_op);
+        out_rgb[3 * i] = c.x; out_rgb[3 * i + 1] = c.y; out_rgb[3 * i + 2] = c.z;
+        if (out_variance) out_variance[i] = e.w;
+    }
+}
+
+void fill_report(const DenoiseState &d, bool rebuilt, rpt_denoise_report *report) {
+    float ms = 0.0f;
+    *report = rpt_denoise_report{};
+    if (hipEventElapsedTime(&ms, d.ev[2], d.ev[3]) == hipSuccess) report->device_ms = ms;
+    if (rebuilt && hipEventElapsedTime(&ms, d.ev[0], d.ev[1]) == hipSuccess) report->guides_ms = ms;
+    report->guides_rebuilt = rebuilt ? 1u : 0u;
+}
+
+/* the two cameras of a call into its TpView: the current position, and — prev_ro != null — the previous view's, with the bit-for-bit comparison */
+void tp_set_cameras(TpView &vw, const float *ro_cur, const float *euler_cur, const float *ro_prev, const float *euler_prev) {
+    memcpy(vw.ro_cur, ro_cur, sizeof vw.ro_cur);
+    if (!ro_prev) return;
+    vw.has_history = 1u;
+    memcpy(vw.ro_prev, ro_prev, sizeof vw.ro_prev);
+    memcpy(vw.euler_prev, euler_prev, sizeof vw.euler_prev);
+    vw.identity = memcmp(ro_cur, ro_prev, sizeof vw.ro_cur) == 0 && memcmp(euler_cur, euler_prev, sizeof vw.euler_prev) == 0 ? 1u : 0u;
+}
+
 }  // namespace
 
 void rpt_denoise_release(rpt_ctx *c, bool events_too) {
     DenoiseState &d = c->dn;
     d.g0.release(); d.g1.release(); d.albedo.release(); d.ping.release(); d.pong.release(); d.rgb.release(); d.order.release(); d.variance.release(); d.moments_in.release();
+    if (d.last.valid || d.previous.valid) d.history_dropped = true;      /* (a resize: the next rpt_denoise_temporal reports it) */
+    d.last.release(); d.previous.release(); d.history_t.release(); d.inverse.release(); d.with_history.release();
     d.width = d.height = 0;
     d.guides_valid = false;
     if (events_too)
@@ -217,10 +313,7 @@ int rpt_denoise_variance(rpt_ctx *c, uint32_t source, const float *moments_xyzw,
     const rpt_denoise_var_params vp = params ? *params : DN_VAR_DEFAULTS;
     const rpt_denoise_params &p = vp.base;
     RPT_TRY(check_var_params(vp, tonemap_op, c->error));
-    if (!moments_xyzw) {                 /* the context's own record: it lies beside the accumulator, and only there */
-        if (source == RPT_DENOISE_GATHERED) { c->error = "rpt_denoise_variance: moments are not part of the gather: RPT_DENOISE_GATHERED needs a moments image (rpt_read_moments / rpt_multi_read_moments)"; return RPT_EINVAL; }
-        if (!c->moments_on) { c->error = "rpt_denoise_variance: moments are off (rpt_set_moments(ctx, 1) first, or pass a moments image)"; return RPT_EINVAL; }
-    }
+    RPT_TRY(check_moments_source(c, source, moments_xyzw, "rpt_denoise_variance"));
     DnSource in;
     RPT_TRY(open_source(c, source, &in));
     hipStream_t s = in.stream;
@@ -228,43 +321,112 @@ int rpt_denoise_variance(rpt_ctx *c, uint32_t source, const float *moments_xyzw,
     RPT_TRY(ensure_guides(c, &rebuilt));
     DenoiseState &d = c->dn;
     const uint32_t W = d.width, H = d.height, n = W * H;
-    if (d.variance.n != n) HIP_TRY(c, d.variance.alloc(n));
-    const float4 *moments = c->moments.p;
-    if (moments_xyzw) {                  /* uploaded for this call (the previous call's kernels have drained: every call is synchronous on return) */
-        if (d.moments_in.n != n) HIP_TRY(c, d.moments_in.alloc(n));
-        HIP_TRY(c, hipMemcpy(d.moments_in.p, moments_xyzw, (size_t)n * sizeof(float4), hipMemcpyHostToDevice));
-        moments = d.moments_in.p;
-    } else if (c->moments.n != n) {      /* (one rank owns every pixel: checked by open_source) */
-        c->error = "rpt_denoise_variance: internal error (the moments record does not cover the image)";
-        return RPT_EHIP;
-    }
+    const float4 *moments = nullptr;
+    RPT_TRY(open_moments(c, moments_xyzw, n, "rpt_denoise_variance", &moments));
     const uint32_t row_major = moments_xyzw ? 1u : 0u;
     const bool demodulated = p.iterations != 0u && p.demodulate != 0u;
     const float4 *albedo = demodulated ? d.albedo.p : nullptr;
     HIP_TRY(c, hipEventRecord(d.ev[2], s));
     if (in.own_counts) k_dn_prepare_var<true><<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(in.sums, moments, in.order, row_major, n, W, 0.0f, albedo, d.ping.p);
     else k_dn_prepare_var<false><<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(in.sums, moments, in.order, row_major, n, W, (float)in.samples, albedo, d.ping.p);
-    if (p.iterations == 0u) {
-        k_dn_resolve<<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(d.ping.p, n, tonemap_op, d.rgb.p);
-        k_dn_variance_plane<<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(d.ping.p, n, d.variance.p);
-    }
-    float4 *src = d.ping.p, *dst = d.pong.p;
-    for (uint32_t i = 0; i < p.iterations; ++i) {
-        const DnPass ps = dn_pass(W, H, i, p.normal_power_log2, p.sigma_color, p.sigma_plane);
-        launch_pass_var(s, ps, vp.sigma_variance, i + 1u == p.iterations, src, d, dst, demodulated ? 1u : 0u, tonemap_op);
-        std::swap(src, dst);
-    }
+    launch_var_passes(s, d, vp, demodulated, tonemap_op);
     HIP_TRY(c, hipEventRecord(d.ev[3], s));
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(out_rgb, d.rgb.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
     if (out_variance) HIP_TRY(c, hipMemcpyAsync(out_variance, d.variance.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
+    if (report) fill_report(d, rebuilt, report);
+    return RPT_OK;
+}
+
+void rpt_temporal_params_default(rpt_temporal_params *out) {
+    if (out) *out = TP_DEFAULTS;
+}
+
+int rpt_temporal_reset(rpt_ctx *c) {
+    if (!c) return RPT_EINVAL;
+    HIP_TRY(c, hipSetDevice(c->device));
+    DenoiseState &d = c->dn;
+    d.last.release(); d.previous.release(); d.history_t.release(); d.inverse.release(); d.with_history.release();
+    d.history_dropped = false;
+    return RPT_OK;
+}
+
+int rpt_denoise_temporal(rpt_ctx *c, uint32_t source, const float *moments_xyzw, const rpt_temporal_params *params, uint32_t tonemap_op, float *out_rgb, float *out_variance,
+                         float *out_history, rpt_temporal_report *report) {
+    if (!c) return RPT_EINVAL;
+    if (!out_rgb) { c->error = "rpt_denoise_temporal: out_rgb is null"; return RPT_EINVAL; }
+    const rpt_temporal_params tp = params ? *params : TP_DEFAULTS;
+    const rpt_denoise_params &p = tp.filter.base;
+    RPT_TRY(check_temporal_params(tp, tonemap_op, c->error));
+    RPT_TRY(check_moments_source(c, source, moments_xyzw, "rpt_denoise_temporal"));
+    DnSource in;
+    RPT_TRY(open_source(c, source, &in));
+    hipStream_t s = in.stream;
+    bool rebuilt = false;
+    RPT_TRY(ensure_guides(c, &rebuilt));
+    DenoiseState &d = c->dn;
+    const uint32_t W = d.width, H = d.height, n = W * H;
+    const float4 *moments = nullptr;
+    RPT_TRY(open_moments(c, moments_xyzw, n, "rpt_denoise_temporal", &moments));
+    const bool demodulated = p.iterations != 0u && p.demodulate != 0u;
+    const float4 *albedo = demodulated ? d.albedo.p : nullptr;
+
+    /* the slots: drop what no longer fits, promote once per accumulator epoch (a resize has freed them already) */
+    uint32_t state = 0u;
+    const bool units_differ = (d.last.valid && d.last.demodulated != demodulated) || (d.previous.valid && d.previous.demodulated != demodulated);
+    if (d.history_dropped || ((d.last.valid || d.previous.valid) && (d.scene_changed || units_differ))) {
+        d.last.release(); d.previous.release();
+        state = 2u;
+    }
+    d.history_dropped = d.scene_changed = false;
+    if (d.last.valid && d.last.epoch != c->accum_epoch) {
+        std::swap(d.last, d.previous);
+        d.last.valid = false;
+    }
+    if (d.previous.valid) state = 1u;
+    TemporalSlot &last = d.last;
+    if (last.h.n != n) { HIP_TRY(c, last.h.alloc(n)); HIP_TRY(c, last.g0.alloc(n)); HIP_TRY(c, last.g1.alloc(n)); HIP_TRY(c, last.mu.alloc(n)); }
+    if (d.history_t.n != n) HIP_TRY(c, d.history_t.alloc(n));
+    if (!d.with_history.p) HIP_TRY(c, d.with_history.alloc(1));
+    if (in.order && d.inverse.n != n) {      /* (one rank owns every pixel: the context's order is the whole image's) */
+        if (c->pixel_xy_host.size() != n) { c->error = "rpt_denoise_temporal: internal error (the pixel order does not cover the image)"; return RPT_EHIP; }
+        std::vector<uint32_t> inverse(n);
+        for (uint32_t i = 0; i < n; ++i) inverse[rpt_pixel_index(c->pixel_xy_host[i], W)] = i;
+        HIP_TRY(c, d.inverse.from_host(inverse.data(), n));
+    }
+    TpView vw = tp_view(W, H, tp.max_history, tp.normal_min, tp.plane_max);
+    tp_set_cameras(vw, c->cfg.c.cam_position, c->cfg.euler, d.previous.valid ? d.previous.ro : nullptr, d.previous.euler);
+    const TpPrev pv = d.previous.valid ? TpPrev{d.previous.h.p, d.previous.mu.p, d.previous.g0.p, d.previous.g1.p} : TpPrev{nullptr, nullptr, nullptr, nullptr};
+    const uint32_t row_major = moments_xyzw ? 1u : 0u;
+    const uint32_t *inverse = in.order ? d.inverse.p : nullptr;
+    const dim3 grid((W + 63u) / 64u, (H + 3u) / 4u);
+    last.valid = false;
+    HIP_TRY(c, hipEventRecord(d.ev[2], s));
+    HIP_TRY(c, hipMemsetAsync(d.with_history.p, 0, sizeof(unsigned long long), s));
+    if (in.own_counts) k_dn_temporal<true><<<grid, 256, 0, s>>>(vw, pv, in.sums, moments, inverse, row_major, 0.0f, d.g0.p, d.g1.p, albedo, d.ping.p, last.h.p, last.mu.p, d.history_t.p, d.with_history.p);
+    else k_dn_temporal<false><<<grid, 256, 0, s>>>(vw, pv, in.sums, moments, inverse, row_major, (float)in.samples, d.g0.p, d.g1.p, albedo, d.ping.p, last.h.p, last.mu.p, d.history_t.p, d.with_history.p);
+    HIP_TRY(c, hipMemcpyAsync(last.g0.p, d.g0.p, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(last.g1.p, d.g1.p, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, s));
+    launch_var_passes(s, d, tp.filter, demodulated, tonemap_op);
+    HIP_TRY(c, hipEventRecord(d.ev[3], s));
+    HIP_TRY(c, hipGetLastError());
+    unsigned long long with_history = 0ull;
+    HIP_TRY(c, hipMemcpyAsync(out_rgb, d.rgb.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (out_variance) HIP_TRY(c, hipMemcpyAsync(out_variance, d.variance.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (out_history) HIP_TRY(c, hipMemcpyAsync(out_history, d.history_t.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&with_history, d.with_history.p, sizeof with_history, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    last.valid = true;
+    last.epoch = c->accum_epoch;
+    last.demodulated = demodulated;
+    memcpy(last.ro, c->cfg.c.cam_position, sizeof last.ro);
+    memcpy(last.euler, c->cfg.euler, sizeof last.euler);
     if (report) {
-        float ms = 0.0f;
-        *report = rpt_denoise_report{};
-        if (hipEventElapsedTime(&ms, d.ev[2], d.ev[3]) == hipSuccess) report->device_ms = ms;
-        if (rebuilt && hipEventElapsedTime(&ms, d.ev[0], d.ev[1]) == hipSuccess) report->guides_ms = ms;
-        report->guides_rebuilt = rebuilt ? 1u : 0u;
+        *report = rpt_temporal_report{};
+        fill_report(d, rebuilt, &report->base);
+        report->pixels_with_history = with_history;
+        report->history_state = state;
     }
     return RPT_OK;
 }
@@ -342,7 +504,7 @@ int rpt_debug_denoise_variance_host(uint32_t width, uint32_t height, const float
     if (check_var_params(vp, tonemap_op, error)) { rpt_create_error() = error; return RPT_EINVAL; }
     const size_t n = (size_t)width * height;
     const bool demodulated = p.iterations != 0u && p.demodulate != 0u;
-    std::vector<float4> g0(n), g1(n), a(n), ping(n), pong(n);
+    std::vector<float4> g0(n), g1(n), a(n), ping(n);
     for (size_t i = 0; i < n; ++i) {
         g0[i] = make_float4(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], depth[i]);
         g1[i] = make_float4(position[3 * i], position[3 * i + 1], position[3 * i + 2], rptm::u2f(kind[i]));
@@ -353,22 +515,66 @@ int rpt_debug_denoise_variance_host(uint32_t width, uint32_t height, const float
         const float4 m = make_float4(moments_xyzw[4 * i], moments_xyzw[4 * i + 1], moments_xyzw[4 * i + 2], moments_xyzw[4 * i + 3]);
         ping[i] = make_float4(c.x, c.y, c.z, dn_prepare_variance(m, demodulated, al));
     }
-    std::vector<float4> *src = &ping, *dst = &pong;
-    for (uint32_t i = 0; i < p.iterations; ++i) {
-        const DnPass ps = dn_pass(width, height, i, p.normal_power_log2, p.sigma_color, p.sigma_plane);
-        for (uint32_t y = 0; y < height; ++y)
-            for (uint32_t x = 0; x < width; ++x) {
-                const DnVarOut o = dn_filter_pixel_var(ps, vp.sigma_variance, src->data(), g0.data(), g1.data(), x, y);
-                (*dst)[(size_t)y * width + x] = make_float4(o.e.x, o.e.y, o.e.z, o.v);
+    host_var_passes(width, height, vp, demodulated, tonemap_op, ping, g0, g1, a, out_rgb, out_variance);
+    return RPT_OK;
+}
+
+/* rpt_denoise_temporal on the host: the loop k_dn_temporal is, over the same RPT_HD function, then the passes above */
+int rpt_debug_denoise_temporal_host(uint32_t width, uint32_t height, const float *mean_rgb, const float *albedo, const float *normal, const float *position, const float *depth,
+                                    const uint32_t *kind, const float *moments_xyzw, const rpt_tracing_config *camera, const rpt_tracing_config *prev_camera, const float *prev_normal,
+                                    const float *prev_position, const uint32_t *prev_kind, const float *prev_history, const rpt_temporal_params *params, uint32_t tonemap_op, float *out_rgb,
+                                    float *out_variance, float *out_history, float *out_records, uint64_t *pixels_with_history_out) {
+    if (!mean_rgb || !albedo || !normal || !position || !depth || !kind || !moments_xyzw || !camera || !out_rgb || width == 0u || height == 0u || width > 65535u || height > 65535u) return RPT_EINVAL;
+    if (prev_camera && (!prev_normal || !prev_position || !prev_kind || !prev_history)) return RPT_EINVAL;
+    const rpt_temporal_params tp = params ? *params : TP_DEFAULTS;
+    const rpt_denoise_params &p = tp.filter.base;
+    std::string error;
+    if (check_temporal_params(tp, tonemap_op, error)) { rpt_create_error() = error; return RPT_EINVAL; }
+    if (camera->width != width || camera->height != height || (prev_camera && (prev_camera->width != width || prev_camera->height != height))) {
+        rpt_create_error() = "rpt_debug_denoise_temporal_host: a camera's width and height must be the image's";
+        return RPT_EINVAL;
+    }
+    const size_t n = (size_t)width * height;
+    const bool demodulated = p.iterations != 0u && p.demodulate != 0u;
+    TpView vw = tp_view(width, height, tp.max_history, tp.normal_min, tp.plane_max);
+    float euler_cur[9], euler_prev[9] = {};
+    rpt_camera_matrix(camera->cam_rotation, euler_cur);
+    if (prev_camera) rpt_camera_matrix(prev_camera->cam_rotation, euler_prev);
+    tp_set_cameras(vw, camera->cam_position, euler_cur, prev_camera ? prev_camera->cam_position : nullptr, euler_prev);
+    std::vector<float4> g0(n), g1(n), a(n), ping(n), ph, pg0, pg1;
+    std::vector<float2> pmu;
+    if (prev_camera) {
+        ph.resize(n); pg0.resize(n); pg1.resize(n); pmu.resize(n);
+        for (size_t i = 0; i < n; ++i) {
+            ph[i] = make_float4(prev_history[6 * i], prev_history[6 * i + 1], prev_history[6 * i + 2], prev_history[6 * i + 3]);
+            pmu[i] = make_float2(prev_history[6 * i + 4], prev_history[6 * i + 5]);
+            pg0[i] = make_float4(prev_normal[3 * i], prev_normal[3 * i + 1], prev_normal[3 * i + 2], 0.0f);      /* (a tap reads no depth) */
+            pg1[i] = make_float4(prev_position[3 * i], prev_position[3 * i + 1], prev_position[3 * i + 2], rptm::u2f(prev_kind[i]));
+        }
+    }
+    const TpPrev pv = TpPrev{ph.data(), pmu.data(), pg0.data(), pg1.data()};
+    uint64_t with_history = 0;
+    for (uint32_t y = 0; y < height; ++y)
+        for (uint32_t x = 0; x < width; ++x) {
+            const size_t i = (size_t)y * width + x;
+            g0[i] = make_float4(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], depth[i]);
+            g1[i] = make_float4(position[3 * i], position[3 * i + 1], position[3 * i + 2], rptm::u2f(kind[i]));
+            a[i] = make_float4(albedo[3 * i], albedo[3 * i + 1], albedo[3 * i + 2], 0.0f);
+            const F3 al = f3(a[i].x, a[i].y, a[i].z);
+            F3 c = f3(mean_rgb[3 * i], mean_rgb[3 * i + 1], mean_rgb[3 * i + 2]);
+            if (demodulated) c = dn_demodulate(c, al);
+            const float4 m = make_float4(moments_xyzw[4 * i], moments_xyzw[4 * i + 1], moments_xyzw[4 * i + 2], moments_xyzw[4 * i + 3]);
+            const TpOut o = tp_pixel(vw, pv, x, y, c, m, g0[i], g1[i], demodulated, al);
+            ping[i] = make_float4(o.e.x, o.e.y, o.e.z, o.v);
+            if (out_history) out_history[i] = o.T;
+            if (out_records) {
+                float *r = out_records + 6 * i;
+                r[0] = o.e.x; r[1] = o.e.y; r[2] = o.e.z; r[3] = o.N; r[4] = o.mu1; r[5] = o.mu2;
             }
-        std::swap(src, dst);
-    }
-    for (size_t i = 0; i < n; ++i) {
-        const float4 e = (*src)[i];
-        const F3 c = dn_finish_pixel(f3(e.x, e.y, e.z), f3(a[i].x, a[i].y, a[i].z), demodulated, tonemap_op);
-        out_rgb[3 * i] = c.x; out_rgb[3 * i + 1] = c.y; out_rgb[3 * i + 2] = c.z;
-        if (out_variance) out_variance[i] = e.w;
-    }
+            with_history += o.reused ? 1u : 0u;
+        }
+    if (pixels_with_history_out) *pixels_with_history_out = with_history;
+    host_var_passes(width, height, tp.filter, demodulated, tonemap_op, ping, g0, g1, a, out_rgb, out_variance);
     return RPT_OK;
 }
 

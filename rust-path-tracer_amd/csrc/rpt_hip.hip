@@ -213,6 +213,14 @@ static uint32_t dispatch_iteration(rpt_ctx *c, uint32_t iteration, uint32_t bloc
 
 }  // namespace
 
+/* DevConfig::euler of a configuration's cam_rotation (x = pitch, y = yaw): column-major RotY(yaw) * RotX(pitch) */
+void rpt_camera_matrix(const float *cam_rotation, float *euler_out) {
+    float ry[9], rx[9];
+    rotation_y(cam_rotation[1], ry);
+    rotation_x(cam_rotation[0], rx);
+    mat3_mul_host(ry, rx, euler_out);
+}
+
 /* The per-slot arrays, for a render call over `n` slots: grown (never shrunk) to what the call needs — the path state always, the shadow
  * queue when the configuration has NEE, the MIS carry when it is MIS.  Growing waits for whatever is in flight, frees the old arrays first
  * and leaves every slot idle; between render calls every slot IS idle, so nothing is carried over. */
@@ -380,10 +388,7 @@ int rpt_set_config(rpt_ctx *c, const rpt_tracing_config *cfg) {
     bool resized = !c->has_config || c->cfg.c.width != cfg->width || c->cfg.c.height != cfg->height;
     c->cfg.c = *cfg;
     c->cfg.nee_mode = nee_mode;
-    float ry[9], rx[9];
-    rotation_y(cfg->cam_rotation[1], ry);
-    rotation_x(cfg->cam_rotation[0], rx);
-    mat3_mul_host(ry, rx, c->cfg.euler);
+    rpt_camera_matrix(cfg->cam_rotation, c->cfg.euler);
     rotation_y(rptm::atan2r(cfg->sun_direction[2], cfg->sun_direction[0]), c->cfg.sky_rot);
     c->dn.guides_valid = false;          /* the denoiser's guides are the first hits of THIS camera: rebuilt at their next use */
     if (resized || !c->has_state) {
@@ -429,6 +434,7 @@ int rpt_set_config(rpt_ctx *c, const rpt_tracing_config *cfg) {
         }
         c->samples = 0;
         c->counts_nonuniform = false;
+        c->accum_epoch += 1;
         RPT_TRY(rpt_moments_reset(c));       /* (moments on: a record for the new pixel count, zeroed like the accumulator) */
     }
     c->has_config = true;
@@ -459,6 +465,7 @@ int rpt_reset(rpt_ctx *c, const rpt_rng_state *seed, const float *accum_init, ui
     RPT_TRY(rpt_moments_reset(c));           /* (not resumed: with accum_init the record counts the samples rendered from here on) */
     c->samples = accum_init ? samples_init : 0u;
     c->counts_nonuniform = false;
+    c->accum_epoch += 1;
     c->has_seeds = true;
     c->stats = rpt_stats{};
     return RPT_OK;

@@ -38,6 +38,19 @@ class DenoiseReport(C.Structure):
     _fields_ = [("device_ms", C.c_double), ("guides_ms", C.c_double), ("guides_rebuilt", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class TemporalParams(C.Structure):
+    """rpt_temporal_params"""
+    _fields_ = [("filter", DenoiseVarParams), ("max_history", C.c_float), ("normal_min", C.c_float), ("plane_max", C.c_float), ("reserved", C.c_uint32 * 5)]
+
+
+class TemporalReport(C.Structure):
+    """rpt_temporal_report"""
+    _fields_ = [("base", DenoiseReport), ("pixels_with_history", C.c_uint64), ("history_state", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+HISTORY_NONE, HISTORY_USED, HISTORY_DROPPED = 0, 1, 2      # rpt_temporal_report.history_state
+
+
 class NoiseCounts(C.Structure):
     """rpt_noise_counts"""
     _fields_ = [("pixels", C.c_uint64), ("measured", C.c_uint64), ("above", C.c_uint64)]
@@ -89,6 +102,23 @@ def denoise_var_params(**changes):
             setattr(p.base, k, v)
         else:
             raise TypeError(f"rpt_denoise_var_params has no field {k}")
+    return p
+
+
+def temporal_params(**changes):
+    """rpt_temporal_params_default, with the named fields replaced; the fields of rpt_denoise_var_params go into .filter and those of rpt_denoise_params
+    into .filter.base: temporal_params(max_history=16, sigma_variance=4, iterations=3)"""
+    p = TemporalParams()
+    lib().rpt_temporal_params_default(C.byref(p))
+    for k, v in changes.items():
+        if k in ("max_history", "normal_min", "plane_max"):
+            setattr(p, k, v)
+        elif k == "sigma_variance":
+            p.filter.sigma_variance = v
+        elif k in ("iterations", "normal_power_log2", "sigma_color", "sigma_plane", "demodulate"):
+            setattr(p.filter.base, k, v)
+        else:
+            raise TypeError(f"rpt_temporal_params has no field {k}")
     return p
 
 
@@ -171,6 +201,11 @@ PROTOTYPES = {
     "rpt_denoise_var_params_default": (None, [C.POINTER(DenoiseVarParams)]),
     "rpt_denoise_variance": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(DenoiseVarParams), C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(DenoiseReport)]),
     "rpt_multi_denoise_variance": (C.c_int, [C.c_void_p, C.POINTER(DenoiseVarParams), C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(DenoiseReport)]),
+    "rpt_temporal_params_default": (None, [C.POINTER(TemporalParams)]),
+    "rpt_denoise_temporal": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(TemporalParams), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TemporalReport)]),
+    "rpt_temporal_reset": (C.c_int, [C.c_void_p]),
+    "rpt_multi_denoise_temporal": (C.c_int, [C.c_void_p, C.POINTER(TemporalParams), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TemporalReport)]),
+    "rpt_multi_temporal_reset": (C.c_int, [C.c_void_p]),
     "rpt_render_pixels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "rpt_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(NoiseTarget), C.POINTER(AdaptiveResult)]),
     "rpt_counts_uniform": (C.c_int, [C.c_void_p, _OUT_U32]),
@@ -190,6 +225,8 @@ PROTOTYPES = {
     "rpt_debug_comm_selftest": (C.c_int, [C.c_void_p, C.c_uint32, _OUT_U64]),
     "rpt_debug_denoise_host": (C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 6 + [C.POINTER(DenoiseParams), C.c_uint32, C.c_void_p]),
     "rpt_debug_denoise_variance_host": (C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 7 + [C.POINTER(DenoiseVarParams), C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rpt_debug_denoise_temporal_host": (C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 7 + [C.POINTER(TracingConfig), C.POINTER(TracingConfig)] + [C.c_void_p] * 4
+                                        + [C.POINTER(TemporalParams), C.c_uint32] + [C.c_void_p] * 4 + [_OUT_U64]),
     "rpt_debug_noise_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.POINTER(NoiseCounts)]),
     "rpt_debug_adaptive_select_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, _OUT_SIZE]),
     "rpt_debug_short_batch": (C.c_int, [C.c_void_p, C.c_int]),
@@ -308,6 +345,17 @@ class _Handle:
         out, var, rep = self._image(3), self._image(), DenoiseReport()
         self._call("denoise_variance", *source, None if params is None else C.byref(params), tonemap_op, ptr(out), ptr(var), C.byref(rep))
         return (out, var, _report_dict(rep)) if with_report else (out, var)
+
+    def _denoise_temporal(self, source, params, tonemap_op, with_report):
+        """source: what rpt_denoise_temporal takes between the handle and params, as a tuple (rpt_multi_denoise_temporal: nothing)"""
+        out, var, hist, rep = self._image(3), self._image(), self._image(), TemporalReport()
+        self._call("denoise_temporal", *source, None if params is None else C.byref(params), tonemap_op, ptr(out), ptr(var), ptr(hist), C.byref(rep))
+        report = dict(_report_dict(rep.base), pixels_with_history=rep.pixels_with_history, history_state=rep.history_state)
+        return (out, var, hist, report) if with_report else (out, var, hist)
+
+    def temporal_reset(self):
+        """rpt_temporal_reset (rpt_multi_: on rank 0, where it lives): forget and free the history of denoise_temporal"""
+        self._call("temporal_reset")
 
     def set_shadow_mode(self, mode):
         """rpt_set_shadow_mode (rpt_multi_: on every rank): SHADOW_EXACT (default: the reference's any-hit walk, bit for bit) or SHADOW_SEGMENT (boxes that begin
@@ -438,6 +486,15 @@ class Renderer(_Handle):
             moments = np.ascontiguousarray(moments, np.float32)
             assert moments.shape == (self.config.height, self.config.width, 4)
         return self._denoise_variance((source, ptr(moments)), params, tonemap_op, with_report)
+
+    def denoise_temporal(self, source=DENOISE_ACCUM, moments=None, params=None, tonemap_op=0, with_report=False):
+        """rpt_denoise_temporal: denoise_variance() with the previous view's history reprojected and blended in front of the passes (params:
+        temporal_params(), None: the defaults; moments as denoise_variance).  Returns (rgb (H, W, 3), variance (H, W), history (H, W): the blended sample
+        count T of every pixel)[, report: that of denoise() and {"pixels_with_history", "history_state": HISTORY_NONE / USED / DROPPED}]."""
+        if moments is not None:
+            moments = np.ascontiguousarray(moments, np.float32)
+            assert moments.shape == (self.config.height, self.config.width, 4)
+        return self._denoise_temporal((source, ptr(moments)), params, tonemap_op, with_report)
 
     def guides(self):
         """rpt_read_guides: the first-hit guide buffers of the current scene and camera:
@@ -683,6 +740,14 @@ class MultiRenderer(_Handle):
         """rpt_multi_denoise_variance: the ranks' moments merged on the host, the gather of denoise(), the filter on rank 0 (see Renderer.denoise_variance)"""
         return self._denoise_variance((), params, tonemap_op, with_report)
 
+    def denoise_temporal(self, params=None, tonemap_op=0, with_report=False):
+        """rpt_multi_denoise_temporal: as denoise_variance(); the history lives on rank 0 (see Renderer.denoise_temporal)"""
+        return self._denoise_temporal((), params, tonemap_op, with_report)
+
+    def denoise_temporal(self, params=None, tonemap_op=0, with_report=False):
+        """rpt_multi_denoise_temporal: as denoise_variance(); the history lives on rank 0 (see Renderer.denoise_temporal)"""
+        return self._denoise_temporal((), params, tonemap_op, with_report)
+
     def stats(self):
         """rpt_multi_get_stats: the counters summed over the GPUs (no times: rank_view(k).stats() has each GPU's)"""
         s = self._get_stats()
@@ -772,6 +837,32 @@ def denoise_variance_host(mean_rgb, albedo, normal, position, depth, kind, momen
     if rc != 0:
         raise RptError(rc, lib().rpt_last_error(None).decode())
     return out, var
+
+
+def denoise_temporal_host(mean_rgb, albedo, normal, position, depth, kind, moments, camera, previous=None, params=None, tonemap_op=0):
+    """rpt_debug_denoise_temporal_host: Renderer.denoise_temporal run on the host from the same headers (no GPU needed).  The arguments of
+    denoise_variance_host, the current view's TracingConfig, and `previous`: None (no history) or {"camera": TracingConfig, "normal", "position": (H, W, 3),
+    "kind": (H, W), "records": (H, W, 6) — e_h.rgb, N, mu1, mu2}.  Returns {"rgb", "variance", "history" (T), "records" (the new history: feed it to the next
+    view as previous["records"]), "pixels_with_history"}."""
+    mean_rgb = np.ascontiguousarray(mean_rgb, np.float32)
+    h, w = mean_rgb.shape[:2]
+    planes = [np.ascontiguousarray(a, np.float32) for a in (albedo, normal, position, depth)]
+    kind, moments = np.ascontiguousarray(kind, np.uint32), np.ascontiguousarray(moments, np.float32)
+    assert mean_rgb.shape == (h, w, 3) and all(a.shape == (h, w, 3) for a in planes[:3]) and planes[3].shape == (h, w) and kind.shape == (h, w) and moments.shape == (h, w, 4)
+    prev = [None] * 5
+    if previous is not None:
+        prev = [C.byref(previous["camera"]), np.ascontiguousarray(previous["normal"], np.float32), np.ascontiguousarray(previous["position"], np.float32),
+                np.ascontiguousarray(previous["kind"], np.uint32), np.ascontiguousarray(previous["records"], np.float32)]
+        assert prev[1].shape == (h, w, 3) and prev[2].shape == (h, w, 3) and prev[3].shape == (h, w) and prev[4].shape == (h, w, 6)
+    out = {"rgb": np.zeros((h, w, 3), np.float32), "variance": np.zeros((h, w), np.float32), "history": np.zeros((h, w), np.float32), "records": np.zeros((h, w, 6), np.float32)}
+    count = C.c_uint64()
+    rc = lib().rpt_debug_denoise_temporal_host(w, h, ptr(mean_rgb), ptr(planes[0]), ptr(planes[1]), ptr(planes[2]), ptr(planes[3]), ptr(kind), ptr(moments), C.byref(camera),
+                                               prev[0], *(ptr(a) for a in prev[1:]), None if params is None else C.byref(params), tonemap_op,
+                                               ptr(out["rgb"]), ptr(out["variance"]), ptr(out["history"]), ptr(out["records"]), C.byref(count))
+    if rc != 0:
+        raise RptError(rc, lib().rpt_last_error(None).decode())
+    out["pixels_with_history"] = count.value
+    return out
 
 
 def noise_host(moments, threshold=0.0):

@@ -17,6 +17,15 @@
                                                     rpt_denoise_variance (own record on the device; the term off = the shipped default, and on at sigma_variance 4)
                                                     side by side, same base parameters, guides cached, device events, median of 25 calls; writes
                                                     profiles/r14_denoise_variance.txt, above the notes the file keeps at its foot
+  python tools/denoise_probe.py --quality-temporal [out]   no GPU: a camera path of eight views per scene (100 x 70; 1, 2 and 4 spp per view, the accumulator zeroed at
+                                                    every view as the reference does while the camera moves); rel-L2 of the LAST view against its 1024-spp oracle image
+                                                    for the raw mean, rpt_denoise, rpt_denoise_variance (sigma_variance 8, three passes) and rpt_denoise_temporal over
+                                                    the grid max_history x normal_min x plane_max x sigma_variance x iterations, the history chained through the eight
+                                                    views by rpt_debug_denoise_temporal_host; writes profiles/r15_temporal_quality.txt; its lowest summed ratio is what
+                                                    rpt_temporal_params_default ships
+  python tools/denoise_probe.py --gpu-temporal [out]   one MI355X: per workload the 32-spp batch (moments on), then view A, then a moved view B: device_ms of
+                                                    rpt_denoise_temporal with B's history reprojected beside rpt_denoise_variance with the same filter parameters,
+                                                    guides cached, device events, median of 25 calls; writes profiles/r15_temporal.txt
 """
 import hashlib
 import importlib
@@ -283,6 +292,180 @@ def gpu_variance(out_path):
     print("\n".join(lines))
 
 
+TEMPORAL_GRID = {"max_history": (8.0, 32.0, 128.0, float("inf")), "normal_min": (0.5, 0.9, 0.99), "plane_max": (0.5, 2.0, 8.0), "sigma_variance": (0.0, 2.0, 8.0, 32.0),
+                 "iterations": (2, 3)}
+PATH_VIEWS, PATH_SPP, PATH_SIZE = 8, (1, 2, 4), (100, 70)
+
+
+def path_camera(cfg, k):
+    """view k of the path: the default camera dragged sideways and yawed, a steady 0.05 units and 0.02 rad per view"""
+    c = cfg.copy()
+    c.cam_position[0] += 0.05 * k
+    c.cam_rotation[1] += 0.02 * k
+    return c
+
+
+def quality_temporal(out_path):
+    from oracle_ffi import Oracle
+    import denoise_ref
+    import denoise_var_ref
+    from denoise_ref import QUALITY
+    rpt = importlib.import_module("rust-path-tracer_amd")
+    hip = importlib.import_module("rust-path-tracer_amd.hip")
+    orc = Oracle("rpt_math")
+    F = np.float32
+    W, H = PATH_SIZE
+    paths = []                                           # (scene, nee, spp, [(cfg, mean, guides, moments)] per view, converged mean of the last view)
+    for scene, nee in QUALITY:
+        t0 = time.time()
+        w = rpt.World.from_path(rpt.fixture(scene + ".glb"))
+        sc = orc.scene(w)
+        cfgs = [path_camera(rpt.default_config(W, H, nee=nee), k) for k in range(PATH_VIEWS)]
+        guides = [denoise_ref.guides(w, c, orc, sc) for c in cfgs]
+        for spp in PATH_SPP:
+            rng = rpt.blue_noise_seeds(W, H)
+            views = []
+            for c, g in zip(cfgs, guides):               # every view from a zero accumulator, the rng carried on
+                moments, acc = np.zeros((H, W, 4), F), np.zeros((H, W, 4), F)
+                for _ in range(spp):
+                    smp, rng, _ = orc.trace_cpu(c, sc, rng, 1)
+                    denoise_var_ref.moments_add(moments, smp[..., :3])
+                    acc = (acc + smp).astype(F)
+                views.append((c, (acc[..., :3] / F(spp)).astype(F), g, moments))
+            conv, _, _ = orc.trace_cpu(cfgs[-1], sc, rng, 1024)
+            paths.append((scene, nee, spp, views, (conv[..., :3] / F(1024)).astype(F)))
+        print(f"{scene}: oracle images in {time.time() - t0:.0f} s", flush=True)
+
+    def temporal(path, p):
+        prev = None
+        for c, mean, g, moments in path[3]:
+            out = hip.denoise_temporal_host(mean, g["albedo"], g["normal"], g["position"], g["depth"], g["kind"], moments, c, prev, p, 0)
+            prev = {"camera": c, "normal": g["normal"], "position": g["position"], "kind": g["kind"], "records": out["records"]}
+        return out
+
+    raw = [rel_l2(path[3][-1][1], path[4]) for path in paths]
+    last = lambda path: (path[3][-1][1],) + tuple(path[3][-1][2][k] for k in ("albedo", "normal", "position", "depth", "kind"))
+    plain = [rel_l2(hip.denoise_host(*last(path), None, 0), path[4]) / e for path, e in zip(paths, raw)]
+    vp = hip.denoise_var_params(sigma_variance=8.0, iterations=3)
+    var = [rel_l2(hip.denoise_variance_host(*last(path), path[3][-1][3], vp, 0)[0], path[4]) / e for path, e in zip(paths, raw)]
+    keys = list(TEMPORAL_GRID)
+    rows = []
+    t0 = time.time()
+    for values in itertools.product(*(TEMPORAL_GRID[k] for k in keys)):
+        p = hip.temporal_params(**dict(zip(keys, values)))
+        ratios = [rel_l2(temporal(path, p)["rgb"], path[4]) / e for path, e in zip(paths, raw)]
+        rows.append((sum(ratios), values, ratios))
+    rows.sort(key=lambda r: r[0])
+    print(f"grid of {len(rows)} points in {time.time() - t0:.0f} s", flush=True)
+    names = [f"{path[0]}@{path[2]}" for path in paths]
+    show = lambda ratios: " ".join(f"{r:.3f}" for r in ratios) + f" | {sum(ratios):.3f}"
+    d = hip.temporal_params()
+    shipped = (d.max_history, d.normal_min, d.plane_max, d.filter.sigma_variance, d.filter.base.iterations)
+    hit = [r for r in rows if tuple(float(v) for v in r[1]) == tuple(float(v) for v in shipped)]
+    with_history = [temporal(path, hip.temporal_params(**dict(zip(keys, rows[0][1]))))["pixels_with_history"] for path in paths]
+    b = hip.denoise_params()
+    lines = ["Temporal reuse (rpt_denoise_temporal) against converged CPU-oracle images (tools/denoise_probe.py --quality-temporal): a camera path of "
+             f"{PATH_VIEWS} views per scene at {W} x {H},",
+             "0.05 units sideways and 0.02 rad of yaw per view, the accumulator zeroed at every view, the rng carried on; 1, 2 and 4 spp per view (SCENE@spp below).",
+             "rel-L2 of the LAST view against a 1024-spp oracle image of that view; ratio = filtered / raw (< 1: the filter helps).  The history is chained through the",
+             "eight views by rpt_debug_denoise_temporal_host over the numpy guides of tests/denoise_ref.py.  The base parameters that are not in the grid are rpt_denoise's",
+             f"defaults (normal_power_log2 {b.normal_power_log2}, sigma_color {b.sigma_color:g}, sigma_plane {b.sigma_plane:g}, demodulate {b.demodulate}).", "",
+             "columns: " + " ".join(names) + " | sum",
+             "rel-L2 of the raw mean:                          " + " ".join(f"{e:.4f}" for e in raw),
+             "rpt_denoise, defaults:                           " + show(plain),
+             "rpt_denoise_variance, sigma_variance 8, 3 passes: " + show(var),
+             f"rpt_denoise_temporal, lowest summed ratio {dict(zip(keys, rows[0][1]))}: " + show(rows[0][2]),
+             f"    pixels of {W * H} with history in the last view at that point: " + " ".join(str(n) for n in with_history),
+             f"rpt_temporal_params_default {dict(zip(keys, shipped))}: " + (show(hit[0][2]) if hit else "not a grid point"),
+             "best point per sigma_variance:"]
+    for sv in TEMPORAL_GRID["sigma_variance"]:
+        r = [r for r in rows if r[1][3] == sv][0]
+        lines.append(f"  sigma_variance {sv:g}: {dict(zip(keys, r[1]))}  ->  " + show(r[2]))
+    lines += ["", "grid (sorted by the summed ratio): " + " ".join(keys) + " | " + " ".join(names) + " | sum"]
+    for total, values, ratios in rows:
+        lines.append("  " + " ".join(f"{v:g}" for v in values) + " | " + show(ratios))
+    open(out_path, "w").write("\n".join(lines) + "\n")
+    print("\n".join(lines[:20]))
+
+
+def gpu_temporal_child(workload):
+    """rpt_denoise_temporal beside rpt_denoise_variance on one workload, in a process of its own; prints one JSON line"""
+    rpt = importlib.import_module("rust-path-tracer_amd")
+    hip = importlib.import_module("rust-path-tracer_amd.hip")
+    scene, W, H, nee, textured = WORKLOADS[workload]
+    if textured:
+        from scenes import pbrtest_textured_scene
+        made = pbrtest_textured_scene()
+        world = made[0] if isinstance(made, tuple) else made
+    else:
+        world = rpt.World.from_path(rpt.fixture(scene + ".glb"))
+    r = hip.Renderer(0)
+    r.upload_scene(world)
+    cfg_a = rpt.default_config(W, H, nee=nee)
+    cfg_b = path_camera(cfg_a, 4)
+    r.set_config(cfg_a)
+    r.set_moments(True)
+    seeds = rpt.blue_noise_seeds(W, H)
+    out = {"workload": workload, "width": W, "height": H}
+    times = []
+    for _ in range(6):                                   # the first is the warm-up (allocations, clocks); leaves 32 spp of view A and their moments
+        r.reset(seeds)
+        t0 = time.perf_counter()
+        r.render(32)
+        times.append((time.perf_counter() - t0) * 1e3)
+    out["batch_ms"] = float(np.median(times[1:]))
+    d = hip.temporal_params()
+    out["defaults"] = {"max_history": d.max_history, "normal_min": d.normal_min, "plane_max": d.plane_max, "sigma_variance": d.filter.sigma_variance, "iterations": d.filter.base.iterations}
+    on = hip.temporal_params(sigma_variance=4.0)
+    first = r.denoise_temporal(params=d, with_report=True)
+    assert first[3]["pixels_with_history"] == 0
+    plain = r.denoise_variance(params=d.filter)
+    assert np.array_equal(first[0].view(np.uint32), plain[0].view(np.uint32))     # no history: rpt_denoise_variance's bytes
+    r.set_config(cfg_b)
+    r.reset(seeds)
+    r.render(32)
+    median = lambda call: float(np.median([call()[-1]["device_ms"] for _ in range(28)][3:]))
+    digest = hashlib.sha256()
+    for name, p in (("default", d), ("on", on)):
+        got = r.denoise_temporal(params=p, with_report=True)         # every call of this epoch blends with view A's history
+        assert got[3]["history_state"] == 1
+        out[f"with_history_{name}"] = got[3]["pixels_with_history"]
+        digest.update(got[0].tobytes() + got[1].tobytes() + got[2].tobytes())
+        out[f"temporal_ms_{name}"] = median(lambda: r.denoise_temporal(params=p, with_report=True))
+        out[f"variance_ms_{name}"] = median(lambda: r.denoise_variance(params=p.filter, with_report=True))
+    out["output_sha256"] = digest.hexdigest()[:16]
+    r.close()
+    print("RESULT " + json.dumps(out), flush=True)
+
+
+def gpu_temporal(out_path):
+    results = []
+    for workload in WORKLOADS:
+        run = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload-temporal", workload], capture_output=True, text=True, timeout=300)
+        line = [l for l in run.stdout.splitlines() if l.startswith("RESULT ")]
+        if run.returncode != 0 or not line:
+            print(run.stdout[-2000:], run.stderr[-2000:])
+            raise SystemExit(f"{workload} failed with status {run.returncode}: nothing more is started on the GPU")
+        results.append(json.loads(line[0][7:]))
+        print(line[0], flush=True)
+    lines = ["rpt_denoise_temporal beside rpt_denoise_variance on one MI355X (tools/denoise_probe.py --gpu-temporal): 32-spp batches with moments on; view A, then view B",
+             "(0.2 units sideways, 0.08 rad of yaw), whose calls reproject A's history; both calls with the same filter parameters and the context's own moments record.",
+             f"shipped defaults {json.dumps(results[0]['defaults'])}; 'term on': the same with sigma_variance 4.",
+             "device_ms: HIP events around the fused temporal kernel (or the pre-pass), the two guide copies and the passes, guides cached, median of 25 calls after 3 warm-up",
+             "calls; batch: host clock around rpt_render(32), median of 5 after a warm-up.", ""]
+    worst = 0.0
+    for res in results:
+        lines.append(f"{res['workload']} {res['width']}x{res['height']}: batch {res['batch_ms']:.2f} ms; output sha256 {res['output_sha256']}")
+        for name, label in (("default", "defaults"), ("on", "term on ")):
+            t, v = res[f"temporal_ms_{name}"], res[f"variance_ms_{name}"]
+            lines.append(f"    {label}: rpt_denoise_variance {v:.3f} ms | rpt_denoise_temporal {t:.3f} ms ({t / v:.2f} x) = {100 * t / res['batch_ms']:.1f} % of the batch; "
+                         f"{res[f'with_history_{name}']} of {res['width'] * res['height']} pixels with history")
+            worst = max(worst, t / res["batch_ms"])
+    lines += ["", f"condition (rpt_denoise_temporal, guides cached, < the 32-spp batch it follows): worst share {100 * worst:.1f} % -> {'HELD' if worst < 1 else 'MISSED'}"]
+    open(out_path, "w").write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
 MAPPING_RECORD = "wave mapping of a pass"
 
 
@@ -318,7 +501,13 @@ def gpu(out_path):
 
 if __name__ == "__main__":
     a = sys.argv[1:]
-    if "--workload-variance" in a:
+    if "--workload-temporal" in a:
+        gpu_temporal_child(a[a.index("--workload-temporal") + 1])
+    elif a and a[0] == "--gpu-temporal":
+        gpu_temporal(a[1] if len(a) > 1 else os.path.join(ROOT, "profiles", "r15_temporal.txt"))
+    elif a and a[0] == "--quality-temporal":
+        quality_temporal(a[1] if len(a) > 1 else os.path.join(ROOT, "profiles", "r15_temporal_quality.txt"))
+    elif "--workload-variance" in a:
         gpu_variance_child(a[a.index("--workload-variance") + 1])
     elif a and a[0] == "--gpu-variance":
         gpu_variance(a[1] if len(a) > 1 else os.path.join(ROOT, "profiles", "r14_denoise_variance.txt"))
