@@ -46,7 +46,9 @@ RPT_HD float noise_rel(const float4 &m) {
 
 /* The empirical variance of the pixel's MEAN luminance (the square of noise_rel's standard error, in radiance units): max(0, sum(Y^2) - sum(Y)^2 / n) /
  * (n (n - 1)), the operations of noise_rel's `ss` and `v` lines in their order.  +inf — "unknown" — for a record that is not measured or whose sums are
- * not finite; a known variance is finite and >= 0 (mo_variance_known).  What rpt_denoise_variance filters by (k_denoise.h). */
+ * not finite; a known variance is finite and >= 0 (mo_variance_known).  What rpt_denoise_variance filters by (k_denoise.h).
+ * The one-pass difference cancels where a pixel's few samples nearly agree, so RELATIVELY the result can be off by anything there; absolutely it stays within
+ * 2 * 2^-24 * sum(Y^2) / (n (n - 1)) + 2 * 2^-24 * v of the exact value for the record (tests/denoise_f64_cases.py derives it; 1.4 is the largest measured). */
 RPT_HD float mo_variance_of_mean(const float4 &m) {
     const float n = m.z;
     if (!mo_measured(m) || !rptm::finiter(m.x) || !rptm::finiter(m.y)) return rptm::u2f(0x7f800000u);

@@ -24,6 +24,9 @@
  *   else                                     e = (N_r e_r + n_cur e_cur) / T,  mu1 = (N_r mu1_r + m.x) / T, mu2 likewise (a record whose m.x or m.y is not finite adds 0),
  *                                            v = max(0, mu2 - mu1 mu1) / (T - 1), known iff T >= 2 and mu1, mu2 are finite, else +inf; divided by Ya^2 where demodulated
  * The new history record is (e | T), (mu1, mu2); N = 0 instead of T where e is not finite.
+ * No rule guards the COUNT: a record whose m.z is NaN or infinite (no render writes one; a caller's moments image can hold one) gives T = N_r + m.z and with
+ * it a blended colour that is NaN although e_cur is finite (tests/test_denoise_f64.py shows it).  It leaves N = 0 behind like any colour that is not finite,
+ * so it reaches no later blend; without history such a record gives e = e_cur as ever.
  */
 #ifndef RPT_K_TEMPORAL_H
 #define RPT_K_TEMPORAL_H
