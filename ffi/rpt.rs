@@ -62,7 +62,9 @@ pub struct rpt_denoise_params {
 pub struct rpt_denoise_var_params {
     pub base: rpt_denoise_params,
     pub sigma_variance: f32,      // width of the luminance term in standard errors of the pixel's mean; 0 = term off
-    pub reserved: [u32; 3],
+    pub clamp_scale: f32,         // firefly clamp: the brightest sample held to clamp_scale x the brightest of its window; 0 = clamp off
+    pub clamp_floor: f32,         // ... and to no less than this
+    pub clamp_radius: u32,        // window radius 1..3; read only while clamp_scale != 0
 }
 
 #[repr(C)]
@@ -71,7 +73,7 @@ pub struct rpt_denoise_report {
     pub device_ms: f64,
     pub guides_ms: f64,
     pub guides_rebuilt: u32,
-    pub reserved: u32,
+    pub pixels_clamped: u32,      // pixels the firefly clamp changed; 0 while it is off
 }
 
 #[repr(C)]

@@ -326,7 +326,7 @@ typedef struct rpt_denoise_report {
     double   device_ms;
     double   guides_ms;
     uint32_t guides_rebuilt;
-    uint32_t reserved;
+    uint32_t pixels_clamped;      /* pixels the firefly clamp of rpt_denoise_variance / rpt_denoise_temporal changed; 0 while it is off, and from rpt_denoise */
 } rpt_denoise_report;
 
 enum { RPT_DENOISE_ACCUM = 0, RPT_DENOISE_GATHERED = 1 };
@@ -439,11 +439,42 @@ int rpt_multi_render_to_noise(rpt_multi *m, const rpt_noise_target *target, rpt_
  * return; leaves the accumulator, the rng, the moments, rpt_stats, the shadow mode and the cached guides untouched.
  * rpt_multi_denoise_variance merges the ranks' records on the host as rpt_multi_read_moments does (OFF THE HOT PATH: a read-back and an upload of 16 bytes
  * per pixel on every call), gathers as rpt_multi_denoise does, and filters on rank 0.
- * Defaults: the lowest summed error of the grid of profiles/r14_denoise_variance_quality.txt. */
+ * Defaults: the lowest summed error of the grid of profiles/r14_denoise_variance_quality.txt.
+ *
+ * FIREFLY CLAMP (clamp_scale != 0; csrc/k_firefly.h ff_pixel, DESIGN.md "Denoiser").  The moments record's m.w is the luminance of the pixel's brightest sample.
+ * Before the mean is demodulated, for a pixel p with mean c (radiance), count_p (its own .w while rpt_counts_uniform is 0, else the uniform count) and record m:
+ *     Ya_q = the luminance of max(albedo_q, 0.01) where the passes demodulate, else 1;   b(q) = m_q.w / Ya_q
+ *     B    = the largest b(q) over the taps q != p with |dx|, |dy| <= clamp_radius that are inside the image, of p's kind, hold m_q.z >= 1 and a finite b(q)
+ *     L    = max(clamp_scale * B, clamp_floor) * Ya_p
+ * p is clamped iff there is such a tap, m.z >= 1, m.z == count_p, m.x, m.y, m.w and L are finite, m.x > 0 and m.w > L; then, with w = m.w:
+ *     x' = max(0, (m.x - w) + L),  y' = max(0, (m.y - w * w) + L * L),  rho = min(1, x' / m.x),  c' = c * rho,  m' = (x', y', m.z, L)
+ * and the call runs unchanged on (c', m'): the variance of the mean comes from m', and rpt_denoise_temporal blends — and keeps as history — c' and m', so a
+ * spike is clamped before it can enter the history.  A record that does not count what the accumulator counts (after rpt_reset with accum_init, or a
+ * caller's image with another m.z) is left alone.  rpt_denoise_report.pixels_clamped counts the clamped pixels (one integer atomic per wave).
+ * The accumulator, the rng and the moments record are only read; with clamp_scale == 0 the other two words are ignored, the kernels launched are the ones
+ * launched before the fields existed, and so are the bytes returned.  Plain rpt_denoise has no record and therefore no clamp.
+ * LIMITS: only a pixel's ONE brightest sample is clamped; the removed part is assumed to have the pixel's mean chroma; two adjacent spikes of like size
+ * shield each other; and the clamp is BIASED — it removes energy.  On the 8-spp oracle images, at clamp_scale 2 and clamp_radius 1, it removes 0.4 % (PBRTest),
+ * 1.2 % (VeachMIS with NEE) and 1.4 % (DarkCornell with NEE) of the image's summed radiance, and 13.2 % of DarkCornell without NEE, where almost every lit
+ * sample is rare; at 1 spp on that scene, clamp_scale 1 and clamp_radius 3, it is 61 % (profiles/r16_firefly_quality.txt, "lost").  It relaxes by itself as
+ * samples grow, because the window then sees more of the rare events.  y' cancels where the spike dominated m.y: with u = 2^-24 and e_L the relative error of L
+ * (9u where the passes demodulate, else u) its absolute error is at most D = u w^2 + u |m.y - w^2| + (2 e_L + u) L^2 + u y' — below 3 u w^2 where the spike
+ * dominated and the limit is well below it (|m.y - w^2| <= w^2 / 4, L <= w / 4), up to 21 u w^2 where L is near w — and the variance of the mean is off by up to
+ * D over n (n - 1).
+ * DEFAULTS: the clamp ships OFF in rpt_denoise_var_params_default and rpt_temporal_params_default, so that a call which does not ask for it returns what it
+ * returned before.  The grid of profiles/r16_firefly_quality.txt (rel-L2 against 1024-spp oracle images, four scenes) has its lowest summed ratio at
+ * clamp_scale 2, clamp_radius 1 for rpt_denoise_variance at 8 spp (2.245 against 2.275 with the clamp off: little) and at clamp_scale 1, clamp_radius 3 for
+ * rpt_denoise_temporal over an eight-view path at 1 / 2 / 4 spp (1.555 against 1.818; the scenes with NEE gain most, DarkCornell with NEE at 2 spp 0.085
+ * against 0.169); the defaults carry those radii, so setting clamp_scale alone turns the recommended window on: clamp_scale 2 goes
+ * with rpt_denoise_var_params_default's clamp_radius 1, clamp_scale 1 with rpt_temporal_params_default's clamp_radius 3.
+ * RPT_EINVAL for a clamp_scale or clamp_floor that is negative, NaN or infinite, and for a clamp_radius outside 1..3 while clamp_scale != 0; the context
+ * stays usable. */
 typedef struct rpt_denoise_var_params {
     rpt_denoise_params base;      /* as rpt_denoise */
     float    sigma_variance;      /* width of the luminance term in standard errors; 0 = term off */
-    uint32_t reserved[3];
+    float    clamp_scale;         /* firefly clamp: a pixel's brightest sample is held to clamp_scale x the brightest sample of its window; 0 = clamp off */
+    float    clamp_floor;         /* ... and to no less than this (radiance; demodulated radiance where the passes demodulate) */
+    uint32_t clamp_radius;        /* the window is (2 r + 1)^2 pixels without its centre, r = 1..3; read only while clamp_scale != 0 */
 } rpt_denoise_var_params;
 void rpt_denoise_var_params_default(rpt_denoise_var_params *out);
 int rpt_denoise_variance(rpt_ctx *ctx, uint32_t source, const float *moments_xyzw /* nullable */, const rpt_denoise_var_params *params /* NULL = defaults */,
@@ -481,14 +512,14 @@ int rpt_multi_denoise_variance(rpt_multi *m, const rpt_denoise_var_params *param
  * the shadow mode and the cached guides untouched.
  * Defaults: the lowest summed error of the grid of profiles/r15_temporal_quality.txt. */
 typedef struct rpt_temporal_params {
-    rpt_denoise_var_params filter;   /* the passes: as rpt_denoise_variance */
+    rpt_denoise_var_params filter;   /* the passes, and the firefly clamp in front of the blend: as rpt_denoise_variance */
     float    max_history;            /* cap on the reprojected sample count N_r; 0 = history never used */
     float    normal_min;             /* a history tap joins only if n_p . n_q >= normal_min */
     float    plane_max;              /* ... and |n_p . (x_q - x_p)| / ((2 / width) * t_p) <= plane_max  (footprints) */
     uint32_t reserved[5];
 } rpt_temporal_params;
 typedef struct rpt_temporal_report {
-    rpt_denoise_report base;         /* device_ms includes the temporal kernel */
+    rpt_denoise_report base;         /* device_ms includes the temporal kernel; pixels_clamped as rpt_denoise_variance */
     uint64_t pixels_with_history;    /* pixels whose N_r > 0 */
     uint32_t history_state;          /* 0 none yet, 1 used, 2 dropped by this call (resize / scene / demodulate changed) */
     uint32_t reserved;

@@ -93,6 +93,17 @@ int rpt_debug_denoise_temporal_host(uint32_t width, uint32_t height, const float
                                     const float *prev_history, const rpt_temporal_params *params, uint32_t tonemap_op, float *out_rgb, float *out_variance,
                                     float *out_history, float *out_records, uint64_t *pixels_with_history_out);
 
+/* The firefly clamp of rpt_denoise_variance / rpt_denoise_temporal on the HOST: the same header (csrc/k_firefly.h ff_pixel) in a plain loop — no device needed.
+ * mean_rgb (the mean in radiance units, before any demodulation) and albedo: width*height*3 floats; kind: width*height words; moments_xyzw: width*height
+ * records of 4 floats; counts (nullable): width*height floats, the count every pixel's mean was divided by — NULL: every pixel has (float)samples; the three
+ * clamp parameters of rpt_denoise_var_params; demodulated: what the call would decide (base.iterations != 0 && base.demodulate != 0).  out_rgb: c',
+ * width*height*3 floats; out_moments_xyzw: m', width*height records; out_mask: width*height bytes, 1 = clamped (an unclamped pixel's c and m are copied).
+ * Every output is nullable.  RPT_EINVAL for the parameter values rpt_denoise_variance refuses; clamp_scale == 0 copies the inputs.
+ * rpt_debug_denoise_variance_host and rpt_debug_denoise_temporal_host honour the clamp fields too; they are handed no count and take count_p = m_p.z. */
+int rpt_debug_firefly_host(uint32_t width, uint32_t height, const float *mean_rgb, const float *albedo, const uint32_t *kind, const float *moments_xyzw,
+                           const float *counts, uint32_t samples, float clamp_scale, float clamp_floor, uint32_t clamp_radius, uint32_t demodulated,
+                           float *out_rgb, float *out_moments_xyzw, uint8_t *out_mask);
+
 /* noise_rel and the counts of rpt_noise_count on the HOST: the same header (csrc/k_moments.h) in a plain loop over n moments records (4 floats each: sum Y,
  * sum Y^2, n, max Y) — no device needed.  rel_out (n floats) and counts_out are nullable; counts_out->pixels = n.  RPT_EINVAL for a negative or NaN threshold. */
 int rpt_debug_noise_host(const float *moments_xyzw, size_t n, float threshold, float *rel_out, rpt_noise_counts *counts_out);

@@ -159,6 +159,7 @@ struct DenoiseState {
     DevBuf<float> history_t;              /* W x H: T per pixel, before it leaves the device */
     DevBuf<uint32_t> inverse;             /* W x H: the element of `order` that is row-major pixel i (the fused kernel reads the tile-major accumulator by rows) */
     DevBuf<unsigned long long> with_history;   /* the kernel's count of pixels that reused history */
+    DevBuf<unsigned long long> clamped;   /* the firefly clamp's count of clamped pixels (k_firefly.h; allocated by the first call with the clamp on) */
     bool scene_changed = false;           /* rpt_upload_scene since the last call of rpt_denoise_temporal: that call drops the history */
     bool history_dropped = false;         /* a resize freed a valid history: the next call reports it */
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   /* guides begin / end, filter begin / end (created with the buffers, destroyed by rpt_denoise_release) */

@@ -1,7 +1,7 @@
 /*
  * rpt_denoise.hip — the denoise step behind the C ABI (include/rpt/rpt.h rpt_denoise, rpt_denoise_variance, rpt_read_guides, rpt_denoise_params_default,
  * rpt_denoise_var_params_default, rpt_denoise_temporal, rpt_temporal_reset, rpt_temporal_params_default) and its host builds (rpt_debug.h rpt_debug_denoise_host,
- * rpt_debug_denoise_variance_host, rpt_debug_denoise_temporal_host): the guide buffers of a context — built with the one-ray-per-lane nearest-hit walk the debug hook launches
+ * rpt_debug_denoise_variance_host, rpt_debug_denoise_temporal_host, rpt_debug_firefly_host): the guide buffers of a context — built with the one-ray-per-lane nearest-hit walk the debug hook launches
  * (rpt_launch_trace_debug: LDS or global variant per scene, no new walk instantiated) and a small shading kernel — and the passes of k_denoise.h.
  */
 #include <cstring>
@@ -11,17 +11,22 @@
 #include "k_denoise.h"
 #include "k_adaptive.h"
 #include "k_temporal.h"
+#include "k_firefly.h"
 
 namespace {
 
 /* csrc/k_denoise.h; chosen on converged images of the shipped scenes: profiles/r11_denoise_quality.txt */
 constexpr rpt_denoise_params DN_DEFAULTS = {2u, 0u, 1.0f, 2.0f, 1u, {0u, 0u, 0u}};
 
-/* the grid of profiles/r14_denoise_variance_quality.txt (tools/denoise_probe.py --quality) */
-constexpr rpt_denoise_var_params DN_VAR_DEFAULTS = {DN_DEFAULTS, 0.0f, {0u, 0u, 0u}};
+/* the grid of profiles/r14_denoise_variance_quality.txt (tools/denoise_probe.py --quality-variance).  The firefly clamp ships OFF (clamp_scale 0): a call
+ * that does not ask for it returns what it returned before the fields existed.  clamp_radius is that of the lowest summed ratio of
+ * profiles/r16_firefly_quality.txt (--quality-firefly), which a caller turns on with clamp_scale = 2 */
+constexpr rpt_denoise_var_params DN_VAR_DEFAULTS = {DN_DEFAULTS, 0.0f, 0.0f, 0.0f, 1u};
 
 /* the grid of profiles/r15_temporal_quality.txt (tools/denoise_probe.py --quality-temporal): with a history the variance term pays, so it is on here */
-constexpr rpt_temporal_params TP_DEFAULTS = {{DN_DEFAULTS, 32.0f, {0u, 0u, 0u}}, 8.0f, 0.5f, 0.5f, {0u, 0u, 0u, 0u, 0u}};
+/* (the clamp off, as above; on the eight-view path the lowest summed ratio of profiles/r16_firefly_quality.txt is at this clamp_radius, 3, with clamp_scale = 1 —
+ * not the 2 that goes with DN_VAR_DEFAULTS' radius 1) */
+constexpr rpt_temporal_params TP_DEFAULTS = {{DN_DEFAULTS, 32.0f, 0.0f, 0.0f, 3u}, 8.0f, 0.5f, 0.5f, {0u, 0u, 0u, 0u, 0u}};
 
 int check_params(const rpt_denoise_params &p, uint32_t tonemap_op, std::string &error) {
     if (p.iterations > RPT_DN_MAX_ITERATIONS) { error = "rpt_denoise: iterations must be 0..6"; return RPT_EINVAL; }
@@ -37,6 +42,10 @@ int check_params(const rpt_denoise_params &p, uint32_t tonemap_op, std::string &
 int check_var_params(const rpt_denoise_var_params &p, uint32_t tonemap_op, std::string &error) {
     RPT_TRY(check_params(p.base, tonemap_op, error));
     if (!(p.sigma_variance >= 0.0f)) { error = "rpt_denoise_variance: sigma_variance must be >= 0 (+inf allowed)"; return RPT_EINVAL; }
+    if (!rptm::finiter(p.clamp_scale) || p.clamp_scale < 0.0f) { error = "rpt_denoise_variance: clamp_scale must be finite and >= 0"; return RPT_EINVAL; }
+    if (p.clamp_scale == 0.0f) return RPT_OK;            /* the clamp is off: the other two words are not read */
+    if (!rptm::finiter(p.clamp_floor) || p.clamp_floor < 0.0f) { error = "rpt_denoise_variance: clamp_floor must be finite and >= 0"; return RPT_EINVAL; }
+    if (p.clamp_radius < 1u || p.clamp_radius > RPT_FF_MAX_RADIUS) { error = "rpt_denoise_variance: clamp_radius must be 1..3"; return RPT_EINVAL; }
     return RPT_OK;
 }
 
@@ -224,12 +233,33 @@ void host_var_passes(uint32_t width, uint32_t height, const rpt_denoise_var_para
     }
 }
 
-void fill_report(const DenoiseState &d, bool rebuilt, rpt_denoise_report *report) {
+void fill_report(const DenoiseState &d, bool rebuilt, unsigned long long clamped, rpt_denoise_report *report) {
     float ms = 0.0f;
     *report = rpt_denoise_report{};
+    report->pixels_clamped = (uint32_t)clamped;          /* (an image has at most 2^28 pixels) */
     if (hipEventElapsedTime(&ms, d.ev[2], d.ev[3]) == hipSuccess) report->device_ms = ms;
     if (rebuilt && hipEventElapsedTime(&ms, d.ev[0], d.ev[1]) == hipSuccess) report->guides_ms = ms;
     report->guides_rebuilt = rebuilt ? 1u : 0u;
+}
+
+/* the element of the context's tile-major records that is row-major pixel i, cached on the context (`order` == null — a gathered image — needs none) */
+int ensure_inverse(rpt_ctx *c, const uint32_t *order, uint32_t W, uint32_t n, const char *who) {
+    DenoiseState &d = c->dn;
+    if (!order || d.inverse.n == n) return RPT_OK;       /* (one rank owns every pixel: the context's order is the whole image's) */
+    if (c->pixel_xy_host.size() != n) { c->error = std::string(who) + ": internal error (the pixel order does not cover the image)"; return RPT_EHIP; }
+    std::vector<uint32_t> inverse(n);
+    for (uint32_t i = 0; i < n; ++i) inverse[rpt_pixel_index(c->pixel_xy_host[i], W)] = i;
+    HIP_TRY(c, d.inverse.from_host(inverse.data(), n));
+    return RPT_OK;
+}
+
+/* the firefly clamp of a call (k_firefly.h): its parameters and the images its window reads; the context's own record is tile-major, a caller's row-major */
+FfView ff_view(const DenoiseState &d, const rpt_denoise_var_params &vp, bool demodulated, const float4 *moments, bool moments_tile_major) {
+    return FfView{d.width, d.height, vp.clamp_radius, demodulated ? 1u : 0u, vp.clamp_scale, vp.clamp_floor, moments, moments_tile_major ? d.inverse.p : nullptr, d.g1.p, d.albedo.p};
+}
+int ensure_clamp_counter(rpt_ctx *c) {
+    if (!c->dn.clamped.p) HIP_TRY(c, c->dn.clamped.alloc(1));
+    return RPT_OK;
 }
 
 /* the two cameras of a call into its TpView: the current position, and — prev_ro != null — the previous view's, with the bit-for-bit comparison */
@@ -248,7 +278,7 @@ void rpt_denoise_release(rpt_ctx *c, bool events_too) {
     DenoiseState &d = c->dn;
     d.g0.release(); d.g1.release(); d.albedo.release(); d.ping.release(); d.pong.release(); d.rgb.release(); d.order.release(); d.variance.release(); d.moments_in.release();
     if (d.last.valid || d.previous.valid) d.history_dropped = true;      /* (a resize: the next rpt_denoise_temporal reports it) */
-    d.last.release(); d.previous.release(); d.history_t.release(); d.inverse.release(); d.with_history.release();
+    d.last.release(); d.previous.release(); d.history_t.release(); d.inverse.release(); d.with_history.release(); d.clamped.release();
     d.width = d.height = 0;
     d.guides_valid = false;
     if (events_too)
@@ -326,16 +356,30 @@ int rpt_denoise_variance(rpt_ctx *c, uint32_t source, const float *moments_xyzw,
     const uint32_t row_major = moments_xyzw ? 1u : 0u;
     const bool demodulated = p.iterations != 0u && p.demodulate != 0u;
     const float4 *albedo = demodulated ? d.albedo.p : nullptr;
+    const bool clamp = vp.clamp_scale != 0.0f;
+    if (clamp) {
+        RPT_TRY(ensure_inverse(c, in.order, W, n, "rpt_denoise_variance"));
+        RPT_TRY(ensure_clamp_counter(c));
+    }
     HIP_TRY(c, hipEventRecord(d.ev[2], s));
-    if (in.own_counts) k_dn_prepare_var<true><<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(in.sums, moments, in.order, row_major, n, W, 0.0f, albedo, d.ping.p);
+    if (clamp) {                                         /* k_dn_prepare_var_clamp in place of k_dn_prepare_var */
+        const FfView fv = ff_view(d, vp, demodulated, moments, in.order && !row_major);
+        const uint32_t *inverse = in.order ? d.inverse.p : nullptr;
+        const dim3 grid((W + 63u) / 64u, (H + 3u) / 4u);
+        HIP_TRY(c, hipMemsetAsync(d.clamped.p, 0, sizeof(unsigned long long), s));
+        if (in.own_counts) k_dn_prepare_var_clamp<true><<<grid, 256, 0, s>>>(fv, in.sums, inverse, 0.0f, d.ping.p, d.clamped.p);
+        else k_dn_prepare_var_clamp<false><<<grid, 256, 0, s>>>(fv, in.sums, inverse, (float)in.samples, d.ping.p, d.clamped.p);
+    } else if (in.own_counts) k_dn_prepare_var<true><<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(in.sums, moments, in.order, row_major, n, W, 0.0f, albedo, d.ping.p);
     else k_dn_prepare_var<false><<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(in.sums, moments, in.order, row_major, n, W, (float)in.samples, albedo, d.ping.p);
     launch_var_passes(s, d, vp, demodulated, tonemap_op);
     HIP_TRY(c, hipEventRecord(d.ev[3], s));
     HIP_TRY(c, hipGetLastError());
+    unsigned long long clamped = 0ull;
     HIP_TRY(c, hipMemcpyAsync(out_rgb, d.rgb.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
     if (out_variance) HIP_TRY(c, hipMemcpyAsync(out_variance, d.variance.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (clamp) HIP_TRY(c, hipMemcpyAsync(&clamped, d.clamped.p, sizeof clamped, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
-    if (report) fill_report(d, rebuilt, report);
+    if (report) fill_report(d, rebuilt, clamped, report);
     return RPT_OK;
 }
 
@@ -389,12 +433,9 @@ int rpt_denoise_temporal(rpt_ctx *c, uint32_t source, const float *moments_xyzw,
     if (last.h.n != n) { HIP_TRY(c, last.h.alloc(n)); HIP_TRY(c, last.g0.alloc(n)); HIP_TRY(c, last.g1.alloc(n)); HIP_TRY(c, last.mu.alloc(n)); }
     if (d.history_t.n != n) HIP_TRY(c, d.history_t.alloc(n));
     if (!d.with_history.p) HIP_TRY(c, d.with_history.alloc(1));
-    if (in.order && d.inverse.n != n) {      /* (one rank owns every pixel: the context's order is the whole image's) */
-        if (c->pixel_xy_host.size() != n) { c->error = "rpt_denoise_temporal: internal error (the pixel order does not cover the image)"; return RPT_EHIP; }
-        std::vector<uint32_t> inverse(n);
-        for (uint32_t i = 0; i < n; ++i) inverse[rpt_pixel_index(c->pixel_xy_host[i], W)] = i;
-        HIP_TRY(c, d.inverse.from_host(inverse.data(), n));
-    }
+    RPT_TRY(ensure_inverse(c, in.order, W, n, "rpt_denoise_temporal"));
+    const bool clamp = tp.filter.clamp_scale != 0.0f;
+    if (clamp) RPT_TRY(ensure_clamp_counter(c));
     TpView vw = tp_view(W, H, tp.max_history, tp.normal_min, tp.plane_max);
     tp_set_cameras(vw, c->cfg.c.cam_position, c->cfg.euler, d.previous.valid ? d.previous.ro : nullptr, d.previous.euler);
     const TpPrev pv = d.previous.valid ? TpPrev{d.previous.h.p, d.previous.mu.p, d.previous.g0.p, d.previous.g1.p} : TpPrev{nullptr, nullptr, nullptr, nullptr};
@@ -404,18 +445,24 @@ int rpt_denoise_temporal(rpt_ctx *c, uint32_t source, const float *moments_xyzw,
     last.valid = false;
     HIP_TRY(c, hipEventRecord(d.ev[2], s));
     HIP_TRY(c, hipMemsetAsync(d.with_history.p, 0, sizeof(unsigned long long), s));
-    if (in.own_counts) k_dn_temporal<true><<<grid, 256, 0, s>>>(vw, pv, in.sums, moments, inverse, row_major, 0.0f, d.g0.p, d.g1.p, albedo, d.ping.p, last.h.p, last.mu.p, d.history_t.p, d.with_history.p);
+    if (clamp) {                                         /* k_dn_temporal_clamp in place of k_dn_temporal */
+        const FfView fv = ff_view(d, tp.filter, demodulated, moments, in.order && !row_major);
+        HIP_TRY(c, hipMemsetAsync(d.clamped.p, 0, sizeof(unsigned long long), s));
+        if (in.own_counts) k_dn_temporal_clamp<true><<<grid, 256, 0, s>>>(fv, vw, pv, in.sums, inverse, 0.0f, d.g0.p, d.ping.p, last.h.p, last.mu.p, d.history_t.p, d.with_history.p, d.clamped.p);
+        else k_dn_temporal_clamp<false><<<grid, 256, 0, s>>>(fv, vw, pv, in.sums, inverse, (float)in.samples, d.g0.p, d.ping.p, last.h.p, last.mu.p, d.history_t.p, d.with_history.p, d.clamped.p);
+    } else if (in.own_counts) k_dn_temporal<true><<<grid, 256, 0, s>>>(vw, pv, in.sums, moments, inverse, row_major, 0.0f, d.g0.p, d.g1.p, albedo, d.ping.p, last.h.p, last.mu.p, d.history_t.p, d.with_history.p);
     else k_dn_temporal<false><<<grid, 256, 0, s>>>(vw, pv, in.sums, moments, inverse, row_major, (float)in.samples, d.g0.p, d.g1.p, albedo, d.ping.p, last.h.p, last.mu.p, d.history_t.p, d.with_history.p);
     HIP_TRY(c, hipMemcpyAsync(last.g0.p, d.g0.p, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(last.g1.p, d.g1.p, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, s));
     launch_var_passes(s, d, tp.filter, demodulated, tonemap_op);
     HIP_TRY(c, hipEventRecord(d.ev[3], s));
     HIP_TRY(c, hipGetLastError());
-    unsigned long long with_history = 0ull;
+    unsigned long long with_history = 0ull, clamped = 0ull;
     HIP_TRY(c, hipMemcpyAsync(out_rgb, d.rgb.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
     if (out_variance) HIP_TRY(c, hipMemcpyAsync(out_variance, d.variance.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
     if (out_history) HIP_TRY(c, hipMemcpyAsync(out_history, d.history_t.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(&with_history, d.with_history.p, sizeof with_history, hipMemcpyDeviceToHost, s));
+    if (clamp) HIP_TRY(c, hipMemcpyAsync(&clamped, d.clamped.p, sizeof clamped, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     last.valid = true;
     last.epoch = c->accum_epoch;
@@ -424,7 +471,7 @@ int rpt_denoise_temporal(rpt_ctx *c, uint32_t source, const float *moments_xyzw,
     memcpy(last.euler, c->cfg.euler, sizeof last.euler);
     if (report) {
         *report = rpt_temporal_report{};
-        fill_report(d, rebuilt, &report->base);
+        fill_report(d, rebuilt, clamped, &report->base);
         report->pixels_with_history = with_history;
         report->history_state = state;
     }
@@ -504,15 +551,24 @@ int rpt_debug_denoise_variance_host(uint32_t width, uint32_t height, const float
     if (check_var_params(vp, tonemap_op, error)) { rpt_create_error() = error; return RPT_EINVAL; }
     const size_t n = (size_t)width * height;
     const bool demodulated = p.iterations != 0u && p.demodulate != 0u;
-    std::vector<float4> g0(n), g1(n), a(n), ping(n);
+    std::vector<float4> g0(n), g1(n), a(n), ping(n), mo(n);
     for (size_t i = 0; i < n; ++i) {
         g0[i] = make_float4(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], depth[i]);
         g1[i] = make_float4(position[3 * i], position[3 * i + 1], position[3 * i + 2], rptm::u2f(kind[i]));
         a[i] = make_float4(albedo[3 * i], albedo[3 * i + 1], albedo[3 * i + 2], 0.0f);
+        mo[i] = make_float4(moments_xyzw[4 * i], moments_xyzw[4 * i + 1], moments_xyzw[4 * i + 2], moments_xyzw[4 * i + 3]);
+    }
+    const bool clamp = vp.clamp_scale != 0.0f;
+    const FfView fv{width, height, vp.clamp_radius, demodulated ? 1u : 0u, vp.clamp_scale, vp.clamp_floor, mo.data(), nullptr, g1.data(), a.data()};
+    for (size_t i = 0; i < n; ++i) {
         const F3 al = f3(a[i].x, a[i].y, a[i].z);
         F3 c = f3(mean_rgb[3 * i], mean_rgb[3 * i + 1], mean_rgb[3 * i + 2]);
+        float4 m = mo[i];
+        if (clamp) {                                     /* (the hook is handed no count: the record's own) */
+            const FfOut f = ff_pixel(fv, (uint32_t)(i % width), (uint32_t)(i / width), c, m.z, m);
+            c = f.c; m = f.m;
+        }
         if (demodulated) c = dn_demodulate(c, al);
-        const float4 m = make_float4(moments_xyzw[4 * i], moments_xyzw[4 * i + 1], moments_xyzw[4 * i + 2], moments_xyzw[4 * i + 3]);
         ping[i] = make_float4(c.x, c.y, c.z, dn_prepare_variance(m, demodulated, al));
     }
     host_var_passes(width, height, vp, demodulated, tonemap_op, ping, g0, g1, a, out_rgb, out_variance);
@@ -541,7 +597,7 @@ int rpt_debug_denoise_temporal_host(uint32_t width, uint32_t height, const float
     rpt_camera_matrix(camera->cam_rotation, euler_cur);
     if (prev_camera) rpt_camera_matrix(prev_camera->cam_rotation, euler_prev);
     tp_set_cameras(vw, camera->cam_position, euler_cur, prev_camera ? prev_camera->cam_position : nullptr, euler_prev);
-    std::vector<float4> g0(n), g1(n), a(n), ping(n), ph, pg0, pg1;
+    std::vector<float4> g0(n), g1(n), a(n), ping(n), mo(n), ph, pg0, pg1;
     std::vector<float2> pmu;
     if (prev_camera) {
         ph.resize(n); pg0.resize(n); pg1.resize(n); pmu.resize(n);
@@ -554,16 +610,25 @@ int rpt_debug_denoise_temporal_host(uint32_t width, uint32_t height, const float
     }
     const TpPrev pv = TpPrev{ph.data(), pmu.data(), pg0.data(), pg1.data()};
     uint64_t with_history = 0;
+    for (size_t i = 0; i < n; ++i) {
+        g0[i] = make_float4(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], depth[i]);
+        g1[i] = make_float4(position[3 * i], position[3 * i + 1], position[3 * i + 2], rptm::u2f(kind[i]));
+        a[i] = make_float4(albedo[3 * i], albedo[3 * i + 1], albedo[3 * i + 2], 0.0f);
+        mo[i] = make_float4(moments_xyzw[4 * i], moments_xyzw[4 * i + 1], moments_xyzw[4 * i + 2], moments_xyzw[4 * i + 3]);
+    }
+    const bool clamp = tp.filter.clamp_scale != 0.0f;
+    const FfView fv{width, height, tp.filter.clamp_radius, demodulated ? 1u : 0u, tp.filter.clamp_scale, tp.filter.clamp_floor, mo.data(), nullptr, g1.data(), a.data()};
     for (uint32_t y = 0; y < height; ++y)
         for (uint32_t x = 0; x < width; ++x) {
             const size_t i = (size_t)y * width + x;
-            g0[i] = make_float4(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], depth[i]);
-            g1[i] = make_float4(position[3 * i], position[3 * i + 1], position[3 * i + 2], rptm::u2f(kind[i]));
-            a[i] = make_float4(albedo[3 * i], albedo[3 * i + 1], albedo[3 * i + 2], 0.0f);
             const F3 al = f3(a[i].x, a[i].y, a[i].z);
             F3 c = f3(mean_rgb[3 * i], mean_rgb[3 * i + 1], mean_rgb[3 * i + 2]);
+            float4 m = mo[i];
+            if (clamp) {                                 /* (the hook is handed no count: the record's own) */
+                const FfOut f = ff_pixel(fv, x, y, c, m.z, m);
+                c = f.c; m = f.m;
+            }
             if (demodulated) c = dn_demodulate(c, al);
-            const float4 m = make_float4(moments_xyzw[4 * i], moments_xyzw[4 * i + 1], moments_xyzw[4 * i + 2], moments_xyzw[4 * i + 3]);
             const TpOut o = tp_pixel(vw, pv, x, y, c, m, g0[i], g1[i], demodulated, al);
             ping[i] = make_float4(o.e.x, o.e.y, o.e.z, o.v);
             if (out_history) out_history[i] = o.T;
@@ -575,6 +640,32 @@ int rpt_debug_denoise_temporal_host(uint32_t width, uint32_t height, const float
         }
     if (pixels_with_history_out) *pixels_with_history_out = with_history;
     host_var_passes(width, height, tp.filter, demodulated, tonemap_op, ping, g0, g1, a, out_rgb, out_variance);
+    return RPT_OK;
+}
+
+/* the firefly clamp on the host: the loop in front of k_dn_prepare_var_clamp / k_dn_temporal_clamp, over the same RPT_HD function */
+int rpt_debug_firefly_host(uint32_t width, uint32_t height, const float *mean_rgb, const float *albedo, const uint32_t *kind, const float *moments_xyzw, const float *counts,
+                           uint32_t samples, float clamp_scale, float clamp_floor, uint32_t clamp_radius, uint32_t demodulated, float *out_rgb, float *out_moments_xyzw, uint8_t *out_mask) {
+    if (!mean_rgb || !albedo || !kind || !moments_xyzw || width == 0u || height == 0u || width > 65535u || height > 65535u) return RPT_EINVAL;
+    rpt_denoise_var_params vp = DN_VAR_DEFAULTS;
+    vp.clamp_scale = clamp_scale; vp.clamp_floor = clamp_floor; vp.clamp_radius = clamp_radius;
+    std::string error;
+    if (check_var_params(vp, 0u, error)) { rpt_create_error() = error; return RPT_EINVAL; }
+    const size_t n = (size_t)width * height;
+    std::vector<float4> g1(n), a(n), mo(n);
+    for (size_t i = 0; i < n; ++i) {
+        g1[i] = make_float4(0.0f, 0.0f, 0.0f, rptm::u2f(kind[i]));
+        a[i] = make_float4(albedo[3 * i], albedo[3 * i + 1], albedo[3 * i + 2], 0.0f);
+        mo[i] = make_float4(moments_xyzw[4 * i], moments_xyzw[4 * i + 1], moments_xyzw[4 * i + 2], moments_xyzw[4 * i + 3]);
+    }
+    const FfView fv{width, height, clamp_radius, demodulated != 0u ? 1u : 0u, clamp_scale, clamp_floor, mo.data(), nullptr, g1.data(), a.data()};
+    for (size_t i = 0; i < n; ++i) {
+        FfOut f{f3(mean_rgb[3 * i], mean_rgb[3 * i + 1], mean_rgb[3 * i + 2]), mo[i], false};
+        if (clamp_scale != 0.0f) f = ff_pixel(fv, (uint32_t)(i % width), (uint32_t)(i / width), f.c, counts ? counts[i] : (float)samples, mo[i]);
+        if (out_rgb) { out_rgb[3 * i] = f.c.x; out_rgb[3 * i + 1] = f.c.y; out_rgb[3 * i + 2] = f.c.z; }
+        if (out_moments_xyzw) { out_moments_xyzw[4 * i] = f.m.x; out_moments_xyzw[4 * i + 1] = f.m.y; out_moments_xyzw[4 * i + 2] = f.m.z; out_moments_xyzw[4 * i + 3] = f.m.w; }
+        if (out_mask) out_mask[i] = f.clamped ? 1u : 0u;
+    }
     return RPT_OK;
 }
 

@@ -30,12 +30,12 @@ class DenoiseParams(C.Structure):
 
 class DenoiseVarParams(C.Structure):
     """rpt_denoise_var_params"""
-    _fields_ = [("base", DenoiseParams), ("sigma_variance", C.c_float), ("reserved", C.c_uint32 * 3)]
+    _fields_ = [("base", DenoiseParams), ("sigma_variance", C.c_float), ("clamp_scale", C.c_float), ("clamp_floor", C.c_float), ("clamp_radius", C.c_uint32)]
 
 
 class DenoiseReport(C.Structure):
     """rpt_denoise_report"""
-    _fields_ = [("device_ms", C.c_double), ("guides_ms", C.c_double), ("guides_rebuilt", C.c_uint32), ("reserved", C.c_uint32)]
+    _fields_ = [("device_ms", C.c_double), ("guides_ms", C.c_double), ("guides_rebuilt", C.c_uint32), ("pixels_clamped", C.c_uint32)]
 
 
 class TemporalParams(C.Structure):
@@ -91,13 +91,21 @@ def denoise_params(**changes):
     return p
 
 
+_VAR_FIELDS = ("sigma_variance", "clamp_scale", "clamp_floor", "clamp_radius")
+# The firefly clamp ships off.  The lowest summed ratios of profiles/r16_firefly_quality.txt: denoise_var_params(**FIREFLY_CLAMP_VARIANCE) for
+# rpt_denoise_variance at 8 spp, temporal_params(**FIREFLY_CLAMP_TEMPORAL) for the eight-view path (tests/test_denoise_firefly.py holds them to the kept grid)
+FIREFLY_CLAMP_VARIANCE = {"clamp_scale": 2.0, "clamp_floor": 0.0, "clamp_radius": 1}
+FIREFLY_CLAMP_TEMPORAL = {"clamp_scale": 1.0, "clamp_floor": 0.0, "clamp_radius": 3}
+
+
 def denoise_var_params(**changes):
-    """rpt_denoise_var_params_default, with the named fields replaced; the fields of rpt_denoise_params go into .base: denoise_var_params(sigma_variance=4, iterations=5)"""
+    """rpt_denoise_var_params_default, with the named fields replaced; the fields of rpt_denoise_params go into .base:
+    denoise_var_params(sigma_variance=4, iterations=5, clamp_scale=2, clamp_radius=2)"""
     p = DenoiseVarParams()
     lib().rpt_denoise_var_params_default(C.byref(p))
     for k, v in changes.items():
-        if k == "sigma_variance":
-            p.sigma_variance = v
+        if k in _VAR_FIELDS:
+            setattr(p, k, v)
         elif k in ("iterations", "normal_power_log2", "sigma_color", "sigma_plane", "demodulate"):
             setattr(p.base, k, v)
         else:
@@ -113,8 +121,8 @@ def temporal_params(**changes):
     for k, v in changes.items():
         if k in ("max_history", "normal_min", "plane_max"):
             setattr(p, k, v)
-        elif k == "sigma_variance":
-            p.filter.sigma_variance = v
+        elif k in _VAR_FIELDS:
+            setattr(p.filter, k, v)
         elif k in ("iterations", "normal_power_log2", "sigma_color", "sigma_plane", "demodulate"):
             setattr(p.filter.base, k, v)
         else:
@@ -227,6 +235,7 @@ PROTOTYPES = {
     "rpt_debug_denoise_variance_host": (C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 7 + [C.POINTER(DenoiseVarParams), C.c_uint32, C.c_void_p, C.c_void_p]),
     "rpt_debug_denoise_temporal_host": (C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 7 + [C.POINTER(TracingConfig), C.POINTER(TracingConfig)] + [C.c_void_p] * 4
                                         + [C.POINTER(TemporalParams), C.c_uint32] + [C.c_void_p] * 4 + [_OUT_U64]),
+    "rpt_debug_firefly_host": (C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 5 + [C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.c_uint32] + [C.c_void_p] * 3),
     "rpt_debug_noise_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.POINTER(NoiseCounts)]),
     "rpt_debug_adaptive_select_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, _OUT_SIZE]),
     "rpt_debug_short_batch": (C.c_int, [C.c_void_p, C.c_int]),
@@ -804,7 +813,7 @@ def debug_math_host(op, x, y=None):
 
 
 def _report_dict(rep):
-    return {"device_ms": rep.device_ms, "guides_ms": rep.guides_ms, "guides_rebuilt": rep.guides_rebuilt}
+    return {"device_ms": rep.device_ms, "guides_ms": rep.guides_ms, "guides_rebuilt": rep.guides_rebuilt, "pixels_clamped": rep.pixels_clamped}
 
 
 def denoise_host(mean_rgb, albedo, normal, position, depth, kind, params=None, tonemap_op=0):
@@ -863,6 +872,25 @@ def denoise_temporal_host(mean_rgb, albedo, normal, position, depth, kind, momen
         raise RptError(rc, lib().rpt_last_error(None).decode())
     out["pixels_with_history"] = count.value
     return out
+
+
+def firefly_host(mean_rgb, albedo, kind, moments, counts=None, samples=0, clamp_scale=2.0, clamp_floor=0.0, clamp_radius=2, demodulated=True):
+    """rpt_debug_firefly_host: the firefly clamp of Renderer.denoise_variance / denoise_temporal (csrc/k_firefly.h ff_pixel) on the host from the same header
+    (no GPU needed).  mean_rgb, albedo: (H, W, 3); kind: (H, W); moments: (H, W, 4); counts: (H, W) per-pixel sample counts, or None: every pixel has `samples`.
+    Returns (the clamped mean (H, W, 3), the clamped records (H, W, 4), mask (H, W) uint8: 1 = clamped)."""
+    mean_rgb, albedo = np.ascontiguousarray(mean_rgb, np.float32), np.ascontiguousarray(albedo, np.float32)
+    h, w = mean_rgb.shape[:2]
+    kind, moments = np.ascontiguousarray(kind, np.uint32), np.ascontiguousarray(moments, np.float32)
+    if counts is not None:
+        counts = np.ascontiguousarray(counts, np.float32)
+        assert counts.shape == (h, w)
+    assert mean_rgb.shape == (h, w, 3) and albedo.shape == (h, w, 3) and kind.shape == (h, w) and moments.shape == (h, w, 4)
+    out, rec, mask = np.zeros((h, w, 3), np.float32), np.zeros((h, w, 4), np.float32), np.zeros((h, w), np.uint8)
+    rc = lib().rpt_debug_firefly_host(w, h, ptr(mean_rgb), ptr(albedo), ptr(kind), ptr(moments), ptr(counts), samples, clamp_scale, clamp_floor, clamp_radius,
+                                      1 if demodulated else 0, ptr(out), ptr(rec), ptr(mask))
+    if rc != 0:
+        raise RptError(rc, lib().rpt_last_error(None).decode())
+    return out, rec, mask
 
 
 def noise_host(moments, threshold=0.0):

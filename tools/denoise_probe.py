@@ -26,6 +26,20 @@
   python tools/denoise_probe.py --gpu-temporal [out]   one MI355X: per workload the 32-spp batch (moments on), then view A, then a moved view B: device_ms of
                                                     rpt_denoise_temporal with B's history reprojected beside rpt_denoise_variance with the same filter parameters,
                                                     guides cached, device events, median of 25 calls; writes profiles/r15_temporal.txt
+  python tools/denoise_probe.py --quality-firefly [out]   no GPU: the firefly clamp (csrc/k_firefly.h) over clamp_scale {0, 1, 2, 4, 8} x clamp_radius {1, 2, 3}, clamp_floor 0, on
+                                                    DarkCornell, VeachMIS (nee 1), PBRTest and DarkCornell with nee 1: rpt_denoise_variance at 8 spp (128 x 128; the shipped
+                                                    filter defaults, and sigma_variance 8 with three passes) and the eight-view path of --quality-temporal at 1 / 2 / 4 spp
+                                                    through rpt_denoise_temporal's shipped defaults; rel-L2 ratios against 1024-spp oracle images and the share of the
+                                                    image's summed radiance the clamp removes; writes profiles/r16_firefly_quality.txt; the lowest summed ratio of the
+                                                    first and of the third grid are the recommended settings hip.FIREFLY_CLAMP_VARIANCE / _TEMPORAL (the clamp ships off)
+  python tools/denoise_probe.py --gpu-firefly [out]   one MI355X: per workload the 32-spp batch (moments on), then device_ms of rpt_denoise_variance and of
+                                                    rpt_denoise_temporal (view B with A's history) with the clamp off and on (clamp_scale 2, clamp_radius 1 / 2 / 3),
+                                                    guides cached, device events, median of 25 calls, and pixels_clamped; writes profiles/r16_firefly.txt.  Two more builds
+                                                    of librpt_hip.so can be timed in the same run, each in processes of its own through RPT_HIP_LIB as tools/ab_libs.sh
+                                                    does it: RPT_PARENT_LIB = the parent commit's (git worktree add DIR HEAD~1 && make -C DIR hip, then
+                                                    DIR/rust-path-tracer_amd/lib/librpt_hip.so), whose clamp-off figures are taken between two runs of this build and
+                                                    whose images are compared; RPT_VARIANT_LIB = a build of this commit with another clamp kernel (RPT_VARIANT_NAME
+                                                    names it in the report), whose clamp-on figures are printed beside this build's
 """
 import hashlib
 import importlib
@@ -499,9 +513,252 @@ def gpu(out_path):
     print("\n".join(lines))
 
 
+FIREFLY_GRID = {"clamp_scale": (0.0, 1.0, 2.0, 4.0, 8.0), "clamp_radius": (1, 2, 3)}
+FIREFLY_SCENES = [("DarkCornell", 0), ("VeachMIS", 1), ("PBRTest", 0), ("DarkCornell", 1)]
+
+
+def quality_firefly(out_path):
+    from oracle_ffi import Oracle
+    import denoise_ref
+    import denoise_var_ref
+    rpt = importlib.import_module("rust-path-tracer_amd")
+    hip = importlib.import_module("rust-path-tracer_amd.hip")
+    orc = Oracle("rpt_math")
+    F = np.float32
+    worlds = {}
+    world = lambda name: worlds.setdefault(name, rpt.World.from_path(rpt.fixture(name + ".glb")))
+    keys = list(FIREFLY_GRID)
+    points = list(itertools.product(*(FIREFLY_GRID[k] for k in keys)))
+    planes = lambda g: tuple(g[k] for k in ("albedo", "normal", "position", "depth", "kind"))
+
+    def lost(mean, g, moments, point, demodulated):
+        """the share of the image's summed radiance the clamp removes, and the clamped pixels"""
+        if point[0] == 0.0:
+            return 0.0, 0
+        c, _, mask = hip.firefly_host(mean, g["albedo"], g["kind"], moments, counts=moments[..., 2], clamp_scale=point[0], clamp_floor=0.0, clamp_radius=point[1], demodulated=demodulated)
+        return float(1.0 - c.astype(np.float64).sum() / mean.astype(np.float64).sum()), int(mask.sum())
+
+    # -- rpt_denoise_variance at 8 spp
+    sets = []
+    for scene, nee in FIREFLY_SCENES:
+        t0 = time.time()
+        noisy, conv, g, moments, _ = denoise_var_ref.quality_inputs(rpt, world, orc, scene, nee)
+        sets.append((f"{scene}/nee{nee}", noisy, conv, g, moments, rel_l2(noisy, conv)))
+        print(f"{scene} nee {nee}: oracle images in {time.time() - t0:.0f} s, rel-L2 of the 8-spp mean {sets[-1][5]:.4f}", flush=True)
+    d = hip.denoise_var_params()
+    filters = [("the shipped filter defaults", dict(sigma_variance=d.sigma_variance, iterations=d.base.iterations)),
+               ("the setting for scenes with NEE: sigma_variance 8, three passes", dict(sigma_variance=8.0, iterations=3))]
+    var_tables = []
+    for _, f in filters:
+        rows = []
+        for point in points:
+            p = hip.denoise_var_params(clamp_scale=point[0], clamp_floor=0.0, clamp_radius=point[1], **f)
+            dem = p.base.iterations != 0 and p.base.demodulate != 0
+            ratios = [rel_l2(hip.denoise_variance_host(s[1], *planes(s[3]), s[4], p, 0)[0], s[2]) / s[5] for s in sets]
+            gone = [lost(s[1], s[3], s[4], point, dem) for s in sets]
+            rows.append((sum(ratios), point, ratios, gone))
+        rows.sort(key=lambda r: (r[0], r[1]))
+        var_tables.append(rows)
+    print("variance grids done", flush=True)
+
+    # -- the eight-view path through rpt_denoise_temporal
+    W, H = PATH_SIZE
+    paths = []
+    for scene, nee in FIREFLY_SCENES:
+        t0 = time.time()
+        w = world(scene)
+        sc = orc.scene(w)
+        cfgs = [path_camera(rpt.default_config(W, H, nee=nee), k) for k in range(PATH_VIEWS)]
+        guides = [denoise_ref.guides(w, c, orc, sc) for c in cfgs]
+        for spp in PATH_SPP:
+            rng = rpt.blue_noise_seeds(W, H)
+            views = []
+            for c, g in zip(cfgs, guides):               # every view from a zero accumulator, the rng carried on (as --quality-temporal)
+                moments, acc = np.zeros((H, W, 4), F), np.zeros((H, W, 4), F)
+                for _ in range(spp):
+                    smp, rng, _ = orc.trace_cpu(c, sc, rng, 1)
+                    denoise_var_ref.moments_add(moments, smp[..., :3])
+                    acc = (acc + smp).astype(F)
+                views.append((c, (acc[..., :3] / F(spp)).astype(F), g, moments))
+            conv, _, _ = orc.trace_cpu(cfgs[-1], sc, rng, 1024)
+            paths.append((f"{scene}/nee{nee}@{spp}", views, (conv[..., :3] / F(1024)).astype(F)))
+        print(f"{scene} nee {nee}: path images in {time.time() - t0:.0f} s", flush=True)
+
+    def temporal(path, p):
+        prev = None
+        for c, mean, g, moments in path[1]:
+            out = hip.denoise_temporal_host(mean, *planes(g), moments, c, prev, p, 0)
+            prev = {"camera": c, "normal": g["normal"], "position": g["position"], "kind": g["kind"], "records": out["records"]}
+        return out
+
+    raw = [rel_l2(path[1][-1][1], path[2]) for path in paths]
+    tp_rows = []
+    for point in points:
+        p = hip.temporal_params(clamp_scale=point[0], clamp_floor=0.0, clamp_radius=point[1])
+        dem = p.filter.base.iterations != 0 and p.filter.base.demodulate != 0
+        ratios = [rel_l2(temporal(path, p)["rgb"], path[2]) / e for path, e in zip(paths, raw)]
+        gone = [lost(path[1][-1][1], path[1][-1][2], path[1][-1][3], point, dem) for path in paths]
+        tp_rows.append((sum(ratios), point, ratios, gone))
+    tp_rows.sort(key=lambda r: (r[0], r[1]))
+
+    show = lambda r: " ".join(f"{x:.3f}" for x in r[2]) + f" | {r[0]:.3f} | " + " ".join(f"{100 * g[0]:.1f}%/{g[1]}" for g in r[3])
+    fmt = lambda point: " ".join(f"{v:g}" for v in point)
+    t = hip.temporal_params()
+    lines = ["The firefly clamp (csrc/k_firefly.h; clamp_scale, clamp_floor, clamp_radius of rpt_denoise_var_params) against converged CPU-oracle images",
+             "(tools/denoise_probe.py --quality-firefly): rel-L2 of the filtered image against the oracle's 1024-spp mean, ratio = filtered / raw mean (< 1: the call helps),",
+             "through the host hooks over the numpy guides of tests/denoise_ref.py.  clamp_floor 0 throughout.  clamp_scale 0 = the clamp off (the radius is then not read:",
+             "its three rows are one point).  After the sum: the share of the image's summed radiance that the clamp removes from the raw mean (of the last view, for a path)",
+             "and the number of clamped pixels — the clamp is biased, and this is the bias.", ""]
+    names = [s[0] for s in sets]
+    for (title, f), rows in zip(filters, var_tables):
+        lines += [f"== rpt_denoise_variance, 8 spp, 128 x 128, {title} ({json.dumps(f)})",
+                  "rel-L2 of the 8-spp mean: " + ", ".join(f"{s[0]} {s[5]:.4f}" for s in sets),
+                  f"lowest summed ratio: {dict(zip(keys, rows[0][1]))}",
+                  "grid (sorted by the summed ratio): " + " ".join(keys) + " | " + " ".join(names) + " | sum | lost/pixels per scene"]
+        lines += ["  " + fmt(r[1]) + " | " + show(r) for r in rows] + [""]
+    lines += [f"== rpt_denoise_temporal, the eight-view path of --quality-temporal ({W} x {H}, SCENE@spp), rpt_temporal_params_default's other fields "
+              f"(max_history {t.max_history:g}, normal_min {t.normal_min:g}, plane_max {t.plane_max:g}, sigma_variance {t.filter.sigma_variance:g}, iterations {t.filter.base.iterations})",
+              "rel-L2 of the raw mean of the last view: " + ", ".join(f"{path[0]} {e:.4f}" for path, e in zip(paths, raw)),
+              f"lowest summed ratio: {dict(zip(keys, tp_rows[0][1]))}",
+              "grid (sorted by the summed ratio): " + " ".join(keys) + " | " + " ".join(path[0] for path in paths) + " | sum | lost/pixels per path"]
+    lines += ["  " + fmt(r[1]) + " | " + show(r) for r in tp_rows] + [""]
+    shipped_v, shipped_t = (d.clamp_scale, d.clamp_radius), (t.filter.clamp_scale, t.filter.clamp_radius)
+    lines += ["The clamp ships OFF in both sets of defaults (a call that does not ask for it returns what it returned before the fields existed); the minima above are the",
+              "recommended settings (hip.FIREFLY_CLAMP_VARIANCE, hip.FIREFLY_CLAMP_TEMPORAL), and the defaults carry their clamp_radius:",
+              f"rpt_denoise_var_params_default ships clamp_scale {shipped_v[0]:g} clamp_radius {shipped_v[1]}; the first grid's minimum is {fmt(var_tables[0][0][1])}",
+              f"rpt_temporal_params_default ships clamp_scale {shipped_t[0]:g} clamp_radius {shipped_t[1]}; the third grid's minimum is {fmt(tp_rows[0][1])}",
+              f"for scenes with NEE (second grid) the minimum is {fmt(var_tables[1][0][1])}"]
+    open(out_path, "w").write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
+def gpu_firefly_child(workload):
+    """rpt_denoise_variance and rpt_denoise_temporal with the clamp off and on, on one workload, in a process of its own; prints one JSON line.  With
+    RPT_PROBE_OFF_ONLY set (RPT_HIP_LIB names a build from before the clamp, which does not read the words) only the clamp-off figures are taken."""
+    rpt = importlib.import_module("rust-path-tracer_amd")
+    hip = importlib.import_module("rust-path-tracer_amd.hip")
+    scene, W, H, nee, textured = WORKLOADS[workload]
+    if textured:
+        from scenes import pbrtest_textured_scene
+        made = pbrtest_textured_scene()
+        world = made[0] if isinstance(made, tuple) else made
+    else:
+        world = rpt.World.from_path(rpt.fixture(scene + ".glb"))
+    other = bool(os.environ.get("RPT_PROBE_OFF_ONLY"))
+    r = hip.Renderer(0)
+    r.upload_scene(world)
+    cfg_a = rpt.default_config(W, H, nee=nee)
+    cfg_b = path_camera(cfg_a, 4)
+    r.set_config(cfg_a)
+    r.set_moments(True)
+    seeds = rpt.blue_noise_seeds(W, H)
+    out = {"workload": workload, "width": W, "height": H, "lib": os.environ.get("RPT_HIP_LIB", "")}
+    times = []
+    for _ in range(6):                                   # the first is the warm-up (allocations, clocks); leaves 32 spp of view A and their moments
+        r.reset(seeds)
+        t0 = time.perf_counter()
+        r.render(32)
+        times.append((time.perf_counter() - t0) * 1e3)
+    out["batch_ms"] = float(np.median(times[1:]))
+
+    def median(call):
+        ms = [call()[-1]["device_ms"] for _ in range(28)][3:]
+        return [float(np.median(ms)), float(min(ms)), float(max(ms))]
+    settings = [("off", {})] + ([] if other else [(f"r{k}", dict(clamp_scale=2.0, clamp_radius=k)) for k in (1, 2, 3)])
+    d = hip.temporal_params()
+    r.denoise_temporal(params=d)                         # view A's history
+    r.set_config(cfg_b)
+    r.reset(seeds)
+    r.render(32)
+    digest = hashlib.sha256()
+    for name, fields in settings:
+        vp, tp = hip.denoise_var_params(**fields), hip.temporal_params(**fields)
+        v, t = r.denoise_variance(params=vp, with_report=True), r.denoise_temporal(params=tp, with_report=True)
+        assert t[3]["history_state"] == 1
+        if name == "off":
+            digest.update(v[0].tobytes() + v[1].tobytes() + t[0].tobytes() + t[1].tobytes() + t[2].tobytes())
+        if not other:
+            out[f"clamped_{name}"] = [v[2]["pixels_clamped"], t[3]["pixels_clamped"]]
+        out[f"variance_ms_{name}"] = median(lambda: r.denoise_variance(params=vp, with_report=True))
+        out[f"temporal_ms_{name}"] = median(lambda: r.denoise_temporal(params=tp, with_report=True))
+    out["off_sha256"] = digest.hexdigest()[:16]           # of the clamp-off images: two builds that filter alike print the same
+    r.close()
+    print("RESULT " + json.dumps(out), flush=True)
+
+
+VARIANT_NAME = os.environ.get("RPT_VARIANT_NAME", "RPT_VARIANT_LIB")
+
+
+def gpu_firefly(out_path, parent_lib, variant_lib):
+    def child(workload, lib, off_only=False):
+        env = dict(os.environ)
+        env.pop("RPT_HIP_LIB", None)
+        env.pop("RPT_PROBE_OFF_ONLY", None)
+        if lib:
+            env["RPT_HIP_LIB"] = lib
+        if off_only:
+            env["RPT_PROBE_OFF_ONLY"] = "1"
+        run = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload-firefly", workload], capture_output=True, text=True, timeout=300, env=env)
+        line = [l for l in run.stdout.splitlines() if l.startswith("RESULT ")]
+        if run.returncode != 0 or not line:
+            print(run.stdout[-2000:], run.stderr[-2000:])
+            raise SystemExit(f"{workload} failed with status {run.returncode}: nothing more is started on the GPU")
+        print(line[0], flush=True)
+        return json.loads(line[0][7:])
+    f3 = lambda m: f"{m[0]:.3f} ms (min {m[1]:.3f}, max {m[2]:.3f})"
+    lines = ["The firefly clamp on one MI355X (tools/denoise_probe.py --gpu-firefly): 32-spp batches with moments on; view A, then view B (0.2 units sideways, 0.08 rad of yaw),",
+             "whose rpt_denoise_temporal calls reproject A's history.  The shipped defaults of both calls but for the clamp: off, and clamp_scale 2 at clamp_radius 1 / 2 / 3",
+             "(k_dn_prepare_var_clamp / k_dn_temporal_clamp in place of k_dn_prepare_var / k_dn_temporal; each workgroup stages the (b, kind) of its 64 x 4 pixels and their halo in LDS).",
+             "device_ms: HIP events around pre-pass (or the fused temporal kernel and the two guide copies) + passes, guides cached, median (min, max) of 25 calls after 3 warm-up",
+             "calls; batch: host clock around rpt_render(32), median of 5 after a warm-up; pixels clamped: rpt_denoise_report.pixels_clamped.", ""]
+    worst, inside = 0.0, True
+    for workload in WORKLOADS:
+        first = child(workload, None)
+        parent = child(workload, parent_lib, True) if parent_lib else None
+        variant = child(workload, variant_lib) if variant_lib else None
+        second = child(workload, None) if parent_lib else None
+        n = first["width"] * first["height"]
+        lines.append(f"{workload} {first['width']}x{first['height']}: batch {first['batch_ms']:.2f} ms")
+        for call in ("variance", "temporal"):
+            off = first[f"{call}_ms_off"]
+            lines.append(f"    rpt_denoise_{call}, clamp off: {f3(off)} = {100 * off[0] / first['batch_ms']:.1f} % of the batch")
+            for k in (1, 2, 3):
+                on = first[f"{call}_ms_r{k}"]
+                lines.append(f"        clamp_scale 2 radius {k}: {f3(on)} ({on[0] / off[0]:.2f} x, +{on[0] - off[0]:.3f} ms) = {100 * on[0] / first['batch_ms']:.1f} % of the batch; "
+                             f"{first[f'clamped_r{k}'][call == 'temporal']} of {n} pixels clamped")
+                worst = max(worst, on[0] / first["batch_ms"])
+                if variant:
+                    von = variant[f"{call}_ms_r{k}"]
+                    same = variant[f"clamped_r{k}"] == first[f"clamped_r{k}"]
+                    lines.append(f"            the other build of the window ({VARIANT_NAME}): {f3(von)} ({von[0] / on[0]:.2f} x this build); pixels clamped {'the same' if same else 'DIFFER'}")
+            if parent:
+                a, b, c = off, second[f"{call}_ms_off"], parent[f"{call}_ms_off"]
+                lo, hi = min(a[1], b[1]), max(a[2], b[2])
+                ok = lo <= c[0] <= hi
+                inside = inside and ok and parent["off_sha256"] == first["off_sha256"] == second["off_sha256"]
+                lines.append(f"        clamp off, the parent commit's library in the same run: {f3(c)}; this build again: {f3(b)}; the parent's median is "
+                             f"{'inside' if ok else 'OUTSIDE'} this build's spread [{lo:.3f}, {hi:.3f}]; images sha256 {parent['off_sha256']} / {first['off_sha256']}")
+    lines += ["", f"condition (the whole call with the clamp on, guides cached, < the 32-spp batch it follows): worst share {100 * worst:.1f} % -> {'HELD' if worst < 1 else 'MISSED'}"]
+    if parent_lib:
+        lines.append(f"clamp off against the parent commit's library: {'every median inside the spread of this build, and the same images' if inside else 'NOT everywhere inside the spread (see above)'}")
+    if os.path.exists(out_path):
+        old = open(out_path).read().splitlines()
+        at = [k for k, l in enumerate(old) if l.startswith(FOOT_RECORD)]
+        if at:
+            lines += [""] + old[at[0]:]
+    open(out_path, "w").write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
 if __name__ == "__main__":
     a = sys.argv[1:]
-    if "--workload-temporal" in a:
+    if "--workload-firefly" in a:
+        gpu_firefly_child(a[a.index("--workload-firefly") + 1])
+    elif a and a[0] == "--gpu-firefly":
+        gpu_firefly(a[1] if len(a) > 1 else os.path.join(ROOT, "profiles", "r16_firefly.txt"), os.environ.get("RPT_PARENT_LIB"), os.environ.get("RPT_VARIANT_LIB"))
+    elif a and a[0] == "--quality-firefly":
+        quality_firefly(a[1] if len(a) > 1 else os.path.join(ROOT, "profiles", "r16_firefly_quality.txt"))
+    elif "--workload-temporal" in a:
         gpu_temporal_child(a[a.index("--workload-temporal") + 1])
     elif a and a[0] == "--gpu-temporal":
         gpu_temporal(a[1] if len(a) > 1 else os.path.join(ROOT, "profiles", "r15_temporal.txt"))
