@@ -27,6 +27,7 @@ pub const RPT_SHADOW_EXACT: u32 = 0;
 pub const RPT_SHADOW_SEGMENT: u32 = 1;
 pub const RPT_DENOISE_ACCUM: u32 = 0;
 pub const RPT_DENOISE_GATHERED: u32 = 1;
+pub const RPT_ADAPTIVE_MAX_RADIUS: u32 = 8;
 
 #[repr(C)] pub struct rpt_ctx { _private: [u8; 0] }
 #[repr(C)] pub struct rpt_multi { _private: [u8; 0] }
@@ -187,6 +188,10 @@ extern "C" {
     pub fn rpt_render_pixels(ctx: *mut rpt_ctx, mask: *const u8, n_samples: u32) -> c_int;
     pub fn rpt_render_adaptive(ctx: *mut rpt_ctx, target: *const rpt_noise_target, out: *mut rpt_adaptive_result) -> c_int;
     pub fn rpt_counts_uniform(ctx: *mut rpt_ctx, uniform_out: *mut u32) -> c_int;
+    // adaptive sampling by a pixel's neighbourhood: selected while any pixel within `radius` (0..=RPT_ADAPTIVE_MAX_RADIUS, clipped to its tile) is above the
+    // threshold; radius 0 is rpt_render_adaptive.  rpt_adaptive_mask: the pixels the next pass would render (width*height bytes), nothing rendered
+    pub fn rpt_render_adaptive_window(ctx: *mut rpt_ctx, target: *const rpt_noise_target, radius: u32, out: *mut rpt_adaptive_result) -> c_int;
+    pub fn rpt_adaptive_mask(ctx: *mut rpt_ctx, target: *const rpt_noise_target, radius: u32, mask_out: *mut u8, counts_out: *mut rpt_noise_counts) -> c_int;
     pub fn rpt_get_stats(ctx: *mut rpt_ctx, out: *mut rpt_stats) -> c_int;
     pub fn rpt_destroy(ctx: *mut rpt_ctx);
 
@@ -218,6 +223,8 @@ extern "C" {
     pub fn rpt_multi_render_to_noise(m: *mut rpt_multi, target: *const rpt_noise_target, out: *mut rpt_noise_result) -> c_int;
     pub fn rpt_multi_render_pixels(m: *mut rpt_multi, mask: *const u8, n_samples: u32) -> c_int;       // each rank among its own pixels + the gather
     pub fn rpt_multi_render_adaptive(m: *mut rpt_multi, target: *const rpt_noise_target, out: *mut rpt_adaptive_result) -> c_int;   // above and selected summed over the ranks
+    pub fn rpt_multi_render_adaptive_window(m: *mut rpt_multi, target: *const rpt_noise_target, radius: u32, out: *mut rpt_adaptive_result) -> c_int;
+    pub fn rpt_multi_adaptive_mask(m: *mut rpt_multi, target: *const rpt_noise_target, radius: u32, mask_out: *mut u8, counts_out: *mut rpt_noise_counts) -> c_int;   // masks merged, counts summed
     pub fn rpt_multi_get_stats(m: *mut rpt_multi, out: *mut rpt_stats) -> c_int;
     pub fn rpt_multi_last_error(m: *mut rpt_multi) -> *const c_char;
     pub fn rpt_multi_destroy(m: *mut rpt_multi);

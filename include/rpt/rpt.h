@@ -590,6 +590,40 @@ int rpt_counts_uniform(rpt_ctx *ctx, uint32_t *uniform_out);
 int rpt_multi_render_pixels(rpt_multi *m, const uint8_t *mask, uint32_t n_samples);
 int rpt_multi_render_adaptive(rpt_multi *m, const rpt_noise_target *target, rpt_adaptive_result *out);
 
+/* --- adaptive sampling by a pixel's NEIGHBOURHOOD (no reference equivalent) -----------------------------------------------------------------------------
+ * Opt-in, a second entry point: rpt_render_adaptive, its kernels and its results are what they were.  rpt_render_adaptive stops a pixel as soon as its OWN
+ * empirical noise is at or below the threshold, so a pixel whose samples so far all agree (noise_rel == 0: a dark pixel that has not met the light yet) is
+ * never sampled again.  Here a pixel keeps being sampled while ANY PIXEL OF ITS WINDOW is still noisy.  With m_q the moments record of pixel q:
+ *     above(q)    = !(noise_rel(m_q) <= threshold)                      (an unmeasured record, +inf and a NaN are above)
+ *     fits(p)     = m_p.z + batch_samples <= max_samples
+ *     near(p)     = some q with |x_q - x_p| <= radius and |y_q - y_p| <= radius, inside the image AND inside p's own RPT_TILE x RPT_TILE tile, has above(q)
+ *     selected(p) = near(p) && fits(p)
+ * near(p) counts p itself; fits is applied after the window, so a pixel at the cap is never selected, yet keeps its neighbours selected.  radius 0 is the
+ * rule of rpt_render_adaptive and launches exactly its kernels: rpt_render_adaptive_window(ctx, target, 0, out) IS rpt_render_adaptive, bit for bit and field
+ * for field except ms.  radius 1 .. RPT_ADAPTIVE_MAX_RADIUS: one kernel with a workgroup per owned tile (csrc/k_adaptive.h k_ad_window) writes the flags,
+ * and the ordered compaction, the masked pass and everything stated above for them are unchanged.
+ * THE WINDOW IS CLIPPED TO THE PIXEL'S TILE on purpose: a rank holds the records of its own tiles only, and with the clip the selection — and therefore the
+ * image — does not depend on the partition or on the number of GPUs, as for every other call here.  The price is a SEAM: a quiet pixel on a tile edge does
+ * not see a noisy neighbour across it.
+ * The loop and its stop conditions are rpt_render_adaptive's: counts (pixels / measured / above) are still about each pixel's OWN noise; converged when every
+ * pixel is measured and above <= max_above; done and not converged when nothing is selected; else batch_samples for the selected.  A pass that selects every
+ * owned pixel — with a large radius the common case — runs as the uniform call it amounts to.
+ * A pixel at or below the threshold can be selected again, so THE CLOSED FORM ABOVE HOLDS FOR RADIUS 0 ONLY; the prediction of a pixel's final count for
+ * radius > 0 is a pass-by-pass simulation (tests/adaptive_window_ref.py), which tests/test_gpu_adaptive_window.py holds the device to, word for word.
+ * WHAT THE RULE STILL CANNOT SEE: a whole region (its windows as clipped) in which no pixel has met the light yet — all of it looks converged.  min_samples
+ * stays the answer there, and the bias of stopping on an empirical variance is reduced, not removed.
+ *
+ * rpt_adaptive_mask     the pixels the NEXT pass of that call would render: width*height bytes, row-major, 1 = selected, other ranks' pixels 0; counts_out
+ *                     (nullable) as rpt_noise_count.  Renders nothing, changes nothing; synchronises.  rpt_render_pixels(ctx, that mask, batch_samples)
+ *                     equals one pass, so a host can drive or draw the sampling map itself.  RPT_EINVAL while moments are off.
+ * rpt_multi_*           as rpt_multi_render_adaptive; rpt_multi_adaptive_mask sums the counts over the ranks and merges their masks on the host.
+ * RPT_EINVAL, the context stays usable: everything rpt_render_adaptive refuses, radius > RPT_ADAPTIVE_MAX_RADIUS, a null mask_out. */
+#define RPT_ADAPTIVE_MAX_RADIUS 8
+int rpt_render_adaptive_window(rpt_ctx *ctx, const rpt_noise_target *target, uint32_t radius, rpt_adaptive_result *out);
+int rpt_multi_render_adaptive_window(rpt_multi *m, const rpt_noise_target *target, uint32_t radius, rpt_adaptive_result *out);
+int rpt_adaptive_mask(rpt_ctx *ctx, const rpt_noise_target *target, uint32_t radius, uint8_t *mask_out, rpt_noise_counts *counts_out);
+int rpt_multi_adaptive_mask(rpt_multi *m, const rpt_noise_target *target, uint32_t radius, uint8_t *mask_out, rpt_noise_counts *counts_out);
+
 /* --- scene preparation on the device ---------------------- */
 /* BVHBuilder::new(vertices, indices).sah_samples(n).build()  (reference src/bvh.rs:59-324, the call at
  * src/asset.rs:196) on the GPU: reorders `triangles` in place and writes the node pool exactly as the sequential

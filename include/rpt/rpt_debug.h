@@ -114,6 +114,17 @@ int rpt_debug_noise_host(const float *moments_xyzw, size_t n, float threshold, f
 int rpt_debug_adaptive_select_host(const float *moments_xyzw, size_t n, float threshold, uint32_t batch_samples, uint32_t max_samples, uint8_t *flags_out,
                                    uint32_t *active_out, size_t *n_active_out);
 
+/* The window rule of rpt_render_adaptive_window on the HOST: the same header (csrc/k_adaptive.h: ad_above, ad_dilate_row, ad_dilate_rows, ad_fits) in a plain
+ * loop over every RPT_TILE x RPT_TILE tile of a row-major image of width*height moments records — no device needed.  flags_out: width*height bytes, 1 =
+ * selected.  RPT_EINVAL for a null pointer, a width or height outside 1..65535, a negative or NaN threshold and a radius above RPT_ADAPTIVE_MAX_RADIUS. */
+int rpt_debug_adaptive_window_host(const float *moments_xyzw, uint32_t width, uint32_t height, float threshold, uint32_t batch_samples, uint32_t max_samples,
+                                   uint32_t radius, uint8_t *flags_out);
+
+/* Measuring aid (tools/adaptive_probe.py --gpu-window): the device time of the selection step of rpt_render_adaptive_window alone — HIP events on the context's
+ * stream around the select kernels of one pass, `repeats` times, after one untimed round; ms_out: `repeats` floats.  Renders nothing, the selection is dropped.
+ * Refuses what rpt_adaptive_mask refuses, a null ms_out and repeats == 0. */
+int rpt_debug_adaptive_select_ms(rpt_ctx *ctx, const rpt_noise_target *target, uint32_t radius, uint32_t repeats, float *ms_out);
+
 /* Test aid: the next asynchronous batches of this context enqueue one iteration too few — proves that the completion checks (rpt_wait, the next
  * batch's k_generate_first) notice a sample left in flight instead of losing it. */
 int rpt_debug_short_batch(rpt_ctx *ctx, int on);

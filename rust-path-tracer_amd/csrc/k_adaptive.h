@@ -8,10 +8,13 @@
  * Compaction in ASCENDING pixel order — count per workgroup (ballot + popcount), exclusive scan of the workgroup counts, scatter — so the survivors keep
  * the tile-major order (their 8 x 8 blocks stay together in a wave) and the result does not depend on the order waves arrive in; no atomic-append list.
  * The per-pixel functions are RPT_HD: the host build (rpt_debug_adaptive_select_host) is the same text in a loop.
+ * rpt_render_adaptive_window selects by a pixel's NEIGHBOURHOOD instead (k_ad_window below, one workgroup per owned tile; its per-pixel and per-row pieces
+ * are RPT_HD too: rpt_debug_adaptive_window_host) and feeds the same compaction through the flag bytes.
  */
 #ifndef RPT_K_ADAPTIVE_H
 #define RPT_K_ADAPTIVE_H
 
+#include "../../include/rpt/rpt.h"       /* RPT_TILE */
 #include "k_common.h"
 #include "k_moments.h"
 #include "k_tonemap.h"
@@ -97,6 +100,110 @@ static __global__ __launch_bounds__(RPT_BLOCK) void k_ad_count(Sel sel, uint32_t
         wg_count[blockIdx.x] = total;
     }
 }
+
+/* ---- the window rule of rpt_render_adaptive_window: a pixel is selected while ANY pixel of its window is still noisy ---------------------------------------
+ *   above(q)    = noise_above(noise_rel(m_q), threshold)                 (an unmeasured record, +inf and a NaN are above)
+ *   fits(p)     = m_p.z + batch <= cap
+ *   selected(p) = fits(p) && some q with |x_q - x_p| <= radius, |y_q - y_p| <= radius, inside the image and inside p's OWN RPT_TILE x RPT_TILE tile, is above
+ * radius 0 is adaptive_selected.  The window is clipped to the tile: a rank holds the records of its own tiles only, so the selection does not depend on the
+ * partition.  A tile's `above` mask is RPT_TILE row words of 64 bits (bit x of word y: the pixel at (x, y) from the tile's origin; rows and bits outside the
+ * tile or the image stay 0) and the dilation is integer work on those words: ad_dilate_row across, ad_dilate_rows down.  fits is applied AFTER the dilation:
+ * a pixel at the cap is never selected, yet spreads. */
+static_assert(RPT_TILE == 64 && RPT_WAVE == 64, "a tile row is one 64-bit word, and a wave's ballot is one 8 x 8 block of a full tile");
+
+RPT_HD bool ad_above(const float4 &m, float threshold) { return noise_above(noise_rel(m), threshold); }
+RPT_HD bool ad_fits(const float4 &m, float batch, float cap) { return m.z + batch <= cap; }
+/* OR of the row shifted by -radius .. radius (bits shifted past either end of the word are lost: no wrap) */
+RPT_HD unsigned long long ad_dilate_row(unsigned long long row, uint32_t radius) {
+    unsigned long long h = row;
+    for (uint32_t d = 1u; d <= radius; ++d) h |= (row << d) | (row >> d);
+    return h;
+}
+/* OR of the RPT_TILE words h[] over rows y - radius .. y + radius, clipped to the tile */
+RPT_HD unsigned long long ad_dilate_rows(const unsigned long long *h, uint32_t y, uint32_t radius) {
+    const uint32_t lo = y > radius ? y - radius : 0u, hi = y + radius < RPT_TILE - 1u ? y + radius : RPT_TILE - 1u;
+    unsigned long long v = 0ull;
+    for (uint32_t q = lo; q <= hi; ++q) v |= h[q];
+    return v;
+}
+
+/* an owned tile in the rank's pixel order (rpt_hip.hip rpt_build_tile_table, beside rpt_build_pixel_order): its pixels are the entries first .. first + count - 1 */
+struct AdTile {
+    uint32_t first, count;
+    uint32_t origin;                       /* x | y << 16 of its top left pixel */
+    uint32_t pad;
+};
+
+/* The selection of the window rule: ONE WORKGROUP PER OWNED TILE.  (1) every pixel's `above` bit into the tile's row words in LDS — on a full tile a wave is
+ * one 8 x 8 block and its ballot is eight row bytes, stored as bytes without atomics; a partial tile (right and bottom edge: narrower blocks) goes through
+ * pixel_xy and an LDS atomic OR — together with the counts and the range of m.z that AdNoiseSel::select reduces, which come out the same; (2) 64 lanes
+ * dilate the 64 rows across, then down; (3) every pixel reads its own bit, ANDs fits and writes flags[s].  No scratch, no global atomics but the counts',
+ * 2 x 64 x 8 = 1024 bytes of LDS. */
+static __global__ __launch_bounds__(RPT_BLOCK) void k_ad_window(const AdTile *tiles, const uint32_t *pixel_xy, const float4 *moments, uint32_t n_pixels, float threshold, float batch, float cap,
+                                                                uint32_t radius, uint8_t *flags, AdResult *res) {
+    __shared__ unsigned long long rows[RPT_TILE], wide[RPT_TILE];
+    const AdTile t = tiles[blockIdx.x];
+    const uint32_t tx = t.origin & 0xffffu, ty = t.origin >> 16, lane = threadIdx.x & (RPT_WAVE - 1u);
+    const bool full = t.count == RPT_TILE * RPT_TILE;
+    if (threadIdx.x < RPT_TILE) rows[threadIdx.x] = 0ull;
+    __syncthreads();
+    uint32_t n_in = 0u, n_measured = 0u, n_above = 0u, lo = 0xffffffffu, hi = 0u;
+    for (uint32_t base = 0u; base < t.count; base += RPT_BLOCK) {
+        const uint32_t i = base + threadIdx.x, s = t.first + i;
+        const bool in_range = i < t.count && s < n_pixels;
+        bool measured = false, above = false;
+        if (in_range) {
+            const float4 m = moments[s];
+            measured = mo_measured(m);
+            above = ad_above(m, threshold);
+            const uint32_t z = m.z >= 0.0f ? (uint32_t)m.z : 0u;
+            lo = z < lo ? z : lo;
+            hi = z > hi ? z : hi;
+        }
+        const unsigned long long ma = rpt_ballot(above);
+        n_in += (uint32_t)__popcll(rpt_ballot(in_range));
+        n_measured += (uint32_t)__popcll(rpt_ballot(measured));
+        n_above += (uint32_t)__popcll(rpt_ballot(measured && above));
+        if (full) {
+            const uint32_t block = i / RPT_WAVE, bx = block & 7u, by = block >> 3;                   /* (the wave's 8 x 8 block: rpt_build_pixel_order) */
+            if (lane < 8u) reinterpret_cast<uint8_t *>(rows)[(by * 8u + lane) * 8u + bx] = (uint8_t)(ma >> (8u * lane));
+        } else if (above) {
+            const uint32_t pxy = pixel_xy[s], x = (pxy & 0xffffu) - tx, y = (pxy >> 16) - ty;
+            if (x < RPT_TILE && y < RPT_TILE) atomicOr(&rows[y], 1ull << x);
+        }
+    }
+#pragma unroll
+    for (int d = 1; d < RPT_WAVE; d <<= 1) {
+        const uint32_t olo = (uint32_t)__shfl_xor((int)lo, d, RPT_WAVE), ohi = (uint32_t)__shfl_xor((int)hi, d, RPT_WAVE);
+        lo = olo < lo ? olo : lo;
+        hi = ohi > hi ? ohi : hi;
+    }
+    if (lane == 0u && n_in != 0u) {
+        atomicAdd(&res->pixels, (unsigned long long)n_in);
+        if (n_measured != 0u) atomicAdd(&res->measured, (unsigned long long)n_measured);
+        if (n_above != 0u) atomicAdd(&res->above, (unsigned long long)n_above);
+        atomicMax(&res->z_min_inv, ~lo);
+        atomicMax(&res->z_max, hi);
+    }
+    __syncthreads();
+    if (threadIdx.x < RPT_TILE) wide[threadIdx.x] = ad_dilate_row(rows[threadIdx.x], radius);
+    __syncthreads();
+    if (threadIdx.x < RPT_TILE) rows[threadIdx.x] = ad_dilate_rows(wide, threadIdx.x, radius);
+    __syncthreads();
+    for (uint32_t base = 0u; base < t.count; base += RPT_BLOCK) {
+        const uint32_t i = base + threadIdx.x, s = t.first + i;
+        if (i >= t.count || s >= n_pixels) continue;
+        const uint32_t pxy = pixel_xy[s], x = (pxy & 0xffffu) - tx, y = (pxy >> 16) - ty;
+        const bool near = x < RPT_TILE && y < RPT_TILE && ((rows[y] >> x) & 1ull) != 0ull;
+        flags[s] = near && ad_fits(moments[s], batch, cap) ? 1u : 0u;
+    }
+}
+
+/* source (c): the flag bytes k_ad_window wrote, into the unchanged ordered compaction */
+struct AdFlagSel {
+    const uint8_t *flags;
+    __device__ __forceinline__ bool select(uint32_t s, bool in_range, AdResult *) const { return in_range && flags[s] != 0u; }
+};
 
 /* step 2b: exclusive scan of the workgroup counts by ONE workgroup (a contiguous run of counts per thread, the 256 run sums scanned by thread 0), and their
  * total: n_active.  The counts are few — a workgroup per 256 pixels — and the scan is off the hot path. */

@@ -821,10 +821,10 @@ int rpt_multi_get_stats(rpt_multi *m, rpt_stats *out) {
 namespace {
 
 /* the select enqueued on EVERY rank, then the results read: the ranks' selects overlap, and so do their passes below */
-int multi_select(rpt_multi *m, const uint8_t *mask, const rpt_noise_target *target, rpt_adaptive_selection *sum_out, uint64_t *pixels_out) {
+int multi_select(rpt_multi *m, const uint8_t *mask, const rpt_noise_target *target, uint32_t radius, rpt_adaptive_selection *sum_out, uint64_t *pixels_out) {
     int rc;
     for (rpt_ctx *c : m->ctx)
-        if ((rc = rpt_adaptive_select(c, mask, target))) return multi_fail(m, c, rc);
+        if ((rc = rpt_adaptive_select(c, mask, target, radius))) return multi_fail(m, c, rc);
     rpt_adaptive_selection sum{0u, 0xffffffffu, 0u, rpt_noise_counts{0, 0, 0}};
     uint64_t pixels = 0, active = 0;
     for (rpt_ctx *c : m->ctx) {
@@ -867,22 +867,23 @@ int rpt_multi_render_pixels(rpt_multi *m, const uint8_t *mask, uint32_t n_sample
     if (n_samples == 0u) return RPT_OK;
     rpt_adaptive_selection sel{};
     uint64_t pixels = 0;
-    int rc = multi_select(m, mask, nullptr, &sel, &pixels);
+    int rc = multi_select(m, mask, nullptr, 0u, &sel, &pixels);
     if (rc) return rc;
     if (sel.n_active == 0u) return RPT_OK;
     if ((rc = multi_pass(m, n_samples, sel.n_active == pixels))) return rc;
     return multi_gather(m);
 }
 
-/* rpt_render_adaptive over every rank: above and selected are sums over the ranks; one gather at the end */
-int rpt_multi_render_adaptive(rpt_multi *m, const rpt_noise_target *target, rpt_adaptive_result *out) {
+/* rpt_render_adaptive (radius 0) and rpt_render_adaptive_window over every rank: above and selected are sums over the ranks; one gather at the end */
+static int multi_render_adaptive(rpt_multi *m, const rpt_noise_target *target, uint32_t radius, rpt_adaptive_result *out, const char *name) {
     if (!m || !target || !out) return RPT_EINVAL;
-    int rc = rpt_noise_check_target(*target, m->error, "rpt_multi_render_adaptive");
+    int rc = rpt_noise_check_target(*target, m->error, name);
     if (rc) return rc;
+    if (radius > RPT_ADAPTIVE_MAX_RADIUS) { m->error = std::string(name) + ": radius must be <= RPT_ADAPTIVE_MAX_RADIUS (8)"; return RPT_EINVAL; }
     for (rpt_ctx *c : m->ctx)
-        if (!c->has_scene || !c->has_config || !c->has_state || !c->has_seeds) { m->error = "scene, config and reset must precede rpt_multi_render_adaptive"; return RPT_EINVAL; }
+        if (!c->has_scene || !c->has_config || !c->has_state || !c->has_seeds) { m->error = std::string("scene, config and reset must precede ") + name; return RPT_EINVAL; }
     if ((rc = rpt_multi_set_moments(m, 1u))) return rc;
-    struct Who { rpt_multi *m; bool whole_image; } who{m, true};
+    struct Who { rpt_multi *m; uint32_t radius; bool whole_image; } who{m, radius, true};
     const rpt_adaptive_driver driver = {
         [](void *w, uint32_t n, uint64_t *rendered) {
             rpt_multi *m = static_cast<Who *>(w)->m;
@@ -897,13 +898,49 @@ int rpt_multi_render_adaptive(rpt_multi *m, const rpt_noise_target *target, rpt_
         [](void *w, const rpt_noise_target *t, rpt_adaptive_selection *sel) {
             Who *who = static_cast<Who *>(w);
             uint64_t pixels = 0;
-            int rc = multi_select(who->m, nullptr, t, sel, &pixels);
+            int rc = multi_select(who->m, nullptr, t, who->radius, sel, &pixels);
             who->whole_image = !rc && sel->n_active == pixels;
             return rc;
         },
         [](void *w, uint32_t n) { Who *who = static_cast<Who *>(w); return multi_pass(who->m, n, who->whole_image); }};
     if ((rc = rpt_render_adaptive_with(target, out, driver, &who))) return rc;
     return multi_gather(m);
+}
+
+int rpt_multi_render_adaptive(rpt_multi *m, const rpt_noise_target *target, rpt_adaptive_result *out) { return multi_render_adaptive(m, target, 0u, out, "rpt_multi_render_adaptive"); }
+
+int rpt_multi_render_adaptive_window(rpt_multi *m, const rpt_noise_target *target, uint32_t radius, rpt_adaptive_result *out) {
+    return multi_render_adaptive(m, target, radius, out, "rpt_multi_render_adaptive_window");
+}
+
+/* rpt_adaptive_mask on every rank: the counts summed, the masks merged on the host as rpt_multi_read_moments merges the records (the ranks' pixels are disjoint) */
+int rpt_multi_adaptive_mask(rpt_multi *m, const rpt_noise_target *target, uint32_t radius, uint8_t *mask_out, rpt_noise_counts *counts_out) {
+    if (!m) return RPT_EINVAL;
+    int rc;
+    for (rpt_ctx *c : m->ctx)
+        if ((rc = rpt_adaptive_mask_check(c, target, radius, m->error, "rpt_multi_adaptive_mask"))) return rc;
+    if (!mask_out) { m->error = "rpt_multi_adaptive_mask: null mask_out"; return RPT_EINVAL; }
+    if ((rc = rpt_multi_wait(m))) return rc;
+    rpt_noise_counts sum{};
+    std::vector<uint8_t> one;
+    for (size_t r = 0; r < m->ctx.size(); ++r) {
+        rpt_ctx *c = m->ctx[r];
+        rpt_noise_counts k{};
+        if (r == 0) {                    /* (rank 0's image is the canvas: zeros where it owns nothing) */
+            if ((rc = rpt_adaptive_mask(c, target, radius, mask_out, &k))) return multi_fail(m, c, rc);
+            one.resize((size_t)c->cfg.c.width * c->cfg.c.height);
+        } else {
+            if ((rc = rpt_adaptive_mask(c, target, radius, one.data(), &k))) return multi_fail(m, c, rc);
+            const uint32_t W = c->cfg.c.width;
+            for (uint32_t pxy : c->pixel_xy_host) {
+                const size_t at = rpt_pixel_index(pxy, W);
+                mask_out[at] = one[at];
+            }
+        }
+        sum.pixels += k.pixels; sum.measured += k.measured; sum.above += k.above;
+    }
+    if (counts_out) *counts_out = sum;
+    return RPT_OK;
 }
 
 }  // extern "C"

@@ -187,9 +187,13 @@ struct AdaptiveState {
     DevBuf<uint32_t> active, pixel_xy;    /* the compact arrays: active[i] = the pixel entry i came from, and the copies of its records */
     DevBuf<uint2> rng;
     DevBuf<float4> accum, moments;
+    DevBuf<uint32_t> tiles;               /* the window rule (k_adaptive.h k_ad_window): one AdTile of 4 words per owned tile, rpt_build_tile_table for tiles_key */
+    uint64_t tiles_key = 0;               /* width | height << 16 | rank << 32 | world << 48 the table was built for (0: none) */
+    uint32_t n_tiles = 0;
     uint32_t n_active = 0;                /* of the last selection read (rpt_adaptive_selected): what the next pass gathers */
     void release() {
         mask.release(); flags.release(); wg_count.release(); wg_offset.release(); result.release();
+        tiles.release(); tiles_key = 0; n_tiles = 0;
         active.release(); pixel_xy.release(); rng.release(); accum.release(); moments.release();
     }
 };
@@ -328,6 +332,8 @@ int ensure_slot_state(rpt_ctx *c, size_t n, bool need_shadow, bool need_mis);
 int rpt_idle_all_slots(rpt_ctx *c);
 /* rank-local slot order (rpt_hip.hip) */
 void rpt_build_pixel_order(uint32_t W, uint32_t H, uint32_t rank, uint32_t world, std::vector<uint32_t> &out);
+/* the rank's tiles in that order, four words each — first entry of the order, pixel count, x | y << 16 of the origin, 0 (k_adaptive.h AdTile) */
+void rpt_build_tile_table(uint32_t W, uint32_t H, uint32_t rank, uint32_t world, std::vector<uint32_t> &out);
 /* rpt_comm.hip: called by rpt_hip.hip when the context goes away */
 void rpt_comm_release(rpt_ctx *c);
 /* rpt_comm.hip, for rpt_denoise(RPT_DENOISE_GATHERED): the image of the last gather on rank 0 of a communicator, once that gather has completed, its sample
@@ -342,10 +348,11 @@ int rpt_render_to_noise_with(const rpt_noise_target *target, rpt_noise_result *o
  * batch's length is known).  Counts view->n_pixels x n_samples into rpt_stats.samples and nothing into the context's uniform sample count. */
 int rpt_render_view(rpt_ctx *c, uint32_t n_samples, const PixelView *view);
 /* rpt_adaptive.hip, for the rpt_multi_* forms (rpt_comm.hip): the three steps of a masked pass on one rank, so that several ranks' passes overlap.
- * select: flags, counts and scan enqueued on the context's stream (mask != null: the byte mask; else the selection rule on the moments with `target`);
+ * select: flags, counts and scan enqueued on the context's stream (mask != null: the byte mask; else the selection rule on the moments with `target` —
+ * radius 0: a pixel's own noise, the kernels of rpt_render_adaptive; 1 .. RPT_ADAPTIVE_MAX_RADIUS: the window rule, k_ad_window);
  * selected: waits and reads what was selected; pass: gather what was last read as selected, n_samples through rpt_render_view, scatter back (nothing when nothing was). */
 struct rpt_adaptive_selection { uint32_t n_active, z_min, z_max; rpt_noise_counts counts; };
-int rpt_adaptive_select(rpt_ctx *c, const uint8_t *mask, const rpt_noise_target *target);
+int rpt_adaptive_select(rpt_ctx *c, const uint8_t *mask, const rpt_noise_target *target, uint32_t radius);
 int rpt_adaptive_selected(rpt_ctx *c, bool with_counts, rpt_adaptive_selection *out);
 int rpt_adaptive_pass(rpt_ctx *c, uint32_t n_samples, bool uniform_ok /* a pass that selected every owned pixel may run as the uniform call it is */);
 /* rpt_moments.hip: the refusals of a noise target, named after the entry point `who` */
@@ -356,6 +363,8 @@ struct rpt_adaptive_driver {
     int (*select)(void *who, const rpt_noise_target *target, rpt_adaptive_selection *out);
     int (*pass)(void *who, uint32_t n_samples);
 };
+/* rpt_adaptive.hip, for rpt_multi_adaptive_mask: what rpt_adaptive_mask refuses, named after `who`; and the call itself after the checks */
+int rpt_adaptive_mask_check(rpt_ctx *c, const rpt_noise_target *target, uint32_t radius, std::string &error, const char *who);
 /* rpt_resolve while the counts are non-uniform: every pixel's sum by its own accum.w (its kernel is compiled in rpt_adaptive.hip, so that the code object of
  * rpt_hip.hip — the pipeline's kernels — is the one it was) */
 int rpt_resolve_own(rpt_ctx *c, uint32_t tonemap_op, float *out_rgb);

@@ -71,6 +71,18 @@ void rpt_build_pixel_order(uint32_t W, uint32_t H, uint32_t rank, uint32_t world
     }
 }
 
+/* the tiles of that order, as the window rule of adaptive sampling takes them (k_adaptive.h AdTile): the same walk over the rank's tiles, so the two stay in step */
+void rpt_build_tile_table(uint32_t W, uint32_t H, uint32_t rank, uint32_t world, std::vector<uint32_t> &out) {
+    const uint32_t T = RPT_TILE, tiles_x = (W + T - 1) / T, tiles_y = (H + T - 1) / T;
+    out.clear();
+    uint32_t first = 0;
+    for (uint32_t t = rank; t < tiles_x * tiles_y; t += world) {
+        const uint32_t tx = (t % tiles_x) * T, ty = (t / tiles_x) * T, count = std::min(T, W - tx) * std::min(T, H - ty);
+        out.insert(out.end(), {first, count, tx | (ty << 16), 0u});
+        first += count;
+    }
+}
+
 namespace {
 
 constexpr int LAG = RPT_RING_LAG, RING = RPT_RING;

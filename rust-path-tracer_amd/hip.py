@@ -80,6 +80,11 @@ def _noise_result_dict(res):
     return {"samples_rendered": res.samples_rendered, "converged": res.converged, "counts": _counts_dict(res.counts), "ms": res.ms}
 
 
+def _adaptive_result_dict(res):
+    return {"passes": res.passes, "converged": res.converged, "min_pixel_samples": res.min_pixel_samples, "max_pixel_samples": res.max_pixel_samples,
+            "pixel_samples": res.pixel_samples, "counts": _counts_dict(res.counts), "ms": res.ms}
+
+
 def denoise_params(**changes):
     """rpt_denoise_params_default, with the named fields replaced: denoise_params(iterations=3, demodulate=0)"""
     p = DenoiseParams()
@@ -96,6 +101,10 @@ _VAR_FIELDS = ("sigma_variance", "clamp_scale", "clamp_floor", "clamp_radius")
 # rpt_denoise_variance at 8 spp, temporal_params(**FIREFLY_CLAMP_TEMPORAL) for the eight-view path (tests/test_denoise_firefly.py holds them to the kept grid)
 FIREFLY_CLAMP_VARIANCE = {"clamp_scale": 2.0, "clamp_floor": 0.0, "clamp_radius": 1}
 FIREFLY_CLAMP_TEMPORAL = {"clamp_scale": 1.0, "clamp_floor": 0.0, "clamp_radius": 3}
+# render_adaptive_window: radius 0 .. ADAPTIVE_MAX_RADIUS (RPT_ADAPTIVE_MAX_RADIUS).  ADAPTIVE_WINDOW_RADIUS: the radius with the lowest summed rel-L2 of the grid
+# kept in profiles/r17_adaptive_window_quality.txt (tests/test_adaptive_window.py holds it to that file)
+ADAPTIVE_MAX_RADIUS = 8
+ADAPTIVE_WINDOW_RADIUS = 3
 
 
 def denoise_var_params(**changes):
@@ -219,6 +228,10 @@ PROTOTYPES = {
     "rpt_counts_uniform": (C.c_int, [C.c_void_p, _OUT_U32]),
     "rpt_multi_render_pixels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "rpt_multi_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(NoiseTarget), C.POINTER(AdaptiveResult)]),
+    "rpt_render_adaptive_window": (C.c_int, [C.c_void_p, C.POINTER(NoiseTarget), C.c_uint32, C.POINTER(AdaptiveResult)]),
+    "rpt_multi_render_adaptive_window": (C.c_int, [C.c_void_p, C.POINTER(NoiseTarget), C.c_uint32, C.POINTER(AdaptiveResult)]),
+    "rpt_adaptive_mask": (C.c_int, [C.c_void_p, C.POINTER(NoiseTarget), C.c_uint32, C.c_void_p, C.POINTER(NoiseCounts)]),
+    "rpt_multi_adaptive_mask": (C.c_int, [C.c_void_p, C.POINTER(NoiseTarget), C.c_uint32, C.c_void_p, C.POINTER(NoiseCounts)]),
     "rpt_bvh_build_gpu": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, _OUT_SIZE, _OUT_F64]),
     "rpt_light_table_build_gpu": (C.c_int, [C.c_int] + [C.c_void_p, C.c_size_t] * 4 + [_OUT_SIZE, _OUT_U32, _OUT_F64]),
     "rpt_debug_math": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -238,6 +251,8 @@ PROTOTYPES = {
     "rpt_debug_firefly_host": (C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 5 + [C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.c_uint32] + [C.c_void_p] * 3),
     "rpt_debug_noise_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.POINTER(NoiseCounts)]),
     "rpt_debug_adaptive_select_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, _OUT_SIZE]),
+    "rpt_debug_adaptive_window_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "rpt_debug_adaptive_select_ms": (C.c_int, [C.c_void_p, C.POINTER(NoiseTarget), C.c_uint32, C.c_uint32, C.c_void_p]),
     "rpt_debug_short_batch": (C.c_int, [C.c_void_p, C.c_int]),
 }
 EXPORTS = sorted(PROTOTYPES)
@@ -412,8 +427,22 @@ class _Handle:
         "max_pixel_samples", "pixel_samples", "counts", "ms"}.  Turns moments on and leaves them on."""
         t, res = NoiseTarget(threshold, min_samples, max_samples, batch_samples, max_above), AdaptiveResult()
         self._call("render_adaptive", C.byref(t), C.byref(res))
-        return {"passes": res.passes, "converged": res.converged, "min_pixel_samples": res.min_pixel_samples, "max_pixel_samples": res.max_pixel_samples,
-                "pixel_samples": res.pixel_samples, "counts": _counts_dict(res.counts), "ms": res.ms}
+        return _adaptive_result_dict(res)
+
+    def render_adaptive_window(self, radius, threshold, max_above=0, batch_samples=8, min_samples=8, max_samples=256):
+        """rpt_render_adaptive_window: render_adaptive, but a pixel is selected while ANY pixel within `radius` (0 .. ADAPTIVE_MAX_RADIUS; clipped to the
+        pixel's 64 x 64 tile) is above the threshold, so pixels whose few samples happen to agree are not abandoned beside noisy ones.  radius 0 is
+        render_adaptive.  The same result dictionary; counts are still about each pixel's own noise."""
+        t, res = NoiseTarget(threshold, min_samples, max_samples, batch_samples, max_above), AdaptiveResult()
+        self._call("render_adaptive_window", C.byref(t), radius, C.byref(res))
+        return _adaptive_result_dict(res)
+
+    def adaptive_mask(self, radius, threshold, max_above=0, batch_samples=8, min_samples=8, max_samples=256):
+        """rpt_adaptive_mask (rpt_multi_: the ranks' masks merged, their counts summed): (the pixels the next pass of render_adaptive_window would render as
+        (H, W) uint8, the counts of noise_count).  Renders nothing; render_pixels(mask, batch_samples) is that pass.  Moments must be on."""
+        t, k, mask = NoiseTarget(threshold, min_samples, max_samples, batch_samples, max_above), NoiseCounts(), self._image(dtype=np.uint8)
+        self._call("adaptive_mask", C.byref(t), radius, ptr(mask), C.byref(k))
+        return mask, _counts_dict(k)
 
     def _get_stats(self):
         s = Stats()
@@ -918,6 +947,19 @@ def adaptive_select_host(moments, threshold, batch_samples, max_samples):
     if rc != 0:
         raise RptError(rc, lib().rpt_last_error(None).decode())
     return flags, active[: n.value]
+
+
+def adaptive_window_host(moments, threshold, batch_samples, max_samples, radius):
+    """rpt_debug_adaptive_window_host: the window rule of render_adaptive_window over the row-major records `moments` (H, W, 4), tile by tile, on the host
+    from the same header (no GPU needed): flags (H, W) uint8"""
+    moments = np.ascontiguousarray(moments, np.float32)
+    assert moments.ndim == 3 and moments.shape[-1] == 4
+    h, w = moments.shape[:2]
+    flags = np.zeros((h, w), np.uint8)
+    rc = lib().rpt_debug_adaptive_window_host(ptr(moments), w, h, threshold, batch_samples, max_samples, radius, ptr(flags))
+    if rc != 0:
+        raise RptError(rc, lib().rpt_last_error(None).decode())
+    return flags
 
 
 def light_table_build_gpu(vertices_xyzw, triangles, materials, device=0):

@@ -10,7 +10,16 @@
                                                            parent commit, through RPT_HIP_LIB), the adaptive leg rpt_render_adaptive with the in-tree library.  Reports ms,
                                                            pixel-samples, passes, and the masked passes' Grays/s against the whole-image rate of the same process.
   (--leg uniform|adaptive WORKLOAD: what --gpu starts; prints one line.)
-Output goes to stdout (kept in profiles/r13_adaptive.txt).  There is no fallback: --gpu needs the GPU."""
+  python tools/adaptive_probe.py --cpu-window [--sizes 100x70 200x140]
+                                                           no GPU: the window rule of rpt_render_adaptive_window (a pixel is sampled while any pixel of its window is
+                                                           noisy) for radius 0 .. 3 on DarkCornell without and with NEE and VeachMIS: pixel-samples, passes, pixels stopped
+                                                           at min_samples, energy and rel-L2 against an independent converged image, and a uniform image of equal budget
+                                                           (kept in profiles/r17_adaptive_window_quality.txt; hip.ADAPTIVE_WINDOW_RADIUS is its minimum).
+  python tools/adaptive_probe.py --gpu-window              one MI355X, the same two workloads, one process each under its own `timeout`: the selection step alone at radius
+                                                           0, 1, 3 and 8 (HIP events, median of 25) beside the masked pass it precedes, and rpt_render_adaptive against
+                                                           rpt_render_adaptive_window at the recommended radius (kept in profiles/r17_adaptive_window.txt).
+  (--window-leg WORKLOAD: what --gpu-window starts; prints one line.)
+Output goes to stdout (--cpu, --gpu: kept in profiles/r13_adaptive.txt).  There is no fallback: --gpu and --gpu-window need the GPU."""
 import argparse
 import importlib
 import json
@@ -59,6 +68,62 @@ def cpu():
         print("  pixels per final count: " + ", ".join(f"{int(c)}: {int(p)}" for c, p in zip(counts, pixels)))
 
 
+WINDOW_CONFIGS = (("DarkCornell", 0, 0.2), ("DarkCornell", 1, 0.2), ("VeachMIS", 1, 0.3))
+WINDOW_RADII = (0, 1, 2, 3)
+WINDOW_TARGET = dict(max_above=0, batch_samples=8, min_samples=8, max_samples=128)
+WINDOW_REFERENCE_SAMPLES = 2048
+
+
+def cpu_window(sizes):
+    """what the window rule of rpt_render_adaptive_window buys, from the CPU oracle alone: per configuration and radius the pass-by-pass prediction
+    (tests/adaptive_window_ref.py simulate), its image against an independent converged one — WINDOW_REFERENCE_SAMPLES FURTHER samples of the same sequence,
+    none of which the adaptive image used — and the uniform image of the same budget (the nearest whole sample count)."""
+    from oracle_ffi import Oracle
+    import adaptive_ref as aref
+    import adaptive_window_ref as awr
+    import moments_ref as ref
+    rpt = importlib.import_module("rust-path-tracer_amd")
+    orc = Oracle("rpt_math")
+    t = aref.Target(0.0, **WINDOW_TARGET)
+    print(f"# window rule on the CPU oracle: min {t.min_samples}, batches of {t.batch_samples}, cap {t.max_samples}, max_above {t.max_above}, blue-noise seeds; reference = "
+          f"{WINDOW_REFERENCE_SAMPLES} further samples of the same sequence; energy = summed radiance over the reference's; uniform = every pixel the nearest whole "
+          f"number of samples to the adaptive image's mean")
+    summed = {}
+    for W, H in sizes:
+        for scene, nee, threshold in WINDOW_CONFIGS:
+            cfg = rpt.default_config(W, H, nee=nee)
+            b = ref.SampleBank(orc, cfg, rpt.World.from_path(rpt.fixture(scene + ".glb")), rpt.blue_noise_seeds(W, H))
+            b.need(t.max_samples)
+            want = orc.trace_cpu(cfg, b.scene, b.rng(t.max_samples), WINDOW_REFERENCE_SAMPLES)[0][..., :3].astype(np.float64) / WINDOW_REFERENCE_SAMPLES
+            t.threshold = threshold
+
+            def against(image):
+                image = image.astype(np.float64)
+                return image.sum() / want.sum(), float(np.linalg.norm(image - want) / np.linalg.norm(want))
+
+            print(f"{scene}/nee{nee} {W} x {H} = {W * H} pixels, threshold {threshold:g}")
+            for radius in WINDOW_RADII:
+                sim = awr.simulate(b, t, radius)
+                n = sim["counts_image"]
+                acc = aref.expected_state(b, n)[0]
+                energy, err = against(acc[..., :3] / acc[..., 3:4])
+                spp = sim["pixel_samples"] / (W * H)
+                n_uniform = max(1, int(round(spp)))
+                u_energy, u_err = against(b.accum(n_uniform)[..., :3] / np.float32(n_uniform))
+                print(f"  radius {radius}: {sim['pixel_samples']:9d} pixel-samples ({spp:6.1f} per pixel), {sim['passes']:2d} passes, converged {sim['converged']}, "
+                      f"{int((n == t.min_samples).sum()):6d} pixels stopped at {t.min_samples}, energy {energy:.3f}, rel-L2 {err:.3f} | uniform {n_uniform:3d} spp: energy {u_energy:.3f}, "
+                      f"rel-L2 {u_err:.3f}")
+                sys.stdout.flush()
+                key = (W, H, radius)
+                s = summed.setdefault(key, [0.0, 0.0, 0])
+                s[0] += err; s[1] += u_err; s[2] += sim["pixel_samples"]
+    for W, H in sizes:
+        print(f"grid {W} x {H} (summed over the {len(WINDOW_CONFIGS)} configurations): radius | rel-L2 | rel-L2 of the uniform images of equal budget | pixel-samples")
+        for radius in WINDOW_RADII:
+            s = summed[(W, H, radius)]
+            print(f"{radius} | {s[0]:.4f} | {s[1]:.4f} | {s[2]}")
+
+
 def leg(kind, workload):
     """one leg in this process: {"ms", "pixel_samples", ...} as one JSON line"""
     rpt = importlib.import_module("rust-path-tracer_amd")
@@ -104,6 +169,60 @@ def leg(kind, workload):
     print(json.dumps(out))
 
 
+def window_leg(workload):
+    """one workload in this process, as one JSON line: per radius the selection step alone (HIP events around the select kernels, rpt_debug_adaptive_select_ms:
+    median and least of 25, after 16 uniform samples) beside the masked pass that selection precedes (host clock over render_pixels(its mask, batch) up to
+    the wait), then the whole calls: render_adaptive against render_adaptive_window at the recommended radius, same target, same seeds"""
+    import ctypes as C
+    rpt = importlib.import_module("rust-path-tracer_amd")
+    hip = importlib.import_module("rust-path-tracer_amd.hip")
+    scene, W, H = WORKLOADS[workload]
+    world = rpt.World.from_path(rpt.fixture(scene + ".glb"))
+    cfg, seeds = rpt.default_config(W, H, nee=1), rpt.blue_noise_seeds(W, H)
+    target = dict(GPU_TARGET, max_above=W * H // 100)
+    t = hip.NoiseTarget(target["threshold"], target["min_samples"], target["max_samples"], target["batch_samples"], target["max_above"])
+    out = {"workload": workload, "pixels": W * H, "target": target, "sources": hip.build_fingerprint(), "select": {}}
+    r = hip.Renderer(0)
+    try:
+        r.upload_scene(world)
+        r.set_config(cfg)
+        r.reset(seeds)
+        r.set_moments(True)
+        r.render(target["batch_samples"])                    # warm-up (allocations, clocks)
+        for radius in (0, 1, 3, 8):
+            r.reset(seeds)
+            r.render(target["min_samples"])
+            ms = np.zeros(25, np.float32)
+            r._check(hip.lib().rpt_debug_adaptive_select_ms(r._h, C.byref(t), radius, len(ms), hip.ptr(ms)))
+            mask, counts = r.adaptive_mask(radius, **target)
+            t0 = time.perf_counter()
+            r.render_pixels(mask, target["batch_samples"])
+            r.wait()
+            pass_ms = (time.perf_counter() - t0) * 1e3
+            out["select"][radius] = {"select_ms_median": float(np.median(ms)), "select_ms_min": float(ms.min()), "selected": int(mask.sum()), "above": counts["above"],
+                                     "pass_ms": pass_ms, "select_over_pass": float(np.median(ms)) / pass_ms}
+        for name, call in (("render_adaptive", lambda: r.render_adaptive(**target)),
+                           ("render_adaptive_window", lambda: r.render_adaptive_window(hip.ADAPTIVE_WINDOW_RADIUS, **target))):
+            r.reset(seeds)
+            res = call()
+            out[name] = {k: res[k] for k in ("ms", "pixel_samples", "passes", "converged", "min_pixel_samples", "max_pixel_samples", "counts")}
+        out["radius"] = hip.ADAPTIVE_WINDOW_RADIUS
+    finally:
+        r.close()
+    print(json.dumps(out))
+
+
+def gpu_window(names, limit):
+    print(f"# window rule on the device: target {GPU_TARGET}, max_above = 1 % of the pixels; one process per workload; select = HIP events around the select kernels, "
+          f"radius 0 = the kernels of rpt_render_adaptive (k_ad_count<AdNoiseSel>, k_ad_scan), radius > 0 = k_ad_window, k_ad_count<AdFlagSel>, k_ad_scan")
+    for name in names:
+        done = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--window-leg", name], capture_output=True, text=True)
+        if done.returncode != 0:                             # a leg that failed ends the run: nothing more is started on the GPU
+            sys.exit(f"{name}: exit status {done.returncode}\n{done.stdout}{done.stderr}")
+        print(f"{name}: {done.stdout.strip().splitlines()[-1]}")
+        sys.stdout.flush()
+
+
 def gpu(parent_lib, names, limit):
     if not parent_lib or not os.path.exists(parent_lib):
         sys.exit("--gpu needs --parent-lib: librpt_hip.so built from the parent commit (the uniform leg is measured against it)")
@@ -129,12 +248,22 @@ if __name__ == "__main__":
     ap.add_argument("--workloads", nargs="*", default=list(WORKLOADS))
     ap.add_argument("--timeout", type=int, default=240, help="seconds per leg")
     ap.add_argument("--leg", nargs=2, metavar=("KIND", "WORKLOAD"))
+    ap.add_argument("--cpu-window", action="store_true")
+    ap.add_argument("--gpu-window", action="store_true")
+    ap.add_argument("--sizes", nargs="*", default=["100x70"], help="--cpu-window: image sizes, W x H each")
+    ap.add_argument("--window-leg", metavar="WORKLOAD")
     args = ap.parse_args()
+    if args.window_leg:
+        window_leg(args.window_leg)
     if args.cpu:
         cpu()
+    if args.cpu_window:
+        cpu_window([tuple(int(v) for v in s.split("x")) for s in args.sizes])
+    if args.gpu_window:
+        gpu_window(args.workloads, args.timeout)
     if args.gpu:
         gpu(args.parent_lib, args.workloads, args.timeout)
     if args.leg:
         leg(*args.leg)
-    if not (args.cpu or args.gpu or args.leg):
+    if not (args.cpu or args.gpu or args.leg or args.cpu_window or args.gpu_window or args.window_leg):
         print(__doc__)
