@@ -96,6 +96,18 @@ pub struct rpt_temporal_report {
     pub reserved: u32,
 }
 
+/// rpt_gathered_info_get: what the ranks' trailers said at the last gather (rpt_gather_set_moments)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct rpt_gathered_info {
+    pub with_moments: u32,   // the last gather carried the moments records
+    pub nonuniform: u32,     // OR over the ranks of counts_nonuniform at their snapshot, or samples_min != samples_max
+    pub samples_min: u32,    // of the ranks' uniform sample counts at their snapshot
+    pub samples_max: u32,
+    pub bad_trailers: u32,   // ranks whose trailer did not carry the format word: 0 unless the setting differs between ranks
+    pub reserved: [u32; 3],
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
 pub struct rpt_noise_counts {
@@ -218,7 +230,8 @@ extern "C" {
     pub fn rpt_multi_denoise_temporal(m: *mut rpt_multi, params: *const rpt_temporal_params, tonemap_op: u32, out_rgb: *mut f32, out_variance: *mut f32, out_history: *mut f32, report: *mut rpt_temporal_report) -> c_int;   // the history lives on rank 0
     pub fn rpt_multi_temporal_reset(m: *mut rpt_multi) -> c_int;
     pub fn rpt_multi_set_moments(m: *mut rpt_multi, on: u32) -> c_int;              // rpt_set_moments on every rank
-    pub fn rpt_multi_read_moments(m: *mut rpt_multi, out_xyzw: *mut Vec4) -> c_int; // the ranks' records merged on the host
+    pub fn rpt_multi_read_moments(m: *mut rpt_multi, out_xyzw: *mut Vec4) -> c_int; // the ranks' records merged on the host (or: the gathered record)
+    pub fn rpt_multi_gather_set_moments(m: *mut rpt_multi, on: u32) -> c_int;       // rpt_gather_set_moments on every rank: the multi denoisers use the gathered record
     pub fn rpt_multi_noise_count(m: *mut rpt_multi, threshold: f32, out: *mut rpt_noise_counts) -> c_int;   // summed over the ranks
     pub fn rpt_multi_render_to_noise(m: *mut rpt_multi, target: *const rpt_noise_target, out: *mut rpt_noise_result) -> c_int;
     pub fn rpt_multi_render_pixels(m: *mut rpt_multi, mask: *const u8, n_samples: u32) -> c_int;       // each rank among its own pixels + the gather
@@ -237,6 +250,13 @@ extern "C" {
     pub fn rpt_gather_wait(ctx: *mut rpt_ctx) -> c_int;
     pub fn rpt_read_gathered(ctx: *mut rpt_ctx, out: *mut Vec4, out_samples: *mut u32) -> c_int;   // rank 0
     pub fn rpt_gathered_device_ptr(ctx: *mut rpt_ctx, dev_ptr: *mut *mut c_void) -> c_int;
+    // opt-in, collective: the gather also carries every rank's moments record and count state; then rpt_denoise_variance / rpt_denoise_temporal
+    // (RPT_DENOISE_GATHERED, moments null) on rank 0 filter by the gathered record, and the per-pixel-count decision comes from every rank's trailer
+    pub fn rpt_gather_set_moments(ctx: *mut rpt_ctx, on: u32) -> c_int;             // default 0; needs a communicator; turns moments on
+    pub fn rpt_gather_moments(ctx: *mut rpt_ctx, on_out: *mut u32) -> c_int;
+    pub fn rpt_read_gathered_moments(ctx: *mut rpt_ctx, out_xyzw: *mut Vec4) -> c_int;             // rank 0; width*height, row-major
+    pub fn rpt_gathered_moments_device_ptr(ctx: *mut rpt_ctx, dev_ptr: *mut *mut c_void) -> c_int; // rank 0
+    pub fn rpt_gathered_info_get(ctx: *mut rpt_ctx, out: *mut rpt_gathered_info) -> c_int;         // rank 0, after a gather; waits for it
 
     // --- optional: BVHBuilder::new(&vertices, &mut indices).sah_samples(n).build() on the GPU (asset.rs:196) ------
     pub fn rpt_bvh_build_gpu(device_id: c_int, vertices: *const Vec4, n_vertices: usize, indices: *mut UVec4, n_triangles: usize,

@@ -210,6 +210,50 @@ int rpt_gather_wait(rpt_ctx *ctx);
 int rpt_read_gathered(rpt_ctx *ctx, float *out_rgba, uint32_t *out_samples);
 int rpt_gathered_device_ptr(rpt_ctx *ctx, void **dev_ptr);
 
+/* --- the moments record and the counts flag inside the gather -------------------------------------------------------------------------------------
+ * Opt-in, a second wire format of the same gather: with the setting off (the default) the gather, its bytes and its kernels are what they were.
+ * With it on, a rank's message is its whole slot — [accumulator block][moments record][trailer of four words: a format word, the rank's
+ * counts_nonuniform, its uniform sample count, its pixel count] — in the one ncclSend / ncclRecv per peer of the one group; rank 0 un-tiles both records
+ * (a second row-major width*height float4 image beside the gathered one) and folds the trailers into rpt_gathered_info, all on the gather's stream.
+ * Nothing is allocated, copied from the host or synchronised per gather; batch k + 1 renders while accumulators AND moments of batch k travel.
+ *
+ * rpt_gather_set_moments(ctx, 1)   needs a communicator (rpt_comm_init, rpt_comm_init_local, a context of an rpt_multi), else RPT_EINVAL.  Turns the
+ *                  context's moments on if they are off and leaves them on (as rpt_render_to_noise does), synchronises both streams and re-sizes the
+ *                  gather buffers (zeroed: no uninitialised memory travels).  No gathered image exists afterwards until the next gather, as after a
+ *                  resize.  While it is on, rpt_set_moments(ctx, 0) is refused with RPT_EINVAL (rpt_gather_set_moments(ctx, 0) is the way out): a
+ *                  rank's message length stays a function of (width, height, world, setting) alone.
+ *                  COLLECTIVE, like the configuration and like rpt_gather_async ("every rank must call it, in the same order"): every rank of a
+ *                  communicator must hold the same value at every gather.  rpt_multi_gather_set_moments sets every rank in one call.
+ *                  (ctx, 0) restores the plain format and every refusal of the plain format, word for word.
+ * With the setting on, on rank 0:
+ *   rpt_denoise_variance / rpt_denoise_temporal (RPT_DENOISE_GATHERED, moments_xyzw == NULL) filter by the gathered record, from device memory, on the
+ *                  gather's stream: no host trip.  RPT_EINVAL until a gather has carried moments; a caller's image still takes precedence when given.
+ *   rpt_denoise, rpt_denoise_variance, rpt_denoise_temporal (RPT_DENOISE_GATHERED) divide every pixel by its own .w iff rpt_gathered_info.nonuniform:
+ *                  the decision comes from every rank's trailer, no longer from rank 0's own flag (ranks of a process-per-GPU run are masked
+ *                  differently as a rule: rpt_render_adaptive on each).
+ *   rpt_read_gathered_moments   width*height float4, row-major: what rpt_read_moments of one context that rendered everything returns.
+ *   rpt_gathered_moments_device_ptr   the device image itself, as rpt_gathered_device_ptr (no synchronisation: rpt_gather_wait first).
+ *   rpt_read_gathered's out_samples stays rank 0's own count; rpt_gathered_info_get is where a caller sees disagreement.
+ * rpt_gathered_info_get (rank 0, after a gather; waits for it): with_moments = the last gather carried the records.  Then nonuniform = the OR over the
+ *                  ranks that own pixels of counts_nonuniform at their snapshot, or samples_min != samples_max; samples_min / samples_max of those ranks'
+ *                  uniform sample counts at their snapshot; bad_trailers = ranks whose trailer did not carry the format word (0 unless the setting
+ *                  differs between ranks: then the image is not to be trusted).  After a plain gather: with_moments = 0, nonuniform = the snapshot's
+ *                  flag of this context (rpt_multi: of any rank), samples_min = samples_max = out_samples of rpt_read_gathered, bad_trailers = 0.
+ * RPT_EINVAL for null pointers, from the read-outs on a rank other than 0, with the setting off, before a gather has carried moments and after a
+ * resize until the next gather; the context stays usable. */
+typedef struct rpt_gathered_info {
+    uint32_t with_moments;
+    uint32_t nonuniform;
+    uint32_t samples_min, samples_max;
+    uint32_t bad_trailers;
+    uint32_t reserved[3];
+} rpt_gathered_info;
+int rpt_gather_set_moments(rpt_ctx *ctx, uint32_t on);     /* default 0 */
+int rpt_gather_moments(rpt_ctx *ctx, uint32_t *on_out);
+int rpt_read_gathered_moments(rpt_ctx *ctx, float *out_xyzw);
+int rpt_gathered_moments_device_ptr(rpt_ctx *ctx, void **dev_ptr);
+int rpt_gathered_info_get(rpt_ctx *ctx, rpt_gathered_info *out);
+
 /* ONE process driving every GPU of the node — the shape the reference's single render thread (src/trace.rs:136-224,
  * src/app.rs:157-164) can call: the same entry points as above, fanned out over n_devices contexts created with
  * ncclCommInitAll; the caller sees one W x H image.  rpt_multi_render = one batch on every GPU + the batch's single
@@ -384,7 +428,8 @@ int rpt_multi_denoise(rpt_multi *m, const rpt_denoise_params *params, uint32_t t
  *                   converged = 0 at max_samples.  The accumulator is bit for bit that of plain rendering of samples_rendered samples: the image never
  *                   depends on how samples are split into calls.  counts = the last count; ms = host clock over the whole call.
  *                   RPT_EINVAL for batch_samples == 0, max_samples < min_samples, a negative or NaN threshold.
- * rpt_multi_*       the same on every rank; rpt_multi_read_moments merges the ranks' images on the host (the pixels are disjoint; off the hot path).
+ * rpt_multi_*       the same on every rank; rpt_multi_read_moments merges the ranks' images on the host (the pixels are disjoint; off the hot path) — or,
+ *                   with rpt_multi_gather_set_moments(m, 1), gathers if nothing is gathered and is one copy of the gathered record from rank 0.
  * RPT_EINVAL from the read and count entry points while moments are off, and for null pointers. */
 int rpt_set_moments(rpt_ctx *ctx, uint32_t on);      /* default 0 */
 int rpt_moments(rpt_ctx *ctx, uint32_t *on_out);
@@ -408,6 +453,7 @@ int rpt_render_to_noise(rpt_ctx *ctx, const rpt_noise_target *target, rpt_noise_
 
 int rpt_multi_set_moments(rpt_multi *m, uint32_t on);
 int rpt_multi_read_moments(rpt_multi *m, float *out_xyzw);
+int rpt_multi_gather_set_moments(rpt_multi *m, uint32_t on);   /* rpt_gather_set_moments on every rank ("the moments record ... inside the gather", above) */
 int rpt_multi_noise_count(rpt_multi *m, float threshold, rpt_noise_counts *out);
 int rpt_multi_render_to_noise(rpt_multi *m, const rpt_noise_target *target, rpt_noise_result *out);
 
@@ -430,15 +476,17 @@ int rpt_multi_render_to_noise(rpt_multi *m, const rpt_noise_target *target, rpt_
  * After rpt_reset with accum_init the moments count only the samples rendered since, while the accumulator continues: v is then the variance of the mean
  * of the samples SINCE THE RESET, a larger figure than that of the whole accumulator's mean.
  *
- * moments_xyzw == NULL   the context's own record, on the device, no host trip.  Only with RPT_DENOISE_ACCUM; RPT_EINVAL while moments are off.
+ * moments_xyzw == NULL   the context's own record, on the device, no host trip.  With RPT_DENOISE_ACCUM; RPT_EINVAL while moments are off.  With
+ *                        RPT_DENOISE_GATHERED only under rpt_gather_set_moments(ctx, 1): the gathered record, on the device, no host trip.
  * moments_xyzw != NULL   a width*height float4 row-major image — what rpt_read_moments / rpt_multi_read_moments return — uploaded for this call; with either
- *                        source.  The way a process-per-GPU caller filters a gathered image: moments are not part of the gather.
+ *                        source.  The way a process-per-GPU caller filters a gathered image while moments are not part of the gather (rpt_gather_set_moments off).
  * out_variance (nullable, width*height floats): the last pass's v_out, in the filter's units (demodulated where demodulation was applied; iterations == 0:
  *                        the pre-pass's v, never demodulated); unknown = +inf.
  * RPT_EINVAL for a negative or NaN sigma_variance, a null out_rgb, and for everything rpt_denoise refuses; the context stays usable.  Synchronous on
  * return; leaves the accumulator, the rng, the moments, rpt_stats, the shadow mode and the cached guides untouched.
  * rpt_multi_denoise_variance merges the ranks' records on the host as rpt_multi_read_moments does (OFF THE HOT PATH: a read-back and an upload of 16 bytes
- * per pixel on every call), gathers as rpt_multi_denoise does, and filters on rank 0.
+ * per pixel on every call), gathers as rpt_multi_denoise does, and filters on rank 0.  With rpt_multi_gather_set_moments(m, 1) it gathers if nothing is
+ * gathered and filters by the gathered record: no per-rank read-back, no host merge, no upload; the result is the host merge's bit for bit.
  * Defaults: the lowest summed error of the grid of profiles/r14_denoise_variance_quality.txt.
  *
  * FIREFLY CLAMP (clamp_scale != 0; csrc/k_firefly.h ff_pixel, DESIGN.md "Denoiser").  The moments record's m.w is the luminance of the pixel's brightest sample.

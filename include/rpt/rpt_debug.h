@@ -125,6 +125,21 @@ int rpt_debug_adaptive_window_host(const float *moments_xyzw, uint32_t width, ui
  * Refuses what rpt_adaptive_mask refuses, a null ms_out and repeats == 0. */
 int rpt_debug_adaptive_select_ms(rpt_ctx *ctx, const rpt_noise_target *target, uint32_t radius, uint32_t repeats, float *ms_out);
 
+/* The gather's second wire format (rpt_gather_set_moments; csrc/k_gather.h) on the HOST — no device needed.
+ * rpt_debug_gather_layout: for an image of width x height over `world` ranks, stride_pixels_out = the largest block of any rank; slot_floats_out = floats of
+ * one rank's slot (with_moments: 2 * stride * 4 + 4, else stride * 4); block_pixels_out[world] = every rank's own pixels; message_floats_out[world] = the
+ * count of its one ncclSend (with_moments: the whole slot for every rank; else its block, 0 = the rank posts nothing).  Every output is nullable.
+ * rpt_debug_gather_host: the host build of pack -> slots -> un-tile.  accum_blocks, moments_blocks: the ranks' tile-major blocks one behind the other
+ * (width*height records of 4 floats in all); trailers: 4 words per rank as a rank would write them — RPT_GATHER_FORMAT, counts_nonuniform, the uniform
+ * sample count, the rank's pixel count.  slots_io (nullable; world * slot floats): the landing buffer, as the caller initialised it — the padding behind
+ * a block is never written — else a zeroed one of the hook's own; image_out, moments_out (nullable): width*height records, row-major; info_out (nullable):
+ * the words of rpt_gathered_info_get.  RPT_EINVAL for a width or height outside 1..65535, a world outside 1..64, null inputs. */
+#define RPT_GATHER_FORMAT 0x52504d32u
+int rpt_debug_gather_layout(uint32_t width, uint32_t height, uint32_t world, uint32_t with_moments, uint64_t *stride_pixels_out, uint64_t *slot_floats_out,
+                            uint64_t *block_pixels_out, uint64_t *message_floats_out);
+int rpt_debug_gather_host(uint32_t width, uint32_t height, uint32_t world, const float *accum_blocks, const float *moments_blocks, const uint32_t *trailers,
+                          float *slots_io, float *image_out, float *moments_out, rpt_gathered_info *info_out);
+
 /* Test aid: the next asynchronous batches of this context enqueue one iteration too few — proves that the completion checks (rpt_wait, the next
  * batch's k_generate_first) notice a sample left in flight instead of losing it. */
 int rpt_debug_short_batch(rpt_ctx *ctx, int on);

@@ -8,6 +8,8 @@
  *               block travels to rank 0 with grouped ncclSend / ncclRecv over xGMI (RCCL), on a second HIP stream so
  *               that batch k+1 renders while the blocks of batch k travel; the root un-tiles with a map built once per
  *               configuration.  Nothing here allocates, copies from the host or synchronises per batch.
+ *               rpt_gather_set_moments: the second wire format (k_gather.h) — the moments record and a trailer travel in the same message, k_gather_pack
+ *               takes the snapshot's place and k_gather_untile2 the un-tile's; with the setting off nothing below differs from the plain gather.
  *   two drivers one process per GPU (rpt_comm_init: ncclCommInitRank from a caller-distributed unique id — bench.py /
  *               torchrun), or ONE process driving every GPU of the node (rpt_multi_*: ncclCommInitAll) — the shape the
  *               reference's single render thread (src/trace.rs:136-224, src/app.rs:157-164) can call directly.
@@ -24,6 +26,8 @@
 
 #include "rpt_ctx.h"
 #include "k_image_order.h"
+#define RPT_GATHER_KERNELS
+#include "k_gather.h"
 
 namespace {
 
@@ -105,8 +109,8 @@ struct rpt_comm {
     hipStream_t stream = nullptr;    /* the gather runs here and overlaps the next batch on ctx->stream */
     hipEvent_t staged = nullptr;     /* ctx->stream: this batch's accumulators are snapshotted in `send` */
     hipEvent_t sent = nullptr;       /* comm stream: `send` may be overwritten (and, root, the full image is complete) */
-    DevBuf<float4> send;             /* stride float4: the collective never touches memory the renderer writes */
-    DevBuf<float4> gathered;         /* root: world x stride */
+    DevBuf<float4> send;             /* one slot (plain: stride float4): the collective never touches memory the renderer writes */
+    DevBuf<float4> gathered;         /* root: world x slot */
     DevBuf<uint32_t> map;            /* root: destination pixel of every element of `gathered` */
     DevBuf<float4> full_image;       /* root: row-major W x H */
     PinnedBuf<float> host_full;      /* root: pinned staging for rpt_read_gathered */
@@ -116,6 +120,13 @@ struct rpt_comm {
     uint32_t gathered_samples = 0;
     bool gathered_nonuniform = false; /* the context's counts_nonuniform when the gathered image was snapshotted (rpt_multi: of any rank) */
     bool started = false;
+    /* rpt_gather_set_moments (k_gather.h): the setting, the format the buffers are sized for, and what only that format has */
+    bool with_moments = false;       /* the setting: collective, every rank holds the same value */
+    bool conf_moments = false;       /* what send / gathered / full_moments were sized under */
+    bool carried = false;            /* the gather that `started` speaks of carried the records */
+    DevBuf<float4> full_moments;     /* root: row-major W x H, beside full_image */
+    DevBuf<rpt_gathered_info> info;  /* root: written by k_gather_untile2 */
+    PinnedBuf<rpt_gathered_info> host_info;   /* root: its pinned twin, copied behind every un-tile on the gather's stream */
 };
 
 void rpt_comm_release(rpt_ctx *c) {
@@ -143,8 +154,29 @@ int rpt_comm_gathered_image(rpt_ctx *c, const float4 **image_out, uint32_t *samp
     HIP_TRY(c, hipGetLastError());
     *image_out = cm->full_image.p;
     *samples_out = cm->gathered_samples;
-    *nonuniform_out = cm->gathered_nonuniform;
+    *nonuniform_out = cm->carried ? cm->host_info.p->nonuniform != 0u : cm->gathered_nonuniform;      /* (every rank's trailer: the stream has drained) */
     *stream_out = cm->stream;
+    return RPT_OK;
+}
+
+bool rpt_comm_gather_moments_on(const rpt_ctx *c) { return c->comm && c->comm->with_moments; }
+
+/* what stands between a caller on this context and the gathered moments image (no synchronisation: the readers wait on the gather's stream themselves) */
+static int gathered_moments_check(rpt_ctx *c, const char *who) {
+    rpt_comm *cm = c->comm;
+    if (!cm || cm->rank != 0) { c->error = std::string(who) + ": gathered moments exist on rank 0 of a communicator"; return RPT_EINVAL; }
+    if (!cm->with_moments) { c->error = std::string(who) + ": the gather does not carry the moments (rpt_gather_set_moments(ctx, 1) first)"; return RPT_EINVAL; }
+    if (!cm->started || !cm->carried || !cm->full_moments.p) { c->error = std::string(who) + ": no gather has carried the moments yet: call rpt_gather_async first"; return RPT_EINVAL; }
+    if (!c->has_config || cm->conf_w != c->cfg.c.width || cm->conf_h != c->cfg.c.height) {
+        c->error = std::string(who) + ": the configuration was resized since the last gather: call rpt_gather_async first";
+        return RPT_EINVAL;
+    }
+    return RPT_OK;
+}
+
+int rpt_comm_gathered_moments(rpt_ctx *c, const char *who, const float4 **moments_out) {
+    RPT_TRY(gathered_moments_check(c, who));      /* (rpt_comm_gathered_image has waited; the filter runs on that stream anyway) */
+    *moments_out = c->comm->full_moments.p;
     return RPT_OK;
 }
 
@@ -178,7 +210,7 @@ int comm_check_partition(rpt_ctx *c);
 int comm_configure(rpt_ctx *c) {
     rpt_comm *cm = c->comm;
     const uint32_t W = c->cfg.c.width, H = c->cfg.c.height;
-    if (cm->conf_w == W && cm->conf_h == H && cm->send.p) return RPT_OK;
+    if (cm->conf_w == W && cm->conf_h == H && cm->conf_moments == cm->with_moments && cm->send.p) return RPT_OK;
     HIP_TRY(c, hipStreamSynchronize(cm->stream));
     std::vector<std::vector<uint32_t>> orders(cm->world);
     cm->sizes.assign(cm->world, 0);
@@ -191,19 +223,36 @@ int comm_configure(rpt_ctx *c) {
     int prc = comm_check_partition(c);
     if (prc) return prc;
     cm->started = false;             /* no gathered image exists for this configuration yet (rpt_read_gathered refuses until one does) */
-    HIP_TRY(c, cm->send.alloc(std::max<uint64_t>(cm->stride, 1)));
+    cm->carried = false;
+    const bool wm = cm->with_moments;
+    const GatherLayout lay = gather_layout(cm->stride, wm ? 1u : 0u);
+    cm->send.release();              /* (so that a failure below leaves nothing that passes for a sized buffer) */
+    HIP_TRY(c, cm->send.alloc(std::max<uint64_t>(lay.slot, 1)));
+    /* the second format sends whole slots: the padding behind a block is zeroed here, once, and never written (k_gather.h) */
+    if (wm) HIP_TRY(c, hipMemsetAsync(cm->send.p, 0, cm->send.n * sizeof(float4), cm->stream));
+    cm->full_moments.release(); cm->info.release();
     if (cm->rank == 0) {
         std::vector<uint32_t> map((size_t)cm->world * cm->stride, 0xffffffffu);
         for (uint32_t r = 0; r < cm->world; ++r) std::copy(orders[r].begin(), orders[r].end(), map.begin() + (size_t)r * cm->stride);
         HIP_TRY(c, cm->map.alloc(std::max<size_t>(map.size(), 1)));
-        HIP_TRY(c, cm->gathered.alloc(std::max<size_t>(map.size(), 1)));
+        HIP_TRY(c, cm->gathered.alloc(std::max<size_t>((size_t)cm->world * lay.slot, 1)));
         HIP_TRY(c, cm->full_image.alloc((size_t)W * H));
+        if (wm) {
+            HIP_TRY(c, cm->full_moments.alloc((size_t)W * H));
+            HIP_TRY(c, cm->info.alloc(1));
+            if (!cm->host_info.p) HIP_TRY(c, cm->host_info.alloc(1, hipHostMallocDefault));
+            HIP_TRY(c, hipMemsetAsync(cm->gathered.p, 0, cm->gathered.n * sizeof(float4), cm->stream));
+            HIP_TRY(c, hipMemsetAsync(cm->full_moments.p, 0, (size_t)W * H * sizeof(float4), cm->stream));
+            HIP_TRY(c, hipMemsetAsync(cm->info.p, 0, sizeof(rpt_gathered_info), cm->stream));
+        }
         if (!map.empty()) HIP_TRY(c, hipMemcpy(cm->map.p, map.data(), map.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         HIP_TRY(c, hipMemsetAsync(cm->full_image.p, 0, (size_t)W * H * sizeof(float4), cm->stream));   /* (on the stream that un-tiles into it: rpt_hip.hip, stream discipline) */
         if (cm->host_full.n != (size_t)W * H * 4) HIP_TRY(c, cm->host_full.alloc((size_t)W * H * 4, hipHostMallocDefault));
     }
+    if (wm) HIP_TRY(c, hipStreamSynchronize(cm->stream));      /* `send` is written on the render stream next: the zeroes are there first */
     cm->conf_w = W;
     cm->conf_h = H;
+    cm->conf_moments = wm;
     return RPT_OK;
 }
 
@@ -246,7 +295,14 @@ int gather_stage(rpt_ctx *c) {
     if (rc) return rc;
     /* on the render stream: after everything it has enqueued (the batch) and after the previous gather released `send` */
     if (cm->started) HIP_TRY(c, hipStreamWaitEvent(c->stream, cm->sent, 0));
-    if (c->n_pixels) HIP_TRY(c, hipMemcpyAsync(cm->send.p, c->accum.p, (size_t)c->n_pixels * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+    if (cm->with_moments) {
+        /* (rpt_set_moments refuses to turn the record off while the setting is on, and the record is re-sized with the pixel state) */
+        if (!c->moments_on || c->moments.n != c->n_pixels) { c->error = "gather: internal error (the moments record does not cover the rank's pixels)"; return RPT_EHIP; }
+        const GatherLayout lay = gather_layout(cm->stride, 1u);
+        k_gather_pack<<<rpt_blocks(std::max<uint32_t>(c->n_pixels, 1u)), RPT_BLOCK, 0, c->stream>>>(c->accum.p, c->moments.p, c->n_pixels, lay,
+                                                                                                   gather_trailer(c->counts_nonuniform ? 1u : 0u, c->samples, c->n_pixels), cm->send.p);
+        HIP_TRY(c, hipGetLastError());
+    } else if (c->n_pixels) HIP_TRY(c, hipMemcpyAsync(cm->send.p, c->accum.p, (size_t)c->n_pixels * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(c, hipEventRecord(cm->staged, c->stream));
     HIP_TRY(c, hipStreamWaitEvent(cm->stream, cm->staged, 0));
     cm->gathered_samples = c->samples;
@@ -258,12 +314,14 @@ int gather_stage(rpt_ctx *c) {
 int gather_exchange(rpt_ctx *c) {
     rpt_comm *cm = c->comm;
     HIP_TRY(c, hipSetDevice(c->device));
+    const uint32_t wm = cm->with_moments ? 1u : 0u;
+    const GatherLayout lay = gather_layout(cm->stride, wm);
     if (cm->rank == 0) {
         for (uint32_t r = 1; r < cm->world; ++r)
-            if (cm->sizes[r])
-                NCCL_TRY(c, rccl().Recv(cm->gathered.p + (size_t)r * cm->stride, cm->sizes[r] * 4, ncclFloat, (int)r, cm->comm, cm->stream));
-    } else if (cm->sizes[cm->rank]) {
-        NCCL_TRY(c, rccl().Send(cm->send.p, cm->sizes[cm->rank] * 4, ncclFloat, 0, cm->comm, cm->stream));
+            if (const uint64_t n = gather_message(lay, cm->sizes[r], wm))
+                NCCL_TRY(c, rccl().Recv(cm->gathered.p + (size_t)r * lay.slot, n * 4, ncclFloat, (int)r, cm->comm, cm->stream));
+    } else if (const uint64_t n = gather_message(lay, cm->sizes[cm->rank], wm)) {
+        NCCL_TRY(c, rccl().Send(cm->send.p, n * 4, ncclFloat, 0, cm->comm, cm->stream));
     }
     return RPT_OK;
 }
@@ -272,13 +330,21 @@ int gather_exchange(rpt_ctx *c) {
 int gather_finish(rpt_ctx *c) {
     rpt_comm *cm = c->comm;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (cm->rank == 0) {
+    if (cm->rank == 0 && cm->with_moments) {
+        const GatherLayout lay = gather_layout(cm->stride, 1u);
+        HIP_TRY(c, hipMemcpyAsync(cm->gathered.p, cm->send.p, lay.slot * sizeof(float4), hipMemcpyDeviceToDevice, cm->stream));
+        const dim3 grid(rpt_blocks(std::max<uint64_t>(cm->stride, 1)), cm->world);
+        k_gather_untile2<<<grid, RPT_BLOCK, 0, cm->stream>>>(cm->map.p, cm->gathered.p, lay, cm->world, c->cfg.c.width, cm->full_image.p, cm->full_moments.p, cm->info.p);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(cm->host_info.p, cm->info.p, sizeof(rpt_gathered_info), hipMemcpyDeviceToHost, cm->stream));
+    } else if (cm->rank == 0) {
         if (cm->sizes[0]) HIP_TRY(c, hipMemcpyAsync(cm->gathered.p, cm->send.p, cm->sizes[0] * sizeof(float4), hipMemcpyDeviceToDevice, cm->stream));
         const uint32_t n = (uint32_t)((size_t)cm->world * cm->stride);
         if (n) k_scatter_pixels<<<rpt_blocks(n), RPT_BLOCK, 0, cm->stream>>>(cm->map.p, n, c->cfg.c.width, PixelCopy<float4>{cm->gathered.p, cm->full_image.p});
     }
     HIP_TRY(c, hipEventRecord(cm->sent, cm->stream));
     cm->started = true;
+    cm->carried = cm->with_moments;
     return RPT_OK;
 }
 
@@ -500,6 +566,66 @@ int rpt_read_gathered(rpt_ctx *c, float *out, uint32_t *out_samples) {
     return RPT_OK;
 }
 
+/* ------------------------------------------------------------- the moments record inside the gather (k_gather.h) -- */
+
+int rpt_gather_set_moments(rpt_ctx *c, uint32_t on) {
+    if (!c) return RPT_EINVAL;
+    rpt_comm *cm = c->comm;
+    if (!cm) { c->error = "rpt_gather_set_moments: no communicator (rpt_comm_init / rpt_comm_init_local / rpt_multi_create)"; return RPT_EINVAL; }
+    const bool want = on != 0u;
+    if (want == cm->with_moments) return RPT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (want) RPT_TRY(rpt_set_moments(c, 1u));           /* (waits for the render stream; on already: the record stays) */
+    else if (c->has_state) RPT_TRY(rpt_wait(c));
+    HIP_TRY(c, hipStreamSynchronize(cm->stream));
+    cm->with_moments = want;
+    cm->started = false;                                 /* no gathered image until the next gather, as after a resize */
+    cm->carried = false;
+    if (!c->has_config || !c->has_state) return RPT_OK;  /* (sized by the first gather) */
+    const int rc = comm_configure(c);
+    if (rc) { cm->with_moments = !want; cm->conf_w = cm->conf_h = 0; }      /* (the next gather sizes the buffers for the format that still holds) */
+    return rc;
+}
+
+int rpt_gather_moments(rpt_ctx *c, uint32_t *on_out) {
+    if (!c || !on_out) return RPT_EINVAL;
+    *on_out = rpt_comm_gather_moments_on(c) ? 1u : 0u;
+    return RPT_OK;
+}
+
+int rpt_read_gathered_moments(rpt_ctx *c, float *out_xyzw) {
+    if (!c || !out_xyzw) return RPT_EINVAL;
+    RPT_TRY(gathered_moments_check(c, "rpt_read_gathered_moments"));
+    rpt_comm *cm = c->comm;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(cm->host_full.p, cm->full_moments.p, cm->host_full.n * sizeof(float), hipMemcpyDeviceToHost, cm->stream));
+    HIP_TRY(c, hipStreamSynchronize(cm->stream));
+    memcpy(out_xyzw, cm->host_full.p, cm->host_full.n * sizeof(float));
+    return RPT_OK;
+}
+
+int rpt_gathered_moments_device_ptr(rpt_ctx *c, void **p) {
+    if (!c || !p) return RPT_EINVAL;
+    RPT_TRY(gathered_moments_check(c, "rpt_gathered_moments_device_ptr"));
+    *p = c->comm->full_moments.p;
+    return RPT_OK;
+}
+
+int rpt_gathered_info_get(rpt_ctx *c, rpt_gathered_info *out) {
+    if (!c || !out) return RPT_EINVAL;
+    rpt_comm *cm = c->comm;
+    if (!cm || cm->rank != 0 || !cm->started) { c->error = "rpt_gathered_info_get: gathered info exists on rank 0 after the first gather"; return RPT_EINVAL; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(cm->stream));
+    HIP_TRY(c, hipGetLastError());
+    if (cm->carried) { *out = *cm->host_info.p; return RPT_OK; }
+    rpt_gathered_info g{};
+    g.nonuniform = cm->gathered_nonuniform ? 1u : 0u;
+    g.samples_min = g.samples_max = cm->gathered_samples;
+    *out = g;
+    return RPT_OK;
+}
+
 }  // extern "C"
 
 /* ------------------------------------------------------------------- one process, every GPU of the node -- */
@@ -542,8 +668,11 @@ int multi_gather(rpt_multi *m) {
         for (size_t r = 1; r < m->ctx.size(); ++r) {
             rpt_comm *pcm = m->ctx[r]->comm;
             if (hipStreamWaitEvent(rcm->stream, pcm->staged, 0) != hipSuccess) { m->error = "hipStreamWaitEvent failed"; return RPT_EHIP; }
-            if (pcm->sizes[r] && hipMemcpyAsync(rcm->gathered.p + r * rcm->stride, pcm->send.p, pcm->sizes[r] * sizeof(float4), hipMemcpyDeviceToDevice,
-                                                rcm->stream) != hipSuccess) { m->error = "peer copy failed"; return RPT_EHIP; }
+            const uint32_t wm = rcm->with_moments ? 1u : 0u;
+            const GatherLayout lay = gather_layout(rcm->stride, wm);
+            const uint64_t n = gather_message(lay, pcm->sizes[r], wm);      /* (the second format: the whole slot) */
+            if (n && hipMemcpyAsync(rcm->gathered.p + r * lay.slot, pcm->send.p, n * sizeof(float4), hipMemcpyDeviceToDevice,
+                                    rcm->stream) != hipSuccess) { m->error = "peer copy failed"; return RPT_EHIP; }
         }
     }
     /* the root finishes first: in copy mode the peers' `sent` must follow the root's copies */
@@ -712,10 +841,44 @@ int rpt_multi_set_moments(rpt_multi *m, uint32_t on) {
     return RPT_OK;
 }
 
-/* the ranks' images merged on the host: their pixels are disjoint (off the hot path, called rarely — nothing is added to the gather) */
+/* rpt_gather_set_moments on every rank (the setting is collective); a rank that refuses leaves the ranks before it as they were */
+int rpt_multi_gather_set_moments(rpt_multi *m, uint32_t on) {
+    if (!m) return RPT_EINVAL;
+    const uint32_t before = rpt_comm_gather_moments_on(m->ctx[0]) ? 1u : 0u;
+    for (size_t r = 0; r < m->ctx.size(); ++r) {
+        const int rc = rpt_gather_set_moments(m->ctx[r], on);
+        if (rc) {
+            multi_fail(m, m->ctx[r], rc);
+            for (size_t k = 0; k < r; ++k) (void)rpt_gather_set_moments(m->ctx[k], before);
+            return rc;
+        }
+    }
+    m->gathered = false;             /* rank 0 holds no image in the new format: the next reader gathers first */
+    return RPT_OK;
+}
+
+/* the setting on: everything rendered so far gathered (as rpt_multi_read_accum gathers it), the root's gathered records are the merged image */
+static int multi_gathered_moments_ready(rpt_multi *m) {
+    int rc = rpt_multi_wait(m);
+    if (rc) return rc;
+    if (!m->gathered) {
+        if ((rc = multi_gather(m))) return rc;
+        if ((rc = rpt_multi_wait(m))) return rc;
+    }
+    return RPT_OK;
+}
+
+/* the ranks' images merged on the host: their pixels are disjoint (off the hot path, called rarely) — unless the gather carries the records
+ * (rpt_multi_gather_set_moments): then one copy of the gathered image from rank 0 */
 int rpt_multi_read_moments(rpt_multi *m, float *out_xyzw) {
     if (!m || !out_xyzw) return RPT_EINVAL;
-    int rc = rpt_multi_wait(m);
+    int rc;
+    if (rpt_comm_gather_moments_on(m->ctx[0])) {
+        if ((rc = multi_gathered_moments_ready(m))) return rc;
+        rc = rpt_read_gathered_moments(m->ctx[0], out_xyzw);
+        return rc ? multi_fail(m, m->ctx[0], rc) : RPT_OK;
+    }
+    rc = rpt_multi_wait(m);
     if (rc) return rc;
     std::vector<float> one;
     for (size_t r = 0; r < m->ctx.size(); ++r) {
@@ -741,6 +904,12 @@ int rpt_multi_denoise_variance(rpt_multi *m, const rpt_denoise_var_params *param
     if (!out_rgb) { m->error = "rpt_denoise_variance: out_rgb is null"; return RPT_EINVAL; }
     rpt_ctx *root = m->ctx[0];
     if (!root->has_config) { m->error = "rpt_denoise_variance: needs a scene and a configuration"; return RPT_EINVAL; }
+    if (rpt_comm_gather_moments_on(root)) {              /* the gathered record: no read-back, no merge, no upload */
+        int rc = multi_gathered_moments_ready(m);
+        if (rc) return rc;
+        rc = rpt_denoise_variance(root, RPT_DENOISE_GATHERED, nullptr, params, tonemap_op, out_rgb, out_variance, report);
+        return rc ? multi_fail(m, root, rc) : RPT_OK;
+    }
     std::vector<float> moments((size_t)root->cfg.c.width * root->cfg.c.height * 4);
     int rc = rpt_multi_read_moments(m, moments.data());              /* (waits; RPT_EINVAL while moments are off) */
     if (rc) return rc;
@@ -758,6 +927,12 @@ int rpt_multi_denoise_temporal(rpt_multi *m, const rpt_temporal_params *params, 
     if (!out_rgb) { m->error = "rpt_denoise_temporal: out_rgb is null"; return RPT_EINVAL; }
     rpt_ctx *root = m->ctx[0];
     if (!root->has_config) { m->error = "rpt_denoise_temporal: needs a scene and a configuration"; return RPT_EINVAL; }
+    if (rpt_comm_gather_moments_on(root)) {              /* the gathered record: no read-back, no merge, no upload */
+        int rc = multi_gathered_moments_ready(m);
+        if (rc) return rc;
+        rc = rpt_denoise_temporal(root, RPT_DENOISE_GATHERED, nullptr, params, tonemap_op, out_rgb, out_variance, out_history, report);
+        return rc ? multi_fail(m, root, rc) : RPT_OK;
+    }
     std::vector<float> moments((size_t)root->cfg.c.width * root->cfg.c.height * 4);
     int rc = rpt_multi_read_moments(m, moments.data());              /* (waits; RPT_EINVAL while moments are off) */
     if (rc) return rc;

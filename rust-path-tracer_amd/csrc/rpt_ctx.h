@@ -339,6 +339,11 @@ void rpt_comm_release(rpt_ctx *c);
 /* rpt_comm.hip, for rpt_denoise(RPT_DENOISE_GATHERED): the image of the last gather on rank 0 of a communicator, once that gather has completed, its sample
  * count, whether the counts were non-uniform when it was snapshotted, and the stream the gather ran on (work on it is ordered after the gather and overlaps the batch on the context's own stream) */
 int rpt_comm_gathered_image(rpt_ctx *c, const float4 **image_out, uint32_t *samples_out, bool *nonuniform_out, hipStream_t *stream_out);
+/* rpt_comm.hip: rpt_gather_set_moments is on (rpt_set_moments refuses to turn the record off then; the denoisers take the gathered record for a null image) */
+bool rpt_comm_gather_moments_on(const rpt_ctx *c);
+/* rpt_comm.hip, for rpt_denoise_variance / rpt_denoise_temporal (RPT_DENOISE_GATHERED, no caller's image, the setting on): the row-major moments image of
+ * the last gather on rank 0 — written on the stream rpt_comm_gathered_image hands out; RPT_EINVAL (named after `who`) until a gather has carried moments */
+int rpt_comm_gathered_moments(rpt_ctx *c, const char *who, const float4 **moments_out);
 /* rpt_moments.hip: the moments record of a context with moments on, for its current pixel count: allocated if need be and zeroed on the context's stream */
 int rpt_moments_reset(rpt_ctx *c);
 /* rpt_moments.hip, for rpt_multi_render_to_noise (rpt_comm.hip): the loop of rpt_render_to_noise over the caller's "render n more samples" and "count" */

@@ -2,11 +2,13 @@
  * rpt_debug.hip — the test hooks of include/rpt/rpt_debug.h that run kernels of their own: the math functions, the BSDF
  * pieces, the image sampler and single rays through the debug and the production traversal stages.
  */
+#include <algorithm>
 #include <cstring>
 
 #include "rpt_ctx.h"
 #include "rpt_fastdiv.h"
 #include "k_bsdf_extra.h"
+#include "k_gather.h"
 #include "k_shade.h"             /* sample_by_lod: the function the shade stage, the sky stage and the denoiser's guides inline (k_shade itself is not instantiated) */
 
 /* one coordinate per thread through the production sampler, on an image of the hook's own */
@@ -189,6 +191,72 @@ int rpt_debug_trace_rays_production(rpt_ctx *c, size_t n, const float *origins, 
         out_tri[i] = (w == HIT_MISS) ? 0u : (w & 0x7fffffffu);
         out_flags[i] = (w == HIT_MISS) ? 0u : (1u | ((w >> 31) << 1));
     }
+    return RPT_OK;
+}
+
+/* ---- the gather's second wire format on the host (k_gather.h): the layout arithmetic, and pack -> slots -> un-tile in plain loops over the functions the
+ * kernels and comm_configure use.  No device needed. ---- */
+static int gather_blocks(uint32_t width, uint32_t height, uint32_t world, std::vector<std::vector<uint32_t>> &orders, uint64_t *stride_out) {
+    if (!width || !height || width > 65535u || height > 65535u || !world || world > 64u) { rpt_create_error() = "gather hooks: width / height must be in 1..65535, world in 1..64"; return RPT_EINVAL; }
+    orders.assign(world, {});
+    uint64_t stride = 0;
+    for (uint32_t r = 0; r < world; ++r) {
+        rpt_build_pixel_order(width, height, r, world, orders[r]);
+        stride = std::max<uint64_t>(stride, orders[r].size());
+    }
+    *stride_out = stride;
+    return RPT_OK;
+}
+
+int rpt_debug_gather_layout(uint32_t width, uint32_t height, uint32_t world, uint32_t with_moments, uint64_t *stride_pixels_out, uint64_t *slot_floats_out,
+                            uint64_t *block_pixels_out, uint64_t *message_floats_out) {
+    std::vector<std::vector<uint32_t>> orders;
+    uint64_t stride = 0;
+    RPT_TRY(gather_blocks(width, height, world, orders, &stride));
+    const GatherLayout lay = gather_layout(stride, with_moments);
+    if (stride_pixels_out) *stride_pixels_out = lay.stride;
+    if (slot_floats_out) *slot_floats_out = lay.slot * 4u;
+    for (uint32_t r = 0; r < world; ++r) {
+        if (block_pixels_out) block_pixels_out[r] = orders[r].size();
+        if (message_floats_out) message_floats_out[r] = gather_message(lay, orders[r].size(), with_moments) * 4u;
+    }
+    return RPT_OK;
+}
+
+int rpt_debug_gather_host(uint32_t width, uint32_t height, uint32_t world, const float *accum_blocks, const float *moments_blocks, const uint32_t *trailers,
+                          float *slots_io, float *image_out, float *moments_out, rpt_gathered_info *info_out) {
+    if (!accum_blocks || !moments_blocks || !trailers) { rpt_create_error() = "rpt_debug_gather_host: null blocks or trailers"; return RPT_EINVAL; }
+    std::vector<std::vector<uint32_t>> orders;
+    uint64_t stride = 0;
+    RPT_TRY(gather_blocks(width, height, world, orders, &stride));
+    const GatherLayout lay = gather_layout(stride, 1u);
+    std::vector<float> own;
+    if (!slots_io) { own.assign((size_t)world * lay.slot * 4u, 0.0f); slots_io = own.data(); }      /* (zeroed when they are sized) */
+    /* k_gather_pack, rank by rank: the two records of every owned pixel and the trailer; the padding behind a block is not touched */
+    size_t first = 0;
+    for (uint32_t r = 0; r < world; ++r) {
+        float *slot = slots_io + (size_t)r * lay.slot * 4u;
+        const size_t n = orders[r].size();
+        memcpy(slot, accum_blocks + first * 4u, n * 4u * sizeof(float));
+        memcpy(slot + lay.moments_at * 4u, moments_blocks + first * 4u, n * 4u * sizeof(float));
+        memcpy(slot + lay.trailer_at * 4u, trailers + (size_t)r * 4u, 4u * sizeof(uint32_t));
+        first += n;
+    }
+    /* k_gather_untile2: the map is the orders padded to the stride */
+    rpt_gathered_info g = gather_info_begin();
+    for (uint32_t r = 0; r < world; ++r) {
+        const float *slot = slots_io + (size_t)r * lay.slot * 4u;
+        uint4 t;
+        memcpy(&t, slot + lay.trailer_at * 4u, sizeof t);
+        gather_fold(g, t);
+        for (size_t i = 0; i < orders[r].size(); ++i) {
+            const size_t at = rpt_pixel_index(orders[r][i], width) * 4u;
+            if (image_out) memcpy(image_out + at, slot + i * 4u, 4u * sizeof(float));
+            if (moments_out) memcpy(moments_out + at, slot + (lay.moments_at + i) * 4u, 4u * sizeof(float));
+        }
+    }
+    gather_info_end(g);
+    if (info_out) *info_out = g;
     return RPT_OK;
 }
 

@@ -173,15 +173,21 @@ int open_source(rpt_ctx *c, uint32_t source, DnSource *out) {
  * (the previous call's kernels have drained: every call is synchronous on return).  `who`: the entry point, for the error text. */
 int check_moments_source(rpt_ctx *c, uint32_t source, const float *moments_xyzw, const char *who) {
     if (moments_xyzw) return RPT_OK;
+    if (source == RPT_DENOISE_GATHERED && rpt_comm_gather_moments_on(c)) {      /* the gathered record, once a gather has carried it (open_moments takes it) */
+        const float4 *record = nullptr;
+        return rpt_comm_gathered_moments(c, who, &record);
+    }
     /* the context's own record: it lies beside the accumulator, and only there */
     if (source == RPT_DENOISE_GATHERED) { c->error = std::string(who) + ": moments are not part of the gather: RPT_DENOISE_GATHERED needs a moments image (rpt_read_moments / rpt_multi_read_moments)"; return RPT_EINVAL; }
     if (!c->moments_on) { c->error = std::string(who) + ": moments are off (rpt_set_moments(ctx, 1) first, or pass a moments image)"; return RPT_EINVAL; }
     return RPT_OK;
 }
-int open_moments(rpt_ctx *c, const float *moments_xyzw, uint32_t n, const char *who, const float4 **out) {
+int open_moments(rpt_ctx *c, uint32_t source, const float *moments_xyzw, uint32_t n, const char *who, const float4 **out, uint32_t *row_major_out) {
     DenoiseState &d = c->dn;
     if (d.variance.n != n) HIP_TRY(c, d.variance.alloc(n));
     *out = c->moments.p;
+    *row_major_out = moments_xyzw || source == RPT_DENOISE_GATHERED ? 1u : 0u;
+    if (!moments_xyzw && source == RPT_DENOISE_GATHERED) return rpt_comm_gathered_moments(c, who, out);      /* (row-major, on the device, on the gather's stream) */
     if (moments_xyzw) {
         if (d.moments_in.n != n) HIP_TRY(c, d.moments_in.alloc(n));
         HIP_TRY(c, hipMemcpy(d.moments_in.p, moments_xyzw, (size_t)n * sizeof(float4), hipMemcpyHostToDevice));
@@ -352,8 +358,8 @@ int rpt_denoise_variance(rpt_ctx *c, uint32_t source, const float *moments_xyzw,
     DenoiseState &d = c->dn;
     const uint32_t W = d.width, H = d.height, n = W * H;
     const float4 *moments = nullptr;
-    RPT_TRY(open_moments(c, moments_xyzw, n, "rpt_denoise_variance", &moments));
-    const uint32_t row_major = moments_xyzw ? 1u : 0u;
+    uint32_t row_major = 0u;
+    RPT_TRY(open_moments(c, source, moments_xyzw, n, "rpt_denoise_variance", &moments, &row_major));
     const bool demodulated = p.iterations != 0u && p.demodulate != 0u;
     const float4 *albedo = demodulated ? d.albedo.p : nullptr;
     const bool clamp = vp.clamp_scale != 0.0f;
@@ -412,7 +418,8 @@ int rpt_denoise_temporal(rpt_ctx *c, uint32_t source, const float *moments_xyzw,
     DenoiseState &d = c->dn;
     const uint32_t W = d.width, H = d.height, n = W * H;
     const float4 *moments = nullptr;
-    RPT_TRY(open_moments(c, moments_xyzw, n, "rpt_denoise_temporal", &moments));
+    uint32_t row_major = 0u;
+    RPT_TRY(open_moments(c, source, moments_xyzw, n, "rpt_denoise_temporal", &moments, &row_major));
     const bool demodulated = p.iterations != 0u && p.demodulate != 0u;
     const float4 *albedo = demodulated ? d.albedo.p : nullptr;
 
@@ -439,7 +446,6 @@ int rpt_denoise_temporal(rpt_ctx *c, uint32_t source, const float *moments_xyzw,
     TpView vw = tp_view(W, H, tp.max_history, tp.normal_min, tp.plane_max);
     tp_set_cameras(vw, c->cfg.c.cam_position, c->cfg.euler, d.previous.valid ? d.previous.ro : nullptr, d.previous.euler);
     const TpPrev pv = d.previous.valid ? TpPrev{d.previous.h.p, d.previous.mu.p, d.previous.g0.p, d.previous.g1.p} : TpPrev{nullptr, nullptr, nullptr, nullptr};
-    const uint32_t row_major = moments_xyzw ? 1u : 0u;
     const uint32_t *inverse = in.order ? d.inverse.p : nullptr;
     const dim3 grid((W + 63u) / 64u, (H + 3u) / 4u);
     last.valid = false;

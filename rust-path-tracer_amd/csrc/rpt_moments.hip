@@ -106,6 +106,10 @@ extern "C" {
 
 int rpt_set_moments(rpt_ctx *c, uint32_t on) {
     if (!c) return RPT_EINVAL;
+    if (on == 0u && rpt_comm_gather_moments_on(c)) {   /* (a rank's message holds the record: its length must not depend on anything but the setting) */
+        c->error = "rpt_set_moments: the gather carries the moments (rpt_gather_set_moments(ctx, 0) first)";
+        return RPT_EINVAL;
+    }
     if (c->has_state) RPT_TRY(rpt_wait(c));          /* batches enqueued so far keep the completion kernel they were enqueued with */
     if (on == 0u) {
         c->moments_on = false;

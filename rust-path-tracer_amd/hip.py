@@ -72,6 +72,19 @@ class AdaptiveResult(C.Structure):
                 ("pixel_samples", C.c_uint64), ("counts", NoiseCounts), ("ms", C.c_double)]
 
 
+class GatheredInfo(C.Structure):
+    """rpt_gathered_info"""
+    _fields_ = [("with_moments", C.c_uint32), ("nonuniform", C.c_uint32), ("samples_min", C.c_uint32), ("samples_max", C.c_uint32), ("bad_trailers", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+
+GATHER_FORMAT = 0x52504D32      # RPT_GATHER_FORMAT (rpt_debug.h): word 0 of a rank's trailer
+
+
+def _gathered_info_dict(g):
+    return {k: getattr(g, k) for k in ("with_moments", "nonuniform", "samples_min", "samples_max", "bad_trailers")}
+
+
 def _counts_dict(k):
     return {"pixels": k.pixels, "measured": k.measured, "above": k.above}
 
@@ -178,6 +191,11 @@ PROTOTYPES = {
     "rpt_gather_wait": (C.c_int, [C.c_void_p]),
     "rpt_read_gathered": (C.c_int, [C.c_void_p, C.c_void_p, _OUT_U32]),
     "rpt_gathered_device_ptr": (C.c_int, [C.c_void_p, _OUT_PTR]),
+    "rpt_gather_set_moments": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rpt_gather_moments": (C.c_int, [C.c_void_p, _OUT_U32]),
+    "rpt_read_gathered_moments": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rpt_gathered_moments_device_ptr": (C.c_int, [C.c_void_p, _OUT_PTR]),
+    "rpt_gathered_info_get": (C.c_int, [C.c_void_p, C.POINTER(GatheredInfo)]),
     "rpt_multi_create": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_uint32, _OUT_PTR]),
     "rpt_multi_size": (C.c_int, [C.c_void_p]),
     "rpt_multi_ctx": (C.c_void_p, [C.c_void_p, C.c_int]),
@@ -213,6 +231,7 @@ PROTOTYPES = {
     "rpt_render_to_noise": (C.c_int, [C.c_void_p, C.POINTER(NoiseTarget), C.POINTER(NoiseResult)]),
     "rpt_multi_set_moments": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rpt_multi_read_moments": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rpt_multi_gather_set_moments": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rpt_multi_noise_count": (C.c_int, [C.c_void_p, C.c_float, C.POINTER(NoiseCounts)]),
     "rpt_multi_render_to_noise": (C.c_int, [C.c_void_p, C.POINTER(NoiseTarget), C.POINTER(NoiseResult)]),
     "rpt_denoise_var_params_default": (None, [C.POINTER(DenoiseVarParams)]),
@@ -253,6 +272,8 @@ PROTOTYPES = {
     "rpt_debug_adaptive_select_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, _OUT_SIZE]),
     "rpt_debug_adaptive_window_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
     "rpt_debug_adaptive_select_ms": (C.c_int, [C.c_void_p, C.POINTER(NoiseTarget), C.c_uint32, C.c_uint32, C.c_void_p]),
+    "rpt_debug_gather_layout": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _OUT_U64, _OUT_U64, C.c_void_p, C.c_void_p]),
+    "rpt_debug_gather_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 6 + [C.POINTER(GatheredInfo)]),
     "rpt_debug_short_batch": (C.c_int, [C.c_void_p, C.c_int]),
 }
 EXPORTS = sorted(PROTOTYPES)
@@ -518,7 +539,8 @@ class Renderer(_Handle):
 
     def denoise_variance(self, source=DENOISE_ACCUM, moments=None, params=None, tonemap_op=0, with_report=False):
         """rpt_denoise_variance: denoise() with the luminance term that the per-pixel variance of the mean drives (params: denoise_var_params(), None: the
-        defaults).  moments None: the renderer's own record (set_moments first; DENOISE_ACCUM only); else an (H, W, 4) image as read_moments() returns.
+        defaults).  moments None: the renderer's own record (set_moments first) with DENOISE_ACCUM, the gathered record (gather_set_moments first) with
+        DENOISE_GATHERED; else an (H, W, 4) image as read_moments() returns.
         Returns (rgb (H, W, 3), variance (H, W): the filtered variance of the mean luminance, inf = unknown)[, report]."""
         if moments is not None:
             moments = np.ascontiguousarray(moments, np.float32)
@@ -651,6 +673,34 @@ class Renderer(_Handle):
         self._check(lib().rpt_read_gathered(self._h, ptr(out), C.byref(samples)))
         return out, samples.value
 
+    # -- the moments record and the counts flag inside the gather (include/rpt/rpt.h "inside the gather")
+    def gather_set_moments(self, on=True):
+        """rpt_gather_set_moments: the gather also carries this rank's moments record and its count state to rank 0 (turns moments on and leaves them on).
+        Collective: every rank of the communicator holds the same value at every gather.  No gathered image exists until the next gather."""
+        self._check(lib().rpt_gather_set_moments(self._h, 1 if on else 0))
+
+    def gather_moments(self):
+        on = C.c_uint32()
+        self._check(lib().rpt_gather_moments(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def read_gathered_moments(self):
+        """rpt_read_gathered_moments (rank 0): (H, W, 4) float32, the whole image's records as the last gather carried them"""
+        out = self._image(4)
+        self._check(lib().rpt_read_gathered_moments(self._h, ptr(out)))
+        return out
+
+    def gathered_moments_device_ptr(self):
+        p = C.c_void_p()
+        self._check(lib().rpt_gathered_moments_device_ptr(self._h, C.byref(p)))
+        return p.value
+
+    def gathered_info(self):
+        """rpt_gathered_info_get (rank 0, waits for the last gather): {"with_moments", "nonuniform", "samples_min", "samples_max", "bad_trailers"}"""
+        g = GatheredInfo()
+        self._check(lib().rpt_gathered_info_get(self._h, C.byref(g)))
+        return _gathered_info_dict(g)
+
     # -- test hooks (include/rpt/rpt_debug.h)
     def debug_short_batch(self, on=True):
         """rpt_debug_short_batch: asynchronous batches enqueue one iteration too few (the completion checks must notice)."""
@@ -762,6 +812,18 @@ class MultiRenderer(_Handle):
     def moments_on(self):
         return self.rank_view(0).moments_on()
 
+    def gather_set_moments(self, on=True):
+        """rpt_multi_gather_set_moments: Renderer.gather_set_moments on every rank; read_moments, denoise_variance and denoise_temporal then use the gathered
+        record on rank 0 — no per-rank read-back, no host merge, no upload"""
+        self._call("gather_set_moments", 1 if on else 0)
+
+    def gather_moments(self):
+        return self.rank_view(0).gather_moments()
+
+    def gathered_info(self):
+        """Renderer.gathered_info of rank 0"""
+        return self.rank_view(0).gathered_info()
+
     def counts_uniform(self):
         """rpt_counts_uniform of every rank"""
         return all(self.rank_view(k).counts_uniform() for k in range(self.size()))
@@ -775,7 +837,8 @@ class MultiRenderer(_Handle):
         return self._denoise((), params, tonemap_op, with_report)
 
     def denoise_variance(self, params=None, tonemap_op=0, with_report=False):
-        """rpt_multi_denoise_variance: the ranks' moments merged on the host, the gather of denoise(), the filter on rank 0 (see Renderer.denoise_variance)"""
+        """rpt_multi_denoise_variance: the ranks' moments merged on the host — or, after gather_set_moments(), the gathered record — the gather of denoise(),
+        the filter on rank 0 (see Renderer.denoise_variance)"""
         return self._denoise_variance((), params, tonemap_op, with_report)
 
     def denoise_temporal(self, params=None, tonemap_op=0, with_report=False):
@@ -839,6 +902,31 @@ def debug_math_host(op, x, y=None):
     if rc != 0:
         raise RptError(rc, "rpt_debug_math_host")
     return out
+
+
+def gather_layout(width, height, world_size, with_moments=True):
+    """rpt_debug_gather_layout (no GPU needed): {"stride": pixels, "slot_floats", "block_pixels": [per rank], "message_floats": [per rank]}"""
+    stride, slot = C.c_uint64(), C.c_uint64()
+    blocks, messages = np.zeros(world_size, np.uint64), np.zeros(world_size, np.uint64)
+    rc = lib().rpt_debug_gather_layout(width, height, world_size, 1 if with_moments else 0, C.byref(stride), C.byref(slot), ptr(blocks), ptr(messages))
+    if rc != 0:
+        raise RptError(rc, lib().rpt_last_error(None).decode())
+    return {"stride": stride.value, "slot_floats": slot.value, "block_pixels": [int(b) for b in blocks], "message_floats": [int(m) for m in messages]}
+
+
+def gather_host(width, height, world_size, accum_blocks, moments_blocks, trailers, slots=None):
+    """rpt_debug_gather_host (no GPU needed): the ranks' blocks one behind the other ((W*H, 4) float32 each) and (world, 4) uint32 trailers through the host
+    build of pack -> slots -> un-tile.  slots: None, or the landing buffer (world * slot_floats float32) as the caller initialised it, written in place.
+    Returns (image (H, W, 4), moments (H, W, 4), the dictionary of gathered_info())."""
+    accum_blocks, moments_blocks = np.ascontiguousarray(accum_blocks, np.float32), np.ascontiguousarray(moments_blocks, np.float32)
+    trailers = np.ascontiguousarray(trailers, np.uint32)
+    assert accum_blocks.size == width * height * 4 and moments_blocks.size == width * height * 4 and trailers.shape == (world_size, 4)
+    assert slots is None or (slots.dtype == np.float32 and slots.flags["C_CONTIGUOUS"] and slots.size == world_size * gather_layout(width, height, world_size)["slot_floats"])
+    image, moments, g = np.zeros((height, width, 4), np.float32), np.zeros((height, width, 4), np.float32), GatheredInfo()
+    rc = lib().rpt_debug_gather_host(width, height, world_size, ptr(accum_blocks), ptr(moments_blocks), ptr(trailers), ptr(slots), ptr(image), ptr(moments), C.byref(g))
+    if rc != 0:
+        raise RptError(rc, lib().rpt_last_error(None).decode())
+    return image, moments, _gathered_info_dict(g)
 
 
 def _report_dict(rep):
