@@ -25,6 +25,9 @@ pub const RPT_COMM_ID_BYTES: usize = 128;
 pub const RPT_MULTI_ALLOW_SHARED_DEVICE: u32 = 1;
 pub const RPT_SHADOW_EXACT: u32 = 0;
 pub const RPT_SHADOW_SEGMENT: u32 = 1;
+pub const RPT_MODEL_PBR: u32 = 0;
+pub const RPT_MODEL_LAMBERTIAN: u32 = 1;
+pub const RPT_MODEL_GLASS: u32 = 2;
 pub const RPT_DENOISE_ACCUM: u32 = 0;
 pub const RPT_DENOISE_GATHERED: u32 = 1;
 pub const RPT_ADAPTIVE_MAX_RADIUS: u32 = 8;
@@ -110,6 +113,14 @@ pub struct rpt_gathered_info {
 
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
+pub struct rpt_material_model {
+    pub model: u32,      // RPT_MODEL_*: which BSDF stands where lib.rs:144 constructs the PBR one
+    pub ior: f32,        // GLASS: finite and above 0; ignored on the others
+    pub reserved: [u32; 2],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
 pub struct rpt_noise_counts {
     pub pixels: u64,     // pixels the context owns
     pub measured: u64,   // of those: two samples or more in the moments record
@@ -158,6 +169,8 @@ extern "C" {
     pub fn rpt_shadow_order(ctx: *mut rpt_ctx, fixed_out: *mut u32, visits_near_out: *mut f64, visits_fixed_out: *mut f64, probe_rays_out: *mut u32, probe_ms_out: *mut f64) -> c_int;   // which (bit-exact) order the shadow walks use
     pub fn rpt_set_shadow_mode(ctx: *mut rpt_ctx, mode: u32) -> c_int;             // RPT_SHADOW_EXACT (default, the reference's any-hit walk) | RPT_SHADOW_SEGMENT (opt-in: boxes behind max_t are not entered)
     pub fn rpt_shadow_mode(ctx: *mut rpt_ctx, mode_out: *mut u32) -> c_int;
+    pub fn rpt_set_material_models(ctx: *mut rpt_ctx, models: *const rpt_material_model, n_models: usize) -> c_int;   // one record per material, beside MaterialData (which stays as it is); (null, 0): all PBR
+    pub fn rpt_material_models(ctx: *mut rpt_ctx, out: *mut rpt_material_model, capacity: usize, n_out: *mut usize) -> c_int;
     pub fn rpt_last_bounce_order(ctx: *mut rpt_ctx, mode_out: *mut u32, n_emissive_triangles_out: *mut u32, visits_out: *mut f64, probe_rays_out: *mut u32, probe_ms_out: *mut f64) -> c_int;   // how the last extension rays of a batch without NEE are walked
 
     // --- one GPU: what trace_gpu needs (each line: the reference call it replaces) -------------------------------
@@ -222,6 +235,7 @@ extern "C" {
     pub fn rpt_multi_set_config(m: *mut rpt_multi, config: *const TracingConfig) -> c_int;
     pub fn rpt_multi_reset(m: *mut rpt_multi, rng_seed: *const UVec2, accum_init: *const Vec4, samples_init: u32) -> c_int;
     pub fn rpt_multi_set_shadow_mode(m: *mut rpt_multi, mode: u32) -> c_int;       // rpt_set_shadow_mode on every rank
+    pub fn rpt_multi_set_material_models(m: *mut rpt_multi, models: *const rpt_material_model, n_models: usize) -> c_int;   // rpt_set_material_models on every rank
     pub fn rpt_multi_render(m: *mut rpt_multi, n_samples: u32) -> c_int;            // one batch on every GPU + the batch's single RCCL gather
     pub fn rpt_multi_wait(m: *mut rpt_multi) -> c_int;
     pub fn rpt_multi_read_accum(m: *mut rpt_multi, out: *mut Vec4, out_samples: *mut u32) -> c_int;   // the whole W x H image, from rank 0

@@ -276,6 +276,7 @@ int rpt_multi_upload_scene(rpt_multi *m,
 int rpt_multi_set_config(rpt_multi *m, const rpt_tracing_config *config);
 int rpt_multi_reset(rpt_multi *m, const rpt_rng_state *rng_seed, const float *accum_init_rgba, uint32_t samples_init);
 int rpt_multi_set_shadow_mode(rpt_multi *m, uint32_t mode);  /* rpt_set_shadow_mode (below) on every rank */
+/* (rpt_multi_set_material_models: with the material models, below) */
 /* (rpt_multi_set_moments, rpt_multi_read_moments, rpt_multi_noise_count, rpt_multi_render_to_noise: with the moments, below) */
 int rpt_multi_render(rpt_multi *m, uint32_t n_samples);
 int rpt_multi_wait(rpt_multi *m);
@@ -325,6 +326,32 @@ int rpt_shadow_order(rpt_ctx *ctx, uint32_t *fixed_out, double *visits_near_out,
 enum { RPT_SHADOW_EXACT = 0, RPT_SHADOW_SEGMENT = 1 };
 int rpt_set_shadow_mode(rpt_ctx *ctx, uint32_t mode);
 int rpt_shadow_mode(rpt_ctx *ctx, uint32_t *mode_out);
+/* Material models.  Opt-in; no reference equivalent as a call: the reference's kernels crate carries Lambertian (kernels/src/bsdf.rs:46-105) and Glass
+ * (bsdf.rs:107-176) behind its BSDF trait and constructs neither (lib.rs:144 always calls get_pbr_bsdf).  A material's model replaces the BSDF constructed at
+ * lib.rs:144 and nothing else of lib.rs:21-186.  With pbr = get_pbr_bsdf(config, material, uv, atlas) exactly as without models (texture lookups and its two
+ * guards included):
+ *   RPT_MODEL_PBR         pbr
+ *   RPT_MODEL_LAMBERTIAN  Lambertian { albedo: pbr.albedo }
+ *   RPT_MODEL_GLASS       Glass { albedo: pbr.albedo, ior: the record's, roughness: pbr.roughness }     (the guarded max(roughness, EPS))
+ * and the reference's generic code around it: every model's sample draws one gen_r3() (the dimension budget of rpt_set_config is unchanged); next-event
+ * estimation runs iff the sampled lobe is the diffuse reflection — always for Lambertian, never for Glass (lobes 1 and 3), so no light is sampled through
+ * glass — and evaluates the surface's own evaluate / pdf (light_pick.rs:153-155); an emitter hit after a Glass bounce adds its emission (lib.rs:97) and the
+ * carried light sample is not reset by one; `inside` is decided by the shading normal (bsdf.rs:131), after normal mapping.  The shared_structs layouts are
+ * untouched: the records travel beside the material buffer.
+ * rpt_set_material_models: after rpt_upload_scene, n_models == the scene's material count; callable between any two batches (it waits for what is enqueued);
+ * leaves accumulator, rng, moments, statistics and shadow mode alone; rpt_upload_scene clears the records, rpt_set_config keeps them.  (NULL, 0): every
+ * material PBR again.  RPT_EINVAL, with the context and its records as they were, for a model above 2, an ior that is not finite or not above 0 on a GLASS
+ * record (ignored on the others), a count that is not the scene's, a call before a scene.  While every record is PBR, or none is set, the kernels launched are
+ * the ones launched without this call.  `reserved` is ignored.
+ * rpt_material_models: the records as set (n_out = 0: none), out nullable, capacity in records.
+ * The denoiser's guides (rpt_read_guides) stay first-hit guides: a glass pixel's guide is the glass surface — kind 1, albedo what the BSDF carries
+ * (get_pbr_bsdf's) — not what is seen through it.
+ * Not carried: by rpt_world_save's .rptscene cache and by the host mirror rpt_trace_gpu (rpt_host.h). */
+enum { RPT_MODEL_PBR = 0, RPT_MODEL_LAMBERTIAN = 1, RPT_MODEL_GLASS = 2 };
+typedef struct rpt_material_model { uint32_t model; float ior; uint32_t reserved[2]; } rpt_material_model;
+int rpt_set_material_models(rpt_ctx *ctx, const rpt_material_model *models, size_t n_models);  /* NULL, 0: all PBR */
+int rpt_material_models(rpt_ctx *ctx, rpt_material_model *out, size_t capacity, size_t *n_out);
+int rpt_multi_set_material_models(rpt_multi *m, const rpt_material_model *models, size_t n_models);   /* on every rank */
 /* How the LAST extension rays of a batch of known length are walked when the configuration has no NEE.  At bounce max_bounces - 1 the reference reads three
  * things off intersect_nearest (kernels/src/lib.rs:62-109): a miss adds the sky, a hit on the front of an emissive triangle adds its emission, any other hit
  * adds nothing — so a ray that passes the Moller-Trumbore test of no emissive triangle only has to answer "hit or miss", which the reference's own walk

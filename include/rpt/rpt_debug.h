@@ -144,6 +144,10 @@ int rpt_debug_gather_host(uint32_t width, uint32_t height, uint32_t world, const
  * batch's k_generate_first) notice a sample left in flight instead of losing it. */
 int rpt_debug_short_batch(rpt_ctx *ctx, int on);
 
+/* Test aid: on != 0 makes the render calls of this context launch the models variant of the shade stage (rpt_set_material_models) whatever the records
+ * say — on an all-PBR scene it must give the plain kernels' image and counters bit for bit. */
+int rpt_debug_force_model_kernels(rpt_ctx *ctx, int on);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "shared_structs.h"
+#include "rpt.h"            /* rpt_material_model */
 
 #ifdef __cplusplus
 extern "C" {
@@ -55,7 +56,14 @@ int rpt_world_load(const char *path, rpt_world **out);
  * (emissive = factor * strength) instead of the reference's fixed x15 (src/asset.rs:163-166) for materials that carry
  * the extension — NOT the reference's behaviour, hence opt-in. */
 #define RPT_LOAD_EMISSIVE_STRENGTH 1u
+/* RPT_LOAD_MATERIAL_MODELS (off by default): a glTF material with extensions.KHR_materials_transmission.transmissionFactor > 0 gets a RPT_MODEL_GLASS record
+ * (rpt.h rpt_set_material_models) whose ior is KHR_materials_ior.ior, 1.5 without that extension; every other material a PBR record.  Lambertian has no glTF
+ * spelling: it is set through the API only.  The buffers of the world do not depend on the flag.
+ * rpt_world_material_models: one record per material of the world (all PBR for a world loaded without the flag, from buffers, from an OBJ or from the
+ * .rptscene cache, which does not carry them); out nullable, capacity in records, n_out = the material count.  The host mirror rpt_trace_gpu does not apply them. */
+#define RPT_LOAD_MATERIAL_MODELS 2u
 int rpt_world_load_ex(const char *path, uint32_t flags, rpt_world **out);
+int rpt_world_material_models(const rpt_world *world, rpt_material_model *out, size_t capacity, size_t *n_out);
 /* load_dynamic_image + dynamic_image_to_cpu_buffer (src/asset.rs:238-273): a skybox file (.png, Radiance .hdr) as the
  * reference's CPU path sees it — quantised to 8 bits per channel, alpha 1 — as width*height float RGBA, the layout
  * rpt_upload_scene takes.  Caller frees with rpt_host_free. */

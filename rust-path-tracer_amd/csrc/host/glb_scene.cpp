@@ -530,6 +530,7 @@ bool load_glb(const char *path, World &out, uint32_t flags) {
 
     /* materials (asset.rs:135-175) */
     out.materials.assign(n_file_materials + (ga.used_default_material ? 1 : 0), rpt_material_data{});
+    out.material_models.assign(out.materials.size(), rpt_material_model{RPT_MODEL_PBR, 0.0f, {0u, 0u}});
     std::vector<Image8> textures;          /* in the reference's push order: per material albedo, metallic, roughness, normals */
     for (size_t i = 0; i < out.materials.size(); ++i) {
         rpt_material_data &m = out.materials[i];
@@ -552,6 +553,13 @@ bool load_glb(const char *path, World &out, uint32_t flags) {
                     if (const JValue *es = ext->get("KHR_materials_emissive_strength")) {
                         strength = (float)es->number_or("emissiveStrength", 1.0);
                         has_strength = true;
+                    }
+            /* RPT_LOAD_MATERIAL_MODELS: a transmissive material is Glass, its ior KHR_materials_ior's (the extension's default: 1.5) */
+            if (flags & RPT_LOAD_MATERIAL_MODELS)
+                if (const JValue *ext = jm.get("extensions"))
+                    if (const JValue *tr = ext->get("KHR_materials_transmission"); tr && tr->number_or("transmissionFactor", 0.0) > 0.0) {
+                        const JValue *ji = ext->get("KHR_materials_ior");
+                        out.material_models[i] = rpt_material_model{RPT_MODEL_GLASS, ji ? (float)ji->number_or("ior", 1.5) : 1.5f, {0u, 0u}};
                     }
             /* textures (asset.rs:140-160).  assimp's glTF2 importer exposes metallicRoughnessTexture under BOTH
              * aiTextureType_METALNESS and aiTextureType_DIFFUSE_ROUGHNESS, so the reference atlases it twice. */

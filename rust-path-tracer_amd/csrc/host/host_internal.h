@@ -50,6 +50,7 @@ struct World {
     std::vector<uint8_t> atlas;
     uint32_t atlas_w = 0, atlas_h = 0;
     uint32_t max_depth = 0, n_emissive = 0;
+    std::vector<rpt_material_model> material_models;   /* one per material, every one PBR unless the loader was asked (RPT_LOAD_MATERIAL_MODELS); not in the .rptscene cache */
 };
 
 /* shared tail of World::from_path (src/asset.rs:194-223) */

@@ -2,14 +2,16 @@
  * k_bsdf_extra.h — the two BSDFs of the reference's kernels crate that trace_pixel never instantiates:
  * Lambertian (kernels/src/bsdf.rs:46-105) and Glass (bsdf.rs:107-176, with util.rs:117-142 sample_ggx_microsurface_normal
  * and util.rs:233-236 fresnel_schlick_scalar).  SURVEY.md 8f N4: dead code in the reference (get_pbr_bsdf is the only
- * constructor trace_pixel calls, lib.rs:144), kept here in the reference's operation order so that a material flag can
- * select them the day the reference does; reachable today through the rpt_debug_bsdf test hook only, which
- * tests/test_bsdf_extra.py compares with the oracle's restatement bit for bit.
+ * constructor trace_pixel calls, lib.rs:144), kept here in the reference's operation order.  A material's model selects
+ * them (rpt_set_material_models, include/rpt/rpt.h: the models variant of the surface stage, k_shade.h shade_slot<.., MODELS>,
+ * instantiated in rpt_models.hip); the rpt_debug_bsdf test hook (rpt_debug.hip) reaches each function alone, and
+ * tests/test_bsdf_extra.py compares that with the oracle's restatement bit for bit.
+ * Included by k_shade.h (which defines RPT_PI_F and RPT_EPS first).
  */
 #ifndef RPT_K_BSDF_EXTRA_H
 #define RPT_K_BSDF_EXTRA_H
 
-#include "k_shade.h"
+#include "k_common.h"
 
 struct BsdfSample {
     float pdf;
@@ -74,24 +76,6 @@ __device__ __forceinline__ BsdfSample glass_sample(F3 albedo, float ior, float r
         o.spectrum = albedo;
     }
     return o;
-}
-
-/* test hook: see oracle_bsdf for the item layout */
-__global__ void k_debug_bsdf(int kind, size_t n, const float *in, float *out) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float *p = in + 16 * i;
-    F3 view = f3(p[0], p[1], p[2]), normal = f3(p[3], p[4], p[5]), r = f3(p[6], p[7], p[8]), albedo = f3(p[9], p[10], p[11]);
-    BsdfSample o;
-    o.pdf = 0.0f; o.lobe = 0u; o.spectrum = f3s(0.0f); o.direction = f3s(0.0f);
-    if (kind == 0) o = lambertian_sample(albedo, normal, r);
-    else if (kind == 1) o = glass_sample(albedo, p[12], p[13], view, normal, r);
-    else if (kind == 2) lambertian_evaluate(albedo, normal, r, o.spectrum, o.pdf);
-    else { o.lobe = rptm::f2u32_sat(r.x); o.spectrum = o.lobe == 1u ? f3s(1.0f) : albedo; o.pdf = 1.0f; }   /* bsdf.rs:115-128, 170-176 */
-    float *q = out + 8 * i;
-    q[0] = o.pdf; q[1] = __uint_as_float(o.lobe);
-    q[2] = o.spectrum.x; q[3] = o.spectrum.y; q[4] = o.spectrum.z;
-    q[5] = o.direction.x; q[6] = o.direction.y; q[7] = o.direction.z;
 }
 
 #endif /* RPT_K_BSDF_EXTRA_H */

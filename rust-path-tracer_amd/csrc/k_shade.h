@@ -12,6 +12,7 @@
  *   sample_direct_lighting           kernels/src/light_pick.rs:100-173
  *   calculate_bsdf_mis_contribution  light_pick.rs:179-199
  *   CPU image sampler                shared_structs/src/image_polyfill.rs:32-55
+ *   Lambertian / Glass (MODELS only) kernels/src/bsdf.rs:46-176 (k_bsdf_extra.h), in place of the PBR BSDF at lib.rs:144
  *
  * Wavefront-specific structure: the shadow ray of light_pick.rs:141 is NOT traced
  * here.  The stage computes the contribution the light sample WOULD add if it
@@ -30,6 +31,8 @@
 
 #define RPT_PI_F 3.14159265358979323846f
 #define RPT_EPS 0.001f   /* util.rs:5 */
+
+#include "k_bsdf_extra.h"        /* Lambertian and Glass: what shade_slot<.., MODELS> constructs in place of the PBR BSDF */
 
 /* ---- CPU-polyfill image sampling (shared_structs/src/image_polyfill.rs:32-55) ----------------------------------------------------------
  * sample_raw: `coord.x as usize % width as usize` — the i32 sign-extends to 64 bits, then an UNSIGNED 64-bit remainder.  Written out that
@@ -186,12 +189,19 @@ __device__ __forceinline__ Mat load_material(const DevScene &sc, uint32_t index)
 /* What the stage does for ONE traversed slot (hit word `hw`): everything of lib.rs:64-181 after the intersection.  Outputs:
  * to_sky (a miss: queued for k_sky), emit_shadow + the shadow-queue entry; a path that ends here with nothing pending is
  * finished through finish_in_side_stage (k_path.h). */
-template <int NEE, bool TEXTURED, bool COMPACT>
+/* MODELS (rpt_set_material_models; instantiated in rpt_models.hip only): `models` holds one record per material, (model, ior bits, -, -), or is null for "every
+ * material is PBR".  The model replaces the BSDF constructed at lib.rs:144 and nothing else: Lambertian { albedo } or Glass { albedo, ior, roughness } from what
+ * get_pbr_bsdf found (texture lookups and guards included), through the reference's generic code — one gen_r3(), NEE iff the sampled lobe is the diffuse
+ * reflection (always / never), Lambertian::evaluate and pdf in the light sample, FLAG_LOBE_SPEC = "the last lobe was not the diffuse reflection". */
+#define RPT_DEV_MODEL_LAMBERTIAN 1u
+#define RPT_DEV_MODEL_GLASS 2u
+template <int NEE, bool TEXTURED, bool COMPACT, bool MODELS = false>
 __device__ __forceinline__ void shade_slot(const DevScene &sc, const DevState &st, const DevQueues &q, const DevConfig &cfg, DevStats *stats,
                                            uint32_t slot, float2 hw, bool active, bool &to_sky, bool &emit_shadow, float4 &sh_o, float4 &sh_d,
                                            float4 &sh_c, bool first /* iteration 0 of the call: every path is a first path (k_path.h) */,
                                            uint32_t n_samples, bool &elided /* an NEE evaluation whose shadow ray decides nothing: not queued */,
-                                           bool last_iteration /* wave-uniform: every path of this launch is at its last bounce and has a radiance record */) {
+                                           bool last_iteration /* wave-uniform: every path of this launch is at its last bounce and has a radiance record */,
+                                           const uint4 *models = nullptr) {
     const uint32_t hit_tri = __float_as_uint(hw.y);
     /* wave-uniform: live paths of this batch keep no radiance record (DevQueues::implicit_zero — their radiance is +0 and they owe nothing): a continuing path
      * writes none, a path that ends with nothing added ends as HIT_DONE_ZERO, one that ends on an emitter's front writes 0 + its term and never loads */
@@ -393,9 +403,27 @@ __device__ __forceinline__ void shade_slot(const DevScene &sc, const DevState &s
                 const F3 view = -rd;
                 const float w_spec = bsdf.specular_weight(view, normal);
                 F3 sdir = f3s(0.0f);
-                const bool spec = !(r3 >= w_spec);
+                bool lambert = false, glass = false;
+                float ior = 1.0f;
+                if (MODELS) {
+                    if (models) {
+                        const uint4 mm = models[__float_as_uint(s2.w)];
+                        lambert = mm.x == RPT_DEV_MODEL_LAMBERTIAN;
+                        glass = mm.x == RPT_DEV_MODEL_GLASS;
+                        ior = __uint_as_float(mm.y);
+                    }
+                }
+                /* "the sampled lobe is not the diffuse reflection": both of Glass's lobes (1 and 3), never Lambertian's */
+                const bool spec = MODELS ? (glass || (!lambert && !(r3 >= w_spec))) : !(r3 >= w_spec);
                 float pdf = 1.0f;
                 F3 spectrum = f3s(0.0f);
+                if (MODELS && glass) {
+                    if (!last) {
+                        const BsdfSample o = glass_sample(bsdf.albedo, ior, bsdf.roughness, view, normal, f3(r1, r2, r3));     /* (pdf 1) */
+                        sdir = o.direction;
+                        spectrum = o.spectrum;
+                    }
+                } else
                 if (!last) {
                 /* Both lobes turn one random number into an azimuth and take its sine and cosine (util.rs:27-28, 70), and
                  * both normalise their final direction (util.rs:31, 84): in a wave that holds both kinds of lanes — nearly
@@ -433,6 +461,13 @@ __device__ __forceinline__ void shade_slot(const DevScene &sc, const DevState &s
                 const float cos_theta = rptm::fmaxr(dot3(normal, sdir), RPT_EPS);
                 const F3 halfway = norm3(view + sdir);
                 const F3 ks = bsdf.ks_of(view, halfway);
+                if (MODELS && lambert) {
+                    /* Lambertian::sample's direction is the diffuse lobe's above, operation for operation (bsdf.rs:71-86 / 283-292; sinr and cosr are the halves of
+                     * sincosr); its cosine is clamped at 0, not EPS (bsdf.rs:87-91) */
+                    const float cos_l = rptm::fmaxr(dot3(normal, sdir), 0.0f);
+                    pdf = cos_l / RPT_PI_F;
+                    spectrum = bsdf.albedo / RPT_PI_F * cos_l;
+                } else
                 if (!spec) {
                     pdf = cos_theta / RPT_PI_F;
                     spectrum = bsdf.diffuse_term(cos_theta, w_spec, ks);
@@ -486,6 +521,7 @@ __device__ __forceinline__ void shade_slot(const DevScene &sc, const DevState &s
                                 F3 ks_e = bsdf.ks_of(view, h_e);
                                 F3 attenuation = bsdf.diffuse_term(cos_e, w_e, ks_e);
                                 float bsdf_pdf = cos_e / RPT_PI_F;
+                                if (MODELS && lambert) lambertian_evaluate(bsdf.albedo, normal, light_direction, attenuation, bsdf_pdf);     /* bsdf.rs:59-69, 94-104 */
                                 if (bsdf_pdf > 0.0f) {
                                     float weight = 1.0f;
                                     if (NEE == RPT_NEE_MIS) {
@@ -640,82 +676,15 @@ __device__ __forceinline__ void count_elided(uint32_t *lds_counter, bool elided)
  * (PBRTest 69.3 -> 67.4 per 4).  The NEE variants spill when pushed (72 VGPRs: 20-44 bytes of scratch; packed: VeachMIS shade 44.0 -> 48.6) and are left alone. */
 constexpr int RPT_SHADE_WAVES_PLAIN = 8;
 constexpr int RPT_SHADE_WAVES_PACKED = 5;
-template <int NEE, bool TEXTURED, bool COMPACT>
-__attribute__((amdgpu_waves_per_eu((NEE == RPT_NEE_NONE && !TEXTURED) ? (COMPACT ? RPT_SHADE_WAVES_PACKED : RPT_SHADE_WAVES_PLAIN) : 1, 8)))
-__global__ __launch_bounds__(RPT_BLOCK) void k_shade(DevScene sc, DevState st, DevQueues q, DevConfig cfg, uint32_t iteration,
-                                                     DevStats *stats, uint32_t n_samples /* of this render call */) {
-    const bool first_paths = iteration == 0u;                  /* every traversed slot holds the first path of its call (k_path.h) */
-    /* a batch of known length: iteration i shades bounce i of every path, so its last iteration is every path's last bounce (not the first one: a first
-       path has no radiance record yet) */
-    const bool last_iteration = q.known_length != 0u && iteration != 0u && iteration + 1u >= cfg.c.max_bounces;
-    __shared__ uint32_t push_scratch[RPT_BLOCK / RPT_WAVE + 1];
-    __shared__ uint32_t c_slot[COMPACT ? RPT_BLOCK * RPT_SHADE_ROUNDS : 1];
-    __shared__ uint32_t n_elided;                              /* NEE evaluations of this workgroup whose shadow ray was not queued (shade_slot) */
-    if (q.count[Q_DRAINED] != 0u) return;                      /* surplus launch (grid-uniform) */
-    if (NEE != RPT_NEE_NONE) {
-        if (threadIdx.x == 0u) n_elided = 0u;
-        __syncthreads();                                       /* before any wave's count_elided (one barrier per workgroup; block-uniform: the returns above are) */
-    }
-    if (NEE != RPT_NEE_NONE && blockIdx.x == 0u && threadIdx.x == 0u) q.count[Q_SPOOL] = 0u;   /* the shadow stage that follows starts its pool at entry 0 */
-    if (COMPACT) {
-        const uint32_t base = blockIdx.x * (RPT_BLOCK * RPT_SHADE_ROUNDS);
-        if (base >= st.n_slots) return;                        /* block-uniform */
-        float2 hws[RPT_SHADE_ROUNDS];
-#pragma unroll
-        for (int r = 0; r < RPT_SHADE_ROUNDS; ++r) {           /* all looks in flight before the first is used */
-            const uint32_t s0 = base + (uint32_t)r * RPT_BLOCK + threadIdx.x;
-            hws[r] = s0 < st.n_slots ? st.hit[s0] : make_float2(0.0f, __uint_as_float(HIT_PARKED));
-        }
-        /* Binned by what the stage will do with the slot (lib.rs:64-79 vs :80-181): HITS fill the list from the front, MISSES from the back, and the
-         * hits are padded to whole waves — so no wave holds both.  A miss only parks its slot and queues it for the sky stage (~25 instructions); in
-         * slot order it sat beside lanes running the ~1 400-instruction surface body: from the second bounce on 40-80 % of the traversed slots of an
-         * open scene are misses, the stage ran at 45 % lanes (profiles/r04_{veachmis,pbrtest}_pmc_sq.txt; tools/shade_bin_sim.py replays it:
-         * 26-31 % fewer wave-instructions).  The order inside the list is no part of any result: every entry touches only its own slot. */
-        constexpr uint32_t CAP = RPT_BLOCK * RPT_SHADE_ROUNDS;
-        uint32_t total_h = 0u, total_m = 0u;                   /* block-uniform */
-#pragma unroll
-        for (int r = 0; r < RPT_SHADE_ROUNDS; ++r) {
-            const uint32_t s0 = base + (uint32_t)r * RPT_BLOCK + threadIdx.x;
-            const uint32_t word = __float_as_uint(hws[r].y);
-            const bool is_hit = word < HIT_IDLE, is_miss = word == HIT_MISS;
-            uint32_t ih, im, nh, nm;
-            block_rank2(is_hit, is_miss, push_scratch, ih, im, nh, nm);
-            if (is_hit) c_slot[total_h + ih] = s0;
-            if (is_miss) c_slot[CAP - 1u - (total_m + im)] = s0;
-            total_h += nh; total_m += nm;
-        }
-        __syncthreads();
-        const uint32_t hits_padded = (total_h + RPT_WAVE - 1u) & ~(uint32_t)(RPT_WAVE - 1u);
-        const uint32_t total = hits_padded + total_m;
-        for (uint32_t first = 0u; first < total; first += RPT_BLOCK) {      /* block-uniform trip count */
-            const uint32_t v = first + threadIdx.x;
-            const bool a_hit = v < total_h, a_miss = v >= hits_padded && v < total;
-            const bool active = a_hit || a_miss;
-            const uint32_t slot = a_hit ? c_slot[v] : (a_miss ? c_slot[CAP - 1u - (v - hits_padded)] : 0u);
-            const float2 hw = a_hit ? st.hit[slot] : make_float2(0.0f, __uint_as_float(a_miss ? HIT_MISS : HIT_PARKED));
-            bool to_sky = false, emit_shadow = false, elided = false;
-            float4 sh_o = make_float4(0, 0, 0, 0), sh_d = sh_o, sh_c = sh_o;
-            shade_slot<NEE, TEXTURED, true>(sc, st, q, cfg, stats, slot, hw, active, to_sky, emit_shadow, sh_o, sh_d, sh_c, first_paths, n_samples, elided, last_iteration);
-            if (NEE != RPT_NEE_NONE) count_elided(&n_elided, elided);
-            shade_emit<NEE>(q, push_scratch, slot, to_sky, emit_shadow, sh_o, sh_d, sh_c);
-        }
-    } else {
-        const uint32_t slot = blockIdx.x * RPT_BLOCK + threadIdx.x;
-        float2 hw = make_float2(0.0f, __uint_as_float(HIT_PARKED));
-        if (slot < st.n_slots) hw = st.hit[slot];
-        const uint32_t hit_tri = __float_as_uint(hw.y);
-        const bool active = hit_tri < HIT_IDLE || hit_tri == HIT_MISS;        /* traversed in this iteration */
-        bool to_sky = false, emit_shadow = false, elided = false;
-        float4 sh_o = make_float4(0, 0, 0, 0), sh_d = sh_o, sh_c = sh_o;
-        shade_slot<NEE, TEXTURED, false>(sc, st, q, cfg, stats, slot, hw, active, to_sky, emit_shadow, sh_o, sh_d, sh_c, first_paths, n_samples, elided, last_iteration);
-        if (NEE != RPT_NEE_NONE) count_elided(&n_elided, elided);
-        shade_emit<NEE>(q, push_scratch, slot, to_sky, emit_shadow, sh_o, sh_d, sh_c);
-    }
-    if (NEE != RPT_NEE_NONE) {
-        /* one sharded, non-returning atomic per workgroup (element 1 of the shard's line: element 0 counts extension rays) */
-        __syncthreads();
-        if (threadIdx.x == 0u && n_elided != 0u) atomicAdd(&q.ray_shards[(blockIdx.x % RPT_STAT_SHARDS) * RPT_STAT_STRIDE + 1u], (unsigned long long)n_elided);
-    }
-}
+/* The kernel: one text (k_shade_body.h) compiled here as k_shade and in rpt_models.hip as k_shade_models */
+#define RPT_SHADE_KERNEL k_shade
+#define RPT_SHADE_MODELS false
+#define RPT_SHADE_MODELS_ARG(...)
+#define RPT_SHADE_OCCUPANCY __attribute__((amdgpu_waves_per_eu((NEE == RPT_NEE_NONE && !TEXTURED) ? (COMPACT ? RPT_SHADE_WAVES_PACKED : RPT_SHADE_WAVES_PLAIN) : 1, 8)))
+#include "k_shade_body.h"
+#undef RPT_SHADE_KERNEL
+#undef RPT_SHADE_MODELS
+#undef RPT_SHADE_MODELS_ARG
+#undef RPT_SHADE_OCCUPANCY
 
 #endif /* RPT_K_SHADE_H */

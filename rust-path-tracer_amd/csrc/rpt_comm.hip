@@ -832,6 +832,16 @@ int rpt_multi_denoise(rpt_multi *m, const rpt_denoise_params *params, uint32_t t
 }
 
 /* rpt_set_moments on every rank */
+/* every rank holds the same scene: a refusal on rank 0 (the records are checked before anything changes) means no rank was changed */
+int rpt_multi_set_material_models(rpt_multi *m, const rpt_material_model *models, size_t n_models) {
+    if (!m) return RPT_EINVAL;
+    for (rpt_ctx *c : m->ctx) {
+        int rc = rpt_set_material_models(c, models, n_models);
+        if (rc) return multi_fail(m, c, rc);
+    }
+    return RPT_OK;
+}
+
 int rpt_multi_set_moments(rpt_multi *m, uint32_t on) {
     if (!m) return RPT_EINVAL;
     for (rpt_ctx *c : m->ctx) {

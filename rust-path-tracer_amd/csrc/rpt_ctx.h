@@ -2,7 +2,8 @@
  * rpt_ctx.h — the context object behind the C ABI of include/rpt/rpt.h, shared by the translation units of
  * librpt_hip.so (rpt_hip.hip: life cycle, state and wavefront scheduling; rpt_scene.hip: scene preparation; rpt_traverse.hip: the traversal stages;
  * rpt_comm.hip: multi-GPU gather over RCCL, read-back; rpt_denoise.hip: guide buffers and the denoise filter; rpt_moments.hip: sample moments, noise estimate,
- * render to a noise target; rpt_adaptive.hip: masked passes over chosen pixels, per-pixel counts to a noise target; rpt_debug.hip: test hooks).  k_image_order.h: the one kernel and the one read-out routine that turn the tile-major pixel order
+ * render to a noise target; rpt_adaptive.hip: masked passes over chosen pixels, per-pixel counts to a noise target; rpt_models.hip: material models and the
+ * shade stage's models variant; rpt_debug.hip: test hooks).  k_image_order.h: the one kernel and the one read-out routine that turn the tile-major pixel order
  * into a row-major image, for every unit that hands one to the caller.
  */
 #ifndef RPT_CTX_H
@@ -252,6 +253,13 @@ struct rpt_ctx {
     DevBuf<uchar4> atlas;
     DevBuf<float4> skybox;
     DevScene scene{};
+    uint32_t n_materials = 0;                  /* of the uploaded scene: what rpt_set_material_models' count must equal */
+    /* rpt_set_material_models (rpt_models.hip): one record per material beside the material buffer — handed to k_shade_models as an argument of its own, DevScene
+     * is what it was — and their host copy for rpt_material_models; both empty until set and after rpt_upload_scene */
+    DevBuf<rpt_material_model> material_models;
+    std::vector<rpt_material_model> material_models_host;
+    bool models_in_use = false;                /* some record is not PBR: the shade stage is k_shade_models */
+    bool force_model_kernels = false;          /* rpt_debug_force_model_kernels: k_shade_models whatever the records say (none: every material PBR) */
     uint32_t bvh_depth = 0;
     int stack_cap = 16;
 
@@ -323,6 +331,10 @@ bool rpt_launch_nearest(rpt_ctx *c, uint32_t iteration, bool last_without_nee /*
                         bool camera_rays /* iteration 0 of a render call: every ray leaves cfg.cam_position */, bool start_paths);
 bool rpt_first_walk_starts_paths(const rpt_ctx *c);
 void rpt_launch_shadow(rpt_ctx *c);
+/* rpt_models.hip: the shade stage of one iteration as k_shade_models (NEE mode, textured or not, packed or not as launch_iteration picks k_shade), and
+ * "no records", for rpt_upload_scene */
+void rpt_launch_shade_models(rpt_ctx *c, uint32_t iteration, uint32_t blocks);
+void rpt_material_models_clear(rpt_ctx *c);
 void rpt_launch_trace_debug(rpt_ctx *c, int any_hit /* 0 nearest, 1 any-hit, 2 segment-bounded any-hit */, uint32_t n, const float *origins, const float *dirs, const float *max_t, float *out_t, uint32_t *out_tri,
                             uint32_t *out_flags);
 hipError_t rpt_last_walk_attributes(hipFuncAttributes *out);      /* of k_traverse_nearest_stream<.., LAST>: its static LDS decides whether the flipped copy fits */

@@ -7,9 +7,8 @@
 
 #include "rpt_ctx.h"
 #include "rpt_fastdiv.h"
-#include "k_bsdf_extra.h"
 #include "k_gather.h"
-#include "k_shade.h"             /* sample_by_lod: the function the shade stage, the sky stage and the denoiser's guides inline (k_shade itself is not instantiated) */
+#include "k_shade.h"             /* sample_by_lod: the function the shade stage, the sky stage and the denoiser's guides inline (k_shade itself is not instantiated); k_bsdf_extra.h */
 
 /* one coordinate per thread through the production sampler, on an image of the hook's own */
 template <bool IS_U8>
@@ -17,6 +16,24 @@ __global__ __launch_bounds__(256) void k_debug_sample_image(DevImage img, size_t
     const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     out[i] = sample_by_lod<IS_U8>(img, coords[i].x, coords[i].y);
+}
+
+/* rpt_debug_bsdf: the functions of k_bsdf_extra.h, one item per thread (see oracle_bsdf for the item layout) */
+__global__ void k_debug_bsdf(int kind, size_t n, const float *in, float *out) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *p = in + 16 * i;
+    F3 view = f3(p[0], p[1], p[2]), normal = f3(p[3], p[4], p[5]), r = f3(p[6], p[7], p[8]), albedo = f3(p[9], p[10], p[11]);
+    BsdfSample o;
+    o.pdf = 0.0f; o.lobe = 0u; o.spectrum = f3s(0.0f); o.direction = f3s(0.0f);
+    if (kind == 0) o = lambertian_sample(albedo, normal, r);
+    else if (kind == 1) o = glass_sample(albedo, p[12], p[13], view, normal, r);
+    else if (kind == 2) lambertian_evaluate(albedo, normal, r, o.spectrum, o.pdf);
+    else { o.lobe = rptm::f2u32_sat(r.x); o.spectrum = o.lobe == 1u ? f3s(1.0f) : albedo; o.pdf = 1.0f; }   /* bsdf.rs:115-128, 170-176 */
+    float *q = out + 8 * i;
+    q[0] = o.pdf; q[1] = __uint_as_float(o.lobe);
+    q[2] = o.spectrum.x; q[3] = o.spectrum.y; q[4] = o.spectrum.z;
+    q[5] = o.direction.x; q[6] = o.direction.y; q[7] = o.direction.z;
 }
 
 extern "C" {

@@ -190,7 +190,8 @@ uint32_t launch_iteration(rpt_ctx *c, uint32_t iteration, uint32_t blocks, bool 
                                           iteration == 0u, iteration == 0u && c->first_walk_starts);
     t.mark(s, RPT_STAGE_TRAVERSE, StageTimer::AT_1 | StageTimer::AT_2);
     if (!ended) {                                           /* (ended: nothing is left for a shade stage, every path of the launch is HIT_DONE or waits in the sky queue) */
-        if (c->shade_compact) k_shade<NEE, TEXTURED, true><<<(c->n_slots + RPT_BLOCK * RPT_SHADE_ROUNDS - 1) / (RPT_BLOCK * RPT_SHADE_ROUNDS), RPT_BLOCK, 0, s>>>(c->scene, c->state, c->queues, c->cfg, iteration, c->dev_stats.p, c->call_samples);
+        if (c->models_in_use || c->force_model_kernels) rpt_launch_shade_models(c, iteration, blocks);     /* (rpt_set_material_models: some material is not PBR) */
+        else if (c->shade_compact) k_shade<NEE, TEXTURED, true><<<(c->n_slots + RPT_BLOCK * RPT_SHADE_ROUNDS - 1) / (RPT_BLOCK * RPT_SHADE_ROUNDS), RPT_BLOCK, 0, s>>>(c->scene, c->state, c->queues, c->cfg, iteration, c->dev_stats.p, c->call_samples);
         else k_shade<NEE, TEXTURED, false><<<blocks, RPT_BLOCK, 0, s>>>(c->scene, c->state, c->queues, c->cfg, iteration, c->dev_stats.p, c->call_samples);
     }
     /* generations are completed (and the next samples started) after every shade stage only where slots take more than one

@@ -11,12 +11,21 @@ import os
 import numpy as np
 
 from . import _ffi
-from ._ffi import RNG_DTYPE, Stats, TracingConfig, ptr
+from ._ffi import MATERIAL_MODEL_DTYPE, RNG_DTYPE, Stats, TracingConfig, ptr
 
 _lib = None
 
 COMM_ID_BYTES = 128
 SHADOW_EXACT, SHADOW_SEGMENT = 0, 1          # rpt_set_shadow_mode
+MODEL_PBR, MODEL_LAMBERTIAN, MODEL_GLASS = 0, 1, 2      # rpt_set_material_models
+
+
+def material_models(models, iors=None):
+    """records for set_material_models: one MODEL_* per material, and the ior of the GLASS ones (a scalar or one per material; default 1.5)"""
+    rec = np.zeros(len(models), MATERIAL_MODEL_DTYPE)
+    rec["model"] = models
+    rec["ior"] = 1.5 if iors is None else iors
+    return rec
 MULTI_ALLOW_SHARED_DEVICE = 1
 DENOISE_ACCUM, DENOISE_GATHERED = 0, 1       # rpt_denoise: which image
 GUIDE_MISS, GUIDE_SURFACE, GUIDE_EMITTER = 0, 1, 2
@@ -218,6 +227,9 @@ PROTOTYPES = {
     "rpt_shadow_order": (C.c_int, [C.c_void_p, _OUT_U32, _OUT_F64, _OUT_F64, _OUT_U32, _OUT_F64]),
     "rpt_set_shadow_mode": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rpt_shadow_mode": (C.c_int, [C.c_void_p, _OUT_U32]),
+    "rpt_set_material_models": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rpt_material_models": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _OUT_SIZE]),
+    "rpt_multi_set_material_models": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "rpt_last_bounce_order": (C.c_int, [C.c_void_p, _OUT_U32, _OUT_U32, _OUT_F64, _OUT_U32, _OUT_F64]),
     "rpt_denoise_params_default": (None, [C.POINTER(DenoiseParams)]),
     "rpt_denoise": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(DenoiseParams), C.c_uint32, C.c_void_p, C.POINTER(DenoiseReport)]),
@@ -275,6 +287,7 @@ PROTOTYPES = {
     "rpt_debug_gather_layout": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _OUT_U64, _OUT_U64, C.c_void_p, C.c_void_p]),
     "rpt_debug_gather_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 6 + [C.POINTER(GatheredInfo)]),
     "rpt_debug_short_batch": (C.c_int, [C.c_void_p, C.c_int]),
+    "rpt_debug_force_model_kernels": (C.c_int, [C.c_void_p, C.c_int]),
 }
 EXPORTS = sorted(PROTOTYPES)
 
@@ -406,6 +419,16 @@ class _Handle:
         """rpt_set_shadow_mode (rpt_multi_: on every rank): SHADOW_EXACT (default: the reference's any-hit walk, bit for bit) or SHADOW_SEGMENT (boxes that begin
         behind the ray's max_t are not entered: faster, an occlusion can in principle be lost); holds for the batches enqueued afterwards."""
         self._call("set_shadow_mode", mode)
+
+    def set_material_models(self, records=None):
+        """rpt_set_material_models (rpt_multi_: on every rank): one record per material of the uploaded scene (material_models(...), or an array of
+        MATERIAL_MODEL_DTYPE) — MODEL_PBR, MODEL_LAMBERTIAN or MODEL_GLASS with its ior — in place of the BSDF the reference constructs at lib.rs:144;
+        None: every material PBR again.  Between batches; accumulator, rng, moments and statistics stay; upload_scene clears the records."""
+        if records is None:
+            self._call("set_material_models", None, 0)
+            return
+        records = np.ascontiguousarray(records, MATERIAL_MODEL_DTYPE)
+        self._call("set_material_models", ptr(records), len(records))
 
     # -- per-pixel sample moments and the noise estimate (no reference equivalent; include/rpt/rpt.h "per-pixel sample moments")
     def set_moments(self, on=True):
@@ -631,6 +654,18 @@ class Renderer(_Handle):
         vn, vf, ms = C.c_double(), C.c_double(), C.c_double()
         self._check(lib().rpt_shadow_order(self._h, C.byref(f), C.byref(vn), C.byref(vf), C.byref(n), C.byref(ms)))
         return {"fixed": bool(f.value), "visits_near": vn.value, "visits_fixed": vf.value, "probe_rays": n.value, "probe_ms": ms.value}
+
+    def material_models(self):
+        """rpt_material_models: the records as set, an array of MATERIAL_MODEL_DTYPE (empty: none set)"""
+        n = C.c_size_t()
+        self._check(lib().rpt_material_models(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, MATERIAL_MODEL_DTYPE)
+        self._check(lib().rpt_material_models(self._h, ptr(out), len(out), C.byref(n)))
+        return out
+
+    def debug_force_model_kernels(self, on=True):
+        """rpt_debug_force_model_kernels (test hook): the models variant of the shade stage whatever the records say"""
+        self._check(lib().rpt_debug_force_model_kernels(self._h, 1 if on else 0))
 
     def shadow_mode(self):
         m = C.c_uint32()
