@@ -2,7 +2,7 @@
 #   rust-path-tracer_amd/lib/librpt_hip.so   HIP kernels + C ABI (gfx950, hipcc)
 #   rust-path-tracer_amd/lib/librpt_host.so  host-side dispatch mirror (g++)
 #   oracle/liboracle.so, oracle/liboracle_libm.so   CPU restatement (test infrastructure)
-#   tests/models_oracle/libmodels_oracle.so         the same with a material's model at lib.rs:144 (test infrastructure)
+#   oracle/libmodels_oracle.so                      the same with a material's model at lib.rs:144 (test infrastructure; source: tests/models_oracle)
 # -ffp-contract=off everywhere: the parity contract forbids implicit FMA fusion.
 
 PKG      := rust-path-tracer_amd
@@ -37,16 +37,17 @@ $(LIBDIR)/librpt_host.so: $(HOST_SRCS) $(CSRC)/host/host_internal.h $(CSRC)/rpt_
 	@mkdir -p $(LIBDIR)
 	$(CXX) $(CXXFLAGS_COMMON) -shared -o $@ $(HOST_SRCS) -lz -ldl -pthread
 
-oracle/liboracle.so: oracle/rpt_oracle.cpp oracle/bvh_oracle.cpp $(CSRC)/rpt_math.h $(CSRC)/rpt_math_consts.h include/rpt/shared_structs.h
+oracle/liboracle.so: oracle/rpt_oracle.cpp oracle/bvh_oracle.cpp $(CSRC)/rpt_math.h $(CSRC)/rpt_fastdiv.h $(CSRC)/rpt_math_consts.h include/rpt/shared_structs.h
 	$(CXX) $(ORACLE_FLAGS) -shared -o $@ oracle/rpt_oracle.cpp oracle/bvh_oracle.cpp
 
-oracle/liboracle_libm.so: oracle/rpt_oracle.cpp oracle/bvh_oracle.cpp $(CSRC)/rpt_math.h $(CSRC)/rpt_math_consts.h include/rpt/shared_structs.h
+oracle/liboracle_libm.so: oracle/rpt_oracle.cpp oracle/bvh_oracle.cpp $(CSRC)/rpt_math.h $(CSRC)/rpt_fastdiv.h $(CSRC)/rpt_math_consts.h include/rpt/shared_structs.h
 	$(CXX) $(ORACLE_FLAGS) -DORACLE_USE_LIBM -shared -o $@ oracle/rpt_oracle.cpp oracle/bvh_oracle.cpp -lm
 
 # test infrastructure: the restatement of trace_pixel with the model switch (tests/models_oracle/models_oracle.cpp includes oracle/rpt_oracle.cpp
-# textually); -Bsymbolic: its copy of the oracle's exported names binds to itself, whichever library a process loaded first
-models_oracle: tests/models_oracle/libmodels_oracle.so
-tests/models_oracle/libmodels_oracle.so: tests/models_oracle/models_oracle.cpp oracle/rpt_oracle.cpp $(CSRC)/rpt_math.h $(CSRC)/rpt_math_consts.h include/rpt/shared_structs.h
+# textually); -Bsymbolic: its copy of the oracle's exported names binds to itself, whichever library a process loaded first.  Built BESIDE the oracle, not
+# beside its source: a build product under tests/ is lost when another commit's tests/ is put over a built tree, and the tests of that commit then fail
+models_oracle: oracle/libmodels_oracle.so
+oracle/libmodels_oracle.so: tests/models_oracle/models_oracle.cpp oracle/rpt_oracle.cpp $(CSRC)/rpt_math.h $(CSRC)/rpt_fastdiv.h $(CSRC)/rpt_math_consts.h include/rpt/shared_structs.h
 	$(CXX) $(ORACLE_FLAGS) -shared -Wl,-Bsymbolic -o $@ tests/models_oracle/models_oracle.cpp
 
 # the fingerprint of the device-side sources is compiled in (rpt_build_fingerprint): bench.py reports PMC-derived figures only for the
@@ -69,6 +70,6 @@ tests/fake_rccl/librccl_fake.so: tests/fake_rccl/fake_rccl.cpp
 	$(HIPCC) -x c++ -std=c++17 -O2 -fPIC -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -shared -o $@ $< -L/opt/rocm/lib -lamdhip64 -lrt -pthread
 
 clean:
-	rm -f $(LIBDIR)/*.so oracle/*.so tests/fake_rccl/*.so tests/models_oracle/*.so
+	rm -f $(LIBDIR)/*.so oracle/*.so tests/fake_rccl/*.so
 
 .PHONY: all host oracle hip fake_rccl models_oracle clean

@@ -16,7 +16,11 @@ extern "C" {
  * check bit-equality with the host build of the same header. op: 0 sin, 1 cos,
  * 2 acos, 3 exp, 4 pow(x,y), 5 asin, 6 atan2(y=x_in, x=y_in), 7 sqrt, 8 IEEE x/y,
  * 9 x/y through the traversal's guarded exact fast-division path (rpt_fastdiv.h), 10 the sky march's float-only exp
- * (rpt_math.h exp_sky), 11 an atlas texel channel u8 / 255 (rpt_math.h unorm8). */
+ * (rpt_math.h exp_sky), 11 an atlas texel channel u8 / 255 (rpt_math.h unorm8); the helpers of rpt_math.h: 12 fminr(x, y),
+ * 13 fmaxr(x, y), 14 floorr, 15 ceilr, 16 f2u32_sat(x) returned as the word's bits, 17 atanr, 18 powi5, 19 absr; the double a
+ * building block returns, as the bits of its low (even op) and high (odd op) word: 20/21 sin_poly and 22/23 cos_poly on [-1, 1],
+ * 24/25 exp_core on [-700, 700], 26/27 log_core on the positive finite floats, 28/29 asin_poly(x, x^2) on [-1, 1], 30/31 atan01 on
+ * [0, 1] (0 outside these domains).  Every other op is refused (RPT_EINVAL). */
 int rpt_debug_math(rpt_ctx *ctx, int op, const float *x, const float *y, float *out, size_t n);
 /* Same on the HOST build (no device needed, ctx may be NULL). */
 int rpt_debug_math_host(int op, const float *x, const float *y, float *out, size_t n);

@@ -55,6 +55,7 @@
 
 #include "../include/rpt/shared_structs.h"
 #include "../rust-path-tracer_amd/csrc/rpt_math.h"
+#include "../rust-path-tracer_amd/csrc/rpt_fastdiv.h"    /* oracle_math op 9 only */
 
 namespace {
 
@@ -1327,9 +1328,28 @@ int oracle_sample_image(const void *texels, int is_u8, uint32_t width, uint32_t 
     return 0;
 }
 
+/* ops 20 .. 31 of rpt_debug_math: one word of the double a building block of rpt_math.h returns (the same statement as csrc/rpt_debug.hip's) */
+static double math_core(int k, float x) {
+    const double d = (double)x;
+    const bool unit = x >= -1.0f && x <= 1.0f;
+    switch (k) {
+        case 0: return unit ? rptm::sin_poly(d) : 0.0;
+        case 1: return unit ? rptm::cos_poly(d) : 0.0;
+        case 2: return (x >= -700.0f && x <= 700.0f) ? rptm::exp_core(d) : 0.0;
+        case 3: return (x > 0.0f && rptm::finiter(x)) ? rptm::log_core(d) : 0.0;
+        case 4: return unit ? rptm::asin_poly(d, d * d) : 0.0;
+        default: return (x >= 0.0f && x <= 1.0f) ? rptm::atan01(d) : 0.0;
+    }
+}
+
 int oracle_math(int op, const float *x, const float *y, float *out, size_t n) {
     for (size_t i = 0; i < n; ++i) {
         float r;
+        if (op >= 20 && op <= 31) {
+            const uint64_t u = rptm::d2u(math_core((op - 20) >> 1, x[i]));
+            out[i] = rptm::u2f((uint32_t)((op & 1) ? u >> 32 : u));
+            continue;
+        }
         switch (op) {
             case 0: r = m_sin(x[i]); break;
             case 1: r = m_cos(x[i]); break;
@@ -1341,6 +1361,16 @@ int oracle_math(int op, const float *x, const float *y, float *out, size_t n) {
             case 6: r = m_atan2(x[i], y[i]); break;
             case 7: r = m_sqrt(x[i]); break;
             case 8: r = x[i] / y[i]; break;
+            /* the helpers of rpt_math.h / rpt_fastdiv.h themselves, whichever backend the transcendentals use (the numbers of rpt_debug_math) */
+            case 9: r = rptm::slab_quotient(x[i], 0.0f, y[i]); break;
+            case 12: r = rptm::fminr(x[i], y[i]); break;
+            case 13: r = rptm::fmaxr(x[i], y[i]); break;
+            case 14: r = rptm::floorr(x[i]); break;
+            case 15: r = rptm::ceilr(x[i]); break;
+            case 16: r = rptm::u2f(rptm::f2u32_sat(x[i])); break;
+            case 17: r = m_atan(x[i]); break;
+            case 18: r = rptm::powi5(x[i]); break;
+            case 19: r = rptm::absr(x[i]); break;
             default: return -1;
         }
         out[i] = r;

@@ -38,8 +38,27 @@ __global__ void k_debug_bsdf(int kind, size_t n, const float *in, float *out) {
 
 extern "C" {
 
+/* ops 20 .. 31: the DOUBLE a building block of rpt_math.h returns, before the rounding to float hides all but a 2^-29th of it: a device Horner step
+ * with two roundings instead of the fma changes no float of a million samples, and every one of these words.  Outside a block's domain: 0. */
+RPT_HD double debug_math_core(int k, float x) {
+    const double d = (double)x;
+    const bool unit = x >= -1.0f && x <= 1.0f;
+    switch (k) {
+        case 0: return unit ? rptm::sin_poly(d) : 0.0;
+        case 1: return unit ? rptm::cos_poly(d) : 0.0;
+        case 2: return (x >= -700.0f && x <= 700.0f) ? rptm::exp_core(d) : 0.0;
+        case 3: return (x > 0.0f && rptm::finiter(x)) ? rptm::log_core(d) : 0.0;
+        case 4: return unit ? rptm::asin_poly(d, d * d) : 0.0;
+        default: return (x >= 0.0f && x <= 1.0f) ? rptm::atan01(d) : 0.0;
+    }
+}
+
 /* the operations of the math hooks: one statement for the kernel and for the host build of rpt_math.h (clang's, as tests/test_math.py needs) */
 RPT_HD float debug_math_op(int op, float x, float y) {
+    if (op >= 20) {
+        const uint64_t u = rptm::d2u(debug_math_core((op - 20) >> 1, x));
+        return rptm::u2f((uint32_t)((op & 1) ? u >> 32 : u));
+    }
     switch (op) {
         case 0: return rptm::sinr(x);
         case 1: return rptm::cosr(x);
@@ -52,6 +71,14 @@ RPT_HD float debug_math_op(int op, float x, float y) {
         case 9: return rptm::slab_quotient(x, 0.0f, y);
         case 10: return rptm::exp_sky(x);
         case 11: return rptm::unorm8(x);
+        case 12: return rptm::fminr(x, y);
+        case 13: return rptm::fmaxr(x, y);
+        case 14: return rptm::floorr(x);
+        case 15: return rptm::ceilr(x);
+        case 16: return rptm::u2f(rptm::f2u32_sat(x));      /* the word's bits */
+        case 17: return rptm::atanr(x);
+        case 18: return rptm::powi5(x);
+        case 19: return rptm::absr(x);
         default: return x / y;
     }
 }
@@ -63,13 +90,13 @@ __global__ void k_debug_math(int op, const float *x, const float *y, float *out,
 }
 
 int rpt_debug_math_host(int op, const float *x, const float *y, float *out, size_t n) {
-    if (op < 0 || op > 11 || !x || !y || !out) return RPT_EINVAL;
+    if (op < 0 || op > 31 || !x || !y || !out) return RPT_EINVAL;
     for (size_t i = 0; i < n; ++i) out[i] = debug_math_op(op, x[i], y[i]);
     return RPT_OK;
 }
 
 int rpt_debug_math(rpt_ctx *c, int op, const float *x, const float *y, float *out, size_t n) {
-    if (!c || op < 0 || op > 11 || !x || !y || !out) return RPT_EINVAL;
+    if (!c || op < 0 || op > 31 || !x || !y || !out) return RPT_EINVAL;
     HIP_TRY(c, hipSetDevice(c->device));
     DevBuf<float> dx, dy, dout;
     HIP_TRY(c, dx.from_host(x, n)); HIP_TRY(c, dy.from_host(y, n)); HIP_TRY(c, dout.alloc(n));

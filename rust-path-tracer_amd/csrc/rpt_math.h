@@ -21,6 +21,12 @@
  * differ from glibc's <1-ulp float routines in well under 1 % of arguments
  * (measured in tests/test_math.py).
  *
+ * Evidence for "bit-identical on both sides" and for "rounded once": tests/test_math_domain.py holds the g++ and the clang host
+ * build to each other and to the float64 value rounded once, tests/test_gpu_math_domain.py holds the device to both host builds, on
+ * the same arrays (tests/math_domain.py) — every sign and exponent field, denormals, infinities and NaNs, every float around every
+ * threshold a function below branches on, every special-case row of powr and atan2r, and the helpers (fminr ... absr) against their
+ * definitions.  The sampled tests (tests/test_gpu_parity.py, tests/test_math.py) cover the hot path's ranges more densely.
+ *
  * Constants come from tools/gen_math_consts.py (mpmath, 120 digits).
  */
 #ifndef RPT_MATH_H
@@ -226,8 +232,10 @@ RPT_UNROLL
 }
 
 /* sin and cos of a float angle; correctly rounded for |x| < 1e5 (the hot path
- * passes [0, 2pi], [0, pi/2] and the user's camera angles).  |x| >= 2^30 is
- * outside the supported domain and yields (0, 1) deterministically. */
+ * passes [0, 2pi], [0, pi/2] and the user's camera angles) — and, as measured, on
+ * the whole of |x| < 2^30: tests/test_math_domain.py finds no difference from float64
+ * rounded once there either, the floats next to k pi/2 up to k = 2^29 included.
+ * |x| >= 2^30 is outside the supported domain and yields (0, 1) deterministically. */
 RPT_HD void sincosr(float xf, float &s, float &c) {
     if (!finiter(xf)) { s = c = u2f(0x7fc00000u); return; }
     if (absr(xf) >= 1073741824.0f) { s = 0.0f; c = 1.0f; return; }
@@ -318,8 +326,35 @@ RPT_UNROLL
     return fmad(ed, RPT_LN2_HI, fmad(ed, RPT_LN2_LO, lm));
 }
 
+/* a^n (a > 0, 2 <= n <= 255) by square-and-multiply in double, for as long as every product is EXACT (its fma residual is zero and it stays
+ * within 2^+-500, where the residual cannot underflow): then p is a^n itself and the caller rounds it once.  False as soon as one product is not —
+ * a^n then has more than 53 significant bits or lies far outside the floats, and exp(n log a) below rounds it correctly.  Why: exp(y log x) is good
+ * to ~1e-16 relative, which decides every rounding except an EXACT tie, and integer powers of floats of few bits are exact ties (x^2 of a 13-bit x
+ * has 25 bits: tests/test_math_domain.py found -1.627e18^2 rounded up instead of to even).  A tie needs a^n in 25 bits, so n <= 15 unless a is a
+ * power of two, where the one tie is 2^-150 and |n| <= 150.  Every production call has a literal exponent that is no integer (2.2, 1.5, 1/2.4):
+ * the compiler drops this path there. */
+RPT_HD bool powi_exact(double a, int n, double &p) {
+    double r = 1.0, b = a;
+    for (;;) {
+        if (n & 1) {
+            const double m = r * b;
+            if (fmad(r, b, -m) != 0.0 || !(m < 0x1p+500) || !(m > 0x1p-500)) return false;
+            r = m;
+        }
+        n >>= 1;
+        if (n == 0) break;
+        const double s = b * b;
+        if (fmad(b, b, -s) != 0.0 || !(s < 0x1p+500) || !(s > 0x1p-500)) return false;
+        b = s;
+    }
+    p = r;
+    return true;
+}
+
 /* f32::powf (reference use: kernels/src/skybox.rs:90,93). Full IEEE special
- * cases for the shapes that can occur: any x, finite y. */
+ * cases for the shapes that can occur: any x, finite y.  Correctly rounded like the rest, exact ties of integer exponents included (powi_exact);
+ * NOT covered: an exact tie under an exponent that is no integer (x = s^2 with a 12-bit s and y = 1.5 gives s^3 in 25 bits), where the result may
+ * be either neighbour — the same one on the host and on the device. */
 RPT_HD float powr(float x, float y) {
     if (y == 0.0f) return 1.0f;
     if (x == 1.0f) return 1.0f;
@@ -344,6 +379,14 @@ RPT_HD float powr(float x, float y) {
         if (!y_is_int) return u2f(0x7fc00000u);
         if (y_is_odd) sign = -1.0f;
         x = -x;
+    }
+    if (y_is_int && absr(y) >= 2.0f && absr(y) <= 255.0f) {
+        double p;
+        if (powi_exact((double)x, (int)absr(y), p)) {
+            if (y > 0.0f) return sign * (float)p;
+            /* a negative exponent: 1 / p is exact only for p = 2^k (no division: the exponent field mirrored) */
+            if ((d2u(p) & 0x000fffffffffffffull) == 0ull) return sign * (float)u2d(0x7fe0000000000000ull - d2u(p));
+        }
     }
     double t = (double)y * log_core((double)x);
     if (t > 89.0) return sign * u2f(0x7f800000u);

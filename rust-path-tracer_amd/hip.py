@@ -742,6 +742,10 @@ class Renderer(_Handle):
         self._check(lib().rpt_debug_short_batch(self._h, 1 if on else 0))
 
     def debug_math(self, op, x, y=None):
+        """rpt_debug_math: one function of csrc/rpt_math.h on the device, elementwise.  op: 0 sin, 1 cos, 2 acos, 3 exp, 4 pow(x, y), 5 asin,
+        6 atan2(y=x, x=y), 7 sqrt, 8 IEEE x / y, 9 slab_quotient(x, 0, y), 10 exp_sky, 11 unorm8, 12 fminr(x, y), 13 fmaxr(x, y), 14 floorr, 15 ceilr,
+        16 f2u32_sat(x) as the word's bits, 17 atanr, 18 powi5, 19 absr; 20 + 2 k / 21 + 2 k the low / high word of the double that sin_poly, cos_poly,
+        exp_core, log_core, asin_poly, atan01 (k = 0 .. 5) return; any other op is refused.  debug_math_host takes the same numbers."""
         x = np.ascontiguousarray(x, np.float32)
         y = x if y is None else np.ascontiguousarray(y, np.float32)
         out = np.empty_like(x)

@@ -1,5 +1,5 @@
 """Procedural scenes with material models (include/rpt/rpt.h rpt_set_material_models), built with the host builders as tests/scenes.py builds its own; and the
-ctypes face of the bit-exact restatement tests/models_oracle/libmodels_oracle.so.  Every scene function returns (world, records, skybox or None, view):
+ctypes face of the bit-exact restatement oracle/libmodels_oracle.so (source: tests/models_oracle).  Every scene function returns (world, records, skybox or None, view):
 records as hip.MATERIAL_MODEL_DTYPE, view = the camera fields of a configuration."""
 import ctypes as C
 import importlib
@@ -154,7 +154,7 @@ def config(name, nee, width, height, **more):
     return rpt.default_config(width, height, has_skybox=0 if skybox is None else 1, **view, **dict(CONFIGS[nee], **more))
 
 
-# ---- tests/models_oracle/libmodels_oracle.so -----------------------------------------------------------------------------------------------------------
+# ---- oracle/libmodels_oracle.so (tests/models_oracle) -----------------------------------------------------------------------------------------------------------
 class ModelsStats(C.Structure):
     _fields_ = [("samples", C.c_uint64), ("extension_rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("sky_evals", C.c_uint64),
                 ("light_index_clamped", C.c_uint64), ("shadow_rays_zero_term", C.c_uint64), ("error_flags", C.c_uint32), ("threads", C.c_uint32)]
@@ -166,7 +166,7 @@ _lib = None
 def models_lib():
     global _lib
     if _lib is None:
-        path = os.path.join(HERE, "models_oracle", "libmodels_oracle.so")
+        path = os.path.join(os.path.dirname(HERE), "oracle", "libmodels_oracle.so")      # beside liboracle.so: build products stay out of tests/
         if not os.path.exists(path):
             raise RuntimeError(f"{path} is missing: run `make models_oracle`")
         _lib = C.CDLL(path)

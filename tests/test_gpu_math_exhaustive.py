@@ -1,6 +1,8 @@
 """The cheap exact division by a constant of rpt_math.h IS the IEEE operation: checked on the device for
 every float they are used on, not argued (rpt_debug_math_sweep compares bit patterns against the compiler's correctly
-rounded expansions; those are themselves compared with the host on samples in test_gpu_parity / test_math)."""
+rounded expansions; those are themselves compared with the host on samples in test_gpu_parity / test_math, and over the
+whole float domain — every exponent field, denormals, the special cases, both sides of every threshold — in
+test_gpu_math_domain, whose host side test_math_domain holds to float64)."""
 import numpy as np
 import pytest
 
