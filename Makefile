@@ -37,17 +37,17 @@ $(LIBDIR)/librpt_host.so: $(HOST_SRCS) $(CSRC)/host/host_internal.h $(CSRC)/rpt_
 	@mkdir -p $(LIBDIR)
 	$(CXX) $(CXXFLAGS_COMMON) -shared -o $@ $(HOST_SRCS) -lz -ldl -pthread
 
-oracle/liboracle.so: oracle/rpt_oracle.cpp oracle/bvh_oracle.cpp $(CSRC)/rpt_math.h $(CSRC)/rpt_fastdiv.h $(CSRC)/rpt_math_consts.h include/rpt/shared_structs.h
+oracle/liboracle.so: oracle/rpt_oracle.cpp oracle/bvh_oracle.cpp $(CSRC)/rpt_math.h $(CSRC)/rpt_fastdiv.h $(CSRC)/rpt_rcp.h $(CSRC)/rpt_math_consts.h include/rpt/shared_structs.h
 	$(CXX) $(ORACLE_FLAGS) -shared -o $@ oracle/rpt_oracle.cpp oracle/bvh_oracle.cpp
 
-oracle/liboracle_libm.so: oracle/rpt_oracle.cpp oracle/bvh_oracle.cpp $(CSRC)/rpt_math.h $(CSRC)/rpt_fastdiv.h $(CSRC)/rpt_math_consts.h include/rpt/shared_structs.h
+oracle/liboracle_libm.so: oracle/rpt_oracle.cpp oracle/bvh_oracle.cpp $(CSRC)/rpt_math.h $(CSRC)/rpt_fastdiv.h $(CSRC)/rpt_rcp.h $(CSRC)/rpt_math_consts.h include/rpt/shared_structs.h
 	$(CXX) $(ORACLE_FLAGS) -DORACLE_USE_LIBM -shared -o $@ oracle/rpt_oracle.cpp oracle/bvh_oracle.cpp -lm
 
 # test infrastructure: the restatement of trace_pixel with the model switch (tests/models_oracle/models_oracle.cpp includes oracle/rpt_oracle.cpp
 # textually); -Bsymbolic: its copy of the oracle's exported names binds to itself, whichever library a process loaded first.  Built BESIDE the oracle, not
 # beside its source: a build product under tests/ is lost when another commit's tests/ is put over a built tree, and the tests of that commit then fail
 models_oracle: oracle/libmodels_oracle.so
-oracle/libmodels_oracle.so: tests/models_oracle/models_oracle.cpp oracle/rpt_oracle.cpp $(CSRC)/rpt_math.h $(CSRC)/rpt_fastdiv.h $(CSRC)/rpt_math_consts.h include/rpt/shared_structs.h
+oracle/libmodels_oracle.so: tests/models_oracle/models_oracle.cpp oracle/rpt_oracle.cpp $(CSRC)/rpt_math.h $(CSRC)/rpt_fastdiv.h $(CSRC)/rpt_rcp.h $(CSRC)/rpt_math_consts.h include/rpt/shared_structs.h
 	$(CXX) $(ORACLE_FLAGS) -shared -Wl,-Bsymbolic -o $@ tests/models_oracle/models_oracle.cpp
 
 # the fingerprint of the device-side sources is compiled in (rpt_build_fingerprint): bench.py reports PMC-derived figures only for the

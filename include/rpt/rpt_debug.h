@@ -41,6 +41,11 @@ int rpt_debug_last_order_host(const rpt_per_vertex_data *vertices, size_t n_vert
  * number of arguments whose results differ in any bit (NaN == NaN) and the smallest such bit pattern (0xffffffff if none). */
 int rpt_debug_math_sweep(rpt_ctx *ctx, int op, uint32_t lo_bits, uint64_t count, float y, uint64_t *mismatches_out,
                          uint32_t *first_bad_bits_out);
+/* rptm::rcp_rn (csrc/rpt_rcp.h: the reciprocal from v_rcp_f32 and one residual step, the division outside its guard; window != 0: rcp_rn_window, the step alone, for arguments inside the window) on the device: over n floats, and
+ * compared on the device with the compiler's `1.0f / x` over the bit patterns [lo_bits, lo_bits + count), count <= 2^32 — the number of arguments whose
+ * results differ in any bit (NaNs too: word for word) and up to 64 of those bit patterns (0xffffffff in the unused places of bad_bits_out[64]). */
+int rpt_debug_rcp(rpt_ctx *ctx, int window, const float *x, float *out, size_t n);
+int rpt_debug_rcp_sweep(rpt_ctx *ctx, int window, uint32_t lo_bits, uint64_t count, uint64_t *mismatches_out, uint32_t *bad_bits_out);
 /* Trace n rays through the uploaded BVH on the device. any_hit = 0: nearest
  * (kernels/src/intersection.rs:169-171) ; 1: any-hit with max_t
  * (:173-175) ; 2: the segment-bounded any-hit walk of RPT_SHADOW_SEGMENT (rpt.h

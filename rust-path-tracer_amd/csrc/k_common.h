@@ -37,6 +37,7 @@
 
 #include "../../include/rpt/shared_structs.h"
 #include "rpt_math.h"
+#include "rpt_rcp.h"
 
 #define RPT_WAVE 64
 #define RPT_BLOCK 256
@@ -59,7 +60,7 @@ __device__ __forceinline__ F3 cross3(F3 a, F3 b) {
     return F3{a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x, a.x * b.y - b.x * a.y};
 }
 __device__ __forceinline__ float len3(F3 a) { return rptm::sqrtr(dot3(a, a)); }
-__device__ __forceinline__ F3 norm3(F3 a) { return a * (1.0f / len3(a)); }
+__device__ __forceinline__ F3 norm3(F3 a) { return a * rptm::rcp_rn(len3(a)); }
 __device__ __forceinline__ F3 lerp3(F3 a, F3 b, float s) { return a + ((b - a) * s); }
 __device__ __forceinline__ bool finite3(F3 a) { return rptm::finiter(a.x) && rptm::finiter(a.y) && rptm::finiter(a.z); }
 /* util.rs:271-277: v if finite, else zero — as ONE select of a bit mask and three ands: three selects on one condition compile to

@@ -565,7 +565,7 @@ __device__ __forceinline__ void shade_slot(const DevScene &sc, const DevState &s
                         if (rng.next() > prob) {
                             done = true;
                         } else {
-                            throughput = throughput * (1.0f / prob);
+                            throughput = throughput * rptm::rcp_rn(prob);
                         }
                     }
                     new_flags = MAKE_FLAGS(bounce + 1u, spec ? 1u : 0u, rng.dim);

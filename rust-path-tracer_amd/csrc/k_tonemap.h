@@ -38,14 +38,14 @@ RPT_HD F3 tonemap(uint32_t op, F3 x) {
         case 4u: return tm_aces_hill(x);
         case 5u: {                                                                           /* Neutral :79-101 */
             F3 w = tm_curve(f3s(5.3f), 0.2f, 0.29f, 0.24f, 0.272f, 0.02f, 0.3f);
-            F3 white_scale = f3(1.0f / w.x, 1.0f / w.y, 1.0f / w.z);
+            F3 white_scale = f3(rptm::rcp_rn(w.x), rptm::rcp_rn(w.y), rptm::rcp_rn(w.z));
             F3 y = tm_curve(x * white_scale, 0.2f, 0.29f, 0.24f, 0.272f, 0.02f, 0.3f) * white_scale;
             return f3(y.x / 1.0f, y.y / 1.0f, y.z / 1.0f);
         }
         case 6u: {                                                                           /* Uncharted :113-121 */
             F3 curr = tm_curve(x * 2.0f, 0.15f, 0.50f, 0.10f, 0.20f, 0.02f, 0.30f);
             F3 w = tm_curve(f3s(11.2f), 0.15f, 0.50f, 0.10f, 0.20f, 0.02f, 0.30f);
-            return curr * f3(1.0f / w.x, 1.0f / w.y, 1.0f / w.z);
+            return curr * f3(rptm::rcp_rn(w.x), rptm::rcp_rn(w.y), rptm::rcp_rn(w.z));
         }
         default: return x;
     }

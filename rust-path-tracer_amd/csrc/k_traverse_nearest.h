@@ -212,7 +212,7 @@ __global__ __launch_bounds__(THREADS) void k_traverse_nearest_stream(DevScene sc
                         slot = cand;
                         took = true;
                         if (fastdiv_ray_ok(sc.fastdiv_ok, ro, rd)) {
-                            ird = f3(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z);
+                            ird = f3(rptm::rcp_rn_window(rd.x), rptm::rcp_rn_window(rd.y), rptm::rcp_rn_window(rd.z));
                             walk_begin(view, w);
                             have = true;
                             if (LAST) {
@@ -331,7 +331,7 @@ __attribute__((amdgpu_waves_per_eu(gstream_waves(STACK, WIDTH, COOP), 8)))
                     ro = f3(ra.x, ra.y, ra.z); rd = f3(ra.w, rb.x, rb.y);
                     have = true;
                     if (fastdiv_ray_ok(sc.fastdiv_ok, ro, rd)) {
-                        ird = f3(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z);
+                        ird = f3(rptm::rcp_rn_window(rd.x), rptm::rcp_rn_window(rd.y), rptm::rcp_rn_window(rd.z));
                         walk_begin(view, w);
                     } else {
                         /* outside the exact-division guard (a zero / denormal-small direction component): walked here, alone;

@@ -94,7 +94,7 @@ __global__ __launch_bounds__(THREADS) void RPT_SHADOW_KERNEL(k_traverse_shadow_s
                     max_t = SEGMENT ? shadow_segment_bound(o.w) : o.w;
                     have = true;
                     if (fastdiv_ray_ok(sc.fastdiv_ok, ro, rd)) {
-                        ird = f3(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z);
+                        ird = f3(rptm::rcp_rn_window(rd.x), rptm::rcp_rn_window(rd.y), rptm::rcp_rn_window(rd.z));
                         walk_begin(view, w);
                     } else {
                         w.res = traverse_loop<STACK, true, false, FIXED, SEGMENT>(view, ro, rd, rd, max_t, stack);   /* alone; recorded at the next refill */
@@ -161,7 +161,7 @@ __attribute__((amdgpu_waves_per_eu(gstream_waves(STACK, WIDTH, COOP), 8)))
                         entry = at;
                         have = true;
                         if (fastdiv_ray_ok(sc.fastdiv_ok, ro, rd)) {
-                            ird = f3(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z);
+                            ird = f3(rptm::rcp_rn_window(rd.x), rptm::rcp_rn_window(rd.y), rptm::rcp_rn_window(rd.z));
                             walk_begin(view, w);
                         } else {
                             w.res = traverse_loop<STACK, true, false, FIXED, SEGMENT>(view, ro, rd, rd, max_t, stack);   /* alone; noted at the next refill */

@@ -268,7 +268,7 @@ __device__ __forceinline__ bool moller_trumbore(F3 edge1, F3 edge2, Corner corne
     float det = dot3(edge1, pv);
     backface = (rptm::f2u(det) >> 31) != 0u;
     if (rptm::absr(det) < 1e-6f) return false;
-    float inv_det = 1.0f / det;
+    float inv_det = rptm::rcp_rn(det);
     F3 tv = ro - corner();
     float u = dot3(tv, pv) * inv_det;
     if (u < 0.0f || u > 1.0f) return false;
@@ -674,7 +674,7 @@ __device__ __forceinline__ bool fastdiv_ray_ok(uint32_t fastdiv_ok, F3 ro, F3 rd
 template <int STACK, bool ANY_HIT, bool SEGMENT = false, typename View, typename StackT>
 __device__ __forceinline__ HitRecord traverse_one(const View &view, uint32_t fastdiv_ok, F3 ro, F3 rd, float max_t, StackT *stack) {
     if (fastdiv_ray_ok(fastdiv_ok, ro, rd)) {
-        F3 ird = f3(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z);
+        F3 ird = f3(rptm::rcp_rn_window(rd.x), rptm::rcp_rn_window(rd.y), rptm::rcp_rn_window(rd.z));
         return traverse_loop<STACK, ANY_HIT, true, false, SEGMENT>(view, ro, rd, ird, max_t, stack);
     }
     return traverse_loop<STACK, ANY_HIT, false, false, SEGMENT>(view, ro, rd, rd, max_t, stack);

@@ -141,6 +141,53 @@ int rpt_debug_math_sweep(rpt_ctx *c, int op, uint32_t lo_bits, uint64_t count, f
     return RPT_OK;
 }
 
+/* rptm::rcp_rn (rpt_rcp.h) against the compiler's `1.0f / x`, word for word (no NaN == NaN: the fallback IS that division; window != 0: rcp_rn_window), over the bit patterns
+ * [lo_bits, lo_bits + count): out[0] the differences, out[1] how many of them out[2 ..] lists (any 64 of them: whichever threads came first) */
+__global__ void k_debug_rcp_sweep(int window, uint32_t lo_bits, unsigned long long count, unsigned long long *out) {
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (unsigned long long)gridDim.x * blockDim.x) {
+        const uint32_t bits = lo_bits + (uint32_t)i;
+        const float x = rptm::u2f(bits);
+        if (rptm::f2u(window ? rptm::rcp_rn_window(x) : rptm::rcp_rn(x)) != rptm::f2u(1.0f / x)) {
+            atomicAdd(&out[0], 1ull);
+            const unsigned long long k = atomicAdd(&out[1], 1ull);
+            if (k < 64ull) out[2 + k] = bits;
+        }
+    }
+}
+
+int rpt_debug_rcp_sweep(rpt_ctx *c, int window, uint32_t lo_bits, uint64_t count, uint64_t *mismatches_out, uint32_t *bad_bits_out /* [64] */) {
+    if (!c || !mismatches_out || !bad_bits_out || count > 0x100000000ull) return RPT_EINVAL;
+    HIP_TRY(c, hipSetDevice(c->device));
+    DevBuf<unsigned long long> d;
+    HIP_TRY(c, d.alloc(66));
+    unsigned long long h[66] = {};
+    HIP_TRY(c, hipMemcpy(d.p, h, sizeof(h), hipMemcpyHostToDevice));
+    k_debug_rcp_sweep<<<4096, 256, 0, c->stream>>>(window, lo_bits, (unsigned long long)count, d.p);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(h, d.p, sizeof(h), hipMemcpyDeviceToHost));
+    *mismatches_out = h[0];
+    for (int k = 0; k < 64; ++k) bad_bits_out[k] = (uint64_t)k < h[0] ? (uint32_t)h[2 + k] : 0xffffffffu;
+    return RPT_OK;
+}
+
+__global__ void k_debug_rcp(int window, const float *x, float *out, size_t n) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = window ? rptm::rcp_rn_window(x[i]) : rptm::rcp_rn(x[i]);
+}
+
+int rpt_debug_rcp(rpt_ctx *c, int window, const float *x, float *out, size_t n) {
+    if (!c || !x || !out) return RPT_EINVAL;
+    if (n == 0) return RPT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    DevBuf<float> dx, dout;
+    HIP_TRY(c, dx.from_host(x, n)); HIP_TRY(c, dout.alloc(n));
+    k_debug_rcp<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(window, dx.p, dout.p, n);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(out, dout.p, n * 4, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+
 int rpt_debug_bsdf(rpt_ctx *c, int kind, size_t n, const float *in, float *out) {
     if (!c || kind < 0 || kind > 3 || !in || !out) return RPT_EINVAL;
     if (n == 0) return RPT_OK;

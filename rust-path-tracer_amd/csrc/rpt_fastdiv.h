@@ -23,6 +23,7 @@
 #define RPT_FASTDIV_H
 
 #include "rpt_math.h"
+#include "rpt_rcp.h"
 
 namespace rptm {
 
@@ -45,7 +46,7 @@ RPT_HD bool fastdiv_operand_ok(float v) {
 /* (b - o) / y exactly as the slab test computes it, choosing the fast path when allowed (test hook) */
 RPT_HD float slab_quotient(float b, float o, float y) {
     float x = b - o;
-    if (fastdiv_divisor_ok(y) && fastdiv_operand_ok(b) && fastdiv_operand_ok(o)) return div_by_rcp(x, y, 1.0f / y);
+    if (fastdiv_divisor_ok(y) && fastdiv_operand_ok(b) && fastdiv_operand_ok(o)) return div_by_rcp(x, y, rcp_rn_window(y));
     return x / y;
 }
 

@@ -50,6 +50,7 @@
 
 #include "../../include/rpt/shared_structs.h"
 #include "rpt_math.h"
+#include "rpt_rcp.h"
 
 #define SHADOW_PROBE_RAYS 4096     /* candidates; about half survive the "decides something" filter */
 #define SHADOW_FIXED_GAIN 0.95
@@ -152,7 +153,7 @@ RPT_HD bool tri_test(V a, V e1, V e2, V o, V d, float max_t) {
     V p = cross(d, e2);
     float det = dot(e1, p);
     if (absf(det) < 1e-6f) return false;
-    float inv = 1.0f / det;
+    float inv = rptm::rcp_rn(det);
     V tv = sub(o, a);
     float u = dot(tv, p) * inv;
     if (u < 0.0f || u > 1.0f) return false;
@@ -295,7 +296,7 @@ RPT_HD uint32_t walk(const View &s, const uint8_t *flip, V o, V d, float max_t, 
     int sp = 0;
     uint32_t visits = 0, node = 0;
     occluded = false;
-    const V id{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
+    const V id{rptm::rcp_rn(d.x), rptm::rcp_rn(d.y), rptm::rcp_rn(d.z)};
     for (;;) {
         visits += 1;
         const rpt_bvh_node &n = s.nodes[node];

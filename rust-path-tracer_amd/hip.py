@@ -270,6 +270,8 @@ PROTOTYPES = {
     "rpt_debug_shadow_order_host": (C.c_int, [C.c_void_p, C.c_size_t] * 5 + [_OUT_U32, _OUT_F64, _OUT_F64, _OUT_U32, C.c_void_p]),
     "rpt_debug_last_order_host": (C.c_int, [C.c_void_p, C.c_size_t] * 4 + [_OUT_U32, _OUT_F64, _OUT_U32, C.c_void_p]),
     "rpt_debug_math_sweep": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_float, _OUT_U64, _OUT_U32]),
+    "rpt_debug_rcp": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rpt_debug_rcp_sweep": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, _OUT_U64, C.c_void_p]),
     "rpt_debug_trace_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t] + [C.c_void_p] * 6),
     "rpt_debug_trace_rays_production": (C.c_int, [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5),
     "rpt_debug_bsdf": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -757,6 +759,19 @@ class Renderer(_Handle):
         bad, first = C.c_uint64(), C.c_uint32()
         self._check(lib().rpt_debug_math_sweep(self._h, op, lo_bits, count, y, C.byref(bad), C.byref(first)))
         return bad.value, first.value
+
+    def debug_rcp(self, x, window=False):
+        """rpt_debug_rcp: rptm::rcp_rn (window: rcp_rn_window) of csrc/rpt_rcp.h on the device, elementwise."""
+        x = np.ascontiguousarray(x, np.float32)
+        out = np.empty_like(x)
+        self._check(lib().rpt_debug_rcp(self._h, 1 if window else 0, ptr(x), ptr(out), x.size))
+        return out
+
+    def debug_rcp_sweep(self, lo_bits, count, window=False):
+        """rpt_debug_rcp_sweep: (differences, up to 64 of the differing bit patterns) of rcp_rn (window: rcp_rn_window) vs the device's own 1.0f / x."""
+        bad, where = C.c_uint64(), np.zeros(64, np.uint32)
+        self._check(lib().rpt_debug_rcp_sweep(self._h, 1 if window else 0, lo_bits, count, C.byref(bad), ptr(where)))
+        return bad.value, where[: min(bad.value, 64)]
 
     def debug_bsdf(self, kind, items):
         """Lambertian / Glass of kernels/src/bsdf.rs:46-176 on the device (rpt_debug_bsdf): (n, 16) in -> (n, 8) out."""
