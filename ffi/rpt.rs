@@ -119,6 +119,18 @@ pub struct rpt_material_model {
     pub reserved: [u32; 2],
 }
 
+/// rpt_guides_info_get: the setting of rpt_set_guides_through_glass and what the last guide build did
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct rpt_guides_info {
+    pub max_interfaces: u32,        // the setting: 0 first-hit guides (default), 1..=8 follow glass through that many interfaces
+    pub rounds: u32,                // walks of the last build (0: none yet)
+    pub rays: [u32; 9],             // rays walked per round
+    pub pixels_through_glass: u32,  // pixels whose chain crossed at least one interface
+    pub pixels_exhausted: u32,      // pixels whose chain ended on a glass surface
+    pub reserved: [u32; 3],
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
 pub struct rpt_noise_counts {
@@ -202,6 +214,10 @@ extern "C" {
     pub fn rpt_denoise_temporal(ctx: *mut rpt_ctx, source: u32, moments_xyzw: *const f32, params: *const rpt_temporal_params, tonemap_op: u32, out_rgb: *mut f32, out_variance: *mut f32, out_history: *mut f32, report: *mut rpt_temporal_report) -> c_int;
     pub fn rpt_temporal_reset(ctx: *mut rpt_ctx) -> c_int;                          // forget and free the history
     pub fn rpt_read_guides(ctx: *mut rpt_ctx, albedo_rgb: *mut f32, normal_xyz: *mut f32, depth: *mut f32, position_xyz: *mut f32, kind: *mut u32) -> c_int;   // each nullable; albedo / normal = OIDN's auxiliary images
+    // opt-in: the guides follow Glass materials through up to max_interfaces (0..=8, default 0 = first-hit guides) interfaces to the surface seen through them
+    pub fn rpt_set_guides_through_glass(ctx: *mut rpt_ctx, max_interfaces: u32) -> c_int;
+    pub fn rpt_guides_through_glass(ctx: *mut rpt_ctx, max_interfaces_out: *mut u32) -> c_int;
+    pub fn rpt_guides_info_get(ctx: *mut rpt_ctx, out: *mut rpt_guides_info) -> c_int;
     // opt-in per-pixel sample moments (sum Y, sum Y^2, n, max Y), the noise estimate from them, and "render until the image is this clean"
     pub fn rpt_set_moments(ctx: *mut rpt_ctx, on: u32) -> c_int;                    // default 0; on: allocates and zeroes the record
     pub fn rpt_moments(ctx: *mut rpt_ctx, on_out: *mut u32) -> c_int;
@@ -236,7 +252,8 @@ extern "C" {
     pub fn rpt_multi_reset(m: *mut rpt_multi, rng_seed: *const UVec2, accum_init: *const Vec4, samples_init: u32) -> c_int;
     pub fn rpt_multi_set_shadow_mode(m: *mut rpt_multi, mode: u32) -> c_int;       // rpt_set_shadow_mode on every rank
     pub fn rpt_multi_set_material_models(m: *mut rpt_multi, models: *const rpt_material_model, n_models: usize) -> c_int;   // rpt_set_material_models on every rank
-    pub fn rpt_multi_render(m: *mut rpt_multi, n_samples: u32) -> c_int;            // one batch on every GPU + the batch's single RCCL gather
+    pub fn rpt_multi_set_guides_through_glass(m: *mut rpt_multi, max_interfaces: u32) -> c_int;   // rpt_set_guides_through_glass on every rank
+    pub fn rpt_multi_render(m: *mut rpt_multi, n_samples: u32) -> c_int;           // one batch on every GPU + the batch's single RCCL gather
     pub fn rpt_multi_wait(m: *mut rpt_multi) -> c_int;
     pub fn rpt_multi_read_accum(m: *mut rpt_multi, out: *mut Vec4, out_samples: *mut u32) -> c_int;   // the whole W x H image, from rank 0
     pub fn rpt_multi_denoise(m: *mut rpt_multi, params: *const rpt_denoise_params, tonemap_op: u32, out_rgb: *mut f32, report: *mut rpt_denoise_report) -> c_int;   // waits, gathers, denoises on rank 0

@@ -344,8 +344,8 @@ int rpt_shadow_mode(rpt_ctx *ctx, uint32_t *mode_out);
  * record (ignored on the others), a count that is not the scene's, a call before a scene.  While every record is PBR, or none is set, the kernels launched are
  * the ones launched without this call.  `reserved` is ignored.
  * rpt_material_models: the records as set (n_out = 0: none), out nullable, capacity in records.
- * The denoiser's guides (rpt_read_guides) stay first-hit guides: a glass pixel's guide is the glass surface — kind 1, albedo what the BSDF carries
- * (get_pbr_bsdf's) — not what is seen through it.
+ * The denoiser's guides (rpt_read_guides) are first-hit guides by default: a glass pixel's guide is the glass surface — kind 1, albedo what the BSDF carries
+ * (get_pbr_bsdf's).  rpt_set_guides_through_glass (with the denoiser, below) makes them follow glass to the surface seen through it.
  * Not carried: by rpt_world_save's .rptscene cache and by the host mirror rpt_trace_gpu (rpt_host.h). */
 enum { RPT_MODEL_PBR = 0, RPT_MODEL_LAMBERTIAN = 1, RPT_MODEL_GLASS = 2 };
 typedef struct rpt_material_model { uint32_t model; float ior; uint32_t reserved[2]; } rpt_material_model;
@@ -410,6 +410,52 @@ int rpt_denoise(rpt_ctx *ctx, uint32_t source, const rpt_denoise_params *params 
 int rpt_read_guides(rpt_ctx *ctx, float *albedo_rgb, float *normal_xyz, float *depth, float *position_xyz, uint32_t *kind);
 /* waits, gathers as rpt_multi_read_accum does, and denoises on rank 0 */
 int rpt_multi_denoise(rpt_multi *m, const rpt_denoise_params *params, uint32_t tonemap_op, float *out_rgb, rpt_denoise_report *report);
+
+/* --- guides that follow glass to the surface seen through it ---------------------------------------------------------------------------------------------
+ * Opt-in, default off: with max_interfaces = 0 the guides, the kernels that build them and their bytes are what they were.  A first-hit guide of a pixel that
+ * looks through a pane or a lens is the glass surface — kind 1, the glass's tint, its smooth normal, its depth, all nearly constant across the pane — while
+ * the radiance there is an image of what lies behind: the passes find no edge and blur it, demodulation divides by the tint instead of the albedo behind, and
+ * the firefly clamp's window mixes an emitter seen through glass with the wall beside it.
+ * With K = max_interfaces in 1..8 the guide of a pixel is the end of a deterministic chain (csrc/k_guides_glass.h dn_glass_step).  From the
+ * centre ray, with A = (1,1,1), L = 0, m = 0, per nearest hit (t, triangle) of the current ray (ro, rd):
+ *   miss                                kind 0, normal (0,0,0), albedo A, L += 1e6; done
+ *   hit                                 shaded as the first-hit guide: n = the normalised shading normal (zero if not finite), a = the albedo ((1,1,1) on an
+ *                                       emitter), L += t
+ *   emitter, record not Glass, no records    that kind, n, albedo A * a; done
+ *   Glass and m == K, or n == 0         the budget is exhausted: kind 1, n, albedo A * a — the glass surface itself; done
+ *   Glass and m < K                     view = -rd; inside = n . view < 0; n' = inside ? -n : n; (in_ior, out_ior) = inside ? (ior, 1) : (1, ior); c = view . n';
+ *                                       F = f0 + (1 - f0) (1 - max(c, 0))^5, f0 = ((in_ior - out_ior) / (in_ior + out_ior))^2   (Glass::sample at zero
+ *                                       roughness, bsdf.rs:128-165, the microsurface normal = n);
+ *                                       F > 0.5: dir = normalize(2 |c| n' - view), A unchanged;
+ *                                       else eta = in_ior / out_ior, dir = normalize((eta c - signum(c) sqrt(max(1 + eta (c c - 1), 0))) n' - eta view), A = A * a
+ *                                       (the reference's clamped root: total internal reflection degrades as the tracer's does);
+ *                                       ro = hit + dir * 0.001, rd = dir, m += 1; a dir that is not finite counts as an exhausted budget
+ * The chain uses the NORMALISED shading normal where the tracer hands its BSDF the un-normalised one (lib.rs:125): it is a guide, not a sample.  L sums the
+ * hit distances only, not the 0.001 shifts of the origin.  The records of the final values, (ro0, rd0) the centre ray:
+ *   normal, albedo = A * a (A on a miss), kind in {0, 1, 2} as before, depth = L, position = ro0 + rd0 * L
+ * — the point at optical path length L UNFOLDED ALONG THE PRIMARY RAY, not the hit point: it lies on the pixel's own ray, so the temporal reprojection stays
+ * self-consistent and depth stays the distance the footprint grows with.  Behind a flat pane it differs from the true point by the pane's small lateral
+ * shift; through a lens the unfolded positions are distorted, the plane term then rejects more taps and the filter is weaker there, not wrong.
+ * A pixel whose chain meets no glass, and every pixel while no record is Glass, has the first-hit guide byte for byte (then the first-hit kernels are the ones
+ * launched).  The filters, the temporal kernel and the firefly clamp are unchanged: they read the same records.
+ * Cost: one walk of the whole image, then one walk per further round of only the rays still inside glass, compacted in ascending ray order; at most K + 1.
+ * rpt_set_guides_through_glass   0..8; above: RPT_EINVAL, the setting stays.  Callable at any time; a change marks the guides stale.  While it is above 0,
+ *                                rpt_set_material_models marks them stale too.  Survives rpt_upload_scene and rpt_set_config.  rpt_multi_: on every rank.
+ * rpt_guides_info_get            the setting and the last build: rounds = walks made (0 before any build), rays[r] = rays walked in round r,
+ *                                pixels_through_glass = pixels whose chain crossed at least one interface, pixels_exhausted = pixels whose chain ended on a
+ *                                glass surface (budget, zero normal or a direction that is not finite). */
+typedef struct rpt_guides_info {
+    uint32_t max_interfaces;
+    uint32_t rounds;
+    uint32_t rays[9];
+    uint32_t pixels_through_glass;
+    uint32_t pixels_exhausted;
+    uint32_t reserved[3];
+} rpt_guides_info;
+int rpt_set_guides_through_glass(rpt_ctx *ctx, uint32_t max_interfaces);     /* default 0 */
+int rpt_guides_through_glass(rpt_ctx *ctx, uint32_t *max_interfaces_out);
+int rpt_guides_info_get(rpt_ctx *ctx, rpt_guides_info *out);
+int rpt_multi_set_guides_through_glass(rpt_multi *m, uint32_t max_interfaces);
 
 /* --- per-pixel sample moments, noise estimate, render to a noise target (no reference equivalent: `samples` is the only progress figure of the reference's
  * TracingState, src/trace.rs:40-50) ------------------------------------------------------------------------------------------------------------------

@@ -113,6 +113,20 @@ int rpt_debug_firefly_host(uint32_t width, uint32_t height, const float *mean_rg
                            const float *counts, uint32_t samples, float clamp_scale, float clamp_floor, uint32_t clamp_radius, uint32_t demodulated,
                            float *out_rgb, float *out_moments_xyzw, uint8_t *out_mask);
 
+/* One step of the chain of rpt_set_guides_through_glass on the HOST: the same header (csrc/k_guides_glass.h dn_glass_step) in a plain loop over n rays — no
+ * device needed, so a test can drive whole chains with any nearest-hit walk (the oracle's).  The scene as rpt_upload_scene takes it, without the tree and the
+ * lights; models: one record per material, or NULL for "every material is PBR"; max_interfaces 0..8.  Per ray: origins_xyz, dirs_xyz (3 floats; overwritten
+ * with the next ray where the chain goes on), its nearest hit as rpt_debug_trace_rays reports it, and the chain so far — chain_albedo (A, 3 floats; a fresh
+ * chain: 1, 1, 1), chain_length (L; 0), chain_interfaces (m; 0) — all three updated in place (a final chain's chain_length is the guide's depth).
+ * active_out: 1 = the chain goes on into the next round; else kind_out, normal_out, albedo_out (A * a) hold the final records and exhausted_out says whether
+ * it ended on a glass surface.  position = primary origin + primary direction * chain_length is the caller's.  RPT_EINVAL for null pointers, a triangle, vertex
+ * or material index out of range, max_interfaces above 8, a texture flag without an atlas. */
+int rpt_debug_glass_step_host(const rpt_per_vertex_data *vertices, size_t n_vertices, const rpt_triangle *indices, size_t n_triangles,
+                              const rpt_material_data *materials, size_t n_materials, const uint8_t *atlas_rgba8, uint32_t atlas_w, uint32_t atlas_h,
+                              const rpt_material_model *models, uint32_t max_interfaces, size_t n, float *origins_xyz, float *dirs_xyz, const float *hit_t,
+                              const uint32_t *hit_tri, const uint32_t *hit_flags, float *chain_albedo, float *chain_length, uint32_t *chain_interfaces,
+                              uint8_t *active_out, uint32_t *kind_out, float *normal_out, float *albedo_out, uint8_t *exhausted_out);
+
 /* noise_rel and the counts of rpt_noise_count on the HOST: the same header (csrc/k_moments.h) in a plain loop over n moments records (4 floats each: sum Y,
  * sum Y^2, n, max Y) — no device needed.  rel_out (n floats) and counts_out are nullable; counts_out->pixels = n.  RPT_EINVAL for a negative or NaN threshold. */
 int rpt_debug_noise_host(const float *moments_xyzw, size_t n, float threshold, float *rel_out, rpt_noise_counts *counts_out);

@@ -155,6 +155,8 @@ struct DenoiseState {
     DevBuf<uint32_t> order;               /* x | y << 16 of every pixel of the image in tile order (rank 0 of 1): a wave of guide rays is an 8 x 8 block */
     uint32_t width = 0, height = 0;       /* what the buffers are sized for */
     bool guides_valid = false;
+    uint32_t through_glass = 0;           /* rpt_set_guides_through_glass: the budget of interfaces K (k_guides_glass.h); 0: first-hit guides */
+    rpt_guides_info info = {};            /* the last build, for rpt_guides_info_get (max_interfaces is filled in when asked) */
     /* rpt_denoise_temporal (k_temporal.h): the two history slots, allocated at its first use, freed by rpt_temporal_reset, a resize and destroy */
     TemporalSlot last, previous;          /* what the most recent call produced; the history from before the current accumulator epoch */
     DevBuf<float> history_t;              /* W x H: T per pixel, before it leaves the device */

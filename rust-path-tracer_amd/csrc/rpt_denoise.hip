@@ -9,6 +9,7 @@
 
 #include "rpt_ctx.h"
 #include "k_denoise.h"
+#include "k_guides_glass.h"
 #include "k_adaptive.h"
 #include "k_temporal.h"
 #include "k_firefly.h"
@@ -77,7 +78,64 @@ int ensure_buffers(rpt_ctx *c) {
     return RPT_OK;
 }
 
-/* the guides of (scene, configuration), on the context's stream; *rebuilt = they were stale.  The rays and their hits live for this call only. */
+/* rpt_set_guides_through_glass: the guides of a context whose setting is above 0 and some of whose records are Glass (k_guides_glass.h) — rounds of one walk
+ * of the rays still inside glass and one step kernel, the survivors compacted in ascending order between them.  One 16-byte read per round sizes the next
+ * launch; a round with no ray launches nothing.  The caller has waited for the batches. */
+template <bool TEXTURED>
+int build_guides_through_glass(rpt_ctx *c) {
+    DenoiseState &d = c->dn;
+    const uint32_t n = d.width * d.height, K = d.through_glass, blocks = rpt_blocks(n);
+    const size_t vec = Arena::pad(3 * (size_t)n * sizeof(float)), word = Arena::pad((size_t)n * sizeof(uint32_t));
+    Arena rays;
+    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{c->stream};      /* (destroyed before the arena: no exit frees rays a kernel still reads) */
+    HIP_TRY(c, rays.reserve(6 * vec + 6 * word + Arena::pad((size_t)n * sizeof(float4)) + Arena::pad(n) + 2 * Arena::pad((size_t)blocks * sizeof(uint32_t)) + Arena::pad(sizeof(GgResult))));
+    float *origins0 = rays.take<float>(3 * (size_t)n), *dirs0 = rays.take<float>(3 * (size_t)n);                    /* the centre rays: round 0, and every position */
+    float *next_o = rays.take<float>(3 * (size_t)n), *next_d = rays.take<float>(3 * (size_t)n);                     /* a round's rays that go on, at their own index */
+    float *cur_o = rays.take<float>(3 * (size_t)n), *cur_d = rays.take<float>(3 * (size_t)n);                       /* ... compacted: the next round's rays */
+    float *hit_t = rays.take<float>(n);
+    uint32_t *hit_tri = rays.take<uint32_t>(n), *hit_flags = rays.take<uint32_t>(n), *next_slot = rays.take<uint32_t>(n), *cur_slot = rays.take<uint32_t>(n);
+    uint32_t *interfaces = rays.take<uint32_t>(n);
+    float4 *chain = rays.take<float4>(n);
+    uint8_t *flags = rays.take<uint8_t>(n);
+    uint32_t *wg_count = rays.take<uint32_t>(blocks), *wg_offset = rays.take<uint32_t>(blocks);
+    GgResult *res = rays.take<GgResult>(1);
+    const GgScene gs{c->scene.tri_geom, c->scene.tri_shade, c->scene.tri_tangent, c->scene.materials, c->scene.mat_lite, reinterpret_cast<const uint32_t *>(c->scene.atlas.texels),
+                     c->scene.atlas.width, c->scene.atlas.height};
+    const uint4 *models = reinterpret_cast<const uint4 *>(c->material_models.p);
+    const GgNext next{next_o, next_d, next_slot, chain, interfaces, flags, wg_count};
+    hipStream_t s = c->stream;
+    d.info = rpt_guides_info{};
+    GgResult got{};
+    HIP_TRY(c, hipEventRecord(d.ev[0], s));
+    HIP_TRY(c, hipMemsetAsync(res, 0, sizeof(GgResult), s));
+    k_dn_camera_rays<<<blocks, RPT_BLOCK, 0, s>>>(c->cfg, d.order.p, n, origins0, dirs0);
+    uint32_t n_cur = n;
+    for (uint32_t round = 0; round <= K && n_cur != 0u; ++round) {        /* (a ray of round r has crossed r interfaces: round K ends every chain) */
+        const GgRays in{round ? cur_o : origins0, round ? cur_d : dirs0, round ? cur_slot : nullptr, hit_t, hit_tri, hit_flags};
+        rpt_launch_trace_debug(c, 0, n_cur, in.origins, in.dirs, nullptr, hit_t, hit_tri, hit_flags);
+        k_dn_glass_step<TEXTURED><<<rpt_blocks(n_cur), RPT_BLOCK, 0, s>>>(gs, models, K, round == 0u ? 1u : 0u, d.width, d.order.p, n_cur, in, origins0, dirs0, next, d.g0.p, d.g1.p,
+                                                                         d.albedo.p, res);
+        d.info.rays[round] = n_cur;
+        d.info.rounds = round + 1u;
+        if (round == K) break;
+        k_dn_glass_scan<<<1, RPT_BLOCK, 0, s>>>(wg_count, rpt_blocks(n_cur), wg_offset, res);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(&got, res, sizeof got, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        const uint32_t n_next = got.n_active <= n_cur ? got.n_active : n_cur;
+        if (n_next != 0u) k_dn_glass_scatter<<<rpt_blocks(n_cur), RPT_BLOCK, 0, s>>>(n_cur, flags, wg_offset, n_next, next_o, next_d, next_slot, cur_o, cur_d, cur_slot);
+        n_cur = n_next;
+    }
+    HIP_TRY(c, hipEventRecord(d.ev[1], s));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(&got, res, sizeof got, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));             /* (before the rays and the chains are freed) */
+    d.info.pixels_through_glass = got.crossed;
+    d.info.pixels_exhausted = got.exhausted;
+    return RPT_OK;
+}
+
+/* the guides of (scene, configuration, setting), on the context's stream; *rebuilt = they were stale.  The rays and their hits live for this call only. */
 int ensure_guides(rpt_ctx *c, bool *rebuilt) {
     DenoiseState &d = c->dn;
     *rebuilt = false;
@@ -85,6 +143,17 @@ int ensure_guides(rpt_ctx *c, bool *rebuilt) {
     if (d.guides_valid) return RPT_OK;
     RPT_TRY(rpt_wait(c));                            /* the walk shares the context's stream (and LDS) with the batches */
     const uint32_t n = d.width * d.height;
+    bool some_glass = false;
+    for (const rpt_material_model &m : c->material_models_host) some_glass = some_glass || m.model == RPT_MODEL_GLASS;
+    if (d.through_glass != 0u && some_glass) {       /* otherwise: exactly the launches below, as before the setting existed */
+        RPT_TRY(c->scene.textured ? build_guides_through_glass<true>(c) : build_guides_through_glass<false>(c));
+        d.guides_valid = true;
+        *rebuilt = true;
+        return RPT_OK;
+    }
+    d.info = rpt_guides_info{};
+    d.info.rounds = 1u;
+    d.info.rays[0] = n;
     Arena rays;
     HIP_TRY(c, rays.reserve(2 * Arena::pad(3 * (size_t)n * sizeof(float)) + 3 * Arena::pad((size_t)n * sizeof(uint32_t))));
     float *origins = rays.take<float>(3 * (size_t)n), *dirs = rays.take<float>(3 * (size_t)n), *hit_t = rays.take<float>(n);
@@ -508,6 +577,91 @@ int rpt_read_guides(rpt_ctx *c, float *albedo_rgb, float *normal_xyz, float *dep
     if (position_xyz) HIP_TRY(c, hipMemcpy(position_xyz, d_position, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     if (depth) HIP_TRY(c, hipMemcpy(depth, d_depth, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     if (kind) HIP_TRY(c, hipMemcpy(kind, d_kind, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+
+int rpt_set_guides_through_glass(rpt_ctx *c, uint32_t max_interfaces) {
+    if (!c) return RPT_EINVAL;
+    if (max_interfaces > RPT_GG_MAX_INTERFACES) { c->error = "rpt_set_guides_through_glass: max_interfaces must be 0..8"; return RPT_EINVAL; }
+    if (c->dn.through_glass != max_interfaces) c->dn.guides_valid = false;
+    c->dn.through_glass = max_interfaces;
+    return RPT_OK;
+}
+
+int rpt_guides_through_glass(rpt_ctx *c, uint32_t *max_interfaces_out) {
+    if (!c) return RPT_EINVAL;
+    if (!max_interfaces_out) { c->error = "rpt_guides_through_glass: max_interfaces_out is null"; return RPT_EINVAL; }
+    *max_interfaces_out = c->dn.through_glass;
+    return RPT_OK;
+}
+
+int rpt_guides_info_get(rpt_ctx *c, rpt_guides_info *out) {
+    if (!c) return RPT_EINVAL;
+    if (!out) { c->error = "rpt_guides_info_get: out is null"; return RPT_EINVAL; }
+    *out = c->dn.info;
+    out->max_interfaces = c->dn.through_glass;
+    return RPT_OK;
+}
+
+/* one step of the chain on the host: the loop k_dn_glass_step is, over the same RPT_HD function; the records of the triangle at hand as k_derive_triangles
+ * (rpt_scene.hip) derives them */
+int rpt_debug_glass_step_host(const rpt_per_vertex_data *vertices, size_t n_vertices, const rpt_triangle *indices, size_t n_triangles, const rpt_material_data *materials,
+                              size_t n_materials, const uint8_t *atlas_rgba8, uint32_t atlas_w, uint32_t atlas_h, const rpt_material_model *models, uint32_t max_interfaces, size_t n,
+                              float *origins_xyz, float *dirs_xyz, const float *hit_t, const uint32_t *hit_tri, const uint32_t *hit_flags, float *chain_albedo, float *chain_length,
+                              uint32_t *chain_interfaces, uint8_t *active_out, uint32_t *kind_out, float *normal_out, float *albedo_out, uint8_t *exhausted_out) {
+    if (!vertices || !indices || !materials || !origins_xyz || !dirs_xyz || !hit_t || !hit_tri || !hit_flags || !chain_albedo || !chain_length || !chain_interfaces || !active_out ||
+        !kind_out || !normal_out || !albedo_out || !exhausted_out)
+        return RPT_EINVAL;
+    if (max_interfaces > RPT_GG_MAX_INTERFACES) { rpt_create_error() = "rpt_debug_glass_step_host: max_interfaces must be 0..8"; return RPT_EINVAL; }
+    bool textured = false;
+    std::vector<float4> lite(2 * n_materials);
+    for (size_t i = 0; i < n_materials; ++i) {
+        const rpt_material_data &m = materials[i];
+        lite[2 * i + 0] = make_float4(m.emissive[0], m.emissive[1], m.emissive[2], m.roughness[0]);
+        lite[2 * i + 1] = make_float4(m.albedo[0], m.albedo[1], m.albedo[2], m.metallic[0]);
+        if (m.has_albedo_texture | m.has_metallic_texture | m.has_roughness_texture | m.has_normal_texture) textured = true;
+    }
+    if (textured && (!atlas_rgba8 || atlas_w == 0u || atlas_h == 0u)) { rpt_create_error() = "rpt_debug_glass_step_host: a material has a texture flag and there is no atlas"; return RPT_EINVAL; }
+    static_assert(sizeof(rpt_material_data) == 6 * sizeof(float4) && sizeof(rpt_material_model) == sizeof(uint4), "the records are read as float4 / uint4");
+    float4 geom[3], shade[4], tangent[3];
+    const GgScene gs{geom, shade, tangent, reinterpret_cast<const float4 *>(materials), lite.data(), reinterpret_cast<const uint32_t *>(atlas_rgba8), atlas_w, atlas_h};
+    for (size_t i = 0; i < n; ++i) {
+        const bool is_hit = (hit_flags[i] & 1u) != 0u;
+        if (is_hit) {
+            if (hit_tri[i] >= n_triangles) { rpt_create_error() = "rpt_debug_glass_step_host: a triangle index is out of range"; return RPT_EINVAL; }
+            const rpt_triangle &t = indices[hit_tri[i]];
+            if (t.v0 >= n_vertices || t.v1 >= n_vertices || t.v2 >= n_vertices || t.material >= n_materials) { rpt_create_error() = "rpt_debug_glass_step_host: a vertex or material index is out of range"; return RPT_EINVAL; }
+            const rpt_per_vertex_data &A = vertices[t.v0], &B = vertices[t.v1], &C = vertices[t.v2];
+            const float *a = A.vertex, *b = B.vertex, *cc = C.vertex;
+            const float e1x = b[0] - a[0], e1y = b[1] - a[1], e1z = b[2] - a[2];
+            const float e2x = cc[0] - a[0], e2y = cc[1] - a[1], e2z = cc[2] - a[2];
+            geom[0] = make_float4(a[0], a[1], a[2], (e1x * e1x + e1y * e1y) + e1z * e1z);
+            geom[1] = make_float4(e1x, e1y, e1z, (e1x * e2x + e1y * e2y) + e1z * e2z);
+            geom[2] = make_float4(e2x, e2y, e2z, (e2x * e2x + e2y * e2y) + e2z * e2z);
+            shade[0] = make_float4(A.normal[0], A.normal[1], A.normal[2], A.uv0[0]);
+            shade[1] = make_float4(B.normal[0], B.normal[1], B.normal[2], A.uv0[1]);
+            shade[2] = make_float4(C.normal[0], C.normal[1], C.normal[2], rptm::u2f(t.material));
+            shade[3] = make_float4(B.uv0[0], B.uv0[1], C.uv0[0], C.uv0[1]);
+            tangent[0] = make_float4(A.tangent[0], A.tangent[1], A.tangent[2], A.tangent[3]);
+            tangent[1] = make_float4(B.tangent[0], B.tangent[1], B.tangent[2], B.tangent[3]);
+            tangent[2] = make_float4(C.tangent[0], C.tangent[1], C.tangent[2], C.tangent[3]);
+        }
+        float *o = origins_xyz + 3 * i, *dd = dirs_xyz + 3 * i, *ca = chain_albedo + 3 * i;
+        const GgChain ch{f3(ca[0], ca[1], ca[2]), chain_length[i], chain_interfaces[i]};
+        const uint4 *mo = reinterpret_cast<const uint4 *>(models);
+        const GgStep s = textured ? dn_glass_step<true>(gs, mo, max_interfaces, f3(o[0], o[1], o[2]), f3(dd[0], dd[1], dd[2]), hit_t[i], 0u, is_hit, ch)
+                                  : dn_glass_step<false>(gs, mo, max_interfaces, f3(o[0], o[1], o[2]), f3(dd[0], dd[1], dd[2]), hit_t[i], 0u, is_hit, ch);
+        active_out[i] = s.final ? 0u : 1u;
+        exhausted_out[i] = s.final && s.exhausted ? 1u : 0u;
+        kind_out[i] = s.kind;
+        normal_out[3 * i] = s.normal.x; normal_out[3 * i + 1] = s.normal.y; normal_out[3 * i + 2] = s.normal.z;
+        albedo_out[3 * i] = s.albedo.x; albedo_out[3 * i + 1] = s.albedo.y; albedo_out[3 * i + 2] = s.albedo.z;
+        o[0] = s.ro.x; o[1] = s.ro.y; o[2] = s.ro.z;
+        dd[0] = s.rd.x; dd[1] = s.rd.y; dd[2] = s.rd.z;
+        ca[0] = s.chain.A.x; ca[1] = s.chain.A.y; ca[2] = s.chain.A.z;
+        chain_length[i] = s.chain.L;
+        chain_interfaces[i] = s.chain.m;
+    }
     return RPT_OK;
 }
 

@@ -71,6 +71,7 @@ int rpt_set_material_models(rpt_ctx *c, const rpt_material_model *models, size_t
     RPT_TRY(rpt_wait(c));
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->dn.through_glass != 0u) c->dn.guides_valid = false;       /* rpt_set_guides_through_glass: the guides follow the Glass records */
     if (!models) { rpt_material_models_clear(c); return RPT_OK; }
     if (c->material_models.n != n_models) HIP_TRY(c, c->material_models.alloc(n_models));
     HIP_TRY(c, hipMemcpy(c->material_models.p, models, n_models * sizeof(rpt_material_model), hipMemcpyHostToDevice));

@@ -87,7 +87,17 @@ class GatheredInfo(C.Structure):
                 ("reserved", C.c_uint32 * 3)]
 
 
-GATHER_FORMAT = 0x52504D32      # RPT_GATHER_FORMAT (rpt_debug.h): word 0 of a rank's trailer
+class GuidesInfo(C.Structure):
+    """rpt_guides_info"""
+    _fields_ = [("max_interfaces", C.c_uint32), ("rounds", C.c_uint32), ("rays", C.c_uint32 * 9), ("pixels_through_glass", C.c_uint32), ("pixels_exhausted", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+
+GUIDES_MAX_INTERFACES = 8       # rpt_set_guides_through_glass takes 0 .. 8; the setting ships off (0)
+# the recommended budget: the K of the lowest summed rel-L2 over the pixels that look through glass in profiles/r20_glass_guides_quality.txt
+# (tools/denoise_probe.py --quality-glass; tests/test_guides_glass.py holds it to that file)
+GUIDES_THROUGH_GLASS = 2
+GATHER_FORMAT = 0x52504D32     # RPT_GATHER_FORMAT (rpt_debug.h): word 0 of a rank's trailer
 
 
 def _gathered_info_dict(g):
@@ -235,6 +245,10 @@ PROTOTYPES = {
     "rpt_denoise": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(DenoiseParams), C.c_uint32, C.c_void_p, C.POINTER(DenoiseReport)]),
     "rpt_read_guides": (C.c_int, [C.c_void_p] + [C.c_void_p] * 5),
     "rpt_multi_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.c_uint32, C.c_void_p, C.POINTER(DenoiseReport)]),
+    "rpt_set_guides_through_glass": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rpt_guides_through_glass": (C.c_int, [C.c_void_p, _OUT_U32]),
+    "rpt_guides_info_get": (C.c_int, [C.c_void_p, C.POINTER(GuidesInfo)]),
+    "rpt_multi_set_guides_through_glass": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rpt_set_moments": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rpt_moments": (C.c_int, [C.c_void_p, _OUT_U32]),
     "rpt_read_moments": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -282,6 +296,7 @@ PROTOTYPES = {
     "rpt_debug_denoise_temporal_host": (C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 7 + [C.POINTER(TracingConfig), C.POINTER(TracingConfig)] + [C.c_void_p] * 4
                                         + [C.POINTER(TemporalParams), C.c_uint32] + [C.c_void_p] * 4 + [_OUT_U64]),
     "rpt_debug_firefly_host": (C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 5 + [C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.c_uint32] + [C.c_void_p] * 3),
+    "rpt_debug_glass_step_host": (C.c_int, [C.c_void_p, C.c_size_t] * 3 + [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_size_t] + [C.c_void_p] * 13),
     "rpt_debug_noise_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.POINTER(NoiseCounts)]),
     "rpt_debug_adaptive_select_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, _OUT_SIZE]),
     "rpt_debug_adaptive_window_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
@@ -431,6 +446,12 @@ class _Handle:
             return
         records = np.ascontiguousarray(records, MATERIAL_MODEL_DTYPE)
         self._call("set_material_models", ptr(records), len(records))
+
+    def set_guides_through_glass(self, max_interfaces):
+        """rpt_set_guides_through_glass (rpt_multi_: on every rank): 0 (default) first-hit guides; 1 .. GUIDES_MAX_INTERFACES: the denoiser's guides follow
+        MODEL_GLASS materials through that many interfaces to the surface seen through them (albedo = the tints crossed x that surface's, depth = the summed
+        path, position on the pixel's own ray).  The guides are rebuilt at their next use."""
+        self._call("set_guides_through_glass", max_interfaces)
 
     # -- per-pixel sample moments and the noise estimate (no reference equivalent; include/rpt/rpt.h "per-pixel sample moments")
     def set_moments(self, on=True):
@@ -582,11 +603,25 @@ class Renderer(_Handle):
         return self._denoise_temporal((source, ptr(moments)), params, tonemap_op, with_report)
 
     def guides(self):
-        """rpt_read_guides: the first-hit guide buffers of the current scene and camera:
+        """rpt_read_guides: the guide buffers of the current scene and camera (first-hit guides; after set_guides_through_glass(K > 0), the surface seen through glass):
         {"albedo", "normal", "position": (H, W, 3) float32, "depth": (H, W) float32, "kind": (H, W) uint32 (GUIDE_MISS / SURFACE / EMITTER)}"""
         g = {"albedo": self._image(3), "normal": self._image(3), "depth": self._image(), "position": self._image(3), "kind": self._image(dtype=np.uint32)}
         self._check(lib().rpt_read_guides(self._h, ptr(g["albedo"]), ptr(g["normal"]), ptr(g["depth"]), ptr(g["position"]), ptr(g["kind"])))
         return g
+
+    def guides_through_glass(self):
+        """rpt_guides_through_glass: the budget of interfaces the guides follow glass through (0: first-hit guides, the default)"""
+        k = C.c_uint32()
+        self._check(lib().rpt_guides_through_glass(self._h, C.byref(k)))
+        return k.value
+
+    def guides_info(self):
+        """rpt_guides_info_get: {"max_interfaces": the setting, "rounds": walks of the last guide build (0: none yet), "rays": rays walked per round (9 entries),
+        "pixels_through_glass": pixels whose chain crossed an interface, "pixels_exhausted": pixels whose chain ended on a glass surface}"""
+        g = GuidesInfo()
+        self._check(lib().rpt_guides_info_get(self._h, C.byref(g)))
+        return {"max_interfaces": g.max_interfaces, "rounds": g.rounds, "rays": list(g.rays), "pixels_through_glass": g.pixels_through_glass,
+                "pixels_exhausted": g.pixels_exhausted}
 
     def moments_on(self):
         on = C.c_uint32()
@@ -1001,6 +1036,34 @@ def denoise_host(mean_rgb, albedo, normal, position, depth, kind, params=None, t
     if rc != 0:
         raise RptError(rc, lib().rpt_last_error(None).decode())
     return out
+
+
+def glass_step_host(world, models, max_interfaces, origins, dirs, hit_t, hit_tri, hit_flags, chain_albedo, chain_length, chain_interfaces):
+    """rpt_debug_glass_step_host: one step of the chain of set_guides_through_glass for n rays, on the host from the same header (no GPU needed).  world: the
+    scene's arrays (per_vertex, indices, materials, atlas or None); models: MATERIAL_MODEL_DTYPE records or None; the rays (n, 3), their nearest hits and the
+    chains so far (A (n, 3), L (n), m (n)).  Nothing is changed in place: {"origins", "dirs": the next rays, "albedo_product", "length", "interfaces": the
+    chains after the step, "active": the chain goes on, "kind", "normal", "albedo": the final records where it does not, "exhausted"}."""
+    o, d = (np.array(a, np.float32).reshape(-1, 3) for a in (origins, dirs))
+    n = len(o)
+    t, tri, fl = np.ascontiguousarray(hit_t, np.float32), np.ascontiguousarray(hit_tri, np.uint32), np.ascontiguousarray(hit_flags, np.uint32)
+    A, L, m = np.array(chain_albedo, np.float32).reshape(-1, 3), np.array(chain_length, np.float32).reshape(-1), np.array(chain_interfaces, np.uint32).reshape(-1)
+    assert len(d) == len(t) == len(tri) == len(fl) == len(A) == len(L) == len(m) == n
+    models = None if models is None else np.ascontiguousarray(models, MATERIAL_MODEL_DTYPE)
+    assert models is None or len(models) == len(world.materials)
+    atlas = getattr(world, "atlas", None)
+    aw = ah = 0
+    if atlas is not None:
+        atlas = np.ascontiguousarray(atlas, np.uint8)
+        ah, aw = atlas.shape[:2]
+    active, exhausted, kind = np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+    normal, albedo = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+    rc = lib().rpt_debug_glass_step_host(ptr(world.per_vertex), len(world.per_vertex), ptr(world.indices), len(world.indices), ptr(world.materials), len(world.materials),
+                                         ptr(atlas), aw, ah, ptr(models), max_interfaces, n, ptr(o), ptr(d), ptr(t), ptr(tri), ptr(fl), ptr(A), ptr(L), ptr(m),
+                                         ptr(active), ptr(kind), ptr(normal), ptr(albedo), ptr(exhausted))
+    if rc != 0:
+        raise RptError(rc, lib().rpt_last_error(None).decode())
+    return {"origins": o, "dirs": d, "albedo_product": A, "length": L, "interfaces": m, "active": active != 0, "kind": kind, "normal": normal, "albedo": albedo,
+            "exhausted": exhausted != 0}
 
 
 def denoise_variance_host(mean_rgb, albedo, normal, position, depth, kind, moments, params=None, tonemap_op=0):

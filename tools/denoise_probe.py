@@ -40,6 +40,11 @@
                                                     DIR/rust-path-tracer_amd/lib/librpt_hip.so), whose clamp-off figures are taken between two runs of this build and
                                                     whose images are compared; RPT_VARIANT_LIB = a build of this commit with another clamp kernel (RPT_VARIANT_NAME
                                                     names it in the report), whose clamp-on figures are printed beside this build's
+  python tools/denoise_probe.py --quality-glass [out]   no GPU: guides that follow glass (rpt_set_guides_through_glass, K = 2, 4, 8) against first-hit guides on the room and
+                                                    the open scene of tests/model_scenes.py (128 x 128, 8 spp against 1024 spp of the restatement with models): rel-L2 over the
+                                                    pixels whose chain crossed glass and over the whole image, rpt_denoise and rpt_denoise_variance at their shipped
+                                                    defaults; writes profiles/r20_glass_guides_quality.txt; the K of the lowest summed error over the glass pixels is
+                                                    hip.GUIDES_THROUGH_GLASS (the setting ships off)
 """
 import hashlib
 import importlib
@@ -750,9 +755,81 @@ def gpu_firefly(out_path, parent_lib, variant_lib):
     print("\n".join(lines))
 
 
+GLASS_K = (0, 2, 4, 8)
+GLASS_SCENES = (("room", 1), ("open", 0))
+
+
+def quality_glass(out_path):
+    """guides that follow glass (rpt_set_guides_through_glass) against first-hit guides, on the CPU: the host filters take guide arrays"""
+    from oracle_ffi import Oracle
+    import denoise_var_ref
+    import guides_glass_ref
+    import model_scenes
+    rpt = importlib.import_module("rust-path-tracer_amd")
+    hip = importlib.import_module("rust-path-tracer_amd.hip")
+    orc = Oracle("rpt_math")
+    F = np.float32
+    W = H = 128
+    part = lambda img, ref, mask: float(np.linalg.norm((img.astype(np.float64) - ref)[mask]) / np.linalg.norm(ref.astype(np.float64)[mask]))
+    planes = lambda g: (g["albedo"], g["normal"], g["position"], g["depth"], g["kind"])
+    filters = (("rpt_denoise, defaults", lambda mean, g, m: hip.denoise_host(mean, *planes(g))),
+               ("rpt_denoise_variance, defaults", lambda mean, g, m: hip.denoise_variance_host(mean, *planes(g), m)[0]),
+               ("rpt_denoise_variance, sigma_variance 4", lambda mean, g, m: hip.denoise_variance_host(mean, *planes(g), m, hip.denoise_var_params(sigma_variance=4.0))[0]))
+    lines = ["Guides that follow glass (rpt_set_guides_through_glass) against first-hit guides (tools/denoise_probe.py --quality-glass): the material-model scenes of",
+             f"tests/model_scenes.py at {W} x {H}, the 8-spp mean of the restatement with models (tests/models_oracle) filtered by the host builds of the filters over the",
+             "guides of tests/guides_glass_ref.py (K = 0: the first-hit guides), rel-L2 against the restatement's 1024-spp mean over (a) the pixels whose chain crossed glass",
+             "and (b) the whole image.  K = max_interfaces.", ""]
+    sums = {}
+    for name, nee in GLASS_SCENES:
+        t0 = time.time()
+        world, rec, skybox, _ = model_scenes.scene(name)
+        cfg = model_scenes.config(name, nee, W, H)
+        sc = orc.scene(world, skybox_f32=skybox)
+        rng = rpt.blue_noise_seeds(W, H)
+        moments, noisy = np.zeros((H, W, 4), F), np.zeros((H, W, 4), F)
+        for _ in range(8):
+            s, rng, _ = model_scenes.models_trace_cpu(cfg, sc, rec, rng, 1)
+            denoise_var_ref.moments_add(moments, s[..., :3])
+            noisy = (noisy + s).astype(F)
+        rest, _, _ = model_scenes.models_trace_cpu(cfg, sc, rec, rng, 1024 - 8)
+        conv = ((noisy[..., :3].astype(np.float64) + rest[..., :3]) / 1024.0)
+        mean = (noisy[..., :3] / F(8)).astype(F)
+        guides = {K: guides_glass_ref.guides(world, rec, K, cfg, orc, sc) for K in GLASS_K}
+        finite = np.isfinite(mean).all(axis=-1) & np.isfinite(conv).all(axis=-1)      # (a sample that is not finite stays in both means: such pixels are left out)
+        through = (guides[8][0]["interfaces"] > 0) & finite
+        everything = finite
+        info = guides[8][1]
+        lines += [f"{name} (nee {nee}): {int(through.sum())} of {W * H} pixels look through glass ({int((~finite).sum())} pixels without a finite mean left out); rays per round at K = 8: {info['rays'][:info['rounds']]}; "
+                  f"ended on glass at K = 2 / 4 / 8: {' / '.join(str(guides[K][1]['pixels_exhausted']) for K in (2, 4, 8))}",
+                  f"  the 8-spp mean, unfiltered: (a) {part(mean, conv, through):.4f}  (b) {part(mean, conv, everything):.4f}"]
+        for label, run in filters:
+            row = []
+            for K in GLASS_K:
+                out = run(mean, guides[K][0], moments)
+                ea, eb = part(out, conv, through), part(out, conv, everything)
+                sums.setdefault((label, K), []).append(ea)
+                row.append(f"K = {K}: (a) {ea:.4f} (b) {eb:.4f}")
+            lines.append(f"  {label:40s} " + "   ".join(row))
+        lines.append("")
+        print(f"{name}: {time.time() - t0:.0f} s", flush=True)
+    lines.append("summed (a) over the scenes:")
+    best = None
+    for label, _ in filters:
+        lines.append(f"  {label:40s} " + "   ".join(f"K = {K}: {sum(sums[(label, K)]):.4f}" for K in GLASS_K))
+    for K in GLASS_K[1:]:
+        total = sum(sum(sums[(label, K)]) for label, _ in filters[:2])
+        if best is None or total < best[0]:
+            best = (total, K)
+    lines += ["", f"lowest summed (a) of K = 2, 4, 8 over the two shipped-default filters: K = {best[1]} (hip.GUIDES_THROUGH_GLASS; the setting ships off)"]
+    open(out_path, "w").write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
 if __name__ == "__main__":
     a = sys.argv[1:]
-    if "--workload-firefly" in a:
+    if a and a[0] == "--quality-glass":
+        quality_glass(a[1] if len(a) > 1 else os.path.join(ROOT, "profiles", "r20_glass_guides_quality.txt"))
+    elif "--workload-firefly" in a:
         gpu_firefly_child(a[a.index("--workload-firefly") + 1])
     elif a and a[0] == "--gpu-firefly":
         gpu_firefly(a[1] if len(a) > 1 else os.path.join(ROOT, "profiles", "r16_firefly.txt"), os.environ.get("RPT_PARENT_LIB"), os.environ.get("RPT_VARIANT_LIB"))
