@@ -128,7 +128,7 @@ struct DevScene {
 };
 
 /* constants of the traversal structures that the upload code (rpt_scene.hip) and the walk kernels (k_traverse.h, compiled in rpt_traverse.hip) share */
-#define LDS_DESC_DEAD 0x4000u      /* 16-bit child descriptor of the LDS image (k_walk.h SceneViewLds): pair index, or LEAF | count << 9 | first triangle */
+#define LDS_DESC_DEAD 0x4000u      /* 16-bit child descriptor of the LDS image (k_walk.h SceneViewLds): 4 x pair index, or LEAF | count << 9 | first triangle */
 #define LDS_DESC_LEAF 0x8000u
 #define RPT_LDS_SCENE_BYTES 32768  /* a traversal image up to this size lives in LDS (+ 32 KB of 16-bit stacks = the 64 KB of one of two workgroups per CU) */
 #define RPT_COOP_LEAF_MIN 6        /* leaves with more triangles than this are tested by the whole wave (global-memory scenes) */

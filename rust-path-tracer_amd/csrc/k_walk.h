@@ -233,12 +233,14 @@ struct SceneViewPairsT : TriRecords {
  *                   RN((hi-o)/d) are ordered by the sign of d (RN subtraction and division are monotone), so the
  *                   reference's six f32::min/max per box (intersection.rs:108-117) become one max3 and one min3,
  *                   value for value.  Rays outside the exact-division guard keep the explicit min/max on K_A.
- *   descriptors     D[p] = desc(L) | desc(R) << 16;  desc = pair index (< 0x4000) of an inner child,
+ *   descriptors     D[p] = desc(L) | desc(R) << 16;  desc = 4 x pair index (< 0x4000) of an inner child — the byte offset of
+ *                   D[p], a quarter of that of the pair's plane records (lds_at) —,
  *                   0x8000 | triangle_count << 9 | first_triangle for a leaf; 0x4000 marks a finished lane.
  *                   The 16-bit stack holds descriptors, so a pop is one ds_read_u16 — no node lookup.
- *   triangles       a[] | e1[] | e2[]  (16-byte records, one array each)
+ *   triangles       (a, e1, e2)[t]  (three 16-byte vectors per triangle, one after the other: one address register
+ *                   and immediate offsets serve the three loads of a triangle test)
  *
- * Every load instruction of a visit addresses "array base + 16 * p": the 16 lanes that ds_read_b128 serves per
+ * Every load instruction of a node visit addresses "array base + 16 * p": the 16 lanes that ds_read_b128 serves per
  * LDS cycle spread over all 64 banks instead of the 4 bank groups an array-of-nodes layout allows.
  * A node array that is not pair-shaped, has an empty/inverted box, or a leaf of 64+ triangles gets no image and
  * is traversed from global memory by the generic loop. */
@@ -254,11 +256,51 @@ struct SceneViewLds {
     __device__ __forceinline__ static bool is_dead(Cur c) { return c == LDS_DESC_DEAD; }      /* (as the two range tests of the other views the streamed kernels compile to other code) */
     __device__ __forceinline__ const float4 *tri_base() const { return img + 6u * pairs + ((pairs + 3u) >> 2); }
     __device__ __forceinline__ void edges(uint32_t ti, F3 &e1, F3 &e2) const {
-        const float4 *t = tri_base() + ti;
-        e1 = xyz4(t[tris]); e2 = xyz4(t[2u * tris]);
+        const float4 *t = tri_base() + 3u * ti;
+        e1 = xyz4(t[1]); e2 = xyz4(t[2]);
     }
-    __device__ __forceinline__ F3 corner(uint32_t ti) const { return xyz4(tri_base()[ti]); }
+    __device__ __forceinline__ F3 corner(uint32_t ti) const { return xyz4(tri_base()[3u * ti]); }
 };
+/* what lies `bytes` behind an array of the image: an inner descriptor is its pair index times FOUR, so the pair's descriptor word is at `descs + cur` and
+ * its plane records are at `base + (cur << 2)` — one shift-and-add per load, nothing to scale first */
+template <typename T> __device__ __forceinline__ T lds_at(const float4 *base, uint32_t bytes) {
+    return *reinterpret_cast<const T *>(reinterpret_cast<const char *>(base) + bytes);
+}
+/* the plane record of the pair behind inner descriptor `desc` in the per-ray array `base`: base + (desc << 2) as ONE instruction (left to itself the compiler
+ * shares the shift between the three axes: four instructions for three addresses) */
+__device__ __forceinline__ float4 lds_planes(const float4 *base, uint32_t desc) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef const __attribute__((address_space(3))) float4 *LdsVec;
+    const uint32_t b = (uint32_t)(LdsVec)base;
+    uint32_t a;
+    asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(a) : "v"(desc), "v"(b));
+    return *(LdsVec)a;
+#else
+    return lds_at<float4>(base, desc << 2);      /* (the host pass only parses device code) */
+#endif
+}
+/* The lane's stack column by its 32-bit LDS address: the walk keeps the ADDRESS of the next free entry instead of its index, a push is a store and an add, a
+ * pop an add and a load (the index costs a shift-and-add at each) */
+constexpr uint32_t LDS_STACK_STRIDE = RPT_WAVE * (uint32_t)sizeof(uint16_t);      /* bytes from one entry of a column to the next */
+__device__ __forceinline__ uint32_t lds_stack_address(const uint16_t *stack) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (uint32_t)(const __attribute__((address_space(3))) uint16_t *)stack;
+#else
+    return 0u;
+#endif
+}
+__device__ __forceinline__ void lds_stack_store(uint32_t at, uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    *(__attribute__((address_space(3))) uint16_t *)at = (uint16_t)v;
+#endif
+}
+__device__ __forceinline__ uint32_t lds_stack_load(uint32_t at) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return *(const __attribute__((address_space(3))) uint16_t *)at;
+#else
+    return 0u;
+#endif
+}
 
 /* intersection.rs:9-54 with edge1/edge2 precomputed at upload; `corner` is a callable: it is asked for the corner only by lanes that get
  * past the determinant test */
@@ -590,9 +632,10 @@ __device__ __forceinline__ void lds_walk_run(const SceneViewLds &view, LdsWalk &
     const float4 *px = img + ((SIGNED && rd.x < 0.0f) ? P : 0u);
     const float4 *py = img + 2u * P + ((SIGNED && rd.y < 0.0f) ? P : 0u);
     const float4 *pz = img + 4u * P + ((SIGNED && rd.z < 0.0f) ? P : 0u);
-    const uint32_t *descs = reinterpret_cast<const uint32_t *>(img + 6u * P);
+    const float4 *descs = img + 6u * P;
     uint32_t cur = w.cur;
-    int sp = w.sp;
+    const uint32_t bottom = lds_stack_address(stack), limit = bottom + (uint32_t)STACK * LDS_STACK_STRIDE;
+    uint32_t top = bottom + (uint32_t)w.sp;                            /* the next free entry of the lane's column (w.sp of an LDS walk: the stack's height in BYTES of a column) */
     HitRecord res = w.res;
     for (int trip = 0; trip < budget; ++trip) {
         const bool at_inner = SceneViewLds::is_inner(cur);
@@ -601,13 +644,19 @@ __device__ __forceinline__ void lds_walk_run(const SceneViewLds &view, LdsWalk &
         if ((inner_m | leaf_m) == 0ull) break;
         /* ONE body per trip, the one with more lanes ready for it: lanes on a leaf no longer sit out a fixed quota of inner
          * steps, and no body is issued for a handful of lanes */
-        /* (the compiler evaluates this wave-uniform comparison on the vector unit, v_mov + v_cmp_gt_u64 per trip; forced into
-         * scalar registers with s_cmp / s_cselect the kernel got SLOWER, 75.8 -> 77.0 ms: the scalar chain bcnt -> mul -> cmp ->
-         * cselect -> nor -> saveexec is latency the vector form hides) */
-        const bool do_leaf = (uint32_t)__popcll(leaf_m) > (uint32_t)__popcll(inner_m);
+        /* The two counts are pinned to scalar registers: left alone the compiler widens the comparison to 64 bits, which the scalar unit cannot do, and takes it
+         * on the vector unit (v_mov + v_cmp_gt_u64 per trip).  Measured on MI355X, DarkCornell 1024^2, traverse per 8 batches: this form 60.4 ms, the vector
+         * form 60.4, a wave-uniform branch around the two bodies 60.3 (one more instruction in each pop) — no difference a run can tell; this one has the
+         * fewest vector instructions (profiles/r21_walk_overhead_ab.txt).  (Round 3's scalar form, 75.8 -> 77.0 ms, also multiplied one count: a longer chain.) */
+        uint32_t n_leaf = (uint32_t)__popcll(leaf_m), n_inner = (uint32_t)__popcll(inner_m);
+        asm("" : "+s"(n_leaf), "+s"(n_inner));
+        const bool do_leaf = n_leaf > n_inner;
         if (at_inner && !do_leaf) {
-            const float4 X = px[cur], Y = py[cur], Z = pz[cur];     /* (L.near, R.near, L.far, R.far) per axis */
-            const uint32_t d = descs[cur];
+            /* (L.near, R.near, L.far, R.far) per axis; without the sign-selected bases (a ray outside the division guard) the three bases are wave-uniform and
+             * the compiler's own addresses are the shorter ones */
+            const float4 X = SIGNED ? lds_planes(px, cur) : lds_at<float4>(px, cur << 2), Y = SIGNED ? lds_planes(py, cur) : lds_at<float4>(py, cur << 2),
+                         Z = SIGNED ? lds_planes(pz, cur) : lds_at<float4>(pz, cur << 2);
+            const uint32_t d = lds_at<uint32_t>(descs, cur);
             float tl, tr;
             const bool hit_l = slab_pair_lds<SIGNED>(X.x, Y.x, Z.x, X.z, Y.z, Z.z, ro_slab, rd, ird, SEGMENT ? max_t : res.t, tl);
             const bool hit_r = slab_pair_lds<SIGNED>(X.y, Y.y, Z.y, X.w, Y.w, Z.w, ro_slab, rd, ird, SEGMENT ? max_t : res.t, tr);
@@ -616,26 +665,26 @@ __device__ __forceinline__ void lds_walk_run(const SceneViewLds &view, LdsWalk &
                                     : (hit_r && (!hit_l || tl > tr));     /* strict: ties keep left first */
             if (hit_l || hit_r) {
                 const uint32_t nf = __builtin_amdgcn_alignbit(d, d, swap ? 16u : 0u);    /* near | far << 16 */
-                if (hit_l && hit_r && sp < STACK) {
-                    stack[sp * RPT_WAVE] = (uint16_t)(nf >> 16);
-                    sp += 1;
+                if (hit_l && hit_r && top < limit) {
+                    lds_stack_store(top, nf >> 16);
+                    top += LDS_STACK_STRIDE;
                 }
                 cur = nf & 0xffffu;
-            } else if (sp == 0) {
+            } else if (top == bottom) {
                 cur = LDS_DESC_DEAD;
             } else {
-                sp -= 1;
-                cur = stack[sp * RPT_WAVE];
+                top -= LDS_STACK_STRIDE;
+                cur = lds_stack_load(top);
             }
         }
         if (at_leaf && do_leaf) {
             bool accepted = false;
             const uint32_t count = (cur >> 9) & 63u, first = cur & 511u;
-            for (uint32_t i = 0; i < count; ++i) {
-                uint32_t ti = first + i;
-                float t = 0.0f;
+            const float4 *rec = view.tri_base() + 3u * first;      /* (corner, edge1, edge2) of the leaf's triangles, one after the other */
+            for (uint32_t ti = first, end = first + count; ti != end; ++ti, rec += 3) {
+                float t;                                           /* (read only behind a passed test: set to 0 ahead of it, every early-out costs a v_mov) */
                 bool bf = false;
-                if (moller_trumbore_view(view, ti, ro, rd, t, bf) && t > 0.001f && (SEGMENT ? t < max_t : (t < res.t && (!ANY_HIT || t <= max_t)))) {
+                if (moller_trumbore(xyz4(rec[1]), xyz4(rec[2]), [&] { return xyz4(rec[0]); }, ro, rd, t, bf) && t > 0.001f && (SEGMENT ? t < max_t : (t < res.t && (!ANY_HIT || t <= max_t)))) {
                     /* (a real branch, as in walk_run) */
                     asm volatile("" ::: "memory");
                     res.t = t;
@@ -643,16 +692,16 @@ __device__ __forceinline__ void lds_walk_run(const SceneViewLds &view, LdsWalk &
                     if (ANY_HIT || (MIXED && stop_first != 0u)) { accepted = true; break; }
                 }
             }
-            if (((ANY_HIT || MIXED) && accepted) || sp == 0) {
+            if (((ANY_HIT || MIXED) && accepted) || top == bottom) {
                 cur = LDS_DESC_DEAD;
             } else {
-                sp -= 1;
-                cur = stack[sp * RPT_WAVE];
+                top -= LDS_STACK_STRIDE;
+                cur = lds_stack_load(top);
             }
         }
     }
     w.cur = cur;
-    w.sp = sp;
+    w.sp = (int)(top - bottom);
     w.res = res;
 }
 

@@ -67,13 +67,13 @@ int validate_scene(rpt_ctx *ctx, const rpt_per_vertex_data *pv, size_t nv, const
 /* The LDS-resident traversal image of a small scene (layout and rationale: k_walk.h, SceneViewLds):
  *   float4 K_A[P], K_B[P] for K = x, y, z   (L.lo, R.lo, L.hi, R.hi) and (L.hi, R.hi, L.lo, R.lo)
  *   u32    D[P] (padded to 16 bytes)        desc(L) | desc(R) << 16
- *   float4 a[T], e1[T], e2[T]
+ *   float4 (a, e1, e2)[T]
  * with pair p = nodes (2p+1, 2p+2).  Returns false when the node array cannot be represented (not pair-shaped,
  * a box with lo > hi or a NaN bound, a leaf of 64+ triangles, 512+ triangles): such a scene is traversed from
  * global memory by the generic loop. */
 bool build_lds_image(const rpt_bvh_node *nodes, size_t nn, const std::vector<float4> &geom, size_t nt,
                      std::vector<float4> &image, uint32_t &pairs, uint32_t &root) {
-    if (nn == 0 || (nn & 1u) == 0u || nt > 512 || nn >= 2 * (size_t)LDS_DESC_DEAD) return false;
+    if (nn == 0 || (nn & 1u) == 0u || nt > 512 || 2 * nn >= (size_t)LDS_DESC_DEAD) return false;      /* (4 x pair index < LDS_DESC_DEAD) */
     auto desc = [&](const rpt_bvh_node &n, uint32_t &out) {
         if (n.triangle_count != 0u) {
             if (n.triangle_count >= 64u || n.left_or_first >= 512u || (size_t)n.left_or_first + n.triangle_count > nt) return false;
@@ -82,7 +82,7 @@ bool build_lds_image(const rpt_bvh_node *nodes, size_t nn, const std::vector<flo
         }
         uint32_t l = n.left_or_first;
         if ((l & 1u) == 0u || (size_t)l + 1 >= nn) return false;
-        out = l >> 1;
+        out = (l >> 1) << 2;      /* the pair index times four: what the walk adds to its bases (k_walk.h lds_at) */
         return true;
     };
     if (!desc(nodes[0], root)) return false;
@@ -103,8 +103,7 @@ bool build_lds_image(const rpt_bvh_node *nodes, size_t nn, const std::vector<flo
             image[(2 * k + 1) * P + p] = make_float4(L.aabb_max[k], R.aabb_max[k], L.aabb_min[k], R.aabb_min[k]);
         }
     }
-    for (size_t t = 0; t < nt; ++t)
-        for (int j = 0; j < 3; ++j) image[6 * P + desc_vecs + (size_t)j * nt + t] = geom[3 * t + j];
+    for (size_t k = 0; k < 3 * nt; ++k) image[6 * P + desc_vecs + k] = geom[k];
     return true;
 }
 
