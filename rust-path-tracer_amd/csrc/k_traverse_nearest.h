@@ -46,18 +46,18 @@ __global__ __launch_bounds__(THREADS) void k_traverse_nearest(DevScene sc, DevSt
  * trips (DarkCornell bounce 2: median 25, p90 34, max 68 node visits), so a one-ray-per-lane wave spends most of its
  * trips with a minority of lanes alive (lane utilisation 40 %).  Here, every RPT_STREAM_TRIPS trips the wave looks at
  * its idle lanes; when at least RPT_STREAM_REFILL are idle they write their hit records and take the next slots from the
- * workgroup's pool (below).  The walk itself (lds_walk_run) is the same code with a trip budget: no per-lane bookkeeping inside
+ * workgroup's pool (below).  The walk itself (lds_stream_walk_run) runs with a trip budget: no per-lane bookkeeping inside
  * the hot loop.  Per ray nothing changes — same tests in the same order — so hit records are the reference's bit for
  * bit, and slots stay identity mapped (a slot's ray is traced by SOME lane of the wave that owns its range). */
 /* LAST: the launch that traces the last extension ray of every path of a batch of known length WITHOUT NEE (the host's choice, rpt_hip.hip launch_iteration:
  * the same condition as the shade stage's last_iteration).  At that bounce the reference reads three things off the walk's result (kernels/src/lib.rs:62-109):
  * a miss adds the sky; a hit on the front of a triangle whose material emits adds its emission; any other hit adds nothing and ends the sample.  A ray that
  * passes the Moller-Trumbore test of NO emissive triangle (sc.last_emit_tri, at most RPT_LAST_EMIT_MAX of them, tested when the lane takes the ray) cannot
- * end on one, so "hit or miss" is all its walk has to say: it stops at its first accepted triangle (lds_walk_run MIXED) — in a closed scene about half of
+ * end on one, so "hit or miss" is all its walk has to say: it stops at its first accepted triangle (lds_stream_walk_run MIXED) — in a closed scene about half of
  * the node visits of the bounce (tools/last_bounce_sim.py).  Its hit record names THAT triangle: not the nearest one, but like the nearest one not an
  * emitter, which is all the shade stage's last iteration looks at.  A ray that does pass such a test runs the reference's walk to its end. */
 /* FIRST: the launch of a render call's first iteration, where every ray is a camera ray and leaves cfg.cam_position (k_path.h camera_ray; lib.rs:36-60):
- * the workgroup stages the plane records with that origin subtracted (lds_walk_run PRESUB) — twelve of the ~ 98 instructions of a node-pair step. */
+ * the workgroup stages the plane records with that origin subtracted (lds_stream_walk_run PRESUB) — twelve of the ~ 98 instructions of a node-pair step. */
 #define RPT_NEAREST_PLAIN 0
 #define RPT_NEAREST_LAST 1
 #define RPT_NEAREST_FIRST 2
@@ -108,6 +108,7 @@ __global__ __launch_bounds__(THREADS) void k_traverse_nearest_stream(DevScene sc
     uint32_t stop_first = 0u;
     float order_bias = 0.0f;
     uint16_t *stack = &lds_stack[wave][0][lane];
+    lds_stream_stack_begin(stack);                             /* entry 0 of the lane's column: the sentinel an empty stack pops (k_walk.h lds_stream_walk_run) */
     F3 ro = f3(0, 0, 0), rd = f3(1, 1, 1), ird = f3(1, 1, 1);
     LdsWalk w;
     walk_begin(view, w);
@@ -231,7 +232,7 @@ __global__ __launch_bounds__(THREADS) void k_traverse_nearest_stream(DevScene sc
                             /* outside the exact-division guard (a zero / denormal-small direction component): walked here, alone */
                             LdsWalk alone;
                             walk_begin(view, alone);
-                            lds_walk_run<STACK, false, false, false, false, FIRST>(view, alone, ro, rd, rd, 0.0f, stack, 0x7fffffff);
+                            lds_walk_run<STACK - 1, false, false, false, FIRST>(view, alone, ro, rd, rd, 0.0f, lds_stream_stack_rest(stack), 0x7fffffff);
                             if (LAST) {
                                 /* the reference's walk to its end; the lane stays idle and ends the path where it next writes (the next refill, or the tail) */
                                 w.res = alone.res;
@@ -252,8 +253,8 @@ __global__ __launch_bounds__(THREADS) void k_traverse_nearest_stream(DevScene sc
             if (!pool_open) break;                             /* nothing in flight and nothing left to hand out */
             continue;
         }
-        if (LAST) lds_walk_run<STACK, false, true, false, true>(view, w, ro, rd, ird, 0.0f, stack, pool_open ? RPT_STREAM_TRIPS : 0x7fffffff, img_lane, stop_first, order_bias);
-        else lds_walk_run<STACK, false, true, false, false, FIRST>(view, w, ro, rd, ird, 0.0f, stack, pool_open ? RPT_STREAM_TRIPS : 0x7fffffff);
+        if (LAST) lds_stream_walk_run<STACK, false, false, true>(view, w, ro, rd, ird, 0.0f, stack, pool_open ? RPT_STREAM_TRIPS : 0x7fffffff, img_lane, stop_first, order_bias);
+        else lds_stream_walk_run<STACK, false, false, false, FIRST>(view, w, ro, rd, ird, 0.0f, stack, pool_open ? RPT_STREAM_TRIPS : 0x7fffffff);
     }
     if (LAST) {
         bool park = false;

@@ -63,6 +63,7 @@ __global__ __launch_bounds__(THREADS) void RPT_SHADOW_KERNEL(k_traverse_shadow_s
     if ((uint32_t)(pool.word >> 32) == 0u) return;             /* block-uniform: nothing (left) to trace */
     const SceneViewLds view = stage_scene_lds<THREADS>(sc, lds_scene, FIXED);
     uint16_t *stack = &lds_stack[wave][0][lane];
+    lds_stream_stack_begin(stack);                             /* entry 0 of the lane's column: the sentinel an empty stack pops (k_walk.h lds_stream_walk_run) */
     F3 ro = f3(0, 0, 0), rd = f3(1, 1, 1), ird = f3(1, 1, 1);
     float max_t = 0.0f;
     LdsWalk w;
@@ -97,7 +98,8 @@ __global__ __launch_bounds__(THREADS) void RPT_SHADOW_KERNEL(k_traverse_shadow_s
                         ird = f3(rptm::rcp_rn_window(rd.x), rptm::rcp_rn_window(rd.y), rptm::rcp_rn_window(rd.z));
                         walk_begin(view, w);
                     } else {
-                        w.res = traverse_loop<STACK, true, false, FIXED, SEGMENT>(view, ro, rd, rd, max_t, stack);   /* alone; recorded at the next refill */
+                        uint16_t *rest = lds_stream_stack_rest(stack);
+                        w.res = traverse_loop<STACK - 1, true, false, FIXED, SEGMENT>(view, ro, rd, rd, max_t, rest);   /* alone; recorded at the next refill */
                     }
                 }
             }
@@ -108,7 +110,7 @@ __global__ __launch_bounds__(THREADS) void RPT_SHADOW_KERNEL(k_traverse_shadow_s
             if (!pool_open) break;                             /* nothing in flight and nothing left to hand out */
             continue;
         }
-        lds_walk_run<STACK, true, true, FIXED, false, false, SEGMENT>(view, w, ro, rd, ird, max_t, stack, pool_open ? RPT_STREAM_TRIPS : 0x7fffffff);
+        lds_stream_walk_run<STACK, true, FIXED, false, false, SEGMENT>(view, w, ro, rd, ird, max_t, stack, pool_open ? RPT_STREAM_TRIPS : 0x7fffffff);
     }
     if (have) q.sh_c[entry].w = w.res.tri == HIT_MISS ? 0.0f : 1.0f;
 }

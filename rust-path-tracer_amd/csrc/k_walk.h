@@ -610,24 +610,16 @@ __device__ __forceinline__ bool slab_pair_lds(float n_x, float n_y, float n_z, f
  * everything a ray needs besides (ro, rd, 1/rd) is in here and in its stack column. */
 typedef Walk<SceneViewLds> LdsWalk;     /* cur: the descriptor of the node the ray stands on; LDS_DESC_DEAD when finished / no ray */
 
-/* MIXED (the last extension rays of a batch without NEE, k_traverse_nearest_stream<.., LAST = true>): a nearest-hit walk in which SOME lanes only have to
- * answer "hit or miss" — `stop_first` lanes leave at their first accepted triangle, which is where the reference's walk makes result.hit true for good
- * (intersection.rs:195-203), and because nothing was accepted before, result.t was 1e6 at every box test up to there: the part of the walk they run is an
- * any-hit walk, whose answer does not depend on the visiting order (header).  They read the planes and child descriptors of `img_lane` — the flipped copy
- * of the pair records when the workgroup staged one, then with order_bias = +inf (tl > tr + inf is never true: the left child first, the fixed order of
- * shadow_order.h choose_last_order); the other lanes read the primary image with order_bias = 0 (tr + 0 compares like tr) and are the reference's walk to its end. */
 /* PRESUB (the camera rays of a call's first iteration, k_traverse_nearest_stream FIRST): every ray of the launch has the SAME origin, and the workgroup
  * staged the plane records with that origin already subtracted — the very `plane - ro` (one IEEE subtraction of the same two floats) each lane would
  * compute at each of the twelve planes of a node pair.  The slab test then divides the staged value directly; the triangle test keeps the true origin. */
-template <int STACK, bool ANY_HIT, bool SIGNED, bool FIXED = false, bool MIXED = false, bool PRESUB = false, bool SEGMENT = false /* as in walk_run */>
-__device__ __forceinline__ void lds_walk_run(const SceneViewLds &view, LdsWalk &w, F3 ro, F3 rd, F3 ird, float max_t, uint16_t *stack,
-                                             int budget, const float4 *img_lane = nullptr, uint32_t stop_first = 0u, float order_bias = 0.0f) {
+template <int STACK, bool ANY_HIT, bool SIGNED, bool FIXED = false, bool PRESUB = false, bool SEGMENT = false /* as in walk_run */>
+__device__ __forceinline__ void lds_walk_run(const SceneViewLds &view, LdsWalk &w, F3 ro, F3 rd, F3 ird, float max_t, uint16_t *stack, int budget) {
     static_assert(!FIXED || ANY_HIT, "only the any-hit walk may choose its order");
-    static_assert(!MIXED || (!ANY_HIT && !FIXED), "MIXED is the nearest-hit walk with per-lane early exits");
     static_assert(!SEGMENT || ANY_HIT, "only a shadow ray is a segment");
     const F3 ro_slab = PRESUB ? f3(0.0f, 0.0f, 0.0f) : ro;         /* x - (+0) is x, bit for bit: the subtraction folds away */
     const uint32_t P = view.pairs;
-    const float4 *img = MIXED ? img_lane : view.img;
+    const float4 *img = view.img;
     /* per-ray plane-record bases (float4 units): x | y | z, A or B variant by the sign of the direction */
     const float4 *px = img + ((SIGNED && rd.x < 0.0f) ? P : 0u);
     const float4 *py = img + 2u * P + ((SIGNED && rd.y < 0.0f) ? P : 0u);
@@ -660,9 +652,7 @@ __device__ __forceinline__ void lds_walk_run(const SceneViewLds &view, LdsWalk &
             float tl, tr;
             const bool hit_l = slab_pair_lds<SIGNED>(X.x, Y.x, Z.x, X.z, Y.z, Z.z, ro_slab, rd, ird, SEGMENT ? max_t : res.t, tl);
             const bool hit_r = slab_pair_lds<SIGNED>(X.y, Y.y, Z.y, X.w, Y.w, Z.w, ro_slab, rd, ird, SEGMENT ? max_t : res.t, tr);
-            const bool swap = FIXED ? (hit_r && !hit_l)
-                            : MIXED ? (hit_r && (!hit_l || tl > tr + order_bias))
-                                    : (hit_r && (!hit_l || tl > tr));     /* strict: ties keep left first */
+            const bool swap = FIXED ? (hit_r && !hit_l) : (hit_r && (!hit_l || tl > tr));     /* strict: ties keep left first */
             if (hit_l || hit_r) {
                 const uint32_t nf = __builtin_amdgcn_alignbit(d, d, swap ? 16u : 0u);    /* near | far << 16 */
                 if (hit_l && hit_r && top < limit) {
@@ -689,10 +679,10 @@ __device__ __forceinline__ void lds_walk_run(const SceneViewLds &view, LdsWalk &
                     asm volatile("" ::: "memory");
                     res.t = t;
                     res.tri = ti | (bf ? 0x80000000u : 0u);
-                    if (ANY_HIT || (MIXED && stop_first != 0u)) { accepted = true; break; }
+                    if (ANY_HIT) { accepted = true; break; }
                 }
             }
-            if (((ANY_HIT || MIXED) && accepted) || top == bottom) {
+            if ((ANY_HIT && accepted) || top == bottom) {
                 cur = LDS_DESC_DEAD;
             } else {
                 top -= LDS_STACK_STRIDE;
@@ -705,12 +695,133 @@ __device__ __forceinline__ void lds_walk_run(const SceneViewLds &view, LdsWalk &
     w.res = res;
 }
 
+/* ---- the walk of the STREAMED LDS kernels (k_traverse_nearest_stream, k_traverse_shadow_stream): lds_walk_run<SIGNED> with its control flattened ----
+ * Per lane it computes what lds_walk_run computes, test for test and in the same order; what differs is how the wave is steered.  Every `if` of a lane-varying
+ * condition costs the SCALAR unit an exec save, a branch and a restore, plus the mask logic that joins the paths, and a SIMD gets a scalar issue slot only every
+ * ~3.5 cycles (profiles/r04_valu_pipes.txt, question 3): on an inner trip of lds_walk_run the scalar port was as long as the vector port.
+ *   - the triangle test is moller_trumbore_flat: no early-outs, ONE predicate;
+ *   - ONE pop site per trip behind both bodies: a body leaves LDS_DESC_POP in `cur` where the lane has to pop;
+ *   - the column's entry 0 holds LDS_DESC_DEAD for good (lds_stream_stack_begin): a pop of an empty stack loads it, there is no `top == bottom` test.  The walk
+ *     has STACK - 1 entries; an LDS image has at most 15 levels under its root (rpt_scene.hip stage_nodes), which is what 16-entry columns leave;
+ *   - descend / push by selects, the stack store under the only exec narrowing of the inner step;
+ *   - the vote is two wave-uniform branches, and the loop has ONE exit, at its end: a scalar minimum, a compare and a branch on SCC (an exit at the head, or a
+ *     `break` inside, is carried as a lane mask through a latch block). */
+/* MIXED (the last extension rays of a batch without NEE, k_traverse_nearest_stream<.., LAST = true>): a nearest-hit walk in which SOME lanes only have to
+ * answer "hit or miss" — `stop_first` lanes leave at their first accepted triangle, which is where the reference's walk makes result.hit true for good
+ * (intersection.rs:195-203), and because nothing was accepted before, result.t was 1e6 at every box test up to there: the part of the walk they run is an
+ * any-hit walk, whose answer does not depend on the visiting order (header).  They read the planes and child descriptors of `img_lane` — the flipped copy
+ * of the pair records when the workgroup staged one, then with order_bias = +inf (tl > tr + inf is never true: the left child first, the fixed order of
+ * shadow_order.h choose_last_order); the other lanes read the primary image with order_bias = 0 (tr + 0 compares like tr) and are the reference's walk to its end. */
+constexpr uint32_t LDS_DESC_POP = LDS_DESC_DEAD + 1u;      /* never in the image, never alive across a trip: neither inner (< DEAD) nor a leaf (>= LEAF) nor dead */
+__device__ __forceinline__ void lds_stream_stack_begin(uint16_t *stack) { stack[0] = (uint16_t)LDS_DESC_DEAD; }
+__device__ __forceinline__ uint16_t *lds_stream_stack_rest(uint16_t *stack) { return stack + RPT_WAVE; }      /* the STACK - 1 entries above the sentinel, for lds_walk_run */
+
+/* intersection.rs:9-54 for every lane at once: det, u, v and t are computed whatever the earlier tests say, and the four early-outs are one predicate.
+ *     u < 0 || v < 0          <=>  fminr(u, v) < 0         (NaN-ignoring min: a NaN operand passes its own test and leaves the other's, as `if (u < 0.0 ..) return` does)
+ *     u > 1 || u + v > 1      <=>  fmaxr(u, u + v) > 1     (a NaN u makes u + v NaN: both pass; a NaN v leaves u > 1)
+ *     t < 0                        is implied by the caller's t > 0.001, which every accept goes through (a NaN t fails that one)
+ * A lane whose |det| < 1e-6 runs the reciprocal like the others (of 0: inf, through rcp_rn's fallback) and is rejected by the predicate. */
+__device__ __forceinline__ bool moller_trumbore_flat(F3 edge1, F3 edge2, F3 corner, F3 ro, F3 rd, float &out_t, float &out_det) {
+    const F3 pv = cross3(rd, edge2);
+    const float det = dot3(edge1, pv);
+    const float inv_det = rptm::rcp_rn(det);
+    const F3 tv = ro - corner;
+    const float u = dot3(tv, pv) * inv_det;
+    const F3 qv = cross3(tv, edge1);
+    const float v = dot3(rd, qv) * inv_det;
+    float lo = rptm::fminr(u, v), hi = rptm::fmaxr(u, u + v), t = dot3(edge2, qv) * inv_det;
+    asm volatile("" : "+v"(lo), "+v"(hi), "+v"(t));      /* all three stand in registers HERE: left alone the optimiser turns the predicate back into a ladder of branches */
+    out_t = t;
+    out_det = det;
+    return !(rptm::absr(det) < 1e-6f) & !(lo < 0.0f) & !(hi > 1.0f);
+}
+
+template <int STACK, bool ANY_HIT, bool FIXED = false, bool MIXED = false, bool PRESUB = false, bool SEGMENT = false /* as in walk_run */>
+__device__ __forceinline__ void lds_stream_walk_run(const SceneViewLds &view, LdsWalk &w, F3 ro, F3 rd, F3 ird, float max_t, uint16_t *stack /* entry 0: the sentinel */,
+                                                    int budget, const float4 *img_lane = nullptr, uint32_t stop_first = 0u, float order_bias = 0.0f) {
+    static_assert(!FIXED || ANY_HIT, "only the any-hit walk may choose its order");
+    static_assert(!MIXED || (!ANY_HIT && !FIXED), "MIXED is the nearest-hit walk with per-lane early exits");
+    static_assert(!SEGMENT || ANY_HIT, "only a shadow ray is a segment");
+    const F3 ro_slab = PRESUB ? f3(0.0f, 0.0f, 0.0f) : ro;
+    const uint32_t P = view.pairs;
+    const float4 *img = MIXED ? img_lane : view.img;
+    const float4 *px = img + (rd.x < 0.0f ? P : 0u);
+    const float4 *py = img + 2u * P + (rd.y < 0.0f ? P : 0u);
+    const float4 *pz = img + 4u * P + (rd.z < 0.0f ? P : 0u);
+    const float4 *descs = img + 6u * P;
+    uint32_t cur = w.cur;
+    const uint32_t bottom = lds_stack_address(stack) + LDS_STACK_STRIDE, limit = bottom + (uint32_t)(STACK - 1) * LDS_STACK_STRIDE;
+    uint32_t top = bottom + (uint32_t)w.sp;                            /* (a lane that popped the sentinel stands one entry BELOW bottom until walk_begin) */
+    HitRecord res = w.res;
+    /* The loop's ONE exit stands at its end, on scalar registers: the budget is used up, or no lane has anything left (one minimum, one compare).  The
+     * callers enter with a budget of at least one trip and a live lane (entered with none, the first trip finds no lane for either body and leaves). */
+    uint32_t left = (uint32_t)budget;
+    uint32_t n_leaf = (uint32_t)__popcll(rpt_ballot(SceneViewLds::is_leaf(cur))), n_inner = (uint32_t)__popcll(rpt_ballot(SceneViewLds::is_inner(cur)));
+    asm("" : "+s"(n_leaf), "+s"(n_inner));                             /* (scalar registers: see lds_walk_run) */
+    uint32_t go;
+    do {
+        if (n_leaf > n_inner) {
+            if (SceneViewLds::is_leaf(cur)) {
+                bool accepted = false;
+                const uint32_t first = cur & 511u;
+                uint32_t ti = first;
+                const uint32_t end = first + ((cur >> 9) & 63u);       /* (a leaf holds at least one triangle: a count of 0 is an inner node) */
+                const float4 *rec = view.tri_base() + 3u * first;
+                do {
+                    float t, det;
+                    const bool ok = moller_trumbore_flat(xyz4(rec[1]), xyz4(rec[2]), xyz4(rec[0]), ro, rd, t, det);
+                    if (ok && t > 0.001f && (SEGMENT ? t < max_t : (t < res.t && (!ANY_HIT || t <= max_t)))) {
+                        asm volatile("" ::: "memory");                 /* (a real branch, as in walk_run) */
+                        res.t = t;
+                        res.tri = ti | (rptm::f2u(det) & 0x80000000u);
+                        if (ANY_HIT || (MIXED && stop_first != 0u)) { accepted = true; break; }
+                    }
+                    ++ti;
+                    rec += 3;
+                } while (ti != end);
+                cur = ((ANY_HIT || MIXED) && accepted) ? LDS_DESC_DEAD : LDS_DESC_POP;
+            }
+        }
+        if (n_leaf <= n_inner) {                                       /* (a branch of its own: as the `else` of the one above, the two are joined through a mask) */
+            if (SceneViewLds::is_inner(cur)) {
+                const float4 X = lds_planes(px, cur), Y = lds_planes(py, cur), Z = lds_planes(pz, cur);
+                const uint32_t d = lds_at<uint32_t>(descs, cur);
+                float tl, tr;
+                const bool hit_l = slab_pair_lds<true>(X.x, Y.x, Z.x, X.z, Y.z, Z.z, ro_slab, rd, ird, SEGMENT ? max_t : res.t, tl);
+                const bool hit_r = slab_pair_lds<true>(X.y, Y.y, Z.y, X.w, Y.w, Z.w, ro_slab, rd, ird, SEGMENT ? max_t : res.t, tr);
+                const bool swap = FIXED ? (hit_r && !hit_l)
+                                : MIXED ? (hit_r && (!hit_l || tl > tr + order_bias))
+                                        : (hit_r && (!hit_l || tl > tr));     /* strict: ties keep left first */
+                const uint32_t nf = __builtin_amdgcn_alignbit(d, d, swap ? 16u : 0u);    /* near | far << 16 */
+                if (hit_l && hit_r && top < limit) {
+                    lds_stack_store(top, nf >> 16);
+                    top += LDS_STACK_STRIDE;
+                }
+                cur = (hit_l || hit_r) ? (nf & 0xffffu) : LDS_DESC_POP;
+            }
+        }
+        if (cur == LDS_DESC_POP) {
+            top -= LDS_STACK_STRIDE;
+            cur = lds_stack_load(top);
+        }
+        --left;
+        n_leaf = (uint32_t)__popcll(rpt_ballot(SceneViewLds::is_leaf(cur)));
+        n_inner = (uint32_t)__popcll(rpt_ballot(SceneViewLds::is_inner(cur)));
+        asm("" : "+s"(n_leaf), "+s"(n_inner));
+        go = n_leaf + n_inner;
+        go = go < left ? go : left;
+    } while (go != 0u);
+    w.cur = cur;
+    w.sp = (int)(top - bottom);
+    w.res = res;
+}
+
 /* One ray walked to its end: over the LDS image by lds_walk_run (FAST there is SIGNED), over the other views by walk_run. */
 template <int STACK, bool ANY_HIT, bool FAST, bool FIXED = false, bool SEGMENT = false, typename View, typename StackRef>
 __device__ __forceinline__ HitRecord traverse_loop(const View &view, F3 ro, F3 rd, F3 ird, float max_t, StackRef &stack) {
     Walk<View> w;
     walk_begin(view, w);
-    if constexpr (std::is_same<View, SceneViewLds>::value) lds_walk_run<STACK, ANY_HIT, FAST, FIXED, false, false, SEGMENT>(view, w, ro, rd, ird, max_t, stack, 0x7fffffff);
+    if constexpr (std::is_same<View, SceneViewLds>::value) lds_walk_run<STACK, ANY_HIT, FAST, FIXED, false, SEGMENT>(view, w, ro, rd, ird, max_t, stack, 0x7fffffff);
     else walk_run<STACK, ANY_HIT, FAST, FIXED, SEGMENT>(view, w, ro, rd, ird, max_t, stack, 0x7fffffff);
     return w.res;
 }

@@ -16,10 +16,17 @@ and the blocks of a walk loop are told apart in text order by what they hold:
     refill path          every block of the refill loop outside its walk loops
 A kernel has one walk loop per instantiation of lds_walk_run it inlines: the exact-division walk of the streamed lanes ("fast") and the walk a ray outside
 the division guard is walked with alone ("ieee": v_div_scale in its inner body).  Counts are STATIC: instructions in the text, not instructions issued.
-VALU = v_*; SALU = s_* without s_waitcnt / s_nop / s_sleep / s_barrier / s_endpgm and without scalar memory; LDS = ds_*; VMEM = global_* / buffer_* / flat_*."""
+VALU = v_*; SALU = s_* without s_waitcnt / s_nop / s_sleep / s_barrier / s_endpgm and without scalar memory; LDS = ds_*; VMEM = global_* / buffer_* / flat_*.
+The flattened walk of the streamed lanes (k_walk.h lds_stream_walk_run) stands in another text order — latch (the ballots and the loop's one exit, ahead of the header label:
+loop head), vote, leaf set-up, triangle loop, inner body, push, and ONE pop site behind both bodies — and the same rules sort it: what follows the triangle loop up to the
+plane loads (the end of the leaf body, the vote's second half) and what follows the stack store (the merged pop) is push / pop.
+`inner trip, total` = loop head + inner body + push / pop: what a trip of the inner step issues.  The last two columns are the region's cost at the unit costs of
+tools/microbench/valu_rates.hip (profiles/r04_valu_pipes.txt, question 3): 3.7 per vector and 6.5 per scalar instruction; a change pays where their sum goes down."""
 import re, subprocess, sys
 
 REGIONS = ['loop head', 'inner body', 'push / pop', 'leaf set-up', 'triangle iteration', 'refill path']
+TRIP = ['loop head', 'inner body', 'push / pop']
+VALU_UNITS, SALU_UNITS = 3.7, 6.5
 NOT_SALU = ('s_waitcnt', 's_nop', 's_sleep', 's_barrier', 's_endpgm', 's_load', 's_buffer_load')
 
 def kind(ins):
@@ -108,17 +115,21 @@ def main(path):
     ks = kernels(open(path).read())
     names = [k for k in ks if re.match(r'_Z\d+k_traverse_(nearest|shadow)_stream', k)]
     pretty = subprocess.run(['c++filt'], input='\n'.join(names), capture_output=True, text=True).stdout.split('\n')
-    fmt = '    %-22s %6s %6s %5s %5s'
+    fmt = '    %-22s %6s %6s %5s %5s %9s %9s'
+    units = lambda c: ('%.1f' % (VALU_UNITS * c['VALU']), '%.1f' % (SALU_UNITS * c['SALU']))
     for n, p in sorted(zip(names, pretty), key=lambda t: t[1]):
         walks, refill = analyse(ks[n])
         print(re.sub(r'\(.*', '', p).replace('void ', ''))
         for w, form, regs in walks:
             print('  walk loop %s (%s)' % (w, form))
-            print(fmt % ('', 'VALU', 'SALU', 'LDS', 'VMEM'))
-            for r in REGIONS[:5]: print(fmt % (r, regs[r]['VALU'], regs[r]['SALU'], regs[r]['LDS'], regs[r]['VMEM']))
+            print(fmt % ('', 'VALU', 'SALU', 'LDS', 'VMEM', 'VALU x3.7', 'SALU x6.5'))
+            for r in REGIONS[:5]: print(fmt % (r, regs[r]['VALU'], regs[r]['SALU'], regs[r]['LDS'], regs[r]['VMEM'], *units(regs[r])))
+            trip = {k: sum(regs[r][k] for r in TRIP) for k in ('VALU', 'SALU', 'LDS', 'VMEM')}
+            print(fmt % ('inner trip, total', trip['VALU'], trip['SALU'], trip['LDS'], trip['VMEM'], *units(trip)))
         print('  refill loop')
-        print(fmt % ('refill path', refill['VALU'], refill['SALU'], refill['LDS'], refill['VMEM']))
-        print(fmt % ('whole kernel', *[count(ks[n])[k] for k in ('VALU', 'SALU', 'LDS', 'VMEM')]))
+        print(fmt % ('refill path', refill['VALU'], refill['SALU'], refill['LDS'], refill['VMEM'], *units(refill)))
+        whole = count(ks[n])
+        print(fmt % ('whole kernel', *[whole[k] for k in ('VALU', 'SALU', 'LDS', 'VMEM')], *units(whole)))
         print()
 
 if __name__ == '__main__':
