@@ -60,6 +60,32 @@ int rpt_debug_trace_rays(rpt_ctx *ctx, int any_hit, size_t n,
  * afterwards the context is as after rpt_reset with nothing rendered (call rpt_reset before rendering again). */
 int rpt_debug_trace_rays_production(rpt_ctx *ctx, size_t n, const float *origins_xyz, const float *dirs_xyz,
                                     float *out_t, uint32_t *out_tri, uint32_t *out_flags);
+/* n caller-chosen rays through ANY of the walks rpt_render launches: the hook writes the rays where the pipeline keeps them (the context's slots, or its
+ * sharded shadow queue) and calls rpt_launch_nearest / rpt_launch_shadow exactly as an iteration of rpt_render does — it chooses no kernel, span, grid or
+ * LDS size, so the scene, rpt_set_shadow_mode and the developer knobs (RPT_NO_LDS_SCENE, RPT_COOP_LEAVES, RPT_STACK_BITS, RPT_SHADOW_ORDER, RPT_LAST_ORDER,
+ * RPT_SLOT_Q_SHIFT) select the instantiation as they do in a render.  kind:
+ *   RPT_WALK_NEAREST_PLAIN  what rpt_debug_trace_rays_production does (that call is this kind).
+ *   RPT_WALK_NEAREST_FIRST  the launch of a render call's first iteration: the streamed LDS walk stages its planes with ONE origin subtracted, so EVERY
+ *                           origin must equal the configuration's cam_position bit for bit (else RPT_EINVAL).  The slots are prepared as k_generate_first
+ *                           leaves them; the form in which the walk starts the paths itself stays covered by renders only.
+ *   RPT_WALK_NEAREST_LAST   the launch of the last extension rays of a batch of known length without NEE, in the form that writes hit records (one slot per
+ *                           pixel): a ray that passes the test of no emissive triangle may stop at its first accepted triangle, so its record names A
+ *                           triangle it hits, not the nearest.  The path-ending form (several slots per pixel: the walk adds emission, parks misses and
+ *                           writes HIT_DONE itself) stays covered by renders only.
+ *   RPT_WALK_SHADOW         any-hit rays (max_t required) through the shadow queue, whose shards the hook fills UNEVENLY so that the swept positions
+ *                           include unfilled ones, then rpt_launch_shadow (k_shadow_resolve behind the streamed LDS walk).  Entry i carries the
+ *                           contribution (1, 1 + i % 4093, 0) for slot i: out_flags bit 0 = occluded (the slot's radiance stayed 0); a radiance record
+ *                           that is neither is an entry resolved into the wrong slot or twice — RPT_EHIP, the message names the ray.  out_t and out_tri
+ *                           are left zero: the production kernels keep no record.
+ * Outputs of the nearest kinds as rpt_debug_trace_rays(any_hit = 0).  n == 0: RPT_OK, nothing launched.  RPT_EINVAL: no scene or configuration, n above
+ * the slot count (SHADOW: or more than the uneven fill leaves room for in the queue), SHADOW without max_t.  Afterwards the context is as after
+ * rpt_reset with nothing rendered, its counters apart: CALL rpt_reset BEFORE RENDERING AGAIN. */
+#define RPT_WALK_NEAREST_PLAIN 0
+#define RPT_WALK_NEAREST_FIRST 1
+#define RPT_WALK_NEAREST_LAST 2
+#define RPT_WALK_SHADOW 3
+int rpt_debug_walk_production(rpt_ctx *ctx, int kind, size_t n, const float *origins_xyz, const float *dirs_xyz, const float *max_t /* shadow kinds only */,
+                              float *out_t, uint32_t *out_tri, uint32_t *out_flags);
 
 /* The two BSDFs of the reference's kernels crate that trace_pixel never instantiates (kernels/src/bsdf.rs:46-176,
  * SURVEY.md 8f N4), evaluated on the device.  One item = 16 floats in: view(3) normal(3) r(3) albedo(3) ior roughness

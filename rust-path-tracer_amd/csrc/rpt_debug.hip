@@ -241,11 +241,13 @@ int rpt_debug_trace_rays(rpt_ctx *c, int any_hit, size_t n, const float *origins
     return RPT_OK;
 }
 
-/* The same question through the PRODUCTION nearest-hit stage: the rays are written into the context's own slots as pending
- * extension rays, the traversal stage is launched exactly as an iteration of rpt_render launches it for this scene and state
- * (launch_nearest: persistent LDS stream / streamed global-memory walk with or without cooperative leaves / one-shot kernels,
- * per the developer knobs), and the hit records it wrote are read back.  Needs a configuration (the slots); leaves the
- * context as after rpt_reset with nothing rendered — call rpt_reset before rendering again. */
+/* The same question through the PRODUCTION stages (rpt_debug_walk_production; rpt_debug_trace_rays_production is its NEAREST_PLAIN kind).  The nearest kinds:
+ * the rays are written into the context's own slots as pending extension rays — as k_generate_first leaves a slot: HIT_PENDING —, the traversal stage is
+ * launched exactly as an iteration of rpt_render launches it for this scene and state (rpt_launch_nearest: persistent LDS stream, PLAIN / FIRST / LAST;
+ * streamed global-memory walk with or without cooperative leaves; the generic walk — per scene and developer knobs), and the hit records it wrote are read
+ * back.  LAST runs in the form that writes hit records (implicit_zero == 0); its path-ending form — emission added, misses parked, HIT_DONE written by the
+ * walk — and FIRST starting its own paths are covered by renders only.  Needs a configuration (the slots); leaves the context as after rpt_reset with
+ * nothing rendered — call rpt_reset before rendering again. */
 __global__ __launch_bounds__(RPT_BLOCK) void k_debug_load_rays(DevState st, uint32_t n, const float *origins, const float *dirs) {
     const uint32_t i = blockIdx.x * RPT_BLOCK + threadIdx.x;
     if (i >= n) return;
@@ -254,20 +256,90 @@ __global__ __launch_bounds__(RPT_BLOCK) void k_debug_load_rays(DevState st, uint
     set_hit_word(st, i, HIT_PENDING);
 }
 
-int rpt_debug_trace_rays_production(rpt_ctx *c, size_t n, const float *origins, const float *dirs, float *out_t, uint32_t *out_tri, uint32_t *out_flags) {
-    if (!c || !origins || !dirs || !out_t || !out_tri || !out_flags) return RPT_EINVAL;
-    if (!c->has_scene || !c->has_state) { c->error = "rpt_debug_trace_rays_production: needs a scene and a configuration"; return RPT_EINVAL; }
-    if (n == 0) return RPT_OK;
-    if (n > c->n_slots) { c->error = "rpt_debug_trace_rays_production: more rays than the context has slots (" + std::to_string(c->n_slots) + ")"; return RPT_EINVAL; }
-    RPT_TRY(rpt_wait(c));
-    HIP_TRY(c, hipSetDevice(c->device));
+/* The SHADOW kind of rpt_debug_walk_production: ray i becomes entry i - first[s] of shard s, first[s] <= i < first[s + 1], of the sharded shadow queue
+ * (k_common.h q_position) with the tag "slot i, the path goes on" and the contribution (1, 1 + i % 4093, 0); the slot's radiance record and the streamed
+ * walk's entry counter are zeroed and the shard counters set, as the shade stage that fills the queue in a render leaves them (Q_DRAINED stays 0). */
+struct DebugShards { uint32_t first[RPT_Q_SHARDS + 1]; };
+__global__ __launch_bounds__(RPT_BLOCK) void k_debug_load_shadow(DevState st, DevQueues q, uint32_t n, DebugShards sh, const float *origins, const float *dirs, const float *max_t) {
+    const uint32_t i = blockIdx.x * RPT_BLOCK + threadIdx.x;
+    if (i < RPT_Q_SHARDS) q.shadow_cnt[i * RPT_Q_SHARD_STRIDE] = sh.first[i + 1] - sh.first[i];
+    if (i == 0u) q.count[Q_SPOOL] = 0u;
+    if (i >= n) return;
+    uint32_t s = 0u;
+    while (i >= sh.first[s + 1]) s += 1u;
+    const uint32_t at = q_position(s, i - sh.first[s]);
+    q.sh_o[at] = make_float4(origins[3 * i], origins[3 * i + 1], origins[3 * i + 2], max_t[i]);
+    q.sh_d[at] = make_float4(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2], __uint_as_float(i));
+    q.sh_c[at] = make_float4(1.0f, (float)(1u + i % 4093u), 0.0f, 0.0f);
+    st.rad[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+/* the shares of the shards: shard s takes 1 + (7 s + 3) % 16 parts of 136 (a permutation of 1 .. 16, the largest share in shard 4, the smallest in shard 11),
+ * what is left over goes to shard 4 too — one ray alone sits at position 1 024, behind four chunks of unfilled positions */
+static DebugShards debug_shadow_shards(uint32_t n, uint32_t &most) {
+    DebugShards sh;
+    uint32_t cnt[RPT_Q_SHARDS], given = 0u;
+    for (uint32_t s = 0; s < RPT_Q_SHARDS; ++s) { cnt[s] = (uint32_t)((uint64_t)n * (1u + (7u * s + 3u) % 16u) / 136u); given += cnt[s]; }
+    cnt[4] += n - given;
+    most = 0u;
+    sh.first[0] = 0u;
+    for (uint32_t s = 0; s < RPT_Q_SHARDS; ++s) { sh.first[s + 1] = sh.first[s] + cnt[s]; most = std::max(most, cnt[s]); }
+    return sh;
+}
+
+static int debug_walk_shadow(rpt_ctx *c, size_t n, const float *origins, const float *dirs, const float *max_t, uint32_t *out_flags) {
+    uint32_t most = 0u;
+    const DebugShards sh = debug_shadow_shards((uint32_t)n, most);
+    /* the positions the consumers sweep (k_common.h q_extent) must lie inside the queue arrays AND inside the grids rpt_launch_shadow sizes by the slot count */
+    const uint64_t positions = (uint64_t)((most + 255u) >> 8) * (256u * RPT_Q_SHARDS);
+    if (positions > (uint64_t)c->n_slots + RPT_Q_SLACK) {
+        c->error = "rpt_debug_walk_production: " + std::to_string(n) + " shadow rays, filled unevenly, span " + std::to_string(positions) + " queue positions; the queue of this configuration has " +
+                   std::to_string((uint64_t)c->n_slots + RPT_Q_SLACK);
+        return RPT_EINVAL;
+    }
+    RPT_TRY(ensure_slot_state(c, c->n_slots, true, false));
+    DevBuf<float> d_o, d_d, d_m;
+    HIP_TRY(c, d_o.from_host(origins, 3 * n)); HIP_TRY(c, d_d.from_host(dirs, 3 * n)); HIP_TRY(c, d_m.from_host(max_t, n));
+    hipStream_t s = c->stream;
+    RPT_TRY(rpt_idle_all_slots(c));
+    k_debug_load_shadow<<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(c->state, c->queues, (uint32_t)n, sh, d_o.p, d_d.p, d_m.p);
+    rpt_launch_shadow(c);
+    std::vector<float4> rad(n);
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpy(rad.data(), c->rad.p, n * sizeof(float4), hipMemcpyDeviceToHost));
+    RPT_TRY(rpt_idle_all_slots(c));             /* back to "nothing in flight": the shard counters too */
+    HIP_TRY(c, hipStreamSynchronize(s));
+    for (size_t i = 0; i < n; ++i) {
+        const float4 r = rad[i];
+        const bool occluded = r.x == 0.0f && r.y == 0.0f && r.z == 0.0f, visible = r.x == 1.0f && r.y == (float)(1u + (uint32_t)i % 4093u) && r.z == 0.0f;
+        if (!occluded && !visible) {
+            c->error = "rpt_debug_walk_production: shadow ray " + std::to_string(i) + " left the radiance (" + std::to_string(r.x) + ", " + std::to_string(r.y) + ", " + std::to_string(r.z) +
+                       ") in its slot: neither nothing nor its own contribution";
+            return RPT_EHIP;
+        }
+        out_flags[i] = occluded ? 1u : 0u;
+    }
+    return RPT_OK;
+}
+
+/* the nearest kinds: `who` names the entry point in the messages */
+static int debug_walk_nearest(rpt_ctx *c, const char *who, int kind, size_t n, const float *origins, const float *dirs, float *out_t, uint32_t *out_tri, uint32_t *out_flags) {
     RPT_TRY(ensure_slot_state(c, c->n_slots, false, false));
     DevBuf<float> d_o, d_d;
     HIP_TRY(c, d_o.from_host(origins, 3 * n)); HIP_TRY(c, d_d.from_host(dirs, 3 * n));
     hipStream_t s = c->stream;
     RPT_TRY(rpt_idle_all_slots(c));
     k_debug_load_rays<<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(c->state, (uint32_t)n, d_o.p, d_d.p);
-    rpt_launch_nearest(c, 0u, false, false, false);
+    if (kind == RPT_WALK_NEAREST_LAST) {
+        /* the form that writes hit records (k_traverse_nearest.h: done_here false), whatever the last render call left in the flag */
+        const uint32_t implicit_zero = c->queues.implicit_zero;
+        c->queues.implicit_zero = 0u;
+        rpt_launch_nearest(c, 0u, true, false, false);
+        c->queues.implicit_zero = implicit_zero;
+    } else {
+        rpt_launch_nearest(c, 0u, false, kind == RPT_WALK_NEAREST_FIRST, false);
+    }
     std::vector<float2> hits(n);
     HIP_TRY(c, hipStreamSynchronize(s));
     HIP_TRY(c, hipGetLastError());
@@ -277,12 +349,45 @@ int rpt_debug_trace_rays_production(rpt_ctx *c, size_t n, const float *origins, 
     for (size_t i = 0; i < n; ++i) {
         uint32_t w;
         memcpy(&w, &hits[i].y, 4);
-        if (w == HIT_PENDING || w == HIT_IDLE) { c->error = "rpt_debug_trace_rays_production: ray " + std::to_string(i) + " was not traversed"; return RPT_EHIP; }
+        if (w == HIT_PENDING || w == HIT_IDLE) { c->error = std::string(who) + ": ray " + std::to_string(i) + " was not traversed"; return RPT_EHIP; }
         out_t[i] = hits[i].x;
         out_tri[i] = (w == HIT_MISS) ? 0u : (w & 0x7fffffffu);
         out_flags[i] = (w == HIT_MISS) ? 0u : (1u | ((w >> 31) << 1));
     }
     return RPT_OK;
+}
+
+static int debug_walk_production(rpt_ctx *c, const char *who, int kind, size_t n, const float *origins, const float *dirs, const float *max_t, float *out_t, uint32_t *out_tri,
+                                 uint32_t *out_flags) {
+    if (!c) return RPT_EINVAL;
+    if (kind < RPT_WALK_NEAREST_PLAIN || kind > RPT_WALK_SHADOW) { c->error = std::string(who) + ": no such kind of walk"; return RPT_EINVAL; }
+    if (!origins || !dirs || !out_t || !out_tri || !out_flags) { c->error = std::string(who) + ": null ray or result arrays"; return RPT_EINVAL; }
+    if (kind == RPT_WALK_SHADOW && !max_t) { c->error = std::string(who) + ": shadow rays need max_t"; return RPT_EINVAL; }
+    if (!c->has_scene || !c->has_state) { c->error = std::string(who) + ": needs a scene and a configuration"; return RPT_EINVAL; }
+    if (n == 0) return RPT_OK;
+    if (n > c->n_slots) { c->error = std::string(who) + ": more rays than the context has slots (" + std::to_string(c->n_slots) + ")"; return RPT_EINVAL; }
+    if (kind == RPT_WALK_NEAREST_FIRST) {
+        for (size_t i = 0; i < n; ++i)
+            if (memcmp(origins + 3 * i, c->cfg.c.cam_position, 3 * sizeof(float)) != 0) {
+                c->error = std::string(who) + ": the origin of ray " + std::to_string(i) + " is not the configuration's cam_position, which the FIRST walk subtracts from its planes";
+                return RPT_EINVAL;
+            }
+    }
+    RPT_TRY(rpt_wait(c));
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (kind == RPT_WALK_SHADOW) {
+        memset(out_t, 0, n * sizeof(float)); memset(out_tri, 0, n * sizeof(uint32_t));
+        return debug_walk_shadow(c, n, origins, dirs, max_t, out_flags);
+    }
+    return debug_walk_nearest(c, who, kind, n, origins, dirs, out_t, out_tri, out_flags);
+}
+
+int rpt_debug_trace_rays_production(rpt_ctx *c, size_t n, const float *origins, const float *dirs, float *out_t, uint32_t *out_tri, uint32_t *out_flags) {
+    return debug_walk_production(c, "rpt_debug_trace_rays_production", RPT_WALK_NEAREST_PLAIN, n, origins, dirs, nullptr, out_t, out_tri, out_flags);
+}
+
+int rpt_debug_walk_production(rpt_ctx *c, int kind, size_t n, const float *origins, const float *dirs, const float *max_t, float *out_t, uint32_t *out_tri, uint32_t *out_flags) {
+    return debug_walk_production(c, "rpt_debug_walk_production", kind, n, origins, dirs, max_t, out_t, out_tri, out_flags);
 }
 
 /* ---- the gather's second wire format on the host (k_gather.h): the layout arithmetic, and pack -> slots -> un-tile in plain loops over the functions the

@@ -17,6 +17,7 @@ _lib = None
 
 COMM_ID_BYTES = 128
 SHADOW_EXACT, SHADOW_SEGMENT = 0, 1          # rpt_set_shadow_mode
+WALK_NEAREST_PLAIN, WALK_NEAREST_FIRST, WALK_NEAREST_LAST, WALK_SHADOW = 0, 1, 2, 3       # rpt_debug_walk_production
 MODEL_PBR, MODEL_LAMBERTIAN, MODEL_GLASS = 0, 1, 2      # rpt_set_material_models
 
 
@@ -288,6 +289,7 @@ PROTOTYPES = {
     "rpt_debug_rcp_sweep": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, _OUT_U64, C.c_void_p]),
     "rpt_debug_trace_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t] + [C.c_void_p] * 6),
     "rpt_debug_trace_rays_production": (C.c_int, [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5),
+    "rpt_debug_walk_production": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t] + [C.c_void_p] * 6),
     "rpt_debug_bsdf": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]),
     "rpt_debug_sample_image": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]),
     "rpt_debug_comm_selftest": (C.c_int, [C.c_void_p, C.c_uint32, _OUT_U64]),
@@ -846,6 +848,21 @@ class Renderer(_Handle):
         tri = np.zeros(n, np.uint32)
         flags = np.zeros(n, np.uint32)
         self._check(lib().rpt_debug_trace_rays_production(self._h, n, ptr(origins), ptr(dirs), ptr(t), ptr(tri), ptr(flags)))
+        return t, tri, flags
+
+    def debug_walk_production(self, kind, origins, dirs, max_t=None):
+        """rpt_debug_walk_production: chosen rays through the launch functions of rpt_render — kind WALK_NEAREST_PLAIN / _FIRST (every origin the configuration's
+        cam_position) / _LAST, or WALK_SHADOW (max_t per ray; flags bit 0 = occluded, t and triangle stay zero).  Call reset() before rendering again."""
+        origins = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        n = len(origins)
+        if max_t is not None:
+            max_t = np.ascontiguousarray(max_t, np.float32)
+            assert max_t.shape == (n,)
+        t = np.zeros(n, np.float32)
+        tri = np.zeros(n, np.uint32)
+        flags = np.zeros(n, np.uint32)
+        self._check(lib().rpt_debug_walk_production(self._h, int(kind), n, ptr(origins), ptr(dirs), None if max_t is None else ptr(max_t), ptr(t), ptr(tri), ptr(flags)))
         return t, tri, flags
 
 
