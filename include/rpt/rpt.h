@@ -352,6 +352,33 @@ typedef struct rpt_material_model { uint32_t model; float ior; uint32_t reserved
 int rpt_set_material_models(rpt_ctx *ctx, const rpt_material_model *models, size_t n_models);  /* NULL, 0: all PBR */
 int rpt_material_models(rpt_ctx *ctx, rpt_material_model *out, size_t capacity, size_t *n_out);
 int rpt_multi_set_material_models(rpt_multi *m, const rpt_material_model *models, size_t n_models);   /* on every rank */
+/* Thin-lens camera.  Opt-in; the reference's camera is a pinhole with a fixed 90 degree HORIZONTAL field of view (kernels/src/lib.rs:38-51) and
+ * rpt_tracing_config carries a position and two angles only.  The lens replaces lib.rs:38-51 and nothing else of trace_pixel (csrc/k_lens.h states the f32
+ * operations): the film coordinates are scaled by tan_half_fov before the direction is normalized, and with aperture_radius > 0 the ray leaves a point of
+ * the lens disk — radius aperture_radius, in the camera's x-y plane — towards the point where the pinhole ray meets the plane focus_distance in front of the
+ * camera.  The lens sample comes from the two entries of the reference's LDS table that no path reads (0 and 31), so every later draw of a path stays on its
+ * dimension; entry 31 is read by a configuration that needs all 31 dimensions, hence: aperture_radius > 0 with such a configuration is RPT_ECONFIG, from
+ * whichever of rpt_set_config / rpt_set_camera_lens comes second (the first one's setting stays).
+ * The lens is INACTIVE iff tan_half_fov == 1.0f && aperture_radius == 0.0f, whatever the focus: the kernels launched and every output are then what they are
+ * without this call.  An active lens needs two slots per pixel (paths are restarted by the completion kernel only): a context held to one
+ * (rpt_set_samples_in_flight(ctx, 1), an image too large for two) refuses to render with RPT_EINVAL and says so.
+ * rpt_set_camera_lens: holds from the next render call, like the camera fields of rpt_set_config: the CALLER resets the accumulator (rpt_reset); the denoiser's
+ * guides are rebuilt at their next use (through the pixel centre and the LENS CENTRE: sharp whatever the aperture; the filters' plane term follows the field of
+ * view).  Refused with RPT_EINVAL while an asynchronous batch is pending (rpt_wait first), for a tan_half_fov that is not finite or not above 0, an
+ * aperture_radius that is negative or not finite, with aperture_radius > 0 a focus_distance that is not finite or not above 0, and reserved != 0 — the
+ * message names the reason, the lens stays.  NULL: the default.  Survives rpt_set_config and rpt_upload_scene.
+ * rpt_denoise_temporal under tan_half_fov != 1 is refused (RPT_EINVAL): its reprojection is the inverse of the reference's camera.
+ * Not carried by the host mirror rpt_trace_gpu (rpt_host.h). */
+typedef struct rpt_camera_lens {
+    float tan_half_fov;     /* tangent of half the HORIZONTAL field of view; 1.0 = the reference's camera */
+    float aperture_radius;  /* lens radius in scene units; 0 = pinhole */
+    float focus_distance;   /* distance of the plane in focus along the view axis; read only when aperture_radius > 0 */
+    uint32_t reserved;      /* 0 */
+} rpt_camera_lens;
+void rpt_camera_lens_default(rpt_camera_lens *out);          /* {1, 0, 1, 0} */
+int rpt_set_camera_lens(rpt_ctx *ctx, const rpt_camera_lens *lens);   /* NULL = default */
+int rpt_camera_lens_get(rpt_ctx *ctx, rpt_camera_lens *out);
+int rpt_multi_set_camera_lens(rpt_multi *m, const rpt_camera_lens *lens);   /* on every rank */
 /* How the LAST extension rays of a batch of known length are walked when the configuration has no NEE.  At bounce max_bounces - 1 the reference reads three
  * things off intersect_nearest (kernels/src/lib.rs:62-109): a miss adds the sky, a hit on the front of an emissive triangle adds its emission, any other hit
  * adds nothing — so a ray that passes the Moller-Trumbore test of no emissive triangle only has to answer "hit or miss", which the reference's own walk

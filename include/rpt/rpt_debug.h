@@ -197,6 +197,14 @@ int rpt_debug_short_batch(rpt_ctx *ctx, int on);
  * say — on an all-PBR scene it must give the plain kernels' image and counters bit for bit. */
 int rpt_debug_force_model_kernels(rpt_ctx *ctx, int on);
 
+/* The camera rays of rpt_set_camera_lens (csrc/k_lens.h lens_ray) for n chosen (pixel, key) pairs: pixels_xy[i] = x | y << 16, keys[i] = the sample's LDS key
+ * n + offset; origins_out, dirs_out: 3 floats per pair.  config: position, rotation, width and height are read; lens NULL = the default.
+ * rpt_debug_lens_rays_host: the host build of the header — no device needed.  rpt_debug_lens_rays: the same header through a device kernel, with the
+ * configuration and the lens the CONTEXT holds.  RPT_EINVAL for null pointers, a lens rpt_set_camera_lens refuses, a width or height of 0. */
+int rpt_debug_lens_rays_host(const rpt_tracing_config *config, const rpt_camera_lens *lens, const uint32_t *pixels_xy, const uint32_t *keys, size_t n,
+                             float *origins_out, float *dirs_out);
+int rpt_debug_lens_rays(rpt_ctx *ctx, const uint32_t *pixels_xy, const uint32_t *keys, size_t n, float *origins_out, float *dirs_out);
+
 #ifdef __cplusplus
 }
 #endif

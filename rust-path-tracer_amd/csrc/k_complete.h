@@ -108,42 +108,36 @@ __device__ __forceinline__ bool complete_stage_rows(const DevState &st, uint32_t
     }
     return restart;
 }
-/* the finished slots of a block that owe another sample start it (lib.rs:36-60) — never in the one completion of a batch of known length.  From the tile
- * (the record's .w is what the slot owes), row by row; slot k takes the samples k, k + S, ... */
-__device__ __forceinline__ bool complete_restart_rows(const DevState &st, const DevConfig &cfg, uint32_t base, uint32_t kb, uint32_t rows, uint32_t rows_log, uint32_t lane,
-                                                      const float4 *tile, const unsigned long long *row_done, unsigned long long ok_mask, uint32_t new_n, uint32_t rng_offset) {
-    bool started = false;
-#pragma unroll 1
-    for (uint32_t t = 0u; t < rows; ++t) {
-        const uint32_t slot = complete_block_slot(st, base, kb, t, rows, rows_log, lane), p = slot_pix(st, slot) & 63u, k = slot_k(st, slot);
-        const uint32_t todo = __float_as_uint(tile[(k - kb) * RPT_COMPLETE_PITCH + p].w);
-        const bool mine = ((row_done[(slot - base) >> 6] >> lane) & 1ull) != 0ull && ((ok_mask >> p) & 1ull) != 0ull && todo != 0u;
-        const uint32_t n_of = (uint32_t)__shfl((int)new_n, (int)p, RPT_WAVE), offset_of = (uint32_t)__shfl((int)rng_offset, (int)p, RPT_WAVE);
-        if (mine) {
-            start_path(st, cfg, slot, n_of + k, offset_of, todo - 1u);
-            started = true;
-        }
-    }
-    return started;
-}
-/* The kernels: one text (k_complete_body.h: the kernel and the q_shift = 0 row helper it calls) compiled twice; RPT_MOM(...) there is its argument in
- * the moments build and nothing in the plain one, so the plain k_complete is compiled from the text it always had.  k_complete stays a plain kernel under that
+/* The kernels: one text (k_complete_body.h: the kernel and the two helpers it calls that differ between the builds — the q_shift = 0 row helper and the q_shift > 0
+ * restart) compiled twice here; RPT_MOM(...) there is its argument in the moments build and nothing in the plain one, RPT_LENS(...) is nothing in either and
+ * RPT_COMPLETE_START is start_path, so the plain k_complete is compiled from the text it always had.  k_complete stays a plain kernel under that
  * name, not a template instantiation (tests/test_kernel_resources.py finds the completion kernels by the prefix "k_complete"); k_complete_moments is launched
  * instead of it by a context with moments on.  The moments pointer is an argument of that kernel, not a field of DevState, which every stage kernel takes:
- * no other kernel changes. */
+ * no other kernel changes.  rpt_lens.hip compiles the text twice more for a context with an active lens: it defines RPT_COMPLETE_HELPERS_ONLY before it
+ * includes this header, because the two kernels below are plain symbols of rpt_hip.hip. */
+#ifndef RPT_COMPLETE_HELPERS_ONLY
+#define RPT_LENS(...)
+#define RPT_COMPLETE_START(...) start_path(__VA_ARGS__)
 #define RPT_COMPLETE_KERNEL k_complete
 #define RPT_COMPLETE_DIRECT_ROWS complete_direct_rows
+#define RPT_COMPLETE_RESTART_ROWS complete_restart_rows
 #define RPT_MOM(...)
 #include "k_complete_body.h"
 #undef RPT_COMPLETE_KERNEL
 #undef RPT_COMPLETE_DIRECT_ROWS
+#undef RPT_COMPLETE_RESTART_ROWS
 #undef RPT_MOM
 #define RPT_COMPLETE_KERNEL k_complete_moments
 #define RPT_COMPLETE_DIRECT_ROWS complete_direct_rows_moments
+#define RPT_COMPLETE_RESTART_ROWS complete_restart_rows_moments
 #define RPT_MOM(...) __VA_ARGS__
 #include "k_complete_body.h"
 #undef RPT_COMPLETE_KERNEL
 #undef RPT_COMPLETE_DIRECT_ROWS
+#undef RPT_COMPLETE_RESTART_ROWS
 #undef RPT_MOM
+#undef RPT_COMPLETE_START
+#undef RPT_LENS
+#endif /* RPT_COMPLETE_HELPERS_ONLY */
 
 #endif /* RPT_K_COMPLETE_H */

@@ -1,8 +1,11 @@
 /*
- * k_complete_body.h — the text of the completion kernels, compiled twice by k_complete.h (as k_traverse_shadow_kernels.h is by rpt_traverse.hip):
- *   RPT_COMPLETE_KERNEL k_complete,         RPT_MOM(...) nothing         the kernel every context launches by default — a plain kernel under that name
- *   RPT_COMPLETE_KERNEL k_complete_moments, RPT_MOM(...) its argument    with the moments record (rpt_set_moments): one more pointer argument
- * RPT_COMPLETE_DIRECT_ROWS names the row helper of the build.  No include guard: k_complete.h defines the three macros around each inclusion.
+ * k_complete_body.h — the text of the completion kernels, compiled once per build (as k_traverse_shadow_kernels.h is by rpt_traverse.hip):
+ *   RPT_COMPLETE_KERNEL k_complete,              RPT_MOM(...) nothing       the kernel every context launches by default — a plain kernel under that name
+ *   RPT_COMPLETE_KERNEL k_complete_moments,      RPT_MOM(...) its argument  with the moments record (rpt_set_moments): one more pointer argument
+ *   RPT_COMPLETE_KERNEL k_lens_complete, k_lens_complete_moments            the same two with RPT_LENS(...) its argument — one more argument, the lens — and
+ *                                                                           RPT_COMPLETE_START the lens's start of a path (rpt_lens.hip, rpt_set_camera_lens)
+ * RPT_COMPLETE_DIRECT_ROWS and RPT_COMPLETE_RESTART_ROWS name the two helpers of the build that hold its macros; RPT_COMPLETE_START(st, cfg, slot, n, offset, todo_after)
+ * is how a finished slot starts its next sample (k_complete.h: k_path.h start_path).  No include guard: the includer defines the six macros around each inclusion.
  */
 /* pass 2 at q_shift = 0 (every shipped scene): row k of the chunk IS sample k of its 64 pixels with the lane's own pixel in its own lane — nothing to
  * transpose, no tile: G rows in flight, added in order straight from the registers; finished slots (k < n_done: the prefix) that owe nothing go idle.
@@ -30,8 +33,26 @@ __device__ __forceinline__ bool RPT_COMPLETE_DIRECT_ROWS(const DevState &st, uin
     }
     return restart;
 }
+/* the finished slots of a block that owe another sample start it (lib.rs:36-60) — never in the one completion of a batch of known length.  From the tile
+ * (the record's .w is what the slot owes), row by row; slot k takes the samples k, k + S, ... */
+__device__ __forceinline__ bool RPT_COMPLETE_RESTART_ROWS(const DevState &st, const DevConfig &cfg, uint32_t base, uint32_t kb, uint32_t rows, uint32_t rows_log, uint32_t lane,
+                                                      const float4 *tile, const unsigned long long *row_done, unsigned long long ok_mask, uint32_t new_n, uint32_t rng_offset RPT_LENS(, const DevLens &lens)) {
+    bool started = false;
+#pragma unroll 1
+    for (uint32_t t = 0u; t < rows; ++t) {
+        const uint32_t slot = complete_block_slot(st, base, kb, t, rows, rows_log, lane), p = slot_pix(st, slot) & 63u, k = slot_k(st, slot);
+        const uint32_t todo = __float_as_uint(tile[(k - kb) * RPT_COMPLETE_PITCH + p].w);
+        const bool mine = ((row_done[(slot - base) >> 6] >> lane) & 1ull) != 0ull && ((ok_mask >> p) & 1ull) != 0ull && todo != 0u;
+        const uint32_t n_of = (uint32_t)__shfl((int)new_n, (int)p, RPT_WAVE), offset_of = (uint32_t)__shfl((int)rng_offset, (int)p, RPT_WAVE);
+        if (mine) {
+            RPT_COMPLETE_START(st, cfg, slot, n_of + k, offset_of, todo - 1u);
+            started = true;
+        }
+    }
+    return started;
+}
 __global__ __launch_bounds__(RPT_WAVE) void RPT_COMPLETE_KERNEL(DevState st, DevQueues q, DevConfig cfg, uint32_t iteration, uint32_t final_pass,
-                                                                DevStats *stats RPT_MOM(, float4 *moments /* n_pixels records beside st.accum */)) {
+                                                                DevStats *stats RPT_MOM(, float4 *moments /* n_pixels records beside st.accum */) RPT_LENS(, DevLens lens)) {
     /* a surplus launch of the run-ahead returns at once (grid-uniform) — but not the one completion of a batch of known length:
      * "drained" there only says that no RAY was left in an earlier iteration, the finished samples still wait to be added */
     if (!final_pass && q.count[Q_DRAINED] != 0u) return;
@@ -92,7 +113,7 @@ __global__ __launch_bounds__(RPT_WAVE) void RPT_COMPLETE_KERNEL(DevState st, Dev
                         const bool has_rad = ok && k < n_done && ((rad_bits >> (k - k0)) & 1u) != 0u;
                         const uint32_t todo = has_rad ? __float_as_uint(st.rad[slot].w) : 0u;
                         if (todo != 0u) {
-                            start_path(st, cfg, slot, new_n + k, rs.y, todo - 1u);      /* slot k takes the samples k, k + S, ... */
+                            RPT_COMPLETE_START(st, cfg, slot, new_n + k, rs.y, todo - 1u);      /* slot k takes the samples k, k + S, ... */
                             started = true;
                         }
                     }
@@ -114,7 +135,7 @@ __global__ __launch_bounds__(RPT_WAVE) void RPT_COMPLETE_KERNEL(DevState st, Dev
                 if (ok && kb + kl < n_done) { acc.x += r.x; acc.y += r.y; acc.z += r.z; acc.w += 1.0f; }
                 RPT_MOM(if (ok && kb + kl < n_done) mo_add(mom, r.x, r.y, r.z);)
             }
-            if (restart) started |= complete_restart_rows(st, cfg, base, kb, rows, rows_log, lane, tile, row_done, ok_mask, new_n, rs.y);
+            if (restart) started |= RPT_COMPLETE_RESTART_ROWS(st, cfg, base, kb, rows, rows_log, lane, tile, row_done, ok_mask, new_n, rs.y RPT_LENS(, lens));
             __syncthreads();
         }
         if (ok) {

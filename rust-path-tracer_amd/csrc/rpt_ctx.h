@@ -3,7 +3,7 @@
  * librpt_hip.so (rpt_hip.hip: life cycle, state and wavefront scheduling; rpt_scene.hip: scene preparation; rpt_traverse.hip: the traversal stages;
  * rpt_comm.hip: multi-GPU gather over RCCL, read-back; rpt_denoise.hip: guide buffers and the denoise filter; rpt_moments.hip: sample moments, noise estimate,
  * render to a noise target; rpt_adaptive.hip: masked passes over chosen pixels, per-pixel counts to a noise target; rpt_models.hip: material models and the
- * shade stage's models variant; rpt_debug.hip: test hooks).  k_image_order.h: the one kernel and the one read-out routine that turn the tile-major pixel order
+ * shade stage's models variant; rpt_lens.hip: the thin-lens camera and the kernels that start paths through it; rpt_debug.hip: test hooks).  k_image_order.h: the one kernel and the one read-out routine that turn the tile-major pixel order
  * into a row-major image, for every unit that hands one to the caller.
  */
 #ifndef RPT_CTX_H
@@ -262,6 +262,9 @@ struct rpt_ctx {
     std::vector<rpt_material_model> material_models_host;
     bool models_in_use = false;                /* some record is not PBR: the shade stage is k_shade_models */
     bool force_model_kernels = false;          /* rpt_debug_force_model_kernels: k_shade_models whatever the records say (none: every material PBR) */
+    /* rpt_set_camera_lens (rpt_lens.hip, k_lens.h): handed to the lens kernels as an argument of its own — DevConfig is what it was.  Active (anything but
+     * {1, 0, *}): render calls open with k_generate_lens, complete with the lens builds of the completion kernels and keep at least two slots per pixel busy */
+    rpt_camera_lens lens{1.0f, 0.0f, 1.0f, 0u};
     uint32_t bvh_depth = 0;
     int stack_cap = 16;
 
@@ -337,6 +340,18 @@ void rpt_launch_shadow(rpt_ctx *c);
  * "no records", for rpt_upload_scene */
 void rpt_launch_shade_models(rpt_ctx *c, uint32_t iteration, uint32_t blocks);
 void rpt_material_models_clear(rpt_ctx *c);
+/* rpt_lens.hip: the lens is anything but the reference's camera; its primary rays leave different origins (aperture > 0: iteration 0 is the plain walk) */
+inline bool rpt_lens_active(const rpt_ctx *c) { return !(c->lens.tan_half_fov == 1.0f && c->lens.aperture_radius == 0.0f); }
+inline bool rpt_lens_scatters_origins(const rpt_ctx *c) { return c->lens.aperture_radius > 0.0f; }
+/* the opening pass of a render call under an active lens (k_generate_lens over all slots, in place of k_generate_first), its completion kernel (in place of
+ * k_complete / k_complete_moments, same grid and LDS) and the centre rays of the denoiser's guides (in place of k_dn_camera_rays) */
+void rpt_launch_generate_lens(rpt_ctx *c, uint32_t n_samples, uint32_t blocks);
+void rpt_launch_complete_lens(rpt_ctx *c, uint32_t iteration, uint32_t final_pass, uint32_t waves, size_t lds_bytes);
+void rpt_launch_guide_rays_lens(rpt_ctx *c, const uint32_t *order, uint32_t n, float *origins, float *dirs);
+/* rpt_hip.hip: the LDS dimensions a configuration's paths draw (kernels/src/rng.rs:20-21,51-54; the table has 31 usable), and the refusal of an aperture
+ * under a configuration that needs all 31 — entry 31 is the lens sample's (k_lens.h); `who`: the entry point that came second */
+uint64_t rpt_config_dimensions(const rpt_tracing_config &cfg);
+int rpt_lens_check_dimensions(rpt_ctx *c, const rpt_tracing_config &cfg, const rpt_camera_lens &lens, const char *who);
 void rpt_launch_trace_debug(rpt_ctx *c, int any_hit /* 0 nearest, 1 any-hit, 2 segment-bounded any-hit */, uint32_t n, const float *origins, const float *dirs, const float *max_t, float *out_t, uint32_t *out_tri,
                             uint32_t *out_flags);
 hipError_t rpt_last_walk_attributes(hipFuncAttributes *out);      /* of k_traverse_nearest_stream<.., LAST>: its static LDS decides whether the flipped copy fits */

@@ -57,6 +57,11 @@ int check_temporal_params(const rpt_temporal_params &p, uint32_t tonemap_op, std
     return RPT_OK;
 }
 
+/* The plane term of the filters is the pixel footprint per unit depth, 2 / W (k_denoise.h DnPass::plane_scale), under a lens 2 tan_half_fov / W: the factor
+ * enters through the parameter — sigma_plane * tan_half_fov, one f32 product on the host, the identity at 1.0f — so it reaches the device passes and the
+ * host builds (rpt_debug_denoise_host, ..._variance_host: handed that sigma_plane) by the one route every parameter takes, dn_pass. */
+float lens_sigma_plane(const rpt_ctx *c, float sigma_plane) { return sigma_plane * c->lens.tan_half_fov; }
+
 /* buffers + events for the current configuration (first use, or the first use after a resize released them) */
 int ensure_buffers(rpt_ctx *c) {
     DenoiseState &d = c->dn;
@@ -108,7 +113,8 @@ int build_guides_through_glass(rpt_ctx *c) {
     GgResult got{};
     HIP_TRY(c, hipEventRecord(d.ev[0], s));
     HIP_TRY(c, hipMemsetAsync(res, 0, sizeof(GgResult), s));
-    k_dn_camera_rays<<<blocks, RPT_BLOCK, 0, s>>>(c->cfg, d.order.p, n, origins0, dirs0);
+    if (rpt_lens_active(c)) rpt_launch_guide_rays_lens(c, d.order.p, n, origins0, dirs0);      /* (rpt_set_camera_lens: pixel centre through the lens centre, with its field of view) */
+    else k_dn_camera_rays<<<blocks, RPT_BLOCK, 0, s>>>(c->cfg, d.order.p, n, origins0, dirs0);
     uint32_t n_cur = n;
     for (uint32_t round = 0; round <= K && n_cur != 0u; ++round) {        /* (a ray of round r has crossed r interfaces: round K ends every chain) */
         const GgRays in{round ? cur_o : origins0, round ? cur_d : dirs0, round ? cur_slot : nullptr, hit_t, hit_tri, hit_flags};
@@ -160,7 +166,8 @@ int ensure_guides(rpt_ctx *c, bool *rebuilt) {
     uint32_t *hit_tri = rays.take<uint32_t>(n), *hit_flags = rays.take<uint32_t>(n);
     hipStream_t s = c->stream;
     HIP_TRY(c, hipEventRecord(d.ev[0], s));
-    k_dn_camera_rays<<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(c->cfg, d.order.p, n, origins, dirs);
+    if (rpt_lens_active(c)) rpt_launch_guide_rays_lens(c, d.order.p, n, origins, dirs);
+    else k_dn_camera_rays<<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(c->cfg, d.order.p, n, origins, dirs);
     rpt_launch_trace_debug(c, 0, n, origins, dirs, nullptr, hit_t, hit_tri, hit_flags);
     if (c->scene.textured) k_dn_shade_guides<true><<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(c->scene, d.width, d.order.p, n, origins, dirs, hit_t, hit_tri, hit_flags, d.g0.p, d.g1.p, d.albedo.p);
     else k_dn_shade_guides<false><<<rpt_blocks(n), RPT_BLOCK, 0, s>>>(c->scene, d.width, d.order.p, n, origins, dirs, hit_t, hit_tri, hit_flags, d.g0.p, d.g1.p, d.albedo.p);
@@ -369,8 +376,9 @@ void rpt_denoise_params_default(rpt_denoise_params *out) {
 
 int rpt_denoise(rpt_ctx *c, uint32_t source, const rpt_denoise_params *params, uint32_t tonemap_op, float *out_rgb, rpt_denoise_report *report) {
     if (!c || !out_rgb) return RPT_EINVAL;
-    const rpt_denoise_params p = params ? *params : DN_DEFAULTS;
+    rpt_denoise_params p = params ? *params : DN_DEFAULTS;
     RPT_TRY(check_params(p, tonemap_op, c->error));
+    p.sigma_plane = lens_sigma_plane(c, p.sigma_plane);
     DnSource in;
     RPT_TRY(open_source(c, source, &in));
     const float4 *sums = in.sums;
@@ -415,9 +423,10 @@ int rpt_denoise_variance(rpt_ctx *c, uint32_t source, const float *moments_xyzw,
                          rpt_denoise_report *report) {
     if (!c) return RPT_EINVAL;
     if (!out_rgb) { c->error = "rpt_denoise_variance: out_rgb is null"; return RPT_EINVAL; }
-    const rpt_denoise_var_params vp = params ? *params : DN_VAR_DEFAULTS;
+    rpt_denoise_var_params vp = params ? *params : DN_VAR_DEFAULTS;
     const rpt_denoise_params &p = vp.base;
     RPT_TRY(check_var_params(vp, tonemap_op, c->error));
+    vp.base.sigma_plane = lens_sigma_plane(c, vp.base.sigma_plane);
     RPT_TRY(check_moments_source(c, source, moments_xyzw, "rpt_denoise_variance"));
     DnSource in;
     RPT_TRY(open_source(c, source, &in));
@@ -478,6 +487,11 @@ int rpt_denoise_temporal(rpt_ctx *c, uint32_t source, const float *moments_xyzw,
     const rpt_temporal_params tp = params ? *params : TP_DEFAULTS;
     const rpt_denoise_params &p = tp.filter.base;
     RPT_TRY(check_temporal_params(tp, tonemap_op, c->error));
+    if (c->lens.tan_half_fov != 1.0f) {      /* (an aperture alone: the projection is the lens centre's, the reference camera's) */
+        c->error = "rpt_denoise_temporal: the camera lens has a field of view (tan_half_fov != 1): the reprojection is the inverse of the reference's camera; "
+                   "rpt_denoise_variance filters the same image without history";
+        return RPT_EINVAL;
+    }
     RPT_TRY(check_moments_source(c, source, moments_xyzw, "rpt_denoise_temporal"));
     DnSource in;
     RPT_TRY(open_source(c, source, &in));

@@ -168,6 +168,10 @@ static uint32_t padded_pixels(uint32_t n_pixels) { return (n_pixels + 63u) & ~63
 
 /* one wave per chunk of 64 pixels (k_complete.h) */
 static void launch_complete(rpt_ctx *c, uint32_t iteration, uint32_t final_pass) {
+    if (rpt_lens_active(c)) {        /* (rpt_set_camera_lens: the same completions, a restarted path takes the lens's ray — rpt_lens.hip) */
+        rpt_launch_complete_lens(c, iteration, final_pass, padded_pixels(c->n_pixels) / RPT_WAVE, complete_lds_bytes(1u << c->group_shift, c->state.q_shift));
+        return;
+    }
     if (c->moments_on) {             /* (rpt_set_moments: the same completion, the samples added to the moments record too — the view's compact one in a masked pass) */
         k_complete_moments<<<padded_pixels(c->n_pixels) / RPT_WAVE, RPT_WAVE, complete_lds_bytes(1u << c->group_shift, c->state.q_shift), c->stream>>>(c->state, c->queues, c->cfg, iteration,
                                                                                                                                  final_pass, c->dev_stats.p, c->view ? c->view->moments : c->moments.p);
@@ -187,7 +191,8 @@ uint32_t launch_iteration(rpt_ctx *c, uint32_t iteration, uint32_t blocks, bool 
     const uint32_t blocks_q = rpt_blocks(c->n_slots + RPT_Q_SLACK);
     /* (the shade stage's last_iteration, k_shade.h: in a batch of known length iteration k is bounce k of every path) */
     const bool ended = rpt_launch_nearest(c, iteration, NEE == RPT_NEE_NONE && c->queues.known_length != 0u && iteration != 0u && iteration + 1u >= c->cfg.c.max_bounces,
-                                          iteration == 0u, iteration == 0u && c->first_walk_starts);
+                                          iteration == 0u && !rpt_lens_scatters_origins(c) /* (an aperture: the camera rays leave a disk, the plain walk takes them) */,
+                                          iteration == 0u && c->first_walk_starts);
     t.mark(s, RPT_STAGE_TRAVERSE, StageTimer::AT_1 | StageTimer::AT_2);
     if (!ended) {                                           /* (ended: nothing is left for a shade stage, every path of the launch is HIT_DONE or waits in the sky queue) */
         if (c->models_in_use || c->force_model_kernels) rpt_launch_shade_models(c, iteration, blocks);     /* (rpt_set_material_models: some material is not PBR) */
@@ -232,6 +237,20 @@ void rpt_camera_matrix(const float *cam_rotation, float *euler_out) {
     rotation_y(cam_rotation[1], ry);
     rotation_x(cam_rotation[0], rx);
     mat3_mul_host(ry, rx, euler_out);
+}
+
+uint64_t rpt_config_dimensions(const rpt_tracing_config &cfg) {
+    const uint32_t nee_mode = cfg.nee <= 2u ? cfg.nee : 0u;
+    const uint64_t per_bounce = 3u + (nee_mode ? 4u : 0u);
+    const uint64_t rr = cfg.max_bounces > cfg.min_bounces + 1u ? cfg.max_bounces - 1u - cfg.min_bounces : 0u;
+    return 2u + (uint64_t)cfg.max_bounces * per_bounce + rr;
+}
+
+int rpt_lens_check_dimensions(rpt_ctx *c, const rpt_tracing_config &cfg, const rpt_camera_lens &lens, const char *who) {
+    if (!(lens.aperture_radius > 0.0f) || rpt_config_dimensions(cfg) < 31u) return RPT_OK;
+    c->error = std::string(who) + ": the configuration needs all 31 LDS dimensions and the lens has an aperture: its sample takes entry 31 of the reference's table "
+               "(aperture_radius = 0, or a configuration of at most 30 dimensions)";
+    return RPT_ECONFIG;
 }
 
 /* The per-slot arrays, for a render call over `n` slots: grown (never shrunk) to what the call needs — the path state always, the shadow
@@ -389,13 +408,12 @@ int rpt_set_config(rpt_ctx *c, const rpt_tracing_config *cfg) {
     if (cfg->max_bounces > 255u) { c->error = "max_bounces > 255"; return RPT_ECONFIG; }
     {
         /* LDS dimension budget (kernels/src/rng.rs:20-21,51-54): the CPU reference panics past 31 */
-        uint64_t per_bounce = 3u + (nee_mode ? 4u : 0u);
-        uint64_t rr = cfg->max_bounces > cfg->min_bounces + 1u ? cfg->max_bounces - 1u - cfg->min_bounces : 0u;
-        uint64_t dims = 2u + (uint64_t)cfg->max_bounces * per_bounce + rr;
+        const uint64_t dims = rpt_config_dimensions(*cfg);
         if (dims > 31u) {
             c->error = "config needs " + std::to_string(dims) + " LDS dimensions; the reference's table has 31 usable";
             return RPT_ECONFIG;
         }
+        RPT_TRY(rpt_lens_check_dimensions(c, *cfg, c->lens, "rpt_set_config"));
     }
     HIP_TRY(c, hipSetDevice(c->device));
     bool resized = !c->has_config || c->cfg.c.width != cfg->width || c->cfg.c.height != cfg->height;
@@ -539,6 +557,12 @@ int rpt_stream(rpt_ctx *c, void **stream_out) {
 static int plan_slots(rpt_ctx *c, uint32_t n_samples) {
     uint32_t shift = 0;
     while (shift < c->max_group_shift && (1u << shift) < n_samples) shift += 1;
+    if (rpt_lens_active(c) && shift == 0u && c->max_group_shift == 0u) {      /* (as moments below: the side stages restart a path with the reference's camera) */
+        c->error = "the camera lens is active and this context keeps one sample of a pixel in flight (rpt_set_samples_in_flight(1), or an image too large for two slots per pixel): "
+                   "paths under a lens are started by the completion kernel, which needs at least two; call rpt_set_samples_in_flight(0) or (>= 2), or rpt_set_camera_lens(ctx, NULL)";
+        return RPT_EINVAL;
+    }
+    if (rpt_lens_active(c) && shift == 0u) shift = 1u;
     if (c->moments_on && shift == 0u) {
         if (c->max_group_shift == 0u) {
             c->error = "moments are on and this context keeps one sample of a pixel in flight (rpt_set_samples_in_flight(1), or an image too large for two slots per pixel): "
@@ -662,8 +686,11 @@ static int render_impl(rpt_ctx *c, uint32_t n_samples, bool allow_async, const P
     t.mark(s, StageTimer::NONE, StageTimer::AT_1);
     /* The stage that opens a render call.  Where the first walk starts the paths itself (an LDS-resident scene, several slots per pixel) it is ONE workgroup
      * that zeroes the call's counters; else a pass over all slots that also writes every slot's camera ray. */
-    c->first_walk_starts = rpt_first_walk_starts_paths(c);
-    k_generate_first<<<c->first_walk_starts ? 1u : blocks, RPT_BLOCK, 0, s>>>(c->state, c->queues, c->cfg, n_samples, c->dev_stats.p, c->first_walk_starts ? 1u : 0u);
+    /* Under an active lens (rpt_set_camera_lens) it is k_generate_lens over all slots: the FIRST walk knows the reference's camera only.  With aperture 0 the
+     * rays still share cam_position and iteration 0 stays the FIRST kernel over prepared slots; with an aperture it is the plain walk (launch_iteration). */
+    c->first_walk_starts = !rpt_lens_active(c) && rpt_first_walk_starts_paths(c);
+    if (rpt_lens_active(c)) rpt_launch_generate_lens(c, n_samples, blocks);
+    else k_generate_first<<<c->first_walk_starts ? 1u : blocks, RPT_BLOCK, 0, s>>>(c->state, c->queues, c->cfg, n_samples, c->dev_stats.p, c->first_walk_starts ? 1u : 0u);
     c->stats.kernel_launches[RPT_STAGE_GENERATE] += 1;
     t.mark(s, RPT_STAGE_GENERATE, StageTimer::AT_1);
 

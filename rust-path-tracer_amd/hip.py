@@ -27,6 +27,24 @@ def material_models(models, iors=None):
     rec["model"] = models
     rec["ior"] = 1.5 if iors is None else iors
     return rec
+
+
+class CameraLens(C.Structure):
+    """rpt_camera_lens"""
+    _fields_ = [("tan_half_fov", C.c_float), ("aperture_radius", C.c_float), ("focus_distance", C.c_float), ("reserved", C.c_uint32)]
+
+
+def tan_half_fov(degrees):
+    """tan_half_fov of a HORIZONTAL field of view in degrees (90: the reference's camera, 1.0)"""
+    import math
+    return 1.0 if degrees == 90 else math.tan(math.radians(degrees) / 2.0)
+
+
+def camera_lens(tan_half_fov=1.0, aperture_radius=0.0, focus_distance=1.0):
+    """an rpt_camera_lens; the defaults are the reference's pinhole"""
+    return CameraLens(tan_half_fov, aperture_radius, focus_distance, 0)
+
+
 MULTI_ALLOW_SHARED_DEVICE = 1
 DENOISE_ACCUM, DENOISE_GATHERED = 0, 1       # rpt_denoise: which image
 GUIDE_MISS, GUIDE_SURFACE, GUIDE_EMITTER = 0, 1, 2
@@ -241,6 +259,10 @@ PROTOTYPES = {
     "rpt_set_material_models": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "rpt_material_models": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _OUT_SIZE]),
     "rpt_multi_set_material_models": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rpt_camera_lens_default": (None, [C.c_void_p]),
+    "rpt_set_camera_lens": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rpt_camera_lens_get": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rpt_multi_set_camera_lens": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rpt_last_bounce_order": (C.c_int, [C.c_void_p, _OUT_U32, _OUT_U32, _OUT_F64, _OUT_U32, _OUT_F64]),
     "rpt_denoise_params_default": (None, [C.POINTER(DenoiseParams)]),
     "rpt_denoise": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(DenoiseParams), C.c_uint32, C.c_void_p, C.POINTER(DenoiseReport)]),
@@ -307,6 +329,8 @@ PROTOTYPES = {
     "rpt_debug_gather_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 6 + [C.POINTER(GatheredInfo)]),
     "rpt_debug_short_batch": (C.c_int, [C.c_void_p, C.c_int]),
     "rpt_debug_force_model_kernels": (C.c_int, [C.c_void_p, C.c_int]),
+    "rpt_debug_lens_rays_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "rpt_debug_lens_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
 }
 EXPORTS = sorted(PROTOTYPES)
 
@@ -448,6 +472,13 @@ class _Handle:
             return
         records = np.ascontiguousarray(records, MATERIAL_MODEL_DTYPE)
         self._call("set_material_models", ptr(records), len(records))
+
+    def set_camera_lens(self, lens=None, **fields):
+        """rpt_set_camera_lens (rpt_multi_: on every rank): a CameraLens, or its fields by name (tan_half_fov — see hip.tan_half_fov(degrees) —, aperture_radius,
+        focus_distance); None and no field: the reference's pinhole again.  Holds from the next render call; the caller resets the accumulator."""
+        if lens is None and fields:
+            lens = camera_lens(**fields)
+        self._call("set_camera_lens", None if lens is None else C.byref(lens))
 
     def set_guides_through_glass(self, max_interfaces):
         """rpt_set_guides_through_glass (rpt_multi_: on every rank): 0 (default) first-hit guides; 1 .. GUIDES_MAX_INTERFACES: the denoiser's guides follow
@@ -701,6 +732,19 @@ class Renderer(_Handle):
         out = np.zeros(n.value, MATERIAL_MODEL_DTYPE)
         self._check(lib().rpt_material_models(self._h, ptr(out), len(out), C.byref(n)))
         return out
+
+    def camera_lens(self):
+        """rpt_camera_lens_get: the lens as set (a CameraLens)"""
+        out = CameraLens()
+        self._check(lib().rpt_camera_lens_get(self._h, C.byref(out)))
+        return out
+
+    def debug_lens_rays(self, pixels_xy, keys):
+        """rpt_debug_lens_rays (test hook): the context's camera rays for (x | y << 16, key) pairs through a device kernel: (origins, dirs), (n, 3) float32 each"""
+        pixels_xy, keys = np.ascontiguousarray(pixels_xy, np.uint32), np.ascontiguousarray(keys, np.uint32)
+        o, d = np.zeros((len(keys), 3), np.float32), np.zeros((len(keys), 3), np.float32)
+        self._check(lib().rpt_debug_lens_rays(self._h, ptr(pixels_xy), ptr(keys), len(keys), ptr(o), ptr(d)))
+        return o, d
 
     def debug_force_model_kernels(self, on=True):
         """rpt_debug_force_model_kernels (test hook): the models variant of the shade stage whatever the records say"""
@@ -972,6 +1016,16 @@ def tile_order(width, height, rank, world_size):
     if rc != 0:
         raise RptError(rc, "rpt_tile_order")
     return out
+
+
+def lens_rays_host(config, lens, pixels_xy, keys):
+    """rpt_debug_lens_rays_host: the camera rays of a configuration and a CameraLens (None: the default) for (x | y << 16, key) pairs, on the host"""
+    pixels_xy, keys = np.ascontiguousarray(pixels_xy, np.uint32), np.ascontiguousarray(keys, np.uint32)
+    o, d = np.zeros((len(keys), 3), np.float32), np.zeros((len(keys), 3), np.float32)
+    rc = lib().rpt_debug_lens_rays_host(C.byref(config), None if lens is None else C.byref(lens), ptr(pixels_xy), ptr(keys), len(keys), ptr(o), ptr(d))
+    if rc != 0:
+        raise RptError(rc, lib().rpt_last_error(None).decode())
+    return o, d
 
 
 def last_order_host(world):
