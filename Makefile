@@ -2,7 +2,7 @@
 #   rust-path-tracer_amd/lib/librpt_hip.so   HIP kernels + C ABI (gfx950, hipcc)
 #   rust-path-tracer_amd/lib/librpt_host.so  host-side dispatch mirror (g++)
 #   oracle/liboracle.so, oracle/liboracle_libm.so   CPU restatement (test infrastructure)
-#   oracle/libmodels_oracle.so                      the same with a material's model at lib.rs:144 (test infrastructure; source: tests/models_oracle)
+#   oracle/libmodels_oracle.so                      the same with a material's model at lib.rs:144, and the lens too (test infrastructure; source: tests/models_oracle)
 #   oracle/liblens_oracle.so                        the same with the thin-lens camera at lib.rs:38-51 (test infrastructure; source: tests/lens_oracle)
 # -ffp-contract=off everywhere: the parity contract forbids implicit FMA fusion.
 
@@ -48,13 +48,13 @@ oracle/liboracle_libm.so: oracle/rpt_oracle.cpp oracle/bvh_oracle.cpp $(CSRC)/rp
 # textually); -Bsymbolic: its copy of the oracle's exported names binds to itself, whichever library a process loaded first.  Built BESIDE the oracle, not
 # beside its source: a build product under tests/ is lost when another commit's tests/ is put over a built tree, and the tests of that commit then fail
 models_oracle: oracle/libmodels_oracle.so
-oracle/libmodels_oracle.so: tests/models_oracle/models_oracle.cpp oracle/rpt_oracle.cpp $(CSRC)/rpt_math.h $(CSRC)/rpt_fastdiv.h $(CSRC)/rpt_rcp.h $(CSRC)/rpt_math_consts.h include/rpt/shared_structs.h
+oracle/libmodels_oracle.so: tests/models_oracle/models_oracle.cpp tests/lens_oracle/lens_camera.h oracle/rpt_oracle.cpp $(CSRC)/rpt_math.h $(CSRC)/rpt_fastdiv.h $(CSRC)/rpt_rcp.h $(CSRC)/rpt_math_consts.h include/rpt/shared_structs.h
 	$(CXX) $(ORACLE_FLAGS) -shared -Wl,-Bsymbolic -o $@ tests/models_oracle/models_oracle.cpp
 
 # test infrastructure: the restatement of trace_pixel with the thin-lens camera of rpt_set_camera_lens in place of lib.rs:38-51 (tests/lens_oracle/lens_oracle.cpp
 # includes oracle/rpt_oracle.cpp textually), built like models_oracle
 lens_oracle: oracle/liblens_oracle.so
-oracle/liblens_oracle.so: tests/lens_oracle/lens_oracle.cpp oracle/rpt_oracle.cpp $(CSRC)/rpt_math.h $(CSRC)/rpt_fastdiv.h $(CSRC)/rpt_rcp.h $(CSRC)/rpt_math_consts.h include/rpt/shared_structs.h
+oracle/liblens_oracle.so: tests/lens_oracle/lens_oracle.cpp tests/lens_oracle/lens_camera.h oracle/rpt_oracle.cpp $(CSRC)/rpt_math.h $(CSRC)/rpt_fastdiv.h $(CSRC)/rpt_rcp.h $(CSRC)/rpt_math_consts.h include/rpt/shared_structs.h
 	$(CXX) $(ORACLE_FLAGS) -shared -Wl,-Bsymbolic -o $@ tests/lens_oracle/lens_oracle.cpp
 
 # the fingerprint of the device-side sources is compiled in (rpt_build_fingerprint): bench.py reports PMC-derived figures only for the

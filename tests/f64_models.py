@@ -145,8 +145,11 @@ def _direct_lighting(mis, sc, rng, mask, throughput, bsdf, lambert, point, norma
                 contribution=throughput * direct, margin=np.minimum(m_pick, m_shadow))
 
 
-def trace(cfg, world, models, px, py, n, offset, skybox=None):
-    """f64_ref.trace with the model switch: models = records with fields model, ior, one per material -> (radiance (N, 3), margin, min_cosine, sky_y)"""
+def trace(cfg, world, models, px, py, n, offset, skybox=None, lens=None):
+    """f64_ref.trace with the model switch: models = records with fields model, ior, one per material -> (radiance (N, 3), margin, min_cosine, sky_y).
+    lens: (tan_half_fov, aperture_radius, focus_distance) of rpt_set_camera_lens, or None for the reference's camera; the ray is then the float64 reading
+    of csrc/k_lens.h's formulas in tests/lens_ref.py rays_f64, whose only f32 inputs are the record and the LDS draws (the jitter's two, which the rng
+    below draws as well, and entries 0 and 31)"""
     sc = world if isinstance(world, f64_ref.Scene) else f64_ref.Scene(world, skybox)
     model_of, ior_of = np.asarray(models["model"], np.int64), np.asarray(models["ior"], np.float64)
     N = len(px)
@@ -156,7 +159,14 @@ def trace(cfg, world, models, px, py, n, offset, skybox=None):
     rng = f64_ref.Rng(n, offset)
     every = np.ones(N, bool)
     with np.errstate(all="ignore"):
-        origin, direction = f64_ref.camera_rays(cfg, np.asarray(px, np.float64), np.asarray(py, np.float64), rng.r2(every))
+        jitter = rng.r2(every)
+        if lens is None:
+            origin, direction = f64_ref.camera_rays(cfg, np.asarray(px, np.float64), np.asarray(py, np.float64), jitter)
+        else:
+            import lens_ref
+            keys = ((np.asarray(n, np.uint64) + np.asarray(offset, np.uint64)) & np.uint64(0xFFFFFFFF)) * np.ones(N, np.uint64)
+            xy = np.asarray(px, np.uint64) | (np.asarray(py, np.uint64) << np.uint64(16))
+            origin, direction = lens_ref.rays_f64(cfg, lens, xy, keys)[:2]
         throughput, radiance, margin, alive, min_cosine = np.ones((N, 3)), np.zeros((N, 3)), np.full(N, INF), every.copy(), np.full(N, INF)
         sky_y = np.zeros(N)
         last_bsdf = dict(pdf=np.zeros(N), lobe=np.zeros(N, np.int64), spectrum=np.zeros((N, 3)), direction=np.zeros((N, 3)))
@@ -253,14 +263,14 @@ def trace(cfg, world, models, px, py, n, offset, skybox=None):
     return radiance, margin, min_cosine, sky_y
 
 
-def trace_image(cfg, world, models, seeds, first_sample, n_samples, skybox=None):
+def trace_image(cfg, world, models, seeds, first_sample, n_samples, skybox=None, lens=None):
     """f64_ref.trace_image with the records -> (radiance (n_samples, H, W, 3), margin, min_cosine, sky_y (n_samples, H, W) each)"""
     W, H = cfg.width, cfg.height
     sc = f64_ref.Scene(world, skybox)
     py, px = np.divmod(np.arange(W * H), W)
     out = [], [], [], []
     for k in range(first_sample, first_sample + n_samples):
-        r, m, c, y = trace(cfg, sc, models, px, py, seeds["n"].astype(np.uint64) + np.uint64(k), seeds["offset"])
+        r, m, c, y = trace(cfg, sc, models, px, py, seeds["n"].astype(np.uint64) + np.uint64(k), seeds["offset"], lens=lens)
         for o, a in zip(out, (r.reshape(H, W, 3), m.reshape(H, W), c.reshape(H, W), y.reshape(H, W))):
             o.append(a)
     return tuple(np.stack(o) for o in out)

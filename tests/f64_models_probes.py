@@ -16,12 +16,16 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import f64_models                    # noqa: E402
+import lens_ref                      # noqa: E402
 import model_scenes                  # noqa: E402
 import scenes                        # noqa: E402
 from f64_probes import COS_MIN, DELTA, FLAGGED_CAP, FLOOR_MEAN, POLE_MIN      # noqa: E402,F401
 
 SIZE = (32, 24)
 CASES = [(name, nee) for name in ("room", "open", "textured") for nee in (0, 1)]
+# the same probes under the lens "both" of tests/lens_ref.py (a field of view and an aperture), with the dimension overrides an aperture needs
+# (model_scenes.APERTURE_OVERRIDES): held under MODELS_TOL and FLAGGED_CAP as they are, no tolerance of their own
+LENS_CASES = [(name, nee, "both") for name in ("room", "open") for nee in (0, 1)]
 # |restatement - f64| / max(|f64|, floor) per sample and channel, the largest over the unflagged samples of all cases as the command above prints it, and
 # the tolerance: eight times that
 # Measured: textured 1.714e-3 (nee 0 and MIS alike: one sample, a texture lookup's float32 uv under a glossy bounce, as TEXTURED_REL_MAX of
@@ -38,20 +42,24 @@ FUNCTION_TOL = 8 * FUNCTION_REL_MAX
 
 
 @functools.lru_cache(maxsize=None)
-def case(name, nee):
+def case(name, nee, lens_name=None):
     """-> dict(cfg, restated (spp, H, W, 3) f32 per-sample radiances, f64 (spp, H, W, 3), margin, flagged (spp, H, W))"""
     rpt = importlib.import_module("rust-path-tracer_amd")
     from oracle_ffi import Oracle
     W, H = SIZE
     world, rec, skybox, _ = model_scenes.scene(name)
-    cfg = model_scenes.config(name, nee, W, H)
+    cfg = model_scenes.config(name, nee, W, H, **model_scenes.lens_overrides(nee, lens_name))
     seeds = rpt.blue_noise_seeds(W, H)
     sc = Oracle("rpt_math").scene(world, skybox_f32=skybox)
     restated, rng = [], seeds
     for _ in range(scenes.PROBE_SPP):                       # one sample per call: the accumulator of a call IS that sample's radiance
-        acc, rng, _ = model_scenes.models_trace_cpu(cfg, sc, rec, rng, 1)
+        if lens_name is None:
+            acc, rng, _ = model_scenes.models_trace_cpu(cfg, sc, rec, rng, 1)
+        else:
+            acc, rng, _ = model_scenes.models_lens_trace_cpu(cfg, sc, rec, lens_ref.lens(lens_name), rng, 1)
         restated.append(acc[..., :3].copy())
-    radiance, margin, min_cosine, sky_y = f64_models.trace_image(cfg, world, rec, seeds, 0, scenes.PROBE_SPP, skybox=skybox)
+    radiance, margin, min_cosine, sky_y = f64_models.trace_image(cfg, world, rec, seeds, 0, scenes.PROBE_SPP, skybox=skybox,
+                                                                 lens=None if lens_name is None else lens_ref.LENSES[lens_name])
     return dict(cfg=cfg, restated=np.stack(restated), f64=radiance, margin=margin, min_cosine=min_cosine, sky_y=sky_y,
                 flagged=(margin < DELTA) | (min_cosine < COS_MIN) | (1.0 - sky_y * sky_y < POLE_MIN))
 
@@ -65,12 +73,13 @@ if __name__ == "__main__":
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     worst = (-1.0, None)
-    for name, nee in CASES:
-        c = case(name, nee)
+    for name, nee, lens_name in [c + (None,) for c in CASES] + LENS_CASES:
+        c = case(name, nee, lens_name)
         d = sample_differences(c)
         keep = ~c["flagged"]
         m = float(np.nanmax(np.where(keep[..., None], d, 0.0)))
-        worst = max(worst, (m, (name, nee)))
-        print(f"{name:10s} nee {nee}   flagged {c['flagged'].mean():8.5f} (by decision {(c['margin'] < DELTA).mean():.5f})   max rel (unflagged) {m:.3e}   "
+        if lens_name is None:
+            worst = max(worst, (m, (name, nee)))
+        print(f"{name:10s} nee {nee} lens {lens_name}   flagged {c['flagged'].mean():8.5f} (by decision {(c['margin'] < DELTA).mean():.5f})   max rel (unflagged) {m:.3e}   "
               f"max rel (all) {float(np.nanmax(d)):.3e}   samples above 1e-2: {int((np.where(keep[..., None], d, 0.0).max(-1) > 1e-2).sum())}")
     print(f"MODELS_REL_MAX = {worst[0]:.3e}   {worst[1]}")

@@ -3,7 +3,7 @@ csrc/k_guides_glass.h): one step of a pixel's chain, and the driver that runs wh
 
 Not a test module (no test_ prefix): tests/test_guides_glass.py holds the host build of the step (hip.glass_step_host) against `step`, and
 tests/test_gpu_guides_glass.py the device against the chain.  The walk is the oracle's nearest hit (oracle.trace_rays(scene, 0, ...)), the atlas lookups the
-oracle's sampler (oracle.sample_image), the camera rays denoise_ref.camera_rays; everything else is plain IEEE f32 arithmetic, which numpy performs
+oracle's sampler (oracle.sample_image), the camera rays denoise_ref.camera_rays unless the caller hands in others; everything else is plain IEEE f32 arithmetic, which numpy performs
 operation by operation without fusing.  `run_chains` takes the step as a function, so the same rounds drive the restatement and the host build.
 """
 import numpy as np
@@ -171,11 +171,12 @@ def oracle_walk(oracle, scene):
     return walk
 
 
-def guides(world, models, K, cfg, oracle, scene=None, step_fn=None):
+def guides(world, models, K, cfg, oracle, scene=None, step_fn=None, rays=None):
     """(the guides of rpt_set_guides_through_glass(K) in the layout of Renderer.guides(), the counts of rpt_guides_info_get); step_fn: another build of the
-    step with `step`'s signature after (world, models, K, oracle)"""
+    step with `step`'s signature after (world, models, K, oracle); rays: the primary rays (origins, dirs) by row-major pixel when they are not the reference
+    camera's — under a camera lens the rays through the lens centre, tests/lens_ref.py centre_rays"""
     scene = scene if scene is not None else oracle.scene(world)
-    ro, rd = camera_rays(cfg, oracle)
+    ro, rd = rays if rays is not None else camera_rays(cfg, oracle)
     fn = step_fn or (lambda *a: step(world, models, K, oracle, *a))
     planes, info = run_chains(fn, oracle_walk(oracle, scene), ro, rd, K)
     return image(planes, cfg.width, cfg.height), info

@@ -15,6 +15,16 @@ MATERIAL_MODEL_DTYPE = np.dtype([("model", np.uint32), ("ior", np.float32), ("re
 
 # the largest paths the reference's 31 dimensions allow (rpt_set_config): without NEE 2 + 8 * 3 + 5 roulette draws, with it 2 + 4 * 7 + 1
 CONFIGS = {0: dict(nee=0, max_bounces=8, min_bounces=2), 1: dict(nee=1, max_bounces=4, min_bounces=2), 2: dict(nee=2, max_bounces=4, min_bounces=2)}
+# A lens with an aperture takes table entry 31 for its own sample (rpt_set_camera_lens refuses a 31-dimension configuration with RPT_ECONFIG), so under one:
+# without NEE roulette starts a bounce later, 2 + 8 * 3 + 4 = 30, which keeps eight bounces for the glass; with NEE three bounces and roulette from the third
+# on, 2 + 3 * 7 + 1 = 24, which keeps the roulette alive.  A lens without an aperture ("fov", "narrow") leaves the 31 dimensions to the path.
+APERTURE_OVERRIDES = {0: dict(min_bounces=3), 1: dict(max_bounces=3, min_bounces=1), 2: dict(max_bounces=3, min_bounces=1)}
+
+
+def lens_overrides(nee, lens_name):
+    """the configuration overrides CONFIGS[nee] needs under the lens of that name (tests/lens_ref.py LENSES; None: no lens)"""
+    import lens_ref
+    return dict(APERTURE_OVERRIDES[nee]) if lens_name is not None and lens_ref.LENSES[lens_name][1] != 0.0 else {}
 
 
 def records(models, iors=None):
@@ -66,8 +76,8 @@ class _Mesh:
         self.n += [[0.0, -1.0, 0.0]] * 4
         self.t += [[k, k + 2, k + 1, material], [k, k + 3, k + 2, material]]
 
-    def sphere(self, center, radius, material):
-        p, n, f = icosphere(center, radius)
+    def sphere(self, center, radius, material, subdivisions=2):
+        p, n, f = icosphere(center, radius, subdivisions)
         k = len(self.v)
         self.v += p.tolist()
         self.n += n.tolist()
@@ -88,7 +98,7 @@ class _Mesh:
 _BLACK = (0.0, 0.0, 0.0)
 
 
-def room():
+def room(subdivisions=2):
     """A closed box with a ceiling lamp: PBR walls (a rough grey one, a metallic one), one wall Lambertian, a glass icosphere of 320 triangles with smooth
     normals (ior 1.5, material roughness 0.05) and a tinted thin pane of two parallel quads."""
     g = _Mesh()
@@ -97,13 +107,20 @@ def room():
                         ((0, 3, 7, 4), (1, 0, 0), 1), ((1, 5, 6, 2), (-1, 0, 0), 2)):
         g.quad([c[i] for i in q], nrm, mat)
     g.lamp(-1.0, 1.0, 3.9, 1.0, 3.0, 5)
-    g.sphere((0.7, 1.1, 2.4), 0.9, 3)
+    g.sphere((0.7, 1.1, 2.4), 0.9, 3, subdivisions)
     g.quad([(-2.4, 0.3, 2.0), (-0.9, 0.3, 2.6), (-0.9, 2.6, 2.6), (-2.4, 2.6, 2.0)], (0.371391, 0.0, -0.928477), 4)          # the pane's front ...
     g.quad([(-2.4186, 0.3, 2.0464), (-0.9186, 0.3, 2.6464), (-0.9186, 2.6, 2.6464), (-2.4186, 2.6, 2.0464)], (-0.371391, 0.0, 0.928477), 4)   # ... and back, 0.05 behind
     w = g.world([(1.0, 0.0, (0.75, 0.75, 0.75), _BLACK), (0.8, 0.0, (0.8, 0.25, 0.2), _BLACK), (0.25, 0.9, (0.3, 0.5, 0.85), _BLACK),
                  (0.05, 0.0, (0.97, 0.98, 1.0), _BLACK), (0.02, 0.0, (0.55, 0.9, 0.65), _BLACK), (1.0, 0.0, _BLACK, (18.0, 17.0, 15.0))])
     rec = records([MODEL_PBR, MODEL_LAMBERTIAN, MODEL_PBR, MODEL_GLASS, MODEL_GLASS, MODEL_PBR], [0.0, 0.0, 0.0, 1.5, 1.45, 0.0])
     return w, rec, None, dict(cam_position=(0.0, 1.6, -0.8, 0.0), cam_rotation=(0.12, 0.0, 0.0, 0.0))
+
+
+def small_room():
+    """The room with an icosphere of 80 triangles: 98 triangles in all, which the device keeps in LDS (rpt_scene.hip: nodes * 50 + triangles * 48 <= 32 KB) —
+    the room, the open scene and the furnace, with their 320-triangle spheres, are walked from global memory.  So this is the scene where the models meet
+    the LDS walks: the FIRST walk over prepared slots, the LAST walk that ends the paths itself (two emissive triangles)."""
+    return room(1)
 
 
 def open_scene():
@@ -137,7 +154,7 @@ def furnace():
     return w, records([MODEL_GLASS]), sky, dict(cam_position=(0.0, 0.0, 0.0, 0.0), cam_rotation=(0.0, 0.0, 0.0, 0.0))
 
 
-SCENES = {"room": room, "open": open_scene, "textured": textured, "furnace": furnace}
+SCENES = {"room": room, "small_room": small_room, "open": open_scene, "textured": textured, "furnace": furnace}
 _built = {}
 
 
@@ -191,21 +208,74 @@ def models_trace_cpu(config, oracle_scene, models, rng, n_samples, rect=None, th
     return accum, rng, st
 
 
+def models_lens_trace_cpu(config, oracle_scene, models, lens_record, rng, n_samples, rect=None, threads=0):
+    """models_trace_cpu with the camera of rpt_set_camera_lens: lens_record a CameraLens (tests/lens_ref.py lens), or None for the reference's camera"""
+    W, H = config.width, config.height
+    rng = np.ascontiguousarray(rng).copy()
+    accum = np.zeros((H, W, 4), np.float32)
+    models = None if models is None else np.ascontiguousarray(models, MATERIAL_MODEL_DTYPE)
+    r = np.array(rect if rect else (0, 0, W, H), np.uint32)
+    st = ModelsStats()
+    rc = models_lib().models_lens_trace_cpu(C.byref(config), C.byref(oracle_scene), _p(models), None if lens_record is None else C.byref(lens_record), _p(rng),
+                                            _p(accum), C.c_uint32(n_samples), _p(r), C.c_int(threads), C.byref(st))
+    assert rc == 0 and st.error_flags == 0, (rc, st.error_flags)
+    return accum, rng, st
+
+
+def models_lens_trace_pixel(config, oracle_scene, models, lens_record, x, y, n, offset):
+    """one pixel-sample of the restatement -> (its radiance (3,) float32, the error flags)"""
+    class Rng(C.Structure):
+        _fields_ = [("n", C.c_uint32), ("offset", C.c_uint32)]
+    models = None if models is None else np.ascontiguousarray(models, MATERIAL_MODEL_DTYPE)
+    out = np.zeros(3, np.float32)
+    fn = models_lib().models_lens_trace_pixel
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, Rng, C.c_void_p]
+    flags = fn(C.addressof(config), C.addressof(oracle_scene), None if models is None else models.ctypes.data,
+               None if lens_record is None else C.addressof(lens_record), x, y, Rng(int(n), int(offset)), out.ctypes.data)
+    return out, flags
+
+
 _references = {}
 
 
-def reference(oracle, name, nee, width, height, spp, **more):
-    """the restatement's accumulator, rng and counters of a scene under CONFIGS[nee], computed once per process and shared"""
-    key = (name, nee, width, height, spp, tuple(sorted(more.items())))
+def reference(oracle, name, nee, width, height, spp, lens=None, records=True, **more):
+    """the restatement's accumulator, rng and counters of a scene under CONFIGS[nee] (and `more`), computed once per process and shared; lens: a name of
+    tests/lens_ref.py LENSES, or None for the reference's camera; records False: every material PBR"""
+    key = (name, nee, width, height, spp, lens, records, tuple(sorted(more.items())))
     if key not in _references:
+        import lens_ref
         rpt = importlib.import_module("rust-path-tracer_amd")
         w, rec, skybox, _ = scene(name)
         cfg = config(name, nee, width, height, **more)
-        acc, rng, st = models_trace_cpu(cfg, oracle.scene(w, skybox_f32=skybox), rec, rpt.blue_noise_seeds(width, height), spp)
+        sc, seeds = oracle.scene(w, skybox_f32=skybox), rpt.blue_noise_seeds(width, height)
+        if lens is None and records:
+            acc, rng, st = models_trace_cpu(cfg, sc, rec, seeds, spp)
+        else:
+            acc, rng, st = models_lens_trace_cpu(cfg, sc, rec if records else None, lens_ref.lens(lens), seeds, spp)
         acc.setflags(write=False)
         rng.setflags(write=False)
         _references[key] = (acc, rng, st)
     return _references[key]
+
+
+_samples = {}
+
+
+def per_sample_radiances(oracle, name, nee, width, height, spp, lens=None, **more):
+    """every sample's radiance, (spp, H, W, 3): one-sample calls of the restatement chained through the returned rng (tests/moments_ref.py SampleBank)"""
+    key = (name, nee, width, height, spp, lens, tuple(sorted(more.items())))
+    if key not in _samples:
+        import lens_ref
+        rpt = importlib.import_module("rust-path-tracer_amd")
+        w, rec, skybox, _ = scene(name)
+        cfg, sc, rng = config(name, nee, width, height, **more), oracle.scene(w, skybox_f32=skybox), rpt.blue_noise_seeds(width, height)
+        out = []
+        for _ in range(spp):
+            acc, rng, _st = models_lens_trace_cpu(cfg, sc, rec, lens_ref.lens(lens), rng, 1)
+            out.append(acc[..., :3].copy())
+        _samples[key] = np.stack(out)
+        _samples[key].setflags(write=False)
+    return _samples[key]
 
 
 # ---- the furnace statement (needs no reference) ------------------------------------------------------------------------------------------------------
@@ -222,7 +292,8 @@ def furnace_check(acc, s, primary_miss, spp):
     for j in range(spp + 1):
         k[np.all(acc[..., :3].view(np.uint32) == sums[j].view(np.uint32), axis=-1)] = j
     assert np.all(k >= 0), f"{int((k < 0).sum())} pixels are no sum of copies of the sky's value"
-    assert np.all(k[primary_miss] == spp)
+    if primary_miss is not None:                            # (None under a lens: the mask below is the reference camera's)
+        assert np.all(k[primary_miss] == spp)
     assert np.all(acc[..., 3] == spp)
     return k
 

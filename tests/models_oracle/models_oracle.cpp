@@ -12,9 +12,13 @@
  * walk, the sky, the sampler, the rng, get_pbr_bsdf and PBR, and oracle_bsdf, whose kinds 0-2 ARE Lambertian::sample, Glass::sample and
  * Lambertian::{evaluate, pdf} (the arithmetic tests/test_bsdf_extra.py pins the device functions to) — and restates only the frame around them.
  * With every record PBR it must give oracle_trace_cpu's words and counters (tests/test_material_models.py).
+ * The camera is a second switch, at lib.rs:38-51: with a lens record (rpt_set_camera_lens) the path starts with lens_camera_ray of
+ * tests/lens_oracle/lens_camera.h, the text tests/lens_oracle starts its own with — models_lens_trace_cpu, models_lens_trace_pixel.  Held from both sides
+ * (tests/test_models_lens.py): under the default record {1, 0, 1, 0} they are models_trace_cpu, with every record PBR they are lens_trace_cpu.
  * Built as libmodels_oracle.so with -Wl,-Bsymbolic: its copy of the oracle's exported names binds to itself.
  */
 #include "../../oracle/rpt_oracle.cpp"
+#include "../lens_oracle/lens_camera.h"
 
 namespace {
 
@@ -125,22 +129,27 @@ DirectLightSample sample_direct_lighting_models(uint32_t nee_mode, const Scene &
     return info;
 }
 
-/* lib.rs:21-186 */
+/* lib.rs:21-186; lens: the camera of rpt_set_camera_lens at lib.rs:38-51, or NULL for the reference's own lines */
 PixelResult trace_pixel_models(uint32_t id_x, uint32_t id_y, const rpt_tracing_config &config, rpt_rng_state rng, const Scene &sc, const ModelRecord *models,
-                               ModelCounters &cnt) {
+                               const LensRecord *lens, ModelCounters &cnt) {
     uint32_t nee_mode = config.nee <= 2 ? config.nee : 0;
     bool nee = nee_mode != RPT_NEE_NONE;
     RngState rng_state{rng.n, rng.offset, 0, false};
 
-    V2 jitter = rng_state.gen_r2();
-    V2 suv = V2{(float)id_x, (float)id_y} + jitter;
-    V2 uv = V2{suv.x / (float)config.width, 1.0f - suv.y / (float)config.height} * 2.0f - V2{1.0f, 1.0f};
-    uv.y *= (float)config.height / (float)config.width;
+    V3 ray_origin, ray_direction;
+    if (lens) {
+        lens_camera_ray(id_x, id_y, config, *lens, rng_state, ray_origin, ray_direction);
+    } else {
+        V2 jitter = rng_state.gen_r2();
+        V2 suv = V2{(float)id_x, (float)id_y} + jitter;
+        V2 uv = V2{suv.x / (float)config.width, 1.0f - suv.y / (float)config.height} * 2.0f - V2{1.0f, 1.0f};
+        uv.y *= (float)config.height / (float)config.width;
 
-    V3 ray_origin = xyz(config.cam_position);
-    V3 ray_direction = normalize(v3(uv.x, uv.y, 1.0f));
-    M3 euler_mat = mul(rotation_y(config.cam_rotation[1]), rotation_x(config.cam_rotation[0]));
-    ray_direction = mul(euler_mat, ray_direction);
+        ray_origin = xyz(config.cam_position);
+        ray_direction = normalize(v3(uv.x, uv.y, 1.0f));
+        M3 euler_mat = mul(rotation_y(config.cam_rotation[1]), rotation_x(config.cam_rotation[0]));
+        ray_direction = mul(euler_mat, ray_direction);
+    }
 
     V3 throughput = splat3(1.0f);
     V3 radiance = splat3(0.0f);
@@ -227,7 +236,7 @@ PixelResult trace_pixel_models(uint32_t id_x, uint32_t id_y, const rpt_tracing_c
             throughput = throughput * (1.0f / prob);
         }
     }
-    if (rng_state.overflow) cnt.walk.error_flags |= 2u;
+    if (rng_state.overflow || (lens && lens_shares_a_dimension(*lens, rng_state))) cnt.walk.error_flags |= 2u;
     PixelResult out;
     out.radiance = V4{radiance.x, radiance.y, radiance.z, 1.0f};
     out.next_n = rng.n + 1;
@@ -246,9 +255,9 @@ typedef struct models_stats {
 } models_stats;
 
 /* oracle_trace_cpu's loop (src/trace.rs:273-308) over trace_pixel_models: n_samples passes over the rectangle rect = (x0, y0, x1, y1), rows in parallel;
- * models: one record per material, or NULL for "every material is PBR" */
-int models_trace_cpu(const rpt_tracing_config *config, const oracle_scene *scene, const ModelRecord *models, rpt_rng_state *rng, float *accum,
-                     uint32_t n_samples, const uint32_t *rect, int n_threads, models_stats *stats) {
+ * models: one record per material, or NULL for "every material is PBR"; lens: a record, or NULL for the reference's camera */
+int models_lens_trace_cpu(const rpt_tracing_config *config, const oracle_scene *scene, const ModelRecord *models, const LensRecord *lens, rpt_rng_state *rng,
+                          float *accum, uint32_t n_samples, const uint32_t *rect, int n_threads, models_stats *stats) {
     if (!config || !scene || !rng || !accum || !rect) return -1;
     Scene sc = make_scene(scene);
     const uint32_t W = config->width, H = config->height;
@@ -265,7 +274,7 @@ int models_trace_cpu(const rpt_tracing_config *config, const oracle_scene *scene
                 if (y >= y1) break;
                 for (uint32_t x = x0; x < x1; ++x) {
                     size_t i = (size_t)y * W + x;
-                    PixelResult r = trace_pixel_models(x, y, *config, rng[i], sc, models, cnt);
+                    PixelResult r = trace_pixel_models(x, y, *config, rng[i], sc, models, lens, cnt);
                     accum[4 * i + 0] += r.radiance.x;
                     accum[4 * i + 1] += r.radiance.y;
                     accum[4 * i + 2] += r.radiance.z;
@@ -299,14 +308,24 @@ int models_trace_cpu(const rpt_tracing_config *config, const oracle_scene *scene
     return 0;
 }
 
+int models_trace_cpu(const rpt_tracing_config *config, const oracle_scene *scene, const ModelRecord *models, rpt_rng_state *rng, float *accum,
+                     uint32_t n_samples, const uint32_t *rect, int n_threads, models_stats *stats) {
+    return models_lens_trace_cpu(config, scene, models, nullptr, rng, accum, n_samples, rect, n_threads, stats);
+}
+
 /* one pixel-sample: its radiance (the sample-by-sample comparisons) */
-int models_trace_pixel(const rpt_tracing_config *config, const oracle_scene *scene, const ModelRecord *models, uint32_t x, uint32_t y, rpt_rng_state rng,
-                       float *out_rgb) {
+int models_lens_trace_pixel(const rpt_tracing_config *config, const oracle_scene *scene, const ModelRecord *models, const LensRecord *lens, uint32_t x, uint32_t y,
+                            rpt_rng_state rng, float *out_rgb) {
     Scene sc = make_scene(scene);
     ModelCounters cnt;
-    PixelResult r = trace_pixel_models(x, y, *config, rng, sc, models, cnt);
+    PixelResult r = trace_pixel_models(x, y, *config, rng, sc, models, lens, cnt);
     out_rgb[0] = r.radiance.x; out_rgb[1] = r.radiance.y; out_rgb[2] = r.radiance.z;
     return (int)cnt.walk.error_flags;
+}
+
+int models_trace_pixel(const rpt_tracing_config *config, const oracle_scene *scene, const ModelRecord *models, uint32_t x, uint32_t y, rpt_rng_state rng,
+                       float *out_rgb) {
+    return models_lens_trace_pixel(config, scene, models, nullptr, x, y, rng, out_rgb);
 }
 
 }  // extern "C"

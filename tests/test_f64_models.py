@@ -78,14 +78,24 @@ def test_the_functions_agree_with_the_oracles(capsys):
         assert worst <= probes.FUNCTION_TOL, (name, worst)
 
 
-@pytest.mark.parametrize("name,nee", probes.CASES)
-def test_the_restatement_agrees_sample_by_sample(name, nee):
-    c = probes.case(name, nee)
+def _agrees_sample_by_sample(name, nee, lens_name=None):
+    c = probes.case(name, nee, lens_name)
     share = float(c["flagged"].mean())
     d = probes.sample_differences(c)
     worst = float(np.nanmax(np.where(~c["flagged"][..., None], d, 0.0)))
-    print(f"{name} nee {nee}: flagged {share:.5f}, max rel over the unflagged samples {worst:.3e}")
+    print(f"{name} nee {nee} lens {lens_name}: flagged {share:.5f}, max rel over the unflagged samples {worst:.3e}")
     assert share <= FLAGGED_CAP                               # a condition: the views were chosen so that the float64 reference alone stays under it
     assert np.isfinite(c["f64"][~c["flagged"]]).all()
     assert worst <= probes.MODELS_TOL
     assert (np.abs(c["f64"]).max(-1) > 0).any()               # (the closed room without NEE: few samples find the lamp, most compare zeros)
+
+
+@pytest.mark.parametrize("name,nee", probes.CASES)
+def test_the_restatement_agrees_sample_by_sample(name, nee):
+    _agrees_sample_by_sample(name, nee)
+
+
+@pytest.mark.parametrize("name,nee,lens_name", probes.LENS_CASES)
+def test_the_restatement_with_both_switches_agrees_sample_by_sample(name, nee, lens_name):
+    """the restatement with the model AND the lens (models_lens_trace_cpu) against f64_models.trace under the same lens: the same tolerance, the same cap"""
+    _agrees_sample_by_sample(name, nee, lens_name)

@@ -2,7 +2,7 @@
 the device's rays against the host build of csrc/k_lens.h, accumulators, rng and counters word for word against the restatement tests/lens_oracle — from LDS
 (aperture 0: the FIRST walk over prepared slots; an aperture: the plain walk) and from global memory, every NEE mode, every route into the pipeline — the
 default record against a context that never set one, the guides and the filters under a lens, and every refusal.  80 x 72 (a whole tile, a 16-pixel and an
-8-pixel remainder), 8 spp unless stated.  Material models under a lens are NOT compared here: the restatement is PBR only."""
+8-pixel remainder), 8 spp unless stated.  Material models under a lens: tests/test_gpu_models_lens.py."""
 import ctypes as C
 import os
 
@@ -90,10 +90,14 @@ def test_device_rays_are_the_host_hook_bit_for_bit(renderer, hipmod, rpt, world,
 @pytest.mark.parametrize("lens_name", IMAGE_LENSES)
 @pytest.mark.parametrize("nee", [0, 1, 2])
 @pytest.mark.parametrize("which,env", [("DarkCornell", {}), ("DarkCornell", {"RPT_NO_LDS_SCENE": "1"}), ("textured", {})])
-def test_words_and_counters_are_the_restatements(hipmod, rpt, oracle, world, which, env, nee, lens_name):
+def test_words_and_counters_are_the_restatements(hipmod, rpt, oracle, world, which, env, nee, lens_name, monkeypatch):
     """DarkCornell lives in LDS — aperture 0 takes the FIRST walk, an aperture the plain one —, with RPT_NO_LDS_SCENE=1 it is walked from global memory"""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)                         # rpt_upload_scene reads RPT_NO_LDS_SCENE AGAIN: in the environment until the scene is up
     with context(hipmod, env) as r:
         prepare(r, rpt, world, which, nee, lens_name)
+        if which == "DarkCornell":
+            assert (r.last_bounce_order()["mode"] == 0) == bool(env)      # (the LAST walk needs the LDS image: off where the scene is walked from global memory)
         r.render(SPP)                                    # a batch of known length: no slot takes a second sample
         check_against(r, reference(oracle, world, which, nee, lens_name))
         assert r.stats()["kernel_launches"]["generate"] == 1

@@ -216,6 +216,66 @@ def test_segment_images_hold_the_parity_contract(monkeypatch, sim, hipmod, oracl
     assert worst < L2_BOUND, worst
 
 
+# ---- image level, with the other opt-in settings: material models (rpt_set_material_models) and a camera lens (rpt_set_camera_lens)
+
+# (scene, records, lens, nee): Lambertian and PBR next-event estimation through the `_seg` kernels — Glass queues no shadow ray —, from global memory (room,
+# open: 320-triangle spheres) and from LDS (small_room, DarkCornell); shadow rays of paths that a lens started; both at once
+COMBINED = [(scene, True, None, nee) for scene in ("room", "small_room", "open") for nee in (1, 2)]
+COMBINED += [("DarkCornell", False, "both", nee) for nee in (1, 2)]
+COMBINED += [(scene, True, "both", nee) for scene in ("room", "small_room") for nee in (1, 2)]
+
+
+@pytest.mark.parametrize("scene,records,lens_name,nee", COMBINED, ids=lambda v: str(v))
+def test_segment_with_material_models_and_a_lens(hipmod, oracle, rpt, world, scene, records, lens_name, nee):
+    """The same contract as above at 80 x 72 x 8 spp, against the restatement that carries the switch (tests/models_oracle with both, tests/lens_oracle for
+    DarkCornell) over the WHOLE image: ray counts equal to the exact run's — and the restatement's —, per-pixel relative L2 of the SEGMENT image < L2_BOUND;
+    and the same context, switched back to EXACT and reset, gives the restatement bit for bit.  Printed: the accumulator words that differ between the modes."""
+    import lens_ref
+    import model_scenes
+    W, H, spp = 80, 72, 8
+    seeds = rpt.blue_noise_seeds(W, H)
+    if scene == "DarkCornell":
+        w, rec, skybox = world(scene), None, None
+        cfg = lens_ref.config(world, scene, nee, W, H)
+        ref, ref_rng, st = lens_ref.reference(oracle, world, scene, nee, lens_name, W, H, spp)
+    else:
+        w, rec, skybox, _ = model_scenes.scene(scene)
+        more = model_scenes.lens_overrides(nee, lens_name)
+        cfg = model_scenes.config(scene, nee, W, H, **more)
+        ref, ref_rng, st = model_scenes.reference(oracle, scene, nee, W, H, spp, lens=lens_name, **more)
+    r = hipmod.Renderer(0)
+    try:
+        r.upload_scene(w, skybox_f32=skybox)
+        if records:
+            r.set_material_models(rec)
+        r.set_config(cfg)
+        r.set_camera_lens(lens_ref.lens(lens_name))
+        images, stats = {}, {}
+        for mode in (hipmod.SHADOW_SEGMENT, hipmod.SHADOW_EXACT):          # EXACT last: what SEGMENT leaves behind
+            r.set_shadow_mode(mode)
+            assert r.shadow_mode() == mode
+            r.reset(seeds)
+            r.render(spp)
+            images[mode], n = r.read_accum()
+            images[mode] = images[mode].copy()
+            stats[mode] = r.stats()
+            assert n == spp
+        rng_after = r.read_rng().copy()
+    finally:
+        r.close()
+    ex, sg = images[hipmod.SHADOW_EXACT], images[hipmod.SHADOW_SEGMENT]
+    se, ss = stats[hipmod.SHADOW_EXACT], stats[hipmod.SHADOW_SEGMENT]
+    differ = int((ex.view(np.uint32) != sg.view(np.uint32)).sum())
+    worst = worst_pixel_rel_l2(sg, ref)
+    print(f"{scene} records={records} lens={lens_name} nee={nee} | {differ} of {ex.size} | {worst:.3e} | {ss['shadow_rays']} ({ss['shadow_rays_elided']})")
+    assert np.array_equal(ex.view(np.uint32), ref.view(np.uint32))         # back in EXACT: the restatement's image, rng and counters word for word
+    assert np.array_equal(rng_after.reshape(-1), np.asarray(ref_rng).reshape(-1))
+    assert (se["extension_rays"], se["shadow_rays"], se["sky_evals"], se["shadow_rays_elided"]) == (st.extension_rays, st.shadow_rays, st.sky_evals, st.shadow_rays_zero_term)
+    assert (scene == "open") == (st.shadow_rays == 0)                      # (the open scene has no emitter: no light is ever sampled)
+    assert (ss["shadow_rays"], ss["shadow_rays_elided"], ss["extension_rays"]) == (se["shadow_rays"], se["shadow_rays_elided"], se["extension_rays"])
+    assert worst < L2_BOUND, worst
+
+
 # ---- plumbing
 
 def test_default_switching_and_invalid_modes(hipmod, oracle, rpt, world):

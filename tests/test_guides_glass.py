@@ -239,6 +239,54 @@ def test_a_pixel_through_the_rooms_pane_carries_the_wall_behind_it(hipmod, oracl
     assert info["pixels_through_glass"] >= pane.sum()
 
 
+@pytest.mark.parametrize("name", ["room", "open", "textured"])
+def test_the_chain_over_lens_centre_rays_at_tan_half_1_is_the_chain(hipmod, oracle, name):
+    """guides_glass_ref.guides takes its primary rays as an argument: handed lens_ref.centre_rays at tan_half_fov 1 — the restatement of
+    k_dn_camera_rays_lens under the reference's field of view — it is the existing chain, byte for byte, counts included"""
+    import lens_ref
+    world, rec, skybox, _ = model_scenes.scene(name)
+    cfg = model_scenes.config(name, 0, W, H)
+    _, (want, want_info) = chains(hipmod, oracle, name, 4)
+    got, info = ref.guides(world, rec, 4, cfg, oracle, oracle.scene(world, skybox_f32=skybox), rays=lens_ref.centre_rays(cfg, 1.0, oracle))
+    for k in PLANES + ("interfaces",):
+        assert same_bits(got[k], want[k]), k
+    assert info == want_info
+
+
+def test_a_pixel_through_the_rooms_pane_under_a_field_of_view(hipmod, oracle):
+    """the pane's semantics under the lens "fov" (tan_half_fov 0.6): the chain starts from the rays through the LENS CENTRE, so a pixel that looks through
+    the pane carries the normal of the wall behind it and a position on ITS lens-centre primary ray — not on the reference camera's ray of that pixel"""
+    import lens_ref
+    tan_half = lens_ref.LENSES["fov"][0]
+    world, rec, _, _ = model_scenes.scene("room")
+    cfg = model_scenes.config("room", 0, W, H)
+    sc = oracle.scene(world)
+    ro, rd = lens_ref.centre_rays(cfg, tan_half, oracle)
+    pin_ro, pin_rd = denoise_ref.camera_rays(cfg, oracle)
+    assert same_bits(ro, pin_ro) and not same_bits(rd, pin_rd)
+    first_material = world.indices[oracle.trace_rays(sc, 0, ro, rd)[1]]["material"].reshape(H, W)
+    g, info = ref.guides(world, rec, 4, cfg, oracle, sc, rays=(ro, rd))
+    host, host_info = ref.guides(world, rec, 4, cfg, oracle, sc, step_fn=host_step(hipmod, world, rec, 4), rays=(ro, rd))
+    assert all(same_bits(g[k], host[k]) for k in PLANES) and info == host_info           # the host build of the step over the same rays
+    first, _ = ref.guides(world, rec, 0, cfg, oracle, sc, rays=(ro, rd))                 # K = 0: the first hit under the lens
+    pane = (first_material == 4) & (first["kind"] == 1)
+    assert pane.sum() > 100
+    tint, red = world.materials["albedo"][4, :3].astype(F), world.materials["albedo"][1, :3].astype(F)
+    on_red = pane & (g["interfaces"] == 2) & (g["kind"] == 1) & (np.abs(g["normal"] - np.array((1, 0, 0), F)).max(axis=-1) < 1e-6)
+    assert on_red.sum() > 50, "pixels through the pane that end on the wall x = -3"
+    assert np.all(np.abs(first["normal"][on_red][:, 0]) < 0.5)                              # (the first-hit normal there is the pane's)
+    expect = (tint * tint) * red
+    assert np.all(g["albedo"][on_red].view(np.uint32) == expect.view(np.uint32))
+    assert np.all(g["depth"][on_red] > first["depth"][on_red])
+    assert same_bits(g["position"], (ro + rd * g["depth"].reshape(-1, 1)).astype(F).reshape(H, W, 3))
+    assert not same_bits(g["position"], (pin_ro + pin_rd * g["depth"].reshape(-1, 1)).astype(F).reshape(H, W, 3))
+    # a narrower field of view magnifies: the pane covers more pixels than under the reference camera
+    (pin, _), _ = chains(hipmod, oracle, "room", 4)
+    pin_first = world.indices[oracle.trace_rays(sc, 0, pin_ro, pin_rd)[1]]["material"].reshape(H, W)
+    assert pane.sum() > (pin_first == 4).sum() and not same_bits(g["depth"], pin["depth"])
+    assert info["pixels_through_glass"] >= pane.sum()
+
+
 def test_the_recommended_budget_is_the_kept_grids_minimum(hipmod):
     import os
     import re
