@@ -254,7 +254,7 @@ __global__ __launch_bounds__(THREADS) void k_traverse_nearest_stream(DevScene sc
             continue;
         }
         if (LAST) lds_stream_walk_run<STACK, false, false, true>(view, w, ro, rd, ird, 0.0f, stack, pool_open ? RPT_STREAM_TRIPS : 0x7fffffff, img_lane, stop_first, order_bias);
-        else lds_stream_walk_run<STACK, false, false, false, FIRST>(view, w, ro, rd, ird, 0.0f, stack, pool_open ? RPT_STREAM_TRIPS : 0x7fffffff);
+        else lds_stream_walk_run<STACK, false, false, false, FIRST, false, FIRST ? 0 : RPT_STREAM_PLAIN_VOTE, !FIRST && RPT_STREAM_PLAIN_ONE_TRI>(view, w, ro, rd, ird, 0.0f, stack, pool_open ? RPT_STREAM_TRIPS : 0x7fffffff);
     }
     if (LAST) {
         bool park = false;

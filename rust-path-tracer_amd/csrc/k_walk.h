@@ -704,7 +704,7 @@ __device__ __forceinline__ void lds_walk_run(const SceneViewLds &view, LdsWalk &
  *   - the column's entry 0 holds LDS_DESC_DEAD for good (lds_stream_stack_begin): a pop of an empty stack loads it, there is no `top == bottom` test.  The walk
  *     has STACK - 1 entries; an LDS image has at most 15 levels under its root (rpt_scene.hip stage_nodes), which is what 16-entry columns leave;
  *   - descend / push by selects, the stack store under the only exec narrowing of the inner step;
- *   - the vote is two wave-uniform branches, and the loop has ONE exit, at its end: a scalar minimum, a compare and a branch on SCC (an exit at the head, or a
+ *   - the vote is two wave-uniform branches (one scalar shift ahead of them where a lane on a leaf counts double, VOTE), and the loop has ONE exit, at its end: a scalar minimum, a compare and a branch on SCC (an exit at the head, or a
  *     `break` inside, is carried as a lane mask through a latch block). */
 /* MIXED (the last extension rays of a batch without NEE, k_traverse_nearest_stream<.., LAST = true>): a nearest-hit walk in which SOME lanes only have to
  * answer "hit or miss" — `stop_first` lanes leave at their first accepted triangle, which is where the reference's walk makes result.hit true for good
@@ -736,7 +736,20 @@ __device__ __forceinline__ bool moller_trumbore_flat(F3 edge1, F3 edge2, F3 corn
     return !(rptm::absr(det) < 1e-6f) & !(lo < 0.0f) & !(hi > 1.0f);
 }
 
-template <int STACK, bool ANY_HIT, bool FIXED = false, bool MIXED = false, bool PRESUB = false, bool SEGMENT = false /* as in walk_run */>
+/* ONE_TRI and VOTE (the plain nearest-hit kernel).  A leaf trip in which every lane walks its whole leaf runs as long as its longest leaf: on
+ * DarkCornell one leaf visit in ten holds a second triangle, a leaf trip carries 20-28 lanes, so nearly every leaf trip ran a second triangle iteration for about
+ * three lanes of 64.  With ONE_TRI a leaf trip has no triangle loop: it tests ONE triangle, `cur & 511`, of every lane on a leaf; a lane whose leaf holds more keeps
+ * standing on the REST of it, the leaf (first + 1, count - 1) — the descriptor minus LDS_LEAF_REST — and takes its next triangle in the next leaf trip.  Per lane the
+ * triangles are tested in the same order against the same res.t; `cur` survives the end of a trip budget and a refill already, and nothing on the stack changes.
+ * The rest of a leaf stays a leaf descriptor: its count is never taken below 1 (no borrow into LDS_DESC_LEAF), and first + count <= 512 in every leaf of an image
+ * (rpt_scene.hip build_lds_image), so first + 1 stays inside its 9 bits.
+ * VOTE is the weight of a lane on a leaf in the vote, as a shift: the leaf trip runs iff (n_leaf << VOTE) > n_inner.  A lane with part of a leaf left idles through the
+ * inner trips until the next leaf trip, so one triangle per trip only pays with leaf trips at half the lanes (VOTE = 1; tools/leaf_trip_sim.py). */
+constexpr uint32_t LDS_LEAF_REST = (1u << 9) - 1u;                    /* leaf (first, count) - LDS_LEAF_REST = leaf (first + 1, count - 1) */
+constexpr uint32_t LDS_DESC_LEAF_MANY = LDS_DESC_LEAF | (2u << 9);    /* a leaf descriptor >= this one holds two triangles or more */
+static_assert(LDS_DESC_LEAF == (1u << 15) && LDS_DESC_LEAF_MANY - LDS_LEAF_REST == (LDS_DESC_LEAF | (1u << 9) | 1u), "descriptor = LEAF | count << 9 | first, count in 6 bits");
+
+template <int STACK, bool ANY_HIT, bool FIXED = false, bool MIXED = false, bool PRESUB = false, bool SEGMENT = false /* as in walk_run */, int VOTE = 0, bool ONE_TRI = false>
 __device__ __forceinline__ void lds_stream_walk_run(const SceneViewLds &view, LdsWalk &w, F3 ro, F3 rd, F3 ird, float max_t, uint16_t *stack /* entry 0: the sentinel */,
                                                     int budget, const float4 *img_lane = nullptr, uint32_t stop_first = 0u, float order_bias = 0.0f) {
     static_assert(!FIXED || ANY_HIT, "only the any-hit walk may choose its order");
@@ -760,29 +773,44 @@ __device__ __forceinline__ void lds_stream_walk_run(const SceneViewLds &view, Ld
     asm("" : "+s"(n_leaf), "+s"(n_inner));                             /* (scalar registers: see lds_walk_run) */
     uint32_t go;
     do {
-        if (n_leaf > n_inner) {
+        if ((n_leaf << VOTE) > n_inner) {
             if (SceneViewLds::is_leaf(cur)) {
-                bool accepted = false;
-                const uint32_t first = cur & 511u;
-                uint32_t ti = first;
-                const uint32_t end = first + ((cur >> 9) & 63u);       /* (a leaf holds at least one triangle: a count of 0 is an inner node) */
-                const float4 *rec = view.tri_base() + 3u * first;
-                do {
+                if constexpr (ONE_TRI) {
+                    const uint32_t ti = cur & 511u;
+                    const float4 *rec = view.tri_base() + 3u * ti;
                     float t, det;
                     const bool ok = moller_trumbore_flat(xyz4(rec[1]), xyz4(rec[2]), xyz4(rec[0]), ro, rd, t, det);
+                    uint32_t next = cur >= LDS_DESC_LEAF_MANY ? cur - LDS_LEAF_REST : LDS_DESC_POP;      /* the rest of the leaf, or the leaf is done */
                     if (ok && t > 0.001f && (SEGMENT ? t < max_t : (t < res.t && (!ANY_HIT || t <= max_t)))) {
                         asm volatile("" ::: "memory");                 /* (a real branch, as in walk_run) */
                         res.t = t;
                         res.tri = ti | (rptm::f2u(det) & 0x80000000u);
-                        if (ANY_HIT || (MIXED && stop_first != 0u)) { accepted = true; break; }
+                        if (ANY_HIT || (MIXED && stop_first != 0u)) next = LDS_DESC_DEAD;
                     }
-                    ++ti;
-                    rec += 3;
-                } while (ti != end);
-                cur = ((ANY_HIT || MIXED) && accepted) ? LDS_DESC_DEAD : LDS_DESC_POP;
+                    cur = next;
+                } else {
+                    bool accepted = false;
+                    const uint32_t first = cur & 511u;
+                    uint32_t ti = first;
+                    const uint32_t end = first + ((cur >> 9) & 63u);       /* (a leaf holds at least one triangle: a count of 0 is an inner node) */
+                    const float4 *rec = view.tri_base() + 3u * first;
+                    do {
+                        float t, det;
+                        const bool ok = moller_trumbore_flat(xyz4(rec[1]), xyz4(rec[2]), xyz4(rec[0]), ro, rd, t, det);
+                        if (ok && t > 0.001f && (SEGMENT ? t < max_t : (t < res.t && (!ANY_HIT || t <= max_t)))) {
+                            asm volatile("" ::: "memory");                 /* (a real branch, as in walk_run) */
+                            res.t = t;
+                            res.tri = ti | (rptm::f2u(det) & 0x80000000u);
+                            if (ANY_HIT || (MIXED && stop_first != 0u)) { accepted = true; break; }
+                        }
+                        ++ti;
+                        rec += 3;
+                    } while (ti != end);
+                    cur = ((ANY_HIT || MIXED) && accepted) ? LDS_DESC_DEAD : LDS_DESC_POP;
+                }
             }
         }
-        if (n_leaf <= n_inner) {                                       /* (a branch of its own: as the `else` of the one above, the two are joined through a mask) */
+        if ((n_leaf << VOTE) <= n_inner) {                             /* (a branch of its own: as the `else` of the one above, the two are joined through a mask) */
             if (SceneViewLds::is_inner(cur)) {
                 const float4 X = lds_planes(px, cur), Y = lds_planes(py, cur), Z = lds_planes(pz, cur);
                 const uint32_t d = lds_at<uint32_t>(descs, cur);

@@ -47,6 +47,12 @@ __device__ __forceinline__ void iteration_bookkeeping(const DevQueues &q, uint32
  * the image); 20 / 16 and 24 / 16 the same within noise, 16 / 20 less. */
 constexpr int RPT_STREAM_TRIPS = 16;
 constexpr int RPT_STREAM_REFILL = 16;
+/* The leaf trips of the PLAIN nearest-hit launches (k_walk.h lds_stream_walk_run ONE_TRI, VOTE): one triangle per leaf trip, a lane on a leaf counts double in the
+ * vote.  Every other streamed LDS kernel keeps the whole leaf per trip and the plain vote: FIRST's coherent waves lose with short leaf trips
+ * (replayed + 8 %, measured + 2.9 %), LAST needs 65 vector registers for them, one more than 8 waves per SIMD leave it, and the shadow kernels have no replay and no
+ * A/B of their own. */
+constexpr bool RPT_STREAM_PLAIN_ONE_TRI = true;
+constexpr int RPT_STREAM_PLAIN_VOTE = 1;
 /* The workgroup's pool is one 64-bit LDS word (next slot | end slot << 32): a wave takes slots with ONE 64-bit ds_add that
  * returns a consistent (next, end) pair.  When the span is used up the wave that notices fetches the next span of SPAN
  * slots from the launch-wide counter (one global atomic per SPAN slots) — PERSISTENT workgroups: the grid holds as many

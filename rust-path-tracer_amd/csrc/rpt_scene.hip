@@ -77,6 +77,9 @@ bool build_lds_image(const rpt_bvh_node *nodes, size_t nn, const std::vector<flo
     auto desc = [&](const rpt_bvh_node &n, uint32_t &out) {
         if (n.triangle_count != 0u) {
             if (n.triangle_count >= 64u || n.left_or_first >= 512u || (size_t)n.left_or_first + n.triangle_count > nt) return false;
+            /* what the streamed walks rely on where they keep the REST of a leaf as a descriptor (k_walk.h lds_stream_walk_run ONE_TRI): every (first + k, count - k),
+             * k < count, is a leaf descriptor again — first + count <= 512 (nt <= 512 above says so already; held here in its own words) */
+            if (n.left_or_first + n.triangle_count > 512u) return false;
             out = LDS_DESC_LEAF | (n.triangle_count << 9) | n.left_or_first;
             return true;
         }

@@ -20,6 +20,8 @@ VALU = v_*; SALU = s_* without s_waitcnt / s_nop / s_sleep / s_barrier / s_endpg
 The flattened walk of the streamed lanes (k_walk.h lds_stream_walk_run) stands in another text order — latch (the ballots and the loop's one exit, ahead of the header label:
 loop head), vote, leaf set-up, triangle loop, inner body, push, and ONE pop site behind both bodies — and the same rules sort it: what follows the triangle loop up to the
 plane loads (the end of the leaf body, the vote's second half) and what follows the stack store (the merged pop) is push / pop.
+A leaf body WITHOUT a triangle loop (one triangle per leaf trip, lds_stream_walk_run RPT_LEAF_ONE) is `triangle iteration` too: from the block of the walk loop that
+loads a triangle record (ds_read_b96) to the block that gives exec back what the leaf body's s_and_saveexec took; its set-up is part of it (`leaf set-up` 0).
 `inner trip, total` = loop head + inner body + push / pop: what a trip of the inner step issues.  The last two columns are the region's cost at the unit costs of
 tools/microbench/valu_rates.hip (profiles/r04_valu_pipes.txt, question 3): 3.7 per vector and 6.5 per scalar instruction; a change pays where their sum goes down."""
 import re, subprocess, sys
@@ -89,15 +91,22 @@ def analyse(blocks):
     result = []
     for w in walks:
         regs = {r: [] for r in REGIONS[:5]}
-        state, seen_header = 'loop head', False
+        state, seen_header, leaf_exec, prev = 'loop head', False, None, None
         for b in blocks:
             if not inside(b['loop'], w): continue
             if b['loop'] != w:
                 regs['triangle iteration'].append(b)
                 state = 'push / pop'                      # behind the triangle loop: the leaf's pop
                 continue
+            own_prev, prev = prev, b
             if b['is_header']: seen_header, state = True, 'loop head'
             elif not seen_header: state = 'loop head'     # latch blocks stand ahead of the header label
+            elif has(b, r'ds_read_b96'):                  # a leaf body WITHOUT a triangle loop (one triangle per leaf trip): its triangle test
+                state = 'triangle iteration'
+                saved = [re.match(r's_and_saveexec_b64 (s\[\d+:\d+\])', i) for i in (own_prev['ins'] if own_prev else [])]
+                leaf_exec = ([m[1] for m in saved if m] or [None])[-1]
+            elif state == 'triangle iteration' and leaf_exec and b['ins'][:1] == ['s_or_b64 exec, exec, ' + leaf_exec]:
+                state = 'push / pop'                      # the lanes that sat the leaf trip out are back: the vote's second half
             elif has(b, r'ds_read_b128'): state = 'inner body'
             elif has(b, r'v_bfe_u32') : state = 'leaf set-up'
             elif state == 'inner body' and (has(b, r'ds_read_u16|ds_write_b16|ds_read_b32') or has(b, r'v_mov_b32_e32 v\d+, 0x4000')): state = 'push / pop'
