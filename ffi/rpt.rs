@@ -119,6 +119,13 @@ pub struct rpt_material_model {
     pub reserved: [u32; 2],
 }
 
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct rpt_material_volume {
+    pub sigma: [f32; 3], // absorption per unit scene length, r g b: finite and not negative; counts on a GLASS material only
+    pub reserved: u32,   // 0
+}
+
 /// rpt_set_camera_lens: field of view, aperture and focus distance in place of the reference's pinhole (lib.rs:38-51); {1, 0, 1, 0} is that pinhole
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -193,6 +200,8 @@ extern "C" {
     pub fn rpt_shadow_mode(ctx: *mut rpt_ctx, mode_out: *mut u32) -> c_int;
     pub fn rpt_set_material_models(ctx: *mut rpt_ctx, models: *const rpt_material_model, n_models: usize) -> c_int;   // one record per material, beside MaterialData (which stays as it is); (null, 0): all PBR
     pub fn rpt_material_models(ctx: *mut rpt_ctx, out: *mut rpt_material_model, capacity: usize, n_out: *mut usize) -> c_int;
+    pub fn rpt_set_material_volumes(ctx: *mut rpt_ctx, volumes: *const rpt_material_volume, n: usize) -> c_int;   // one record per material, beside the model records; (null, 0): none
+    pub fn rpt_material_volumes(ctx: *mut rpt_ctx, out: *mut rpt_material_volume, capacity: usize, n_out: *mut usize) -> c_int;
     pub fn rpt_camera_lens_default(out: *mut rpt_camera_lens);                      // {1, 0, 1, 0}
     pub fn rpt_set_camera_lens(ctx: *mut rpt_ctx, lens: *const rpt_camera_lens) -> c_int;   // null: the default; holds from the next render call, the caller resets the accumulator
     pub fn rpt_camera_lens_get(ctx: *mut rpt_ctx, out: *mut rpt_camera_lens) -> c_int;
@@ -265,6 +274,7 @@ extern "C" {
     pub fn rpt_multi_reset(m: *mut rpt_multi, rng_seed: *const UVec2, accum_init: *const Vec4, samples_init: u32) -> c_int;
     pub fn rpt_multi_set_shadow_mode(m: *mut rpt_multi, mode: u32) -> c_int;       // rpt_set_shadow_mode on every rank
     pub fn rpt_multi_set_material_models(m: *mut rpt_multi, models: *const rpt_material_model, n_models: usize) -> c_int;   // rpt_set_material_models on every rank
+    pub fn rpt_multi_set_material_volumes(m: *mut rpt_multi, volumes: *const rpt_material_volume, n: usize) -> c_int;   // rpt_set_material_volumes on every rank
     pub fn rpt_multi_set_camera_lens(m: *mut rpt_multi, lens: *const rpt_camera_lens) -> c_int;   // rpt_set_camera_lens on every rank
     pub fn rpt_multi_set_guides_through_glass(m: *mut rpt_multi, max_interfaces: u32) -> c_int;   // rpt_set_guides_through_glass on every rank
     pub fn rpt_multi_render(m: *mut rpt_multi, n_samples: u32) -> c_int;           // one batch on every GPU + the batch's single RCCL gather

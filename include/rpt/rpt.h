@@ -352,6 +352,35 @@ typedef struct rpt_material_model { uint32_t model; float ior; uint32_t reserved
 int rpt_set_material_models(rpt_ctx *ctx, const rpt_material_model *models, size_t n_models);  /* NULL, 0: all PBR */
 int rpt_material_models(rpt_ctx *ctx, rpt_material_model *out, size_t capacity, size_t *n_out);
 int rpt_multi_set_material_models(rpt_multi *m, const rpt_material_model *models, size_t n_models);   /* on every rank */
+/* Absorbing glass: per-material Beer-Lambert attenuation.  Opt-in; no reference equivalent (Glass::sample's only colour is `spectrum = albedo`, once per
+ * refracting interface, bsdf.rs:165: a thick block and a thin pane of one material come out the same colour).  One record per material beside the model
+ * records: sigma, the absorption per unit scene length, r g b.  The rule, for closed, non-nested glass — a segment that ARRIVES at a Glass surface from the
+ * inside has travelled through that glass:
+ *   where    in the surface stage, at the hit (t, triangle) of an extension ray, whichever bounce it is, after the emission branch (lib.rs:86-108) has NOT
+ *            ended the path
+ *   iff      the material's model is RPT_MODEL_GLASS and dot(normal, view) < 0, with normal the very vector handed to Glass::sample — the shading normal after
+ *            normal mapping, un-normalised (lib.rs:125) — and view = -ray_direction
+ *   what     T_c = exp(-(sigma_c * t)), c = x, y, z: an f32 product, negated, through the deterministic, correctly rounded exp of csrc/rpt_math.h (rptm::expr);
+ *            throughput = throughput * T, before the sample's own throughput = throughput * (spectrum / pdf)         (csrc/k_volume.h vol_transmit)
+ * Nothing else changes: the draws and their dimensions, Glass::sample, next-event estimation (never for Glass), the roulette — which sees the attenuated
+ * throughput as it sees any other — and the ray counts.  sigma_c == 0 gives exp(-0) = 1 and leaves that channel bit for bit; at the last bounce nothing reads
+ * the throughput; an emissive Glass material ends the path before the rule applies.
+ * Limits: the segment is attributed to the glass it ENDS on — one that ends on a non-glass object embedded in the glass, on an emitter, or in the sky through
+ * an open mesh is not attenuated; there are no nested dielectrics; a single-sided Glass sheet reads "inside" from its back and attenuates by the distance to
+ * the previous vertex, so volumes belong on closed meshes; the camera may start inside.  The denoiser's guides are unchanged: with
+ * rpt_set_guides_through_glass the chain's albedo does not carry T (demodulation then leaves a smooth thickness term in the filtered image).
+ * rpt_set_material_volumes: the life cycle of rpt_set_material_models — after rpt_upload_scene, n == the scene's material count; callable between any two
+ * batches (it waits for what is enqueued); leaves accumulator, rng, moments, statistics, shadow mode, lens and guides alone (the guides are NOT marked stale);
+ * rpt_upload_scene clears the records, rpt_set_config keeps them.  (NULL, 0): none.  Independent of the order in which it and rpt_set_material_models are
+ * called: a record on a material that is not Glass is stored and ignored.  RPT_EINVAL, the message naming the record, with the context and both record sets
+ * as they were, for a sigma channel that is negative, NaN or infinite, reserved != 0, a count that is not the scene's, NULL with n != 0 or the reverse, a call
+ * before a scene.  With no records, with every sigma zero or with no Glass material the kernels launched are the ones launched without this call.
+ * rpt_material_volumes: the records as set (n_out = 0: none), out nullable, capacity in records.
+ * Not carried: by rpt_world_save's .rptscene cache and by the host mirror rpt_trace_gpu (rpt_host.h). */
+typedef struct rpt_material_volume { float sigma[3]; uint32_t reserved; } rpt_material_volume;   /* absorption per unit scene length, r g b */
+int rpt_set_material_volumes(rpt_ctx *ctx, const rpt_material_volume *volumes, size_t n);   /* NULL, 0: none */
+int rpt_material_volumes(rpt_ctx *ctx, rpt_material_volume *out, size_t capacity, size_t *n_out);
+int rpt_multi_set_material_volumes(rpt_multi *m, const rpt_material_volume *volumes, size_t n);   /* on every rank */
 /* Thin-lens camera.  Opt-in; the reference's camera is a pinhole with a fixed 90 degree HORIZONTAL field of view (kernels/src/lib.rs:38-51) and
  * rpt_tracing_config carries a position and two angles only.  The lens replaces lib.rs:38-51 and nothing else of trace_pixel (csrc/k_lens.h states the f32
  * operations): the film coordinates are scaled by tan_half_fov before the direction is normalized, and with aperture_radius > 0 the ray leaves a point of

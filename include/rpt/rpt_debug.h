@@ -197,6 +197,17 @@ int rpt_debug_short_batch(rpt_ctx *ctx, int on);
  * say — on an all-PBR scene it must give the plain kernels' image and counters bit for bit. */
 int rpt_debug_force_model_kernels(rpt_ctx *ctx, int on);
 
+/* Test aid: on != 0 makes the render calls of this context launch the volumes variant of the shade stage (rpt_set_material_volumes) whatever the records
+ * say — with no records, or with all-zero ones, it must give the models variant's image and counters bit for bit.
+ * rpt_debug_last_shade_variant: which build of the shade stage the context's last shade launch was — 0 k_shade, 1 k_shade_models, 2 k_shade_volumes. */
+int rpt_debug_force_volume_kernels(rpt_ctx *ctx, int on);
+int rpt_debug_last_shade_variant(rpt_ctx *ctx, uint32_t *variant_out);
+
+/* The arithmetic of rpt_set_material_volumes alone (csrc/k_volume.h vol_transmit) on n items: throughput_xyz, sigma_xyz, out_xyz 3 floats per item, t one.
+ * on_device == 0: the host build of the header — no device needed, ctx may be NULL; else the same header through a device kernel of the context's device.
+ * RPT_EINVAL for null pointers (and a null ctx with on_device != 0). */
+int rpt_debug_volume_transmit(rpt_ctx *ctx, int on_device, const float *throughput_xyz, const float *sigma_xyz, const float *t, size_t n, float *out_xyz);
+
 /* The camera rays of rpt_set_camera_lens (csrc/k_lens.h lens_ray) for n chosen (pixel, key) pairs: pixels_xy[i] = x | y << 16, keys[i] = the sample's LDS key
  * n + offset; origins_out, dirs_out: 3 floats per pair.  config: position, rotation, width and height are read; lens NULL = the default.
  * rpt_debug_lens_rays_host: the host build of the header — no device needed.  rpt_debug_lens_rays: the same header through a device kernel, with the

@@ -64,6 +64,14 @@ int rpt_world_load(const char *path, rpt_world **out);
 #define RPT_LOAD_MATERIAL_MODELS 2u
 int rpt_world_load_ex(const char *path, uint32_t flags, rpt_world **out);
 int rpt_world_material_models(const rpt_world *world, rpt_material_model *out, size_t capacity, size_t *n_out);
+/* RPT_LOAD_MATERIAL_VOLUMES (off by default): a glTF material with extensions.KHR_materials_volume, thicknessFactor > 0 and a finite attenuationDistance > 0
+ * gets an absorption record (rpt.h rpt_set_material_volumes) with sigma_c = -ln(attenuationColor_c) / attenuationDistance, computed in double and rounded to
+ * f32; colour channels are clamped to [0, 1] (the extension's default colour: 1, 1, 1), a channel of 0 gives FLT_MAX.  Every other material gets zeros.  The
+ * records count on Glass materials only, so the flag goes with RPT_LOAD_MATERIAL_MODELS.  The buffers of the world do not depend on the flag.
+ * rpt_world_material_volumes: one record per material of the world (zeros for a world loaded without the flag, from buffers, from an OBJ or from the .rptscene
+ * cache, which does not carry them); out nullable, capacity in records, n_out = the material count.  The host mirror rpt_trace_gpu does not apply them. */
+#define RPT_LOAD_MATERIAL_VOLUMES 4u
+int rpt_world_material_volumes(const rpt_world *world, rpt_material_volume *out, size_t capacity, size_t *n_out);
 /* load_dynamic_image + dynamic_image_to_cpu_buffer (src/asset.rs:238-273): a skybox file (.png, Radiance .hdr) as the
  * reference's CPU path sees it — quantised to 8 bits per channel, alpha 1 — as width*height float RGBA, the layout
  * rpt_upload_scene takes.  Caller frees with rpt_host_free. */

@@ -52,6 +52,7 @@ BVH_NODE_DTYPE = np.dtype([("aabb_min", "<f4", 3), ("triangle_count", "<u4"), ("
 TRIANGLE_DTYPE = np.dtype([("v0", "<u4"), ("v1", "<u4"), ("v2", "<u4"), ("material", "<u4")])
 RNG_DTYPE = np.dtype([("n", "<u4"), ("offset", "<u4")])
 MATERIAL_MODEL_DTYPE = np.dtype([("model", "<u4"), ("ior", "<f4"), ("reserved", "<u4", 2)])      # rpt_material_model (include/rpt/rpt.h)
+MATERIAL_VOLUME_DTYPE = np.dtype([("sigma", "<f4", 3), ("reserved", "<u4")])      # rpt_material_volume
 assert MATERIAL_DTYPE.itemsize == 96 and PER_VERTEX_DTYPE.itemsize == 64 and LIGHT_PICK_DTYPE.itemsize == 28
 assert BVH_NODE_DTYPE.itemsize == 32 and TRIANGLE_DTYPE.itemsize == 16 and RNG_DTYPE.itemsize == 8
 

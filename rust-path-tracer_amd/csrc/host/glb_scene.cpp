@@ -24,6 +24,7 @@
  * tangents (left zero; only read when a normal texture exists, and no shipped
  * scene has textures).  Texture atlas packing (src/atlas.rs) is out of scope.
  */
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -531,6 +532,7 @@ bool load_glb(const char *path, World &out, uint32_t flags) {
     /* materials (asset.rs:135-175) */
     out.materials.assign(n_file_materials + (ga.used_default_material ? 1 : 0), rpt_material_data{});
     out.material_models.assign(out.materials.size(), rpt_material_model{RPT_MODEL_PBR, 0.0f, {0u, 0u}});
+    out.material_volumes.assign(out.materials.size(), rpt_material_volume{{0.0f, 0.0f, 0.0f}, 0u});
     std::vector<Image8> textures;          /* in the reference's push order: per material albedo, metallic, roughness, normals */
     for (size_t i = 0; i < out.materials.size(); ++i) {
         rpt_material_data &m = out.materials[i];
@@ -560,6 +562,23 @@ bool load_glb(const char *path, World &out, uint32_t flags) {
                     if (const JValue *tr = ext->get("KHR_materials_transmission"); tr && tr->number_or("transmissionFactor", 0.0) > 0.0) {
                         const JValue *ji = ext->get("KHR_materials_ior");
                         out.material_models[i] = rpt_material_model{RPT_MODEL_GLASS, ji ? (float)ji->number_or("ior", 1.5) : 1.5f, {0u, 0u}};
+                    }
+            /* RPT_LOAD_MATERIAL_VOLUMES: KHR_materials_volume with a thickness and a finite attenuation distance absorbs, sigma = -ln(colour) / distance in
+             * double, rounded to f32 once; colour channels clamped to [0, 1], a channel of 0 absorbs everything a finite sigma can */
+            if (flags & RPT_LOAD_MATERIAL_VOLUMES)
+                if (const JValue *ext = jm.get("extensions"))
+                    if (const JValue *vol = ext->get("KHR_materials_volume")) {
+                        const double distance = vol->number_or("attenuationDistance", HUGE_VAL);
+                        if (vol->number_or("thicknessFactor", 0.0) > 0.0 && std::isfinite(distance) && distance > 0.0) {
+                            double colour[3] = {1.0, 1.0, 1.0};
+                            if (const JValue *c = vol->get("attenuationColor"); c && c->arr.size() == 3)
+                                for (int k = 0; k < 3; ++k) colour[k] = c->arr[k]->num;
+                            for (int k = 0; k < 3; ++k) {
+                                const double ck = colour[k] < 0.0 ? 0.0 : (colour[k] > 1.0 ? 1.0 : colour[k]);      /* (a NaN stays: it fails both tests and gives FLT_MAX below) */
+                                const double sigma = -std::log(ck) / distance;
+                                out.material_volumes[i].sigma[k] = (ck > 0.0 && sigma <= (double)FLT_MAX) ? (float)sigma + 0.0f : FLT_MAX;   /* (+ 0: -0 of a channel of 1 is +0) */
+                            }
+                        }
                     }
             /* textures (asset.rs:140-160).  assimp's glTF2 importer exposes metallicRoughnessTexture under BOTH
              * aiTextureType_METALNESS and aiTextureType_DIFFUSE_ROUGHNESS, so the reference atlases it twice. */

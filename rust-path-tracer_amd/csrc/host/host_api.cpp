@@ -160,6 +160,18 @@ int rpt_world_material_models(const rpt_world *world, rpt_material_model *out, s
     return 0;
 }
 
+int rpt_world_material_volumes(const rpt_world *world, rpt_material_volume *out, size_t capacity, size_t *n_out) {
+    if (!world || !n_out) { set_error("null argument"); return RPT_EINVAL; }
+    const World &w = world->w;
+    *n_out = w.materials.size();
+    if (out) {
+        if (capacity < w.materials.size()) { set_error("rpt_world_material_volumes: capacity below the material count"); return RPT_EINVAL; }
+        for (size_t i = 0; i < w.materials.size(); ++i)      /* (a world no loader gave records — buffers, OBJ, the cache — absorbs nothing) */
+            out[i] = i < w.material_volumes.size() ? w.material_volumes[i] : rpt_material_volume{{0.0f, 0.0f, 0.0f}, 0u};
+    }
+    return 0;
+}
+
 void rpt_world_free(rpt_world *world) { delete world; }
 
 int rpt_bvh_build(const float *vertices_xyzw, size_t n_vertices, rpt_triangle *triangles, size_t n_triangles,

@@ -33,6 +33,7 @@
 #define RPT_EPS 0.001f   /* util.rs:5 */
 
 #include "k_bsdf_extra.h"        /* Lambertian and Glass: what shade_slot<.., MODELS> constructs in place of the PBR BSDF */
+#include "k_volume.h"            /* vol_transmit: what shade_slot<.., VOLUMES> multiplies the throughput by at a Glass hit from the inside */
 
 /* ---- CPU-polyfill image sampling (shared_structs/src/image_polyfill.rs:32-55) ----------------------------------------------------------
  * sample_raw: `coord.x as usize % width as usize` — the i32 sign-extends to 64 bits, then an UNSIGNED 64-bit remainder.  Written out that
@@ -193,15 +194,18 @@ __device__ __forceinline__ Mat load_material(const DevScene &sc, uint32_t index)
  * material is PBR".  The model replaces the BSDF constructed at lib.rs:144 and nothing else: Lambertian { albedo } or Glass { albedo, ior, roughness } from what
  * get_pbr_bsdf found (texture lookups and guards included), through the reference's generic code — one gen_r3(), NEE iff the sampled lobe is the diffuse
  * reflection (always / never), Lambertian::evaluate and pdf in the light sample, FLAG_LOBE_SPEC = "the last lobe was not the diffuse reflection". */
+/* VOLUMES (rpt_set_material_volumes; instantiated in rpt_volumes.hip only, with MODELS): `volumes` holds one record per material, (sigma r, g, b, -), or is null
+ * for "no material absorbs".  At a hit of a Glass material from its inside — dot(normal, view) < 0 with the normal handed to glass_sample — the throughput is
+ * multiplied by vol_transmit(sigma, hit_t) before the sample's own factor (k_volume.h); nothing else of the stage changes. */
 #define RPT_DEV_MODEL_LAMBERTIAN 1u
 #define RPT_DEV_MODEL_GLASS 2u
-template <int NEE, bool TEXTURED, bool COMPACT, bool MODELS = false>
+template <int NEE, bool TEXTURED, bool COMPACT, bool MODELS = false, bool VOLUMES = false>
 __device__ __forceinline__ void shade_slot(const DevScene &sc, const DevState &st, const DevQueues &q, const DevConfig &cfg, DevStats *stats,
                                            uint32_t slot, float2 hw, bool active, bool &to_sky, bool &emit_shadow, float4 &sh_o, float4 &sh_d,
                                            float4 &sh_c, bool first /* iteration 0 of the call: every path is a first path (k_path.h) */,
                                            uint32_t n_samples, bool &elided /* an NEE evaluation whose shadow ray decides nothing: not queued */,
                                            bool last_iteration /* wave-uniform: every path of this launch is at its last bounce and has a radiance record */,
-                                           const uint4 *models = nullptr) {
+                                           const uint4 *models = nullptr, const float4 *volumes = nullptr) {
     const uint32_t hit_tri = __float_as_uint(hw.y);
     /* wave-uniform: live paths of this batch keep no radiance record (DevQueues::implicit_zero — their radiance is +0 and they owe nothing): a continuing path
      * writes none, a path that ends with nothing added ends as HIT_DONE_ZERO, one that ends on an emitter's front writes 0 + its term and never loads */
@@ -405,12 +409,19 @@ __device__ __forceinline__ void shade_slot(const DevScene &sc, const DevState &s
                 F3 sdir = f3s(0.0f);
                 bool lambert = false, glass = false;
                 float ior = 1.0f;
+                F3 sigma = f3s(0.0f);
                 if (MODELS) {
                     if (models) {
                         const uint4 mm = models[__float_as_uint(s2.w)];
                         lambert = mm.x == RPT_DEV_MODEL_LAMBERTIAN;
                         glass = mm.x == RPT_DEV_MODEL_GLASS;
                         ior = __uint_as_float(mm.y);
+                        if (VOLUMES) {
+                            if (volumes) {                          /* (beside the model record: both loads are in flight together) */
+                                const float4 vv = volumes[__float_as_uint(s2.w)];
+                                sigma = f3(vv.x, vv.y, vv.z);
+                            }
+                        }
                     }
                 }
                 /* "the sampled lobe is not the diffuse reflection": both of Glass's lobes (1 and 3), never Lambertian's */
@@ -419,6 +430,10 @@ __device__ __forceinline__ void shade_slot(const DevScene &sc, const DevState &s
                 F3 spectrum = f3s(0.0f);
                 if (MODELS && glass) {
                     if (!last) {
+                        /* rpt_set_material_volumes: the segment that ends here ran through this glass (at the last bounce nothing reads the throughput) */
+                        if (VOLUMES) {
+                            if (dot3(normal, view) < 0.0f) throughput = vol_transmit(throughput, sigma, hit_t);
+                        }
                         const BsdfSample o = glass_sample(bsdf.albedo, ior, bsdf.roughness, view, normal, f3(r1, r2, r3));     /* (pdf 1) */
                         sdir = o.direction;
                         spectrum = o.spectrum;
@@ -676,15 +691,19 @@ __device__ __forceinline__ void count_elided(uint32_t *lds_counter, bool elided)
  * (PBRTest 69.3 -> 67.4 per 4).  The NEE variants spill when pushed (72 VGPRs: 20-44 bytes of scratch; packed: VeachMIS shade 44.0 -> 48.6) and are left alone. */
 constexpr int RPT_SHADE_WAVES_PLAIN = 8;
 constexpr int RPT_SHADE_WAVES_PACKED = 5;
-/* The kernel: one text (k_shade_body.h) compiled here as k_shade and in rpt_models.hip as k_shade_models */
+/* The kernel: one text (k_shade_body.h) compiled here as k_shade, in rpt_models.hip as k_shade_models and in rpt_volumes.hip as k_shade_volumes */
 #define RPT_SHADE_KERNEL k_shade
 #define RPT_SHADE_MODELS false
 #define RPT_SHADE_MODELS_ARG(...)
+#define RPT_SHADE_VOLUMES false
+#define RPT_SHADE_VOLUMES_ARG(...)
 #define RPT_SHADE_OCCUPANCY __attribute__((amdgpu_waves_per_eu((NEE == RPT_NEE_NONE && !TEXTURED) ? (COMPACT ? RPT_SHADE_WAVES_PACKED : RPT_SHADE_WAVES_PLAIN) : 1, 8)))
 #include "k_shade_body.h"
 #undef RPT_SHADE_KERNEL
 #undef RPT_SHADE_MODELS
 #undef RPT_SHADE_MODELS_ARG
+#undef RPT_SHADE_VOLUMES
+#undef RPT_SHADE_VOLUMES_ARG
 #undef RPT_SHADE_OCCUPANCY
 
 #endif /* RPT_K_SHADE_H */

@@ -842,6 +842,16 @@ int rpt_multi_set_material_models(rpt_multi *m, const rpt_material_model *models
     return RPT_OK;
 }
 
+/* rpt_set_material_volumes on every rank (the records are checked before anything changes: a refusal on rank 0 means no rank was changed) */
+int rpt_multi_set_material_volumes(rpt_multi *m, const rpt_material_volume *volumes, size_t n) {
+    if (!m) return RPT_EINVAL;
+    for (rpt_ctx *c : m->ctx) {
+        int rc = rpt_set_material_volumes(c, volumes, n);
+        if (rc) return multi_fail(m, c, rc);
+    }
+    return RPT_OK;
+}
+
 /* rpt_set_camera_lens on every rank (the record is checked before anything changes: a refusal on rank 0 means no rank was changed) */
 int rpt_multi_set_camera_lens(rpt_multi *m, const rpt_camera_lens *lens) {
     if (!m) return RPT_EINVAL;

@@ -262,6 +262,14 @@ struct rpt_ctx {
     std::vector<rpt_material_model> material_models_host;
     bool models_in_use = false;                /* some record is not PBR: the shade stage is k_shade_models */
     bool force_model_kernels = false;          /* rpt_debug_force_model_kernels: k_shade_models whatever the records say (none: every material PBR) */
+    /* rpt_set_material_volumes (rpt_volumes.hip): one absorption record per material, handed to k_shade_volumes as one more argument of its own, and their
+     * host copy for rpt_material_volumes; the life cycle of the model records.  volumes_in_use is recomputed by both setters and both clears
+     * (rpt_material_volumes_recount): it does not depend on the order in which the two record sets arrive */
+    DevBuf<rpt_material_volume> material_volumes;
+    std::vector<rpt_material_volume> material_volumes_host;
+    bool volumes_in_use = false;               /* some Glass record has a volume record with a non-zero sigma: the shade stage is k_shade_volumes */
+    bool force_volume_kernels = false;         /* rpt_debug_force_volume_kernels: k_shade_volumes whatever the records say */
+    uint32_t last_shade_variant = 0;           /* rpt_debug_last_shade_variant: 0 k_shade, 1 k_shade_models, 2 k_shade_volumes — what the last shade launch was */
     /* rpt_set_camera_lens (rpt_lens.hip, k_lens.h): handed to the lens kernels as an argument of its own — DevConfig is what it was.  Active (anything but
      * {1, 0, *}): render calls open with k_generate_lens, complete with the lens builds of the completion kernels and keep at least two slots per pixel busy */
     rpt_camera_lens lens{1.0f, 0.0f, 1.0f, 0u};
@@ -340,6 +348,10 @@ void rpt_launch_shadow(rpt_ctx *c);
  * "no records", for rpt_upload_scene */
 void rpt_launch_shade_models(rpt_ctx *c, uint32_t iteration, uint32_t blocks);
 void rpt_material_models_clear(rpt_ctx *c);
+/* rpt_volumes.hip: the same stage as k_shade_volumes; "no volume records", for rpt_upload_scene; volumes_in_use from the two record sets as they stand */
+void rpt_launch_shade_volumes(rpt_ctx *c, uint32_t iteration, uint32_t blocks);
+void rpt_material_volumes_clear(rpt_ctx *c);
+void rpt_material_volumes_recount(rpt_ctx *c);
 /* rpt_lens.hip: the lens is anything but the reference's camera; its primary rays leave different origins (aperture > 0: iteration 0 is the plain walk) */
 inline bool rpt_lens_active(const rpt_ctx *c) { return !(c->lens.tan_half_fov == 1.0f && c->lens.aperture_radius == 0.0f); }
 inline bool rpt_lens_scatters_origins(const rpt_ctx *c) { return c->lens.aperture_radius > 0.0f; }

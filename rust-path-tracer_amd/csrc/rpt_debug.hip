@@ -200,6 +200,32 @@ int rpt_debug_bsdf(rpt_ctx *c, int kind, size_t n, const float *in, float *out) 
     return RPT_OK;
 }
 
+__global__ void k_debug_volume_transmit(const float *thr, const float *sigma, const float *t, size_t n, float *out) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const F3 o = vol_transmit(f3(thr[3 * i], thr[3 * i + 1], thr[3 * i + 2]), f3(sigma[3 * i], sigma[3 * i + 1], sigma[3 * i + 2]), t[i]);
+    out[3 * i] = o.x; out[3 * i + 1] = o.y; out[3 * i + 2] = o.z;
+}
+
+int rpt_debug_volume_transmit(rpt_ctx *c, int on_device, const float *thr, const float *sigma, const float *t, size_t n, float *out) {
+    if (!thr || !sigma || !t || !out || (on_device && !c)) return RPT_EINVAL;
+    if (n == 0) return RPT_OK;
+    if (!on_device) {
+        for (size_t i = 0; i < n; ++i) {
+            const F3 o = vol_transmit(f3(thr[3 * i], thr[3 * i + 1], thr[3 * i + 2]), f3(sigma[3 * i], sigma[3 * i + 1], sigma[3 * i + 2]), t[i]);
+            out[3 * i] = o.x; out[3 * i + 1] = o.y; out[3 * i + 2] = o.z;
+        }
+        return RPT_OK;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    DevBuf<float> dthr, dsigma, dt, dout;
+    HIP_TRY(c, dthr.from_host(thr, 3 * n)); HIP_TRY(c, dsigma.from_host(sigma, 3 * n)); HIP_TRY(c, dt.from_host(t, n)); HIP_TRY(c, dout.alloc(3 * n));
+    k_debug_volume_transmit<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(dthr.p, dsigma.p, dt.p, n, dout.p);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(out, dout.p, 12 * n, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+
 int rpt_debug_sample_image(rpt_ctx *c, int is_u8, const void *texels, uint32_t width, uint32_t height, size_t n, const float *coords_uv, float *out_rgba) {
     if (!c || !texels || !coords_uv || !out_rgba || width == 0u || height == 0u) return RPT_EINVAL;
     /* the limits of rpt_upload_scene: texel indices are 32-bit in sample_by_lod */

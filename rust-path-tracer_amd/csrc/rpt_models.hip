@@ -18,11 +18,15 @@ static_assert(RPT_MODEL_LAMBERTIAN == RPT_DEV_MODEL_LAMBERTIAN && RPT_MODEL_GLAS
 #define RPT_SHADE_KERNEL k_shade_models
 #define RPT_SHADE_MODELS true
 #define RPT_SHADE_MODELS_ARG(...) __VA_ARGS__
+#define RPT_SHADE_VOLUMES false
+#define RPT_SHADE_VOLUMES_ARG(...)
 #define RPT_SHADE_OCCUPANCY
 #include "k_shade_body.h"
 #undef RPT_SHADE_KERNEL
 #undef RPT_SHADE_MODELS
 #undef RPT_SHADE_MODELS_ARG
+#undef RPT_SHADE_VOLUMES
+#undef RPT_SHADE_VOLUMES_ARG
 #undef RPT_SHADE_OCCUPANCY
 
 template <int NEE, bool TEXTURED>
@@ -46,6 +50,7 @@ void rpt_material_models_clear(rpt_ctx *c) {
     c->material_models.release();
     c->material_models_host.clear();
     c->models_in_use = false;
+    rpt_material_volumes_recount(c);     /* (no Glass record: no volume record is in use) */
 }
 
 extern "C" {
@@ -77,6 +82,7 @@ int rpt_set_material_models(rpt_ctx *c, const rpt_material_model *models, size_t
     HIP_TRY(c, hipMemcpy(c->material_models.p, models, n_models * sizeof(rpt_material_model), hipMemcpyHostToDevice));
     c->material_models_host.assign(models, models + n_models);
     c->models_in_use = in_use;
+    rpt_material_volumes_recount(c);     /* (rpt_set_material_volumes: a volume record counts on a Glass material only) */
     return RPT_OK;
 }
 

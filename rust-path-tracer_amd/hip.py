@@ -11,7 +11,7 @@ import os
 import numpy as np
 
 from . import _ffi
-from ._ffi import MATERIAL_MODEL_DTYPE, RNG_DTYPE, Stats, TracingConfig, ptr
+from ._ffi import MATERIAL_MODEL_DTYPE, MATERIAL_VOLUME_DTYPE, RNG_DTYPE, Stats, TracingConfig, ptr
 
 _lib = None
 
@@ -27,6 +27,26 @@ def material_models(models, iors=None):
     rec["model"] = models
     rec["ior"] = 1.5 if iors is None else iors
     return rec
+
+
+def material_volumes(sigmas):
+    """records for set_material_volumes: one (r, g, b) absorption per unit scene length per material (zeros: the material does not absorb)"""
+    sigmas = np.asarray(sigmas, np.float32).reshape(-1, 3)
+    rec = np.zeros(len(sigmas), MATERIAL_VOLUME_DTYPE)
+    rec["sigma"] = sigmas
+    return rec
+
+
+def absorption(color, distance):
+    """sigma of glTF's KHR_materials_volume: the (r, g, b) absorption under which white light has `color` after `distance` scene units,
+    -ln(color) / distance in float64, rounded to float32; colour channels are clamped to [0, 1], a channel of 0 gives the largest finite float"""
+    color = np.clip(np.asarray(color, np.float64), 0.0, 1.0)
+    if not (np.isfinite(distance) and distance > 0):
+        raise ValueError("absorption: the distance must be finite and above 0")
+    with np.errstate(divide="ignore"):
+        sigma = -np.log(color) / float(distance)
+    fmax = float(np.finfo(np.float32).max)
+    return np.where(color == 0.0, fmax, np.minimum(sigma, fmax)).astype(np.float32) + np.float32(0.0)      # (+ 0: -0.0 of a channel of 1 becomes +0.0)
 
 
 class CameraLens(C.Structure):
@@ -259,6 +279,9 @@ PROTOTYPES = {
     "rpt_set_material_models": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "rpt_material_models": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _OUT_SIZE]),
     "rpt_multi_set_material_models": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rpt_set_material_volumes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rpt_material_volumes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _OUT_SIZE]),
+    "rpt_multi_set_material_volumes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "rpt_camera_lens_default": (None, [C.c_void_p]),
     "rpt_set_camera_lens": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rpt_camera_lens_get": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -329,6 +352,9 @@ PROTOTYPES = {
     "rpt_debug_gather_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 6 + [C.POINTER(GatheredInfo)]),
     "rpt_debug_short_batch": (C.c_int, [C.c_void_p, C.c_int]),
     "rpt_debug_force_model_kernels": (C.c_int, [C.c_void_p, C.c_int]),
+    "rpt_debug_force_volume_kernels": (C.c_int, [C.c_void_p, C.c_int]),
+    "rpt_debug_last_shade_variant": (C.c_int, [C.c_void_p, _OUT_U32]),
+    "rpt_debug_volume_transmit": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rpt_debug_lens_rays_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "rpt_debug_lens_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
 }
@@ -472,6 +498,16 @@ class _Handle:
             return
         records = np.ascontiguousarray(records, MATERIAL_MODEL_DTYPE)
         self._call("set_material_models", ptr(records), len(records))
+
+    def set_material_volumes(self, records=None):
+        """rpt_set_material_volumes (rpt_multi_: on every rank): one absorption record per material of the uploaded scene (material_volumes(...), or an array
+        of MATERIAL_VOLUME_DTYPE): a path segment that reaches a MODEL_GLASS surface from its inside is attenuated by exp(-sigma * length) per channel.
+        None: no records.  Between batches; accumulator, rng, moments, statistics and guides stay; upload_scene clears the records."""
+        if records is None:
+            self._call("set_material_volumes", None, 0)
+            return
+        records = np.ascontiguousarray(records, MATERIAL_VOLUME_DTYPE)
+        self._call("set_material_volumes", ptr(records), len(records))
 
     def set_camera_lens(self, lens=None, **fields):
         """rpt_set_camera_lens (rpt_multi_: on every rank): a CameraLens, or its fields by name (tan_half_fov — see hip.tan_half_fov(degrees) —, aperture_radius,
@@ -733,6 +769,14 @@ class Renderer(_Handle):
         self._check(lib().rpt_material_models(self._h, ptr(out), len(out), C.byref(n)))
         return out
 
+    def material_volumes(self):
+        """rpt_material_volumes: the records as set, an array of MATERIAL_VOLUME_DTYPE (empty: none set)"""
+        n = C.c_size_t()
+        self._check(lib().rpt_material_volumes(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, MATERIAL_VOLUME_DTYPE)
+        self._check(lib().rpt_material_volumes(self._h, ptr(out), len(out), C.byref(n)))
+        return out
+
     def camera_lens(self):
         """rpt_camera_lens_get: the lens as set (a CameraLens)"""
         out = CameraLens()
@@ -749,6 +793,20 @@ class Renderer(_Handle):
     def debug_force_model_kernels(self, on=True):
         """rpt_debug_force_model_kernels (test hook): the models variant of the shade stage whatever the records say"""
         self._check(lib().rpt_debug_force_model_kernels(self._h, 1 if on else 0))
+
+    def debug_force_volume_kernels(self, on=True):
+        """rpt_debug_force_volume_kernels (test hook): the volumes variant of the shade stage whatever the records say"""
+        self._check(lib().rpt_debug_force_volume_kernels(self._h, 1 if on else 0))
+
+    def debug_last_shade_variant(self):
+        """rpt_debug_last_shade_variant (test hook): 0 k_shade, 1 k_shade_models, 2 k_shade_volumes — the context's last shade launch"""
+        v = C.c_uint32()
+        self._check(lib().rpt_debug_last_shade_variant(self._h, C.byref(v)))
+        return v.value
+
+    def debug_volume_transmit(self, throughput, sigma, t):
+        """rpt_debug_volume_transmit on the device (test hook): vol_transmit of csrc/k_volume.h, (n, 3), (n, 3), (n,) -> (n, 3) float32"""
+        return _volume_transmit(self._h, 1, throughput, sigma, t)
 
     def shadow_mode(self):
         m = C.c_uint32()
@@ -1062,6 +1120,24 @@ def debug_math_host(op, x, y=None):
     if rc != 0:
         raise RptError(rc, "rpt_debug_math_host")
     return out
+
+
+def _volume_transmit(handle, on_device, throughput, sigma, t):
+    throughput = np.ascontiguousarray(throughput, np.float32).reshape(-1, 3)
+    sigma = np.ascontiguousarray(sigma, np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(t, np.float32).reshape(-1)
+    if not len(throughput) == len(sigma) == len(t):
+        raise ValueError("debug_volume_transmit: one throughput, one sigma and one t per item")
+    out = np.zeros_like(throughput)
+    rc = lib().rpt_debug_volume_transmit(handle, on_device, ptr(throughput), ptr(sigma), ptr(t), len(t), ptr(out))
+    if rc != 0:
+        raise RptError(rc, "rpt_debug_volume_transmit")
+    return out
+
+
+def debug_volume_transmit_host(throughput, sigma, t):
+    """The host build of csrc/k_volume.h vol_transmit inside librpt_hip.so (no GPU needed): (n, 3), (n, 3), (n,) -> (n, 3) float32"""
+    return _volume_transmit(None, 0, throughput, sigma, t)
 
 
 def gather_layout(width, height, world_size, with_moments=True):

@@ -12,7 +12,7 @@ import os
 import numpy as np
 
 from . import _ffi
-from ._ffi import (BVH_NODE_DTYPE, LIGHT_PICK_DTYPE, MATERIAL_DTYPE, MATERIAL_MODEL_DTYPE, PER_VERTEX_DTYPE, RNG_DTYPE, TRIANGLE_DTYPE,
+from ._ffi import (BVH_NODE_DTYPE, LIGHT_PICK_DTYPE, MATERIAL_DTYPE, MATERIAL_MODEL_DTYPE, MATERIAL_VOLUME_DTYPE, PER_VERTEX_DTYPE, RNG_DTYPE, TRIANGLE_DTYPE,
                    TracingConfig, WorldView, ptr)
 
 _lib = None
@@ -22,6 +22,7 @@ PROTOTYPES = {
     "rpt_world_load": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]),
     "rpt_world_load_ex": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     "rpt_world_material_models": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "rpt_world_material_volumes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rpt_skybox_load": (C.c_int, [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rpt_host_free": (None, [C.c_void_p]),
     "rpt_world_from_buffers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
@@ -111,6 +112,8 @@ class World:
         self.n_emissive_triangles = n_emissive_triangles
         # rpt_world_material_models: one record per material (hip.Renderer.set_material_models takes them); all PBR unless from_path(material_models=True) found glass
         self.material_models = np.zeros(len(self.materials), MATERIAL_MODEL_DTYPE)
+        # rpt_world_material_volumes: one absorption record per material (hip.Renderer.set_material_volumes takes them); zeros unless from_path(material_volumes=True) found KHR_materials_volume
+        self.material_volumes = np.zeros(len(self.materials), MATERIAL_VOLUME_DTYPE)
 
     @classmethod
     def _from_handle(cls, handle):
@@ -127,16 +130,20 @@ class World:
                 atlas, v.bvh_max_depth, v.n_emissive_triangles)
         n = C.c_size_t()
         _check(lib().rpt_world_material_models(handle, ptr(w.material_models), len(w.material_models), C.byref(n)))
+        _check(lib().rpt_world_material_volumes(handle, ptr(w.material_volumes), len(w.material_volumes), C.byref(n)))
         lib().rpt_world_free(handle)
         return w
 
     @classmethod
-    def from_path(cls, path, emissive_strength=False, material_models=False):
+    def from_path(cls, path, emissive_strength=False, material_models=False, material_volumes=False):
         """World::from_path (reference: src/asset.rs:55-224).  emissive_strength=True honours
         KHR_materials_emissive_strength instead of the reference's fixed x15 (opt-in: not the reference's behaviour).
-        material_models=True (RPT_LOAD_MATERIAL_MODELS): materials with KHR_materials_transmission get a Glass record in .material_models, ior from KHR_materials_ior."""
+        material_models=True (RPT_LOAD_MATERIAL_MODELS): materials with KHR_materials_transmission get a Glass record in .material_models, ior from KHR_materials_ior.
+        material_volumes=True (RPT_LOAD_MATERIAL_VOLUMES): materials with KHR_materials_volume (a thickness and a finite attenuation distance) get an absorption
+        record in .material_volumes, sigma = -ln(attenuationColor) / attenuationDistance."""
         h = C.c_void_p()
-        _check(lib().rpt_world_load_ex(os.fsencode(path), (1 if emissive_strength else 0) | (2 if material_models else 0), C.byref(h)))
+        flags = (1 if emissive_strength else 0) | (2 if material_models else 0) | (4 if material_volumes else 0)
+        _check(lib().rpt_world_load_ex(os.fsencode(path), flags, C.byref(h)))
         return cls._from_handle(h)
 
     @classmethod
