@@ -4,6 +4,7 @@
 #   oracle/liboracle.so, oracle/liboracle_libm.so   CPU restatement (test infrastructure)
 #   oracle/libmodels_oracle.so                      the same with a material's model at lib.rs:144, and the lens too (test infrastructure; source: tests/models_oracle)
 #   oracle/libvolume_oracle.so                      the models restatement with the absorption rule of rpt_set_material_volumes (test infrastructure; source: tests/volume_oracle)
+#   oracle/liblights_oracle.so                      the volume restatement with the punctual lights of rpt_set_punctual_lights (test infrastructure; source: tests/lights_oracle)
 #   oracle/liblens_oracle.so                        the same with the thin-lens camera at lib.rs:38-51 (test infrastructure; source: tests/lens_oracle)
 # -ffp-contract=off everywhere: the parity contract forbids implicit FMA fusion.
 
@@ -15,7 +16,7 @@ CXX      ?= g++
 
 HOST_SRCS := $(CSRC)/host/host_api.cpp $(CSRC)/host/glb_scene.cpp $(CSRC)/host/bvh_build.cpp \
              $(CSRC)/host/light_table.cpp $(CSRC)/host/bluenoise.cpp $(CSRC)/host/image_io.cpp $(CSRC)/host/textures.cpp $(CSRC)/host/obj_scene.cpp $(CSRC)/host/jpeg_decode.cpp
-HIP_SRCS  := $(CSRC)/rpt_hip.hip $(CSRC)/rpt_scene.hip $(CSRC)/rpt_traverse.hip $(CSRC)/rpt_comm.hip $(CSRC)/rpt_lights.hip $(CSRC)/rpt_bvh.hip $(CSRC)/rpt_denoise.hip $(CSRC)/rpt_moments.hip $(CSRC)/rpt_adaptive.hip $(CSRC)/rpt_models.hip $(CSRC)/rpt_volumes.hip $(CSRC)/rpt_lens.hip $(CSRC)/rpt_debug.hip
+HIP_SRCS  := $(CSRC)/rpt_hip.hip $(CSRC)/rpt_scene.hip $(CSRC)/rpt_traverse.hip $(CSRC)/rpt_comm.hip $(CSRC)/rpt_lights.hip $(CSRC)/rpt_bvh.hip $(CSRC)/rpt_denoise.hip $(CSRC)/rpt_moments.hip $(CSRC)/rpt_adaptive.hip $(CSRC)/rpt_models.hip $(CSRC)/rpt_volumes.hip $(CSRC)/rpt_punctual.hip $(CSRC)/rpt_lens.hip $(CSRC)/rpt_debug.hip
 HIP_OBJS  := $(patsubst $(CSRC)/%.hip,build/%.o,$(HIP_SRCS))
 HIP_DEPS  := $(wildcard $(CSRC)/*.h) $(wildcard $(CSRC)/*.hip) $(wildcard include/rpt/*.h)
 
@@ -29,7 +30,7 @@ HIPFLAGS := --offload-arch=gfx950 -std=c++20 -O3 -fPIC -ffp-contract=off -fno-fa
 # -fno-slp-vectorize: the packed f32 operations the SLP vectorizer forms issue in the time of two plain ones on gfx950 and cost v_mov
 # shuffles and registers (profiles/r03_slp.txt)
 
-all: host oracle hip fake_rccl models_oracle lens_oracle volume_oracle
+all: host oracle hip fake_rccl models_oracle lens_oracle volume_oracle lights_oracle
 
 host: $(LIBDIR)/librpt_host.so
 oracle: oracle/liboracle.so oracle/liboracle_libm.so
@@ -64,6 +65,12 @@ volume_oracle: oracle/libvolume_oracle.so
 oracle/libvolume_oracle.so: tests/volume_oracle/volume_oracle.cpp tests/lens_oracle/lens_camera.h oracle/rpt_oracle.cpp $(CSRC)/rpt_math.h $(CSRC)/rpt_fastdiv.h $(CSRC)/rpt_rcp.h $(CSRC)/rpt_math_consts.h include/rpt/shared_structs.h
 	$(CXX) $(ORACLE_FLAGS) -shared -Wl,-Bsymbolic -o $@ tests/volume_oracle/volume_oracle.cpp
 
+# test infrastructure: the volume restatement with the punctual lights of rpt_set_punctual_lights (tests/lights_oracle/lights_oracle.cpp includes
+# oracle/rpt_oracle.cpp textually), built like volume_oracle
+lights_oracle: oracle/liblights_oracle.so
+oracle/liblights_oracle.so: tests/lights_oracle/lights_oracle.cpp tests/lens_oracle/lens_camera.h oracle/rpt_oracle.cpp $(CSRC)/rpt_math.h $(CSRC)/rpt_fastdiv.h $(CSRC)/rpt_rcp.h $(CSRC)/rpt_math_consts.h include/rpt/shared_structs.h
+	$(CXX) $(ORACLE_FLAGS) -shared -Wl,-Bsymbolic -o $@ tests/lights_oracle/lights_oracle.cpp
+
 # the fingerprint of the device-side sources is compiled in (rpt_build_fingerprint): bench.py reports PMC-derived figures only for the
 # sources the LOADED library was built from, and says so when the library is older than the source tree
 # one object per translation unit, built in PARALLEL (the recipe below re-invokes make with one job per unit): the walk kernels (rpt_traverse.hip)
@@ -86,4 +93,4 @@ tests/fake_rccl/librccl_fake.so: tests/fake_rccl/fake_rccl.cpp
 clean:
 	rm -f $(LIBDIR)/*.so oracle/*.so tests/fake_rccl/*.so
 
-.PHONY: all host oracle hip fake_rccl models_oracle lens_oracle volume_oracle clean
+.PHONY: all host oracle hip fake_rccl models_oracle lens_oracle volume_oracle lights_oracle clean

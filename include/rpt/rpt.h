@@ -381,6 +381,53 @@ typedef struct rpt_material_volume { float sigma[3]; uint32_t reserved; } rpt_ma
 int rpt_set_material_volumes(rpt_ctx *ctx, const rpt_material_volume *volumes, size_t n);   /* NULL, 0: none */
 int rpt_material_volumes(rpt_ctx *ctx, rpt_material_volume *out, size_t capacity, size_t *n_out);
 int rpt_multi_set_material_volumes(rpt_multi *m, const rpt_material_volume *volumes, size_t n);   /* on every rank */
+/* Punctual lights: point, spot and directional (glTF's KHR_lights_punctual), sampled by next-event estimation.  Opt-in; no reference equivalent (its only
+ * emitters are emissive triangles — the alias table of light_pick.rs — and the sky).  One record per light, 64 bytes.  The lights act ONLY inside
+ * sample_direct_lighting: NEE modes 1 and 2, at a bounce whose sampled lobe is the diffuse reflection.  A delta light cannot be met by a BSDF sample, so with
+ * nee = 0 the lights add nothing and the kernels launched are the ones launched without this call.
+ * Shares: with n lights the effective share q of the first light draw is 1 when the scene's table is the sentinel (no emissive triangle; pick_share is then
+ * ignored), else pick_share, which must lie in (0, 1) exclusive; q = 0 when n = 0.
+ * The four draws l1, l2, p1, p2 of light_pick.rs are made exactly when NEE runs and there is a mesh light or a punctual light: no dimension moves and
+ * rpt_set_config's budget is unchanged.
+ *   l1 < q   a punctual light j = min(f2u32_sat((l1 / q) * (float)n), n - 1), with pick pdf q / (float)n
+ *   else     u = (l1 - q) / (1 - q) takes l1's place in the reference's alias pick (an over-run is clamped and counted as it is without lights) and
+ *            light_pick_pdf becomes light_pick_pdf * (1 - q), in the light sample and in the carried MIS term of calculate_bsdf_mis_contribution alike.
+ *            Over the sentinel table (q = 1) the only such draw is l1 == 1.0: nothing is picked, nothing evaluated and nothing counted.
+ * Every quotient is an IEEE f32 division; with q = 0 this is the arithmetic without lights bit for bit (u = l1, the pdf times 1.0f).
+ * The unoccluded term of a punctual pick (csrc/k_punctual.h punctual_sample states the f32 operation order):
+ *   point, spot   v = position - hit, d = |v|, L = v / d; shadow ray from hit + L * EPS with max_t = d - 2 EPS, as the reference's; E = intensity * (spot / (d * d));
+ *                 spot = 1 for a point light, and for a spot light a = clamp(dot(direction, -L) * angle_scale + angle_offset, 0, 1), spot = a * a
+ *   directional   L = -direction, max_t = 1e6, E = intensity
+ *   then          attenuation and bsdf_pdf are the surface's own diffuse evaluate / pdf (Lambertian::evaluate for a Lambertian record); if bsdf_pdf > 0:
+ *                 direct = (attenuation * E) / pick_pdf — the weight is 1 in BOTH NEE modes — and contribution = throughput * direct
+ * The elision rule is unchanged (a mask_nan term of zero: the ray is not queued); rpt_stats.shadow_rays and shadow_rays_elided count a punctual pick as they
+ * count any NEE evaluation.  In MIS mode a punctual pick writes the carry "no triangle": an emitter met by the next BSDF sample then adds nothing, which is
+ * the reference's one-sample rule (a BSDF hit counts only on the picked light, divided by that pick's pdf) and keeps the estimator unbiased.
+ * Limits: no light is sampled through Glass (NEE never runs there): a glass object casts an opaque shadow from these lights and there are no caustics; no light
+ * radius, so no soft shadows; no `range` attribute; the denoiser's guides are unchanged; the lights are not in rpt_world_save's .rptscene cache and not in the
+ * host mirror rpt_trace_gpu.  glTF gives point and spot intensities in candela and directional ones in lux (683 lm/W): scaling to scene units is the caller's.
+ * rpt_set_punctual_lights: callable after rpt_upload_scene, between any two batches (it waits for what is enqueued); cleared by rpt_upload_scene, kept by
+ * rpt_set_config; the caller resets the accumulator, as for the lens; n <= 65535; (NULL, 0): none.  RPT_EINVAL, with the context and the lights as they were
+ * and the message naming the record, for a type above 2; a non-finite position, direction or intensity; a negative intensity; a direction with
+ * |len^2 - 1| > 1e-3 on a spot or directional record; a non-finite angle_scale or angle_offset; reserved != 0; NULL with n != 0 or the reverse; a pick_share
+ * outside (0, 1), or NaN, while the scene has emissive triangles (and n != 0); a call before a scene.
+ * rpt_punctual_lights: the records as set (n_out = 0: none) and the effective share q; out and effective_share_out nullable, capacity in records.
+ * Checked: the device against a CPU restatement of the rule word for word; that restatement against an independent float64 reading of this text within
+ * 8 x 1.714e-3 relative per sample, measured 0.03-0.13 % of the samples flagged as undecidable against a cap of 1 % (tests/f64_lights.py).  Measured on one MI355X, 32-spp MIS batches
+ * (profiles/r23_punctual_lights.txt): the variant with no lights costs x 1.002 (DarkCornell 1024^2, 18.69 -> 18.72 ms) and x 1.009 (VeachMIS 1080p,
+ * 28.41 -> 28.66 ms) of a batch; a context without lights launches what it launched before. */
+enum { RPT_LIGHT_POINT = 0, RPT_LIGHT_SPOT = 1, RPT_LIGHT_DIRECTIONAL = 2 };
+typedef struct rpt_punctual_light {
+    uint32_t type;
+    float position[3];      /* point, spot; ignored for directional */
+    float direction[3];     /* spot, directional: the way the light shines, unit length, used AS GIVEN */
+    float intensity[3];     /* point/spot: radiant intensity r g b (per steradian); directional: irradiance on a surface facing the light */
+    float angle_scale, angle_offset;   /* spot: glTF's 1 / max(0.001, cos inner - cos outer) and -cos outer * scale */
+    uint32_t reserved[4];   /* 0 */
+} rpt_punctual_light;
+int rpt_set_punctual_lights(rpt_ctx *ctx, const rpt_punctual_light *lights, size_t n, float pick_share);  /* NULL, 0: none */
+int rpt_punctual_lights(rpt_ctx *ctx, rpt_punctual_light *out, size_t capacity, size_t *n_out, float *effective_share_out);
+int rpt_multi_set_punctual_lights(rpt_multi *m, const rpt_punctual_light *lights, size_t n, float pick_share);   /* on every rank */
 /* Thin-lens camera.  Opt-in; the reference's camera is a pinhole with a fixed 90 degree HORIZONTAL field of view (kernels/src/lib.rs:38-51) and
  * rpt_tracing_config carries a position and two angles only.  The lens replaces lib.rs:38-51 and nothing else of trace_pixel (csrc/k_lens.h states the f32
  * operations): the film coordinates are scaled by tan_half_fov before the direction is normalized, and with aperture_radius > 0 the ray leaves a point of

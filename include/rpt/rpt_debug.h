@@ -199,7 +199,8 @@ int rpt_debug_force_model_kernels(rpt_ctx *ctx, int on);
 
 /* Test aid: on != 0 makes the render calls of this context launch the volumes variant of the shade stage (rpt_set_material_volumes) whatever the records
  * say — with no records, or with all-zero ones, it must give the models variant's image and counters bit for bit.
- * rpt_debug_last_shade_variant: which build of the shade stage the context's last shade launch was — 0 k_shade, 1 k_shade_models, 2 k_shade_volumes. */
+ * rpt_debug_last_shade_variant: which build of the shade stage the context's last shade launch was — 0 k_shade, 1 k_shade_models, 2 k_shade_volumes,
+ * 3 k_shade_punctual. */
 int rpt_debug_force_volume_kernels(rpt_ctx *ctx, int on);
 int rpt_debug_last_shade_variant(rpt_ctx *ctx, uint32_t *variant_out);
 
@@ -215,6 +216,25 @@ int rpt_debug_volume_transmit(rpt_ctx *ctx, int on_device, const float *throughp
 int rpt_debug_lens_rays_host(const rpt_tracing_config *config, const rpt_camera_lens *lens, const uint32_t *pixels_xy, const uint32_t *keys, size_t n,
                              float *origins_out, float *dirs_out);
 int rpt_debug_lens_rays(rpt_ctx *ctx, const uint32_t *pixels_xy, const uint32_t *keys, size_t n, float *origins_out, float *dirs_out);
+
+/* Test aid: on != 0 makes the render calls of this context launch the punctual variant of the shade stage (rpt_set_punctual_lights) under NEE modes 1 and 2
+ * whatever the lights say — with no lights it must give the other variants' image and counters bit for bit.  nee = 0 keeps the other variants.
+ * rpt_debug_last_shade_variant then reports 3 (k_shade_punctual). */
+int rpt_debug_force_punctual_kernels(rpt_ctx *ctx, int on);
+
+/* The arithmetic of rpt_set_punctual_lights alone (csrc/k_punctual.h punctual_sample) on n_items items against n_lights host records and a share q: hits_xyz 3
+ * floats per item, l1 one; out per item: j_out one word, dirs_out (L) 3 floats, max_t_out one, e_out (E) 3 floats, pick_pdf_out one.  The records are
+ * converted as the setter converts them.  rpt_debug_punctual_sample_host: the host build of the header — no device needed.  rpt_debug_punctual_sample: the
+ * same header through a device kernel of the context's device.  RPT_EINVAL for null pointers, n_lights == 0, a q outside (0, 1] and records that
+ * rpt_set_punctual_lights refuses (the hooks and the setter share one check).
+ * rpt_debug_punctual_lights_check: that check alone, no context and no device needed — everything the setter refuses except a call before a scene;
+ * scene_has_emitters stands for the scene (non-zero: the light table is not the sentinel, so pick_share must lie in (0, 1)); message_out (nullable,
+ * capacity bytes, zero-terminated) receives the message the setter would leave in the context.  RPT_OK or RPT_EINVAL. */
+int rpt_debug_punctual_lights_check(const rpt_punctual_light *lights, size_t n, float pick_share, int scene_has_emitters, char *message_out, size_t capacity);
+int rpt_debug_punctual_sample_host(const rpt_punctual_light *lights, size_t n_lights, float q, const float *hits_xyz, const float *l1, size_t n_items,
+                                   uint32_t *j_out, float *dirs_out, float *max_t_out, float *e_out, float *pick_pdf_out);
+int rpt_debug_punctual_sample(rpt_ctx *ctx, const rpt_punctual_light *lights, size_t n_lights, float q, const float *hits_xyz, const float *l1, size_t n_items,
+                              uint32_t *j_out, float *dirs_out, float *max_t_out, float *e_out, float *pick_pdf_out);
 
 #ifdef __cplusplus
 }

@@ -72,6 +72,17 @@ int rpt_world_material_models(const rpt_world *world, rpt_material_model *out, s
  * cache, which does not carry them); out nullable, capacity in records, n_out = the material count.  The host mirror rpt_trace_gpu does not apply them. */
 #define RPT_LOAD_MATERIAL_VOLUMES 4u
 int rpt_world_material_volumes(const rpt_world *world, rpt_material_volume *out, size_t capacity, size_t *n_out);
+/* RPT_LOAD_PUNCTUAL_LIGHTS (off by default): the lights of glTF's KHR_lights_punctual — the root extension's `lights`, one record (rpt.h rpt_set_punctual_lights)
+ * per NODE that refers to one, in the order the nodes are walked, so a light referred to twice comes out twice.  Each takes its node's world transform:
+ * position = the translation, direction = the node's -Z axis, normalised in double and rounded once (a scaled parent does not lengthen it), both with the
+ * reference's (x, z, y) swap that the meshes take.  intensity = color * intensity AS WRITTEN: glTF counts candela (point, spot) and lux (directional) at
+ * 683 lm/W, scaling to the scene's units is the caller's.  A spot light's cone by glTF's formula, angle_scale = 1 / max(0.001, cos inner - cos outer) and
+ * angle_offset = -cos outer * angle_scale (defaults 0 and pi / 4), in double, rounded once.  `range` is not read.  A light the setter would refuse for what the file says (a spot or
+ * directional light under a node whose -Z axis has no length, anything not finite, a negative intensity) is left out.  The buffers of the world do not depend on
+ * the flag.  rpt_world_punctual_lights: the records (none for a world loaded without the flag, from buffers, from an OBJ or from the .rptscene cache, which
+ * does not carry them); out nullable, capacity in records, n_out = the light count.  The host mirror rpt_trace_gpu does not apply them. */
+#define RPT_LOAD_PUNCTUAL_LIGHTS 8u
+int rpt_world_punctual_lights(const rpt_world *world, rpt_punctual_light *out, size_t capacity, size_t *n_out);
 /* load_dynamic_image + dynamic_image_to_cpu_buffer (src/asset.rs:238-273): a skybox file (.png, Radiance .hdr) as the
  * reference's CPU path sees it — quantised to 8 bits per channel, alpha 1 — as width*height float RGBA, the layout
  * rpt_upload_scene takes.  Caller frees with rpt_host_free. */

@@ -53,6 +53,9 @@ TRIANGLE_DTYPE = np.dtype([("v0", "<u4"), ("v1", "<u4"), ("v2", "<u4"), ("materi
 RNG_DTYPE = np.dtype([("n", "<u4"), ("offset", "<u4")])
 MATERIAL_MODEL_DTYPE = np.dtype([("model", "<u4"), ("ior", "<f4"), ("reserved", "<u4", 2)])      # rpt_material_model (include/rpt/rpt.h)
 MATERIAL_VOLUME_DTYPE = np.dtype([("sigma", "<f4", 3), ("reserved", "<u4")])      # rpt_material_volume
+PUNCTUAL_LIGHT_DTYPE = np.dtype([("type", "<u4"), ("position", "<f4", 3), ("direction", "<f4", 3), ("intensity", "<f4", 3), ("angle_scale", "<f4"),
+                                 ("angle_offset", "<f4"), ("reserved", "<u4", 4)])      # rpt_punctual_light
+assert PUNCTUAL_LIGHT_DTYPE.itemsize == 64
 assert MATERIAL_DTYPE.itemsize == 96 and PER_VERTEX_DTYPE.itemsize == 64 and LIGHT_PICK_DTYPE.itemsize == 28
 assert BVH_NODE_DTYPE.itemsize == 32 and TRIANGLE_DTYPE.itemsize == 16 and RNG_DTYPE.itemsize == 8
 

@@ -280,7 +280,57 @@ struct Gather {
     std::vector<rpt_triangle> indices;
     bool used_default_material = false;
     uint32_t default_material_index = 0;
+    bool want_lights = false;                       /* RPT_LOAD_PUNCTUAL_LIGHTS */
+    std::vector<rpt_punctual_light> lights;         /* one per node reference of KHR_lights_punctual, in walk order */
 };
+
+/* RPT_LOAD_PUNCTUAL_LIGHTS: the light a node refers to (extensions.KHR_lights_punctual.light, an index into the root extension's `lights`) under the node's world
+ * transform: position = its translation, direction = its -Z axis normalised (in double, rounded once), both with the (x, z, y) swap the meshes take;
+ * intensity = color * intensity as written; the cone by glTF's formula.  A reference that names no light, or a type that is none of the three, adds nothing;
+ * neither does a light whose record rpt_set_punctual_lights would refuse for what the FILE says — a node whose world -Z axis has no length (a zero scale) under
+ * a spot or directional light, a transform, colour, intensity or cone that is not finite, a negative colour * intensity: the setter names records, not nodes,
+ * so such a light is dropped here instead of poisoning the array.  A colour that is not three numbers is the default, (1, 1, 1). */
+void gather_light(const Glb &g, const JValue &node, const M4 &world, Gather &out) {
+    const JValue *next = node.get("extensions");
+    const JValue *ref = next ? next->get("KHR_lights_punctual") : nullptr;
+    const JValue *rext = g.root->get("extensions");
+    const JValue *rl = rext ? rext->get("KHR_lights_punctual") : nullptr;
+    const JValue *lights = rl ? rl->get("lights") : nullptr;
+    if (!ref || !lights || lights->kind != JValue::Arr) return;
+    const double index = ref->number_or("light", -1.0);
+    if (!(index >= 0.0) || index != std::floor(index) || index >= (double)lights->arr.size()) return;
+    const JValue &jl = *lights->arr[(size_t)index];
+    const JValue *type = jl.get("type");
+    if (!type || type->kind != JValue::Str) return;
+    rpt_punctual_light l{};
+    if (type->str == "point") l.type = RPT_LIGHT_POINT;
+    else if (type->str == "spot") l.type = RPT_LIGHT_SPOT;
+    else if (type->str == "directional") l.type = RPT_LIGHT_DIRECTIONAL;
+    else return;
+    double colour[3] = {1.0, 1.0, 1.0};
+    if (const JValue *c = jl.get("color"); c && c->kind == JValue::Arr && c->arr.size() == 3 && c->arr[0]->kind == JValue::Num && c->arr[1]->kind == JValue::Num &&
+                                            c->arr[2]->kind == JValue::Num)
+        for (int k = 0; k < 3; ++k) colour[k] = c->arr[k]->num;
+    const double intensity = jl.number_or("intensity", 1.0);
+    for (int k = 0; k < 3; ++k) l.intensity[k] = (float)(colour[k] * intensity);
+    const double z[3] = {world.m[2][0], world.m[2][1], world.m[2][2]};
+    const double len = std::sqrt(z[0] * z[0] + z[1] * z[1] + z[2] * z[2]);
+    const double d[3] = {-z[0] / len, -z[1] / len, -z[2] / len};
+    if (l.type != RPT_LIGHT_POINT && !(len > 0.0 && std::isfinite(len))) return;
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(l.intensity[k]) || l.intensity[k] < 0.0f || !std::isfinite(world.m[3][k])) return;
+    if (l.type != RPT_LIGHT_DIRECTIONAL) { l.position[0] = world.m[3][0]; l.position[1] = world.m[3][2]; l.position[2] = world.m[3][1]; }
+    if (l.type != RPT_LIGHT_POINT) { l.direction[0] = (float)d[0]; l.direction[1] = (float)d[2]; l.direction[2] = (float)d[1]; }
+    if (l.type == RPT_LIGHT_SPOT) {
+        const JValue *spot = jl.get("spot");
+        const double inner = spot ? spot->number_or("innerConeAngle", 0.0) : 0.0, outer = spot ? spot->number_or("outerConeAngle", 0.7853981633974483) : 0.7853981633974483;
+        const double scale = 1.0 / std::max(0.001, std::cos(inner) - std::cos(outer));
+        l.angle_scale = (float)scale;
+        l.angle_offset = (float)(-std::cos(outer) * scale);
+        if (!std::isfinite(l.angle_scale) || !std::isfinite(l.angle_offset)) return;
+    }
+    out.lights.push_back(l);
+}
 
 bool walk_node(const Glb &g, int node_index, const M4 &trs, Gather &out, int depth) {
     const JValue *nodes = g.arr("nodes"), *meshes = g.arr("meshes");
@@ -394,6 +444,7 @@ bool walk_node(const Glb &g, int node_index, const M4 &trs, Gather &out, int dep
                 }
             }
     }
+    if (out.want_lights) gather_light(g, node, new_trs, out);
     if (const JValue *children = node.get("children"))
         for (auto &c : children->arr)
             if (!walk_node(g, (int)c->num, new_trs, out, depth + 1)) return false;
@@ -518,6 +569,7 @@ bool load_glb(const char *path, World &out, uint32_t flags) {
     size_t n_file_materials = materials ? materials->arr.size() : 0;
     Gather ga;
     ga.default_material_index = (uint32_t)n_file_materials;
+    ga.want_lights = (flags & RPT_LOAD_PUNCTUAL_LIGHTS) != 0u;
 
     const JValue *scenes = g.arr("scenes");
     int scene_index = (int)g.root->number_or("scene", 0);
@@ -528,6 +580,7 @@ bool load_glb(const char *path, World &out, uint32_t flags) {
         for (auto &r : roots->arr)
             if (!walk_node(g, (int)r->num, identity(), ga, 0)) { set_error("GLB node/mesh data invalid"); return false; }
     if (ga.indices.empty()) { set_error("GLB contains no triangles"); return false; }
+    out.punctual_lights = ga.lights;
 
     /* materials (asset.rs:135-175) */
     out.materials.assign(n_file_materials + (ga.used_default_material ? 1 : 0), rpt_material_data{});

@@ -172,6 +172,17 @@ int rpt_world_material_volumes(const rpt_world *world, rpt_material_volume *out,
     return 0;
 }
 
+int rpt_world_punctual_lights(const rpt_world *world, rpt_punctual_light *out, size_t capacity, size_t *n_out) {
+    if (!world || !n_out) { set_error("null argument"); return RPT_EINVAL; }
+    const World &w = world->w;
+    *n_out = w.punctual_lights.size();
+    if (out) {
+        if (capacity < w.punctual_lights.size()) { set_error("rpt_world_punctual_lights: capacity below the light count"); return RPT_EINVAL; }
+        for (size_t i = 0; i < w.punctual_lights.size(); ++i) out[i] = w.punctual_lights[i];
+    }
+    return 0;
+}
+
 void rpt_world_free(rpt_world *world) { delete world; }
 
 int rpt_bvh_build(const float *vertices_xyzw, size_t n_vertices, rpt_triangle *triangles, size_t n_triangles,

@@ -51,6 +51,7 @@ struct World {
     uint32_t atlas_w = 0, atlas_h = 0;
     uint32_t max_depth = 0, n_emissive = 0;
     std::vector<rpt_material_model> material_models;   /* one per material, every one PBR unless the loader was asked (RPT_LOAD_MATERIAL_MODELS); not in the .rptscene cache */
+    std::vector<rpt_punctual_light> punctual_lights;   /* KHR_lights_punctual, one per node reference, only when the loader was asked (RPT_LOAD_PUNCTUAL_LIGHTS); not in the .rptscene cache */
     std::vector<rpt_material_volume> material_volumes; /* one per material, every one zero unless the loader was asked (RPT_LOAD_MATERIAL_VOLUMES); not in the .rptscene cache */
 };
 

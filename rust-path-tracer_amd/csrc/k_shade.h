@@ -34,6 +34,7 @@
 
 #include "k_bsdf_extra.h"        /* Lambertian and Glass: what shade_slot<.., MODELS> constructs in place of the PBR BSDF */
 #include "k_volume.h"            /* vol_transmit: what shade_slot<.., VOLUMES> multiplies the throughput by at a Glass hit from the inside */
+#include "k_punctual.h"          /* punctual_sample: the light shade_slot<.., PUNCTUAL> picks when the first light draw falls below the lights' share */
 
 /* ---- CPU-polyfill image sampling (shared_structs/src/image_polyfill.rs:32-55) ----------------------------------------------------------
  * sample_raw: `coord.x as usize % width as usize` — the i32 sign-extends to 64 bits, then an UNSIGNED 64-bit remainder.  Written out that
@@ -197,15 +198,22 @@ __device__ __forceinline__ Mat load_material(const DevScene &sc, uint32_t index)
 /* VOLUMES (rpt_set_material_volumes; instantiated in rpt_volumes.hip only, with MODELS): `volumes` holds one record per material, (sigma r, g, b, -), or is null
  * for "no material absorbs".  At a hit of a Glass material from its inside — dot(normal, view) < 0 with the normal handed to glass_sample — the throughput is
  * multiplied by vol_transmit(sigma, hit_t) before the sample's own factor (k_volume.h); nothing else of the stage changes. */
+/* PUNCTUAL (rpt_set_punctual_lights; instantiated in rpt_punctual.hip only, with MODELS and VOLUMES): pl_lights, pl_n, pl_q are the lights, their count n and the
+ * effective share q of the first light draw (n == 0: q == 0, the arithmetic without lights) — three plain arguments: a struct with a default argument left
+ * the other builds of the stage a temporary that cost them their register allocation, bit-identical results but not the same instruction stream.  With n > 0
+ * the four light draws are made whether or not the scene has an emissive triangle; l1 < q picks a punctual light (k_punctual.h) — weight 1 in both NEE
+ * modes, carry code 0xffffffff — and otherwise (l1 - q) / (1 - q) takes l1's place in the alias pick and the pick pdf is multiplied by 1 - q, here and in
+ * the carried MIS term.  Everything new sits behind `if (PUNCTUAL)`. */
 #define RPT_DEV_MODEL_LAMBERTIAN 1u
 #define RPT_DEV_MODEL_GLASS 2u
-template <int NEE, bool TEXTURED, bool COMPACT, bool MODELS = false, bool VOLUMES = false>
+template <int NEE, bool TEXTURED, bool COMPACT, bool MODELS = false, bool VOLUMES = false, bool PUNCTUAL = false>
 __device__ __forceinline__ void shade_slot(const DevScene &sc, const DevState &st, const DevQueues &q, const DevConfig &cfg, DevStats *stats,
                                            uint32_t slot, float2 hw, bool active, bool &to_sky, bool &emit_shadow, float4 &sh_o, float4 &sh_d,
                                            float4 &sh_c, bool first /* iteration 0 of the call: every path is a first path (k_path.h) */,
                                            uint32_t n_samples, bool &elided /* an NEE evaluation whose shadow ray decides nothing: not queued */,
                                            bool last_iteration /* wave-uniform: every path of this launch is at its last bounce and has a radiance record */,
-                                           const uint4 *models = nullptr, const float4 *volumes = nullptr) {
+                                           const uint4 *models = nullptr, const float4 *volumes = nullptr,
+                                           const float4 *pl_lights = nullptr, uint32_t pl_n = 0u, float pl_q = 0.0f) {
     const uint32_t hit_tri = __float_as_uint(hw.y);
     /* wave-uniform: live paths of this batch keep no radiance record (DevQueues::implicit_zero — their radiance is +0 and they owe nothing): a continuing path
      * writes none, a path that ends with nothing added ends as HIT_DONE_ZERO, one that ends on an emitter's front writes 0 + its term and never loads */
@@ -310,7 +318,8 @@ __device__ __forceinline__ void shade_slot(const DevScene &sc, const DevState &s
                         if (tri_index == light_tri) {                                    /* light_pick.rs:185 */
                             const float4 *lr = sc.light_rec + 8u * (code >> 1) + (side_b ? 4u : 0u);
                             const float light_area = side_b ? e.triangle_area_b : e.triangle_area_a;
-                            const float light_pick_pdf = side_b ? e.triangle_pick_pdf_b : e.triangle_pick_pdf_a;
+                            float light_pick_pdf = side_b ? e.triangle_pick_pdf_b : e.triangle_pick_pdf_a;
+                            if (PUNCTUAL) light_pick_pdf = light_pick_pdf * (1.0f - pl_q);          /* (the mesh pick was made with what the punctual lights left) */
                             F3 light_normal = f3(lr[0].w, lr[1].w, lr[2].w);
                             float cos_theta = dot3(light_normal, -rd);                  /* last sampled_direction == rd */
                             float light_pdf = cos_theta <= 0.0f ? 0.0f : rptm::powi2(hit_t) / (light_area * cos_theta);
@@ -495,6 +504,96 @@ __device__ __forceinline__ void shade_slot(const DevScene &sc, const DevState &s
 
                 /* ---- next-event estimation set-up (light_pick.rs:100-173) ---- */
                 if (nee && !spec) {
+                    if (PUNCTUAL) {
+                        /* rpt_set_punctual_lights: the whole set-up again, with the lights in front of the alias pick (the text below is the one every other
+                         * build of the stage compiles, untouched).  The four draws are made when there is a mesh light or a punctual light. */
+                        if (sc.no_lights && pl_n == 0u) {
+                            if (NEE == RPT_NEE_MIS && !last) st.mis_a[slot] = make_float4(__uint_as_float(0xffffffffu), 0, 0, 0);
+                        } else {
+                            const float l1 = rng.next(), l2 = rng.next();
+                            const float p1 = rng.next(), p2 = rng.next();       /* (drawn before the pick here, after it in the twin: the same dimensions) */
+                            const bool punctual = l1 < pl_q;                 /* (no lights: q == 0) */
+                            const bool evaluated = punctual || !sc.no_lights;   /* not: l1 == 1.0 over a share of 1 — nothing to pick, evaluate or count */
+                            F3 light_direction = f3s(0.0f), direct = f3s(0.0f);
+                            float max_t = 0.0f;
+                            uint32_t carry = 0xffffffffu;                    /* "no triangle": an emitter the next BSDF sample meets adds nothing */
+                            if (punctual) {
+                                const PunctualSample ps = punctual_sample(hit, l1, pl_lights, pl_n, pl_q);
+                                light_direction = ps.L;
+                                max_t = ps.max_t;
+                                /* PBR::evaluate(view, n, L, Diffuse) and PBR::pdf(.., Diffuse), as for a mesh light */
+                                float w_e = bsdf.specular_weight(view, normal);
+                                float cos_e = rptm::fmaxr(dot3(normal, light_direction), 0.0f);
+                                F3 h_e = norm3(view + light_direction);
+                                F3 ks_e = bsdf.ks_of(view, h_e);
+                                F3 attenuation = bsdf.diffuse_term(cos_e, w_e, ks_e);
+                                float bsdf_pdf = cos_e / RPT_PI_F;
+                                if (MODELS && lambert) lambertian_evaluate(bsdf.albedo, normal, light_direction, attenuation, bsdf_pdf);
+                                if (bsdf_pdf > 0.0f) direct = (attenuation * ps.E) / ps.pick_pdf;      /* weight 1 in both NEE modes: no BSDF sample meets a delta light */
+                            } else if (evaluated) {
+                                /* the alias pick below with u in l1's place and the pick pdf times what the lights leave (q == 0: l1 and 1.0f, bit for bit) */
+                                const float keep = 1.0f - pl_q;
+                                const float u = (l1 - pl_q) / keep;
+                                uint32_t idx = rptm::f2u32_sat(u * (float)sc.n_light_pick);
+                                if (idx >= sc.n_light_pick) {
+                                    idx = sc.n_light_pick - 1u;
+                                    atomicAdd(&stats->light_index_clamped, 1ull);
+                                }
+                                const rpt_light_pick_entry e = sc.light_pick[idx];
+                                const bool pick_a = l2 < e.ratio;
+                                const float light_area = pick_a ? e.triangle_area_a : e.triangle_area_b;
+                                const float light_pick_pdf = (pick_a ? e.triangle_pick_pdf_a : e.triangle_pick_pdf_b) * keep;
+                                const float4 *lr = sc.light_rec + 8u * idx + (pick_a ? 0u : 4u);
+                                const float4 lra = lr[0], lrb = lr[1], lrc = lr[2], lre = lr[3];
+                                const F3 light_normal = f3(lra.w, lrb.w, lrc.w);
+                                const F3 light_emission = xyz4(lre);
+                                const float r1_sqrt = rptm::sqrtr(p1);
+                                const F3 light_point = (1.0f - r1_sqrt) * xyz4(lra) + (r1_sqrt * (1.0f - p2)) * xyz4(lrb) +
+                                                       (r1_sqrt * p2) * xyz4(lrc);
+                                const F3 unorm = light_point - hit;
+                                const float light_distance = len3(unorm);
+                                light_direction = unorm / light_distance;
+                                max_t = light_distance - RPT_EPS * 2.0f;
+                                carry = 2u * idx + (pick_a ? 0u : 1u);
+                                float cos_l = dot3(light_normal, -light_direction);
+                                float light_pdf = cos_l <= 0.0f ? 0.0f : rptm::powi2(light_distance) / (light_area * cos_l);
+                                if (light_pdf > 0.0f) {
+                                    float w_e = bsdf.specular_weight(view, normal);
+                                    float cos_e = rptm::fmaxr(dot3(normal, light_direction), 0.0f);
+                                    F3 h_e = norm3(view + light_direction);
+                                    F3 ks_e = bsdf.ks_of(view, h_e);
+                                    F3 attenuation = bsdf.diffuse_term(cos_e, w_e, ks_e);
+                                    float bsdf_pdf = cos_e / RPT_PI_F;
+                                    if (MODELS && lambert) lambertian_evaluate(bsdf.albedo, normal, light_direction, attenuation, bsdf_pdf);
+                                    if (bsdf_pdf > 0.0f) {
+                                        float weight = 1.0f;
+                                        if (NEE == RPT_NEE_MIS) {
+                                            float q1 = light_pdf * light_pdf;
+                                            weight = q1 / (q1 + bsdf_pdf * bsdf_pdf);
+                                        }
+                                        direct = (attenuation * light_emission * weight / light_pdf) / light_pick_pdf;
+                                    }
+                                }
+                            }
+                            /* the tail of the set-up below: the elision rule, the queue entry, the carry */
+                            const F3 contribution = throughput * direct;
+                            const F3 term = mask_nan3(contribution);
+                            const bool decides = term.x != 0.0f || term.y != 0.0f || term.z != 0.0f;
+                            elided = evaluated && !decides;
+                            const F3 so = hit + light_direction * RPT_EPS;
+                            emit_shadow = decides;
+                            sh_o = make_float4(so.x, so.y, so.z, max_t);
+                            sh_d = make_float4(light_direction.x, light_direction.y, light_direction.z, 0.0f);
+                            sh_c = make_float4(contribution.x, contribution.y, contribution.z, 0.0f);
+                            if (NEE == RPT_NEE_MIS && !last) {
+                                const bool mesh = carry != 0xffffffffu;          /* (a carry without a triangle is the sentinel's: zeros) */
+                                st.mis_a[slot] = make_float4(__uint_as_float(carry), mesh ? throughput.x : 0.0f, mesh ? throughput.y : 0.0f, mesh ? throughput.z : 0.0f);
+                            }
+                        }
+                    } else
+                    /* (The alias pick from here to the end of this block has a TWIN in the `if (PUNCTUAL)` block above, with u in l1's place and the pick pdf
+                     * times 1 - q: a change to the NEE set-up is made in both.  The twin keeps this text, and with it the instruction streams of the
+                     * other builds, as they were; the forced-variant tests hold the two to the same bytes.) */
                     if (sc.no_lights) {
                         /* sentinel: DirectLightSample::default() — zero contribution, zeroed carry */
                         if (NEE == RPT_NEE_MIS && !last) st.mis_a[slot] = make_float4(__uint_as_float(0xffffffffu), 0, 0, 0);
@@ -691,12 +790,15 @@ __device__ __forceinline__ void count_elided(uint32_t *lds_counter, bool elided)
  * (PBRTest 69.3 -> 67.4 per 4).  The NEE variants spill when pushed (72 VGPRs: 20-44 bytes of scratch; packed: VeachMIS shade 44.0 -> 48.6) and are left alone. */
 constexpr int RPT_SHADE_WAVES_PLAIN = 8;
 constexpr int RPT_SHADE_WAVES_PACKED = 5;
-/* The kernel: one text (k_shade_body.h) compiled here as k_shade, in rpt_models.hip as k_shade_models and in rpt_volumes.hip as k_shade_volumes */
+/* The kernel: one text (k_shade_body.h) compiled here as k_shade, in rpt_models.hip as k_shade_models, in rpt_volumes.hip as k_shade_volumes and in
+ * rpt_punctual.hip as k_shade_punctual */
 #define RPT_SHADE_KERNEL k_shade
 #define RPT_SHADE_MODELS false
 #define RPT_SHADE_MODELS_ARG(...)
 #define RPT_SHADE_VOLUMES false
 #define RPT_SHADE_VOLUMES_ARG(...)
+#define RPT_SHADE_PUNCTUAL false
+#define RPT_SHADE_PUNCTUAL_ARG(...)
 #define RPT_SHADE_OCCUPANCY __attribute__((amdgpu_waves_per_eu((NEE == RPT_NEE_NONE && !TEXTURED) ? (COMPACT ? RPT_SHADE_WAVES_PACKED : RPT_SHADE_WAVES_PLAIN) : 1, 8)))
 #include "k_shade_body.h"
 #undef RPT_SHADE_KERNEL
@@ -704,6 +806,8 @@ constexpr int RPT_SHADE_WAVES_PACKED = 5;
 #undef RPT_SHADE_MODELS_ARG
 #undef RPT_SHADE_VOLUMES
 #undef RPT_SHADE_VOLUMES_ARG
+#undef RPT_SHADE_PUNCTUAL
+#undef RPT_SHADE_PUNCTUAL_ARG
 #undef RPT_SHADE_OCCUPANCY
 
 #endif /* RPT_K_SHADE_H */

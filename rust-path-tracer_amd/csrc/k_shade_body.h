@@ -1,13 +1,16 @@
 /*
  * k_shade_body.h — the text of the surface stage's kernel (k_shade.h describes it), compiled once per kernel that shares it, as k_complete_body.h is:
  * k_shade (k_shade.h), k_shade_models (rpt_models.hip) for a context whose materials carry models (rpt_set_material_models), and k_shade_volumes
- * (rpt_volumes.hip) for one whose Glass materials absorb (rpt_set_material_volumes).  The includer defines
+ * (rpt_volumes.hip) for one whose Glass materials absorb (rpt_set_material_volumes), and k_shade_punctual (rpt_punctual.hip) for one that has punctual lights
+ * (rpt_set_punctual_lights).  The includer defines
  *   RPT_SHADE_KERNEL          the kernel's name
  *   RPT_SHADE_MODELS          shade_slot's MODELS: false / true
  *   RPT_SHADE_MODELS_ARG(...) its argument in the models build — the records, a kernel argument of their own and not a field of DevScene, which every stage
  *                             kernel takes — and nothing in the plain one, so k_shade is compiled from the text it always had
  *   RPT_SHADE_VOLUMES         shade_slot's VOLUMES: false / true (true only with MODELS)
  *   RPT_SHADE_VOLUMES_ARG(...) its argument in the volumes build, the volume records, in the same way
+ *   RPT_SHADE_PUNCTUAL        shade_slot's PUNCTUAL: false / true (true only with MODELS and VOLUMES)
+ *   RPT_SHADE_PUNCTUAL_ARG(...) its argument in the punctual build, the lights with their count and share (k_punctual.h DevPunctual), in the same way
  *   RPT_SHADE_OCCUPANCY       the waves per SIMD asked of the compiler (k_shade.h RPT_SHADE_WAVES_*), or nothing
  * (A function template over MODELS that both kernels call was tried first: inlined, it did not give k_shade the instruction stream it had.)
  */
@@ -16,7 +19,8 @@ RPT_SHADE_OCCUPANCY
 __global__ __launch_bounds__(RPT_BLOCK) void RPT_SHADE_KERNEL(DevScene sc, DevState st, DevQueues q, DevConfig cfg, uint32_t iteration,
                                                               DevStats *stats, uint32_t n_samples /* of this render call */
                                                               RPT_SHADE_MODELS_ARG(, const uint4 *models /* one record per material, or null: every material PBR */)
-                                                              RPT_SHADE_VOLUMES_ARG(, const float4 *volumes /* one record per material, or null: no material absorbs */)) {
+                                                              RPT_SHADE_VOLUMES_ARG(, const float4 *volumes /* one record per material, or null: no material absorbs */)
+                                                              RPT_SHADE_PUNCTUAL_ARG(, DevPunctual pl /* the punctual lights, or n == 0 */)) {
     const bool first_paths = iteration == 0u;                  /* every traversed slot holds the first path of its call (k_path.h) */
     /* a batch of known length: iteration i shades bounce i of every path, so its last iteration is every path's last bounce (not the first one: a first
        path has no radiance record yet) */
@@ -68,7 +72,7 @@ __global__ __launch_bounds__(RPT_BLOCK) void RPT_SHADE_KERNEL(DevScene sc, DevSt
             const float2 hw = a_hit ? st.hit[slot] : make_float2(0.0f, __uint_as_float(a_miss ? HIT_MISS : HIT_PARKED));
             bool to_sky = false, emit_shadow = false, elided = false;
             float4 sh_o = make_float4(0, 0, 0, 0), sh_d = sh_o, sh_c = sh_o;
-            shade_slot<NEE, TEXTURED, true, RPT_SHADE_MODELS, RPT_SHADE_VOLUMES>(sc, st, q, cfg, stats, slot, hw, active, to_sky, emit_shadow, sh_o, sh_d, sh_c, first_paths, n_samples, elided, last_iteration RPT_SHADE_MODELS_ARG(, models) RPT_SHADE_VOLUMES_ARG(, volumes));
+            shade_slot<NEE, TEXTURED, true, RPT_SHADE_MODELS, RPT_SHADE_VOLUMES, RPT_SHADE_PUNCTUAL>(sc, st, q, cfg, stats, slot, hw, active, to_sky, emit_shadow, sh_o, sh_d, sh_c, first_paths, n_samples, elided, last_iteration RPT_SHADE_MODELS_ARG(, models) RPT_SHADE_VOLUMES_ARG(, volumes) RPT_SHADE_PUNCTUAL_ARG(, pl.lights, pl.n, pl.q));
             if (NEE != RPT_NEE_NONE) count_elided(&n_elided, elided);
             shade_emit<NEE>(q, push_scratch, slot, to_sky, emit_shadow, sh_o, sh_d, sh_c);
         }
@@ -80,7 +84,7 @@ __global__ __launch_bounds__(RPT_BLOCK) void RPT_SHADE_KERNEL(DevScene sc, DevSt
         const bool active = hit_tri < HIT_IDLE || hit_tri == HIT_MISS;        /* traversed in this iteration */
         bool to_sky = false, emit_shadow = false, elided = false;
         float4 sh_o = make_float4(0, 0, 0, 0), sh_d = sh_o, sh_c = sh_o;
-        shade_slot<NEE, TEXTURED, false, RPT_SHADE_MODELS, RPT_SHADE_VOLUMES>(sc, st, q, cfg, stats, slot, hw, active, to_sky, emit_shadow, sh_o, sh_d, sh_c, first_paths, n_samples, elided, last_iteration RPT_SHADE_MODELS_ARG(, models) RPT_SHADE_VOLUMES_ARG(, volumes));
+        shade_slot<NEE, TEXTURED, false, RPT_SHADE_MODELS, RPT_SHADE_VOLUMES, RPT_SHADE_PUNCTUAL>(sc, st, q, cfg, stats, slot, hw, active, to_sky, emit_shadow, sh_o, sh_d, sh_c, first_paths, n_samples, elided, last_iteration RPT_SHADE_MODELS_ARG(, models) RPT_SHADE_VOLUMES_ARG(, volumes) RPT_SHADE_PUNCTUAL_ARG(, pl.lights, pl.n, pl.q));
         if (NEE != RPT_NEE_NONE) count_elided(&n_elided, elided);
         shade_emit<NEE>(q, push_scratch, slot, to_sky, emit_shadow, sh_o, sh_d, sh_c);
     }

@@ -852,6 +852,16 @@ int rpt_multi_set_material_volumes(rpt_multi *m, const rpt_material_volume *volu
     return RPT_OK;
 }
 
+/* rpt_set_punctual_lights on every rank (the records are checked before anything changes: a refusal on rank 0 means no rank was changed) */
+int rpt_multi_set_punctual_lights(rpt_multi *m, const rpt_punctual_light *lights, size_t n, float pick_share) {
+    if (!m) return RPT_EINVAL;
+    for (rpt_ctx *c : m->ctx) {
+        int rc = rpt_set_punctual_lights(c, lights, n, pick_share);
+        if (rc) return multi_fail(m, c, rc);
+    }
+    return RPT_OK;
+}
+
 /* rpt_set_camera_lens on every rank (the record is checked before anything changes: a refusal on rank 0 means no rank was changed) */
 int rpt_multi_set_camera_lens(rpt_multi *m, const rpt_camera_lens *lens) {
     if (!m) return RPT_EINVAL;

@@ -269,7 +269,13 @@ struct rpt_ctx {
     std::vector<rpt_material_volume> material_volumes_host;
     bool volumes_in_use = false;               /* some Glass record has a volume record with a non-zero sigma: the shade stage is k_shade_volumes */
     bool force_volume_kernels = false;         /* rpt_debug_force_volume_kernels: k_shade_volumes whatever the records say */
-    uint32_t last_shade_variant = 0;           /* rpt_debug_last_shade_variant: 0 k_shade, 1 k_shade_models, 2 k_shade_volumes — what the last shade launch was */
+    uint32_t last_shade_variant = 0;           /* rpt_debug_last_shade_variant: 0 k_shade, 1 k_shade_models, 2 k_shade_volumes, 3 k_shade_punctual — what the last shade launch was */
+    /* rpt_set_punctual_lights (rpt_punctual.hip): four float4 per light (k_punctual.h), handed to k_shade_punctual as one more argument of its own, their host
+     * records for rpt_punctual_lights, and the effective share of the first light draw: 0 with no lights, 1 over a scene without emissive triangles, else as set */
+    DevBuf<float4> punctual_lights;
+    std::vector<rpt_punctual_light> punctual_lights_host;
+    float punctual_share = 0.0f;
+    bool force_punctual_kernels = false;       /* rpt_debug_force_punctual_kernels: k_shade_punctual under NEE whatever the lights say (none: the parent's arithmetic) */
     /* rpt_set_camera_lens (rpt_lens.hip, k_lens.h): handed to the lens kernels as an argument of its own — DevConfig is what it was.  Active (anything but
      * {1, 0, *}): render calls open with k_generate_lens, complete with the lens builds of the completion kernels and keep at least two slots per pixel busy */
     rpt_camera_lens lens{1.0f, 0.0f, 1.0f, 0u};
@@ -352,6 +358,12 @@ void rpt_material_models_clear(rpt_ctx *c);
 void rpt_launch_shade_volumes(rpt_ctx *c, uint32_t iteration, uint32_t blocks);
 void rpt_material_volumes_clear(rpt_ctx *c);
 void rpt_material_volumes_recount(rpt_ctx *c);
+/* rpt_punctual.hip: the same stage as k_shade_punctual (NEE modes 1 and 2 only); "no lights", for rpt_upload_scene */
+void rpt_launch_shade_punctual(rpt_ctx *c, uint32_t iteration, uint32_t blocks);
+void rpt_punctual_lights_clear(rpt_ctx *c);
+/* what rpt_set_punctual_lights refuses without looking at a context (the message as the setter gives it), and the device records of k_punctual.h */
+int rpt_punctual_lights_check(const rpt_punctual_light *lights, size_t n, float pick_share, bool mesh_lights, std::string &error);
+std::vector<float4> rpt_punctual_records(const rpt_punctual_light *lights, size_t n);
 /* rpt_lens.hip: the lens is anything but the reference's camera; its primary rays leave different origins (aperture > 0: iteration 0 is the plain walk) */
 inline bool rpt_lens_active(const rpt_ctx *c) { return !(c->lens.tan_half_fov == 1.0f && c->lens.aperture_radius == 0.0f); }
 inline bool rpt_lens_scatters_origins(const rpt_ctx *c) { return c->lens.aperture_radius > 0.0f; }

@@ -226,6 +226,58 @@ int rpt_debug_volume_transmit(rpt_ctx *c, int on_device, const float *thr, const
     return RPT_OK;
 }
 
+/* the records a hook may sample: what the setter accepts, with any share in (0, 1] */
+static bool punctual_hook_refuses(const rpt_punctual_light *lights, size_t n_lights, float q) {
+    std::string error;
+    return !lights || n_lights == 0 || !(q > 0.0f && q <= 1.0f) || rpt_punctual_lights_check(lights, n_lights, 0.5f, false, error) != RPT_OK;
+}
+
+RPT_HD void punctual_item(const float4 *lights, uint32_t n_lights, float q, const float *hits, const float *l1, size_t i, uint32_t *j_out, float *dirs, float *max_t,
+                          float *e_out, float *pick_pdf) {
+    const PunctualSample o = punctual_sample(f3(hits[3 * i], hits[3 * i + 1], hits[3 * i + 2]), l1[i], lights, n_lights, q);
+    j_out[i] = o.j;
+    dirs[3 * i] = o.L.x; dirs[3 * i + 1] = o.L.y; dirs[3 * i + 2] = o.L.z;
+    max_t[i] = o.max_t;
+    e_out[3 * i] = o.E.x; e_out[3 * i + 1] = o.E.y; e_out[3 * i + 2] = o.E.z;
+    pick_pdf[i] = o.pick_pdf;
+}
+
+__global__ void k_debug_punctual_sample(const float4 *lights, uint32_t n_lights, float q, const float *hits, const float *l1, size_t n, uint32_t *j_out, float *dirs,
+                                        float *max_t, float *e_out, float *pick_pdf) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    punctual_item(lights, n_lights, q, hits, l1, i, j_out, dirs, max_t, e_out, pick_pdf);
+}
+
+int rpt_debug_punctual_sample_host(const rpt_punctual_light *lights, size_t n_lights, float q, const float *hits, const float *l1, size_t n, uint32_t *j_out,
+                                   float *dirs, float *max_t, float *e_out, float *pick_pdf) {
+    if (punctual_hook_refuses(lights, n_lights, q) || !hits || !l1 || !j_out || !dirs || !max_t || !e_out || !pick_pdf) return RPT_EINVAL;
+    const std::vector<float4> rec = rpt_punctual_records(lights, n_lights);
+    for (size_t i = 0; i < n; ++i) punctual_item(rec.data(), (uint32_t)n_lights, q, hits, l1, i, j_out, dirs, max_t, e_out, pick_pdf);
+    return RPT_OK;
+}
+
+int rpt_debug_punctual_sample(rpt_ctx *c, const rpt_punctual_light *lights, size_t n_lights, float q, const float *hits, const float *l1, size_t n, uint32_t *j_out,
+                              float *dirs, float *max_t, float *e_out, float *pick_pdf) {
+    if (!c || punctual_hook_refuses(lights, n_lights, q) || !hits || !l1 || !j_out || !dirs || !max_t || !e_out || !pick_pdf) return RPT_EINVAL;
+    if (n == 0) return RPT_OK;
+    const std::vector<float4> rec = rpt_punctual_records(lights, n_lights);
+    HIP_TRY(c, hipSetDevice(c->device));
+    DevBuf<float4> drec;
+    DevBuf<float> dhits, dl1, ddirs, dmax_t, de, dpdf;
+    DevBuf<uint32_t> dj;
+    HIP_TRY(c, drec.from_host(rec.data(), rec.size())); HIP_TRY(c, dhits.from_host(hits, 3 * n)); HIP_TRY(c, dl1.from_host(l1, n));
+    HIP_TRY(c, dj.alloc(n)); HIP_TRY(c, ddirs.alloc(3 * n)); HIP_TRY(c, dmax_t.alloc(n)); HIP_TRY(c, de.alloc(3 * n)); HIP_TRY(c, dpdf.alloc(n));
+    k_debug_punctual_sample<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(drec.p, (uint32_t)n_lights, q, dhits.p, dl1.p, n, dj.p, ddirs.p, dmax_t.p, de.p, dpdf.p);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(j_out, dj.p, 4 * n, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(dirs, ddirs.p, 12 * n, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(max_t, dmax_t.p, 4 * n, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(e_out, de.p, 12 * n, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(pick_pdf, dpdf.p, 4 * n, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+
 int rpt_debug_sample_image(rpt_ctx *c, int is_u8, const void *texels, uint32_t width, uint32_t height, size_t n, const float *coords_uv, float *out_rgba) {
     if (!c || !texels || !coords_uv || !out_rgba || width == 0u || height == 0u) return RPT_EINVAL;
     /* the limits of rpt_upload_scene: texel indices are 32-bit in sample_by_lod */

@@ -196,7 +196,9 @@ uint32_t launch_iteration(rpt_ctx *c, uint32_t iteration, uint32_t blocks, bool 
     t.mark(s, RPT_STAGE_TRAVERSE, StageTimer::AT_1 | StageTimer::AT_2);
     if (!ended) {                                           /* (ended: nothing is left for a shade stage, every path of the launch is HIT_DONE or waits in the sky queue) */
         c->last_shade_variant = (c->volumes_in_use || c->force_volume_kernels) ? 2u : ((c->models_in_use || c->force_model_kernels) ? 1u : 0u);
-        if (c->last_shade_variant == 2u) rpt_launch_shade_volumes(c, iteration, blocks);                   /* (rpt_set_material_volumes: some Glass material absorbs) */
+        if (NEE != RPT_NEE_NONE && (!c->punctual_lights_host.empty() || c->force_punctual_kernels)) c->last_shade_variant = 3u;
+        if (c->last_shade_variant == 3u) rpt_launch_shade_punctual(c, iteration, blocks);                  /* (rpt_set_punctual_lights: NEE has punctual lights to pick) */
+        else if (c->last_shade_variant == 2u) rpt_launch_shade_volumes(c, iteration, blocks);                   /* (rpt_set_material_volumes: some Glass material absorbs) */
         else if (c->last_shade_variant == 1u) rpt_launch_shade_models(c, iteration, blocks);               /* (rpt_set_material_models: some material is not PBR) */
         else if (c->shade_compact) k_shade<NEE, TEXTURED, true><<<(c->n_slots + RPT_BLOCK * RPT_SHADE_ROUNDS - 1) / (RPT_BLOCK * RPT_SHADE_ROUNDS), RPT_BLOCK, 0, s>>>(c->scene, c->state, c->queues, c->cfg, iteration, c->dev_stats.p, c->call_samples);
         else k_shade<NEE, TEXTURED, false><<<blocks, RPT_BLOCK, 0, s>>>(c->scene, c->state, c->queues, c->cfg, iteration, c->dev_stats.p, c->call_samples);

@@ -20,6 +20,8 @@ static_assert(RPT_MODEL_LAMBERTIAN == RPT_DEV_MODEL_LAMBERTIAN && RPT_MODEL_GLAS
 #define RPT_SHADE_MODELS_ARG(...) __VA_ARGS__
 #define RPT_SHADE_VOLUMES false
 #define RPT_SHADE_VOLUMES_ARG(...)
+#define RPT_SHADE_PUNCTUAL false
+#define RPT_SHADE_PUNCTUAL_ARG(...)
 #define RPT_SHADE_OCCUPANCY
 #include "k_shade_body.h"
 #undef RPT_SHADE_KERNEL
@@ -27,6 +29,8 @@ static_assert(RPT_MODEL_LAMBERTIAN == RPT_DEV_MODEL_LAMBERTIAN && RPT_MODEL_GLAS
 #undef RPT_SHADE_MODELS_ARG
 #undef RPT_SHADE_VOLUMES
 #undef RPT_SHADE_VOLUMES_ARG
+#undef RPT_SHADE_PUNCTUAL
+#undef RPT_SHADE_PUNCTUAL_ARG
 #undef RPT_SHADE_OCCUPANCY
 
 template <int NEE, bool TEXTURED>

@@ -692,6 +692,7 @@ int rpt_upload_scene(rpt_ctx *c, const rpt_per_vertex_data *pv, size_t nv, const
     c->n_materials = (uint32_t)nm;
     rpt_material_models_clear(c);        /* the records belong to the materials of the scene that was */
     rpt_material_volumes_clear(c);
+    rpt_punctual_lights_clear(c);
     c->dn.guides_valid = false;          /* the denoiser's guides are first hits in THIS scene */
     c->dn.scene_changed = true;          /* ... and so is the history of rpt_denoise_temporal: its next call drops it */
     return RPT_OK;

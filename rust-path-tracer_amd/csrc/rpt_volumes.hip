@@ -20,6 +20,8 @@ static_assert(sizeof(rpt_material_volume) == sizeof(float4), "the kernels read a
 #define RPT_SHADE_MODELS_ARG(...) __VA_ARGS__
 #define RPT_SHADE_VOLUMES true
 #define RPT_SHADE_VOLUMES_ARG(...) __VA_ARGS__
+#define RPT_SHADE_PUNCTUAL false
+#define RPT_SHADE_PUNCTUAL_ARG(...)
 #define RPT_SHADE_OCCUPANCY
 #include "k_shade_body.h"
 #undef RPT_SHADE_KERNEL
@@ -27,6 +29,8 @@ static_assert(sizeof(rpt_material_volume) == sizeof(float4), "the kernels read a
 #undef RPT_SHADE_MODELS_ARG
 #undef RPT_SHADE_VOLUMES
 #undef RPT_SHADE_VOLUMES_ARG
+#undef RPT_SHADE_PUNCTUAL
+#undef RPT_SHADE_PUNCTUAL_ARG
 #undef RPT_SHADE_OCCUPANCY
 
 template <int NEE, bool TEXTURED>

@@ -11,7 +11,7 @@ import os
 import numpy as np
 
 from . import _ffi
-from ._ffi import MATERIAL_MODEL_DTYPE, MATERIAL_VOLUME_DTYPE, RNG_DTYPE, Stats, TracingConfig, ptr
+from ._ffi import MATERIAL_MODEL_DTYPE, MATERIAL_VOLUME_DTYPE, PUNCTUAL_LIGHT_DTYPE, RNG_DTYPE, Stats, TracingConfig, ptr
 
 _lib = None
 
@@ -47,6 +47,49 @@ def absorption(color, distance):
         sigma = -np.log(color) / float(distance)
     fmax = float(np.finfo(np.float32).max)
     return np.where(color == 0.0, fmax, np.minimum(sigma, fmax)).astype(np.float32) + np.float32(0.0)      # (+ 0: -0.0 of a channel of 1 becomes +0.0)
+
+
+LIGHT_POINT, LIGHT_SPOT, LIGHT_DIRECTIONAL = 0, 1, 2      # rpt_set_punctual_lights
+
+
+def _light(kind, position=(0.0, 0.0, 0.0), direction=None, intensity=(1.0, 1.0, 1.0), scale=0.0, offset=0.0):
+    rec = np.zeros(1, PUNCTUAL_LIGHT_DTYPE)
+    rec["type"] = kind
+    rec["position"] = np.asarray(position, np.float64)
+    if direction is not None:
+        d = np.asarray(direction, np.float64)
+        length = float(np.sqrt(np.sum(d * d)))
+        if not (np.isfinite(length) and length > 0):
+            raise ValueError("a light's direction must be finite and not zero")
+        rec["direction"] = d / length               # normalised in float64, rounded once
+    rec["intensity"] = np.broadcast_to(np.asarray(intensity, np.float64), (3,))
+    rec["angle_scale"], rec["angle_offset"] = scale, offset
+    return rec
+
+
+def point_light(position, intensity):
+    """one record for set_punctual_lights: a point light of radiant intensity (r, g, b) per steradian (a scalar: white)"""
+    return _light(LIGHT_POINT, position, None, intensity)
+
+
+def spot_light(position, direction, intensity, inner_deg, outer_deg):
+    """one record for set_punctual_lights: a spot light shining along `direction` (normalised here), full inside the inner cone angle, nothing outside the
+    outer one, glTF's smooth step between: angle_scale = 1 / max(0.001, cos inner - cos outer), angle_offset = -cos outer * angle_scale (float64, rounded once)"""
+    ci, co = np.cos(np.radians(float(inner_deg))), np.cos(np.radians(float(outer_deg)))
+    scale = 1.0 / max(0.001, ci - co)
+    return _light(LIGHT_SPOT, position, direction, intensity, scale, -co * scale)
+
+
+def directional_light(direction, irradiance):
+    """one record for set_punctual_lights: a directional light shining along `direction` (normalised here) with irradiance (r, g, b) on a surface facing it"""
+    return _light(LIGHT_DIRECTIONAL, (0.0, 0.0, 0.0), direction, irradiance)
+
+
+def punctual_lights(*records):
+    """the records of point_light / spot_light / directional_light (or arrays of PUNCTUAL_LIGHT_DTYPE) joined into one array"""
+    if not records:
+        return np.zeros(0, PUNCTUAL_LIGHT_DTYPE)
+    return np.concatenate([np.ascontiguousarray(r, PUNCTUAL_LIGHT_DTYPE).reshape(-1) for r in records])
 
 
 class CameraLens(C.Structure):
@@ -282,6 +325,9 @@ PROTOTYPES = {
     "rpt_set_material_volumes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "rpt_material_volumes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _OUT_SIZE]),
     "rpt_multi_set_material_volumes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rpt_set_punctual_lights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float]),
+    "rpt_punctual_lights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _OUT_SIZE, C.c_void_p]),
+    "rpt_multi_set_punctual_lights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float]),
     "rpt_camera_lens_default": (None, [C.c_void_p]),
     "rpt_set_camera_lens": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rpt_camera_lens_get": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -357,6 +403,10 @@ PROTOTYPES = {
     "rpt_debug_volume_transmit": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rpt_debug_lens_rays_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "rpt_debug_lens_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "rpt_debug_force_punctual_kernels": (C.c_int, [C.c_void_p, C.c_int]),
+    "rpt_debug_punctual_lights_check": (C.c_int, [C.c_void_p, C.c_size_t, C.c_float, C.c_int, C.c_void_p, C.c_size_t]),
+    "rpt_debug_punctual_sample_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 5),
+    "rpt_debug_punctual_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 5),
 }
 EXPORTS = sorted(PROTOTYPES)
 
@@ -508,6 +558,17 @@ class _Handle:
             return
         records = np.ascontiguousarray(records, MATERIAL_VOLUME_DTYPE)
         self._call("set_material_volumes", ptr(records), len(records))
+
+    def set_punctual_lights(self, lights=None, pick_share=0.5):
+        """rpt_set_punctual_lights (rpt_multi_: on every rank): point, spot and directional lights (punctual_lights(point_light(..), spot_light(..), ..), or an
+        array of PUNCTUAL_LIGHT_DTYPE) sampled by next-event estimation — NEE modes 1 and 2 only; pick_share: the share of light picks they take from the
+        scene's emissive triangles, in (0, 1) (ignored, 1, where the scene has none).  None or empty: no lights.  Between batches; the caller resets the
+        accumulator; upload_scene clears the lights."""
+        if lights is None or len(lights) == 0:
+            self._call("set_punctual_lights", None, 0, float(pick_share))
+            return
+        lights = np.ascontiguousarray(lights, PUNCTUAL_LIGHT_DTYPE).reshape(-1)
+        self._call("set_punctual_lights", ptr(lights), len(lights), float(pick_share))
 
     def set_camera_lens(self, lens=None, **fields):
         """rpt_set_camera_lens (rpt_multi_: on every rank): a CameraLens, or its fields by name (tan_half_fov — see hip.tan_half_fov(degrees) —, aperture_radius,
@@ -777,6 +838,22 @@ class Renderer(_Handle):
         self._check(lib().rpt_material_volumes(self._h, ptr(out), len(out), C.byref(n)))
         return out
 
+    def punctual_lights(self):
+        """rpt_punctual_lights: (the records as set, an array of PUNCTUAL_LIGHT_DTYPE — empty: none —, the effective share of the first light draw)"""
+        n, q = C.c_size_t(), C.c_float()
+        self._check(lib().rpt_punctual_lights(self._h, None, 0, C.byref(n), C.byref(q)))
+        out = np.zeros(n.value, PUNCTUAL_LIGHT_DTYPE)
+        self._check(lib().rpt_punctual_lights(self._h, ptr(out), len(out), C.byref(n), C.byref(q)))
+        return out, q.value
+
+    def debug_force_punctual_kernels(self, on=True):
+        """rpt_debug_force_punctual_kernels (test hook): the punctual variant of the shade stage under NEE whatever the lights say"""
+        self._check(lib().rpt_debug_force_punctual_kernels(self._h, 1 if on else 0))
+
+    def debug_punctual_sample(self, lights, q, hits, l1):
+        """rpt_debug_punctual_sample on the device (test hook): punctual_sample of csrc/k_punctual.h -> (j, L, max_t, E, pick_pdf)"""
+        return _punctual_sample(self._h, lights, q, hits, l1)
+
     def camera_lens(self):
         """rpt_camera_lens_get: the lens as set (a CameraLens)"""
         out = CameraLens()
@@ -799,7 +876,7 @@ class Renderer(_Handle):
         self._check(lib().rpt_debug_force_volume_kernels(self._h, 1 if on else 0))
 
     def debug_last_shade_variant(self):
-        """rpt_debug_last_shade_variant (test hook): 0 k_shade, 1 k_shade_models, 2 k_shade_volumes — the context's last shade launch"""
+        """rpt_debug_last_shade_variant (test hook): 0 k_shade, 1 k_shade_models, 2 k_shade_volumes, 3 k_shade_punctual — the context's last shade launch"""
         v = C.c_uint32()
         self._check(lib().rpt_debug_last_shade_variant(self._h, C.byref(v)))
         return v.value
@@ -1120,6 +1197,37 @@ def debug_math_host(op, x, y=None):
     if rc != 0:
         raise RptError(rc, "rpt_debug_math_host")
     return out
+
+
+def _punctual_sample(handle, lights, q, hits, l1):
+    lights = np.ascontiguousarray(lights, PUNCTUAL_LIGHT_DTYPE).reshape(-1)
+    hits, l1 = np.ascontiguousarray(hits, np.float32).reshape(-1, 3), np.ascontiguousarray(l1, np.float32).reshape(-1)
+    if len(hits) != len(l1):
+        raise ValueError("debug_punctual_sample: one hit and one l1 per item")
+    n = len(l1)
+    j, L, max_t, E, pdf = np.zeros(n, np.uint32), np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.float32)
+    if handle is None:
+        rc = lib().rpt_debug_punctual_sample_host(ptr(lights), len(lights), float(q), ptr(hits), ptr(l1), n, ptr(j), ptr(L), ptr(max_t), ptr(E), ptr(pdf))
+    else:
+        rc = lib().rpt_debug_punctual_sample(handle, ptr(lights), len(lights), float(q), ptr(hits), ptr(l1), n, ptr(j), ptr(L), ptr(max_t), ptr(E), ptr(pdf))
+    if rc != 0:
+        raise RptError(rc, "rpt_debug_punctual_sample")
+    return j, L, max_t, E, pdf
+
+
+def debug_punctual_lights_check(lights, pick_share=0.5, scene_has_emitters=True):
+    """rpt_debug_punctual_lights_check (no GPU needed): what rpt_set_punctual_lights would say to these records and this share over a scene with or without
+    emissive triangles -> (code, message); lights None: (NULL, 0)"""
+    if lights is not None:
+        lights = np.ascontiguousarray(lights, PUNCTUAL_LIGHT_DTYPE).reshape(-1)
+    msg = C.create_string_buffer(512)
+    rc = lib().rpt_debug_punctual_lights_check(ptr(lights), 0 if lights is None else len(lights), float(pick_share), 1 if scene_has_emitters else 0, msg, len(msg))
+    return rc, msg.value.decode()
+
+
+def debug_punctual_sample_host(lights, q, hits, l1):
+    """The host build of csrc/k_punctual.h punctual_sample inside librpt_hip.so (no GPU needed) -> (j, L, max_t, E, pick_pdf)"""
+    return _punctual_sample(None, lights, q, hits, l1)
 
 
 def _volume_transmit(handle, on_device, throughput, sigma, t):

@@ -12,7 +12,7 @@ import os
 import numpy as np
 
 from . import _ffi
-from ._ffi import (BVH_NODE_DTYPE, LIGHT_PICK_DTYPE, MATERIAL_DTYPE, MATERIAL_MODEL_DTYPE, MATERIAL_VOLUME_DTYPE, PER_VERTEX_DTYPE, RNG_DTYPE, TRIANGLE_DTYPE,
+from ._ffi import (BVH_NODE_DTYPE, LIGHT_PICK_DTYPE, MATERIAL_DTYPE, MATERIAL_MODEL_DTYPE, MATERIAL_VOLUME_DTYPE, PER_VERTEX_DTYPE, PUNCTUAL_LIGHT_DTYPE, RNG_DTYPE, TRIANGLE_DTYPE,
                    TracingConfig, WorldView, ptr)
 
 _lib = None
@@ -23,6 +23,7 @@ PROTOTYPES = {
     "rpt_world_load_ex": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     "rpt_world_material_models": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rpt_world_material_volumes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "rpt_world_punctual_lights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rpt_skybox_load": (C.c_int, [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rpt_host_free": (None, [C.c_void_p]),
     "rpt_world_from_buffers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
@@ -114,6 +115,8 @@ class World:
         self.material_models = np.zeros(len(self.materials), MATERIAL_MODEL_DTYPE)
         # rpt_world_material_volumes: one absorption record per material (hip.Renderer.set_material_volumes takes them); zeros unless from_path(material_volumes=True) found KHR_materials_volume
         self.material_volumes = np.zeros(len(self.materials), MATERIAL_VOLUME_DTYPE)
+        # rpt_world_punctual_lights: the lights of KHR_lights_punctual (hip.Renderer.set_punctual_lights takes them); none unless from_path(punctual_lights=True) found some
+        self.punctual_lights = np.zeros(0, PUNCTUAL_LIGHT_DTYPE)
 
     @classmethod
     def _from_handle(cls, handle):
@@ -131,18 +134,23 @@ class World:
         n = C.c_size_t()
         _check(lib().rpt_world_material_models(handle, ptr(w.material_models), len(w.material_models), C.byref(n)))
         _check(lib().rpt_world_material_volumes(handle, ptr(w.material_volumes), len(w.material_volumes), C.byref(n)))
+        _check(lib().rpt_world_punctual_lights(handle, None, 0, C.byref(n)))
+        w.punctual_lights = np.zeros(n.value, PUNCTUAL_LIGHT_DTYPE)
+        _check(lib().rpt_world_punctual_lights(handle, ptr(w.punctual_lights), len(w.punctual_lights), C.byref(n)))
         lib().rpt_world_free(handle)
         return w
 
     @classmethod
-    def from_path(cls, path, emissive_strength=False, material_models=False, material_volumes=False):
+    def from_path(cls, path, emissive_strength=False, material_models=False, material_volumes=False, punctual_lights=False):
         """World::from_path (reference: src/asset.rs:55-224).  emissive_strength=True honours
         KHR_materials_emissive_strength instead of the reference's fixed x15 (opt-in: not the reference's behaviour).
         material_models=True (RPT_LOAD_MATERIAL_MODELS): materials with KHR_materials_transmission get a Glass record in .material_models, ior from KHR_materials_ior.
         material_volumes=True (RPT_LOAD_MATERIAL_VOLUMES): materials with KHR_materials_volume (a thickness and a finite attenuation distance) get an absorption
-        record in .material_volumes, sigma = -ln(attenuationColor) / attenuationDistance."""
+        record in .material_volumes, sigma = -ln(attenuationColor) / attenuationDistance.
+        punctual_lights=True (RPT_LOAD_PUNCTUAL_LIGHTS): the lights of KHR_lights_punctual under their nodes' world transforms in .punctual_lights, intensities
+        as the file writes them (candela and lux: scaling is the caller's)."""
         h = C.c_void_p()
-        flags = (1 if emissive_strength else 0) | (2 if material_models else 0) | (4 if material_volumes else 0)
+        flags = (1 if emissive_strength else 0) | (2 if material_models else 0) | (4 if material_volumes else 0) | (8 if punctual_lights else 0)
         _check(lib().rpt_world_load_ex(os.fsencode(path), flags, C.byref(h)))
         return cls._from_handle(h)
 
