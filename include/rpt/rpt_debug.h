@@ -31,6 +31,10 @@ int rpt_debug_shadow_order_host(const rpt_per_vertex_data *vertices, size_t n_ve
                                 const rpt_bvh_node *nodes, size_t n_nodes, const rpt_material_data *materials, size_t n_materials,
                                 const rpt_light_pick_entry *light_pick, size_t n_light_pick, uint32_t *fixed_out, double *visits_near_out,
                                 double *visits_fixed_out, uint32_t *probe_rays_out, uint8_t *flip_out);
+/* The reason behind that decision, in the probe's own words ("node pool is not pair-shaped", "no lights", "no probe ray could be formed",
+ * "RPT_SHADOW_ORDER=fixed", ...): of the scene the context holds, or with ctx NULL of this thread's last rpt_debug_shadow_order_host call.  A static
+ * string, never NULL ("" for a context without a scene, and before the first host call). */
+const char *rpt_debug_shadow_order_why(rpt_ctx *ctx);
 /* The same for the order of the hit-or-miss lanes of the last extension rays (rpt_last_bounce_order): rule_out 0 near child first, 1 / 2 / 3 the fixed rules. */
 int rpt_debug_last_order_host(const rpt_per_vertex_data *vertices, size_t n_vertices, const rpt_triangle *indices, size_t n_triangles,
                               const rpt_bvh_node *nodes, size_t n_nodes, const rpt_material_data *materials, size_t n_materials,

@@ -155,7 +155,8 @@ struct SceneViewGlobal : TriRecords {
  * bytes; the 8-byte one returns half the data on the shared lines near the top of the tree), and a popped node index costs one 4-byte load from
  * `links[]` instead of two.  Pair p = the children (2p + 1, 2p + 2) of the reference's node pool (its builder allocates children in pairs after the
  * root); a scene whose pool is not pair-shaped, or with a leaf of 255+ triangles or 2^24+ triangles, keeps the one-shot generic walks.  The node
- * is one register: an inner node is its left child's index (< 2^24). */
+ * is one register: an inner node is its left child's index (< 2^24 - 1: the right child's index, which the walks push, is below 2^24 as well —
+ * rpt_scene.hip pool_is_pair_shaped; a pool with a child at 2^24 or beyond keeps the generic walks and their 32-bit entries). */
 template <bool COOP>
 struct SceneViewPairsT : TriRecords {
     static constexpr bool kCoopLeaves = COOP;                  /* leaves may hold dozens of triangles: see walk_run.  The streamed walks are

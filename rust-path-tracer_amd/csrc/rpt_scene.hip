@@ -191,7 +191,9 @@ __global__ __launch_bounds__(RPT_BLOCK) void k_node_flags(const rpt_bvh_node *no
     if (n < nn) {
         const rpt_bvh_node node = nodes[n];
         if (node.triangle_count > (uint32_t)RPT_COOP_LEAF_MIN) bits |= 1u;
-        if (node.triangle_count >= 255u || node.left_or_first >= (1u << 24) || (node.triangle_count == 0u && ((node.left_or_first & 1u) == 0u || (size_t)node.left_or_first + 1 >= nn))) bits |= 2u;
+        /* (an inner node's link names BOTH children: the right one, left_or_first + 1, has to fit the 24 bits too) */
+        const uint32_t link_end = node.triangle_count == 0u ? (1u << 24) - 1u : (1u << 24);
+        if (node.triangle_count >= 255u || node.left_or_first >= link_end || (node.triangle_count == 0u && ((node.left_or_first & 1u) == 0u || (size_t)node.left_or_first + 1 >= nn))) bits |= 2u;
         for (int k = 0; k < 3; ++k)
             if (!rptm::fastdiv_operand_ok(node.aabb_min[k]) || !rptm::fastdiv_operand_ok(node.aabb_max[k])) bits |= 4u;
     }
@@ -221,7 +223,9 @@ static int device_validate_tree(rpt_ctx *c, const rpt_bvh_node *d_nodes, size_t 
 }
 
 /* what the pair records of the streamed global-memory walks (k_walk.h SceneViewPairsT) and the flipped copies can express: children of every inner node
- * are the nodes (2p + 1, 2p + 2) of one pair — every pool the reference's builder makes (src/bvh.rs:296-320) —, leaves of fewer than 255 triangles, links in 24 bits.
+ * are the nodes (2p + 1, 2p + 2) of one pair — every pool the reference's builder makes (src/bvh.rs:296-320) —, leaves of fewer than 255 triangles, and every index a
+ * link stands for below 2^24: a leaf's first triangle, and BOTH children of an inner node (left_or_first + 1 < 2^24 — the walks push the right child's index, and a
+ * 24-entry stack keeps 24 bits of it: node 2^24 would come back as node 0, the root).
  * `every_node_fits`: no node of the pool has bit 2 of NodeFacts::flags (k_node_flags on the device, the loop below on the host) */
 static bool pool_is_pair_shaped(const rpt_bvh_node *nodes, size_t nn, bool every_node_fits) {
     return (nn & 1u) == 1u && nn >= 3 && nodes[0].triangle_count == 0u && every_node_fits;
@@ -231,7 +235,8 @@ static bool pool_is_pair_shaped(const rpt_bvh_node *nodes, size_t nn) {
     bool fits = true;
     for (size_t i = 0; i < nn && fits; ++i) {
         const rpt_bvh_node &n = nodes[i];
-        fits = n.triangle_count < 255u && n.left_or_first < (1u << 24) && (n.triangle_count != 0u || ((n.left_or_first & 1u) != 0u && (size_t)n.left_or_first + 1 < nn));
+        const uint32_t link_end = n.triangle_count == 0u ? (1u << 24) - 1u : (1u << 24);
+        fits = n.triangle_count < 255u && n.left_or_first < link_end && (n.triangle_count != 0u || ((n.left_or_first & 1u) != 0u && (size_t)n.left_or_first + 1 < nn));
     }
     return pool_is_pair_shaped(nodes, nn, fits);
 }
@@ -687,7 +692,9 @@ int rpt_upload_scene(rpt_ctx *c, const rpt_per_vertex_data *pv, size_t nv, const
     HIP_TRY(c, hipStreamSynchronize(nullptr));                 /* the derive / pair kernels ran on the null stream; the context renders on its own */
     HIP_TRY(c, hipGetLastError());
     c->bvh_depth = u.facts.max_depth;
-    c->stack_cap = c->bvh_depth <= 15 ? 16 : (c->bvh_depth <= 23 ? 24 : 32);
+    /* the 16-entry stack has 16-bit entries and nothing wider (rpt_traverse.hip with_stack_width): it takes a tree of at most 15 levels in a pool of fewer than 65 536
+     * nodes.  A sparse pool can be that shallow and still link to node 65 536 and beyond: it walks with 24 entries, whose widths follow the node count. */
+    c->stack_cap = c->bvh_depth <= 15 && nn < 65536u ? 16 : (c->bvh_depth <= 23 ? 24 : 32);
     c->has_scene = true;
     c->n_materials = (uint32_t)nm;
     rpt_material_models_clear(c);        /* the records belong to the materials of the scene that was */
@@ -732,6 +739,12 @@ static int validate_for_host_probe(const rpt_per_vertex_data *pv, size_t nv, con
     return rc;
 }
 
+/* the reason of this thread's last rpt_debug_shadow_order_host decision (a string literal of shadow_order.h) */
+static const char *&host_shadow_why() {
+    static thread_local const char *why = "";
+    return why;
+}
+
 int rpt_debug_shadow_order_host(const rpt_per_vertex_data *pv, size_t nv, const rpt_triangle *idx, size_t nt, const rpt_bvh_node *nodes, size_t nn,
                                 const rpt_material_data *mats, size_t nm, const rpt_light_pick_entry *lp, size_t nlp, uint32_t *fixed_out,
                                 double *visits_near_out, double *visits_fixed_out, uint32_t *probe_rays_out, uint8_t *flip_out /* (nn - 1) / 2, nullable */) {
@@ -744,7 +757,13 @@ int rpt_debug_shadow_order_host(const rpt_per_vertex_data *pv, size_t nv, const 
     if (visits_fixed_out) *visits_fixed_out = so.visits_fixed;
     if (probe_rays_out) *probe_rays_out = so.probe_rays;
     if (flip_out && !so.flip.empty()) memcpy(flip_out, so.flip.data(), so.flip.size());
+    host_shadow_why() = so.why;
     return RPT_OK;
+}
+
+const char *rpt_debug_shadow_order_why(rpt_ctx *c) {
+    if (!c) return host_shadow_why();
+    return c->has_scene ? c->shadow_order.why : "";
 }
 
 int rpt_debug_last_order_host(const rpt_per_vertex_data *pv, size_t nv, const rpt_triangle *idx, size_t nt, const rpt_bvh_node *nodes, size_t nn,

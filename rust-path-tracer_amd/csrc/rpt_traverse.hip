@@ -21,8 +21,10 @@ constexpr int LDS_THREADS = 1024;
 
 template <int STACK>
 static int gstream_stack_width(const rpt_ctx *c) {
-    /* a tree of at most 15 levels has fewer than 65 536 nodes, one of at most 23 fewer than 2^24: the entry widths a stack capacity can meet
-     * (RPT_STACK_BITS, a test aid, widens the entries of deep trees) */
+    /* An entry is a node index, so its width follows the POOL's size, not the tree's depth (a shallow tree may sit in a sparse pool).  The 16-entry stack is
+     * given only to pools of fewer than 65 536 nodes (rpt_scene.hip, where stack_cap is set); a pair-shaped pool links to no index from 2^24 on
+     * (pool_is_pair_shaped), so the 24 bits that the 24-entry stack stops at hold every entry whatever the node count.  RPT_STACK_BITS, a test aid, widens
+     * the entries of deep trees. */
     if (STACK == 16) return 16;
     const int bits = c->knobs.stack_bits;
     const int w = (c->scene.n_nodes < 65536u && bits <= 16) ? 16 : (c->scene.n_nodes < (1u << 21) && bits <= 21) ? 21 : (c->scene.n_nodes < (1u << 24) && bits <= 24) ? 24 : 32;

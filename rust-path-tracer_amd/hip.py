@@ -374,6 +374,7 @@ PROTOTYPES = {
     "rpt_debug_math": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "rpt_debug_math_host": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "rpt_debug_shadow_order_host": (C.c_int, [C.c_void_p, C.c_size_t] * 5 + [_OUT_U32, _OUT_F64, _OUT_F64, _OUT_U32, C.c_void_p]),
+    "rpt_debug_shadow_order_why": (C.c_char_p, [C.c_void_p]),
     "rpt_debug_last_order_host": (C.c_int, [C.c_void_p, C.c_size_t] * 4 + [_OUT_U32, _OUT_F64, _OUT_U32, C.c_void_p]),
     "rpt_debug_math_sweep": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_float, _OUT_U64, _OUT_U32]),
     "rpt_debug_rcp": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -816,11 +817,12 @@ class Renderer(_Handle):
         self._check(lib().rpt_comm_init_local(self._h))
 
     def shadow_order(self):
-        """rpt_shadow_order: {"fixed": bool, "visits_near", "visits_fixed", "probe_rays"} — which (bit-exact) order the shadow walks of the scene use."""
+        """rpt_shadow_order: {"fixed": bool, "visits_near", "visits_fixed", "probe_rays", "why": the probe's reason} — which (bit-exact) order the shadow walks of the scene use."""
         f, n = C.c_uint32(), C.c_uint32()
         vn, vf, ms = C.c_double(), C.c_double(), C.c_double()
         self._check(lib().rpt_shadow_order(self._h, C.byref(f), C.byref(vn), C.byref(vf), C.byref(n), C.byref(ms)))
-        return {"fixed": bool(f.value), "visits_near": vn.value, "visits_fixed": vf.value, "probe_rays": n.value, "probe_ms": ms.value}
+        return {"fixed": bool(f.value), "visits_near": vn.value, "visits_fixed": vf.value, "probe_rays": n.value, "probe_ms": ms.value,
+                "why": lib().rpt_debug_shadow_order_why(self._h).decode()}
 
     def material_models(self):
         """rpt_material_models: the records as set, an array of MATERIAL_MODEL_DTYPE (empty: none set)"""
@@ -1185,7 +1187,8 @@ def shadow_order_host(world):
                                            C.byref(f), C.byref(vn), C.byref(vf), C.byref(n), ptr(flip))
     if rc != 0:
         raise RptError(rc, "rpt_debug_shadow_order_host")
-    return {"fixed": bool(f.value), "visits_near": vn.value, "visits_fixed": vf.value, "probe_rays": n.value, "flip": flip}
+    return {"fixed": bool(f.value), "visits_near": vn.value, "visits_fixed": vf.value, "probe_rays": n.value, "flip": flip,
+            "why": lib().rpt_debug_shadow_order_why(None).decode()}
 
 
 def debug_math_host(op, x, y=None):

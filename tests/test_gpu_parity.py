@@ -1396,6 +1396,29 @@ def test_malformed_scene_buffers_are_rejected_not_traversed(hipmod, oracle, rpt,
     r.close()
 
 
+def test_a_tree_of_32_levels_is_refused_and_the_scene_before_it_stays(hipmod, oracle, rpt, world):
+    """A chain of 33 layers (tests/chain_pools.py: depth 32, one level more than the reference's 32-entry stack holds — the oracle reports its overflow,
+    tests/test_chain_pools.py) over a context that holds DarkCornell: RPT_ESCENE, the message names the depth, and the context still renders DarkCornell's
+    oracle image (the pool is checked before the scene in place is touched); a chain of 32 layers is taken."""
+    import chain_pools
+    base = world("DarkCornell")
+    W, H = 80, 56
+    cfg = rpt.default_config(W, H, nee=1)
+    seeds = rpt.blue_noise_seeds(W, H)
+    r = hipmod.Renderer(0)
+    try:
+        r.upload_scene(base)
+        with pytest.raises(hipmod.RptError) as e:
+            r.upload_scene(chain_pools.pool(rpt, "compact32"))
+        assert e.value.code == -5 and "deeper than the reference's 32-entry traversal stack" in str(e.value), str(e.value)
+        r.set_config(cfg); r.reset(seeds); r.render(3)
+        ref, _, _ = oracle.trace_cpu(cfg, oracle.scene(base), seeds, 3)
+        assert np.array_equal(r.read_accum()[0].view(np.uint32), ref.view(np.uint32))
+        r.upload_scene(chain_pools.pool(rpt, "compact31"))                  # 31 levels: accepted
+    finally:
+        r.close()
+
+
 def test_nan_and_infinite_inputs_follow_the_reference_too():
     """tools/nan_probe.py: NaN / infinite / zero camera, rotation, sun and lobe-clamp values, a NaN vertex, a NaN box —
     nothing hangs, and image (NaN for NaN) and ray counts equal the oracle's on the LDS walk and the global-memory walk."""
